@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR   (also writes the edges of the last timed step: see dump_outputs)
 
 One "step" = one pass of the hot path (what src/pairwise.cpp:194-237 does on the CPU) over one batch of
 synthetic sketches that already sit in HBM as sorted uint64 runs:
@@ -188,6 +189,27 @@ def edge_checksum(ev: np.ndarray) -> int:
     return int(x.sum(dtype=np.uint64))
 
 
+DUMP_BYTES = 64 << 20   # cap on what --dump-outputs writes in all
+
+
+def dump_outputs(out_dir: str, ev: np.ndarray) -> dict:
+    """--dump-outputs: the edges the last timed step handed over, one float64 array per field (DIR/source_1.npy,
+    DIR/source_2.npy, DIR/shared.npy), rows ordered by (source_1, source_2, shared) — the order in which the engine
+    emits edges follows its source order, which differs from build to build; the edge set does not.  When the edges
+    exceed DUMP_BYTES, a fixed, seeded sample of the ordered rows is written."""
+    ev = ev[np.lexsort((ev["shared"], ev["source_2"], ev["source_1"]))]
+    names = ev.dtype.names
+    cap = (DUMP_BYTES - 4096) // (8 * len(names))   # (4096: room for the .npy headers)
+    rows = np.arange(len(ev))
+    if len(ev) > cap:
+        rows = np.sort(np.random.default_rng(0).choice(len(ev), cap, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name in names:
+        np.save(os.path.join(out_dir, name + ".npy"), ev[name][rows].astype(np.float64))
+    return {"dir": out_dir, "files": [name + ".npy" for name in names], "rows": int(len(rows)),
+            "of_rows": int(len(ev)), "sampled": bool(len(rows) < len(ev))}
+
+
 def holder_pair_sum(torch, keys_d) -> int:
     """sum over distinct hashes of C(holders, 2), from a plain torch sort of the keys on the GPU — independent of the
     engine.  Every source pair shares exactly the keys both hold, so the sum of all `shared` counts must equal it
@@ -327,7 +349,11 @@ def main():
     ap.add_argument("--other-configs", default="C3,C4,C5",
                     help="full-size configs timed once each after the main measurement (N = 1 only; '' = skip)")
     ap.add_argument("--profile-steps", type=int, default=5, help="extra steps with per-phase events (N = 1; 0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the edges of the last timed step to DIR/<field>.npy (float64, rows ordered, <= 64 MB)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step (--steps >= 1)")
 
     import torch
     import torch.distributed as dist
@@ -510,6 +536,7 @@ def main():
     if rank == 0 and "last_buf" in stats:
         copy_stream.synchronize()
         final_edges = edges_hh[stats["last_buf"]][: stats["edges"]].numpy().view(engine.EDGE_DTYPE).reshape(-1).copy()
+    dumped = dump_outputs(args.dump_outputs, final_edges) if args.dump_outputs and final_edges is not None else None
 
     steps = max(1, args.steps)
     ms_step = 1e3 * elapsed / steps
@@ -621,6 +648,8 @@ def main():
                          {"build_blocks": ms_build, "of which partition": ms_part, "join": ms_join,
                           "other (gather, D2H, sync, host)": ms_step - ms_build - ms_join}),
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and args.cpu_sample > 0:
             try:
                 out["cpu_baseline"] = cpu_baseline(sk, args.cpu_sample, final_edges)

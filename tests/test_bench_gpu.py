@@ -1,11 +1,13 @@
-"""bench.py on the GPU box: the 1-rank line is well-formed, and a 2-rank run (both ranks on the one
-card, gloo for the exchange — the box has a single GPU, RCCL needs one device per rank) gathers exactly
-the edge set of the 1-rank run: tile-range sharding + gather on real engine output."""
+"""bench.py on the GPU box: the 1-rank line is well-formed, --dump-outputs writes the edge set the line's
+checksum describes, and a 2-rank run (both ranks on the one card, gloo for the exchange — the box has a single
+GPU, RCCL needs one device per rank) gathers exactly the edge set of the 1-rank run: tile-range sharding +
+gather on real engine output."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,9 +23,10 @@ def _run(cmd, env):
     return json.loads(line)
 
 
-def test_bench_line_and_two_rank_equivalence():
+def test_bench_line_and_two_rank_equivalence(tmp_path):
     common = ["--steps", "2", "--warmup", "1", "--n-sources", "1500", "--cpu-sample", "0"]
-    one = _run([sys.executable, "bench.py", "--gpus", "1"] + common, {"KSP_BENCH_CHECKSUM": "1"})
+    dump = str(tmp_path / "outputs")
+    one = _run([sys.executable, "bench.py", "--gpus", "1"] + common + ["--dump-outputs", dump], {"KSP_BENCH_CHECKSUM": "1"})
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in one
@@ -37,6 +40,15 @@ def test_bench_line_and_two_rank_equivalence():
     assert all(g["ms"] > 0 for g in r["groups"])
     assert one["naive_pairwise"]["bytes_per_step"] > r["bytes_per_step"]
     assert one["config"]["buffers_regrown_in_timed_region"] == 0
+    assert one["steps"] == 2 and one["ms_per_step"] > 0
+    # --dump-outputs: the whole edge set of the last timed step (small enough not to be sampled), rows ordered
+    assert one["dump_outputs"]["rows"] == one["config"]["nonzero_pairs"] and not one["dump_outputs"]["sampled"]
+    cols = {k: np.load(os.path.join(dump, k + ".npy")) for k in ("source_1", "source_2", "shared")}
+    assert all(c.dtype == np.float64 and len(c) == one["config"]["nonzero_pairs"] for c in cols.values())
+    assert (np.diff(cols["source_1"]) >= 0).all() and (cols["source_1"] < cols["source_2"]).all()
+    u = {k: c.astype(np.uint64) for k, c in cols.items()}
+    x = (u["source_1"] << np.uint64(40)) + (u["source_2"] << np.uint64(20)) + u["shared"]
+    assert int(x.sum(dtype=np.uint64)) == one["config"]["checksum"]
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", "29713", "bench.py", "--gpus", "2"] + common,
                {"KSP_BENCH_CHECKSUM": "1", "KSP_BENCH_SHARE_GPU": "1", "KSP_BENCH_BACKEND": "gloo"})
