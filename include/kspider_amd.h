@@ -276,11 +276,39 @@ int ksp_components(int device, uint32_t n_nodes, const uint32_t* h_a, const uint
  *   device pass: writes PREFIX_kSpider_seqToKmersNo.tsv and PREFIX_kSpider_pairwise.tsv exactly as kspider_pairwise
  *   and PREFIX_kSpider_clusters_<cutoff*100>%.tsv exactly as kspider_cluster would from that TSV — but the components
  *   come from the edges while they are in HBM (the TSV is never read back).  dist_type: "min_cont", "avg_cont",
- *   "max_cont" (NULL / ""); "ani" needs the separate ANI column file and stays with kspider_cluster.  Reads
+ *   "max_cont" (NULL / ""); "ani" is refused here: kspider_pairwise_ani_and_cluster is the ANI form.  Reads
  *   PREFIX.namesMap like kspider_cluster.                                                                          */
 int ksp_components_edges(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
                          int dist_col, double cutoff, uint32_t* h_label);
 int kspider_pairwise_and_cluster(const char* index_prefix, int user_threads, const char* dist_type, double cutoff);
+
+/* ---- ANI (`kSpider pairwise --estimate-ani`, then `kSpider cluster -d ani`) -------------------------
+ * The value of a pairwise row is what pykSpider/kSpider2/ks_pairwise.py:64-82 writes: columns 3 and 5 (min / max
+ * containment) read as Python floats from their 6-significant-digit text, each turned into sourmash's point-estimate ANI
+ *   g(c) = 0.0 if c <= 0.0001;  1.0 if c >= 0.9999;  1 - (1.0 - c ** (1.0 / k)) otherwise
+ * and the row's value (g(min) + g(max)) / 2.0, written with Python's repr.  k is the first line of PREFIX.extra
+ * (:44-46).  sourmash's scale and the k-mer counts only feed a quantity .ani discards: the scale must still be > 0 (:41)
+ * and every id of a row must be in PREFIX_kSpider_seqToKmersNo.tsv (:77-78).  A NaN containment has no ANI: an error.
+ * The formula is restated from sourmash, which is not vendored: no reference-generated output pins it.
+ * kspider_estimate_ani: `kSpider pairwise -i PREFIX --estimate-ani -s SCALE` (ks_pairwise.py:29-84) over existing files:
+ *   reads PREFIX.extra, PREFIX_kSpider_seqToKmersNo.tsv and PREFIX_kSpider_pairwise.tsv (any producer, rows in any order)
+ *   and writes PREFIX_kSpider_pairwise.ani_col.tsv ("avg_ani", then one line per row in the TSV's order) through a
+ *   .partial file; on any error nothing is written.  Host only, user_threads threads parse and format.
+ * kspider_pairwise_ani: kspider_pairwise followed by kspider_estimate_ani in one pass: the same two TSVs byte for byte,
+ *   plus the ANI column, evaluated from the rows' floats (no text is read back).
+ * kspider_pairwise_ani_and_cluster: also `kSpider cluster -d ani -c CUTOFF` (ks_clustering.py:63-137): the components
+ *   come from the edges while they are in HBM (the device evaluates the ANI of every edge, an edge counts when
+ *   ani * 100 is not below cutoff * 100) and go to PREFIX_kSpider_clusters_<cutoff*100>%.tsv as kspider_cluster
+ *   writes it.  Every kept edge counts (the reference's batch loses one edge per 10 000 001: INTEGRATION.md).
+ * ksp_edges_ani: d_ani[e] = the ANI of edge record e (all pointers DEVICE memory, as ksp_components_edges takes them);
+ *   KSP_E_ARG if any edge has a NaN containment (its d_ani is NaN).
+ * ksp_components_edges_ani: ksp_components_edges with the ANI column (ksize) as the distance.                      */
+int kspider_estimate_ani(const char* index_prefix, int user_threads, int64_t scale);
+int kspider_pairwise_ani(const char* index_prefix, int user_threads, int64_t scale);
+int kspider_pairwise_ani_and_cluster(const char* index_prefix, int user_threads, int64_t scale, double cutoff);
+int ksp_edges_ani(int device, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int ksize, double* d_ani);
+int ksp_components_edges_ani(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
+                             int ksize, double cutoff, uint32_t* h_label);
 
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
@@ -290,6 +318,14 @@ int kspider_pairwise_and_cluster(const char* index_prefix, int user_threads, con
  * (src/pairwise.cpp:266-273); buf must hold 32 bytes; returns the length.             */
 int ksp_index_info(const char* index_prefix, uint64_t out[6]);
 int ksp_format_float(float value, char* buf);
+/* ksp_ani_value: the ANI of a row whose containment floats are min_c / max_c (see above) for k-mer size ksize.
+ * via_table 0: the text definition ("%.6g" -> strtod -> libm pow); 1: the device's code path on the host (exact
+ * 6-digit decimal of each float, then the table the device reads).  KSP_E_ARG on a NaN.  ksp_ani_values: n rows at
+ * once (a NaN row gets NaN and the call returns KSP_E_ARG).  ksp_format_ani: text of a double as Python's repr()
+ * prints it (the ANI column's format); buf must hold 32 bytes; returns the length.                                */
+int ksp_ani_value(float min_c, float max_c, int ksize, int via_table, double* out);
+int ksp_ani_values(const float* min_c, const float* max_c, uint64_t n, int ksize, int via_table, double* out);
+int ksp_format_ani(double value, char* buf);
 
 #ifdef __cplusplus
 }

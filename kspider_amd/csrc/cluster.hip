@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/kspider_amd.h"
+#include "ani.h"
 #include "engine_internal.h"
 
 typedef uint32_t u32;
@@ -88,6 +89,63 @@ __global__ void k_cc_hook_edges(const ksp_edge* __restrict__ ed, u64 m, const u3
         if (atomicMin(&parent[hi], lo) > lo) *changed = 1;
     }
     if (kept && mine) atomicAdd(kept, mine);
+}
+
+// The ANI of `kSpider pairwise --estimate-ani` (ani.h) on the join's edge records: columns 3 and 5 computed as
+// cc_edge_kept computes them (the writer's single-precision maths, std::min / std::max NaN semantics), then the
+// 6-digit decimal of each and one gather per column from the table the host filled.  A NaN column has no ANI.
+__device__ inline void edge_min_max(const ksp_edge& x, const u32* __restrict__ cnt, float* mn, float* mx) {
+    const float n1 = (float)cnt[x.source_1], n2 = (float)cnt[x.source_2];
+    const float c12 = (float)x.shared / n2, c21 = (float)x.shared / n1;
+    *mn = c21 < c12 ? c21 : c12;   // std::min(c12, c21)
+    *mx = c12 < c21 ? c21 : c12;   // std::max(c12, c21)
+}
+__global__ void k_edges_ani(const ksp_edge* __restrict__ ed, u64 m, const u32* __restrict__ cnt, const double* __restrict__ table,
+                            double* __restrict__ ani, u32* __restrict__ nan_seen) {
+    for (u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += (u64)gridDim.x * blockDim.x) {
+        float mn, mx;
+        edge_min_max(ed[e], cnt, &mn, &mx);
+        double v;
+        if (!ksp::ani_of_row(mn, mx, table, &v)) { v = __builtin_nan(""); *nan_seen = 1; }
+        ani[e] = v;
+    }
+}
+// The ANI cut, evaluated once per edge rather than once per hooking round: bit e of keep[] says edge e counts, i.e.
+// float(repr(ani)) * 100 is not below cutoff * 100 (ks_clustering.py:101-105; repr round-trips, so that is the double
+// compare below, thr = cutoff * 100.0).  A wave takes 64 consecutive edges and writes their 64 bits as one word (the
+// loop bound is uniform over the wave: base is a multiple of 64, so every lane takes part in the ballot).
+__global__ void k_ani_keep(const ksp_edge* __restrict__ ed, u64 m, const u32* __restrict__ cnt, const double* __restrict__ table,
+                           const double thr, unsigned long long* __restrict__ keep, u32* __restrict__ nan_seen,
+                           unsigned long long* __restrict__ kept) {
+    const u32 lane = threadIdx.x & 63;
+    unsigned long long mine = 0;
+    for (u64 base = (u64)blockIdx.x * blockDim.x + (threadIdx.x - lane); base < m; base += (u64)gridDim.x * blockDim.x) {
+        const u64 e = base + lane;
+        bool k = false;
+        if (e < m) {
+            float mn, mx;
+            edge_min_max(ed[e], cnt, &mn, &mx);
+            double v;
+            if (!ksp::ani_of_row(mn, mx, table, &v)) *nan_seen = 1;
+            else k = !(v * 100.0 < thr);
+        }
+        const unsigned long long bits = __ballot(k);
+        if (lane == 0) keep[base >> 6] = bits;
+        mine += k ? 1 : 0;
+    }
+    if (mine) atomicAdd(kept, mine);
+}
+// k_cc_hook_edges over the edges whose bit in keep[] is set
+__global__ void k_cc_hook_kept(const ksp_edge* __restrict__ ed, u64 m, const unsigned long long* __restrict__ keep, u32* __restrict__ parent,
+                               u32* __restrict__ changed) {
+    for (u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += (u64)gridDim.x * blockDim.x) {
+        if (!((keep[e >> 6] >> (e & 63)) & 1ull)) continue;
+        const ksp_edge x = ed[e];
+        const u32 pu = parent[x.source_1], pv = parent[x.source_2];
+        if (pu == pv) continue;
+        const u32 hi = pu > pv ? pu : pv, lo = pu > pv ? pv : pu;
+        if (atomicMin(&parent[hi], lo) > lo) *changed = 1;
+    }
 }
 
 #define CL_HIP(call)                                                                     \
@@ -218,16 +276,41 @@ void cc_critical(const double cutoff, float* vcrit, int* mode) {
     std::memcpy(vcrit, &hi, 4);
 }
 
+// the ANI table of ksize (ani.h) in device memory of the current device; the caller frees *d_table
+int upload_ani_table(const int ksize, double** d_table) {
+    int rc = KSP_OK;
+    *d_table = nullptr;
+    if (ksize < 1) { set_error("ANI: k-mer size < 1"); return KSP_E_ARG; }
+    {
+        std::shared_ptr<const std::vector<double>> t;
+        try {
+            t = ani_table(ksize);
+        } catch (const std::exception&) {
+            set_error("ANI: cannot build the table on the host (out of memory?)");
+            return KSP_E_LIMIT;
+        }
+        CL_HIP(hipMalloc((void**)d_table, (size_t)kAniTableSize * sizeof(double)));
+        CL_HIP(hipMemcpy(*d_table, t->data(), (size_t)kAniTableSize * sizeof(double), hipMemcpyHostToDevice));
+    }
+    return KSP_OK;
+done:
+    if (*d_table) (void)hipFree(*d_table);
+    *d_table = nullptr;
+    return rc;
+}
+
 // connected components of the kept edges among `d_edges` (device memory, on the current device); see ksp_components_edges
 int cc_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, double cutoff,
-                       uint32_t* h_label, uint64_t* n_kept) {
+                       uint32_t* h_label, uint64_t* n_kept, int ksize) {
     int rc = KSP_OK;
-    u32 *d_parent = nullptr, *d_changed = nullptr;
+    u32 *d_parent = nullptr, *d_changed = nullptr;   // d_changed: [0] changed, [1] NaN ANI seen, [2..3] kept edges
     unsigned long long* d_kept = nullptr;
+    double* d_table = nullptr;
+    unsigned long long* d_keep = nullptr;   // ANI: one bit per edge, the cut evaluated once
     u32 h_changed = 1;
     float vcrit = 0;
     int mode = 0;
-    cc_critical(cutoff, &vcrit, &mode);
+    if (col != 6) cc_critical(cutoff, &vcrit, &mode);
     if (n_kept) *n_kept = 0;
     if (n_nodes == 0) return KSP_OK;
     CL_HIP(hipMalloc((void**)&d_parent, (size_t)n_nodes * 4));
@@ -237,14 +320,31 @@ int cc_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edg
         const unsigned gn = (n_nodes + 255) / 256;
         const unsigned ge = (unsigned)std::min<u64>((n_edges + 255) / 256, 1u << 16);
         hipLaunchKernelGGL(k_cc_init, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes);
+        if (col == 6 && n_edges) {   // the ANI cut of every edge, once: a bit per edge
+            if ((rc = upload_ani_table(ksize, &d_table))) goto done;
+            CL_HIP(hipMalloc((void**)&d_keep, (n_edges + 63) / 64 * 8));
+            CL_HIP(hipMemsetAsync(d_changed, 0, 16, nullptr));
+            hipLaunchKernelGGL(k_ani_keep, dim3((unsigned)std::min<u64>((n_edges + 255) / 256, 2048)), dim3(256), 0, nullptr, d_edges, n_edges, d_cnt,
+                               d_table, cutoff * 100.0, d_keep, d_changed + 1, d_kept);
+            CL_HIP(hipGetLastError());
+            u32 head[4] = {0, 0, 0, 0};   // [1] NaN seen, [2..3] kept edges
+            CL_HIP(hipMemcpy(head, d_changed, 16, hipMemcpyDeviceToHost));
+            if (head[1]) { set_error("components: an edge has a NaN containment (0 shared k-mers of a source with 0 k-mers): it has no ANI"); rc = KSP_E_ARG; goto done; }
+            if (n_kept) { unsigned long long k; std::memcpy(&k, head + 2, 8); *n_kept = k; }
+            (void)hipFree(d_table);
+            d_table = nullptr;
+        }
         for (int round = 0; n_edges && h_changed && round < 10000; ++round) {
             CL_HIP(hipMemsetAsync(d_changed, 0, 16, nullptr));
-            hipLaunchKernelGGL(k_cc_hook_edges, dim3(ge), dim3(256), 0, nullptr, d_edges, n_edges, d_cnt, col, vcrit, mode, d_parent, d_changed,
-                               round == 0 ? d_kept : nullptr);
+            if (col == 6)
+                hipLaunchKernelGGL(k_cc_hook_kept, dim3(ge), dim3(256), 0, nullptr, d_edges, n_edges, d_keep, d_parent, d_changed);
+            else
+                hipLaunchKernelGGL(k_cc_hook_edges, dim3(ge), dim3(256), 0, nullptr, d_edges, n_edges, d_cnt, col, vcrit, mode, d_parent, d_changed,
+                                   round == 0 ? d_kept : nullptr);
             hipLaunchKernelGGL(k_cc_jump, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes, d_changed);
             hipLaunchKernelGGL(k_cc_jump, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes, d_changed);
             CL_HIP(hipMemcpy(&h_changed, d_changed, 4, hipMemcpyDeviceToHost));
-            if (round == 0 && n_kept) { unsigned long long k = 0; CL_HIP(hipMemcpy(&k, d_kept, 8, hipMemcpyDeviceToHost)); *n_kept = k; }
+            if (round == 0 && n_kept && col != 6) { unsigned long long k = 0; CL_HIP(hipMemcpy(&k, d_kept, 8, hipMemcpyDeviceToHost)); *n_kept = k; }
         }
         if (n_edges && h_changed) { set_error("components: did not converge"); rc = KSP_E_HIP; goto done; }
         CL_HIP(hipMemcpy(h_label, d_parent, (size_t)n_nodes * 4, hipMemcpyDeviceToHost));
@@ -252,6 +352,8 @@ int cc_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edg
 done:
     if (d_parent) (void)hipFree(d_parent);
     if (d_changed) (void)hipFree(d_changed);
+    if (d_table) (void)hipFree(d_table);
+    if (d_keep) (void)hipFree(d_keep);
     return rc;
 }
 
@@ -324,6 +426,43 @@ extern "C" int ksp_components_edges(int device, uint32_t n_nodes, const ksp_edge
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { ksp::set_error("ksp_components_edges: no such device"); return KSP_E_HIP; }
     if (hipSetDevice(device) != hipSuccess) { ksp::set_error("ksp_components_edges: hipSetDevice"); return KSP_E_HIP; }
     return ksp::cc_edges_on_device(n_nodes, d_edges, n_edges, d_kmer_counts, dist_col, cutoff, h_label, nullptr);
+}
+
+extern "C" int ksp_components_edges_ani(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
+                                        int ksize, double cutoff, uint32_t* h_label) {
+    if ((n_edges && (!d_edges || !d_kmer_counts)) || (n_nodes && !h_label)) { ksp::set_error("ksp_components_edges_ani: NULL argument"); return KSP_E_ARG; }
+    if (ksize < 1) { ksp::set_error("ksp_components_edges_ani: ksize < 1"); return KSP_E_ARG; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { ksp::set_error("ksp_components_edges_ani: no such device"); return KSP_E_HIP; }
+    if (hipSetDevice(device) != hipSuccess) { ksp::set_error("ksp_components_edges_ani: hipSetDevice"); return KSP_E_HIP; }
+    return ksp::cc_edges_on_device(n_nodes, d_edges, n_edges, d_kmer_counts, 6, cutoff, h_label, nullptr, ksize);
+}
+
+extern "C" int ksp_edges_ani(int device, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int ksize, double* d_ani) {
+    if (n_edges && (!d_edges || !d_kmer_counts || !d_ani)) { ksp::set_error("ksp_edges_ani: NULL argument"); return KSP_E_ARG; }
+    if (ksize < 1) { ksp::set_error("ksp_edges_ani: ksize < 1"); return KSP_E_ARG; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { ksp::set_error("ksp_edges_ani: no such device"); return KSP_E_HIP; }
+    if (hipSetDevice(device) != hipSuccess) { ksp::set_error("ksp_edges_ani: hipSetDevice"); return KSP_E_HIP; }
+    if (n_edges == 0) return KSP_OK;
+    int rc = KSP_OK;
+    double* d_table = nullptr;
+    u32* d_nan = nullptr;
+    u32 h_nan = 0;
+    if ((rc = ksp::upload_ani_table(ksize, &d_table))) return rc;
+    CL_HIP(hipMalloc((void**)&d_nan, 4));
+    CL_HIP(hipMemsetAsync(d_nan, 0, 4, nullptr));
+    {   // a gather per edge: grid-stride over at most 8 workgroups per CU
+        const unsigned g = (unsigned)std::min<u64>((n_edges + 255) / 256, 2048);
+        hipLaunchKernelGGL(k_edges_ani, dim3(g), dim3(256), 0, nullptr, d_edges, n_edges, d_kmer_counts, d_table, d_ani, d_nan);
+        CL_HIP(hipGetLastError());
+        CL_HIP(hipMemcpy(&h_nan, d_nan, 4, hipMemcpyDeviceToHost));
+        if (h_nan) { ksp::set_error("ksp_edges_ani: an edge has a NaN containment (0 shared k-mers of a source with 0 k-mers): it has no ANI"); rc = KSP_E_ARG; }
+    }
+done:
+    if (d_table) (void)hipFree(d_table);
+    if (d_nan) (void)hipFree(d_nan);
+    return rc;
 }
 
 extern "C" int kspider_cluster(const char* index_prefix, const char* dist_type, double cutoff) {

@@ -602,7 +602,7 @@ static int stage1_lists_by_key(const Stage1<V>& c, bool& done) {
                     hipLaunchKernelGGL(k_blk_raw_groups, dim3(grid_for((u64)nb + 1, bs)), dim3(bs), 0, st, sblk, (u32)e->h_scal[1], blk_raw, nb);
                     hipLaunchKernelGGL(k_blk_pos, dim3(1), dim3(1024), 0, st, blk_raw, blk_pos, scal, nb);
                 }
-                hipLaunchKernelGGL(k_pad, dim3(nb + 1), dim3(256), 0, st, blk_raw, blk_pos, e->bkeys.as<u32>(), nb, PAD);
+                hipLaunchKernelGGL(k_pad, dim3(nb + 1), dim3(256), 0, st, blk_raw, blk_pos, e->bkeys.as<u32>(), nb, PAD, (const u64*)nullptr);
                 hipLaunchKernelGGL((k_place_groups<W>), dim3(grid_for(K, bs)), dim3(bs), 0, st, sblk, sval, blk_raw, blk_pos, wkey,
                                    e->bkeys.as<u32>(), e->info.as<u32>(), W ? e->bw.as<u32>() : nullptr, (u32)e->h_scal[1]);
             }
@@ -663,7 +663,7 @@ static int stage1_lists_by_sort(const Stage1<V>& c) {
     KSP_HIP(hipMemcpyAsync(e->h_scal + 1, scal + 1, 8, hipMemcpyDeviceToHost, st));
     hipLaunchKernelGGL((k_blk_raw<V>), dim3(grid_for((u64)nb + 1, bs)), dim3(bs), 0, st, T, estart, scal, blk_raw, nb, m);
     hipLaunchKernelGGL(k_blk_pos, dim3(1), dim3(1024), 0, st, blk_raw, blk_pos, scal, nb);
-    hipLaunchKernelGGL(k_pad, dim3(nb + 1), dim3(256), 0, st, blk_raw, blk_pos, e->bkeys.as<u32>(), nb, PAD);
+    hipLaunchKernelGGL(k_pad, dim3(nb + 1), dim3(256), 0, st, blk_raw, blk_pos, e->bkeys.as<u32>(), nb, PAD, (const u64*)nullptr);
     KSP_HIP(hipStreamSynchronize(st));
     const u64 K = std::max<u64>(1, e->h_scal[1]);
     u32* mmsz = flag;                      // (VA is free: the head flags are computed on the fly)
@@ -1218,7 +1218,7 @@ static int build_impl(ksp_engine* e, const u64* d_keys, const u32* d_w, hipStrea
                 hipLaunchKernelGGL(k_fms_scan, dim3(nb), dim3(256), 0, st, hist, mb, chunks, scal, tot, blk_raw, blk_pos, nb);
                 KSP_HIP(hipMemcpyAsync(e->h_scal, scal, 120, hipMemcpyDeviceToHost, st));   // [0] max key, [1] list words, [2] keys, [6] entries, [9] / [14] overflow (one copy)
                 KSP_HIP(hipEventRecord(e->ev_rb, st));
-                hipLaunchKernelGGL(k_pad, dim3(nb + 1), dim3(256), 0, st, blk_raw, blk_pos, e->bkeys.as<u32>(), nb, PAD);
+                hipLaunchKernelGGL(k_pad, dim3(nb + 1), dim3(256), 0, st, blk_raw, blk_pos, e->bkeys.as<u32>(), nb, PAD, scal);
                 if ((rc = e->pmask.ensure((Kcap + (u64)nb * (WIN + 4) + 4 * WIN) * 16))) return rc;
                 const size_t bit_words = (size_t)(((Tt + 63) / 64) * 2 + 2);
                 unsigned char* flags = (unsigned char*)e->tbits.p + bit_words * 4;
@@ -2224,7 +2224,8 @@ int ksp_engine_assemble(ksp_engine* e, uint32_t nparts, const uint64_t* h_sizes 
     u64* scal = e->scalars.as<u64>();
     hipLaunchKernelGGL(k_asm_counts, dim3(1), dim3(64), 0, st, d_blk_raw_all, nb + 1, nparts, nb, e->blk_raw.as<u32>());
     hipLaunchKernelGGL(k_blk_pos, dim3(1), dim3(1024), 0, st, e->blk_raw.as<u32>(), e->blk_pos.as<u32>(), scal, nb);
-    hipLaunchKernelGGL(k_pad, dim3(nb + 1), dim3(256), 0, st, e->blk_raw.as<u32>(), e->blk_pos.as<u32>(), e->bkeys.as<u32>(), nb, PAD);
+    hipLaunchKernelGGL(k_pad, dim3(nb + 1), dim3(256), 0, st, e->blk_raw.as<u32>(), e->blk_pos.as<u32>(), e->bkeys.as<u32>(), nb, PAD,
+                       (const u64*)nullptr);
     const u32* roff = e->asm_small.as<u32>();
     if (e->weighted)
         hipLaunchKernelGGL((k_asm_copy<true>), dim3(nb, nparts), dim3(256), 0, st, d_brk_all, d_info_all, d_bw_all,
@@ -3090,7 +3091,8 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
                 job.cc->labels->assign((size_t)N, 0);
                 Buf d_cnt;
                 if (N && ((rc = d_cnt.ensure((size_t)N * 4)) || (rc = ksp_memcpy_h2d(d_cnt.p, job.cc->kmer_counts, (u64)N * 4)) ||
-                          (rc = cc_edges_on_device(N, d_all, total, d_cnt.as<u32>(), job.cc->col, job.cc->cutoff, job.cc->labels->data(), &job.cc->n_kept)))) {
+                          (rc = cc_edges_on_device(N, d_all, total, d_cnt.as<u32>(), job.cc->col, job.cc->cutoff, job.cc->labels->data(), &job.cc->n_kept,
+                                                  job.cc->ksize)))) {
                     d_cnt.release();
                     fail(rc);
                     return;

@@ -243,6 +243,19 @@ struct FkOut {
 __device__ inline bool fk_abandoned(const u64* __restrict__ scal) {
     return ((u32)scal[9] | (u32)scal[PC_OVF] | reinterpret_cast<const u32*>(scal + 9)[1]) != 0;
 }
+// tail pads of every block list (+inf ranks): from the end of list b to the start of list b + 1, and 4 windows of slack
+// behind the last list (every build; defined here to see fk_abandoned).
+// scal != nullptr — the bucket-resident build: when that build was abandoned k_fms_scan wrote no block offsets, and
+// blk_raw / blk_pos hold whatever the memory held before; padding from them would write anywhere, so nothing is padded
+// (the host repeats the build pass by pass).
+__global__ void k_pad(const u32* __restrict__ blk_raw, const u32* __restrict__ blk_pos, u32* __restrict__ brk, u32 nb, u32 padv,
+                      const u64* __restrict__ scal) {
+    if (scal && fk_abandoned(scal)) return;
+    const u32 b = blockIdx.x;
+    const u32 lo = b < nb ? blk_pos[b] + (blk_raw[b + 1] - blk_raw[b]) : blk_pos[nb];
+    const u32 hi = b < nb ? blk_pos[b + 1] : blk_pos[nb] + 4u * WIN;
+    for (u32 i = lo + threadIdx.x; i < hi; i += blockDim.x) brk[i] = padv;
+}
 // (timing build, make fktime: thread 0 of every workgroup adds the shader-clock time of every stage to fk_time[stage])
 #ifdef KSP_FKTIME
 __device__ unsigned long long fk_time[16];

@@ -6,6 +6,7 @@
 //   :166-181  load k-mer counts, write seqToKmersNo.tsv
 //   :194-237  accumulate shared k-mers per pair -> MI355X engine (engine.hip)
 //   :242-275  write pairwise.tsv (float maths + formatting on the host)
+// kspider_pairwise_ani[_and_cluster] add the ANI column of `pairwise --estimate-ani` (ks_pairwise.py:29-84, ani.h).
 // The same progress lines go to stdout.
 #include <algorithm>
 #include <chrono>
@@ -20,6 +21,7 @@
 
 #include "../../include/kSpider.hpp"
 #include "../../include/kspider_amd.h"
+#include "ani.h"
 #include "engine_internal.h"
 #include "index_io.h"
 
@@ -52,11 +54,18 @@ typedef std::chrono::high_resolution_clock Clock;
 double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
 
 // dist_type != nullptr: also cluster (kSpider cluster, ks_clustering.py:63-137) from the edges while they are on the device
-int run_pairwise(const std::string& prefix, int user_threads, const char* dist_type = nullptr, double cutoff = 0) {
-    int cc_col = 0;
+// ani: also write the ANI column of `pairwise --estimate-ani` (ks_pairwise.py:29-84; k from PREFIX.extra); dist_type "ani"
+// then clusters on it
+int run_pairwise(const std::string& prefix, int user_threads, const char* dist_type = nullptr, double cutoff = 0, bool ani = false) {
+    int cc_col = 0, ksize = 0;
+    std::shared_ptr<const std::vector<double>> ani_tab;
+    if (ani) {   // before anything is read or written: the k-mer size (:44-46) and its table
+        ksize = ksp::read_extra_ksize(prefix);
+        ani_tab = ksp::ani_table(ksize);
+    }
     if (dist_type) {
         const std::string dt = *dist_type ? dist_type : "max_cont";
-        cc_col = dt == "min_cont" ? 3 : dt == "avg_cont" ? 4 : dt == "max_cont" ? 5 : 0;
+        cc_col = dt == "min_cont" ? 3 : dt == "avg_cont" ? 4 : dt == "max_cont" ? 5 : dt == "ani" && ani ? 6 : 0;
         if (!cc_col) {
             ksp::set_error("kspider_pairwise_and_cluster: distance '" + dt + "' is not min_cont, avg_cont or max_cont (ani needs the separate ANI column file: run kspider_cluster)");
             return KSP_E_ARG;
@@ -159,7 +168,7 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
             auto it = kmer_count.find(ids[i]);
             cc_counts[i] = it == kmer_count.end() ? 0u : it->second;   // (a missing group counts 0 k-mers, as operator[] of the reference yields)
         }
-        cc.kmer_counts = cc_counts.data(); cc.col = cc_col; cc.cutoff = cutoff; cc.labels = &cc_labels;
+        cc.kmer_counts = cc_counts.data(); cc.col = cc_col; cc.cutoff = cutoff; cc.labels = &cc_labels; cc.ksize = ksize;
     }
     int rc = ksp::pairwise_postings_multi_cc(key_off.data(), post_src.data(), key_w.data(), (uint32_t)key_w.size(), N,
                                              devices.data(), (int)devices.size(), &edges, &n_edges, &st, cc_col ? &cc : nullptr);
@@ -186,12 +195,29 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
             return a.source_1 != b.source_1 ? a.source_1 < b.source_1 : a.source_2 < b.source_2;
         });
     }
+    if (ani)   // a row of a weight-0 colour with a source of 0 k-mers has a NaN containment, so no ANI: fail before writing
+        for (auto& r : rows) {
+            if (r.shared) continue;
+            auto i1 = kmer_count.find(r.source_1), i2 = kmer_count.find(r.source_2);
+            float mn, mx;
+            ksp::row_min_max(0, i1 == kmer_count.end() ? 0 : i1->second, i2 == kmer_count.end() ? 0 : i2->second, &mn, &mx);
+            if (mn != mn || mx != mx) {
+                ksp::set_error("pairwise row " + std::to_string(r.source_1) + "\t" + std::to_string(r.source_2) +
+                               " has a NaN containment (0 shared k-mers of a source with 0 k-mers): it has no ANI");
+                return KSP_E_ARG;
+            }
+        }
     std::cout << "pairwise hashmap construction: " << since(t0) << " secs" << std::endl;
     if (std::getenv("KSPIDER_VERBOSE"))
         std::cout << "kspider_amd: postings from the colour index " << t_transpose << " s, device round trip " << t_device
                   << " s (stage 1 " << st.ms_build << " ms, join " << st.ms_join << " ms)" << std::endl;
     std::cout << "writing pairwise matrix to " << prefix << "_kSpider_pairwise.tsv" << std::endl;
     ksp::write_pairwise_tsv(prefix, rows, kmer_count, user_threads);
+    if (ani) {
+        t0 = Clock::now();
+        ksp::write_ani_column(prefix, rows, kmer_count, ani_tab->data(), user_threads);
+        if (std::getenv("KSPIDER_VERBOSE")) std::cout << "kspider_amd: ANI column " << since(t0) << " s" << std::endl;
+    }
     if (std::getenv("KSPIDER_VERBOSE"))
         std::cout << "kspider_amd: sources=" << N << " colour-entries=" << E << " pairs=" << rows.size() << std::endl;
     if (cc_col) {
@@ -218,7 +244,12 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
                 const float n1 = (float)cc_counts[a], n2 = (float)cc_counts[b];
                 const float c12 = 0.0f / n2, c21 = 0.0f / n1;
                 const float v = cc_col == 3 ? std::min(c12, c21) : cc_col == 5 ? std::max(c12, c21) : (float)((c12 + c21) / 2.0);
-                const bool kept = mode ? v != v : !(v < vcrit);
+                bool kept = mode ? v != v : !(v < vcrit);
+                if (cc_col == 6) {   // (the NaN rows were refused above)
+                    double g = 0;
+                    ksp::ani_of_row(std::min(c12, c21), std::max(c12, c21), ani_tab->data(), &g);
+                    kept = !(g * 100.0 < cutoff * 100.0);
+                }
                 if (!kept) continue;
                 const uint32_t ra = find(a), rb = find(b);
                 if (ra != rb) { parent[std::max(ra, rb)] = std::min(ra, rb); merged = true; }
@@ -271,6 +302,36 @@ extern "C" int kspider_pairwise_and_cluster(const char* index_prefix, int user_t
         return KSP_E_LIMIT;
     } catch (const std::exception& e) {
         ksp::set_error(e.what());
+        const std::string m = e.what();
+        return m.find("2^32") != std::string::npos ? KSP_E_LIMIT : KSP_E_IO;
+    }
+}
+
+extern "C" int kspider_pairwise_ani(const char* index_prefix, int user_threads, int64_t scale) {
+    if (!index_prefix) { ksp::set_error("kspider_pairwise_ani: index_prefix is NULL"); return KSP_E_ARG; }
+    if (scale <= 0) { ksp::set_error("kspider_pairwise_ani: estimating ANI needs the sourmash scale (> 0)"); return KSP_E_ARG; }
+    try {
+        return run_pairwise(index_prefix, user_threads < 1 ? 1 : user_threads, nullptr, 0, true);
+    } catch (const std::bad_alloc&) {
+        ksp::set_error("kspider_pairwise_ani: out of host memory");
+        return KSP_E_LIMIT;
+    } catch (const std::exception& e) {
+        ksp::set_error(std::string("kspider_pairwise_ani: ") + e.what());
+        const std::string m = e.what();
+        return m.find("2^32") != std::string::npos ? KSP_E_LIMIT : KSP_E_IO;
+    }
+}
+
+extern "C" int kspider_pairwise_ani_and_cluster(const char* index_prefix, int user_threads, int64_t scale, double cutoff) {
+    if (!index_prefix) { ksp::set_error("kspider_pairwise_ani_and_cluster: index_prefix is NULL"); return KSP_E_ARG; }
+    if (scale <= 0) { ksp::set_error("kspider_pairwise_ani_and_cluster: estimating ANI needs the sourmash scale (> 0)"); return KSP_E_ARG; }
+    try {
+        return run_pairwise(index_prefix, user_threads < 1 ? 1 : user_threads, "ani", cutoff, true);
+    } catch (const std::bad_alloc&) {
+        ksp::set_error("kspider_pairwise_ani_and_cluster: out of host memory");
+        return KSP_E_LIMIT;
+    } catch (const std::exception& e) {
+        ksp::set_error(std::string("kspider_pairwise_ani_and_cluster: ") + e.what());
         const std::string m = e.what();
         return m.find("2^32") != std::string::npos ? KSP_E_LIMIT : KSP_E_IO;
     }

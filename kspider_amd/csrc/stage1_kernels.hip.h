@@ -1677,14 +1677,6 @@ __global__ void k_blk_pos(const u32* __restrict__ blk_raw, u32* __restrict__ blk
     if (tid == nt - 1) { blk_pos[nb] = s_part[nt - 1]; scal[3] = s_part[nt - 1]; }
 }
 
-// tail pads of every block list (+inf ranks): from the end of list b to the start of list b + 1, and
-// 4 windows of slack behind the last list
-__global__ void k_pad(const u32* __restrict__ blk_raw, const u32* __restrict__ blk_pos, u32* __restrict__ brk, u32 nb, u32 padv) {
-    const u32 b = blockIdx.x;
-    const u32 lo = b < nb ? blk_pos[b] + (blk_raw[b + 1] - blk_raw[b]) : blk_pos[nb];
-    const u32 hi = b < nb ? blk_pos[b + 1] : blk_pos[nb] + 4u * WIN;
-    for (u32 i = lo + threadIdx.x; i < hi; i += blockDim.x) brk[i] = padv;
-}
 __global__ void k_fill(u32* __restrict__ p, u32 v, u64 n) {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;

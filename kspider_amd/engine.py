@@ -32,6 +32,8 @@ ABI_SYMBOLS = [
     "ksp_engine_set_profiling", "ksp_engine_phase_times",
     "ksp_pairwise_host_multi", "ksp_pairwise_postings_host_multi",
     "kspider_cluster", "ksp_components", "ksp_components_edges", "kspider_pairwise_and_cluster",
+    "kspider_estimate_ani", "kspider_pairwise_ani", "kspider_pairwise_ani_and_cluster", "ksp_edges_ani",
+    "ksp_components_edges_ani", "ksp_ani_value", "ksp_ani_values", "ksp_format_ani",
 ]
 
 
@@ -130,6 +132,15 @@ def lib():
         L.ksp_format_float.argtypes = [ctypes.c_float, ctypes.c_char_p]
         L.kspider_pairwise_sigs.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.kspider_pairwise_bins.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]
+        L.kspider_estimate_ani.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int64]
+        L.kspider_pairwise_ani.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int64]
+        L.kspider_pairwise_ani_and_cluster.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double]
+        L.ksp_edges_ani.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.ksp_components_edges_ani.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                               ctypes.c_int, ctypes.c_double, ctypes.c_void_p]
+        L.ksp_ani_value.argtypes = [ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
+        L.ksp_ani_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        L.ksp_format_ani.argtypes = [ctypes.c_double, ctypes.c_char_p]
         _lib = L
     return _lib
 
@@ -230,6 +241,51 @@ def components_edges(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts
     _check(L.ksp_components_edges(device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, dist_col, float(cutoff),
                                   out.ctypes.data))
     return out[:n_nodes]
+
+
+def estimate_ani(index_prefix: str, user_threads: int, scale: int) -> None:
+    """`kSpider pairwise -i PREFIX --estimate-ani -s SCALE` (ks_pairwise.py:29-84) over the files already there: writes
+    PREFIX_kSpider_pairwise.ani_col.tsv.  Host only; k is the first line of PREFIX.extra."""
+    _check(lib().kspider_estimate_ani(os.fsencode(index_prefix), int(user_threads), int(scale)))
+
+
+def pairwise_ani(index_prefix: str, user_threads: int, scale: int, cutoff: float | None = None) -> None:
+    """`kSpider pairwise` and `pairwise --estimate-ani` in one device pass (both TSVs as kspider_pairwise writes them, plus
+    the ANI column); with a cutoff also `kSpider cluster -d ani -c CUTOFF`, the components taken from the edges in HBM."""
+    L = lib()
+    if cutoff is None:
+        _check(L.kspider_pairwise_ani(os.fsencode(index_prefix), int(user_threads), int(scale)))
+    else:
+        _check(L.kspider_pairwise_ani_and_cluster(os.fsencode(index_prefix), int(user_threads), int(scale), float(cutoff)))
+
+
+def edges_ani(d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, ksize: int, d_ani_ptr: int, device: int = 0) -> None:
+    """d_ani[e] = average ANI of the ksp_edge record e (all DEVICE pointers); KspError on a NaN containment."""
+    _check(lib().ksp_edges_ani(device, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, int(ksize), d_ani_ptr or None))
+
+
+def components_edges_ani(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, ksize: int, cutoff: float,
+                         device: int = 0) -> np.ndarray:
+    """components_edges with the ANI column as the distance: an edge counts when ani * 100 is not below cutoff * 100."""
+    out = np.empty(max(1, n_nodes), dtype=np.uint32)
+    _check(lib().ksp_components_edges_ani(device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, int(ksize),
+                                          float(cutoff), out.ctypes.data))
+    return out[:n_nodes]
+
+
+def ani_values(min_c: np.ndarray, max_c: np.ndarray, ksize: int, via_table: bool) -> tuple:
+    """(rc, values): the ANI of rows with these containment floats, by the text definition or the device's table path."""
+    mn = np.ascontiguousarray(min_c, dtype=np.float32)
+    mx = np.ascontiguousarray(max_c, dtype=np.float32)
+    out = np.empty(mn.size, dtype=np.float64)
+    rc = lib().ksp_ani_values(mn.ctypes.data, mx.ctypes.data, mn.size, int(ksize), int(bool(via_table)), out.ctypes.data)
+    return rc, out
+
+
+def format_ani(v: float) -> str:
+    buf = ctypes.create_string_buffer(32)
+    n = lib().ksp_format_ani(float(v), buf)
+    return buf.raw[:n].decode()
 
 
 def components(n_nodes: int, a: np.ndarray, b: np.ndarray, device: int = 0) -> np.ndarray:
