@@ -181,3 +181,68 @@ def containment_rows(edges: np.ndarray, kmer_count: dict) -> list:
         rows.append((int(e["source_1"]), int(e["source_2"]), int(e["shared"]), min(c12, c21),
                      np.float32((np.float64(c12 + c21)) / 2.0), max(c12, c21)))
     return rows
+
+
+def _check_index(rc):
+    if rc != 0:
+        raise RuntimeError(lib().oracle_index_last_error().decode())
+
+
+def _threads(threads):
+    return max(1, min(32, len(os.sched_getaffinity(0)))) if threads is None else int(threads)
+
+
+def key_index(keys: np.ndarray, offsets: np.ndarray, threads: int | None = None):
+    """Every key held by two sources or more -> (keys ascending, key_off uint64, holders uint32 ascending per key);
+    a source that holds a key twice raises."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    L = lib()
+    L.oracle_index_last_error.restype = ctypes.c_char_p
+    kp = ctypes.POINTER(ctypes.c_uint64)()
+    op = ctypes.POINTER(ctypes.c_uint64)()
+    sp = ctypes.POINTER(ctypes.c_uint32)()
+    nk = ctypes.c_uint64(0)
+    nh = ctypes.c_uint64(0)
+    _check_index(L.oracle_key_index(_p(keys, ctypes.c_uint64), _p(offsets, ctypes.c_uint64), ctypes.c_uint32(offsets.size - 1),
+                                    ctypes.c_int(_threads(threads)), ctypes.byref(kp), ctypes.byref(op), ctypes.byref(sp),
+                                    ctypes.byref(nk), ctypes.byref(nh)))
+    K, M = nk.value, nh.value
+    try:
+        uniq = np.ctypeslib.as_array(kp, shape=(max(1, K),))[:K].copy()
+        key_off = np.ctypeslib.as_array(op, shape=(K + 1,)).copy()
+        holders = np.ctypeslib.as_array(sp, shape=(max(1, M),))[:M].copy()
+    finally:
+        for ptr in (kp, op, sp):
+            L.oracle_free(ptr)
+    return uniq, key_off, holders
+
+
+def key_probe(key_off: np.ndarray, holders: np.ndarray, weights, n_sources: int, us: np.ndarray, vs: np.ndarray,
+              threads: int | None = None) -> np.ndarray:
+    """u_j^T S v_j mod 2^64 for every row j of us / vs (shape (probes, n_sources)), S = sum_k w_k (1_H 1_H^T - diag)."""
+    key_off = np.ascontiguousarray(key_off, dtype=np.uint64)
+    holders = np.ascontiguousarray(holders, dtype=np.uint32)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint32)
+    us = np.ascontiguousarray(us, dtype=np.uint64)
+    vs = np.ascontiguousarray(vs, dtype=np.uint64)
+    assert us.shape == vs.shape and us.shape[1] == n_sources
+    out = np.zeros(us.shape[0], dtype=np.uint64)
+    _check_index(lib().oracle_key_probe(_p(key_off, ctypes.c_uint64), _p(holders, ctypes.c_uint32), ctypes.c_uint64(key_off.size - 1),
+                                        _p(w, ctypes.c_uint32) if w is not None else None, ctypes.c_uint32(n_sources),
+                                        _p(us, ctypes.c_uint64), _p(vs, ctypes.c_uint64), ctypes.c_int(us.shape[0]),
+                                        ctypes.c_int(_threads(threads)), _p(out, ctypes.c_uint64)))
+    return out
+
+
+def key_rows(key_off: np.ndarray, holders: np.ndarray, weights, n_sources: int, threads: int | None = None):
+    """(row sums of S as uint64[n_sources], sum_k w_k C(m_k, 2)) in integer arithmetic."""
+    key_off = np.ascontiguousarray(key_off, dtype=np.uint64)
+    holders = np.ascontiguousarray(holders, dtype=np.uint32)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint32)
+    rows = np.zeros(max(1, n_sources), dtype=np.uint64)
+    total = ctypes.c_uint64(0)
+    _check_index(lib().oracle_key_rows(_p(key_off, ctypes.c_uint64), _p(holders, ctypes.c_uint32), ctypes.c_uint64(key_off.size - 1),
+                                       _p(w, ctypes.c_uint32) if w is not None else None, ctypes.c_uint32(n_sources),
+                                       ctypes.c_int(_threads(threads)), _p(rows, ctypes.c_uint64), ctypes.byref(total)))
+    return rows[:n_sources], total.value

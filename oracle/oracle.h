@@ -66,6 +66,19 @@ int oracle_write_bin_sketch(const char* path, const uint64_t* hashes, uint64_t n
 int64_t oracle_brute_pairs(const uint64_t* keys, const uint64_t* offsets, uint32_t n_sources, oracle_edge* out,
                            uint64_t capacity);
 
+/* Pair-matrix probes (tests/pair_probe.py).  oracle_key_index: every key held by two sources or more (ascending), its
+ * holders out_src[out_off[k] .. out_off[k+1]) ascending; malloc'ed, free with oracle_free(); a source holding a key twice
+ * is an error.  oracle_key_probe: out[j] = u_j^T S v_j mod 2^64 with S = sum_k w_k (1_H 1_H^T - diag) (w NULL: 1; probe j
+ * reads us / vs + j * n_sources).  oracle_key_rows: the row sums of S and sum_k w_k C(m_k, 2).  Errors:
+ * oracle_index_last_error(). */
+const char* oracle_index_last_error(void);
+int oracle_key_index(const uint64_t* keys, const uint64_t* offsets, uint32_t n_sources, int threads, uint64_t** out_keys,
+                     uint64_t** out_off, uint32_t** out_src, uint64_t* n_keys, uint64_t* n_held);
+int oracle_key_probe(const uint64_t* key_off, const uint32_t* src, uint64_t n_keys, const uint32_t* w, uint32_t n_sources,
+                     const uint64_t* us, const uint64_t* vs, int n_probes, int threads, uint64_t* out);
+int oracle_key_rows(const uint64_t* key_off, const uint32_t* src, uint64_t n_keys, const uint32_t* w, uint32_t n_sources,
+                    int threads, uint64_t* rows, uint64_t* total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,10 @@
 //     hash table.  Real phmap could iterate these files but not look keys up
 //     (we do not know its hash): reader-side test data only.
 // (3) Brute-force |A ∩ B| over all pairs (test/generate_golden_files.py:40-49).
+// (4) The key side of the pair-matrix probes (tests/pair_probe.py): every key held by two sources or more with its
+//     holders, and from that index alone the fingerprint u^T S v and the row sums of S, threaded.
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -20,6 +23,7 @@
 #include <map>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "oracle.h"
@@ -80,6 +84,31 @@ struct RawTable {
 };
 
 thread_local std::string g_err2;
+
+#pragma pack(push, 1)
+struct KeySrc {   // 12 bytes: the sort buffer of a C3-sized set (5e8 entries) stays at 6 GB
+    uint64_t k;
+    uint32_t s;
+    bool operator<(const KeySrc& o) const { return k != o.k ? k < o.k : s < o.s; }
+};
+#pragma pack(pop)
+
+// fn(t) on threads 0..T-1; the first exception is rethrown on the caller's thread
+template <class F> void run_threads(int T, F fn) {
+    std::vector<std::thread> th;
+    std::vector<std::string> errs(T);
+    for (int t = 0; t < T; ++t)
+        th.emplace_back([&, t] {
+            try {
+                fn(t);
+            } catch (const std::exception& e) {
+                errs[t] = e.what();
+            }
+        });
+    for (auto& x : th) x.join();
+    for (auto& e : errs)
+        if (!e.empty()) throw std::runtime_error(e);
+}
 
 }  // namespace
 
@@ -248,6 +277,181 @@ int64_t oracle_brute_pairs(const uint64_t* keys, const uint64_t* offsets, uint32
         }
     }
     return (int64_t)ne;
+}
+
+const char* oracle_index_last_error(void) { return g_err2.c_str(); }
+
+// Every key held by two sources or more: out_keys[k] ascending, its holders out_src[out_off[k] .. out_off[k+1]) ascending.
+// The entries are cut into ranges of the key (P parts, monotone in the key, so the output is globally sorted), scattered
+// as (key, source) and every part sorted by a thread.  A source that holds a key twice is an error.
+int oracle_key_index(const uint64_t* keys, const uint64_t* offsets, uint32_t n_sources, int threads, uint64_t** out_keys,
+                     uint64_t** out_off, uint32_t** out_src, uint64_t* n_keys, uint64_t* n_held) {
+    try {
+        const int T = std::max(1, threads);
+        const uint64_t total = offsets[n_sources];
+        uint64_t lo = ~0ull, hi = 0;
+        for (uint64_t i = 0; i < total; ++i) { lo = std::min(lo, keys[i]); hi = std::max(hi, keys[i]); }
+        const uint64_t P = total ? (uint64_t)T * 16 : 1;
+        const unsigned __int128 span = total ? (unsigned __int128)(hi - lo) + 1 : 1;
+        auto part_of = [&](uint64_t k) { return (uint64_t)(((unsigned __int128)(k - lo) * P) / span); };
+        // sources of thread t: [s_of[t], s_of[t + 1]), about total / T entries each
+        std::vector<uint32_t> s_of(T + 1, n_sources);
+        s_of[0] = 0;
+        for (int t = 1; t < T; ++t)
+            s_of[t] = (uint32_t)(std::upper_bound(offsets, offsets + n_sources + 1, total / T * t) - offsets - 1);
+        for (int t = 1; t <= T; ++t) s_of[t] = std::max(s_of[t], s_of[t - 1]);
+        std::vector<uint64_t> cnt((size_t)T * P, 0);   // [t][p]
+        run_threads(T, [&](int t) {
+            uint64_t* c = &cnt[(size_t)t * P];
+            for (uint64_t i = offsets[s_of[t]]; i < offsets[s_of[t + 1]]; ++i) ++c[part_of(keys[i])];
+        });
+        std::vector<uint64_t> part_off(P + 1, 0);   // cnt[t][p] becomes the write position of thread t in part p
+        uint64_t o = 0;
+        for (uint64_t p = 0; p < P; ++p) {
+            part_off[p] = o;
+            for (int t = 0; t < T; ++t) { uint64_t c = cnt[(size_t)t * P + p]; cnt[(size_t)t * P + p] = o; o += c; }
+        }
+        part_off[P] = o;
+        std::vector<KeySrc> ent(total);
+        run_threads(T, [&](int t) {
+            uint64_t* c = &cnt[(size_t)t * P];
+            for (uint32_t s = s_of[t]; s < s_of[t + 1]; ++s)
+                for (uint64_t i = offsets[s]; i < offsets[s + 1]; ++i) ent[c[part_of(keys[i])]++] = KeySrc{keys[i], s};
+        });
+        // sort every part; count its keys of two holders or more and their holders
+        std::vector<uint64_t> pk(P + 1, 0), ph(P + 1, 0);
+        std::atomic<uint64_t> next{0};
+        run_threads(T, [&](int) {
+            for (uint64_t p; (p = next++) < P;) {
+                KeySrc* b = ent.data() + part_off[p];
+                KeySrc* e = ent.data() + part_off[p + 1];
+                std::sort(b, e);
+                for (KeySrc* i = b; i < e;) {
+                    KeySrc* j = i + 1;
+                    for (; j < e && j->k == i->k; ++j)
+                        if (j->s == (j - 1)->s)
+                            throw std::runtime_error("key_index: source " + std::to_string(j->s) + " holds key " +
+                                                     std::to_string(j->k) + " twice");
+                    if (j - i >= 2) { ++pk[p]; ph[p] += (uint64_t)(j - i); }
+                    i = j;
+                }
+            }
+        });
+        uint64_t K = 0, M = 0;
+        for (uint64_t p = 0; p < P; ++p) {
+            uint64_t a = pk[p], b = ph[p];
+            pk[p] = K; ph[p] = M;
+            K += a; M += b;
+        }
+        uint64_t* ok = (uint64_t*)std::malloc(8 * std::max<uint64_t>(1, K));
+        uint64_t* oo = (uint64_t*)std::malloc(8 * (K + 1));
+        uint32_t* os = (uint32_t*)std::malloc(4 * std::max<uint64_t>(1, M));
+        if (!ok || !oo || !os) {
+            std::free(ok); std::free(oo); std::free(os);
+            throw std::runtime_error("key_index: out of memory");
+        }
+        next = 0;
+        run_threads(T, [&](int) {
+            for (uint64_t p; (p = next++) < P;) {
+                const KeySrc* e = ent.data() + part_off[p + 1];
+                uint64_t k = pk[p], m = ph[p];
+                for (const KeySrc* i = ent.data() + part_off[p]; i < e;) {
+                    const KeySrc* j = i + 1;
+                    while (j < e && j->k == i->k) ++j;
+                    if (j - i >= 2) {
+                        ok[k] = i->k;
+                        oo[k++] = m;
+                        for (const KeySrc* x = i; x < j; ++x) os[m++] = x->s;
+                    }
+                    i = j;
+                }
+            }
+        });
+        oo[K] = M;
+        *out_keys = ok;
+        *out_off = oo;
+        *out_src = os;
+        *n_keys = K;
+        *n_held = M;
+        return 0;
+    } catch (const std::exception& e) {
+        g_err2 = e.what();
+        return 1;
+    }
+}
+
+// u^T S v mod 2^64 for every probe j (u = us + j * n_sources, likewise v), S = sum_k w_k (1_H 1_H^T - diag):
+// out[j] = sum_k w_k ((sum_H u)(sum_H v) - sum_H u v).  w NULL: 1.
+int oracle_key_probe(const uint64_t* key_off, const uint32_t* src, uint64_t n_keys, const uint32_t* w, uint32_t n_sources,
+                     const uint64_t* us, const uint64_t* vs, int n_probes, int threads, uint64_t* out) {
+    try {
+        const int T = std::max(1, threads);
+        std::vector<uint64_t> acc((size_t)T * n_probes, 0);
+        run_threads(T, [&](int t) {
+            const uint64_t k0 = n_keys * t / T, k1 = n_keys * (t + 1) / T;
+            for (int j = 0; j < n_probes; ++j) {
+                const uint64_t* u = us + (size_t)j * n_sources;
+                const uint64_t* v = vs + (size_t)j * n_sources;
+                uint64_t a = 0;
+                for (uint64_t k = k0; k < k1; ++k) {
+                    uint64_t su = 0, sv = 0, suv = 0;
+                    for (uint64_t i = key_off[k]; i < key_off[k + 1]; ++i) {
+                        const uint32_t s = src[i];
+                        su += u[s];
+                        sv += v[s];
+                        suv += u[s] * v[s];
+                    }
+                    a += (w ? (uint64_t)w[k] : 1ull) * (su * sv - suv);
+                }
+                acc[(size_t)t * n_probes + j] = a;
+            }
+        });
+        for (int j = 0; j < n_probes; ++j) {
+            uint64_t a = 0;
+            for (int t = 0; t < T; ++t) a += acc[(size_t)t * n_probes + j];
+            out[j] = a;
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        g_err2 = e.what();
+        return 1;
+    }
+}
+
+// The row sums of S, rows[a] = sum_{k held by a} w_k (m_k - 1), and its total / 2 = sum_k w_k C(m_k, 2), in integers.
+int oracle_key_rows(const uint64_t* key_off, const uint32_t* src, uint64_t n_keys, const uint32_t* w, uint32_t n_sources,
+                    int threads, uint64_t* rows, uint64_t* total) {
+    try {
+        const int T = std::max(1, threads);
+        std::vector<std::vector<uint64_t>> part(T);
+        std::vector<unsigned __int128> tot(T, 0);
+        run_threads(T, [&](int t) {
+            std::vector<uint64_t>& r = part[t];
+            r.assign(n_sources, 0);
+            const uint64_t k0 = n_keys * t / T, k1 = n_keys * (t + 1) / T;
+            for (uint64_t k = k0; k < k1; ++k) {
+                const uint64_t m = key_off[k + 1] - key_off[k], c = (w ? (uint64_t)w[k] : 1ull) * (m - 1);
+                tot[t] += (unsigned __int128)c * m / 2;
+                for (uint64_t i = key_off[k]; i < key_off[k + 1]; ++i) {
+                    if (src[i] >= n_sources) throw std::runtime_error("key_rows: source id out of range");
+                    r[src[i]] += c;
+                }
+            }
+        });
+        unsigned __int128 all = 0;
+        for (int t = 0; t < T; ++t) all += tot[t];
+        if (all >> 64) throw std::runtime_error("key_rows: total above 2^64");
+        *total = (uint64_t)all;
+        for (uint32_t a = 0; a < n_sources; ++a) {
+            uint64_t x = 0;
+            for (int t = 0; t < T; ++t) x += part[t][a];
+            rows[a] = x;
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        g_err2 = e.what();
+        return 1;
+    }
 }
 
 }  // extern "C"

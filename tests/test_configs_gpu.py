@@ -10,11 +10,13 @@
   configs[4] C5 1 000 000 read groups, <= 294 hashes              size-independent properties
 
 Properties at the sizes the oracle cannot reach (what /root/reference/test/validate.py:100-108 checks per
-key, restated so that it is independent of the size):
+key, restated so that it is independent of the size), from a host-side key index (tests/pair_probe.py):
   * sum of all shared counts == sum_k C(holders_k, 2) from an independent host-side inverted index;
   * every edge has source_1 < source_2 < N, no pair twice, shared >= 1, shared <= min(n_a, n_b);
   * COMPLETE ROWS of 300 sampled sources: sum_b shared(a, b) == sum_{k in K(a)} (holders_k - 1);
   * 300 sampled reported pairs and 300 sampled absent pairs by direct set intersection.
+and the whole edge set by tests/pair_probe.check_edge_set: all N row sums and two random probes u^T S v of the pair
+matrix, computed from the keys alone (an error that keeps the total and every row sum is caught too).
 These runs reach the code the shrunken cases do not: > 2^32-thread launch chunking, the cell-index clamp,
 T > 2^26 tiles (no work list), 32-bit tags above 65 536 sources, C4's ~10^6-hash sketch in the
 32-bit-counter instantiation of the join.
@@ -25,6 +27,7 @@ import numpy as np
 import pytest
 
 from kspider_amd import engine, synth
+from pair_probe import check_edge_set, config
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +56,7 @@ def _join_all(e, cap):
     return ev[o], key[o]
 
 
-def _properties(sk, ev, key, seed):
+def _properties(sk, idx, ev, key, seed):
     n = sk.n_sources
     sizes = sk.sizes
     assert len(ev) > 0
@@ -61,16 +64,15 @@ def _properties(sk, ev, key, seed):
     assert (np.diff(key) > 0).all()                       # sorted, and no pair twice
     assert (ev["shared"] > 0).all()
     assert (ev["shared"] <= np.minimum(sizes[ev["source_1"]], sizes[ev["source_2"]])).all()
-    # independent inverted index on the host: every key held by m sources contributes C(m, 2)
-    uniq, counts = np.unique(sk.keys, return_counts=True)
-    counts = counts.astype(np.int64)
+    # independent inverted index on the host: every key held by m sources contributes C(m, 2) (keys held once: 0)
+    counts = idx.counts
     assert int(ev["shared"].sum(dtype=np.uint64)) == int((counts * (counts - 1) // 2).sum())
     # complete rows of sampled sources
     row = np.bincount(ev["source_1"], weights=ev["shared"].astype(np.float64), minlength=n)
     row += np.bincount(ev["source_2"], weights=ev["shared"].astype(np.float64), minlength=n)
     rng = np.random.default_rng(seed)
     for a in rng.choice(n, size=300, replace=False):
-        want = int((counts[np.searchsorted(uniq, sk.run(int(a)))] - 1).sum())
+        want = int((idx.holders_of(sk.run(int(a))) - 1).sum())
         assert int(row[a]) == want, f"row sum of source {a}"
     # sampled reported pairs / sampled absent pairs by direct intersection
     for i in rng.choice(len(ev), size=min(300, len(ev)), replace=False):
@@ -85,6 +87,8 @@ def _properties(sk, ev, key, seed):
             continue
         assert np.intersect1d(sk.run(a), sk.run(b), assume_unique=True).size == 0
         absent += 1
+    # the whole edge set: all N rows, two random probes of the pair matrix
+    check_edge_set(ev, idx, n, probes=2, seed=seed)
 
 
 def test_c1_full_size_bit_exact(oracle_lib, tmp_path):
@@ -133,7 +137,7 @@ def test_c2_full_size_edge_set_equals_restated_reference(oracle_lib):
 @pytest.mark.parametrize("cfg,n", [("C3", 100_000), ("C4", 50_000), ("C5", 1_000_000)])
 def test_full_size_properties(cfg, n):
     """configs[2..4] at the sizes BASELINE.json names."""
-    sk = synth.generate(cfg)
+    sk, idx = config(cfg)
     assert sk.n_sources == n
     dk = engine.DeviceBuffer.from_numpy(sk.keys)
     e = engine.Engine(0)
@@ -141,6 +145,6 @@ def test_full_size_properties(cfg, n):
     st = e.stats()
     assert st["n_sources"] == n and st["n_entries"] == int(sk.offsets[-1])
     ev, key = _join_all(e, int(min(e.edge_bound(0, e.num_tiles), 1 << 26)) + 1)
-    _properties(sk, ev, key, seed=100 + synth.CONFIGS[cfg]["idx"])
+    _properties(sk, idx, ev, key, seed=100 + synth.CONFIGS[cfg]["idx"])
     dk.free()
     e.close()

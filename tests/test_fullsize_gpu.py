@@ -1,10 +1,11 @@
 """Full-size checks on BASELINE.json's bench workload (C2: 10k sources, ~5k hashes each),
 where the brute-force oracle is too slow for every pair: size-independent properties plus
-sampled pair checks against direct set intersection."""
+sampled pair checks against direct set intersection, and the whole edge set by tests/pair_probe.check_edge_set."""
 import numpy as np
 import pytest
 
 from kspider_amd import engine, synth
+from pair_probe import check_edge_set, key_index
 
 pytestmark = pytest.mark.gpu
 
@@ -59,8 +60,10 @@ def test_c2_properties_and_sampled_pairs(c2):
         assert (s > 0) == ((a * n + b) in present)
     # every same-cluster pair shares something in this generator; check the checksum of
     # per-source totals against an independent inverted-index count: sum_k C(m_k, 2)
-    uniq, counts = np.unique(sk.keys, return_counts=True)
-    assert int(full["shared"].sum()) == int((counts.astype(np.int64) * (counts - 1) // 2).sum())
+    idx = key_index(sk.keys, sk.offsets)
+    counts = idx.counts
+    assert int(full["shared"].sum()) == int((counts * (counts - 1) // 2).sum())
+    check_edge_set(full, idx, n, probes=2, seed=1)
 
 
 def test_overflow_is_reported_not_silent(c2):
@@ -110,8 +113,9 @@ def test_other_shapes_checksum_and_samples(cfg, n, env, monkeypatch):
     cap = int(e.edge_bound(0, T)) + 1
     de = engine.DeviceBuffer(cap * 16)
     ev = _join(e, de, cap, 0, T)
-    _, counts = np.unique(sk.keys, return_counts=True)
-    assert int(ev["shared"].sum()) == int((counts.astype(np.int64) * (counts - 1) // 2).sum())
+    idx = key_index(sk.keys, sk.offsets)
+    counts = idx.counts
+    assert int(ev["shared"].sum()) == int((counts * (counts - 1) // 2).sum())
     assert (ev["source_1"] < ev["source_2"]).all() and int(ev["source_2"].max()) < sk.n_sources
     key = ev["source_1"].astype(np.int64) * sk.n_sources + ev["source_2"]
     assert (np.diff(key) > 0).all()
@@ -119,6 +123,7 @@ def test_other_shapes_checksum_and_samples(cfg, n, env, monkeypatch):
     for i in rng.choice(len(ev), size=min(300, len(ev)), replace=False):
         a, b, s = int(ev["source_1"][i]), int(ev["source_2"][i]), int(ev["shared"][i])
         assert np.intersect1d(sk.run(a), sk.run(b), assume_unique=True).size == s
+    check_edge_set(ev, idx, sk.n_sources, probes=2, seed=5)
 
 
 def test_join_to_host_in_pieces_equals_one_join(monkeypatch):
