@@ -62,10 +62,11 @@ typedef struct ksp_stats {
                                    input, 1 rocPRIM radix partition or sort, 2 the hand-written paged
                                    partition, 3 the segment partition: level 1 read off the sorted runs
                                    (partition_kernels.hip.h)                                             */
-    int partition_fallback;     /* 0, or why a hand-written partition handed the build on: 1 page table / pool
+    int partition_fallback;     /* 0, or why a hand-written partition handed the last build on: 1 page table / pool
                                    full (keys far from uniform; -> rocPRIM), 2 internal count mismatch, 3 page
                                    wait timed out (2 and 3 are defects, never expected), 4 / 5 a tile / a bucket
-                                   of the segment partition overflowed (-> the paged partition)           */
+                                   of the segment partition overflowed (-> the paged partition).  Such a hand-over
+                                   sticks to the engine: its later builds go straight to the fallback and report 0 */
     uint64_t n_match_records;   /* match-list join: (key, block pair) records stage 1 handed to the join (0: the
                                    join searches the block lists)                                         */
     uint64_t n_join_workgroups; /* shares of the work list (workgroups of a join over all tiles)           */
@@ -90,8 +91,12 @@ void ksp_engine_destroy(ksp_engine* e);
  * posting list per block (device).  d_keys: device pointer, concatenated sorted-unique
  * uint64 runs; d_weights: device pointer (one uint32 per key entry; the colour weight
  * w_c of src/pairwise.cpp:221) or NULL for weight 1; h_offsets: HOST pointer,
- * n_sources+1 element offsets; key_bits: significant bits of the largest key, 0 = find
- * out on the device.  stream: hipStream_t (NULL = default stream).                    */
+ * n_sources+1 element offsets; key_bits: significant bits of the largest key (at least the true width, at most 64),
+ * 0 = find out on the device.  stream: hipStream_t (NULL = default stream).
+ * Every argument is checked before the engine changes: a build refused with KSP_E_ARG or KSP_E_LIMIT leaves the last
+ * build joinable and a pending join (ksp_engine_join_launch) collectable.  A build on another stream than a join still
+ * pending on this engine is refused (KSP_E_ARG: nothing orders the two streams; collect the join first).  The same holds
+ * for ksp_engine_build_slice, ksp_engine_build_postings[_slice], ksp_engine_slice_finish and ksp_engine_assemble.  */
 int ksp_engine_build_blocks(ksp_engine* e, const uint64_t* d_keys, const uint32_t* d_weights,
                             const uint64_t* h_offsets, uint32_t n_sources, int key_bits, void* stream);
 
@@ -113,7 +118,9 @@ int ksp_engine_balanced_cuts(const ksp_engine* e, uint32_t nparts, uint64_t* cut
 int ksp_engine_join(ksp_engine* e, uint64_t tile_begin, uint64_t tile_end, ksp_edge* d_edges, uint64_t capacity,
                     uint64_t* h_count, void* stream);
 /* The same in two halves, for callers that pipeline: _launch queues the join on `stream` and returns; _wait blocks
- * until it has finished and reports the count (one launched join per engine at a time).  Work queued on the same
+ * until it has finished and reports the count (one launched join per engine at a time: ksp_engine_join_launch,
+ * ksp_engine_join and ksp_engine_join_to_host refuse with KSP_E_ARG while a launched join is not collected, and leave
+ * it collectable).  Work queued on the same
  * stream after _launch — the next ksp_engine_build_blocks on this engine included — runs behind the join, so the
  * device does not idle while the host collects the count and hands the edges on (bench.py does exactly that). */
 int ksp_engine_join_launch(ksp_engine* e, uint64_t tile_begin, uint64_t tile_end, ksp_edge* d_edges, uint64_t capacity, void* stream);
@@ -128,7 +135,7 @@ int ksp_engine_join_wait(ksp_engine* e, uint64_t* h_count);
  * into d_edges — nothing between the build and the launch of its join but the cutting of the work list.
  * KSP_E_OVERFLOW: *bound + 1 > capacity, nothing was launched (grow the buffer, then ksp_engine_join_launch).
  * A join launched on this engine before the call (the previous step's) is collected on the way — it ran in front of
- * this build on the stream: *prev_count / *prev_status are what ksp_engine_join_wait would have returned for it,
+ * this build on the stream (a join pending on another stream makes the call fail with KSP_E_ARG, the join uncollected): *prev_count / *prev_status are what ksp_engine_join_wait would have returned for it,
  * *prev_ms_join (may be NULL) its kernel time.
  * Collect the join launched here with ksp_engine_join_wait, or with the next ksp_engine_step_launch.
  * A step launched this way puts NO timing events into the stream (an event record is a ~6 us bubble between two

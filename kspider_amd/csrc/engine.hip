@@ -226,6 +226,7 @@ struct ksp_engine {
     hipEvent_t ev_aux[2] = {nullptr, nullptr};
     hipEvent_t ev_copy[2] = {nullptr, nullptr};
     bool join_pending = false;           // a launched join whose count has not been collected (ksp_engine_join_wait)
+    hipStream_t join_st = nullptr;       // ... and the stream it runs on
     u64 join_cap = 0;
     ksp_stats jst{};                     // last_* of the launched join
 #ifdef KSP_WGTIME
@@ -1782,6 +1783,20 @@ static int build_schedule(ksp_engine* e) {
     return KSP_OK;
 }
 
+// A join still pending on another stream than `st` may be reading the block lists a build on `st` would overwrite, and
+// nothing orders the two streams: refuse (collect it with ksp_engine_join_wait first).
+static bool join_elsewhere(const ksp_engine* e, hipStream_t st, const char* what) {
+    if (!e->join_pending || e->join_st == st) return false;
+    set_error(std::string(what) + ": a join launched on another stream is pending (ksp_engine_join_wait first)");
+    return true;
+}
+// One launched join per engine at a time: a second join before the first is collected would lose its count.
+static bool join_still_pending(const ksp_engine* e, const char* what) {
+    if (!e->join_pending) return false;
+    set_error(std::string(what) + ": a launched join is pending (ksp_engine_join_wait first)");
+    return true;
+}
+
 static int finish_build(ksp_engine* e) {
     e->st.key_bits = e->key_bits;
     if (e->blk_staged) {
@@ -1820,14 +1835,11 @@ static int finish_build(ksp_engine* e) {
 // common front end of build_blocks / build_slice
 static int build_common(ksp_engine* e, const uint64_t* d_keys, const uint32_t* d_weights, const uint64_t* h_offsets,
                         uint32_t n_sources, int key_bits, u32 part, u32 nparts, hipStream_t st, const bool slice = false) {
+    // every argument is checked before anything of the engine changes: a refused build leaves the last build joinable
+    // and a pending join collectable
     if (!e || !h_offsets) { set_error("build: NULL argument"); return KSP_E_ARG; }
     if (nparts == 0 || part >= nparts) { set_error("build: bad part / nparts"); return KSP_E_ARG; }
-    KSP_HIP(hipSetDevice(e->device));
-    e->built = false;
-    e->slice_ready = false;
-    e->post_slice = false;
-    e->sched_on = false; e->collect = false; e->have_bits = false; e->matches_on = false; e->pmask_on = false;   // (nothing of the previous build's work list survives)
-    e->act_tid.clear(); e->act_rec.clear();
+    if (key_bits < 0 || key_bits > 64) { set_error("build: key_bits outside [0, 64]"); return KSP_E_ARG; }
     for (u32 s = 0; s < n_sources; ++s)
         if (h_offsets[s + 1] < h_offsets[s]) { set_error("build: offsets not monotone"); return KSP_E_ARG; }
     const u64 n = n_sources ? h_offsets[n_sources] - h_offsets[0] : 0;
@@ -1837,6 +1849,14 @@ static int build_common(ksp_engine* e, const uint64_t* d_keys, const uint32_t* d
     // sets into enough slices by itself
     if (n >= (1ull << 30) && !(slice && nparts > 1)) { set_error("build: more than 2^30 key entries per call"); return KSP_E_LIMIT; }
     if (n && !d_keys) { set_error("build: d_keys is NULL"); return KSP_E_ARG; }
+    if (join_elsewhere(e, st, "build")) return KSP_E_ARG;
+    KSP_HIP(hipSetDevice(e->device));
+    e->built = false;
+    e->slice_ready = false;
+    e->post_slice = false;
+    e->sched_on = false; e->collect = false; e->have_bits = false; e->matches_on = false; e->pmask_on = false;   // (nothing of the previous build's work list survives)
+    e->act_tid.clear(); e->act_rec.clear();
+    e->part_fail = 0;   // (stats: partition_fallback describes this build)
     if (const char* ro = std::getenv("KSP_REORDER")) e->reorder = std::atoi(ro) != 0;   // diagnostic / tests
     e->n_sources = n_sources;
     e->n_entries = n;
@@ -1850,7 +1870,6 @@ static int build_common(ksp_engine* e, const uint64_t* d_keys, const uint32_t* d
     const bool same_offsets = e->d_off_sketch && e->h_off.size() == (size_t)n_sources + 1 &&
                               std::memcmp(e->h_off.data(), h_offsets, ((size_t)n_sources + 1) * 8) == 0;
     if (!same_offsets) { e->h_off.assign(h_offsets, h_offsets + n_sources + 1); e->d_off_sketch = false; e->seg_groups_ok = false; }
-    e->blk_staged = false;
     if (std::getenv("KSP_FULL_SORT")) e->full_sort = true;   // diagnostic: sort on all key bits
     if (const char* hg = std::getenv("KSP_HASH_GROUP")) e->hash_off = std::atoi(hg) == 0;   // diagnostic / tests
     if (const char* kg = std::getenv("KSP_KEY_GROUPS")) e->key_groups_off = std::atoi(kg) == 0;
@@ -1897,6 +1916,8 @@ static int build_common(ksp_engine* e, const uint64_t* d_keys, const uint32_t* d
         const int phase = slice ? 1 : 0;   // a slice stops at the source labels (ksp_engine_slice_finish does the rest)
         e->scal_fresh = false;
         e->sched_early = false;
+        e->blk_staged = false;        // (an abandoned attempt's block tables and copy-out signal are not this attempt's)
+        e->sched_signalled = false;
         rc = build_dispatch(e, d_keys, d_weights, st, phase);
         if (rc) return rc;
         if (!e->scal_fresh) {   // (the key-by-key list build has read [1] .. [11] back already: nothing changes them after)
@@ -1960,6 +1981,12 @@ static int build_postings_common(ksp_engine* e, const uint64_t* h_key_off, const
                                  uint32_t n_keys, uint32_t n_sources, void* stream, const bool slice) {
     if (!e || (n_keys && (!h_key_off || !d_sources))) { set_error("build_postings: NULL argument"); return KSP_E_ARG; }
     hipStream_t st = (hipStream_t)stream;
+    const u64 n = n_keys ? h_key_off[n_keys] : 0;
+    if (n_keys && h_key_off[0] != 0) { set_error("build_postings: key_off[0] must be 0"); return KSP_E_ARG; }
+    for (u32 k = 0; k < n_keys; ++k)
+        if (h_key_off[k + 1] < h_key_off[k] + 2) { set_error("build_postings: every key needs at least two holders"); return KSP_E_ARG; }
+    if (n >= (1ull << 30)) { set_error("build_postings: more than 2^30 entries per call"); return KSP_E_LIMIT; }
+    if (join_elsewhere(e, st, "build_postings")) return KSP_E_ARG;
     KSP_HIP(hipSetDevice(e->device));
     e->built = false;
     e->slice_ready = false;
@@ -1968,11 +1995,7 @@ static int build_postings_common(ksp_engine* e, const uint64_t* h_key_off, const
     e->ph_n = 0;
     e->slice_phase = 0;
     e->post_slice = false;
-    const u64 n = n_keys ? h_key_off[n_keys] : 0;
-    if (n_keys && h_key_off[0] != 0) { set_error("build_postings: key_off[0] must be 0"); return KSP_E_ARG; }
-    for (u32 k = 0; k < n_keys; ++k)
-        if (h_key_off[k + 1] < h_key_off[k] + 2) { set_error("build_postings: every key needs at least two holders"); return KSP_E_ARG; }
-    if (n >= (1ull << 30)) { set_error("build_postings: more than 2^30 entries per call"); return KSP_E_LIMIT; }
+    e->part_fail = 0;
     if (const char* ro = std::getenv("KSP_REORDER")) e->reorder = std::atoi(ro) != 0;
     e->n_sources = n_sources;
     e->n_entries = n;
@@ -2118,6 +2141,7 @@ int ksp_engine_slice_finish(ksp_engine* e, const uint32_t* d_labels, void* strea
     if (!e) { set_error("slice_finish: NULL argument"); return KSP_E_ARG; }
     if (e->slice_phase != 1) { set_error("slice_finish: build_slice has not been run"); return KSP_E_ARG; }
     hipStream_t st = (hipStream_t)stream;
+    if (join_elsewhere(e, st, "slice_finish")) return KSP_E_ARG;
     KSP_HIP(hipSetDevice(e->device));
     e->slice_phase = 0;
     if (e->n_entries == 0 || e->nb == 0) { e->slice_ready = true; return KSP_OK; }
@@ -2188,6 +2212,7 @@ int ksp_engine_assemble(ksp_engine* e, uint32_t nparts, const uint64_t* h_sizes 
     if (!e || !h_sizes || nparts == 0) { set_error("assemble: bad argument"); return KSP_E_ARG; }
     if (!e->slice_ready) { set_error("assemble: build_slice must run on this engine first (it sets the geometry)"); return KSP_E_ARG; }
     hipStream_t st = (hipStream_t)stream;
+    if (join_elsewhere(e, st, "assemble")) return KSP_E_ARG;
     KSP_HIP(hipSetDevice(e->device));
     e->built = false;
     e->pmask_on = false;   // (the assembled lists have no positional masks)
@@ -2324,15 +2349,16 @@ int ksp_engine_balanced_cuts(const ksp_engine* e, uint32_t nparts, uint64_t* cut
 int ksp_engine_join_launch(ksp_engine* e, uint64_t tile_begin, uint64_t tile_end, ksp_edge* d_edges, uint64_t capacity, void* stream) {
     if (!e) { set_error("join: NULL argument"); return KSP_E_ARG; }
     if (!e->built) { set_error("join: build_blocks has not been run"); return KSP_E_ARG; }
+    if (join_still_pending(e, "join")) return KSP_E_ARG;
     hipStream_t st = (hipStream_t)stream;
-    KSP_HIP(hipSetDevice(e->device));
     const u64 T = ksp_engine_num_tiles(e);
     if (tile_end > T) tile_end = T;
-    e->join_pending = false;
+    const bool none = tile_begin >= tile_end || e->n_entries == 0 || e->n_kept == 0;
+    if (!none && capacity && !d_edges) { set_error("join: d_edges is NULL"); return KSP_E_ARG; }
+    KSP_HIP(hipSetDevice(e->device));
     e->jst = ksp_stats{};
     e->st.last_tiles = 0; e->st.last_pairs = 0; e->st.last_edges = 0; e->st.last_stream_bytes = 0; e->st.ms_join = 0;
-    if (tile_begin >= tile_end || e->n_entries == 0 || e->n_kept == 0) return KSP_OK;
-    if (capacity && !d_edges) { set_error("join: d_edges is NULL"); return KSP_E_ARG; }
+    if (none) return KSP_OK;
     int rc;
     if ((rc = e->count.ensure(64))) return rc;
     JoinArgs a;
@@ -2527,6 +2553,7 @@ int ksp_engine_join_launch(ksp_engine* e, uint64_t tile_begin, uint64_t tile_end
         e->jst.last_stream_bytes = bytes;
     }
     e->join_cap = capacity;
+    e->join_st = st;
     e->join_pending = true;
     return KSP_OK;
 }
@@ -2542,7 +2569,7 @@ int ksp_engine_join_wait(ksp_engine* e, uint64_t* h_count) {
         volatile unsigned long long* f = reinterpret_cast<volatile unsigned long long*>(e->h_count + 6);
         for (unsigned long long spins = 1; *f != e->join_seq; ++spins) {
             if ((spins & 0xFFFFF) == 0) {   // (now and then: is the stream still alive?)
-                const hipError_t q = hipStreamQuery(e->rb_stream);
+                const hipError_t q = hipStreamQuery(e->join_st);
                 if (q == hipSuccess && *f != e->join_seq) KSP_HIP(hipErrorUnknown);
                 if (q != hipErrorNotReady && q != hipSuccess) KSP_HIP(q);
             }
@@ -2593,6 +2620,7 @@ int ksp_engine_join_to_host(ksp_engine* e, uint64_t tile_begin, uint64_t tile_en
     if (!e || !h_count) { set_error("join_to_host: NULL argument"); return KSP_E_ARG; }
     *h_count = 0;
     if (!e->built) { set_error("join: build_blocks has not been run"); return KSP_E_ARG; }
+    if (join_still_pending(e, "join_to_host")) return KSP_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     KSP_HIP(hipSetDevice(e->device));
     const u64 T = ksp_engine_num_tiles(e);
@@ -2686,7 +2714,10 @@ int ksp_engine_join_to_host(ksp_engine* e, uint64_t tile_begin, uint64_t tile_en
 int ksp_engine_step_launch(ksp_engine* e, const uint64_t* d_keys, const uint32_t* d_weights, const uint64_t* h_offsets, uint32_t n_sources,
                            int key_bits, uint32_t part, uint32_t nparts, ksp_edge* d_edges, uint64_t capacity, uint64_t range[2],
                            uint64_t* bound, uint64_t* prev_count, int* prev_status, float* prev_ms_join, void* stream) {
-    if (!range || !bound || !prev_count || !prev_status || nparts == 0 || part >= nparts) { set_error("step_launch: bad argument"); return KSP_E_ARG; }
+    if (!range || !bound || !prev_count || !prev_status || nparts == 0 || part >= nparts || (capacity && !d_edges)) {
+        set_error("step_launch: bad argument");
+        return KSP_E_ARG;
+    }
     *prev_count = 0;
     *prev_status = KSP_OK;
     if (prev_ms_join) *prev_ms_join = 0;

@@ -61,6 +61,15 @@ class KspError(RuntimeError):
         self.code = code
 
 
+class PrevJoinError(KspError):
+    """Engine.step_launch: the join of the previous step failed (``code`` is its status), but this call's step went
+    ahead all the same — ``step`` is the (t0, t1, bound, launched, prev_count) that step_launch would have returned."""
+
+    def __init__(self, code, msg, step):
+        super().__init__(code, msg)
+        self.step = step
+
+
 _lib = None
 
 
@@ -336,10 +345,12 @@ class Engine:
                                              h_offsets.ctypes.data, h_offsets.size - 1, key_bits, stream or None))
 
     def step_launch(self, d_keys_ptr: int, h_offsets: np.ndarray, part: int, nparts: int, d_edges_ptr: int, capacity: int,
-                    stream: int = 0):
+                    stream: int = 0, d_weights_ptr: int = 0, key_bits: int = 0):
         """build_blocks + this rank's tile range + join_launch on it in one call (include/kspider_amd.h).  Returns
         (t0, t1, bound, launched, prev_count); launched False: the bound does not fit `capacity`, call join_launch(t0, t1, ...);
-        prev_count: the count of the join that was pending on this engine (None: there was none)."""
+        prev_count: the count of the join that was pending on this engine (None: there was none).
+        If that join failed (KSP_E_OVERFLOW: its buffer was too small), PrevJoinError carries its status and, in .step, this
+        call's return value: the new step was built (and launched) all the same."""
         h_offsets = np.ascontiguousarray(h_offsets, dtype=np.uint64)
         self._off = h_offsets
         L = lib()
@@ -351,16 +362,24 @@ class Engine:
         prev = ctypes.c_uint64(0)
         prev_rc = ctypes.c_int(0)
         prev_ms = ctypes.c_float(0)
-        had = bool(self._join_in_flight) if hasattr(self, "_join_in_flight") else False
-        rc = L.ksp_engine_step_launch(self._h, d_keys_ptr or None, None, h_offsets.ctypes.data, h_offsets.size - 1, 0, part, nparts,
-                                      d_edges_ptr or None, capacity, rng, ctypes.byref(bound), ctypes.byref(prev), ctypes.byref(prev_rc),
-                                      ctypes.byref(prev_ms), stream or None)
+        had = bool(getattr(self, "_join_in_flight", False))
+        rc = L.ksp_engine_step_launch(self._h, d_keys_ptr or None, d_weights_ptr or None, h_offsets.ctypes.data, h_offsets.size - 1,
+                                      key_bits, part, nparts, d_edges_ptr or None, capacity, rng, ctypes.byref(bound), ctypes.byref(prev),
+                                      ctypes.byref(prev_rc), ctypes.byref(prev_ms), stream or None)
+        # the engine's state first: KSP_OK / KSP_E_OVERFLOW built this step (and collected the previous join), KSP_OK launched
+        # its join; KSP_E_ARG / KSP_E_LIMIT refused the call before anything changed (a pending join stays pending)
+        if rc in (KSP_OK, KSP_E_OVERFLOW):
+            self._join_in_flight = rc == KSP_OK
+        elif rc not in (KSP_E_ARG, KSP_E_LIMIT):
+            self._join_in_flight = False
         self.prev_ms_join = float(prev_ms.value)
-        _check(prev_rc.value)
-        self._join_in_flight = rc == KSP_OK
-        if rc != KSP_E_OVERFLOW:
+        if rc not in (KSP_OK, KSP_E_OVERFLOW):
             _check(rc)
-        return int(rng[0]), int(rng[1]), int(bound.value), rc == KSP_OK, (int(prev.value) if had else None)
+        step = (int(rng[0]), int(rng[1]), int(bound.value), rc == KSP_OK, (int(prev.value) if had else None))
+        if prev_rc.value != KSP_OK:
+            raise PrevJoinError(prev_rc.value, f"the previous step's join failed with status {prev_rc.value} "
+                                "(KSP_E_OVERFLOW: its edge buffer was too small); this step went ahead: see .step", step)
+        return step
 
     def build_postings(self, h_key_off: np.ndarray, d_sources_ptr: int, d_key_weights_ptr: int, n_sources: int,
                        stream: int = 0):
