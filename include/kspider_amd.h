@@ -317,6 +317,39 @@ int ksp_edges_ani(int device, const ksp_edge* d_edges, uint64_t n_edges, const u
 int ksp_components_edges_ani(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
                              int ksize, double cutoff, uint32_t* h_label);
 
+/* ---- export (`kSpider export`) ----------------------------------------------------------------------
+ * kspider_export: what `kSpider export -i PREFIX -d DIST [--newick] [-o OUT]` writes (pykSpider/kSpider2/ks_export.py):
+ *   reads PREFIX.namesMap, PREFIX_kSpider_seqToKmersNo.tsv (must parse; values unused) and PREFIX_kSpider_pairwise.tsv
+ *   (dist_type "ani": also PREFIX_kSpider_pairwise.ani_col.tsv, line for line), dist_type "min_cont" 3, "avg_cont" 4,
+ *   "max_cont" 5 (NULL / "") or "ani", and writes
+ *     OUT_pairwise.tsv   "grp1\tgrp2\t<dist>" ("source1\tsource2\tani"), then both names and repr() of the value per row;
+ *     OUT_distmat.tsv    pandas' to_csv(sep='\t') of the N x N matrix over the names that occur (sorted): cell (a, b) =
+ *                        (b, a) = 1 - value, the fill 0 printed "0.0" in a column with a non-NaN value and "0" in a column
+ *                        whose values are all NaN (pandas' int64 downcast); a NaN value is the fill;
+ *     OUT.newick         (newick != 0) scipy's linkage(M, 'single') of that matrix as read_csv reads it back (Euclidean
+ *                        distances between ROWS) ON THE GPU, printed as the reference's get_newick prints to_tree.
+ *   out_prefix NULL / "": kSpider_<basename(PREFIX)>_pairwise.tsv, ..._distmat.tsv, kSpider_<basename>.newick in the
+ *   current directory.  Every file goes through OUT....partial and a rename; on any error none is left behind.
+ *   Refused up front (before any file is written, unlike the reference, which writes two files and then raises):
+ *   KSP_E_ARG for an unknown distance, a row id missing from .namesMap (ids are matched by their text, as the reference's
+ *   dict does: '01' is not '1'), a repeated unordered pair or a self pair, and with newick fewer than 2 nodes, a
+ *   non-finite 1 - value or a non-finite distance between two rows (scipy refuses it; found on the device, still
+ *   before any file is written); KSP_E_LIMIT with newick above 65 536 nodes or when the two
+ *   N x N double matrices do not fit the device's free memory.  Device = $KSPIDER_DEVICE (default 0).
+ * ksp_single_linkage_rows: the device part alone.  d_rows: an n x n row-major double matrix in DEVICE memory (not
+ *   changed); h_Z receives (n - 1) x 4 doubles equal to scipy.cluster.hierarchy.linkage(rows, 'single') bit for bit for
+ *   any finite matrix.  KSP_E_ARG when a distance between two rows is not finite (a cell of 1e200 squares to inf), as
+ *   scipy refuses it.  KSP_E_LIMIT above n = 65 536 (checked first) or when the n x n distance matrix does not fit.
+ * ksp_single_linkage_prim: the same computation, but h_prim receives Prim's (n - 1) x 4 rows (x, y, height, m) in the
+ *   order scipy's mst_single_linkage finds them, before the sort and the relabel: x is the node merged last (scipy's
+ *   Z[k, 0]), m the merged node whose row set D[y], so that height = distance(m, y) exactly (tests check every edge).
+ * ksp_csv_float: host only — the text of one cell as pandas' read_csv parses it (precise_xstrtod, not correctly
+ *   rounded; "inf", "-inf", "nan" too).  KSP_E_ARG when the text is not a number.                                     */
+int kspider_export(const char* index_prefix, const char* dist_type, int newick, const char* out_prefix);
+int ksp_single_linkage_rows(int device, uint32_t n, const double* d_rows, double* h_Z);
+int ksp_single_linkage_prim(int device, uint32_t n, const double* d_rows, double* h_prim);
+int ksp_csv_float(const char* text, double* out);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "kspider_cluster", "ksp_components", "ksp_components_edges", "kspider_pairwise_and_cluster",
     "kspider_estimate_ani", "kspider_pairwise_ani", "kspider_pairwise_ani_and_cluster", "ksp_edges_ani",
     "ksp_components_edges_ani", "ksp_ani_value", "ksp_ani_values", "ksp_format_ani",
+    "kspider_export", "ksp_single_linkage_rows", "ksp_single_linkage_prim", "ksp_csv_float",
 ]
 
 
@@ -150,6 +151,10 @@ def lib():
         L.ksp_ani_value.argtypes = [ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
         L.ksp_ani_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
         L.ksp_format_ani.argtypes = [ctypes.c_double, ctypes.c_char_p]
+        L.kspider_export.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p]
+        L.ksp_single_linkage_rows.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_single_linkage_prim.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_csv_float.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double)]
         _lib = L
     return _lib
 
@@ -295,6 +300,37 @@ def format_ani(v: float) -> str:
     buf = ctypes.create_string_buffer(32)
     n = lib().ksp_format_ani(float(v), buf)
     return buf.raw[:n].decode()
+
+
+def export(index_prefix: str, dist_type: str = "max_cont", newick: bool = False, out_prefix: str | None = None) -> None:
+    """`kSpider export -i PREFIX -d DIST [--newick] [-o OUT]` (ks_export.py): the named pairwise TSV, the N x N distance
+    matrix and, with newick, the single-linkage tree computed on the GPU.  out_prefix None: the reference's names
+    (kSpider_<basename>_...) in the current directory."""
+    _check(lib().kspider_export(os.fsencode(index_prefix), dist_type.encode(), int(bool(newick)),
+                                os.fsencode(out_prefix) if out_prefix else None))
+
+
+def single_linkage_rows(d_rows_ptr: int, n: int, device: int = 0) -> np.ndarray:
+    """scipy.cluster.hierarchy.linkage(rows, 'single') of the n x n row-major float64 matrix at DEVICE pointer d_rows_ptr,
+    bit for bit: an (n - 1) x 4 float64 array."""
+    Z = np.empty((max(int(n) - 1, 0), 4), dtype=np.float64)
+    _check(lib().ksp_single_linkage_rows(int(device), int(n), d_rows_ptr or None, Z.ctypes.data if Z.size else None))
+    return Z
+
+
+def single_linkage_prim(d_rows_ptr: int, n: int, device: int = 0) -> np.ndarray:
+    """Prim's (x, y, height, m) rows of single_linkage_rows in the order they are found (before the sort and relabel):
+    x the node merged last, m the merged node nearest to y (height = distance(m, y))."""
+    P = np.empty((max(int(n) - 1, 0), 4), dtype=np.float64)
+    _check(lib().ksp_single_linkage_prim(int(device), int(n), d_rows_ptr or None, P.ctypes.data if P.size else None))
+    return P
+
+
+def csv_float(text: str) -> float:
+    """The value pandas' read_csv makes of one cell's text (its default, not correctly rounded, parser)."""
+    out = ctypes.c_double()
+    _check(lib().ksp_csv_float(text.encode(), ctypes.byref(out)))
+    return out.value
 
 
 def components(n_nodes: int, a: np.ndarray, b: np.ndarray, device: int = 0) -> np.ndarray:
