@@ -571,10 +571,11 @@ __global__ __launch_bounds__(HB_THREADS, 6) void k_bucket_group(const u64* __res
     __shared__ u32 tcnt2[HB_SLOTS / 2 + 1];   // entries per key, two 16-bit counters per word
     __shared__ unsigned short eslot[HB_CAP];
     __shared__ u32 wpart[NWV];
-    // after the inserts the keys are dead and their storage holds, per slot, the first place of the key's
-    // entries | its rank << 16, and the fill cursor
+    // after the inserts the keys are dead and their storage holds, per slot, one cursor word: the first place of the
+    // key's entries (bits 0..15) | entries placed so far (bits 16..30) | kept (bit 31).  One atomic per entry then
+    // gives the entry its place, its first-ness and whether it is kept — the placement used to take three random LDS
+    // accesses per entry (the count, a separate fill cursor, the offset)
     u32* toff = (u32*)tkey;
-    u32* tfill = toff + (HB_SLOTS + 1);
     constexpr unsigned long long EMPTY = ~0ull;
     constexpr u32 EPT = HB_CAP / NT;
     constexpr u32 PER = (HB_SLOTS + 1 + NT - 1) / NT;
@@ -665,7 +666,7 @@ __global__ __launch_bounds__(HB_THREADS, 6) void k_bucket_group(const u64* __res
 #pragma unroll
         for (u32 j = 0; j < PER; ++j) {
             const u32 sl = tid * per + j;
-            if (j < per && sl <= slots) { toff[sl] = run; tfill[sl] = 0; }
+            if (j < per && sl <= slots) toff[sl] = (run & 0xFFFFu) | (cnt[j] >= 2 ? 1u << 31 : 0u);
             if (cnt[j] >= 2) run += cnt[j] | (1u << 16);
         }
         __syncthreads();
@@ -678,12 +679,10 @@ __global__ __launch_bounds__(HB_THREADS, 6) void k_bucket_group(const u64* __res
             const u32 i = tid + j * NT;
             if (i >= size) break;
             const u32 sl = eslot[i];
+            // (places < 2^16 and at most HB_CAP entries per key: neither half carries into the next field)
+            const u32 t = atomicAdd(&toff[sl], 0x10001u);
             u32 r = 0;
-            if (((tcnt2[sl >> 1] >> (16 * (sl & 1))) & 0xFFFFu) >= 2) {
-                const u32 fill = atomicAdd(&tfill[sl], 1u);
-                const u32 t = toff[sl];
-                r = HB_KEPT | (fill == 0 ? HB_FIRST : 0u) | ((t & 0xFFFFu) + fill);
-            }
+            if (t >> 31) r = HB_KEPT | ((t & 0x7FFF0000u) == 0 ? HB_FIRST : 0u) | (t & 0xFFFFu);
             rec[b0 + i] = (unsigned short)r;
         }
 #ifdef KSP_FKTIME
