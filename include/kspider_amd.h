@@ -74,7 +74,8 @@ typedef struct ksp_stats {
     uint64_t n_kept_keys;       /* distinct keys among them                                                */
     int stage1_kind;            /* middle of stage 1: 1 bucket-resident (grouping + emit + labels in one kernel, group
                                    records straight to rank order: fused_kernels.hip.h), 0 pass by pass      */
-    int reserved_;
+    int big_buckets;            /* buckets of more than 3 072 entries (HB_CAP) the last build's hash grouping passed to
+                                   k_bucket_big; 0 on paths that do not group buckets                       */
 } ksp_stats;
 
 const char* ksp_last_error(void);

@@ -145,6 +145,7 @@ struct ksp_engine {
                                   // sparse sharing that wants match records): the pass-by-pass kernels from now on
     bool fused_flags = false;     // the tile flags and the diagonal work of this build were written with the block lists (k_fms_place, k_fkeys)
     int fused_used = 0;           // (stats) the last build took the bucket-resident path
+    u32 big_buckets = 0;          // (stats) buckets above HB_CAP entries the last build handed to k_bucket_big
     bool have_rank_pairs = false; // gp holds (block, rank) of every list word in rank order (key-by-key build)
     bool have_dwork = false;      // ... and dwork the diagonal work / holder sums (k_move_groups)
     ksp::Buf gp, gm, ms_hist;     // group records of the key-by-key build; parked masks; per-chunk block counts of the split (k_ms_*)
@@ -696,6 +697,7 @@ static int build_impl(ksp_engine* e, const u64* d_keys, const u32* d_w, hipStrea
     const u32 N = e->n_sources, nb = e->nb;
     const u64 lmax = n + (u64)nb * (WIN + 4) + 4 * WIN;   // upper bound of the padded layout (+ read slack)
     int rc;
+    e->big_buckets = 0;   // (stats: set below once k_bucket_group's counts are read back; a build handed on starts over)
     if ((rc = e->KA.ensure((n + 4) * 8))) return rc;
     if ((rc = e->KB.ensure((n + 4) * 8))) return rc;
     if ((rc = e->VA.ensure((n + 4) * sizeof(V)))) return rc;
@@ -1339,6 +1341,7 @@ static int build_impl(ksp_engine* e, const u64* d_keys, const u32* d_w, hipStrea
             while (bits < 64 && (e->max_key >> bits)) ++bits;
             e->key_bits = bits;
         }
+        e->big_buckets = (u32)(e->h_scal[9] >> 32);   // (d_hovf[1]: the oversize buckets k_bucket_group listed)
         if ((u32)e->h_scal[9]) {   // a bucket did not fit (skewed keys): this engine sorts from now on
             e->hash_off = true;
             return build_impl<V>(e, d_keys, d_w, st, phase);
@@ -1973,6 +1976,7 @@ static int build_common(ksp_engine* e, const uint64_t* d_keys, const uint32_t* d
     e->st.partition_kind = e->sort_entries ? e->part_kind : 0;
     e->st.partition_fallback = e->part_fail;
     e->st.stage1_kind = e->fused_used;
+    e->st.big_buckets = (int)e->big_buckets;
     if (e->sort_entries && e->time_sort) KSP_HIP(hipEventElapsedTime(&e->st.ms_sort, e->ev[4], e->ev[5]));
     return KSP_OK;
 }
