@@ -4,6 +4,7 @@
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py ... --dump-outputs DIR   (also writes the edges of the last timed step: see dump_outputs)
+    python bench.py ... --full               (also the figures that take runs of their own: see below)
 
 One "step" = one pass of the hot path (what src/pairwise.cpp:194-237 does on the CPU) over one batch of
 synthetic sketches that already sit in HBM as sorted uint64 runs:
@@ -25,14 +26,19 @@ slices), tiles are sharded by estimated work, the edges are gathered to rank 0.
 value = whole-job source pairs per second = [S(S-1)/2] * K / t, t = max over ranks of the wall time of K
 steps bracketed by barrier + torch.cuda.synchronize().
 
-The JSON line also carries (N = 1):
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; nothing else.  The
+JSON line also carries:
   roofline       HBM roofline of the whole step: the bytes the step MUST move (SURVEY 8d "compulsory":
                  8 * sum(n) read once + 16 bytes per non-zero pair written) / step time / 8 TB/s — a fraction
-                 <= 1 — plus the dominant kernel group and, per kernel group of stage 1 + the join, HIP-event
-                 time, modelled bytes and (when profiles/traffic.json was measured on the same kernels) PMC bytes
+                 <= 1; with --full (N = 1) also the dominant kernel group and, per kernel group of stage 1 + the
+                 join, HIP-event time, modelled bytes and (when profiles/traffic.json was measured on the same
+                 kernels) PMC bytes, from a phase pass of --profile-steps extra steps after the clock
   naive_pairwise the pairwise-merge-equivalent rate A/t (SURVEY 8d's per-pair bytes; exceeds the HBM peak by
                  design: the engine never reads a sketch once per source pair) — NOT a roofline
-  cpu_baseline   the reference algorithm (oracle port) on the host cores, 1 thread and all cores
+With --full (N = 1) it also runs and reports, after the timed steps:
+  cpu_baseline   the reference algorithm (oracle port) on the host cores, 1 thread and all cores, on --cpu-sample
+                 sources; its 1-thread edges are compared with the last timed step's (verified_against_cpu_baseline)
+  dropin_s       the `pairwise PREFIX T` exe end to end on index files of that sample, next to the restated reference
   other_configs  one timed step each of C3 / C4 / C5 at full size (build + join + D2H into pinned memory)
 """
 from __future__ import annotations
@@ -345,10 +351,14 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: sources = N(config) * sqrt(gpus); strong: the config's own size on every GPU count")
     ap.add_argument("--n-sources", type=int, default=0, help="override the source count (debug)")
-    ap.add_argument("--cpu-sample", type=int, default=10000, help="sources in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the phase pass, the CPU baseline and the other configs (N = 1)")
+    ap.add_argument("--cpu-sample", type=int, default=10000,
+                    help="sources in the CPU-baseline sample (--full, N = 1; 0 = skip)")
     ap.add_argument("--other-configs", default="C3,C4,C5",
-                    help="full-size configs timed once each after the main measurement (N = 1 only; '' = skip)")
-    ap.add_argument("--profile-steps", type=int, default=5, help="extra steps with per-phase events (N = 1; 0 = skip)")
+                    help="full-size configs timed once each after the main measurement (--full, N = 1; '' = skip)")
+    ap.add_argument("--profile-steps", type=int, default=5,
+                    help="extra steps with per-phase events (--full, N = 1; 0 = skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="write the edges of the last timed step to DIR/<field>.npy (float64, rows ordered, <= 64 MB)")
     args = ap.parse_args()
@@ -552,7 +562,7 @@ def main():
         # ---- per kernel group: HIP events at the phase starts of a few extra, untimed steps ----------------
         groups = []
         tag_b = 2 if n <= 65536 and not os.environ.get("KSP_TAG32") else 4
-        if world == 1 and args.profile_steps > 0:
+        if args.full and world == 1 and args.profile_steps > 0:
             eng.set_profiling(True)
             acc, joins = {}, 0.0
             order = []
@@ -605,11 +615,20 @@ def main():
                                "model_GBps": (mb / (ms * 1e-3) / 1e9) if (mb and ms > 0) else None,
                                "counter_bytes": cb,
                                "frac_of_hbm": ((cb or mb) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if ((cb or mb) and ms > 0) else None})
-        dominant = max(groups, key=lambda g: g["ms"]) if groups else {"group": "stage 1", "ms": ms_build}
+        dominant = (max(groups, key=lambda g: g["ms"]) if groups
+                    else {"group": "stage 1", "ms": ms_build} if ms_build > 0 else None)
         step_traffic = None
         if groups and all(g["counter_bytes"] is not None for g in groups):
             step_traffic = int(sum(g["counter_bytes"] for g in groups))
         naive = naive_pairwise_bytes(sk.sizes, n)
+        stage_ms = {"build_blocks": ms_build, "of which partition": ms_part, "join": ms_join}
+        if stage_from_phase_pass:
+            stage_ms["measured_in"] = ("the phase pass after the timed steps (one timing event per phase start: ~0.05 ms of "
+                                       "bubbles per step that the timed steps, which carry no events, do not have)")
+        else:
+            stage_ms["other (gather, D2H, sync, host)"] = ms_step - ms_build - ms_join
+            if ms_build == 0.0:
+                stage_ms["measured_in"] = "not split: the timed steps carry no timing events (--full adds a phase pass)"
         out = {
             "metric": "sketch-pairs/sec (NxN containment)", "value": total_pairs * args.steps / elapsed,
             "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -631,7 +650,8 @@ def main():
                                           else "on the one GPU") + "; RCCL p2p gather of the edges to rank 0")},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": step_traffic,
-                         "kernel": f"whole step; dominant kernel group: {dominant['group']} ({dominant['ms']:.3f} ms)",
+                         "kernel": (f"whole step; dominant kernel group: {dominant['group']} ({dominant['ms']:.3f} ms)"
+                                    if dominant else "whole step (per kernel group: the phase pass of --full)"),
                          "bytes_per_step": compulsory,
                          "note": "compulsory traffic of one step (SURVEY 8d): 8 B x every hash read once + 16 B x every "
                                  "non-zero pair written once, / ms_per_step / n_gpus; `traffic` = PMC bytes per step summed "
@@ -641,16 +661,11 @@ def main():
                                "x_hbm_peak": naive / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS / world,
                                "note": "SURVEY 8(d) per-pair bytes 8(n_a+n_b)+4 over all pairs / step time: what a "
                                        "pair-by-pair merge would have to stream; not a roofline of this engine"},
-            "stage_ms": ({"build_blocks": ms_build, "of which partition": ms_part, "join": ms_join,
-                          "measured_in": "the phase pass after the timed steps (one timing event per phase start: ~0.05 ms of "
-                                         "bubbles per step that the timed steps, which carry no events, do not have)"}
-                         if stage_from_phase_pass else
-                         {"build_blocks": ms_build, "of which partition": ms_part, "join": ms_join,
-                          "other (gather, D2H, sync, host)": ms_step - ms_build - ms_join}),
+            "stage_ms": stage_ms,
         }
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             try:
                 out["cpu_baseline"] = cpu_baseline(sk, args.cpu_sample, final_edges)
                 out["config"]["verified_against_cpu_baseline"] = out["cpu_baseline"].pop("edges_equal_gpu")
@@ -658,7 +673,7 @@ def main():
             except Exception as ex:  # the baseline must never take the bench line down
                 out["cpu_baseline"] = {"value": None, "unit": "pairs/s", "cores": 0, "kind": "port",
                                        "sample": f"failed: {ex}"}
-        if world == 1 and args.other_configs and not args.n_sources:
+        if args.full and world == 1 and args.other_configs and not args.n_sources:
             del keys_d
             others = []
             for cfg in [c for c in args.other_configs.split(",") if c and c != args.config]:

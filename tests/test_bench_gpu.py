@@ -1,5 +1,5 @@
-"""bench.py on the GPU box: the 1-rank line is well-formed, --dump-outputs writes the edge set the line's
-checksum describes, and a 2-rank run (both ranks on the one card, gloo for the exchange — the box has a single
+"""bench.py on the GPU box: the 1-rank --full line is well-formed, --dump-outputs writes the edge set the line's
+checksum describes, a plain run does nothing but its timed steps (no phase pass, no CPU baseline), and a 2-rank run (both ranks on the one card, gloo for the exchange — the box has a single
 GPU, RCCL needs one device per rank) gathers exactly the edge set of the 1-rank run: tile-range sharding +
 gather on real engine output."""
 import json
@@ -26,7 +26,8 @@ def _run(cmd, env):
 def test_bench_line_and_two_rank_equivalence(tmp_path):
     common = ["--steps", "2", "--warmup", "1", "--n-sources", "1500", "--cpu-sample", "0"]
     dump = str(tmp_path / "outputs")
-    one = _run([sys.executable, "bench.py", "--gpus", "1"] + common + ["--dump-outputs", dump], {"KSP_BENCH_CHECKSUM": "1"})
+    one = _run([sys.executable, "bench.py", "--gpus", "1", "--full"] + common + ["--dump-outputs", dump],
+               {"KSP_BENCH_CHECKSUM": "1"})
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in one
@@ -55,3 +56,21 @@ def test_bench_line_and_two_rank_equivalence(tmp_path):
     assert two["n_gpus"] == 2
     assert two["config"]["nonzero_pairs"] == one["config"]["nonzero_pairs"] > 1000
     assert two["config"]["checksum"] == one["config"]["checksum"] != 0
+
+
+def test_bench_plain_line(tmp_path):
+    """Without --full: the headline fields and --dump-outputs as in a --full run, but no phase pass, no CPU baseline
+    (its sample size left at the default) and no other configs."""
+    dump = str(tmp_path / "outputs")
+    line = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--n-sources", "1500",
+                 "--dump-outputs", dump], {})
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "config", "roofline"):
+        assert k in line
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 2
+    assert line["roofline"]["groups"] == [] and 0 < line["roofline"]["frac"] <= 1
+    assert not {"cpu_baseline", "dropin_s", "other_configs"} & set(line)
+    assert line["config"]["verified_against_cpu_baseline"] is None
+    assert line["dump_outputs"]["rows"] == line["config"]["nonzero_pairs"] > 1000
+    u = {k: np.load(os.path.join(dump, k + ".npy")).astype(np.uint64) for k in ("source_1", "source_2", "shared")}
+    x = (u["source_1"] << np.uint64(40)) + (u["source_2"] << np.uint64(20)) + u["shared"]
+    assert int(x.sum(dtype=np.uint64)) == line["config"]["checksum"] != 0

@@ -5,7 +5,7 @@ O=gpurun_out/p_$TAG; mkdir -p $O
 i=0
 for envs in "$@"; do
   i=$((i+1))
-  env $envs timeout -k 10 200 python bench.py --steps 20 --warmup 5 --cpu-sample 0 --other-configs= > $O/bench_$i.json 2> $O/bench_$i.err || { tail -c 300 $O/bench_$i.err; }
+  env $envs timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --other-configs= > $O/bench_$i.json 2> $O/bench_$i.err || { tail -c 300 $O/bench_$i.err; }
   python - <<EOF
 import json
 d=json.load(open("$O/bench_$i.json"))
