@@ -344,11 +344,17 @@ int ksp_components_edges_ani(int device, uint32_t n_nodes, const ksp_edge* d_edg
  * ksp_single_linkage_prim: the same computation, but h_prim receives Prim's (n - 1) x 4 rows (x, y, height, m) in the
  *   order scipy's mst_single_linkage finds them, before the sort and the relabel: x is the node merged last (scipy's
  *   Z[k, 0]), m the merged node whose row set D[y], so that height = distance(m, y) exactly (tests check every edge).
+ * ksp_row_distances: a test entry — h_dist (host memory) receives the n x n row-major matrix of distances between the
+ *   rows of d_rows that both entries above compute on the device and Prim reads (scipy's pdist(rows) in square form, bit
+ *   for bit), launched by the same code.  The checks and their order are theirs: KSP_E_LIMIT above n = 65 536 (before
+ *   any device call), KSP_E_ARG for n < 2 or a NULL pointer, KSP_E_LIMIT when the matrix does not fit the device's free
+ *   memory, KSP_E_ARG when a distance is not finite.
  * ksp_csv_float: host only — the text of one cell as pandas' read_csv parses it (precise_xstrtod, not correctly
  *   rounded; "inf", "-inf", "nan" too).  KSP_E_ARG when the text is not a number.                                     */
 int kspider_export(const char* index_prefix, const char* dist_type, int newick, const char* out_prefix);
 int ksp_single_linkage_rows(int device, uint32_t n, const double* d_rows, double* h_Z);
 int ksp_single_linkage_prim(int device, uint32_t n, const double* d_rows, double* h_prim);
+int ksp_row_distances(int device, uint32_t n, const double* d_rows, double* h_dist);
 int ksp_csv_float(const char* text, double* out);
 
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------

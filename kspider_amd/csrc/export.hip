@@ -256,6 +256,18 @@ bool relabel(u32 n, const std::vector<double>& prim, double* Z) {
     return true;
 }
 
+// k_row_dist + k_dist_sqrt: the n x n distances between the rows of d_rows into d_dist (device memory of the current
+// device), *d_not_finite = 1 when one is not finite.  The export's linkage and ksp_row_distances both launch them here.
+hipError_t launch_row_distances(u32 n, const double* d_rows, double* d_dist, u32* d_not_finite) {
+    const u64 nn = (u64)n * n;
+    const u32 nb = (n + kTile - 1) / kTile;
+    hipLaunchKernelGGL(k_row_dist, dim3(nb, nb), dim3(256), 0, nullptr, d_rows, n, d_dist);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(k_dist_sqrt, dim3((unsigned)std::min<u64>((nn + 255) / 256, 8192)), dim3(256), 0, nullptr, d_dist, nn, d_not_finite);
+    return hipGetLastError();
+}
+
 // linkage of the n x n row matrix d_rows (device memory of the current device) into h_Z and / or Prim's (x, y, height)
 // rows before the sort, each with the merged node nearest to y, into h_prim ((n - 1) x 4; either may be NULL); d_rows is
 // not changed.  KSP_E_ARG when a distance is not finite.
@@ -277,11 +289,7 @@ int single_linkage_on_device(u32 n, const double* d_rows, double* h_Z, double* h
     if (!use_lds) EX_HIP(hipMalloc((void**)&d_D, (u64)n * sizeof(double)));
     if (h_prim) EX_HIP(hipMalloc((void**)&d_near, (u64)n * sizeof(u32)));
     {
-        const u32 nb = (n + kTile - 1) / kTile;
-        hipLaunchKernelGGL(k_row_dist, dim3(nb, nb), dim3(256), 0, nullptr, d_rows, n, d_dist);
-        EX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_dist_sqrt, dim3((unsigned)std::min<u64>((nn + 255) / 256, 8192)), dim3(256), 0, nullptr, d_dist, nn, d_flags);
-        EX_HIP(hipGetLastError());
+        EX_HIP(launch_row_distances(n, d_rows, d_dist, d_flags));
         EX_HIP(hipMemcpy(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost));
         if (ph) ph->mark("k_row_dist+sqrt");
         if (flags[0]) {
@@ -852,9 +860,11 @@ extern "C" int ksp_csv_float(const char* text, double* out) {
 }
 
 namespace {
-int linkage_entry(const char* who, int device, uint32_t n, const double* d_rows, double* h_Z, double* h_prim) {
+// the checks of the device entry points, in this order, then run() on the selected device
+template <class F>
+int linkage_entry(const char* who, int device, uint32_t n, const double* d_rows, bool has_output, F&& run) {
     if (n > kMaxNodes) { ksp::set_error(std::string(who) + ": n above the limit of 65536"); return KSP_E_LIMIT; }
-    if (n < 2 || !d_rows || (!h_Z && !h_prim)) { ksp::set_error(std::string(who) + ": n < 2 or NULL argument"); return KSP_E_ARG; }
+    if (n < 2 || !d_rows || !has_output) { ksp::set_error(std::string(who) + ": n < 2 or NULL argument"); return KSP_E_ARG; }
     if (int rc = select_device(device, who)) return rc;
     u64 fr = 0;
     if (!bytes_fit((u64)n * n * sizeof(double) + ((u64)n * 4 + 64) * sizeof(double), &fr)) {
@@ -862,20 +872,49 @@ int linkage_entry(const char* who, int device, uint32_t n, const double* d_rows,
         return KSP_E_LIMIT;
     }
     try {
-        return single_linkage_on_device(n, d_rows, h_Z, h_prim, nullptr);
+        return run();
     } catch (const std::bad_alloc&) {
         ksp::set_error(std::string(who) + ": out of host memory");
         return KSP_E_LIMIT;
     }
 }
+
+int row_distances_on_device(u32 n, const double* d_rows, double* h_dist) {
+    int rc = KSP_OK;
+    double* d_dist = nullptr;
+    u32* d_flag = nullptr;
+    u32 flag = 0;
+    EX_HIP(hipMalloc((void**)&d_dist, (u64)n * n * sizeof(double)));
+    EX_HIP(hipMalloc((void**)&d_flag, sizeof flag));
+    EX_HIP(hipMemsetAsync(d_flag, 0, sizeof flag, nullptr));
+    EX_HIP(launch_row_distances(n, d_rows, d_dist, d_flag));
+    EX_HIP(hipMemcpy(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost));
+    if (flag) {
+        ksp::set_error("row distances: a distance between two rows is not finite (scipy's linkage refuses it)");
+        rc = KSP_E_ARG;
+        goto done;
+    }
+    EX_HIP(hipMemcpy(h_dist, d_dist, (u64)n * n * sizeof(double), hipMemcpyDeviceToHost));
+done:
+    if (d_dist) (void)hipFree(d_dist);
+    if (d_flag) (void)hipFree(d_flag);
+    return rc;
+}
 }  // namespace
 
 extern "C" int ksp_single_linkage_rows(int device, uint32_t n, const double* d_rows, double* h_Z) {
-    return linkage_entry("ksp_single_linkage_rows", device, n, d_rows, h_Z, nullptr);
+    return linkage_entry("ksp_single_linkage_rows", device, n, d_rows, h_Z != nullptr,
+                         [&] { return single_linkage_on_device(n, d_rows, h_Z, nullptr, nullptr); });
 }
 
 extern "C" int ksp_single_linkage_prim(int device, uint32_t n, const double* d_rows, double* h_prim) {
-    return linkage_entry("ksp_single_linkage_prim", device, n, d_rows, nullptr, h_prim);
+    return linkage_entry("ksp_single_linkage_prim", device, n, d_rows, h_prim != nullptr,
+                         [&] { return single_linkage_on_device(n, d_rows, nullptr, h_prim, nullptr); });
+}
+
+extern "C" int ksp_row_distances(int device, uint32_t n, const double* d_rows, double* h_dist) {
+    return linkage_entry("ksp_row_distances", device, n, d_rows, h_dist != nullptr,
+                         [&] { return row_distances_on_device(n, d_rows, h_dist); });
 }
 
 extern "C" int kspider_export(const char* index_prefix, const char* dist_type, int newick, const char* out_prefix) {

@@ -34,7 +34,8 @@ ABI_SYMBOLS = [
     "kspider_cluster", "ksp_components", "ksp_components_edges", "kspider_pairwise_and_cluster",
     "kspider_estimate_ani", "kspider_pairwise_ani", "kspider_pairwise_ani_and_cluster", "ksp_edges_ani",
     "ksp_components_edges_ani", "ksp_ani_value", "ksp_ani_values", "ksp_format_ani",
-    "kspider_export", "ksp_single_linkage_rows", "ksp_single_linkage_prim", "ksp_csv_float",
+    "kspider_export", "ksp_single_linkage_rows", "ksp_single_linkage_prim", "ksp_row_distances",
+    "ksp_csv_float",
 ]
 
 
@@ -154,6 +155,7 @@ def lib():
         L.kspider_export.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p]
         L.ksp_single_linkage_rows.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
         L.ksp_single_linkage_prim.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_row_distances.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
         L.ksp_csv_float.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double)]
         _lib = L
     return _lib
@@ -324,6 +326,14 @@ def single_linkage_prim(d_rows_ptr: int, n: int, device: int = 0) -> np.ndarray:
     P = np.empty((max(int(n) - 1, 0), 4), dtype=np.float64)
     _check(lib().ksp_single_linkage_prim(int(device), int(n), d_rows_ptr or None, P.ctypes.data if P.size else None))
     return P
+
+
+def row_distances(d_rows_ptr: int, n: int, device: int = 0) -> np.ndarray:
+    """(tests) The n x n float64 matrix of distances between the rows of the n x n row-major float64 matrix at DEVICE
+    pointer d_rows_ptr, as the device computes it for the two linkage entries above: scipy's pdist in square form."""
+    S = np.empty((max(int(n), 0), max(int(n), 0)), dtype=np.float64)
+    _check(lib().ksp_row_distances(int(device), int(n), d_rows_ptr or None, S.ctypes.data if S.size else None))
+    return S
 
 
 def csv_float(text: str) -> float:

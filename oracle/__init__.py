@@ -31,7 +31,7 @@ EDGE_DTYPE = np.dtype([("source_1", "<u4"), ("source_2", "<u4"), ("shared", "<u8
 
 def build(force: bool = False) -> str:
     so = os.path.join(_HERE, "liboracle.so")
-    srcs = [os.path.join(_HERE, f) for f in ("ref_pairwise.cpp", "ref_index.cpp", "oracle.h")]
+    srcs = [os.path.join(_HERE, f) for f in ("ref_pairwise.cpp", "ref_index.cpp", "ref_linkage.cpp", "oracle.h")]
     stale = force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-C", _HERE, "liboracle.so"], stdout=subprocess.DEVNULL)
@@ -246,3 +246,18 @@ def key_rows(key_off: np.ndarray, holders: np.ndarray, weights, n_sources: int, 
                                        _p(w, ctypes.c_uint32) if w is not None else None, ctypes.c_uint32(n_sources),
                                        ctypes.c_int(_threads(threads)), _p(rows, ctypes.c_uint64), ctypes.byref(total)))
     return rows[:n_sources], total.value
+
+
+def row_pdist(M: np.ndarray, threads: int | None = None) -> np.ndarray:
+    """scipy's pdist(M, 'euclidean') in square form for a square float64 M whose rows are contiguous (a leading block
+    M[:n, :n] of a larger C-ordered matrix is fine): per pair the sequential, unfused sum over the nonzero columns of
+    either row (ref_linkage.cpp), bit for bit what tests/export_restate.py's row_pdist computes."""
+    n = M.shape[0]
+    if M.dtype != np.float64 or M.ndim != 2 or M.shape[1] != n or M.strides[1] != 8 or M.strides[0] % 8:
+        raise ValueError("row_pdist: a square float64 matrix with contiguous rows")
+    out = np.empty((n, n))
+    rc = lib().oracle_row_pdist(ctypes.c_void_p(M.ctypes.data), ctypes.c_uint64(M.strides[0] // 8), ctypes.c_uint32(n),
+                                ctypes.c_void_p(out.ctypes.data), ctypes.c_int(min(16, _threads(threads))))
+    if rc:
+        raise ValueError("row_pdist: bad argument")
+    return out

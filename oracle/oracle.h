@@ -49,6 +49,11 @@ int oracle_build_colors(const uint64_t* keys, const uint64_t* offsets, uint32_t 
                         uint32_t** color_w, uint32_t* n_colors);
 void oracle_free(void* p);
 
+/* scipy's pdist(M, 'euclidean') between the rows of the leading n x n block of the row-major matrix M (leading
+ * dimension ld >= n), in square form into out (n x n): per pair the sequential, unfused sum over the columns in
+ * ascending order, then sqrt (ref_linkage.cpp).  threads >= 1 host threads.  Nonzero on a bad argument. */
+int oracle_row_pdist(const double* M, uint64_t ld, uint32_t n, double* out, int threads);
+
 /* Write the three .bin files + .namesMap in the (restated) phmap dump layout. */
 int oracle_write_index(const char* index_prefix, const uint32_t* color_off, const uint32_t* sources,
                        const uint32_t* color_w, uint32_t n_colors, const uint32_t* group_ids,

@@ -176,9 +176,12 @@ def relabel(rows, n):
     size = [1] * n + [0] * (n - 1)
 
     def find(x):
-        while parent[x] != x:
-            x = parent[x]
-        return x
+        r = x
+        while parent[r] != r:
+            r = parent[r]
+        while parent[x] != r:          # path compression: a chain of n merges stays O(n), not O(n^2)
+            parent[x], x = r, parent[x]
+        return r
 
     Z = np.empty((n - 1, 4))
     for i in range(n - 1):

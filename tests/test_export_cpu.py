@@ -220,6 +220,36 @@ def test_linkage_limit_is_checked_first():
     rc = engine.lib().ksp_single_linkage_rows(0, 65537, None, None)
     assert rc == engine.KSP_E_LIMIT and b"65536" in engine.lib().ksp_last_error()
     assert engine.lib().ksp_single_linkage_rows(0, 1, None, None) == engine.KSP_E_ARG
+    L, host = engine.lib(), np.zeros(4)   # ksp_row_distances: the same checks, in the same order, before any device call
+    assert L.ksp_row_distances(0, 65537, None, None) == engine.KSP_E_LIMIT and b"65536" in L.ksp_last_error()
+    assert L.ksp_row_distances(0, 1, host.ctypes.data, host.ctypes.data) == engine.KSP_E_ARG
+    assert L.ksp_row_distances(0, 2, None, host.ctypes.data) == engine.KSP_E_ARG
+    assert L.ksp_row_distances(0, 2, host.ctypes.data, None) == engine.KSP_E_ARG
+
+
+@pytest.mark.parametrize("n", [2, 3, 63, 64, 65, 127, 128, 129, 1000, 2500])
+def test_oracle_row_distances_equal_the_restatement(n, oracle_lib):
+    """oracle.row_pdist (the sparse column merge the size tests use as their reference) == export_restate.row_pdist bit
+    for bit, on export-like cells, duplicated rows, signed and tie-heavy values, and a leading block of a wider matrix."""
+    rng = np.random.default_rng(n)
+    density = min(1.0, 24 / n)    # (about 24 nonzeros per row, as in the size tests: keeps the restatement quick)
+    keep = np.triu(rng.random((n, n)) < density, 1)
+    M = np.zeros((n, n))
+    M[keep] = [er.xstrtod(repr(1 - float("%.6g" % c))) for c in rng.random(int(keep.sum()))]
+    M = M + M.T
+    if n >= 4:
+        M[n // 2] = M[1]
+        M[:, n // 2] = M[:, 1]
+    wide = np.where(rng.random((n + 3, n + 3)) < density, rng.random((n + 3, n + 3)), 0.0)
+    mats = {"export-like": M, "zeros": np.zeros((n, n)), "leading block": wide[:n, :n]}
+    if n <= 1000:
+        mats["signed"] = np.where(rng.random((n, n)) < density, rng.normal(size=(n, n)), 0.0)
+    if n <= 129:
+        mats["tie-heavy"] = _tie_heavy(rng, n)
+    for what, A in mats.items():
+        got = oracle_lib.row_pdist(A)
+        want = er.row_pdist(np.ascontiguousarray(A))
+        assert (got.view(np.uint64) == want.view(np.uint64)).all(), what
 
 
 def test_iterative_newick_is_not_depth_limited():

@@ -146,7 +146,10 @@ def test_c2_size_export(oracle_lib, capfd):
     """C2: 10 000 sources, of which 9 984 occur in the 447 298 rows of its pairwise TSV.  The tree is well formed, every
     node is a leaf exactly once, no branch length is negative.  On the matrix as read_csv reads it back, every one of the
     N - 1 Prim edges the device finds weighs exactly the host's sequential distance of its pair, and sorting and
-    relabelling those rows gives the device's linkage matrix.  The wall time and the phases are reported."""
+    relabelling those rows gives the device's linkage matrix.  The device's distance matrix (the one Prim reads) equals
+    the host's sequential distance on 2 * 10^4 random pairs and on every row of k_row_dist's last 64-row tile against
+    256 random rows, and Prim replayed on it gives the device's rows: the minimum was taken at every step.  The wall
+    time and the phases are reported."""
     pd = pytest.importorskip("pandas")
     with tempfile.TemporaryDirectory() as d:
         prefix = _index(oracle_lib, d, 10000, None)
@@ -176,6 +179,7 @@ def test_c2_size_export(oracle_lib, capfd):
         Z = engine.single_linkage_rows(buf.ptr.value, n)
         t_link = time.perf_counter() - t1
         P = engine.single_linkage_prim(buf.ptr.value, n)
+        S = engine.row_distances(buf.ptr.value, n)
     finally:
         buf.free()
     assert (np.diff(Z[:, 2]) >= 0).all() and Z[-1, 3] == n
@@ -187,8 +191,14 @@ def test_c2_size_export(oracle_lib, capfd):
     got = _seq_dist(M, m, y)                            # every one of the N - 1 edge weights, exactly
     assert (got.view(np.uint64) == P[:, 2].view(np.uint64)).all()
     assert (er.relabel(P[:, :3], n).view(np.uint64) == Z.view(np.uint64)).all()
+    assert (P.view(np.uint64) == er.prim_rows(S, nearest=True).view(np.uint64)).all()   # the minimum at every step
+    rng = np.random.default_rng(n)
+    tile = np.arange((n - 1) // 64 * 64, n)             # k_row_dist's last 64-row tile (partly filled unless 64 | n)
+    a = np.concatenate([rng.integers(0, n, 20000), np.repeat(tile, 256)])
+    b = np.concatenate([rng.integers(0, n, 20000), rng.integers(0, n, 256 * len(tile))])
+    assert (_seq_dist(M, a, b).view(np.uint64) == S[a, b].view(np.uint64)).all()
     print(f"\nC2 export --newick, {n} nodes, {n_rows} rows: {wall:.1f} s wall ({phases}); "
-          f"linkage of the read-back matrix {t_link:.2f} s; all {n - 1} Prim edge weights checked")
+          f"linkage of the read-back matrix {t_link:.2f} s; all {n - 1} Prim edge weights and steps checked")
 
 
 def _overflowing():
@@ -198,11 +208,11 @@ def _overflowing():
 
 @pytest.mark.parametrize("n", [2, 3, 200])
 def test_non_finite_distances_are_refused(n):
-    """scipy refuses a matrix whose row distances overflow; so do both device entry points (before Prim runs)."""
+    """scipy refuses a matrix whose row distances overflow; so do all three device entry points (before Prim runs)."""
     M = np.ascontiguousarray(_overflowing()[n])
     buf = engine.DeviceBuffer.from_numpy(M)
     try:
-        for f in (engine.single_linkage_rows, engine.single_linkage_prim):
+        for f in (engine.single_linkage_rows, engine.single_linkage_prim, engine.row_distances):
             with pytest.raises(engine.KspError) as ei:
                 f(buf.ptr.value, n)
             assert ei.value.code == engine.KSP_E_ARG and "not finite" in str(ei.value)
