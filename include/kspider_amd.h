@@ -175,10 +175,11 @@ int ksp_engine_build_postings(ksp_engine* e, const uint64_t* h_key_off, const ui
                               const uint32_t* d_key_weights, uint32_t n_keys, uint32_t n_sources, void* stream);
 /* One SLICE of such an index: any subset of its keys, every key with all its holders (same arguments, the offsets
  * starting at 0; fewer than 2^30 memberships per slice).  Stops at the source labels; from there the calls of a
- * key-range slice of sketches apply (ksp_engine_slice_labels, MIN over the slices, ksp_engine_slice_finish, _sizes,
- * _export, ksp_engine_assemble).  The reference loads an index of any size (src/pairwise.cpp:95-111): kspider_pairwise
- * cuts one of 2^30 memberships or more into such slices by itself, and with $KSPIDER_DEVICES every device builds the
- * slice of 1 / n of the colours.                                                                                  */
+ * key-range slice of sketches apply, plus the exchange of the counter bounds (ksp_engine_slice_labels, MIN over the
+ * slices, ksp_engine_slice_bounds, SUM over the slices, ksp_engine_slice_set_bounds, ksp_engine_slice_finish, _sizes,
+ * _export, ksp_engine_assemble).  The reference loads an index of any size (src/pairwise.cpp:95-111):
+ * kspider_pairwise cuts one of 2^30 memberships or more into such slices by itself, and with $KSPIDER_DEVICES every
+ * device builds the slice of 1 / n of the colours.                                                               */
 int ksp_engine_build_postings_slice(ksp_engine* e, const uint64_t* h_key_off, const uint32_t* d_sources,
                                     const uint32_t* d_key_weights, uint32_t n_keys, uint32_t n_sources, void* stream);
 
@@ -205,6 +206,14 @@ int ksp_engine_build_slice(ksp_engine* e, const uint64_t* d_keys, const uint32_t
                            uint32_t nparts, void* stream);
 int ksp_engine_slice_labels(ksp_engine* e, uint32_t* d_labels, void* stream);
 int ksp_engine_slice_finish(ksp_engine* e, const uint32_t* d_labels, void* stream);
+/* The bound of every source's pair counters as the slice knows it (n_sources uint32: number of keys / weight sum), and
+ * the combined bounds handed back before ksp_engine_slice_finish.  Slices of sketches report full bounds (every slice
+ * sees every source's whole run): the exchange is not needed.  Slices of an inverted index (ksp_engine_build_postings_slice)
+ * see their own keys only: the caller adds the slices' bounds up element by element (a SUM all-reduce) and sets the
+ * sums on every slice.  A slice of an index finished without them takes every source for one that needs 32-bit
+ * counters (correct, slower): one slice's share says nothing about the sums the assembled lists reach.        */
+int ksp_engine_slice_bounds(ksp_engine* e, uint32_t* d_bounds, void* stream);
+int ksp_engine_slice_set_bounds(ksp_engine* e, const uint32_t* d_bounds, void* stream);
 int ksp_engine_slice_sizes(const ksp_engine* e, uint64_t out[4]);
 int ksp_engine_slice_export(ksp_engine* e, uint32_t* d_brk, uint32_t* d_info, uint32_t* d_bw, uint32_t* d_blk_raw,
                             uint32_t* d_blk_pos, void* d_big, void* stream);

@@ -114,6 +114,7 @@ struct ksp_engine {
     const u32 *post_off = nullptr, *post_src = nullptr, *post_w = nullptr;   // postings input of the build in progress (device)
     u32 post_nkeys = 0;
     int slice_phase = 0;          // 1: build_slice done, waiting for ksp_engine_slice_finish
+    bool bounds_set = false;      // ... whose counter bounds were combined over the slices (ksp_engine_slice_set_bounds)
     bool post_slice = false;      // ... of a postings input (ksp_engine_build_postings_slice): post_off stays valid until the finish
     u64 slice_hdr[4] = {0, 0, 0, 0};   // padded length, distinct keys (U), big postings, block keys
     u32 ncell = ksp::NP;          // fine rank cells per block (power of two)
@@ -937,13 +938,21 @@ static int build_impl(ksp_engine* e, const u64* d_keys, const u32* d_w, hipStrea
     const V* tags_in = VA;
     u64 nw = n;
     int topbit = kbits;   // the bucket partition takes the bits just below this one
+    // equal shares of [0, largest key] (or of [0, 2^key_bits) when the caller fixed key_bits): part p holds the keys
+    // span * p / nparts <= key < span * (p + 1) / nparts
+    unsigned __int128 cut_lo = 0, cut_end = 1;
     if (e->nparts > 1) {
-        // equal shares of [0, largest key] (or of [0, 2^key_bits) when the caller fixed key_bits)
         const unsigned __int128 span = e->have_max_key ? (unsigned __int128)e->max_key + 1
                                        : kbits >= 64   ? ((unsigned __int128)1 << 64)
                                                        : ((unsigned __int128)1 << kbits);
-        const u64 lo = (u64)((span * e->part_id) / e->nparts);
-        const u64 hi = (u64)((span * (e->part_id + 1)) / e->nparts - 1);
+        cut_lo = (span * e->part_id) / e->nparts;
+        cut_end = (span * (e->part_id + 1)) / e->nparts;
+    }
+    if (cut_end == cut_lo) {
+        nw = 0;   // fewer keys in the span than parts: none belongs to this one (an empty slice, like any other)
+    } else if (e->nparts > 1) {
+        const u64 lo = (u64)cut_lo;
+        const u64 hi = (u64)(cut_end - 1);
         // a slice spans hi - lo: the bits below that width spread its keys evenly over the buckets (the bits
         // above take at most two values inside the slice; the buckets compare whole keys anyway)
         topbit = 1;
@@ -2070,6 +2079,7 @@ static int build_postings_common(ksp_engine* e, const uint64_t* h_key_off, const
         e->h_scal[4] = 0;
         KSP_HIP(hipEventElapsedTime(&e->st.ms_build, e->ev[0], e->ev[1]));
         e->post_slice = true;
+        e->bounds_set = false;
         e->slice_phase = 1;
         return KSP_OK;
     }
@@ -2093,9 +2103,11 @@ int ksp_engine_build_postings(ksp_engine* e, const uint64_t* h_key_off, const ui
     return build_postings_common(e, h_key_off, d_sources, d_key_weights, n_keys, n_sources, stream, false);
 }
 // One slice of an inverted index — any subset of its keys, every key with ALL its holders (so the pruning of stage 1 has
-// nothing to do and every slice's ranks are its own key order) — up to the source labels; then exactly the calls of a
-// key-range slice of sketches: ksp_engine_slice_labels, (MIN over the slices), ksp_engine_slice_finish, _sizes, _export,
-// ksp_engine_assemble.  This is how an index of 2^30 memberships or more goes through (slices built in turn or on several
+// nothing to do and every slice's ranks are its own key order) — up to the source labels; then the calls of a key-range
+// slice of sketches, plus the counter bounds, which a slice of an index knows for its own keys only:
+// ksp_engine_slice_labels, (MIN over the slices), ksp_engine_slice_bounds, (SUM over the slices),
+// ksp_engine_slice_set_bounds, ksp_engine_slice_finish, _sizes, _export, ksp_engine_assemble.  A slice finished without
+// the combined bounds takes 32-bit counters everywhere (correct, slower).  This is how an index of 2^30 memberships or more goes through (slices built in turn or on several
 // GPUs), and how the devices of $KSPIDER_DEVICES share stage 1 of the reference's own entry point.
 int ksp_engine_build_postings_slice(ksp_engine* e, const uint64_t* h_key_off, const uint32_t* d_sources,
                                     const uint32_t* d_key_weights, uint32_t n_keys, uint32_t n_sources, void* stream) {
@@ -2141,6 +2153,43 @@ int ksp_engine_slice_labels(ksp_engine* e, uint32_t* d_labels, void* stream) {
     return KSP_OK;
 }
 
+static u32* bound_array(ksp_engine* e) { return e->smap.as<u32>() + 5 * smap_stride(e); }   // [5] of the per-source maps
+
+// The bound of every source's pair counters as this slice knows it (n_sources uint32: k-mer count / weight sum).  A slice of
+// sketches sees every source's whole run and reports the full bound; a slice of an inverted index sees its own keys only:
+// the caller adds the slices' bounds up and hands the sums back (ksp_engine_slice_set_bounds) before ksp_engine_slice_finish,
+// or the 16-bit / 32-bit counter decision of the assembled lists is taken from one slice's share.
+int ksp_engine_slice_bounds(ksp_engine* e, uint32_t* d_bounds, void* stream) {
+    if (!e || !d_bounds) { set_error("slice_bounds: NULL argument"); return KSP_E_ARG; }
+    if (e->slice_phase != 1) { set_error("slice_bounds: build_slice has not been run"); return KSP_E_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    KSP_HIP(hipSetDevice(e->device));
+    if (e->n_entries == 0 || e->nb == 0) {   // nothing was built
+        if (e->n_sources) KSP_HIP(hipMemsetAsync(d_bounds, 0, (size_t)e->n_sources * 4, st));
+    } else {
+        KSP_HIP(hipMemcpyAsync(d_bounds, bound_array(e), (size_t)e->n_sources * 4, hipMemcpyDeviceToDevice, st));
+    }
+    KSP_HIP(hipStreamSynchronize(st));
+    return KSP_OK;
+}
+
+int ksp_engine_slice_set_bounds(ksp_engine* e, const uint32_t* d_bounds, void* stream) {
+    if (!e || !d_bounds) { set_error("slice_set_bounds: NULL argument"); return KSP_E_ARG; }
+    if (e->slice_phase != 1) { set_error("slice_set_bounds: build_slice has not been run"); return KSP_E_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    if (join_elsewhere(e, st, "slice_set_bounds")) return KSP_E_ARG;
+    KSP_HIP(hipSetDevice(e->device));
+    if (e->n_entries == 0 || e->nb == 0) return KSP_OK;
+    KSP_HIP(hipMemcpyAsync(bound_array(e), d_bounds, (size_t)e->n_sources * 4, hipMemcpyDeviceToDevice, st));
+    if (!e->reorder)   // (the identity order took the blocks' maxima at the build: raise them to the combined bounds)
+        hipLaunchKernelGGL(k_blk_bound, dim3(grid_for(e->n_sources, 256)), dim3(256), 0, st, bound_array(e),
+                           e->smap.as<u32>() + 4 * smap_stride(e), e->blk_max.as<u32>(), e->n_sources);
+    KSP_HIP(hipGetLastError());
+    KSP_HIP(hipStreamSynchronize(st));
+    e->bounds_set = true;
+    return KSP_OK;
+}
+
 int ksp_engine_slice_finish(ksp_engine* e, const uint32_t* d_labels, void* stream) {
     if (!e) { set_error("slice_finish: NULL argument"); return KSP_E_ARG; }
     if (e->slice_phase != 1) { set_error("slice_finish: build_slice has not been run"); return KSP_E_ARG; }
@@ -2153,6 +2202,15 @@ int ksp_engine_slice_finish(ksp_engine* e, const uint32_t* d_labels, void* strea
     KSP_HIP(resolve_build_ms(e));   // (the previous build's time, before its events are recorded again)
     KSP_HIP(hipEventRecord(e->ev[0], st));
     if (d_labels) KSP_HIP(hipMemcpyAsync(label_array(e), d_labels, (size_t)e->n_sources * 4, hipMemcpyDeviceToDevice, st));
+    if (e->post_slice && !e->bounds_set) {
+        // a slice of an index that was never told the bounds over all slices: its own share says nothing about the
+        // sums the assembled lists reach, so every source counts as one that needs 32-bit counters
+        hipLaunchKernelGGL(k_fill, dim3(grid_for(e->n_sources, 256)), dim3(256), 0, st, bound_array(e), 0xFFFFFFFFu, (u64)e->n_sources);
+        if (!e->reorder)
+            hipLaunchKernelGGL(k_blk_bound, dim3(grid_for(e->n_sources, 256)), dim3(256), 0, st, bound_array(e),
+                               e->smap.as<u32>() + 4 * smap_stride(e), e->blk_max.as<u32>(), e->n_sources);
+        KSP_HIP(hipGetLastError());
+    }
     rc = build_dispatch(e, nullptr, nullptr, st, 2);
     if (rc) return rc;
     KSP_HIP(hipMemcpyAsync(e->h_scal + 1, e->scalars.as<u64>() + 1, 64, hipMemcpyDeviceToHost, st));
@@ -2983,6 +3041,8 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
     FailBarrier bar(nd);   // (the failure decision is latched once per barrier generation: host_sync.h)
     std::vector<u32> lab_min;                 // MIN-combined labels (host)
     std::vector<std::vector<u32>> lab_dev((size_t)nd);
+    std::vector<u32> bnd_sum;                 // per-source counter bounds summed over postings slices (host)
+    std::vector<std::vector<u32>> bnd_dev((size_t)nd);
     std::vector<u64> all_sizes((size_t)nd * 4, 0);
     u64 total = 0;
     std::vector<u64> edge_off((size_t)nd + 1, 0);
@@ -3048,14 +3108,30 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
                     (rc = ksp_memcpy_d2h(lab_dev[(size_t)i].data(), D.labels.p, (u64)N * 4)))
                     fail(rc);
             }
+            // postings slices hold a share of every source's keys: the counters' bounds are the sums over the slices
+            if (!bar.failed_hint() && N && job.postings) {
+                bnd_dev[(size_t)i].resize(N);
+                if ((rc = ksp_engine_slice_bounds(D.e, D.labels.as<u32>(), nullptr)) ||
+                    (rc = ksp_memcpy_d2h(bnd_dev[(size_t)i].data(), D.labels.p, (u64)N * 4)))
+                    fail(rc);
+            }
             if (sync_point()) return;
             if (i == 0) {
                 lab_min = lab_dev[0];
                 for (int j = 1; j < nd; ++j)
                     for (u32 s = 0; s < N; ++s) lab_min[s] = std::min(lab_min[s], lab_dev[(size_t)j][s]);
+                if (job.postings && N) {
+                    bnd_sum.assign(N, 0);
+                    for (int j = 0; j < nd; ++j)
+                        for (u32 s = 0; s < N; ++s)
+                            bnd_sum[s] = (u32)std::min<u64>((u64)bnd_sum[s] + bnd_dev[(size_t)j][s], 0xFFFFFFFFull);
+                }
             }
             if (sync_point()) return;
-            if (N && ((rc = ksp_memcpy_h2d(D.labels.p, lab_min.data(), (u64)N * 4)) || (rc = ksp_engine_slice_finish(D.e, D.labels.as<u32>(), nullptr))))
+            if (N && job.postings &&
+                ((rc = ksp_memcpy_h2d(D.labels.p, bnd_sum.data(), (u64)N * 4)) || (rc = ksp_engine_slice_set_bounds(D.e, D.labels.as<u32>(), nullptr))))
+                fail(rc);
+            else if (N && ((rc = ksp_memcpy_h2d(D.labels.p, lab_min.data(), (u64)N * 4)) || (rc = ksp_engine_slice_finish(D.e, D.labels.as<u32>(), nullptr))))
                 fail(rc);
             else if (!N && (rc = ksp_engine_slice_finish(D.e, nullptr, nullptr)))
                 fail(rc);

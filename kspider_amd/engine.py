@@ -27,7 +27,8 @@ ABI_SYMBOLS = [
     "ksp_pairwise_host", "ksp_free", "kspider_pairwise", "ksp_index_info", "ksp_format_float",
     "kspider_pairwise_sigs", "kspider_pairwise_bins",
     "ksp_engine_build_slice", "ksp_engine_slice_sizes", "ksp_engine_slice_export", "ksp_engine_assemble",
-    "ksp_engine_edge_bound", "ksp_engine_slice_labels", "ksp_engine_slice_finish", "ksp_engine_balanced_cuts",
+    "ksp_engine_edge_bound", "ksp_engine_slice_labels", "ksp_engine_slice_finish",
+    "ksp_engine_slice_bounds", "ksp_engine_slice_set_bounds", "ksp_engine_balanced_cuts",
     "ksp_engine_build_postings", "ksp_engine_build_postings_slice", "ksp_pairwise_postings_host",
     "ksp_engine_set_profiling", "ksp_engine_phase_times",
     "ksp_pairwise_host_multi", "ksp_pairwise_postings_host_multi",
@@ -106,6 +107,8 @@ def lib():
                                              ctypes.c_void_p]
         L.ksp_engine_slice_sizes.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
         L.ksp_engine_slice_labels.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_engine_slice_bounds.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_engine_slice_set_bounds.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.ksp_engine_slice_finish.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.ksp_engine_slice_export.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 7
         L.ksp_engine_assemble.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
@@ -128,6 +131,7 @@ def lib():
                                                        ctypes.POINTER(Stats)]
         L.ksp_engine_build_postings.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+        L.ksp_engine_build_postings_slice.argtypes = L.ksp_engine_build_postings.argtypes
         L.ksp_pairwise_postings_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                  ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(Stats)]
@@ -435,6 +439,18 @@ class Engine:
         _check(lib().ksp_engine_build_postings(self._h, h_key_off.ctypes.data, d_sources_ptr or None,
                                                d_key_weights_ptr or None, h_key_off.size - 1, n_sources, stream or None))
 
+    def build_postings_slice(self, h_key_off: np.ndarray, d_sources_ptr: int, d_key_weights_ptr: int, n_sources: int,
+                             stream: int = 0):
+        """One slice of an inverted index (any subset of its keys, every key with all its holders; h_key_off from 0), up
+        to the source labels: then slice_labels (MIN over the slices), slice_bounds (SUM over the slices),
+        slice_set_bounds, slice_finish, slice_export, assemble.  Without set_bounds the slice takes 32-bit pair counters
+        everywhere: its own share of a source's keys / weights is no bound for the assembled lists."""
+        h_key_off = np.ascontiguousarray(h_key_off, dtype=np.uint64)
+        self._off = h_key_off
+        _check(lib().ksp_engine_build_postings_slice(self._h, h_key_off.ctypes.data, d_sources_ptr or None,
+                                                     d_key_weights_ptr or None, h_key_off.size - 1, n_sources,
+                                                     stream or None))
+
     # ---- key-range sharded stage 1 (multi-GPU) ------------------------------------------------
     def build_slice(self, d_keys_ptr: int, h_offsets: np.ndarray, part: int, nparts: int, d_weights_ptr: int = 0,
                     key_bits: int = 0, stream: int = 0):
@@ -447,6 +463,14 @@ class Engine:
     def slice_labels(self, d_labels: int, stream: int = 0):
         """Copy the slice's source labels (n_sources uint32) into a device buffer."""
         _check(lib().ksp_engine_slice_labels(self._h, d_labels, stream or None))
+
+    def slice_bounds(self, d_bounds: int, stream: int = 0):
+        """Copy the slice's per-source counter bounds (n_sources uint32: keys / weight sum) into a device buffer."""
+        _check(lib().ksp_engine_slice_bounds(self._h, d_bounds, stream or None))
+
+    def slice_set_bounds(self, d_bounds: int, stream: int = 0):
+        """The bounds summed over the slices of an inverted index, before slice_finish (include/kspider_amd.h)."""
+        _check(lib().ksp_engine_slice_set_bounds(self._h, d_bounds, stream or None))
 
     def slice_finish(self, d_labels: int = 0, stream: int = 0):
         """Second half of a slice build, in the source order given by the combined labels."""

@@ -445,6 +445,26 @@ def test_call_sequences_on_one_engine(pool, edges_buf, monkeypatch, seed):
     r.close()
 
 
+def test_slice_calls_without_a_slice_build_are_refused(pool, edges_buf):
+    """slice_labels / slice_bounds / slice_set_bounds / slice_finish on a fresh engine and after a whole build: KSP_E_ARG,
+    and the whole build stays joinable."""
+    inp = pool["n700"]
+    buf = engine.DeviceBuffer(max(4, inp.n_sources * 4))
+    e = engine.Engine(0)
+    try:
+        for built in (False, True):
+            if built:
+                inp.build(e)
+            for call in (e.slice_labels, e.slice_bounds, e.slice_set_bounds, e.slice_finish):
+                with pytest.raises(engine.KspError) as ei:
+                    call(buf.ptr.value)
+                assert ei.value.code == engine.KSP_E_ARG and "build_slice has not been run" in str(ei.value), call
+        assert _same(_full_join(e, inp, edges_buf), inp.ref)
+    finally:
+        buf.free()
+        e.close()
+
+
 # ---- refused calls, one by one (C1 / C2 of the engine's contract) --------------------------------------------------
 
 @pytest.mark.parametrize("kind", ["monotone", "first", "limit", "key_bits", "part"])

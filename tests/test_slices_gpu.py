@@ -5,58 +5,13 @@ import numpy as np
 import pytest
 
 from kspider_amd import engine, synth
+from slice_driver import sliced_edges
 
 pytestmark = pytest.mark.gpu
 
 
 def _sliced_edges(sk, nparts, weights=None):
-    dk = engine.DeviceBuffer.from_numpy(sk.keys)
-    dw = engine.DeviceBuffer.from_numpy(weights) if weights is not None else None
-    e = engine.Engine(0)
-    nb = None
-    # what the ranks' MIN all-reduce does: element-wise minimum of the slices' source labels
-    lab = engine.DeviceBuffer(sk.n_sources * 4)
-    labels = np.full(sk.n_sources, 0xFFFFFFFF, dtype=np.uint32)
-    for p in range(nparts):
-        e.build_slice(dk.ptr.value, sk.offsets, p, nparts, d_weights_ptr=dw.ptr.value if dw else 0)
-        e.slice_labels(lab.ptr.value)
-        nb = e.stats()["n_blocks"]   # (blocks of the build: may hold spare ones for cluster-aligned boundaries)
-        labels = np.minimum(labels, lab.to_numpy(np.uint32, sk.n_sources))
-    lab = engine.DeviceBuffer.from_numpy(labels)
-    sizes, parts = [], []
-    for p in range(nparts):
-        e.build_slice(dk.ptr.value, sk.offsets, p, nparts, d_weights_ptr=dw.ptr.value if dw else 0)
-        e.slice_finish(lab.ptr.value)
-        sz = e.slice_sizes()
-        L, nbig = int(sz[0]), int(sz[2])
-        bufs = dict(brk=engine.DeviceBuffer(max(4, L * 4)), info=engine.DeviceBuffer(max(4, L * 4)),
-                    bw=engine.DeviceBuffer(max(4, L * 4)), raw=engine.DeviceBuffer((nb + 1) * 4),
-                    pos=engine.DeviceBuffer((nb + 1) * 4), big=engine.DeviceBuffer(max(16, nbig * 16)))
-        e.slice_export(bufs["brk"].ptr.value, bufs["info"].ptr.value, bufs["bw"].ptr.value, bufs["raw"].ptr.value,
-                       bufs["pos"].ptr.value, bufs["big"].ptr.value)
-        host = {k: b.to_numpy(np.uint8, b.nbytes) for k, b in bufs.items()}
-        sizes.append(sz)
-        parts.append(host)
-    sizes = np.concatenate(sizes)
-    lstride = max(1, int(sizes[0::4].max()))
-    bigstride = max(1, int(sizes[2::4].max()))
-
-    def stack(key, row_bytes):
-        out = np.zeros((nparts, row_bytes), dtype=np.uint8)
-        for p, h in enumerate(parts):
-            n = min(row_bytes, h[key].size)
-            out[p, :n] = h[key][:n]
-        return engine.DeviceBuffer.from_numpy(out)
-
-    brk_all, info_all, bw_all = stack("brk", lstride * 4), stack("info", lstride * 4), stack("bw", lstride * 4)
-    raw_all, pos_all = stack("raw", (nb + 1) * 4), stack("pos", (nb + 1) * 4)
-    big_all = stack("big", bigstride * 16)
-    e.assemble(sizes, brk_all.ptr.value, info_all.ptr.value, bw_all.ptr.value, lstride, raw_all.ptr.value,
-               pos_all.ptr.value, big_all.ptr.value, bigstride)
-    cap = max(16, e.tile_pairs(0, e.num_tiles))
-    de = engine.DeviceBuffer(cap * 16)
-    cnt = e.join(0, e.num_tiles, de.ptr.value, cap)
-    return np.sort(de.to_numpy(engine.EDGE_DTYPE, cnt), order=["source_1", "source_2"]), sizes
+    return sliced_edges(sk, nparts, weights)[:2]
 
 
 @pytest.mark.parametrize("nparts", [1, 2, 3, 8])
