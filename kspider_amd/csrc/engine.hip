@@ -414,76 +414,205 @@ static hipError_t resolve_build_ms(ksp_engine* e) {
     return hipEventElapsedTime(&e->st.ms_build, e->ev[0], e->ev[1]);
 }
 
-// What the parts of a stage-1 build share: the engine's arrays under the names its passes use (build_impl fills it in).
+// what a step of stage 1 answers besides KSP_OK (go on with the next step) and the KSP_E_* codes; build_to_end takes them, its callers never see them
+constexpr int S1_DONE = -1;         // the build is complete, or nothing is left for it to do
+constexpr int S1_START_OVER = -2;   // a sticky engine flag was set (seg_off, part_off, fused_off, hash_off): again from the top, on the path that is left
+
+static inline int key_bits_of(const u64 mx) {
+    int bits = 1;
+    while (bits < 64 && (mx >> bits)) ++bits;
+    return bits;
+}
+// e->hb_slots: persistent workgroups of k_bucket_group — as many as fit on the device at once
+static int bucket_slots(ksp_engine* e) {
+    if (e->hb_slots) return KSP_OK;
+    int per_cu = 0, cus = 0;
+    KSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bucket_group, HB_THREADS, 0));
+    KSP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
+    e->hb_slots = (u32)std::max(1, per_cu * cus);
+    return KSP_OK;
+}
+// a rocPRIM call as the library wants it made: call(storage, bytes) with no storage asks for the size, e->tmp takes it, then the
+// run.  timed: the events of st.ms_sort around the run alone.
+template <class F>
+static int with_tmp(ksp_engine* e, hipStream_t st, F&& call, const bool timed = false) {
+    size_t tb = 0;
+    KSP_HIP(call(nullptr, tb));
+    if (const int rc = e->tmp.ensure(tb)) return rc;
+    if (timed) KSP_HIP(hipEventRecord(e->ev[4], st));
+    KSP_HIP(call(e->tmp.p, tb));
+    if (timed) KSP_HIP(hipEventRecord(e->ev[5], st));
+    return KSP_OK;
+}
+
+// How a build's entries reach their buckets (Stage1::plan_partition: host arithmetic only; zero_and_prep carves the arena).
+struct PartPlan {
+    u32 nb_hand = 0;   // buckets of the hand-written partition (any number up to 2^21; above 2^16: three levels; 0: not used)
+    // the segment partition (k_seg_bounds / k_seg_scatter): two levels, runs long enough to leave a dozen entries per
+    // (source, range) and no run so long that the one wave that streams it would be the launch
+    bool seg = false;
+    bool seg3 = false;   // three levels: level 1 is read off the sorted runs too (k_seg_mid)
+    int seg_pb2 = 0;
+    u32 seg_cap = 0, seg_nb1 = 0;
+    u64 nslots = 0;    // places of the partitioned entries (seg: fixed ranges per bucket, with gaps)
+    // the hand-written partition's arena: level 1 (`A`), and for more than 65 536 buckets a middle level (`M`) between it and
+    // the final scatter
+    int hp_pb2 = 0, hp_pbm = 0;
+    u32 hp_nb1 = 0, hp_nchunks = 0, hp_ngroups = 0;
+    size_t hp_words_a = 0, hp_words_m = 0, hp_zero_words = 0, hp_pages_a = 0, hp_pages_m = 0;
+    PartLists hp_a{}, hp_m{};
+    u32 *hp_gcnt = nullptr, *hp_gbase = nullptr, *hp_src = nullptr;
+};
+// page lists of one level for n entries; returns the words it takes in the arena (all zeroed per build)
+static size_t plan_lists(PartLists& pl, const u64 n, const u32 buckets, const u32 subs, size_t& pages) {
+    const u32 lists = buckets * subs;
+    pl.subs = subs;
+    pl.ptw = (u32)std::min<u64>(P1_PTW_MAX, 8 * (((n / lists) >> P1_PLOG) + 1) + 16);
+    const u64 per = n / subs;
+    pl.pool_pages = (u32)((per >> P1_PLOG) + (per >> (P1_PLOG + 3)) + buckets + 8);   // pages per sub-list class
+    pages = (size_t)pl.pool_pages * subs;
+    return (size_t)subs * P1_LINE + (size_t)lists * P1_LINE + (size_t)lists * pl.ptw + pages;
+}
+static void carve_lists(PartLists& pl, u32* base, const u32 buckets) {
+    const size_t lists = (size_t)buckets * pl.subs;
+    pl.pools = base;
+    pl.cursors = pl.pools + (size_t)pl.subs * P1_LINE;
+    pl.pt = pl.cursors + lists * P1_LINE;
+    pl.owner = pl.pt + lists * pl.ptw;
+}
+
+// One attempt at a stage-1 build: what its steps share, and the steps in the order build_impl calls them.
 template <class V>
 struct Stage1 {
-    ksp_engine* e;
-    hipStream_t st;
-    int phase;
-    u64 n;              // entries of this build
-    u32 N, nb;          // sources, blocks
-    u64* KA;
+    static constexpr bool W = std::is_same<V, u64>::value;   // weighted: 64-bit tags carry the key's weight
+    static constexpr unsigned bs = 256;
+    ksp_engine* const e;
+    const u64* const d_keys;
+    const u32* const d_w;
+    const hipStream_t st;
+    const int phase;
+    const u64 n;        // entries of this build
+    const u32 N, nb;    // sources, blocks
+    const bool reorder;
+    // the engine's arrays under the names the passes use (bind(): read again after an ensure() that may have moved one)
+    u64 *KA, *d_off;
     V *VA, *VB;
-    u64* scal;
+    u64* scal;          // [0] max key, [1] Ktot, [2] U, [3] padded length, [4] overflow, [5] fix count,
+                        // [6] kept entries, [7] big postings, [8] entries of the slice
     u32 *blk_raw, *blk_pos, *rank1, *crank;
-    u32 *label, *iota, *labs, *order, *newidx, *sbound, *sorted_src, *blk_src;   // the per-source maps (smap)
-    int bbits;          // bits of a block id
-    bool reorder, hand_zeroed;
-    u64 m;              // kept entries
+    // per-source maps (smap): label, iota, sorted labels, order (= engine index -> source id; ~0: a hole), newidx (source
+    // id -> engine index), bound of a source's pair counters, sources in (label, id) order
+    u32 *label, *iota, *labs, *order, *newidx, *sbound, *sorted_src;
+    u32* blk_src;       // (behind the per-block maxima: one staging copy for both)
+    int bbits = 1;      // bits of a block id
+    u32 label_max = 0;  // holders above which a key is ignored by the label pass
+    bool hand_zeroed = false;   // this build began with the hand-written partition's zeroing launch (the whole scalar block)
+    PartPlan pp;
+    // what the grouping reads (slice_range): the whole input, or the entries of this part's key range
+    const u64* keys_in = nullptr;
+    const V* tags_in = nullptr;
+    u64 nw = 0;
+    int topbit = 0;     // the bucket partition takes the bits just below this one
+    u32* first = nullptr;   // first kept entry of every rank
+    // the buckets (bucket_layout): KB is free until the grouping scans — per-entry records, then the bucket tables
+    int pb = 0;         // bits of a bucket id (0: no buckets, sort_and_prune)
+    u32 nbuckets = 0;
+    unsigned short* rec = nullptr;   // (16 bits per partitioned entry; the tables behind keep their place)
+    u64 *bsum = nullptr, *bbase = nullptr;
+    u32* bstart = nullptr;           // nbuckets + 1
+    BucketBounds bb{};   // where every bucket's entries lie (partition)
+    bool labels_queued = false;   // the label pass was queued before the grouping's counts were read back
+    bool order_queued = false;    // ... and the source order (label sort, block cuts, placement) together with it
+    u64 m;              // kept entries (phase 2: set by phase 1)
+
+    Stage1(ksp_engine* e_, const u64* keys, const u32* w, hipStream_t st_, int phase_)
+        : e(e_), d_keys(keys), d_w(w), st(st_), phase(phase_), n(e_->n_entries), N(e_->n_sources), nb(e_->nb), reorder(e_->reorder), m(e_->n_kept) {}
+    u32* d_ovf() const { return (u32*)(scal + 4); }    // set by k_fix_runs when a run is too long; checked at the end of the build
+    u32* d_hovf() const { return (u32*)(scal + 9); }   // the grouping's overflow word, its count of oversize buckets
+    void bind();
+    int setup(), from_postings();
+    void label_pass(const u32* firstp, u32 n_keys, u64 kept, const u64* scal_dev = nullptr, Rider rider = Rider{nullptr, nullptr, nullptr, 0, 0});
+    bool seg_runs_fit(u32 r1) const;
+    PartPlan plan_partition() const;
+    int zero_and_prep(), tags_and_sizes(), slice_range();
+    void bucket_layout();
+    int seg_tables(u32 r1);
+    int partition_segment(), partition_paged(), partition_library(), partition(), partition_outcome();
+    int fused_middle(), group_buckets(), sort_and_prune(), kept_and_labels();
+    void shrink_cells_and_index(u64 K);
+    int source_order(), lists_by_key(bool& done), lists_by_sort();
 };
-// the names of a Stage1 as locals (the bodies below were written inside build_impl)
-#define KSP_STAGE1_LOCALS(c)                                                                                             \
-    constexpr bool W = std::is_same<V, u64>::value;                                                                      \
-    ksp_engine* const e = (c).e;                                                                                         \
-    const hipStream_t st = (c).st;                                                                                       \
-    const int phase = (c).phase;                                                                                         \
-    const u64 n = (c).n, m = (c).m;                                                                                      \
-    const u32 N = (c).N, nb = (c).nb;                                                                                    \
-    const unsigned bs = 256;                                                                                             \
-    u64* const KA = (c).KA;                                                                                              \
-    V *const VA = (c).VA, *const VB = (c).VB;                                                                            \
-    u64* const scal = (c).scal;                                                                                          \
-    u32 *const blk_raw = (c).blk_raw, *const blk_pos = (c).blk_pos, *const rank1 = (c).rank1, *const crank = (c).crank;   \
-    u32 *const label = (c).label, *const iota = (c).iota, *const labs = (c).labs, *const order = (c).order;              \
-    u32 *const newidx = (c).newidx, *const sbound = (c).sbound, *const sorted_src = (c).sorted_src, *const blk_src = (c).blk_src; \
-    const int bbits = (c).bbits;                                                                                         \
-    const bool reorder = (c).reorder, hand_zeroed = (c).hand_zeroed;                                                     \
-    int rc = KSP_OK;                                                                                                     \
-    size_t tb = 0;                                                                                                       \
-    (void)W; (void)phase; (void)n; (void)m; (void)N; (void)nb; (void)bs; (void)KA; (void)VA; (void)VB; (void)scal;       \
-    (void)blk_raw; (void)blk_pos; (void)rank1; (void)crank; (void)label; (void)iota; (void)labs; (void)order;            \
-    (void)newidx; (void)sbound; (void)sorted_src; (void)blk_src; (void)bbits; (void)reorder; (void)hand_zeroed;          \
-    (void)rc; (void)tb
+
+template <class V> void Stage1<V>::bind() {
+    KA = e->KA.as<u64>(), d_off = e->d_off.as<u64>(), scal = e->scalars.as<u64>();
+    VA = e->VA.as<V>(), VB = e->VB.as<V>();
+    blk_raw = e->blk_raw.as<u32>(), blk_pos = e->blk_pos.as<u32>(), rank1 = e->R1.as<u32>(), crank = e->crank.as<u32>();
+    const size_t NN = smap_stride(e);
+    u32* sm = e->smap.as<u32>();
+    label = sm, iota = sm + NN, labs = sm + 2 * NN, order = sm + 3 * NN, newidx = sm + 4 * NN, sbound = sm + 5 * NN, sorted_src = sm + 6 * NN;
+    blk_src = e->blk_max.as<u32>() + ((size_t)nb + 1);
+}
+
+// the arrays every build needs, sized for this one
+template <class V> int Stage1<V>::setup() {
+    const u64 lmax = n + (u64)nb * (WIN + 4) + 4 * WIN;   // upper bound of the padded layout (+ read slack)
+    e->big_buckets = 0;   // (stats: set once k_bucket_group's counts are read back; a build that starts over starts here)
+    const struct { Buf* b; size_t bytes; } need[] = {
+        {&e->KA, (n + 4) * 8}, {&e->KB, (n + 4) * 8}, {&e->VA, (n + 4) * sizeof(V)}, {&e->VB, (n + 4) * sizeof(V)},
+        {&e->bkeys, lmax * 4}, {&e->info, lmax * 4}, {&e->bw, W ? lmax * 4 : 0},
+        {&e->mm, (n / (INLINE_MAX + 1) + 16) * 16},   // 128-bit masks of big postings
+        {&e->blk_raw, ((size_t)nb + 2) * 4}, {&e->blk_pos, ((size_t)nb + 2) * 4}, {&e->part, ((size_t)nb + 1) * ((size_t)e->ncell + 1) * 4},
+        {&e->blk_max, (2 * (size_t)nb + 4) * 4}, {&e->scalars, 128}, {&e->R1, (n + 4) * 4}, {&e->crank, (n / CR_CHUNK + 4) * 4},
+        {&e->smap, 7 * smap_stride(e) * 4}};
+    for (const auto& a : need)
+        if (const int rc = a.b->ensure(a.bytes)) return rc;
+    bind();
+    while ((1u << bbits) < nb) ++bbits;
+    label_max = std::max<u32>(256, N / 16);
+    if (const char* lm = std::getenv("KSP_DEBUG_LABEL_MAX")) label_max = (u32)std::max(1, std::atoi(lm));
+    return KSP_OK;
+}
+
+// the label pass over the kept keys (firstp[] = where each key's entries start); KB is free whenever it runs
+template <class V> void Stage1<V>::label_pass(const u32* firstp, const u32 n_keys, const u64 kept, const u64* scal_dev, const Rider rider) {
+    const u32 skip = label_sampling(e, kept);
+    // labels on memory lines of their own while they are lowered — for source sets whose labels would otherwise share a
+    // few hundred lines (10 000 sources: 98 -> 39 us).  A large set spreads its atomics by itself, and 128 bytes per
+    // source turn every look at a label into a line of its own from HBM: 1 M sources, k_label 2.46 ms and 17 GB fetched
+    // (a quarter of that build) against a 4 MB table that stays in L2.
+    u32 spread_max = 262144;   // (100 000 sources: still 1 % faster spread; 1 M: 0.9 ms slower)
+    if (const char* sv = std::getenv("KSP_DEBUG_LABEL_SPREAD")) spread_max = (u32)std::atoi(sv);   // (timing experiments: sources up to which the labels are spread)
+    const int ls = N <= spread_max && e->KB.bytes >= (size_t)N * 128 ? 5 : 0;
+    u32* lab = ls ? (u32*)e->KB.p : label;
+    if (ls) hipLaunchKernelGGL(k_label_spread, dim3(grid_for(N, bs)), dim3(bs), 0, st, lab, ls, N);
+    hipLaunchKernelGGL((k_label<V>), dim3(grid_for(n_keys / (skip + 1) + 1, bs)), dim3(bs), 0, st, VA, firstp, lab, ls,
+                       skip, label_max, n_keys, scal_dev, rider);
+    if (ls) hipLaunchKernelGGL(k_label_gather, dim3(grid_for(N, bs)), dim3(bs), 0, st, lab, ls, label, N);
+}
 
 // the sources in (label, id) order: engine index of every source, block boundaries at cluster boundaries
-template <class V>
-static int stage1_source_order(const Stage1<V>& c) {
-    KSP_STAGE1_LOCALS(c);
-    if (reorder) {
-        // order the sources by (label, id) and move the kept entries to the new indices
-        int lbits = 1;
-        while (lbits < 32 && (N >> lbits)) ++lbits;
-        tb = 0;
-        u32* sort_out = e->padded ? sorted_src : order;
-        KSP_HIP(rocprim::radix_sort_pairs(nullptr, tb, label, labs, iota, sort_out, (size_t)N, 0, lbits, st));
-        if ((rc = e->tmp.ensure(tb))) return rc;
-        KSP_HIP(rocprim::radix_sort_pairs(e->tmp.p, tb, label, labs, iota, sort_out, (size_t)N, 0, lbits, st));
-        if (e->padded) {   // block boundaries at cluster boundaries where the spare slots allow
-            hipLaunchKernelGGL(k_pack_blocks, dim3(1), dim3(1024), 0, st, labs, N, nb, blk_src);
-            hipLaunchKernelGGL(k_place_sources, dim3(grid_for((u64)nb * TB, bs)), dim3(bs), 0, st, sorted_src, blk_src, newidx, order,
-                               sbound, e->blk_max.as<u32>(), nb);
-        } else {
-            hipLaunchKernelGGL(k_perm_bound, dim3(grid_for(N, bs)), dim3(bs), 0, st, order, newidx, sbound, e->blk_max.as<u32>(), N);
-        }
+template <class V> int Stage1<V>::source_order() {
+    if (!reorder) return KSP_OK;
+    // order the sources by (label, id) and move the kept entries to the new indices
+    int lbits = 1;
+    while (lbits < 32 && (N >> lbits)) ++lbits;
+    u32* sort_out = e->padded ? sorted_src : order;
+    if (const int rc = with_tmp(e, st, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, label, labs, iota, sort_out, (size_t)N, 0, lbits, st); })) return rc;
+    if (e->padded) {   // block boundaries at cluster boundaries where the spare slots allow
+        hipLaunchKernelGGL(k_pack_blocks, dim3(1), dim3(1024), 0, st, labs, N, nb, blk_src);
+        hipLaunchKernelGGL(k_place_sources, dim3(grid_for((u64)nb * TB, bs)), dim3(bs), 0, st, sorted_src, blk_src, newidx, order,
+                           sbound, e->blk_max.as<u32>(), nb);
+    } else {
+        hipLaunchKernelGGL(k_perm_bound, dim3(grid_for(N, bs)), dim3(bs), 0, st, order, newidx, sbound, e->blk_max.as<u32>(), N);
     }
     return KSP_OK;
 }
 
 // The block lists, key by key (k_key_groups ... k_ms_place / the library sort of the group records ... k_cidx).  done = false:
 // a key with thousands of holders in too many blocks — the caller takes the sort-by-block path (and the engine remembers).
-template <class V>
-static int stage1_lists_by_key(const Stage1<V>& c, bool& done) {
-    KSP_STAGE1_LOCALS(c);
+template <class V> int Stage1<V>::lists_by_key(bool& done) {
+    int rc;
+    size_t tb;
     done = false;
     // ---- the block lists, key by key (see k_key_groups) ------------------------------------------------
     if (!e->key_groups_off && m < (1ull << 32) - KG_CHUNK) {
@@ -609,16 +738,7 @@ static int stage1_lists_by_key(const Stage1<V>& c, bool& done) {
                 hipLaunchKernelGGL((k_place_groups<W>), dim3(grid_for(K, bs)), dim3(bs), 0, st, sblk, sval, blk_raw, blk_pos, wkey,
                                    e->bkeys.as<u32>(), e->info.as<u32>(), W ? e->bw.as<u32>() : nullptr, (u32)e->h_scal[1]);
             }
-            {   // the fine cell index was sized from the raw entries of a block; the lists are an order of magnitude shorter
-                // (pruned, one word per key and block): ~32 words of an average list x 4 per cell is as fine as the join
-                // ever looks (it merges cells up to ~216 keys anyway) — 16 x fewer bisections on C2 (32 -> 4 us)
-                const u64 avg = K / nb + 1;
-                u32 nc = NP;
-                while ((u64)nc * 32 < 4 * avg && nc < e->ncell) nc <<= 1;
-                e->ncell = std::min(e->ncell, nc);
-            }
-            hipLaunchKernelGGL(k_cidx, dim3(grid_for((u64)nb * (e->ncell + 1), bs)), dim3(bs), 0, st, e->bkeys.as<u32>(),
-                               blk_raw, blk_pos, scal, e->part.as<u32>(), nb, e->ncell);
+            shrink_cells_and_index(K);
             KSP_HIP(hipGetLastError());
             e->scal_fresh = phase == 0;   // (h_scal[1] .. [11] are this build's: build_common need not fetch them again)
             e->have_rank_pairs = true;   // rec_rank / rec_blk: (rank, block) of every list word in rank order
@@ -629,10 +749,9 @@ static int stage1_lists_by_key(const Stage1<V>& c, bool& done) {
     return KSP_OK;
 }
 
-// The block lists by sorting the kept entries by block (the fallback of stage1_lists_by_key, and inputs beyond its limits).
-template <class V>
-static int stage1_lists_by_sort(const Stage1<V>& c) {
-    KSP_STAGE1_LOCALS(c);
+// The block lists by sorting the kept entries by block (the fallback of lists_by_key, and inputs beyond its limits).
+template <class V> int Stage1<V>::lists_by_sort() {
+    int rc;
     // ---- the block lists by sorting the entries by block -------------------------------------------------
     if (!e->rank1_ok) {   // (the grouping wrote crank[] only: a rank per entry from first[])
         const u32* fp = (phase == 3 || e->post_slice) ? e->post_off : (const u32*)e->FK.p;
@@ -642,11 +761,8 @@ static int stage1_lists_by_sort(const Stage1<V>& c) {
     if (reorder) hipLaunchKernelGGL((k_retag<V>), dim3(grid_for(m / (16 / sizeof(V)) + 1, bs)), dim3(bs), 0, st, VA, newidx, m);
     // sort 2: stable by block id (bits [8, 8+bbits) of the tag), payload = rank:  VA,rank1 -> VB,rk2
     u32* rk2 = (u32*)KA;                   // KA (sorted keys) is dead from here on
-    tb = 0;
     const int bbeg = sizeof(V) == 2 ? 7 : 8;   // the block id inside a compact / canonical tag
-    KSP_HIP(rocprim::radix_sort_pairs(nullptr, tb, VA, VB, rank1, rk2, m, bbeg, bbeg + bbits, st));
-    if ((rc = e->tmp.ensure(tb))) return rc;
-    KSP_HIP(rocprim::radix_sort_pairs(e->tmp.p, tb, VA, VB, rank1, rk2, m, bbeg, bbeg + bbits, st));
+    if ((rc = with_tmp(e, st, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, VA, VB, rank1, rk2, m, bbeg, bbeg + bbits, st); }))) return rc;
     // now: rk2 = ranks sorted by (block, rank); VB = tags in the same order.  KB, VA, R1 are free.
     V* T = VB;
     u32* flag = (u32*)VA;
@@ -656,10 +772,7 @@ static int stage1_lists_by_sort(const Stage1<V>& c) {
     auto hf = rocprim::make_transform_iterator(rocprim::make_counting_iterator<u64>(0), head);
     {
         HeadScatterIt<V> out{{head, estart, grank, scal, m}, 0};
-        tb = 0;
-        KSP_HIP(rocprim::inclusive_scan(nullptr, tb, hf, out, m, rocprim::plus<u32>(), st));
-        if ((rc = e->tmp.ensure(tb))) return rc;
-        KSP_HIP(rocprim::inclusive_scan(e->tmp.p, tb, hf, out, m, rocprim::plus<u32>(), st));
+        if ((rc = with_tmp(e, st, [&](void* t, size_t& b) { return rocprim::inclusive_scan(t, b, hf, out, m, rocprim::plus<u32>(), st); }))) return rc;
     }
     // the number of distinct (block, key) groups sizes the posting passes (after the source reordering it is
     // an order of magnitude below the entry count: one 8-byte read-back pays for itself)
@@ -674,10 +787,7 @@ static int stage1_lists_by_sort(const Stage1<V>& c) {
     hipLaunchKernelGGL((k_emit_keys<V>), dim3(grid_for(K, bs)), dim3(bs), 0, st, grank, T, estart, blk_raw, blk_pos,
                        e->bkeys.as<u32>(), e->h_scal[1]);
     hipLaunchKernelGGL(k_bigflag, dim3(grid_for(K, bs)), dim3(bs), 0, st, estart, scal, mmsz, K);
-    tb = 0;
-    KSP_HIP(rocprim::exclusive_scan(nullptr, tb, mmsz, mmoff, (u32)0, K, rocprim::plus<u32>(), st));
-    if ((rc = e->tmp.ensure(tb))) return rc;
-    KSP_HIP(rocprim::exclusive_scan(e->tmp.p, tb, mmsz, mmoff, (u32)0, K, rocprim::plus<u32>(), st));
+    if ((rc = with_tmp(e, st, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, mmsz, mmoff, (u32)0, K, rocprim::plus<u32>(), st); }))) return rc;
     hipLaunchKernelGGL(k_nbig, dim3(1), dim3(64), 0, st, mmsz, mmoff, scal);
     hipLaunchKernelGGL((k_emit_info<V, W>), dim3(grid_for(K, bs)), dim3(bs), 0, st, estart, mmoff, scal, T,
                        blk_raw, blk_pos, e->info.as<u32>(), e->mm.as<uint4>(), W ? e->bw.as<u32>() : nullptr);
@@ -688,256 +798,171 @@ static int stage1_lists_by_sort(const Stage1<V>& c) {
     return KSP_OK;
 }
 
-template <class V>
-static int build_impl(ksp_engine* e, const u64* d_keys, const u32* d_w, hipStream_t st, const int phase) {
-    constexpr bool W = std::is_same<V, u64>::value;   // weighted: 64-bit tags carry the key's weight
-    // phase 0: the whole of stage 1;  1: up to the source labels (key-range slice, before the labels of all
-    // slices are combined);  2: the rest (source order from the final labels, block lists);  3: postings
-    // input (ksp_engine_build_postings: sorting and pruning are already done by the caller's inverted index)
-    const u64 n = e->n_entries;
-    const u32 N = e->n_sources, nb = e->nb;
-    const u64 lmax = n + (u64)nb * (WIN + 4) + 4 * WIN;   // upper bound of the padded layout (+ read slack)
-    int rc;
-    e->big_buckets = 0;   // (stats: set below once k_bucket_group's counts are read back; a build handed on starts over)
-    if ((rc = e->KA.ensure((n + 4) * 8))) return rc;
-    if ((rc = e->KB.ensure((n + 4) * 8))) return rc;
-    if ((rc = e->VA.ensure((n + 4) * sizeof(V)))) return rc;
-    if ((rc = e->VB.ensure((n + 4) * sizeof(V)))) return rc;
-    if ((rc = e->bkeys.ensure(lmax * 4))) return rc;
-    if ((rc = e->info.ensure(lmax * 4))) return rc;
-    if (W && (rc = e->bw.ensure(lmax * 4))) return rc;
-    if ((rc = e->mm.ensure((n / (INLINE_MAX + 1) + 16) * 16))) return rc;   // 128-bit masks of big postings
-    if ((rc = e->blk_raw.ensure(((size_t)nb + 2) * 4))) return rc;
-    if ((rc = e->blk_pos.ensure(((size_t)nb + 2) * 4))) return rc;
-    if ((rc = e->part.ensure(((size_t)nb + 1) * ((size_t)e->ncell + 1) * 4))) return rc;
-    if ((rc = e->blk_max.ensure((2 * (size_t)nb + 4) * 4))) return rc;
-    if ((rc = e->scalars.ensure(128))) return rc;
-    if ((rc = e->R1.ensure((n + 4) * 4))) return rc;
-
-    u64* KA = e->KA.as<u64>();
-    V* VA = e->VA.as<V>();
-    V* VB = e->VB.as<V>();
-    u64* d_off = e->d_off.as<u64>();
-    u64* scal = e->scalars.as<u64>();   // [0] max key, [1] Ktot, [2] U, [3] padded length, [4] overflow, [5] fix count,
-                                        // [6] kept entries, [7] big postings, [8] entries of the slice
-    u32* blk_raw = e->blk_raw.as<u32>();
-    u32* blk_pos = e->blk_pos.as<u32>();
-    const unsigned bs = 256;
-    u32* rank1 = e->R1.as<u32>();
-    if ((rc = e->crank.ensure((n / CR_CHUNK + 4) * 4))) return rc;
-    u32* crank = e->crank.as<u32>();
-    const size_t NN = smap_stride(e);
-    if ((rc = e->smap.ensure(7 * NN * 4))) return rc;
-    // per-source maps: [0] label, [1] iota, [2] sorted labels, [3] order (= engine index -> source id; ~0: a hole),
-    // [4] newidx (source id -> engine index), [5] bound of a source's pair counters, [6] sources in (label, id) order
-    u32* sm = e->smap.as<u32>();
-    u32 *label = sm, *iota = sm + NN, *labs = sm + 2 * NN, *order = sm + 3 * NN, *newidx = sm + 4 * NN, *sbound = sm + 5 * NN;
-    u32* sorted_src = sm + 6 * NN;
-    u32* blk_src = e->blk_max.as<u32>() + ((size_t)nb + 1);   // (behind the per-block maxima: one staging copy for both)
-    const bool reorder = e->reorder;
-    u32 label_max = std::max<u32>(256, N / 16);   // holders above which a key is ignored by the label pass
-    if (const char* lm = std::getenv("KSP_DEBUG_LABEL_MAX")) label_max = (u32)std::max(1, std::atoi(lm));
-    // the label pass over the kept keys (first[] = where each key's entries start); KB is free whenever it runs
-    auto run_label = [&](const u32* firstp, const u32 n_keys, const u64 kept, const u64* scal_dev = nullptr, const Rider rider = Rider{nullptr, nullptr, nullptr, 0, 0}) {
-        const u32 skip = label_sampling(e, kept);
-        // labels on memory lines of their own while they are lowered — for source sets whose labels would otherwise share a
-        // few hundred lines (10 000 sources: 98 -> 39 us).  A large set spreads its atomics by itself, and 128 bytes per
-        // source turn every look at a label into a line of its own from HBM: 1 M sources, k_label 2.46 ms and 17 GB fetched
-        // (a quarter of that build) against a 4 MB table that stays in L2.
-        u32 spread_max = 262144;   // (100 000 sources: still 1 % faster spread; 1 M: 0.9 ms slower)
-        if (const char* sv = std::getenv("KSP_DEBUG_LABEL_SPREAD")) spread_max = (u32)std::atoi(sv);   // (timing experiments: sources up to which the labels are spread)
-        const int ls = N <= spread_max && e->KB.bytes >= (size_t)N * 128 ? 5 : 0;
-        u32* lab = ls ? (u32*)e->KB.p : label;
-        if (ls) hipLaunchKernelGGL(k_label_spread, dim3(grid_for(N, bs)), dim3(bs), 0, st, lab, ls, N);
-        hipLaunchKernelGGL((k_label<V>), dim3(grid_for(n_keys / (skip + 1) + 1, bs)), dim3(bs), 0, st, VA, firstp, lab, ls,
-                           skip, label_max, n_keys, scal_dev, rider);
-        if (ls) hipLaunchKernelGGL(k_label_gather, dim3(grid_for(N, bs)), dim3(bs), 0, st, lab, ls, label, N);
-    };
-    bool hand_zeroed = false;   // this build began with the hand-written partition's zeroing launch (the whole scalar block)
-    int bbits = 1;
-    while ((1u << bbits) < nb) ++bbits;
-    size_t tb = 0;
-    u64 m = e->n_kept;   // (phase 2: set by phase 1)
-    bool order_queued = false;   // the source order (label sort, block cuts, placement) was queued together with the label pass
-    if (phase == 3 || phase == 4) {   // (4: a slice of a postings input — stops at the labels, ksp_engine_slice_finish runs phase 2)
-        m = n;
-        e->n_kept = m;
-        hipLaunchKernelGGL(k_iota4, dim3(grid_for(N, bs)), dim3(bs), 0, st, iota, order, newidx, label, N);
-        KSP_HIP(hipMemsetAsync(e->blk_max.p, 0, ((size_t)nb + 1) * 4, st));
-        KSP_HIP(hipMemsetAsync(sbound, 0, (size_t)N * 4, st));
-        const u32 nk = e->post_nkeys;
-        KSP_HIP(hipMemsetAsync(scal + 4, 0, 8, st));
-        hipLaunchKernelGGL((k_post_expand<V, W>), dim3(grid_for(nk, bs)), dim3(bs), 0, st, e->post_off, e->post_src,
-                           e->post_w, VA, rank1, sbound, nk, N, (u32*)(scal + 4));
-        hipLaunchKernelGGL(k_crank_from_rank, dim3(grid_for(m / CR_CHUNK + 1, bs)), dim3(bs), 0, st, rank1, crank, (u32)m);   // (postings: a rank per entry exists)
-        e->rank1_ok = true;
-        {   // U = number of keys (what the prune scan reports on the sketch path)
-            e->h_scal[2] = nk;
-            KSP_HIP(hipMemcpyAsync(scal + 2, e->h_scal + 2, 8, hipMemcpyHostToDevice, st));
-        }
-        if (reorder) {
-            run_label(e->post_off, nk, m);
-        } else {
-            hipLaunchKernelGGL(k_blk_bound, dim3(grid_for(N, bs)), dim3(bs), 0, st, sbound, newidx, e->blk_max.as<u32>(), N);
-        }
-        if (phase == 4) return KSP_OK;
-    } else if (phase != 2) {
-
-    // the hand-written partition (partition_kernels.hip.h) finds the key range on the device and makes the
-    // source tags itself: no read-back, no tagging pass.  Unweighted whole builds whose bucket count fits
-    // its two levels; everything else (weighted sketches, key-range slices, > 2^16 buckets) takes the
-    // rocPRIM partition below.
-    u32 nb_hand = 0;   // buckets of the hand-written partition (any number up to 2^21; above 2^16: three levels; 0: not used)
-    if (!W && phase == 0 && e->nparts == 1 && !e->hash_off && !e->full_sort && !e->part_off && n >= e->part_min) {
-        u32 mean = HB_HAND_MEAN;
-        if (const char* bm = std::getenv("KSP_DEBUG_BUCKET_MEAN")) mean = (u32)std::max(8, std::atoi(bm));   // (timing experiments; tests: tiny buckets force the middle level)
-        u64 want = (n + mean - 1) / mean;
-        if (want > 65536 && (n + 65535) / 65536 <= HB_HAND_MEAN_MAX && !std::getenv("KSP_DEBUG_BUCKET_MEAN"))
-            want = 65536;   // (somewhat larger buckets rather than a third level)
-        if (want <= (256u * 32u * 256u) && !(want > 65536 && std::getenv("KSP_DEBUG_NO_MID"))) nb_hand = (u32)std::max<u64>(1, want);
+// postings input (phases 3 / 4): sorting and pruning were done by the caller's inverted index — tags, ranks and labels from it
+template <class V> int Stage1<V>::from_postings() {
+    m = n;
+    e->n_kept = m;
+    hipLaunchKernelGGL(k_iota4, dim3(grid_for(N, bs)), dim3(bs), 0, st, iota, order, newidx, label, N);
+    KSP_HIP(hipMemsetAsync(e->blk_max.p, 0, ((size_t)nb + 1) * 4, st));
+    KSP_HIP(hipMemsetAsync(sbound, 0, (size_t)N * 4, st));
+    const u32 nk = e->post_nkeys;
+    KSP_HIP(hipMemsetAsync(scal + 4, 0, 8, st));
+    hipLaunchKernelGGL((k_post_expand<V, W>), dim3(grid_for(nk, bs)), dim3(bs), 0, st, e->post_off, e->post_src,
+                       e->post_w, VA, rank1, sbound, nk, N, (u32*)(scal + 4));
+    hipLaunchKernelGGL(k_crank_from_rank, dim3(grid_for(m / CR_CHUNK + 1, bs)), dim3(bs), 0, st, rank1, crank, (u32)m);   // (postings: a rank per entry exists)
+    e->rank1_ok = true;
+    // U = number of keys (what the prune scan reports on the sketch path)
+    e->h_scal[2] = nk;
+    KSP_HIP(hipMemcpyAsync(scal + 2, e->h_scal + 2, 8, hipMemcpyHostToDevice, st));
+    if (reorder) {
+        label_pass(e->post_off, nk, m);
+    } else {
+        hipLaunchKernelGGL(k_blk_bound, dim3(grid_for(N, bs)), dim3(bs), 0, st, sbound, newidx, e->blk_max.as<u32>(), N);
     }
-    const bool hand = nb_hand > 0;
-    // the segment partition (k_seg_bounds / k_seg_scatter): two levels, runs long enough to leave a dozen entries per
-    // (source, range) and no run so long that the one wave that streams it would be the launch
-    bool seg = false, seg3_used = false;
-    u32 seg_cap = 0, seg_nb1 = 0;
-    // (one source's segment must fit a tile: a run so long that its share of one range would not is a build for the
-    //  paged levels — known before anything is launched, instead of finding out from the overflow word)
-    auto seg_runs_fit = [&](const u32 r1) {
-        u64 longest = 0;
-        for (u32 s_ = 0; s_ < N; ++s_) longest = std::max(longest, e->h_off[s_ + 1] - e->h_off[s_]);
-        return longest / std::max<u32>(1, r1) <= SEG_FILL;
-    };
-    int seg_pb2 = 0;
-    if (hand && nb_hand <= 65536 && !e->seg_off && e->h_off.size() == (size_t)N + 1 && N) {
-        const char* sv = std::getenv("KSP_SEG");   // 0: never, 1: whatever the segment length (diagnostic / tests)
-        while (((nb_hand + (1u << seg_pb2) - 1) >> seg_pb2) > 256) ++seg_pb2;
+    return KSP_OK;
+}
+
+// (one source's segment must fit a tile: a run so long that its share of one range would not is a build for the
+//  paged levels — known before anything is launched, instead of finding out from the overflow word)
+template <class V> bool Stage1<V>::seg_runs_fit(const u32 r1) const {
+    u64 longest = 0;
+    for (u32 s_ = 0; s_ < N; ++s_) longest = std::max(longest, e->h_off[s_ + 1] - e->h_off[s_]);
+    return longest / std::max<u32>(1, r1) <= SEG_FILL;
+}
+
+// The hand-written partition (partition_kernels.hip.h) finds the key range on the device and makes the source tags
+// itself: no read-back, no tagging pass.  Unweighted whole builds whose bucket count fits its levels; everything else
+// (weighted sketches, key-range slices, > 2^21 buckets) takes the rocPRIM partition.
+template <class V> PartPlan Stage1<V>::plan_partition() const {
+    PartPlan p;
+    p.nslots = n;
+    if (W || phase != 0 || e->nparts != 1 || e->hash_off || e->full_sort || e->part_off || n < e->part_min) return p;
+    u32 mean = HB_HAND_MEAN;
+    if (const char* bm = std::getenv("KSP_DEBUG_BUCKET_MEAN")) mean = (u32)std::max(8, std::atoi(bm));   // (timing experiments; tests: tiny buckets force the middle level)
+    u64 want = (n + mean - 1) / mean;
+    if (want > 65536 && (n + 65535) / 65536 <= HB_HAND_MEAN_MAX && !std::getenv("KSP_DEBUG_BUCKET_MEAN"))
+        want = 65536;   // (somewhat larger buckets rather than a third level)
+    if (want > (256u * 32u * 256u) || (want > 65536 && std::getenv("KSP_DEBUG_NO_MID"))) return p;
+    p.nb_hand = (u32)std::max<u64>(1, want);
+    const bool runs_known = !e->seg_off && e->h_off.size() == (size_t)N + 1 && N;
+    const char* sv = std::getenv("KSP_SEG");   // 0: never, 1: whatever the segment length (diagnostic / tests)
+    if (p.nb_hand <= 65536 && runs_known) {
+        while (((p.nb_hand + (1u << p.seg_pb2) - 1) >> p.seg_pb2) > 256) ++p.seg_pb2;
         // (fewer, longer segments — 256 final buckets per range, C2: 51 entries per segment instead of 26 — were measured with
         //  the vectorised boundary pass: partition 0.42 -> 0.44 ms, the shorter write runs cost more than the longer reads save)
-        const int pb2_min = seg_pb2;
-        if (const char* pv = std::getenv("KSP_DEBUG_SEG_PB2")) seg_pb2 = std::min(8, std::max(pb2_min, std::atoi(pv)));   // (timing experiments)
-        seg_nb1 = (nb_hand + (1u << seg_pb2) - 1) >> seg_pb2;
-        const u64 mean_seg = n / N / seg_nb1;
-        seg = (sv ? std::atoi(sv) != 0 : mean_seg >= SEG_MIN_LEN && seg_runs_fit(seg_nb1));
-        if (seg) {
-            const u64 mean = n / nb_hand + 1;
-            seg_cap = (u32)((mean + mean / 2 + 128 + 63) & ~63ull);   // (a multiple of 64 places: every bucket starts on a memory line)
-            if ((u64)nb_hand * seg_cap + P2_TILE >= (1ull << 31)) seg = false;
+        const int pb2_min = p.seg_pb2;
+        if (const char* pv = std::getenv("KSP_DEBUG_SEG_PB2")) p.seg_pb2 = std::min(8, std::max(pb2_min, std::atoi(pv)));   // (timing experiments)
+        p.seg_nb1 = (p.nb_hand + (1u << p.seg_pb2) - 1) >> p.seg_pb2;
+        const u64 mean_seg = n / N / p.seg_nb1;
+        p.seg = (sv ? std::atoi(sv) != 0 : mean_seg >= SEG_MIN_LEN && seg_runs_fit(p.seg_nb1));
+        if (p.seg) {
+            const u64 mean_b = n / p.nb_hand + 1;
+            p.seg_cap = (u32)((mean_b + mean_b / 2 + 128 + 63) & ~63ull);   // (a multiple of 64 places: every bucket starts on a memory line)
+            if ((u64)p.nb_hand * p.seg_cap + P2_TILE >= (1ull << 31)) p.seg = false;
         }
     }
-    const u64 nslots = seg ? (u64)nb_hand * seg_cap + P2_TILE : n;   // places of the partitioned entries (fixed ranges per bucket: with gaps)
-    if (seg) {
-        if ((rc = e->KA.ensure((nslots + 4) * 8))) return rc;
-        if ((rc = e->VB.ensure((nslots + 4) * sizeof(V)))) return rc;
-        if ((rc = e->KB.ensure((nslots / 2 + 1 + 2 * (u64)nb_hand + nb_hand / 2 + 8) * 8))) return rc;
-        KA = e->KA.as<u64>();   // (the buffers may have moved)
-        VB = e->VB.as<V>();
+    if (p.seg) p.nslots = (u64)p.nb_hand * p.seg_cap + P2_TILE;
+    if (p.nb_hand <= 65536) {
+        while (((p.nb_hand + (1u << p.hp_pb2) - 1) >> p.hp_pb2) > 256) ++p.hp_pb2;
+    } else {
+        // three levels: the middle one orders whole pages in LDS and writes long runs, so it takes as many bits as
+        // it can (up to 5) and level 1 — whose runs are a source's keys inside one bucket — as few as possible
+        p.hp_pb2 = 8;
+        const u32 pre = (p.nb_hand + 255u) >> 8;
+        while (p.hp_pbm < 5 && ((pre + (1u << p.hp_pbm) - 1) >> p.hp_pbm) > 64) ++p.hp_pbm;
+        while (((pre + (1u << p.hp_pbm) - 1) >> p.hp_pbm) > 256) ++p.hp_pbm;
     }
+    const u32 prefixes = (p.nb_hand + (1u << p.hp_pb2) - 1) >> p.hp_pb2;   // groups of 2^pb2 final buckets
+    p.hp_nb1 = (prefixes + (1u << p.hp_pbm) - 1) >> p.hp_pbm;                // level-1 buckets (<= 256)
+    p.hp_ngroups = p.hp_nb1 << p.hp_pbm;
+    p.hp_words_a = plan_lists(p.hp_a, n, p.hp_nb1, P1_R, p.hp_pages_a);
+    p.hp_words_m = p.hp_pbm ? plan_lists(p.hp_m, n, p.hp_ngroups, 2, p.hp_pages_m) : 0;
+    p.hp_nchunks = grid_for(n, P1_CH);
+    // arena: [level 1 | middle level | bucket counters] zeroed per build, then group bases and chunk sources
+    p.hp_zero_words = p.hp_words_a + p.hp_words_m + ((size_t)p.nb_hand + 1);
+    // (three levels: level 1 for runs that leave a dozen entries per (source, level-1 bucket))
+    if (p.hp_pbm && runs_known) p.seg3 = sv ? std::atoi(sv) != 0 : n / N / p.hp_nb1 >= SEG_MIN_LEN && seg_runs_fit(p.hp_nb1);
+    return p;
+}
+
+// The hand path's start: its arrays, then everything this build needs zeroed in one launch — the scalar block, the
+// per-block maxima, the partition's arena, the bucket totals, and (small inputs) the diagonal work and the tile bitmap of
+// the work list — and the key range, source sizes and identity maps from k_prep_sources.
+template <class V> int Stage1<V>::zero_and_prep() {
+    int rc;
+    if (pp.seg) {
+        if ((rc = e->KA.ensure((pp.nslots + 4) * 8))) return rc;
+        if ((rc = e->VB.ensure((pp.nslots + 4) * sizeof(V)))) return rc;
+        if ((rc = e->KB.ensure((pp.nslots / 2 + 1 + 2 * (u64)pp.nb_hand + pp.nb_hand / 2 + 8) * 8))) return rc;
+        bind();
+    }
+    if ((rc = e->parena.ensure((pp.hp_zero_words + pp.hp_ngroups + 2 + pp.hp_nchunks + 2) * 4))) return rc;
+    carve_lists(pp.hp_a, e->parena.as<u32>(), pp.hp_nb1);
+    if (pp.hp_pbm) carve_lists(pp.hp_m, e->parena.as<u32>() + pp.hp_words_a, pp.hp_ngroups);
+    pp.hp_gcnt = e->parena.as<u32>() + pp.hp_words_a + pp.hp_words_m;
+    pp.hp_gbase = pp.hp_gcnt + ((size_t)pp.nb_hand + 1);
+    pp.hp_src = pp.hp_gbase + (pp.hp_ngroups + 2);
+    ZeroList z{};
+    zero_add(z, scal, 128);
+    zero_add(z, e->blk_max.p, ((size_t)nb + 1) * 4);
+    zero_add(z, e->parena.p, pp.hp_zero_words * 4);
+    zero_add(z, (u64*)e->KB.p + (pp.nslots / 2 + 1), (size_t)pp.nb_hand * 8);   // bsum (bucket_layout)
+    if (nb <= KG_WORK) {
+        if ((rc = e->dwork.ensure(((size_t)nb + 2) * 8))) return rc;
+        zero_add(z, e->dwork.p, ((size_t)nb + 2) * 8);
+        e->pre_zeroed_work = true;
+    }
+    const u64 T = (u64)nb * (nb + 1) / 2;
+    if (T <= (1ull << 22)) {
+        const size_t bit_words = (size_t)(((T + 63) / 64) * 2 + 2);
+        if ((rc = e->tbits.ensure(bit_words * 4 + T + 64))) return rc;
+        zero_add(z, e->tbits.p, bit_words * 4 + T + 64);
+        e->pre_zeroed_bits = true;
+    }
+    phase_mark(e, st, "key range + source sizes");
+    hipLaunchKernelGGL(k_zero_regions, dim3(256), dim3(256), 0, st, z);
+    hand_zeroed = true;
+    hipLaunchKernelGGL(k_prep_sources, dim3(grid_for(N, bs)), dim3(bs), 0, st, d_keys, d_off, (unsigned long long*)scal, sbound,
+                       iota, order, newidx, label, N);
+    return KSP_OK;
+}
+
+// key range, source tags and sizes, identity maps: from the hand path's one start (zero_and_prep), or pass by pass
+template <class V> int Stage1<V>::tags_and_sizes() {
     e->pre_zeroed_work = e->pre_zeroed_bits = false;
-    // layout of the hand-written partition's arena (see the partition step below): level 1 (`A`), and for more than
-    // 65 536 buckets a middle level (`M`) between it and the final scatter
-    int hp_pb2 = 0, hp_pbm = 0;
-    u32 hp_nb1 = 0, hp_nchunks = 0, hp_ngroups = 0;
-    size_t hp_zero_words = 0, hp_pages_a = 0, hp_pages_m = 0;
-    PartLists hp_a{}, hp_m{};
-    u32 *hp_gcnt = nullptr, *hp_gbase = nullptr, *hp_src = nullptr;
-    if (hand) {
-        if (nb_hand <= 65536) {
-            while (((nb_hand + (1u << hp_pb2) - 1) >> hp_pb2) > 256) ++hp_pb2;
-        } else {
-            // three levels: the middle one orders whole pages in LDS and writes long runs, so it takes as many bits as
-            // it can (up to 5) and level 1 — whose runs are a source's keys inside one bucket — as few as possible
-            hp_pb2 = 8;
-            const u32 pre = (nb_hand + 255u) >> 8;
-            while (hp_pbm < 5 && ((pre + (1u << hp_pbm) - 1) >> hp_pbm) > 64) ++hp_pbm;
-            while (((pre + (1u << hp_pbm) - 1) >> hp_pbm) > 256) ++hp_pbm;
-        }
-        const u32 prefixes = (nb_hand + (1u << hp_pb2) - 1) >> hp_pb2;           // groups of 2^pb2 final buckets
-        hp_nb1 = (prefixes + (1u << hp_pbm) - 1) >> hp_pbm;                         // level-1 buckets (<= 256)
-        hp_ngroups = hp_nb1 << hp_pbm;
-        auto plan = [&](PartLists& pl, const u32 buckets, const u32 subs, size_t& pages) {
-            const u32 lists = buckets * subs;
-            pl.subs = subs;
-            pl.ptw = (u32)std::min<u64>(P1_PTW_MAX, 8 * (((n / lists) >> P1_PLOG) + 1) + 16);
-            const u64 per = n / subs;
-            pl.pool_pages = (u32)((per >> P1_PLOG) + (per >> (P1_PLOG + 3)) + buckets + 8);   // pages per sub-list class
-            pages = (size_t)pl.pool_pages * subs;
-            return (size_t)subs * P1_LINE + (size_t)lists * P1_LINE + (size_t)lists * pl.ptw + pages;   // words, all zeroed per build
-        };
-        const size_t words_a = plan(hp_a, hp_nb1, P1_R, hp_pages_a);
-        const size_t words_m = hp_pbm ? plan(hp_m, hp_ngroups, 2, hp_pages_m) : 0;
-        hp_nchunks = grid_for(n, P1_CH);
-        // arena: [level 1 | middle level | bucket counters] zeroed per build, then group bases and chunk sources
-        hp_zero_words = words_a + words_m + ((size_t)nb_hand + 1);
-        if ((rc = e->parena.ensure((hp_zero_words + hp_ngroups + 2 + hp_nchunks + 2) * 4))) return rc;
-        auto carve = [&](PartLists& pl, u32* base, const u32 buckets) {
-            const size_t lists = (size_t)buckets * pl.subs;
-            pl.pools = base;
-            pl.cursors = pl.pools + (size_t)pl.subs * P1_LINE;
-            pl.pt = pl.cursors + lists * P1_LINE;
-            pl.owner = pl.pt + lists * pl.ptw;
-        };
-        carve(hp_a, e->parena.as<u32>(), hp_nb1);
-        if (hp_pbm) carve(hp_m, e->parena.as<u32>() + words_a, hp_ngroups);
-        hp_gcnt = e->parena.as<u32>() + words_a + words_m;
-        hp_gbase = hp_gcnt + ((size_t)nb_hand + 1);
-        hp_src = hp_gbase + (hp_ngroups + 2);
-        // everything this build needs zeroed, in one launch: the scalar block, the per-block maxima, the partition's
-        // arena, the bucket totals, and (small inputs) the diagonal work and the tile bitmap of the work list
-        ZeroList z{};
-        zero_add(z, scal, 128);
-        zero_add(z, e->blk_max.p, ((size_t)nb + 1) * 4);
-        zero_add(z, e->parena.p, hp_zero_words * 4);
-        zero_add(z, (u64*)e->KB.p + (nslots / 2 + 1), (size_t)nb_hand * 8);   // bsum (see the partition step)
-        if (nb <= KG_WORK) {
-            if ((rc = e->dwork.ensure(((size_t)nb + 2) * 8))) return rc;
-            zero_add(z, e->dwork.p, ((size_t)nb + 2) * 8);
-            e->pre_zeroed_work = true;
-        }
-        const u64 T = (u64)nb * (nb + 1) / 2;
-        if (T <= (1ull << 22)) {
-            const size_t bit_words = (size_t)(((T + 63) / 64) * 2 + 2);
-            if ((rc = e->tbits.ensure(bit_words * 4 + T + 64))) return rc;
-            zero_add(z, e->tbits.p, bit_words * 4 + T + 64);
-            e->pre_zeroed_bits = true;
-        }
-        phase_mark(e, st, "key range + source sizes");
-        hipLaunchKernelGGL(k_zero_regions, dim3(256), dim3(256), 0, st, z);
-        hand_zeroed = true;
-        hipLaunchKernelGGL(k_prep_sources, dim3(grid_for(N, bs)), dim3(bs), 0, st, d_keys, d_off, (unsigned long long*)scal, sbound,
-                           iota, order, newidx, label, N);
+    if (pp.nb_hand) {
+        if (const int rc = zero_and_prep()) return rc;
     } else {
         KSP_HIP(hipMemsetAsync(scal + 4, 0, 8 * 11, st));   // [4] .. [14]: overflow words, counters of the partition
-    }
-    // key range (one 8-byte D2H, unless the caller passed key_bits)
-    if (!hand && e->key_bits <= 0) {
-        KSP_HIP(hipMemsetAsync(scal, 0, 8, st));
-        hipLaunchKernelGGL(k_max_last, dim3(grid_for(N, bs)), dim3(bs), 0, st, d_keys, d_off, (unsigned long long*)scal, N);
-        KSP_HIP(hipMemcpyAsync(e->h_scal, scal, 8, hipMemcpyDeviceToHost, st));
-        KSP_HIP(hipStreamSynchronize(st));
-        u64 mx = e->h_scal[0];
-        e->max_key = mx;
-        e->have_max_key = true;
-        int bits = 1;
-        while (bits < 64 && (mx >> bits)) ++bits;
-        e->key_bits = bits;
-    }
-    const int kbits = e->key_bits;
-    if (!hand) phase_mark(e, st, "tags + source sizes");
-    if ((W || e->nparts == 1) && !hand)   // (weighted slices still need the per-source weight sums of all entries)
-        hipLaunchKernelGGL((k_tag<V, W>), dim3(N), dim3(256), 0, st, d_off, d_w, VA, sbound);
-    if (!hand) {
+        if (e->key_bits <= 0) {   // key range (one 8-byte D2H, unless the caller passed key_bits)
+            KSP_HIP(hipMemsetAsync(scal, 0, 8, st));
+            hipLaunchKernelGGL(k_max_last, dim3(grid_for(N, bs)), dim3(bs), 0, st, d_keys, d_off, (unsigned long long*)scal, N);
+            KSP_HIP(hipMemcpyAsync(e->h_scal, scal, 8, hipMemcpyDeviceToHost, st));
+            KSP_HIP(hipStreamSynchronize(st));
+            e->max_key = e->h_scal[0];
+            e->have_max_key = true;
+            e->key_bits = key_bits_of(e->max_key);
+        }
+        phase_mark(e, st, "tags + source sizes");
+        if (W || e->nparts == 1)   // (weighted slices still need the per-source weight sums of all entries)
+            hipLaunchKernelGGL((k_tag<V, W>), dim3(N), dim3(256), 0, st, d_off, d_w, VA, sbound);
         if (!W) hipLaunchKernelGGL(k_src_size, dim3(grid_for(N, bs)), dim3(bs), 0, st, d_off, sbound, N);
         hipLaunchKernelGGL(k_iota4, dim3(grid_for(N, bs)), dim3(bs), 0, st, iota, order, newidx, label, N);   // (order, newidx: identity until the labels are known)
+        KSP_HIP(hipMemsetAsync(e->blk_max.p, 0, ((size_t)nb + 1) * 4, st));
     }
-    if (!hand) KSP_HIP(hipMemsetAsync(e->blk_max.p, 0, ((size_t)nb + 1) * 4, st));
     if (!reorder) hipLaunchKernelGGL(k_blk_bound, dim3(grid_for(N, bs)), dim3(bs), 0, st, sbound, newidx, e->blk_max.as<u32>(), N);
-    // slice mode (multi-GPU build): keep only the entries of this part's key range — one contiguous
-    // sub-run per (sorted) source, so the cost is proportional to the slice, not to the sketch set
-    const u64* keys_in = d_keys;
-    const V* tags_in = VA;
-    u64 nw = n;
-    int topbit = kbits;   // the bucket partition takes the bits just below this one
+    return KSP_OK;
+}
+
+// What the grouping reads.  Slice mode (multi-GPU build): only the entries of this part's key range — one contiguous
+// sub-run per (sorted) source, so the cost is proportional to the slice, not to the sketch set.
+template <class V> int Stage1<V>::slice_range() {
+    const int kbits = e->key_bits;
+    int rc;
+    keys_in = d_keys;
+    tags_in = VA;
+    nw = n;
+    topbit = kbits;
     // equal shares of [0, largest key] (or of [0, 2^key_bits) when the caller fixed key_bits): part p holds the keys
     // span * p / nparts <= key < span * (p + 1) / nparts
     unsigned __int128 cut_lo = 0, cut_end = 1;
@@ -957,16 +982,10 @@ static int build_impl(ksp_engine* e, const u64* d_keys, const u32* d_w, hipStrea
         // above take at most two values inside the slice; the buckets compare whole keys anyway)
         topbit = 1;
         while (topbit < kbits && ((hi - lo) >> topbit)) ++topbit;
-        u32* first = (u32*)e->KB.p;                 // N
-        u32* cnt = (u32*)e->KB.p + (N + 2);         // N
-        u32* fpos = (u32*)e->KB.p + 2 * ((size_t)N + 2);   // N   (KB holds 2(n+4) u32 >= 3(N+2) whenever n >= 2N; checked below)
-        if ((rc = e->KB.ensure(std::max<size_t>((n + 4) * 8, 3 * ((size_t)N + 2) * 4)))) return rc;
-        first = (u32*)e->KB.p; cnt = first + (N + 2); fpos = first + 2 * ((size_t)N + 2);
-        hipLaunchKernelGGL(k_range_bounds, dim3(grid_for(N, bs)), dim3(bs), 0, st, d_keys, d_off, lo, hi, first, cnt, N);
-        tb = 0;
-        KSP_HIP(rocprim::exclusive_scan(nullptr, tb, cnt, fpos, (u32)0, (size_t)N, rocprim::plus<u32>(), st));
-        if ((rc = e->tmp.ensure(tb))) return rc;
-        KSP_HIP(rocprim::exclusive_scan(e->tmp.p, tb, cnt, fpos, (u32)0, (size_t)N, rocprim::plus<u32>(), st));
+        if ((rc = e->KB.ensure(std::max<size_t>((n + 4) * 8, 3 * ((size_t)N + 2) * 4)))) return rc;   // (KB holds 2(n+4) u32 >= 3(N+2) whenever n >= 2N)
+        u32 *run0 = (u32*)e->KB.p, *cnt = run0 + (N + 2), *fpos = run0 + 2 * ((size_t)N + 2);   // N each
+        hipLaunchKernelGGL(k_range_bounds, dim3(grid_for(N, bs)), dim3(bs), 0, st, d_keys, d_off, lo, hi, run0, cnt, N);
+        if ((rc = with_tmp(e, st, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, cnt, fpos, (u32)0, (size_t)N, rocprim::plus<u32>(), st); }))) return rc;
         hipLaunchKernelGGL(k_range_total, dim3(1), dim3(64), 0, st, fpos, cnt, scal, N);
         KSP_HIP(hipMemcpyAsync(e->h_scal + 8, scal + 8, 8, hipMemcpyDeviceToHost, st));
         KSP_HIP(hipStreamSynchronize(st));
@@ -974,393 +993,364 @@ static int build_impl(ksp_engine* e, const u64* d_keys, const u32* d_w, hipStrea
         if (nw >= (1ull << 30)) { set_error("build_slice: more than 2^30 key entries in this slice (use more parts)"); return KSP_E_LIMIT; }
         if ((rc = e->FK.ensure((nw + 4) * 8))) return rc;
         if ((rc = e->FT.ensure((nw + 4) * sizeof(V)))) return rc;
-        hipLaunchKernelGGL((k_range_copy<V, W>), dim3(N), dim3(128), 0, st, d_keys, d_w, d_off, first, cnt, fpos,
+        hipLaunchKernelGGL((k_range_copy<V, W>), dim3(N), dim3(128), 0, st, d_keys, d_w, d_off, run0, cnt, fpos,
                            e->FK.as<u64>(), e->FT.as<V>());
         keys_in = e->FK.as<u64>();
         tags_in = e->FT.as<V>();
     }
     e->n_kept = 0;
     m = 0;
-    bool labels_queued = false;   // the label pass was queued before the grouping's counts were read back
-    order_queued = false;
-    if (nw == 0) return KSP_OK;   // (slice mode only) no key of this range: labels stay the identity
-    // sort 1: all entries by the top 32 significant key bits (payload = tag [+weight]):
-    // d_keys,VA -> KA,VB; then order the rare mixed runs by the full key (k_fix_runs)
-    // (rocPRIM 4.2 / ROCm 7.2 mis-sorts 64-bit keys on any bit range [b > 0, 64) below ~1M items —
-    //  found with a stand-alone sweep on MI355X; ranges ending below bit 64 are fine — so keys
-    //  that use all 64 bits take the full-width sort.)
-    const int shift = (e->full_sort || kbits >= 64) ? 0 : std::max(0, kbits - 32);
-    u32* d_ovf = (u32*)(scal + 4);   // set by k_fix_runs when a run is too long; checked at the end of the build
-    if (!hand) KSP_HIP(hipMemsetAsync(d_ovf, 0, 8, st));   // (the hand-written partition's build zeroes the scalar block at its start)
-    tb = 0;
-    // grouping by hash bucket (see k_bucket_group): partition on the top pb key bits only — buckets of
-    // 400-800 entries for uniform hashes (up to twice that when the keys span just over half of [0, 2^kbits))
-    // (never a bit range that ends at bit 64 — see the rocPRIM note below: bit 63 is left to the buckets,
-    //  which compare whole keys; folding the two halves of the key range keeps the buckets even)
+    if (nw == 0) return S1_DONE;   // (slice mode only) no key of this range: labels stay the identity
+    if ((rc = e->FK.ensure((nw / 2 + 16) * 4))) return rc;
+    first = (u32*)e->FK.p;   // (FK: the slice's input keys are dead after sort 1)
+    return KSP_OK;
+}
+
+// Grouping by hash bucket (see k_bucket_group): partition on the top pb key bits only — buckets of 400-800 entries for
+// uniform hashes (up to twice that when the keys span just over half of [0, 2^kbits)).  Never a bit range that ends at
+// bit 64 (see the rocPRIM note at sort_and_prune): bit 63 is left to the buckets, which compare whole keys; folding the
+// two halves of the key range keeps the buckets even.
+template <class V> void Stage1<V>::bucket_layout() {
     if (topbit > 63) topbit = 63;
-    int pb = 0;
-    if (hand) { pb = 1; while ((1u << pb) < nb_hand) ++pb; }   // (statistics; the hand-written partition takes any bucket count)
+    pb = 0;
+    if (pp.nb_hand) { pb = 1; while ((1u << pb) < pp.nb_hand) ++pb; }   // (statistics; the hand-written partition takes any bucket count)
     else if ((phase == 0 || phase == 1) && !e->hash_off && !e->full_sort && nw >= 4096u) {
         pb = 1;
         while ((nw >> pb) > HB_MEAN) ++pb;
         if (pb > topbit) pb = 0;   // (few distinct keys, many holders each: the sort path)
     }
-    if ((rc = e->FK.ensure((nw / 2 + 16) * 4))) return rc;
-    u32* first = (u32*)e->FK.p;            // first kept entry of every rank (FK: the slice's input keys are dead after sort 1)
-    if (pb) {
-        const int shiftb = topbit - pb;
-        const u32 nbuckets = hand ? nb_hand : 1u << pb;
-        // KB is free until the grouping scans: per-entry records, then the bucket tables
-        unsigned short* rec = (unsigned short*)e->KB.p;   // (16 bits per partitioned entry; the tables behind keep their place)
-        u64* bsum = (u64*)e->KB.p + ((seg ? nslots : nw) / 2 + 1);
-        u64* bbase = bsum + nbuckets;
-        u32* bstart = (u32*)(bbase + nbuckets);   // nbuckets + 1
-        u32* d_hovf = (u32*)(scal + 9);
-        // tables of the segment partition for `r1` ranges: boundary table, source groups and 2 048-entry chunks (host side,
-        // rebuilt when the offsets or the range count change)
-        auto seg_tables = [&](const u32 r1) -> int {
-            const size_t tbl_words = (size_t)N * (r1 + 1);
-            if ((rc = e->seg_tbl.ensure(tbl_words * 4))) return rc;
-            if (!e->seg_groups_ok || e->seg_groups_nb1 != r1) {
-                std::vector<u32>& gs = e->seg_groups;
-                gs.clear();
-                gs.push_back(0);
-                const u64 per = (u64)SEG_FILL * r1;
-                u64 acc = 0;
-                u32 cnt_s = 0;
-                for (u32 s_ = 0; s_ < N; ++s_) {
-                    const u64 len = e->h_off[s_ + 1] - e->h_off[s_];
-                    if (cnt_s && (acc + len > per || cnt_s == SEG_SMAX)) { gs.push_back(s_); acc = 0; cnt_s = 0; }
-                    acc += len;
-                    ++cnt_s;
-                }
-                gs.push_back(N);
-                std::vector<uint4>& ck = e->seg_chunks;   // chunks of k_seg_bounds: 2 048 consecutive entries of one run each
-                ck.clear();
-                for (u32 s_ = 0; s_ < N; ++s_) {
-                    const u64 b_ = e->h_off[s_], len = e->h_off[s_ + 1] - b_;
-                    u64 a = 0;
-                    do {
-                        const u64 c = std::min<u64>(SEG_BPART, len - a);
-                        ck.push_back(make_uint4((u32)(b_ + a), (u32)a, s_, (u32)c | (a + c == len ? 0x80000000u : 0u)));
-                        a += c;
-                    } while (a < len);
-                }
-                if ((rc = e->seg_chk.ensure(ck.size() * 16))) return rc;
-                KSP_HIP(hipMemcpyAsync(e->seg_chk.p, ck.data(), ck.size() * 16, hipMemcpyHostToDevice, st));
-                e->seg_groups_nb1 = r1;
-                e->seg_groups_ok = true;
-                if ((rc = e->seg_grp.ensure(gs.size() * 4 + 16 + 258 * 8))) return rc;   // (+ the ranges' first keys, k_seg_prep)
-                KSP_HIP(hipMemcpyAsync(e->seg_grp.p, gs.data(), gs.size() * 4, hipMemcpyHostToDevice, st));
-            }
-            return KSP_OK;
-        };
-        BucketBounds bb{bstart, nullptr, 0u};
-        if (seg) {
-            // level 1 is already in the sketches (sorted runs): boundaries of every source's segments, then the scatter
-            // gathers its tiles from the segments; fixed places per bucket, the cursors count what arrived
-            if ((rc = seg_tables(seg_nb1))) return rc;
-            const u32 ngroups_s = (u32)e->seg_groups.size() - 1;
-            phase_mark(e, st, "partition");
-            if (e->time_sort) KSP_HIP(hipEventRecord(e->ev[4], st));
-            u64* kmin = (u64*)((char*)e->seg_grp.p + (((e->seg_groups.size() * 4) + 15) & ~(size_t)15));   // (behind the groups)
-            hipLaunchKernelGGL(k_seg_prep, dim3(1), dim3(256), 0, st, scal, nbuckets, seg_pb2, seg_nb1, kmin);   // (the multiplier of this build, the ranges' first keys)
-            hipLaunchKernelGGL(k_seg_bounds, dim3((u32)e->seg_chunks.size()), dim3(64 * SEG_BW), 0, st, d_keys, e->seg_chk.as<uint4>(), scal, kmin,
-                               seg_pb2, nbuckets - 1, seg_nb1, e->seg_tbl.as<u32>());
-            hipLaunchKernelGGL((k_seg_scatter<V>), dim3(ngroups_s * seg_nb1), dim3(P2_THREADS), 0, st, d_keys, d_off, e->seg_tbl.as<u32>(),
-                               e->seg_grp.as<u32>(), scal, seg_pb2, nbuckets - 1, seg_nb1, seg_cap, hp_gcnt, KA, VB);
-            if (e->time_sort) KSP_HIP(hipEventRecord(e->ev[5], st));
-            phase_mark(e, st, "bucket grouping");
-            bb = BucketBounds{nullptr, hp_gcnt, seg_cap};
-        } else if (hand) {
-            // partition by bucket = floor(key * nbuckets / (max key + 1)): d_keys -> level-1 pages [-> middle pages] -> KA, VB, bstart
-            // three levels: level 1 can be read off the sorted runs too (k_seg_mid), for runs that leave a dozen entries per
-            // (source, level-1 bucket)
-            bool seg3 = false;
-            if (hp_pbm && !e->seg_off && e->h_off.size() == (size_t)N + 1 && N) {
-                const char* sv = std::getenv("KSP_SEG");
-                seg3 = sv ? std::atoi(sv) != 0 : n / N / hp_nb1 >= SEG_MIN_LEN && seg_runs_fit(hp_nb1);
-            }
-            seg3_used = seg3;
-            if (!seg3) {
-                if ((rc = e->PK.ensure(hp_pages_a * P1_PAGE * 8))) return rc;
-                if ((rc = e->PT.ensure(hp_pages_a * P1_PAGE * sizeof(V)))) return rc;
-                if ((rc = e->PD.ensure(hp_pages_a * P1_PAGE))) return rc;
-            } else if ((rc = seg_tables(hp_nb1))) return rc;
-            if (hp_pbm) {
-                if ((rc = e->PK2.ensure(hp_pages_m * P1_PAGE * 8))) return rc;
-                if ((rc = e->PT2.ensure(hp_pages_m * P1_PAGE * sizeof(V)))) return rc;
-                if ((rc = e->PD2.ensure(hp_pages_m * P1_PAGE))) return rc;
-            }
-            phase_mark(e, st, "partition");
-            if (e->time_sort) KSP_HIP(hipEventRecord(e->ev[4], st));
-            if (seg3) {
-                u64* kmin = (u64*)((char*)e->seg_grp.p + (((e->seg_groups.size() * 4) + 15) & ~(size_t)15));
-                hipLaunchKernelGGL(k_seg_prep, dim3(1), dim3(256), 0, st, scal, nbuckets, hp_pb2 + hp_pbm, hp_nb1, kmin);
-                hipLaunchKernelGGL(k_seg_bounds, dim3((u32)e->seg_chunks.size()), dim3(64 * SEG_BW), 0, st, d_keys, e->seg_chk.as<uint4>(), scal, kmin,
-                                   hp_pb2 + hp_pbm, nbuckets - 1, hp_nb1, e->seg_tbl.as<u32>());
-                hipLaunchKernelGGL((k_seg_mid<V>), dim3(((u32)e->seg_groups.size() - 1) * hp_nb1), dim3(P2_THREADS), 0, st, d_keys, d_off,
-                                   e->seg_tbl.as<u32>(), e->seg_grp.as<u32>(), scal, hp_pb2, hp_pbm, nbuckets - 1, hp_nb1, hp_m, e->PK2.as<u64>(),
-                                   e->PT2.as<V>(), e->PD2.as<u8>());
-            } else {
-            hipLaunchKernelGGL(k_part_src, dim3(grid_for((u64)hp_nchunks + 1, bs)), dim3(bs), 0, st, d_off, N, hp_nchunks, hp_src, scal,
-                               nbuckets);
-            // (short sources — fewer than two consecutive entries per level-1 bucket on average — are ordered in LDS before
-            //  they are written: see k_part1; KSP_DEBUG_PART_SORTED=0 / 1 forces the choice: timing experiments, tests)
-            bool p1_sorted = N && n / N < 2ull * hp_nb1;
-            if (const char* sv = std::getenv("KSP_DEBUG_PART_SORTED")) p1_sorted = std::atoi(sv) != 0;
-            if (p1_sorted)
-                hipLaunchKernelGGL((k_part1<V, true>), dim3(hp_nchunks), dim3(P1_THREADS), 0, st, d_keys, d_off, N, (u32)nw, scal,
-                                   hp_pb2 + hp_pbm, hp_pb2, nbuckets - 1, hp_a, hp_src, e->PK.as<u64>(), e->PT.as<V>(), e->PD.as<u8>());
-            else
-            hipLaunchKernelGGL((k_part1<V>), dim3(hp_nchunks), dim3(P1_THREADS), 0, st, d_keys, d_off, N, (u32)nw, scal,
-                               hp_pb2 + hp_pbm, hp_pb2, nbuckets - 1, hp_a, hp_src, e->PK.as<u64>(), e->PT.as<V>(), e->PD.as<u8>());
-            }
-            if (hp_pbm && !seg3)
-                hipLaunchKernelGGL((k_part_mid<V>), dim3((u32)hp_pages_a), dim3(P2_THREADS), 0, st, scal, hp_a, hp_m, hp_pb2, hp_pbm,
-                                   nbuckets - 1, e->PK.as<u64>(), e->PT.as<V>(), e->PD.as<u8>(), e->PK2.as<u64>(), e->PT2.as<V>(),
-                                   e->PD2.as<u8>());
-            const PartLists& last = hp_pbm ? hp_m : hp_a;
-            const size_t pages_last = hp_pbm ? hp_pages_m : hp_pages_a;
-            const u64* Kl = hp_pbm ? e->PK2.as<u64>() : e->PK.as<u64>();
-            const V* Tl = hp_pbm ? e->PT2.as<V>() : e->PT.as<V>();
-            const u8* Dl = hp_pbm ? e->PD2.as<u8>() : e->PD.as<u8>();
-            hipLaunchKernelGGL(k_hist2, dim3((u32)pages_last), dim3(256), 0, st, scal, last, hp_pb2, Dl, hp_gcnt);
-            hipLaunchKernelGGL(k_group_base, dim3(1), dim3(1024), 0, st, scal, last, hp_ngroups, (u32)nw, hp_gbase);
-            hipLaunchKernelGGL(k_scan2, dim3(hp_ngroups), dim3(256), 0, st, hp_gbase, hp_pb2, nbuckets, hp_ngroups, hp_gcnt, bstart);
-            hipLaunchKernelGGL((k_scatter2<V>), dim3((u32)pages_last), dim3(P2_THREADS), 0, st, scal, last, hp_pb2, nbuckets - 1, Kl, Tl,
-                               hp_gcnt, KA, VB);
-            if (e->time_sort) KSP_HIP(hipEventRecord(e->ev[5], st));
-            phase_mark(e, st, "bucket grouping");   // (bsum: zeroed with the rest at the start of the build)
-        } else {
-        phase_mark(e, st, "partition");
-        KSP_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys_in, KA, tags_in, VB, nw, shiftb, topbit, st));
-        if ((rc = e->tmp.ensure(tb))) return rc;
-        if (e->time_sort) KSP_HIP(hipEventRecord(e->ev[4], st));
-        KSP_HIP(rocprim::radix_sort_pairs(e->tmp.p, tb, keys_in, KA, tags_in, VB, nw, shiftb, topbit, st));
-        if (e->time_sort) KSP_HIP(hipEventRecord(e->ev[5], st));
-        phase_mark(e, st, "bucket grouping");
-        KSP_HIP(hipMemsetAsync(d_hovf, 0, 8, st));
-        KSP_HIP(hipMemsetAsync(bsum, 0, (size_t)nbuckets * 8, st));
-        hipLaunchKernelGGL(k_bucket_bounds, dim3(grid_for((u64)nbuckets + 1, bs)), dim3(bs), 0, st, KA, nw, shiftb, nbuckets,
-                           bstart);
-        }
-        e->sort_entries = nw;
-        e->sort_bits = pb;
-        e->part_kind = (seg || seg3_used) ? 3 : hand ? 2 : 1;
-        // ---- the bucket-resident middle of stage 1 (fused_kernels.hip.h): grouping + emit + labels in one kernel, the
-        // group records straight to rank order, one read-back.  Unweighted whole builds on the hand-written partition
-        // whose blocks fit the split's tables; anything it cannot take (an oversize bucket, sparse sharing) sets
-        // fused_off and the build is repeated pass by pass.  Measured on C2 (round 3): correct, 0.6 GB less HBM traffic per
-        // step, but 0.14 ms SLOWER than the pass-by-pass kernels (bucket-at-a-time kernels are bound by LDS latency and
-        // barriers, not by HBM: DESIGN.md section 5) — so it only runs when KSP_FUSED=1 asks for it (tests run both).
-        e->fused_flags = false;
-        e->fused_used = 0;
-        if constexpr (!W) {
-            const char* fv = std::getenv("KSP_FUSED");
-            const char* msv = std::getenv("KSP_MS");
-            const u32 ms_max = (msv && std::atoi(msv) == 1024) ? MS_MAXB : 256u;
-            const u64 Tt = (u64)nb * (nb + 1) / 2;
-            if (hand && phase == 0 && reorder && nb <= ms_max && nb <= FK_NB_MAX && Tt <= (1ull << 22) && !e->fused_off && !e->key_groups_off &&
-                (fv && std::atoi(fv) == 1) && !(msv && std::atoi(msv) == 0) && e->pre_zeroed_bits && e->pre_zeroed_work) {
-                if ((rc = e->biglist.ensure(((size_t)nbuckets + 1) * 4))) return rc;
-                if ((rc = e->VA.ensure((nslots + 4) * sizeof(V)))) return rc;
-                if ((rc = e->FK.ensure((nslots / 2 + (u64)nbuckets + 16) * 4))) return rc;
-                if ((rc = e->mm.ensure((nw / (INLINE_MAX + 1) + 16) * 16))) return rc;   // (a mask per 5 kept entries at most)
-                VA = e->VA.as<V>();
-                u32* kst = (u32*)e->FK.p;
-                if (!e->hb_slots) {
-                    int per_cu = 0, cus = 0;
-                    KSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bucket_group, HB_THREADS, 0));
-                    KSP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
-                    e->hb_slots = (u32)std::max(1, per_cu * cus);
-                }
-                // labels on lines of their own while they are lowered (the head of KB: no per-entry records on this path)
-                const u32 skip = label_sampling(e, (u64)((double)nw * e->kept_frac));
-                const int ls = e->KB.bytes >= (size_t)N * 128 && (size_t)N * 128 <= (size_t)(nslots / 2) * 8 ? 5 : 0;
-                u32* lab = ls ? (u32*)e->KB.p : label;
-                if (ls) hipLaunchKernelGGL(k_label_spread, dim3(grid_for(N, bs)), dim3(bs), 0, st, lab, ls, N);
-                hipLaunchKernelGGL((k_fgroup<V>), dim3(std::min(nbuckets, e->hb_slots)), dim3(HB_THREADS), 0, st, KA, VB, bb, nbuckets, VA, kst,
-                                   bsum, d_hovf, e->biglist.as<u32>(), lab, ls, skip, label_max);
-                size_t tb2 = 0;
-                KSP_HIP(rocprim::exclusive_scan(nullptr, tb2, bsum, bbase, (u64)0, (size_t)nbuckets, rocprim::plus<u64>(), st));
-                if ((rc = e->tmp.ensure(tb2))) return rc;
-                KSP_HIP(rocprim::exclusive_scan(e->tmp.p, tb2, bsum, bbase, (u64)0, (size_t)nbuckets, rocprim::plus<u64>(), st));
-                hipLaunchKernelGGL(k_ftotals, dim3(1), dim3(64), 0, st, bsum, bbase, nbuckets, scal);
-                phase_mark(e, st, "source labels + order");
-                if (ls) hipLaunchKernelGGL(k_label_gather, dim3(grid_for(N, bs)), dim3(bs), 0, st, lab, ls, label, N);
-                {
-                    int lbits = 1;
-                    while (lbits < 32 && (N >> lbits)) ++lbits;
-                    tb = 0;
-                    u32* sort_out = e->padded ? sorted_src : order;
-                    KSP_HIP(rocprim::radix_sort_pairs(nullptr, tb, label, labs, iota, sort_out, (size_t)N, 0, lbits, st));
-                    if ((rc = e->tmp.ensure(tb))) return rc;
-                    KSP_HIP(rocprim::radix_sort_pairs(e->tmp.p, tb, label, labs, iota, sort_out, (size_t)N, 0, lbits, st));
-                    if (e->padded) {
-                        hipLaunchKernelGGL(k_pack_blocks, dim3(1), dim3(1024), 0, st, labs, N, nb, blk_src);
-                        hipLaunchKernelGGL(k_place_sources, dim3(grid_for((u64)nb * TB, bs)), dim3(bs), 0, st, sorted_src, blk_src, newidx, order,
-                                           sbound, e->blk_max.as<u32>(), nb);
-                    } else {
-                        hipLaunchKernelGGL(k_perm_bound, dim3(grid_for(N, bs)), dim3(bs), 0, st, order, newidx, sbound, e->blk_max.as<u32>(), N);
-                    }
-                }
-                // the (block, key) groups, chunk by chunk, straight into rank order
-                phase_mark(e, st, "key groups");
-                u32 gb = 8;
-                if (const char* gv = std::getenv("KSP_DEBUG_FK_GB")) gb = (u32)std::min<int>(FK_GBMAX, std::max(1, std::atoi(gv)));   // (timing experiments)
-                const u32 chunks = grid_for(nbuckets, gb);
-                const u32 mb = nb <= 256 ? 256u : 1024u;
-                const u64 Kcap = nw;   // records <= kept entries <= entries
-                if ((rc = e->gp.ensure((Kcap + 4) * 12))) return rc;
-                e->gp_stride = Kcap + 4;
-                u64* rec_val = e->gp.as<u64>();
-                u32* rec_blk = (u32*)(rec_val + (Kcap + 4));
-                if ((rc = e->ms_hist.ensure(((size_t)chunks + 1) * mb * 4 + (size_t)chunks * 4 + 8192))) return rc;
-                u32* hist = e->ms_hist.as<u32>();
-                u32* tot = hist + (size_t)chunks * mb;
-                u32* nrec = tot + mb + 64;
-                FkOut fo{rec_blk, rec_val, nrec, hist, e->mm.as<uint4>(), e->dwork.as<unsigned long long>()};
-                if (mb == 256)
-                    hipLaunchKernelGGL((k_fkeys<V, 256>), dim3(chunks), dim3(FK_THREADS), 0, st, VA, kst, bb, bsum, bbase, nbuckets, gb, newidx, N, nb, fo, scal);
-                else
-                    hipLaunchKernelGGL((k_fkeys<V, 1024>), dim3(chunks), dim3(FK_THREADS), 0, st, VA, kst, bb, bsum, bbase, nbuckets, gb, newidx, N, nb, fo, scal);
-                e->pre_zeroed_work = false;
-                phase_mark(e, st, "block lists");
-                hipLaunchKernelGGL(k_fms_scan, dim3(nb), dim3(256), 0, st, hist, mb, chunks, scal, tot, blk_raw, blk_pos, nb);
-                KSP_HIP(hipMemcpyAsync(e->h_scal, scal, 120, hipMemcpyDeviceToHost, st));   // [0] max key, [1] list words, [2] keys, [6] entries, [9] / [14] overflow (one copy)
-                KSP_HIP(hipEventRecord(e->ev_rb, st));
-                hipLaunchKernelGGL(k_pad, dim3(nb + 1), dim3(256), 0, st, blk_raw, blk_pos, e->bkeys.as<u32>(), nb, PAD, scal);
-                if ((rc = e->pmask.ensure((Kcap + (u64)nb * (WIN + 4) + 4 * WIN) * 16))) return rc;
-                const size_t bit_words = (size_t)(((Tt + 63) / 64) * 2 + 2);
-                unsigned char* flags = (unsigned char*)e->tbits.p + bit_words * 4;
-                if (mb == 256)
-                    hipLaunchKernelGGL((k_fms_place<256>), dim3(chunks), dim3(MS_THREADS), 0, st, rec_blk, rec_val, nrec, bbase, gb, hist, blk_pos, nb,
-                                       e->bkeys.as<u32>(), e->info.as<u32>(), e->mm.as<uint4>(), e->pmask.as<uint4>(), flags, scal);
-                else
-                    hipLaunchKernelGGL((k_fms_place<1024>), dim3(chunks), dim3(MS_THREADS), 0, st, rec_blk, rec_val, nrec, bbase, gb, hist, blk_pos, nb,
-                                       e->bkeys.as<u32>(), e->info.as<u32>(), e->mm.as<uint4>(), e->pmask.as<uint4>(), flags, scal);
-                KSP_HIP(wait_readback(e));
-                if ((seg || seg3_used) && ((u32)e->h_scal[PC_OVF] == 4 || (u32)e->h_scal[PC_OVF] == 5)) {
-                    e->seg_off = true;
-                    e->part_fail = (int)(u32)e->h_scal[PC_OVF];
-                    return build_impl<V>(e, d_keys, d_w, st, phase);
-                }
-                if ((u32)e->h_scal[PC_OVF]) {
-                    e->part_off = true;
-                    e->part_fail = (int)(u32)e->h_scal[PC_OVF];
-                    return build_impl<V>(e, d_keys, d_w, st, phase);
-                }
-                e->max_key = e->h_scal[0];
-                e->have_max_key = true;
-                {
-                    int bits = 1;
-                    while (bits < 64 && (e->max_key >> bits)) ++bits;
-                    e->key_bits = bits;
-                }
-                const char* jm = std::getenv("KSP_JOIN");
-                const bool want_matches = (jm && std::string(jm) == "matches") || (!jm && e->h_scal[6] < 4 * e->h_scal[1]);
-                if ((u32)(e->h_scal[9] >> 32) || (u32)e->h_scal[9] || want_matches) {   // an oversize bucket / sparse sharing: pass by pass from now on
-                    e->fused_off = true;
-                    return build_impl<V>(e, d_keys, d_w, st, phase);
-                }
-                m = e->h_scal[6];
-                e->n_kept = m;
-                if (nw) e->kept_frac = std::max(0.05, (double)m / (double)nw);
-                e->rank1_ok = false;
-                e->fused_used = 1;
-                if (m == 0) return KSP_OK;
-                const u64 K = std::max<u64>(1, e->h_scal[1]);
-                {
-                    const u64 avg = K / nb + 1;
-                    u32 nc = NP;
-                    while ((u64)nc * 32 < 4 * avg && nc < e->ncell) nc <<= 1;
-                    e->ncell = std::min(e->ncell, nc);
-                }
-                hipLaunchKernelGGL(k_cidx, dim3(grid_for((u64)nb * (e->ncell + 1), bs)), dim3(bs), 0, st, e->bkeys.as<u32>(),
-                                   blk_raw, blk_pos, scal, e->part.as<u32>(), nb, e->ncell);
-                KSP_HIP(hipGetLastError());
-                e->pmask_on = true;
-                e->have_dwork = true;
-                e->have_rank_pairs = false;
-                e->fused_flags = true;
-                e->pre_zeroed_bits = false;
-                e->scal_fresh = true;
-                return KSP_OK;
-            }
-        }
-        if (!e->hb_slots) {   // persistent workgroups: as many as fit on the device at once
-            int per_cu = 0, cus = 0;
-            KSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bucket_group, HB_THREADS, 0));
-            KSP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
-            e->hb_slots = (u32)std::max(1, per_cu * cus);
-        }
-        // buckets above HB_CAP entries (d_hovf[1] counts them): a slot per bucket, so data whose keys have hundreds of
-        // holders each (C3: a third of the buckets at a mean of 2 000) stays on this path instead of falling back to the sort
-        if ((rc = e->biglist.ensure(((size_t)nbuckets + 1) * 4))) return rc;
-        u32* big_list = e->biglist.as<u32>();
-        hipLaunchKernelGGL(k_bucket_group, dim3(std::min(nbuckets, e->hb_slots)), dim3(HB_THREADS), 0, st, KA, bb,
-                           nbuckets, (u32)nw, rec, bsum, d_hovf, big_list);
-        // (a rank per kept entry only when the sort-by-block fallback is known to follow: the key-by-key build reads crank[])
-        u32* rank_out = e->key_groups_off ? rank1 : nullptr;
-        e->rank1_ok = rank_out != nullptr;
-        hipLaunchKernelGGL((k_bucket_big<V, 0>), dim3(1024), dim3(HB_THREADS), 0, st, KA, VB, bb, big_list, d_hovf,
-                           bsum, (const u64*)nullptr, VA, rank_out, first, crank);
-        size_t tb2 = 0;
-        KSP_HIP(rocprim::exclusive_scan(nullptr, tb2, bsum, bbase, (u64)0, (size_t)nbuckets, rocprim::plus<u64>(), st));
-        if ((rc = e->tmp.ensure(tb2))) return rc;
-        KSP_HIP(rocprim::exclusive_scan(e->tmp.p, tb2, bsum, bbase, (u64)0, (size_t)nbuckets, rocprim::plus<u64>(), st));
-        hipLaunchKernelGGL((k_bucket_emit<V>), dim3((nbuckets + HB_EMIT - 1) / HB_EMIT), dim3(HB_THREADS), 0, st, rec, VB, bb,
-                           bbase, bsum, nbuckets, VA, rank_out, first, scal, crank);
-        hipLaunchKernelGGL((k_bucket_big<V, 1>), dim3(1024), dim3(HB_THREADS), 0, st, KA, VB, bb, big_list, d_hovf,
-                           bsum, bbase, VA, rank_out, first, crank);
-        // [0] max key, [2] keys, [6] entries, [9] / [14] overflow.  The kept-entry count sizes every later pass — but the label
-        // pass can be queued without it (its key count comes from the device, its sampling rate from the kept fraction of
-        // the engine's previous build), so the device works on while the host waits for the words
-        if (!reorder) KSP_HIP(hipMemcpyAsync(e->h_scal, scal, 120, hipMemcpyDeviceToHost, st));
-        if (reorder) {
-            phase_mark(e, st, "source labels + order");
-            run_label(first, (u32)std::min<u64>(nw / 2 + 1, 0x7FFFFFFFu), (u64)((double)nw * e->kept_frac), scal,
-                      ride_readback(e, st, scal, e->h_scal, 15));   // (the words ride along with k_label)
-            labels_queued = true;
-            if (phase == 0) {   // (... and neither does the order of the sources need it: sort, block cuts and placement are queued too)
-                const Stage1<V> so{e, st, phase, n, N, nb, KA, VA, VB, scal, blk_raw, blk_pos, rank1, crank, label, iota, labs, order, newidx,
-                                   sbound, sorted_src, blk_src, bbits, reorder, hand_zeroed, 0};
-                if ((rc = stage1_source_order(so))) return rc;
-                order_queued = true;
-            }
-            KSP_HIP(wait_readback(e));
-        } else {
-            KSP_HIP(hipStreamSynchronize(st));
-        }
-        if (hand) {
-            if ((seg || seg3_used) && ((u32)e->h_scal[PC_OVF] == 4 || (u32)e->h_scal[PC_OVF] == 5)) {   // a tile or a bucket of the segment partition overflowed: the paged levels from now on
-                e->seg_off = true;
-                e->part_fail = (int)(u32)e->h_scal[PC_OVF];
-                return build_impl<V>(e, d_keys, d_w, st, phase);
-            }
-            if ((u32)e->h_scal[PC_OVF]) {   // the page tables could not hold these keys: the library partition from now on
-                e->part_off = true;
-                e->part_fail = (int)(u32)e->h_scal[PC_OVF];
-                return build_impl<V>(e, d_keys, d_w, st, phase);
-            }
-            e->max_key = e->h_scal[0];
-            e->have_max_key = true;
-            int bits = 1;
-            while (bits < 64 && (e->max_key >> bits)) ++bits;
-            e->key_bits = bits;
-        }
-        e->big_buckets = (u32)(e->h_scal[9] >> 32);   // (d_hovf[1]: the oversize buckets k_bucket_group listed)
-        if ((u32)e->h_scal[9]) {   // a bucket did not fit (skewed keys): this engine sorts from now on
-            e->hash_off = true;
-            return build_impl<V>(e, d_keys, d_w, st, phase);
-        }
-    } else {
-    KSP_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys_in, KA, tags_in, VB, nw, shift, kbits, st));
-    if ((rc = e->tmp.ensure(tb))) return rc;
+    if (!pb) return;
+    nbuckets = pp.nb_hand ? pp.nb_hand : 1u << pb;
+    rec = (unsigned short*)e->KB.p;
+    bsum = (u64*)e->KB.p + ((pp.seg ? pp.nslots : nw) / 2 + 1);
+    bbase = bsum + nbuckets;
+    bstart = (u32*)(bbase + nbuckets);
+}
+
+// tables of the segment partition for `r1` ranges: boundary table, source groups and 2 048-entry chunks (host side,
+// rebuilt when the offsets or the range count change)
+template <class V> int Stage1<V>::seg_tables(const u32 r1) {
+    int rc;
+    const size_t tbl_words = (size_t)N * (r1 + 1);
+    if ((rc = e->seg_tbl.ensure(tbl_words * 4))) return rc;
+    if (e->seg_groups_ok && e->seg_groups_nb1 == r1) return KSP_OK;
+    std::vector<u32>& gs = e->seg_groups;
+    gs.clear();
+    gs.push_back(0);
+    const u64 per = (u64)SEG_FILL * r1;
+    u64 acc = 0;
+    u32 cnt_s = 0;
+    for (u32 s_ = 0; s_ < N; ++s_) {
+        const u64 len = e->h_off[s_ + 1] - e->h_off[s_];
+        if (cnt_s && (acc + len > per || cnt_s == SEG_SMAX)) { gs.push_back(s_); acc = 0; cnt_s = 0; }
+        acc += len;
+        ++cnt_s;
+    }
+    gs.push_back(N);
+    std::vector<uint4>& ck = e->seg_chunks;   // chunks of k_seg_bounds: 2 048 consecutive entries of one run each
+    ck.clear();
+    for (u32 s_ = 0; s_ < N; ++s_) {
+        const u64 b_ = e->h_off[s_], len = e->h_off[s_ + 1] - b_;
+        u64 a = 0;
+        do {
+            const u64 c = std::min<u64>(SEG_BPART, len - a);
+            ck.push_back(make_uint4((u32)(b_ + a), (u32)a, s_, (u32)c | (a + c == len ? 0x80000000u : 0u)));
+            a += c;
+        } while (a < len);
+    }
+    if ((rc = e->seg_chk.ensure(ck.size() * 16))) return rc;
+    KSP_HIP(hipMemcpyAsync(e->seg_chk.p, ck.data(), ck.size() * 16, hipMemcpyHostToDevice, st));
+    e->seg_groups_nb1 = r1;
+    e->seg_groups_ok = true;
+    if ((rc = e->seg_grp.ensure(gs.size() * 4 + 16 + 258 * 8))) return rc;   // (+ the ranges' first keys, k_seg_prep)
+    KSP_HIP(hipMemcpyAsync(e->seg_grp.p, gs.data(), gs.size() * 4, hipMemcpyHostToDevice, st));
+    return KSP_OK;
+}
+
+// Segment partition: level 1 is already in the sketches (sorted runs) — boundaries of every source's segments, then the
+// scatter gathers its tiles from the segments; fixed places per bucket, the cursors count what arrived.
+template <class V> int Stage1<V>::partition_segment() {
+    if (const int rc = seg_tables(pp.seg_nb1)) return rc;
+    const u32 ngroups_s = (u32)e->seg_groups.size() - 1;
+    phase_mark(e, st, "partition");
     if (e->time_sort) KSP_HIP(hipEventRecord(e->ev[4], st));
-    KSP_HIP(rocprim::radix_sort_pairs(e->tmp.p, tb, keys_in, KA, tags_in, VB, nw, shift, kbits, st));
+    u64* kmin = (u64*)((char*)e->seg_grp.p + (((e->seg_groups.size() * 4) + 15) & ~(size_t)15));   // (behind the groups)
+    hipLaunchKernelGGL(k_seg_prep, dim3(1), dim3(256), 0, st, scal, nbuckets, pp.seg_pb2, pp.seg_nb1, kmin);   // (the multiplier of this build, the ranges' first keys)
+    hipLaunchKernelGGL(k_seg_bounds, dim3((u32)e->seg_chunks.size()), dim3(64 * SEG_BW), 0, st, d_keys, e->seg_chk.as<uint4>(), scal, kmin,
+                       pp.seg_pb2, nbuckets - 1, pp.seg_nb1, e->seg_tbl.as<u32>());
+    hipLaunchKernelGGL((k_seg_scatter<V>), dim3(ngroups_s * pp.seg_nb1), dim3(P2_THREADS), 0, st, d_keys, d_off, e->seg_tbl.as<u32>(),
+                       e->seg_grp.as<u32>(), scal, pp.seg_pb2, nbuckets - 1, pp.seg_nb1, pp.seg_cap, pp.hp_gcnt, KA, VB);
     if (e->time_sort) KSP_HIP(hipEventRecord(e->ev[5], st));
+    phase_mark(e, st, "bucket grouping");
+    bb = BucketBounds{nullptr, pp.hp_gcnt, pp.seg_cap};
+    return KSP_OK;
+}
+
+// Paged partition by bucket = floor(key * nbuckets / (max key + 1)): d_keys -> level-1 pages [-> middle pages] -> KA, VB,
+// bstart.  With three levels, level 1 can be read off the sorted runs too (pp.seg3: k_seg_mid).
+template <class V> int Stage1<V>::partition_paged() {
+    int rc;
+    const int pb2 = pp.hp_pb2, pbm = pp.hp_pbm;
+    if (!pp.seg3) {
+        if ((rc = e->PK.ensure(pp.hp_pages_a * P1_PAGE * 8))) return rc;
+        if ((rc = e->PT.ensure(pp.hp_pages_a * P1_PAGE * sizeof(V)))) return rc;
+        if ((rc = e->PD.ensure(pp.hp_pages_a * P1_PAGE))) return rc;
+    } else if ((rc = seg_tables(pp.hp_nb1))) return rc;
+    if (pbm) {
+        if ((rc = e->PK2.ensure(pp.hp_pages_m * P1_PAGE * 8))) return rc;
+        if ((rc = e->PT2.ensure(pp.hp_pages_m * P1_PAGE * sizeof(V)))) return rc;
+        if ((rc = e->PD2.ensure(pp.hp_pages_m * P1_PAGE))) return rc;
+    }
+    phase_mark(e, st, "partition");
+    if (e->time_sort) KSP_HIP(hipEventRecord(e->ev[4], st));
+    if (pp.seg3) {
+        u64* kmin = (u64*)((char*)e->seg_grp.p + (((e->seg_groups.size() * 4) + 15) & ~(size_t)15));
+        hipLaunchKernelGGL(k_seg_prep, dim3(1), dim3(256), 0, st, scal, nbuckets, pb2 + pbm, pp.hp_nb1, kmin);
+        hipLaunchKernelGGL(k_seg_bounds, dim3((u32)e->seg_chunks.size()), dim3(64 * SEG_BW), 0, st, d_keys, e->seg_chk.as<uint4>(), scal, kmin,
+                           pb2 + pbm, nbuckets - 1, pp.hp_nb1, e->seg_tbl.as<u32>());
+        hipLaunchKernelGGL((k_seg_mid<V>), dim3(((u32)e->seg_groups.size() - 1) * pp.hp_nb1), dim3(P2_THREADS), 0, st, d_keys, d_off,
+                           e->seg_tbl.as<u32>(), e->seg_grp.as<u32>(), scal, pb2, pbm, nbuckets - 1, pp.hp_nb1, pp.hp_m, e->PK2.as<u64>(),
+                           e->PT2.as<V>(), e->PD2.as<u8>());
+    } else {
+        hipLaunchKernelGGL(k_part_src, dim3(grid_for((u64)pp.hp_nchunks + 1, bs)), dim3(bs), 0, st, d_off, N, pp.hp_nchunks, pp.hp_src, scal,
+                           nbuckets);
+        // (short sources — fewer than two consecutive entries per level-1 bucket on average — are ordered in LDS before
+        //  they are written: see k_part1; KSP_DEBUG_PART_SORTED=0 / 1 forces the choice: timing experiments, tests)
+        bool p1_sorted = N && n / N < 2ull * pp.hp_nb1;
+        if (const char* sv = std::getenv("KSP_DEBUG_PART_SORTED")) p1_sorted = std::atoi(sv) != 0;
+        if (p1_sorted)
+            hipLaunchKernelGGL((k_part1<V, true>), dim3(pp.hp_nchunks), dim3(P1_THREADS), 0, st, d_keys, d_off, N, (u32)nw, scal,
+                               pb2 + pbm, pb2, nbuckets - 1, pp.hp_a, pp.hp_src, e->PK.as<u64>(), e->PT.as<V>(), e->PD.as<u8>());
+        else
+            hipLaunchKernelGGL((k_part1<V>), dim3(pp.hp_nchunks), dim3(P1_THREADS), 0, st, d_keys, d_off, N, (u32)nw, scal,
+                               pb2 + pbm, pb2, nbuckets - 1, pp.hp_a, pp.hp_src, e->PK.as<u64>(), e->PT.as<V>(), e->PD.as<u8>());
+        if (pbm)
+            hipLaunchKernelGGL((k_part_mid<V>), dim3((u32)pp.hp_pages_a), dim3(P2_THREADS), 0, st, scal, pp.hp_a, pp.hp_m, pb2, pbm,
+                               nbuckets - 1, e->PK.as<u64>(), e->PT.as<V>(), e->PD.as<u8>(), e->PK2.as<u64>(), e->PT2.as<V>(),
+                               e->PD2.as<u8>());
+    }
+    const PartLists& last = pbm ? pp.hp_m : pp.hp_a;
+    const size_t pages_last = pbm ? pp.hp_pages_m : pp.hp_pages_a;
+    const u64* Kl = pbm ? e->PK2.as<u64>() : e->PK.as<u64>();
+    const V* Tl = pbm ? e->PT2.as<V>() : e->PT.as<V>();
+    const u8* Dl = pbm ? e->PD2.as<u8>() : e->PD.as<u8>();
+    hipLaunchKernelGGL(k_hist2, dim3((u32)pages_last), dim3(256), 0, st, scal, last, pb2, Dl, pp.hp_gcnt);
+    hipLaunchKernelGGL(k_group_base, dim3(1), dim3(1024), 0, st, scal, last, pp.hp_ngroups, (u32)nw, pp.hp_gbase);
+    hipLaunchKernelGGL(k_scan2, dim3(pp.hp_ngroups), dim3(256), 0, st, pp.hp_gbase, pb2, nbuckets, pp.hp_ngroups, pp.hp_gcnt, bstart);
+    hipLaunchKernelGGL((k_scatter2<V>), dim3((u32)pages_last), dim3(P2_THREADS), 0, st, scal, last, pb2, nbuckets - 1, Kl, Tl,
+                       pp.hp_gcnt, KA, VB);
+    if (e->time_sort) KSP_HIP(hipEventRecord(e->ev[5], st));
+    phase_mark(e, st, "bucket grouping");   // (bsum: zeroed with the rest at the start of the build)
+    bb = BucketBounds{bstart, nullptr, 0u};
+    return KSP_OK;
+}
+
+// Library partition: a radix sort on the bucket bits, the bucket bounds read off the sorted keys.
+template <class V> int Stage1<V>::partition_library() {
+    const int shiftb = topbit - pb;
+    KSP_HIP(hipMemsetAsync(d_ovf(), 0, 8, st));
+    phase_mark(e, st, "partition");
+    if (const int rc = with_tmp(e, st, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, keys_in, KA, tags_in, VB, nw, shiftb, topbit, st); }, e->time_sort)) return rc;
+    phase_mark(e, st, "bucket grouping");
+    KSP_HIP(hipMemsetAsync(d_hovf(), 0, 8, st));
+    KSP_HIP(hipMemsetAsync(bsum, 0, (size_t)nbuckets * 8, st));
+    hipLaunchKernelGGL(k_bucket_bounds, dim3(grid_for((u64)nbuckets + 1, bs)), dim3(bs), 0, st, KA, nw, shiftb, nbuckets,
+                       bstart);
+    bb = BucketBounds{bstart, nullptr, 0u};
+    return KSP_OK;
+}
+
+// The entries to their buckets, by the back-end the plan chose; bb says where each bucket lies.
+template <class V> int Stage1<V>::partition() {
+    if (const int rc = pp.seg ? partition_segment() : pp.nb_hand ? partition_paged() : partition_library()) return rc;
+    e->sort_entries = nw;
+    e->sort_bits = pb;
+    e->part_kind = (pp.seg || pp.seg3) ? 3 : pp.nb_hand ? 2 : 1;
+    e->fused_flags = false;
+    e->fused_used = 0;
+    return KSP_OK;
+}
+
+// What the hand-written partition reported (h_scal holds this build's words): an overflow — a tile or a bucket of the
+// segment partition (4 / 5): the paged levels from now on; page tables that could not hold these keys: the library
+// partition from now on — or the key range it found.
+template <class V> int Stage1<V>::partition_outcome() {
+    if (const u32 ovf = (u32)e->h_scal[PC_OVF]) {
+        if ((pp.seg || pp.seg3) && (ovf == 4 || ovf == 5)) e->seg_off = true;
+        else e->part_off = true;
+        e->part_fail = (int)ovf;
+        return S1_START_OVER;
+    }
+    e->max_key = e->h_scal[0];
+    e->have_max_key = true;
+    e->key_bits = key_bits_of(e->max_key);
+    return KSP_OK;
+}
+
+// the fine cell index was sized from the raw entries of a block; the lists are an order of magnitude shorter
+// (pruned, one word per key and block): ~32 words of an average list x 4 per cell is as fine as the join
+// ever looks (it merges cells up to ~216 keys anyway) — 16 x fewer bisections on C2 (32 -> 4 us)
+template <class V> void Stage1<V>::shrink_cells_and_index(const u64 K) {
+    const u64 avg = K / nb + 1;
+    u32 nc = NP;
+    while ((u64)nc * 32 < 4 * avg && nc < e->ncell) nc <<= 1;
+    e->ncell = std::min(e->ncell, nc);
+    hipLaunchKernelGGL(k_cidx, dim3(grid_for((u64)nb * (e->ncell + 1), bs)), dim3(bs), 0, st, e->bkeys.as<u32>(),
+                       blk_raw, blk_pos, scal, e->part.as<u32>(), nb, e->ncell);
+}
+
+// The bucket-resident middle of stage 1 (fused_kernels.hip.h): grouping + emit + labels in one kernel, the group records
+// straight to rank order, one read-back.  Unweighted whole builds on the hand-written partition whose blocks fit the
+// split's tables; anything it cannot take (an oversize bucket, sparse sharing) sets fused_off and the build starts over
+// pass by pass.  Measured on C2 (round 3): correct, 0.6 GB less HBM traffic per step, but 0.14 ms SLOWER than the
+// pass-by-pass kernels (bucket-at-a-time kernels are bound by LDS latency and barriers, not by HBM: DESIGN.md section 5)
+// — so it only runs when KSP_FUSED=1 asks for it (tests run both).  KSP_OK: not taken, group_buckets follows.
+template <class V> int Stage1<V>::fused_middle() {
+    const char* fv = std::getenv("KSP_FUSED");
+    const char* msv = std::getenv("KSP_MS");
+    const u32 ms_max = (msv && std::atoi(msv) == 1024) ? MS_MAXB : 256u;
+    const u64 Tt = (u64)nb * (nb + 1) / 2;
+    if (!(pp.nb_hand && phase == 0 && reorder && nb <= ms_max && nb <= FK_NB_MAX && Tt <= (1ull << 22) && !e->fused_off && !e->key_groups_off &&
+          (fv && std::atoi(fv) == 1) && !(msv && std::atoi(msv) == 0) && e->pre_zeroed_bits && e->pre_zeroed_work))
+        return KSP_OK;
+    int rc;
+    if ((rc = e->biglist.ensure(((size_t)nbuckets + 1) * 4))) return rc;
+    if ((rc = e->VA.ensure((pp.nslots + 4) * sizeof(V)))) return rc;
+    if ((rc = e->FK.ensure((pp.nslots / 2 + (u64)nbuckets + 16) * 4))) return rc;
+    if ((rc = e->mm.ensure((nw / (INLINE_MAX + 1) + 16) * 16))) return rc;   // (a mask per 5 kept entries at most)
+    bind();
+    u32* kst = (u32*)e->FK.p;
+    if ((rc = bucket_slots(e))) return rc;
+    // labels on lines of their own while they are lowered (the head of KB: no per-entry records on this path)
+    const u32 skip = label_sampling(e, (u64)((double)nw * e->kept_frac));
+    const int ls = e->KB.bytes >= (size_t)N * 128 && (size_t)N * 128 <= (size_t)(pp.nslots / 2) * 8 ? 5 : 0;
+    u32* lab = ls ? (u32*)e->KB.p : label;
+    if (ls) hipLaunchKernelGGL(k_label_spread, dim3(grid_for(N, bs)), dim3(bs), 0, st, lab, ls, N);
+    hipLaunchKernelGGL((k_fgroup<V>), dim3(std::min(nbuckets, e->hb_slots)), dim3(HB_THREADS), 0, st, KA, VB, bb, nbuckets, VA, kst,
+                       bsum, d_hovf(), e->biglist.as<u32>(), lab, ls, skip, label_max);
+    if ((rc = with_tmp(e, st, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, bsum, bbase, (u64)0, (size_t)nbuckets, rocprim::plus<u64>(), st); }))) return rc;
+    hipLaunchKernelGGL(k_ftotals, dim3(1), dim3(64), 0, st, bsum, bbase, nbuckets, scal);
+    phase_mark(e, st, "source labels + order");
+    if (ls) hipLaunchKernelGGL(k_label_gather, dim3(grid_for(N, bs)), dim3(bs), 0, st, lab, ls, label, N);
+    if ((rc = source_order())) return rc;
+    // the (block, key) groups, chunk by chunk, straight into rank order
+    phase_mark(e, st, "key groups");
+    u32 gb = 8;
+    if (const char* gv = std::getenv("KSP_DEBUG_FK_GB")) gb = (u32)std::min<int>(FK_GBMAX, std::max(1, std::atoi(gv)));   // (timing experiments)
+    const u32 chunks = grid_for(nbuckets, gb);
+    const u32 mb = nb <= 256 ? 256u : 1024u;
+    const u64 Kcap = nw;   // records <= kept entries <= entries
+    if ((rc = e->gp.ensure((Kcap + 4) * 12))) return rc;
+    e->gp_stride = Kcap + 4;
+    u64* rec_val = e->gp.as<u64>();
+    u32* rec_blk = (u32*)(rec_val + (Kcap + 4));
+    if ((rc = e->ms_hist.ensure(((size_t)chunks + 1) * mb * 4 + (size_t)chunks * 4 + 8192))) return rc;
+    u32* hist = e->ms_hist.as<u32>();
+    u32* tot = hist + (size_t)chunks * mb;
+    u32* nrec = tot + mb + 64;
+    FkOut fo{rec_blk, rec_val, nrec, hist, e->mm.as<uint4>(), e->dwork.as<unsigned long long>()};
+    if (mb == 256)
+        hipLaunchKernelGGL((k_fkeys<V, 256>), dim3(chunks), dim3(FK_THREADS), 0, st, VA, kst, bb, bsum, bbase, nbuckets, gb, newidx, N, nb, fo, scal);
+    else
+        hipLaunchKernelGGL((k_fkeys<V, 1024>), dim3(chunks), dim3(FK_THREADS), 0, st, VA, kst, bb, bsum, bbase, nbuckets, gb, newidx, N, nb, fo, scal);
+    e->pre_zeroed_work = false;
+    phase_mark(e, st, "block lists");
+    hipLaunchKernelGGL(k_fms_scan, dim3(nb), dim3(256), 0, st, hist, mb, chunks, scal, tot, blk_raw, blk_pos, nb);
+    KSP_HIP(hipMemcpyAsync(e->h_scal, scal, 120, hipMemcpyDeviceToHost, st));   // [0] max key, [1] list words, [2] keys, [6] entries, [9] / [14] overflow (one copy)
+    KSP_HIP(hipEventRecord(e->ev_rb, st));
+    hipLaunchKernelGGL(k_pad, dim3(nb + 1), dim3(256), 0, st, blk_raw, blk_pos, e->bkeys.as<u32>(), nb, PAD, scal);
+    if ((rc = e->pmask.ensure((Kcap + (u64)nb * (WIN + 4) + 4 * WIN) * 16))) return rc;
+    const size_t bit_words = (size_t)(((Tt + 63) / 64) * 2 + 2);
+    unsigned char* flags = (unsigned char*)e->tbits.p + bit_words * 4;
+    if (mb == 256)
+        hipLaunchKernelGGL((k_fms_place<256>), dim3(chunks), dim3(MS_THREADS), 0, st, rec_blk, rec_val, nrec, bbase, gb, hist, blk_pos, nb,
+                           e->bkeys.as<u32>(), e->info.as<u32>(), e->mm.as<uint4>(), e->pmask.as<uint4>(), flags, scal);
+    else
+        hipLaunchKernelGGL((k_fms_place<1024>), dim3(chunks), dim3(MS_THREADS), 0, st, rec_blk, rec_val, nrec, bbase, gb, hist, blk_pos, nb,
+                           e->bkeys.as<u32>(), e->info.as<u32>(), e->mm.as<uint4>(), e->pmask.as<uint4>(), flags, scal);
+    KSP_HIP(wait_readback(e));
+    if ((rc = partition_outcome())) return rc;
+    const char* jm = std::getenv("KSP_JOIN");
+    const bool want_matches = (jm && std::string(jm) == "matches") || (!jm && e->h_scal[6] < 4 * e->h_scal[1]);
+    if ((u32)(e->h_scal[9] >> 32) || (u32)e->h_scal[9] || want_matches) {   // an oversize bucket / sparse sharing: pass by pass from now on
+        e->fused_off = true;
+        return S1_START_OVER;
+    }
+    m = e->h_scal[6];
+    e->n_kept = m;
+    if (nw) e->kept_frac = std::max(0.05, (double)m / (double)nw);
+    e->rank1_ok = false;
+    e->fused_used = 1;
+    if (m == 0) return S1_DONE;
+    shrink_cells_and_index(std::max<u64>(1, e->h_scal[1]));
+    KSP_HIP(hipGetLastError());
+    e->pmask_on = true;
+    e->have_dwork = true;
+    e->have_rank_pairs = false;
+    e->fused_flags = true;
+    e->pre_zeroed_bits = false;
+    e->scal_fresh = true;
+    return S1_DONE;
+}
+
+// The buckets pass by pass: every bucket's keys grouped in an LDS table (k_bucket_group; k_bucket_big for those above its
+// capacity), ranks from a scan of the bucket totals, the kept entries emitted — and, while the host waits for the
+// counts, the label pass and the source order.
+template <class V> int Stage1<V>::group_buckets() {
+    int rc;
+    if ((rc = bucket_slots(e))) return rc;
+    // buckets above HB_CAP entries (d_hovf[1] counts them): a slot per bucket, so data whose keys have hundreds of
+    // holders each (C3: a third of the buckets at a mean of 2 000) stays on this path instead of falling back to the sort
+    if ((rc = e->biglist.ensure(((size_t)nbuckets + 1) * 4))) return rc;
+    u32* big_list = e->biglist.as<u32>();
+    hipLaunchKernelGGL(k_bucket_group, dim3(std::min(nbuckets, e->hb_slots)), dim3(HB_THREADS), 0, st, KA, bb,
+                       nbuckets, (u32)nw, rec, bsum, d_hovf(), big_list);
+    // (a rank per kept entry only when the sort-by-block fallback is known to follow: the key-by-key build reads crank[])
+    u32* rank_out = e->key_groups_off ? rank1 : nullptr;
+    e->rank1_ok = rank_out != nullptr;
+    hipLaunchKernelGGL((k_bucket_big<V, 0>), dim3(1024), dim3(HB_THREADS), 0, st, KA, VB, bb, big_list, d_hovf(),
+                       bsum, (const u64*)nullptr, VA, rank_out, first, crank);
+    if ((rc = with_tmp(e, st, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, bsum, bbase, (u64)0, (size_t)nbuckets, rocprim::plus<u64>(), st); }))) return rc;
+    hipLaunchKernelGGL((k_bucket_emit<V>), dim3((nbuckets + HB_EMIT - 1) / HB_EMIT), dim3(HB_THREADS), 0, st, rec, VB, bb,
+                       bbase, bsum, nbuckets, VA, rank_out, first, scal, crank);
+    hipLaunchKernelGGL((k_bucket_big<V, 1>), dim3(1024), dim3(HB_THREADS), 0, st, KA, VB, bb, big_list, d_hovf(),
+                       bsum, bbase, VA, rank_out, first, crank);
+    // [0] max key, [2] keys, [6] entries, [9] / [14] overflow.  The kept-entry count sizes every later pass — but the label
+    // pass can be queued without it (its key count comes from the device, its sampling rate from the kept fraction of
+    // the engine's previous build), so the device works on while the host waits for the words
+    if (reorder) {
+        phase_mark(e, st, "source labels + order");
+        label_pass(first, (u32)std::min<u64>(nw / 2 + 1, 0x7FFFFFFFu), (u64)((double)nw * e->kept_frac), scal,
+                   ride_readback(e, st, scal, e->h_scal, 15));   // (the words ride along with k_label)
+        labels_queued = true;
+        if (phase == 0) {   // (... and neither does the order of the sources need it: sort, block cuts and placement are queued too)
+            if ((rc = source_order())) return rc;
+            order_queued = true;
+        }
+        KSP_HIP(wait_readback(e));
+    } else {
+        KSP_HIP(hipMemcpyAsync(e->h_scal, scal, 120, hipMemcpyDeviceToHost, st));
+        KSP_HIP(hipStreamSynchronize(st));
+    }
+    if (pp.nb_hand && (rc = partition_outcome())) return rc;
+    e->big_buckets = (u32)(e->h_scal[9] >> 32);   // (d_hovf[1]: the oversize buckets k_bucket_group listed)
+    if ((u32)e->h_scal[9]) {   // a bucket did not fit (skewed keys): this engine sorts from now on
+        e->hash_off = true;
+        return S1_START_OVER;
+    }
+    return KSP_OK;
+}
+
+// No buckets.  Sort 1: all entries by the top 32 significant key bits (payload = tag [+weight]), d_keys,VA -> KA,VB; then
+// order the rare mixed runs by the full key (k_fix_runs); then singleton pruning + dense ranks.
+// (rocPRIM 4.2 / ROCm 7.2 mis-sorts 64-bit keys on any bit range [b > 0, 64) below ~1M items — found with a stand-alone
+//  sweep on MI355X; ranges ending below bit 64 are fine — so keys that use all 64 bits take the full-width sort.)
+template <class V> int Stage1<V>::sort_and_prune() {
+    const int kbits = e->key_bits;
+    const int shift = (e->full_sort || kbits >= 64) ? 0 : std::max(0, kbits - 32);
+    int rc;
+    KSP_HIP(hipMemsetAsync(d_ovf(), 0, 8, st));
+    if ((rc = with_tmp(e, st, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, keys_in, KA, tags_in, VB, nw, shift, kbits, st); }, e->time_sort))) return rc;
     e->sort_entries = nw;
     e->sort_bits = kbits - shift;
     e->part_kind = 1;
@@ -1371,56 +1361,90 @@ static int build_impl(ksp_engine* e, const u64* d_keys, const u32* d_w, hipStrea
         u32* d_cnt = (u32*)(scal + 5);
         KSP_HIP(hipMemsetAsync(d_cnt, 0, 8, st));
         hipLaunchKernelGGL(k_find_mixed, dim3(grid_for(nw, 4096)), dim3(1024), 0, st, KA, nw, shift, fixlist, d_cnt,
-                           fixcap, d_ovf);
-        hipLaunchKernelGGL(k_mark_first, dim3(4096), dim3(64), 0, st, KA, shift, fixlist, d_cnt, fixcap, d_ovf);
+                           fixcap, d_ovf());
+        hipLaunchKernelGGL(k_mark_first, dim3(4096), dim3(64), 0, st, KA, shift, fixlist, d_cnt, fixcap, d_ovf());
         hipLaunchKernelGGL((k_fix_runs<V>), dim3(2048), dim3(256), 0, st, KA, VB, nw, shift, fixlist, d_cnt, fixcap,
-                           d_ovf);
+                           d_ovf());
     }
     // singleton pruning + dense ranks of the kept keys (packed counters, one scan):  KA,VB -> R1 (ranks), VA (tags)
     // (the scan's output iterator scatters entry e as soon as its prefix sums are known: no second pass)
-    {
-        auto pf = rocprim::make_transform_iterator(rocprim::make_counting_iterator<u64>(0), PruneFn{KA, nw});
-        PruneScatterIt<V> out{{KA, VB, VA, rank1, first, scal, nw}, 0};
-        tb = 0;
-        KSP_HIP(rocprim::inclusive_scan(nullptr, tb, pf, out, nw, rocprim::plus<u64>(), st));
-        if ((rc = e->tmp.ensure(tb))) return rc;
-        KSP_HIP(rocprim::inclusive_scan(e->tmp.p, tb, pf, out, nw, rocprim::plus<u64>(), st));
-    }
+    auto pf = rocprim::make_transform_iterator(rocprim::make_counting_iterator<u64>(0), PruneFn{KA, nw});
+    PruneScatterIt<V> out{{KA, VB, VA, rank1, first, scal, nw}, 0};
+    if ((rc = with_tmp(e, st, [&](void* t, size_t& b) { return rocprim::inclusive_scan(t, b, pf, out, nw, rocprim::plus<u64>(), st); }))) return rc;
     KSP_HIP(hipMemcpyAsync(e->h_scal + 2, scal + 2, 40, hipMemcpyDeviceToHost, st));   // [2] keys ... [6] entries (one copy)
     KSP_HIP(hipStreamSynchronize(st));   // the kept-entry count sizes every later pass
     e->rank1_ok = true;   // (the prune scan writes a rank per kept entry)
     if (e->h_scal[6])
         hipLaunchKernelGGL(k_crank_from_rank, dim3(grid_for(e->h_scal[6] / CR_CHUNK + 1, bs)), dim3(bs), 0, st, rank1, crank, (u32)e->h_scal[6]);
-    }
+    return KSP_OK;
+}
+
+// the kept entries are counted (h_scal[6]): the label pass, unless it was queued with the grouping
+template <class V> int Stage1<V>::kept_and_labels() {
     m = e->h_scal[6];
     e->n_kept = m;
     if (nw) e->kept_frac = std::max(0.05, (double)m / (double)nw);
-    if (m == 0 && phase == 0) return KSP_OK;   // no key is shared by two sources: no pair at all
+    if (m == 0 && phase == 0) return S1_DONE;   // no key is shared by two sources: no pair at all
     if (reorder && m && !labels_queued) {
         // label = smallest source id among the holders of a source's shared keys
         phase_mark(e, st, "source labels + order");
-        run_label(first, (u32)e->h_scal[2], m);
+        label_pass(first, (u32)e->h_scal[2], m);
     }
-    if (phase == 1) return KSP_OK;
-    }   // phase != 2
-    Stage1<V> s1{e, st, phase, n, N, nb, KA, VA, VB, scal, blk_raw, blk_pos, rank1, crank, label, iota, labs, order, newidx, sbound,
-                 sorted_src, blk_src, bbits, reorder, hand_zeroed, m};
-    if (reorder && !order_queued && (rc = stage1_source_order(s1))) return rc;
-    if (m == 0) return KSP_OK;
-    e->have_rank_pairs = false;
-    e->have_dwork = false;
-    if (!e->key_groups_off && m < (1ull << 32) - KG_CHUNK) {
-        bool done = false;
-        if ((rc = stage1_lists_by_key(s1, done)) || done) return rc;
-    }
-    return stage1_lists_by_sort(s1);
+    return phase == 1 ? S1_DONE : KSP_OK;
 }
 
-// tag type of a build: 64-bit (weighted), compact 16-bit (unweighted, <= 65536 sources) or canonical 32-bit
+// One attempt at stage 1.  phase 0: the whole of it;  1: up to the source labels (key-range slice, before the labels of all
+// slices are combined);  2: the rest (source order from the final labels, block lists);  3: postings input
+// (ksp_engine_build_postings);  4: a slice of a postings input — stops at the labels, ksp_engine_slice_finish runs phase 2.
+// Returns S1_DONE / S1_START_OVER too: call it through build_to_end.
+template <class V>
+static int build_impl(ksp_engine* e, const u64* d_keys, const u32* d_w, hipStream_t st, const int phase) {
+    Stage1<V> c(e, d_keys, d_w, st, phase);
+    int rc;
+    if ((rc = c.setup())) return rc;
+    if (phase == 3 || phase == 4) {
+        if ((rc = c.from_postings())) return rc;
+        if (phase == 4) return S1_DONE;
+    } else if (phase != 2) {
+        c.pp = c.plan_partition();
+        if ((rc = c.tags_and_sizes())) return rc;
+        if ((rc = c.slice_range())) return rc;
+        c.bucket_layout();
+        if (c.pb) {
+            if ((rc = c.partition())) return rc;
+            if constexpr (!Stage1<V>::W) {
+                if ((rc = c.fused_middle())) return rc;
+            }
+            if ((rc = c.group_buckets())) return rc;
+        } else if ((rc = c.sort_and_prune())) {
+            return rc;
+        }
+        if ((rc = c.kept_and_labels())) return rc;
+    }
+    if (c.reorder && !c.order_queued && (rc = c.source_order())) return rc;
+    if (c.m == 0) return S1_DONE;
+    e->have_rank_pairs = false;
+    e->have_dwork = false;
+    bool done = false;
+    if ((rc = c.lists_by_key(done)) || done) return rc;
+    return c.lists_by_sort();
+}
+
+// A build whose keys defeat the path it began on (S1_START_OVER: the engine remembers which) is made again from the top.
+template <class V>
+static int build_to_end(ksp_engine* e, const u64* d_keys, const u32* d_w, hipStream_t st, const int phase) {
+    int rc;
+    do {
+        rc = build_impl<V>(e, d_keys, d_w, st, phase);
+    } while (rc == S1_START_OVER);
+    return rc == S1_DONE ? KSP_OK : rc;
+}
+
+// tag type of a build: 64-bit (weighted), compact 16-bit (unweighted, <= 65536 sources) or canonical 32-bit.
 static int build_dispatch(ksp_engine* e, const u64* d_keys, const u32* d_w, hipStream_t st, const int phase) {
-    if (e->weighted) return build_impl<u64>(e, d_keys, d_w, st, phase);
-    if (e->n_sources <= 65536u && !std::getenv("KSP_TAG32")) return build_impl<u16>(e, d_keys, d_w, st, phase);
-    return build_impl<u32>(e, d_keys, d_w, st, phase);
+    if (e->weighted) return build_to_end<u64>(e, d_keys, d_w, st, phase);
+    if (e->n_sources <= 65536u && !std::getenv("KSP_TAG32")) return build_to_end<u16>(e, d_keys, d_w, st, phase);
+    return build_to_end<u32>(e, d_keys, d_w, st, phase);
 }
 
 // host-side bookkeeping once the full block lists sit in the engine's arrays

@@ -1,7 +1,7 @@
 // Stage 1 of the engine: device kernels that turn the sketches (sorted uint64 runs) — or an inverted
 // index — into per-block posting lists, the source order and the join's tile bitmap.
 // Included by engine.hip inside namespace ksp (one translation unit: the kernels are templates over the
-// tag type and share the constants defined there).  Host orchestration: build_impl in engine.hip.
+// tag type and share the constants defined there).  Host orchestration: the steps of Stage1, in build_impl's order (engine.hip).
 #pragma once
 
 // Entry tags.  Canonical form: (block << 8) | local id in 32 bits; weighted input carries the key's weight in
