@@ -366,6 +366,44 @@ int ksp_single_linkage_prim(int device, uint32_t n, const double* d_rows, double
 int ksp_row_distances(int device, uint32_t n, const double* d_rows, double* h_dist);
 int ksp_csv_float(const char* text, double* out);
 
+/* ---- representative sketches (the reference's tool `repr_sketches`, apps/repr_sketches.cpp:27-33,38-43) -----------------
+ * The tool reads PREFIX_kSpider_pairwise.tsv: a row passes when stof(text of column 4, avg_containment) > 0.20 (the float
+ * promoted to double, strictly; a NaN never passes), a passing row counts one neighbour for both of its ids, and the ids
+ * with a count are printed as "id: count" lines, largest count first.  The order among equal counts is not pinned by the
+ * reference (an unstable sort over a hash map's iteration order); here it is canonical: count descending, then id
+ * ascending.  The text of a float has 6 significant digits, so the test on a float is not `v > threshold`: it is
+ * monotone, and one critical float decides it (0.20: bit pattern 0x3e4cccac, 0.199999511 — it prints "0.2").
+ * ksp_edges_degrees: the neighbour counts straight over the join's edge records.  d_edges: `n_edges` ksp_edge records in
+ *   DEVICE memory, in any order, every record counted; d_kmer_counts[v] = k-mer count of source v (device memory); dist_col
+ *   3 min, 4 avg (the reference's), 5 max containment, single-precision maths of src/pairwise.cpp:260-264.  h_degree[v] (host,
+ *   n_nodes entries) = number of records naming v whose column passes the text test against `threshold`.  An edge naming a
+ *   node >= n_nodes is the caller's error, as for ksp_components_edges: it is not counted and not reported.
+ * ksp_edges_repr: the same counts ranked on the device: h_node[i] / h_count[i] for i < *n_ranked are the nodes with a
+ *   non-zero count in (count descending, node ascending) order; both arrays hold n_nodes entries.
+ *   Both: KSP_E_ARG for a NULL pointer with n_edges > 0, a column other than 3 / 4 / 5 and a NaN threshold; KSP_E_LIMIT for
+ *   2^32 edges or more (the counters are 32-bit).  n_edges = 0: all-zero degrees, *n_ranked = 0, no kernel runs.
+ * ksp_repr_critical: host only — the smallest non-negative float that passes the text test for `threshold`
+ *   ("%.6g" text -> strtof -> as double -> > threshold); *none_pass = 1 when not even +inf passes (nothing is counted).
+ * kspider_repr_sketches: the tool itself over an existing TSV of any producer, rows in any order: the host parses columns
+ *   0, 1 and dist_type ("min_cont" 3, "avg_cont" 4 = NULL / "", "max_cont" 5; "ani" is refused with KSP_E_ARG) and applies
+ *   the text test, the device counts and ranks.  The reference call is (tsv, "avg_cont", 0.20, NULL).  out_path NULL / "":
+ *   stdout, as the reference; otherwise through out_path.partial and a rename, and on any error nothing is left behind.
+ *   KSP_E_IO (naming the line) for a row with too few columns or a value that is not a number / an id that is not a decimal
+ *   integer (the reference throws there); KSP_E_ARG for an id outside [0, 2^31 - 1] (the reference reads ids with stoi).
+ *   Device = $KSPIDER_DEVICE (default 0).
+ * kspider_pairwise_and_repr: kspider_pairwise followed by the tool in ONE device pass: the same two TSVs byte for byte, plus
+ *   the ranking (out_path NULL / "": PREFIX_kSpider_repr_sketches.txt), counted from the edges while they are in HBM; ids
+ *   are the index's group ids.  KSP_E_LIMIT, before any file is written, when a group id exceeds 2^31 - 1.  Works with
+ *   $KSPIDER_DEVICES like kspider_pairwise.                                                                              */
+int ksp_edges_degrees(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
+                      int dist_col, double threshold, uint32_t* h_degree);
+int ksp_edges_repr(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
+                   int dist_col, double threshold, uint32_t* h_node, uint32_t* h_count, uint32_t* n_ranked);
+int ksp_repr_critical(double threshold, float* vcrit, int* none_pass);
+int kspider_repr_sketches(const char* pairwise_tsv, const char* dist_type, double threshold, const char* out_path);
+int kspider_pairwise_and_repr(const char* index_prefix, int user_threads, const char* dist_type, double threshold,
+                              const char* out_path);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

@@ -32,6 +32,7 @@
 
 #include "../../include/kspider_amd.h"
 #include "ani.h"
+#include "edge_cut.hip.h"
 #include "engine_internal.h"
 
 typedef uint32_t u32;
@@ -61,21 +62,7 @@ __global__ void k_cc_jump(u32* __restrict__ parent, u32 n, u32* __restrict__ cha
 }
 
 // The same pass straight over the join's edge records (ksp_edge, device memory): an edge counts when its containment
-// column — single-precision maths of the pairwise writer, index_io.cpp::format_rows = src/pairwise.cpp:260-264 — is not
-// below the cut.  `vcrit` is the smallest float the reference's test (text of the float with 6 significant digits ->
-// Python float -> x 100 -> not below cutoff x 100, ks_clustering.py:101-105) lets through: that test is monotone in the
-// float, so one compare against the critical value found on the host (ksp::cc_critical) IS that test, digit for digit.
-// mode 1: no finite value passes, only NaN rows do (a NaN is never "below": kept, as in the reference).
-__device__ inline bool cc_edge_kept(const ksp_edge& x, const u32* __restrict__ cnt, const int col, const float vcrit, const int mode) {
-    const float n1 = (float)cnt[x.source_1], n2 = (float)cnt[x.source_2];
-    const float c12 = (float)x.shared / n2, c21 = (float)x.shared / n1;
-    float v;
-    if (col == 3) v = c21 < c12 ? c21 : c12;        // std::min(c12, c21)
-    else if (col == 5) v = c12 < c21 ? c21 : c12;   // std::max(c12, c21)
-    else v = (float)((double)(c12 + c21) / 2.0);
-    if (mode) return v != v;
-    return !(v < vcrit);
-}
+// column is not below the cut (cc_edge_kept, edge_cut.hip.h: one compare against the critical float of ksp::cc_critical).
 __global__ void k_cc_hook_edges(const ksp_edge* __restrict__ ed, u64 m, const u32* __restrict__ cnt, const int col, const float vcrit,
                                 const int mode, u32* __restrict__ parent, u32* __restrict__ changed, unsigned long long* __restrict__ kept) {
     unsigned long long mine = 0;

@@ -2983,6 +2983,7 @@ struct MultiJob {
     u32 n_keys = 0, n_sources = 0;
     bool postings = false;
     ksp::CcRequest* cc = nullptr;   // also wanted: the components of the result, from the edges while they are on the device
+    ksp::ReprRequest* repr = nullptr;   // also wanted: the neighbour counts of the result and their ranking, likewise
 };
 }  // namespace
 
@@ -3234,6 +3235,22 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
                 }
                 d_cnt.release();
             }
+            if (job.repr && job.repr->node && job.repr->count) {   // representatives from HBM: neighbour counts of the same edge records
+                job.repr->node->assign((size_t)N, 0);
+                job.repr->count->assign((size_t)N, 0);
+                u32 n_ranked = 0;
+                Buf d_cnt;
+                if (N && ((rc = d_cnt.ensure((size_t)N * 4)) || (rc = ksp_memcpy_h2d(d_cnt.p, job.repr->kmer_counts, (u64)N * 4)) ||
+                          (rc = repr_edges_on_device(N, d_all, total, d_cnt.as<u32>(), job.repr->col, job.repr->threshold, nullptr,
+                                                     job.repr->node->data(), job.repr->count->data(), &n_ranked)))) {
+                    d_cnt.release();
+                    fail(rc);
+                    return;
+                }
+                d_cnt.release();
+                job.repr->node->resize(n_ranked);
+                job.repr->count->resize(n_ranked);
+            }
             ksp_edge* out = (ksp_edge*)alloc_result(total * sizeof(ksp_edge));
             if (!out) { set_error("pairwise_host: out of pinned host memory"); fail(KSP_E_LIMIT); return; }
             if (total && (rc = ksp_memcpy_d2h(out, d_all, total * sizeof(ksp_edge)))) { ksp_free(out); fail(rc); return; }
@@ -3291,7 +3308,7 @@ int ksp_debug_sttime(unsigned long long* out64, int reset) {
 }  // extern "C"
 int ksp::pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                     uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
-                                    ksp_stats* stats, CcRequest* cc) {
+                                    ksp_stats* stats, CcRequest* cc, ReprRequest* repr) {
     if (!out_edges || !n_edges || !devices || (n_keys && (!key_off || !sources))) { set_error("pairwise_postings_host: NULL argument"); return KSP_E_ARG; }
     const u64 n = n_keys ? key_off[n_keys] : 0;
     for (u64 i = 0; i < n; ++i)
@@ -3300,6 +3317,7 @@ int ksp::pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sou
     job.postings = true;
     job.key_off = key_off; job.sources = sources; job.key_weights = key_weights; job.n_keys = n_keys; job.n_sources = n_sources;
     job.cc = cc;
+    job.repr = repr;
     return run_multi(job, devices, n_devices, out_edges, n_edges, stats);
 }
 extern "C" {

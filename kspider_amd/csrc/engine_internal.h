@@ -35,9 +35,29 @@ struct CcRequest {
     std::vector<uint32_t>* labels = nullptr; // out: per source index, the smallest index of its component
     uint64_t n_kept = 0;                     // out: edges that passed the cut
 };
+// ---- neighbour counts straight from the join's edges (repr.hip; apps/repr_sketches.cpp) ----
+// the text test of the reference on one float: "%.6g" text -> strtof -> as double -> > threshold
+bool repr_text_passes(float v, double threshold);
+// the smallest non-negative float that passes it (*none_pass = 1: not even +inf passes, nothing is counted)
+void repr_critical(double threshold, float* vcrit, int* none_pass);
+// neighbour counts of the edges among d_edges (device memory of the CURRENT device) whose column col passes the text test,
+// and their ranking by (count descending, node ascending); see ksp_edges_degrees / ksp_edges_repr.  h_degree (n_nodes
+// entries) or h_node / h_count / n_ranked may be NULL: that half is not computed.
+int repr_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, double threshold,
+                         uint32_t* h_degree, uint32_t* h_node, uint32_t* h_count, uint32_t* n_ranked);
+// "id: count\n" per ranked node (id = ids[node]) to out_path through out_path.partial and a rename, or to stdout ("")
+void write_repr_file(const std::string& out_path, const std::vector<uint32_t>& ids, const uint32_t* node, const uint32_t* count, uint64_t n_ranked);
+// a drop-in call that also wants the ranking of its result, taken from the edges while they are in HBM
+struct ReprRequest {
+    const uint32_t* kmer_counts = nullptr;   // per (dense) source index
+    int col = 4;                             // 3 / 4 / 5
+    double threshold = 0.20;
+    std::vector<uint32_t>* node = nullptr;   // out: the sources with a neighbour, (count descending, index ascending)
+    std::vector<uint32_t>* count = nullptr;  // out: their counts
+};
 int pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
-                               ksp_stats* stats, CcRequest* cc);
+                               ksp_stats* stats, CcRequest* cc, ReprRequest* repr = nullptr);
 }
 
 extern "C" {

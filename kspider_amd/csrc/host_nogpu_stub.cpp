@@ -15,17 +15,35 @@ void set_error(const std::string& s) { g_error = s; }
 
 namespace ksp {
 int pairwise_postings_multi_cc(const uint64_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, const int*, int, ksp_edge**,
-                               uint64_t*, ksp_stats*, CcRequest*) {
+                               uint64_t*, ksp_stats*, CcRequest*, ReprRequest*) {
     set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }
 void cc_critical(double, float* vcrit, int* mode) { *vcrit = 0; *mode = 0; }
 void read_names_map(const std::string&, std::vector<std::string>& name_of) { name_of.clear(); }
 void write_cluster_file(const std::string&, double, const std::vector<uint32_t>&, const std::vector<std::string>&) {}
+bool repr_text_passes(float, double) { return false; }
+void write_repr_file(const std::string&, const std::vector<uint32_t>&, const uint32_t*, const uint32_t*, uint64_t) {}
 }  // namespace ksp
 
 extern "C" {
 const char* ksp_last_error(void) { return ksp::g_error.c_str(); }
+int ksp_edges_degrees(int, uint32_t, const ksp_edge*, uint64_t, const uint32_t*, int, double, uint32_t*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_edges_repr(int, uint32_t, const ksp_edge*, uint64_t, const uint32_t*, int, double, uint32_t*, uint32_t*, uint32_t*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_repr_critical(double, float*, int*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int kspider_repr_sketches(const char*, const char*, double, const char*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
 void ksp_free(void* p) { std::free(p); }
 int ksp_pairwise_host_multi(const uint64_t*, const uint32_t*, const uint64_t*, uint32_t, const int*, int, ksp_edge**,
                             uint64_t*, ksp_stats*) {

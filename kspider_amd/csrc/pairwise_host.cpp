@@ -56,7 +56,14 @@ double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock:
 // dist_type != nullptr: also cluster (kSpider cluster, ks_clustering.py:63-137) from the edges while they are on the device
 // ani: also write the ANI column of `pairwise --estimate-ani` (ks_pairwise.py:29-84; k from PREFIX.extra); dist_type "ani"
 // then clusters on it
-int run_pairwise(const std::string& prefix, int user_threads, const char* dist_type = nullptr, double cutoff = 0, bool ani = false) {
+// repr: also rank the sources by their neighbour counts (apps/repr_sketches.cpp:27-33,38-43), likewise from the edges on the device
+struct ReprOpts {
+    int col = 4;
+    double threshold = 0.20;
+    std::string out_path;   // "": PREFIX_kSpider_repr_sketches.txt
+};
+int run_pairwise(const std::string& prefix, int user_threads, const char* dist_type = nullptr, double cutoff = 0, bool ani = false,
+                 const ReprOpts* repr = nullptr) {
     int cc_col = 0, ksize = 0;
     std::shared_ptr<const std::vector<double>> ani_tab;
     if (ani) {   // before anything is read or written: the k-mer size (:44-46) and its table
@@ -74,6 +81,13 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
     auto t0 = Clock::now();
     ksp::IndexData ix;
     ksp::load_index(prefix, ix);
+    if (repr)   // the reference tool reads the ids with stoi: refused before any file is written
+        for (auto& c : ix.colors)
+            for (uint32_t g : c.second)
+                if (g > 2147483647u) {
+                    ksp::set_error("kspider_pairwise_and_repr: group id " + std::to_string(g) + " exceeds 2^31 - 1 (the reference tool reads ids as int)");
+                    return KSP_E_LIMIT;
+                }
     std::cout << "mapping colors to groups: " << since(t0) << " secs" << std::endl;
     t0 = Clock::now();
     std::cout << "parsing index colors: " << since(t0) << " secs" << std::endl;
@@ -162,16 +176,19 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
     auto t1 = Clock::now();
     ksp::CcRequest cc;
     std::vector<uint32_t> cc_counts, cc_labels;
-    if (cc_col) {
+    ksp::ReprRequest rq;
+    std::vector<uint32_t> rq_node, rq_count;
+    if (cc_col || repr) {
         cc_counts.resize(N);
         for (uint32_t i = 0; i < N; ++i) {
             auto it = kmer_count.find(ids[i]);
             cc_counts[i] = it == kmer_count.end() ? 0u : it->second;   // (a missing group counts 0 k-mers, as operator[] of the reference yields)
         }
         cc.kmer_counts = cc_counts.data(); cc.col = cc_col; cc.cutoff = cutoff; cc.labels = &cc_labels; cc.ksize = ksize;
+        if (repr) { rq.kmer_counts = cc_counts.data(); rq.col = repr->col; rq.threshold = repr->threshold; rq.node = &rq_node; rq.count = &rq_count; }
     }
     int rc = ksp::pairwise_postings_multi_cc(key_off.data(), post_src.data(), key_w.data(), (uint32_t)key_w.size(), N,
-                                             devices.data(), (int)devices.size(), &edges, &n_edges, &st, cc_col ? &cc : nullptr);
+                                             devices.data(), (int)devices.size(), &edges, &n_edges, &st, cc_col ? &cc : nullptr, repr ? &rq : nullptr);
     const double t_device = since(t1);
     if (rc != KSP_OK) return rc;
     std::vector<ksp::EdgeRow> rows;
@@ -220,6 +237,38 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
     }
     if (std::getenv("KSPIDER_VERBOSE"))
         std::cout << "kspider_amd: sources=" << N << " colour-entries=" << E << " pairs=" << rows.size() << std::endl;
+    if (repr) {
+        // rows that only exist with shared_kmers = 0 (colours of weight 0) are rows of the TSV too: their value is 0 or NaN, which
+        // passes a negative threshold only — the same text test, on the host, and the ranking redone with their counts
+        std::vector<uint32_t> extra;
+        for (auto& zp : zero_pairs) {
+            auto it = std::lower_bound(rows.begin(), rows.end(), zp, [](const ksp::EdgeRow& r, const std::pair<uint32_t, uint32_t>& k) {
+                return r.source_1 != k.first ? r.source_1 < k.first : r.source_2 < k.second;
+            });
+            if (it == rows.end() || it->source_1 != zp.first || it->source_2 != zp.second || it->shared != 0) continue;
+            const uint32_t a = dense(zp.first), b = dense(zp.second);
+            const float n1 = (float)cc_counts[a], n2 = (float)cc_counts[b];
+            const float c12 = 0.0f / n2, c21 = 0.0f / n1;
+            const float v = repr->col == 3 ? std::min(c12, c21) : repr->col == 5 ? std::max(c12, c21) : (float)((c12 + c21) / 2.0);
+            if (!ksp::repr_text_passes(v, repr->threshold)) continue;
+            extra.push_back(a);
+            extra.push_back(b);
+        }
+        if (!extra.empty()) {
+            std::vector<uint32_t> degree((size_t)N, 0);
+            for (size_t i = 0; i < rq_node.size(); ++i) degree[rq_node[i]] = rq_count[i];
+            for (uint32_t v : extra) ++degree[v];
+            rq_node.clear();
+            for (uint32_t v = 0; v < N; ++v)
+                if (degree[v]) rq_node.push_back(v);
+            std::stable_sort(rq_node.begin(), rq_node.end(), [&](uint32_t x, uint32_t y) { return degree[x] > degree[y]; });
+            rq_count.resize(rq_node.size());
+            for (size_t i = 0; i < rq_node.size(); ++i) rq_count[i] = degree[rq_node[i]];
+        }
+        ksp::write_repr_file(repr->out_path.empty() ? prefix + "_kSpider_repr_sketches.txt" : repr->out_path, ids, rq_node.data(), rq_count.data(),
+                             rq_node.size());
+        if (std::getenv("KSPIDER_VERBOSE")) std::cout << "kspider_amd: " << rq_node.size() << " sources with a neighbour ranked" << std::endl;
+    }
     if (cc_col) {
         // the cluster file of `kSpider cluster` from the components the device found on the join's own edge records
         std::vector<std::string> name_of;
@@ -302,6 +351,27 @@ extern "C" int kspider_pairwise_and_cluster(const char* index_prefix, int user_t
         return KSP_E_LIMIT;
     } catch (const std::exception& e) {
         ksp::set_error(e.what());
+        const std::string m = e.what();
+        return m.find("2^32") != std::string::npos ? KSP_E_LIMIT : KSP_E_IO;
+    }
+}
+
+extern "C" int kspider_pairwise_and_repr(const char* index_prefix, int user_threads, const char* dist_type, double threshold, const char* out_path) {
+    if (!index_prefix) { ksp::set_error("kspider_pairwise_and_repr: index_prefix is NULL"); return KSP_E_ARG; }
+    if (threshold != threshold) { ksp::set_error("kspider_pairwise_and_repr: the threshold is NaN"); return KSP_E_ARG; }
+    ReprOpts opts;
+    const std::string dt = dist_type && *dist_type ? dist_type : "avg_cont";
+    opts.col = dt == "min_cont" ? 3 : dt == "avg_cont" ? 4 : dt == "max_cont" ? 5 : 0;
+    if (!opts.col) { ksp::set_error("kspider_pairwise_and_repr: distance '" + dt + "' is not min_cont, avg_cont or max_cont"); return KSP_E_ARG; }
+    opts.threshold = threshold;
+    if (out_path) opts.out_path = out_path;
+    try {
+        return run_pairwise(index_prefix, user_threads < 1 ? 1 : user_threads, nullptr, 0, false, &opts);
+    } catch (const std::bad_alloc&) {
+        ksp::set_error("kspider_pairwise_and_repr: out of host memory");
+        return KSP_E_LIMIT;
+    } catch (const std::exception& e) {
+        ksp::set_error(std::string("kspider_pairwise_and_repr: ") + e.what());
         const std::string m = e.what();
         return m.find("2^32") != std::string::npos ? KSP_E_LIMIT : KSP_E_IO;
     }

@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "ksp_components_edges_ani", "ksp_ani_value", "ksp_ani_values", "ksp_format_ani",
     "kspider_export", "ksp_single_linkage_rows", "ksp_single_linkage_prim", "ksp_row_distances",
     "ksp_csv_float",
+    "ksp_edges_degrees", "ksp_edges_repr", "ksp_repr_critical", "kspider_repr_sketches", "kspider_pairwise_and_repr",
 ]
 
 
@@ -161,6 +162,13 @@ def lib():
         L.ksp_single_linkage_prim.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
         L.ksp_row_distances.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
         L.ksp_csv_float.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double)]
+        L.ksp_edges_degrees.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
+                                        ctypes.c_double, ctypes.c_void_p]
+        L.ksp_edges_repr.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
+                                     ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+        L.ksp_repr_critical.argtypes = [ctypes.c_double, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
+        L.kspider_repr_sketches.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double, ctypes.c_char_p]
+        L.kspider_pairwise_and_repr.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_double, ctypes.c_char_p]
         _lib = L
     return _lib
 
@@ -261,6 +269,51 @@ def components_edges(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts
     _check(L.ksp_components_edges(device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, dist_col, float(cutoff),
                                   out.ctypes.data))
     return out[:n_nodes]
+
+
+def edges_degrees(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, dist_col: int = 4, threshold: float = 0.20,
+                  device: int = 0) -> np.ndarray:
+    """Neighbour counts over ksp_edge records in DEVICE memory (apps/repr_sketches.cpp): degree[v] = records naming v whose
+    containment column passes the reference's text test against `threshold` (include/kspider_amd.h)."""
+    out = np.zeros(max(1, n_nodes), dtype=np.uint32)
+    _check(lib().ksp_edges_degrees(device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, int(dist_col), float(threshold),
+                                   out.ctypes.data))
+    return out[:n_nodes]
+
+
+def edges_repr(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, dist_col: int = 4, threshold: float = 0.20,
+               device: int = 0) -> tuple:
+    """(nodes, counts): the nodes with a neighbour, ranked on the device by (count descending, node ascending)."""
+    node = np.zeros(max(1, n_nodes), dtype=np.uint32)
+    count = np.zeros(max(1, n_nodes), dtype=np.uint32)
+    n = ctypes.c_uint32(0)
+    _check(lib().ksp_edges_repr(device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, int(dist_col), float(threshold),
+                                node.ctypes.data, count.ctypes.data, ctypes.byref(n)))
+    return node[:n.value].copy(), count[:n.value].copy()
+
+
+def repr_critical(threshold: float = 0.20) -> tuple:
+    """(vcrit, none_pass): the smallest non-negative float whose 6-digit text, read back with strtof, is > threshold, as a
+    numpy float32; none_pass: not even +inf passes.  Host only."""
+    v = ctypes.c_float(0)
+    none = ctypes.c_int(0)
+    _check(lib().ksp_repr_critical(float(threshold), ctypes.byref(v), ctypes.byref(none)))
+    return np.float32(v.value), bool(none.value)
+
+
+def repr_sketches(pairwise_tsv: str, dist_type: str | None = None, threshold: float = 0.20, out_path: str | None = None) -> None:
+    """The reference's `repr_sketches TSV` over an existing pairwise TSV: "id: count" lines, count descending then id
+    ascending, to out_path (None: stdout).  The device counts and ranks."""
+    _check(lib().kspider_repr_sketches(os.fsencode(pairwise_tsv), dist_type.encode() if dist_type is not None else None, float(threshold),
+                                       os.fsencode(out_path) if out_path else None))
+
+
+def pairwise_and_repr(index_prefix: str, user_threads: int = 1, dist_type: str | None = None, threshold: float = 0.20,
+                      out_path: str | None = None) -> None:
+    """`kSpider pairwise` + `repr_sketches` in one device pass: both TSVs as kspider_pairwise writes them, plus the ranking
+    (None: PREFIX_kSpider_repr_sketches.txt), counted from the edges while they are in HBM."""
+    _check(lib().kspider_pairwise_and_repr(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
+                                           float(threshold), os.fsencode(out_path) if out_path else None))
 
 
 def estimate_ani(index_prefix: str, user_threads: int, scale: int) -> None:
