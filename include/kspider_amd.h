@@ -404,6 +404,39 @@ int kspider_repr_sketches(const char* pairwise_tsv, const char* dist_type, doubl
 int kspider_pairwise_and_repr(const char* index_prefix, int user_threads, const char* dist_type, double threshold,
                               const char* out_path);
 
+/* ---- the containment cut: a minimum containment on the producer -------------------------------------------
+ * A row is kept exactly when `kSpider cluster -d DIST -c CUTOFF` would keep it (ks_clustering.py:101-105): text of the
+ * column's float with 6 significant digits -> Python float -> x 100 -> not below cutoff x 100; a NaN row is kept.  The test
+ * is monotone in the float, so the device makes one compare against the critical float, as ksp_components_edges does.
+ * Guarantee: after kspider_pairwise_cut(PREFIX, T, D, c), kspider_cluster(PREFIX, D, c') for any c' with
+ * c' x 100 >= c x 100 writes the same cluster file, byte for byte, as over the full TSV.
+ * ksp_edges_cut: the device part alone — a STABLE compaction.  d_edges: `n_edges` ksp_edge records in DEVICE memory, in any
+ *   order, never written; d_kmer_counts[v] = k-mer count of source v (device memory); dist_col 3 min, 4 avg, 5 max
+ *   containment, single-precision maths of src/pairwise.cpp:260-264.  The kept records go to d_out[0 .. *n_kept) (device
+ *   memory with room for n_edges records, or for as many as are kept) in their input order; d_out[*n_kept ..] is not written.
+ *   KSP_E_ARG for a NULL pointer with n_edges > 0, a column other than 3 / 4 / 5, a NaN cut-off and d_out overlapping
+ *   d_edges.  n_edges = 0: *n_kept = 0, no kernel runs.  Every count and offset is 64-bit: 2^32 records or more are not
+ *   refused.  An edge naming a node outside the counts is the caller's error, as for ksp_components_edges.
+ *   KSP_CUT_CHUNK_EDGES: records per chunk of the two passes (one 64-bit count per chunk).
+ * ksp_pairwise_host_cut: ksp_pairwise_host_multi with the cut made on every device directly after its join: only the kept
+ *   edges are gathered, sorted and copied.  kmer_counts[v] = k-mer count of source v (host; NULL: the run lengths
+ *   offsets[v + 1] - offsets[v]).  *out_edges / *n_edges: the kept edges sorted by (source_1, source_2) (ksp_free);
+ *   *n_found (may be NULL): the edges before the cut; stats->last_edges is the kept total.  KSP_E_ARG as above.
+ * kspider_pairwise_cut: kspider_pairwise with the cut: PREFIX_kSpider_pairwise.tsv holds the kept rows in (source_1, source_2)
+ *   order, rows that exist only with shared_kmers = 0 (colours of weight 0) tested the same way on the host;
+ *   PREFIX_kSpider_seqToKmersNo.tsv is never affected.  dist_type "min_cont", "avg_cont", "max_cont" (NULL / "": max_cont);
+ *   "ani" and a cut-off outside kspider_cluster's range [0, 1] (or NaN) are refused with KSP_E_ARG before any file is
+ *   written.  Works with $KSPIDER_DEVICE / $KSPIDER_DEVICES like kspider_pairwise; with $KSPIDER_VERBOSE one line reports
+ *   the rows found and kept.  The cut TSV is a valid input of kspider_cluster / kspider_export / kspider_repr_sketches at
+ *   cut-offs not below the cut.                                                                                          */
+#define KSP_CUT_CHUNK_EDGES 2048u
+int ksp_edges_cut(int device, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col, double cutoff,
+                  ksp_edge* d_out, uint64_t* n_kept);
+int ksp_pairwise_host_cut(const uint64_t* keys, const uint32_t* weights, const uint64_t* offsets, uint32_t n_sources,
+                          const uint32_t* kmer_counts, int dist_col, double cutoff, const int* devices, int n_devices,
+                          ksp_edge** out_edges, uint64_t* n_edges, uint64_t* n_found, ksp_stats* stats);
+int kspider_pairwise_cut(const char* index_prefix, int user_threads, const char* dist_type, double cutoff);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

@@ -2984,6 +2984,7 @@ struct MultiJob {
     bool postings = false;
     ksp::CcRequest* cc = nullptr;   // also wanted: the components of the result, from the edges while they are on the device
     ksp::ReprRequest* repr = nullptr;   // also wanted: the neighbour counts of the result and their ranking, likewise
+    ksp::CutRequest* cut = nullptr;     // only the edges that pass a containment cut are wanted: cut on every device, directly after its join
 };
 }  // namespace
 
@@ -3001,6 +3002,8 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
     *out_edges = nullptr;
     *n_edges = 0;
     if (nd < 1 || nd > 64) { set_error("pairwise: between 1 and 64 devices"); return KSP_E_ARG; }
+    if (job.cut && (job.cc || job.repr)) { set_error("pairwise: a cut together with the clustering or the ranking of the same job is not offered"); return KSP_E_ARG; }
+    if (job.cut) job.cut->n_found = 0;
     const u32 N = job.n_sources;
     const u64 n = job.postings ? (job.n_keys ? job.key_off[job.n_keys] : 0) : (N ? job.offsets[N] : 0);
     // A sketch set of 2^30 entries or more does not fit one build (32-bit entry positions): it is cut into hash-range
@@ -3055,7 +3058,7 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
         ksp_engine* e = nullptr;
         void *d_a = nullptr, *d_b = nullptr;      // keys + weights, or sources + key weights
         Buf edges, labels, gather[6], exp[6];
-        u64 count = 0, sizes[4] = {0, 0, 0, 0};
+        u64 count = 0, found = 0, sizes[4] = {0, 0, 0, 0};   // count: edges I hand on; found: edges of my join (the same without a cut)
         std::vector<u64> cuts;
         float ms_join = 0;
         int rc = KSP_OK;
@@ -3207,10 +3210,33 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
                 }
         if (sync_point()) return;
         if ((rc = join_range_grow(D.e, D.cuts[(size_t)i], D.cuts[(size_t)i + 1], D.edges, D.count, D.ms_join))) fail(rc);
+        D.found = D.count;
+        if (!rc && job.cut && D.count) {   // the cut, on my own edges: what follows (gather, sort, copy) sees the kept records only
+            Buf d_cnt, kept;
+            CutPass pass;
+            u64 n_kept = 0;
+            if ((rc = d_cnt.ensure((size_t)N * 4)) || (rc = ksp_memcpy_h2d(d_cnt.p, job.cut->kmer_counts, (u64)N * 4)) ||
+                (rc = cut_count_on_device(D.edges.as<ksp_edge>(), D.count, d_cnt.as<u32>(), job.cut->col, job.cut->cutoff, pass, &n_kept)))
+                fail(rc);
+            else if (n_kept == D.count) {}   // (every record passes: they stay where they are)
+            else if (n_kept == 0) D.count = 0;
+            else if ((rc = kept.ensure(n_kept * sizeof(ksp_edge))) ||   // (sized by the count pass's total, not by the input)
+                     (rc = cut_scatter_on_device(D.edges.as<ksp_edge>(), D.count, d_cnt.as<u32>(), job.cut->col, pass, kept.as<ksp_edge>())))
+                fail(rc);
+            else {
+                D.edges.release();
+                D.edges = kept;
+                kept = Buf();
+                D.count = n_kept;
+            }
+            pass.release(); d_cnt.release(); kept.release();
+        }
         if (sync_point()) return;
         if (i == 0) {
             for (int j = 0; j < nd; ++j) edge_off[(size_t)j + 1] = edge_off[(size_t)j] + dev[(size_t)j].count;
             total = edge_off[(size_t)nd];
+            if (job.cut)
+                for (int j = 0; j < nd; ++j) job.cut->n_found += dev[(size_t)j].found;
             if (nd > 1 && total && (rc = merged.ensure(total * sizeof(ksp_edge)))) fail(rc);
         }
         if (sync_point()) return;
@@ -3308,7 +3334,7 @@ int ksp_debug_sttime(unsigned long long* out64, int reset) {
 }  // extern "C"
 int ksp::pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                     uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
-                                    ksp_stats* stats, CcRequest* cc, ReprRequest* repr) {
+                                    ksp_stats* stats, CcRequest* cc, ReprRequest* repr, CutRequest* cut) {
     if (!out_edges || !n_edges || !devices || (n_keys && (!key_off || !sources))) { set_error("pairwise_postings_host: NULL argument"); return KSP_E_ARG; }
     const u64 n = n_keys ? key_off[n_keys] : 0;
     for (u64 i = 0; i < n; ++i)
@@ -3318,6 +3344,7 @@ int ksp::pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sou
     job.key_off = key_off; job.sources = sources; job.key_weights = key_weights; job.n_keys = n_keys; job.n_sources = n_sources;
     job.cc = cc;
     job.repr = repr;
+    job.cut = cut;
     return run_multi(job, devices, n_devices, out_edges, n_edges, stats);
 }
 extern "C" {
@@ -3328,6 +3355,33 @@ int ksp_pairwise_host_multi(const uint64_t* keys, const uint32_t* weights, const
     MultiJob job;
     job.keys = keys; job.weights = weights; job.offsets = offsets; job.n_sources = n_sources;
     return run_multi(job, devices, n_devices, out_edges, n_edges, stats);
+}
+
+int ksp_pairwise_host_cut(const uint64_t* keys, const uint32_t* weights, const uint64_t* offsets, uint32_t n_sources,
+                          const uint32_t* kmer_counts, int dist_col, double cutoff, const int* devices, int n_devices,
+                          ksp_edge** out_edges, uint64_t* n_edges, uint64_t* n_found, ksp_stats* stats) {
+    if (!offsets || !out_edges || !n_edges || !devices) { set_error("ksp_pairwise_host_cut: NULL argument"); return KSP_E_ARG; }
+    if (dist_col < 3 || dist_col > 5) { set_error("ksp_pairwise_host_cut: dist_col is 3 (min), 4 (avg) or 5 (max containment)"); return KSP_E_ARG; }
+    if (cutoff != cutoff) { set_error("ksp_pairwise_host_cut: the cut-off is NaN"); return KSP_E_ARG; }
+    std::vector<u32> lengths;
+    if (!kmer_counts) {   // the k-mer count of a source is the length of its run
+        lengths.resize(n_sources);
+        for (u32 v = 0; v < n_sources; ++v) {
+            const u64 len = offsets[v + 1] - offsets[v];
+            if (len > 0xFFFFFFFFull) { set_error("ksp_pairwise_host_cut: a run of 2^32 keys or more"); return KSP_E_LIMIT; }
+            lengths[v] = (u32)len;
+        }
+        kmer_counts = lengths.data();
+    }
+    CutRequest cut;
+    cut.kmer_counts = kmer_counts; cut.col = dist_col; cut.cutoff = cutoff;
+    MultiJob job;
+    job.keys = keys; job.weights = weights; job.offsets = offsets; job.n_sources = n_sources;
+    job.cut = &cut;
+    if (n_found) *n_found = 0;
+    const int rc = run_multi(job, devices, n_devices, out_edges, n_edges, stats);
+    if (!rc && n_found) *n_found = cut.n_found;
+    return rc;
 }
 
 int ksp_pairwise_postings_host_multi(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights,

@@ -55,14 +55,39 @@ struct ReprRequest {
     std::vector<uint32_t>* node = nullptr;   // out: the sources with a neighbour, (count descending, index ascending)
     std::vector<uint32_t>* count = nullptr;  // out: their counts
 };
+// ---- the containment cut on the join's edges, before they are gathered, sorted and copied (cut.hip) ----
+// what the count pass leaves for the scatter pass (device memory of the device it ran on; release() frees it)
+struct CutPass {
+    uint64_t n_chunks = 0;
+    uint64_t* d_off = nullptr;                 // n_chunks + 1 exclusive offsets: the last is the total
+    unsigned long long* d_ballots = nullptr;   // one kept bit per record, or NULL: the scatter evaluates the predicate again
+    float vcrit = 0;                           // cc_critical of the cut-off
+    int mode = 0;
+    void release();
+};
+// count + scan over d_edges (device memory of the CURRENT device): *n_kept = records whose column col is kept by cc_edge_kept
+int cut_count_on_device(const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, double cutoff, CutPass& pass, uint64_t* n_kept);
+// the kept records into d_out (room for *n_kept of them), in their input order; nothing behind them is written
+int cut_scatter_on_device(const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, const CutPass& pass, ksp_edge* d_out);
+// a job whose edges are cut on every device directly after its join: only the kept ones are gathered, sorted and copied
+struct CutRequest {
+    const uint32_t* kmer_counts = nullptr;   // per (dense) source index
+    int col = 5;                             // 3 / 4 / 5
+    double cutoff = 0;
+    uint64_t n_found = 0;                    // out: edges before the cut, summed over the devices
+};
 int pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
-                               ksp_stats* stats, CcRequest* cc, ReprRequest* repr = nullptr);
+                               ksp_stats* stats, CcRequest* cc, ReprRequest* repr = nullptr, CutRequest* cut = nullptr);
 }
 
 extern "C" {
 /* test/diagnostic hook: distinct-key offsets of the block lists (nb + 1 values). */
 int ksp_engine_block_key_counts(const ksp_engine* e, uint32_t* h_blk_off);
 int ksp_engine_source_order(const ksp_engine* e, uint32_t* h_newidx);   // (diagnostics) engine index of every source
+/* (tools/cut_times.py) HIP-event times of `reps` cuts of one list: which 0 = hand-written, predicate evaluated in both passes,
+ * 1 = hand-written with kept ballots, 2 = rocprim::select with the same predicate. */
+int ksp_debug_cut_times(int device, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col, double cutoff,
+                        ksp_edge* d_out, int which, int reps, float* ms, uint64_t* n_kept);
 }
 #endif

@@ -15,7 +15,7 @@ void set_error(const std::string& s) { g_error = s; }
 
 namespace ksp {
 int pairwise_postings_multi_cc(const uint64_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, const int*, int, ksp_edge**,
-                               uint64_t*, ksp_stats*, CcRequest*, ReprRequest*) {
+                               uint64_t*, ksp_stats*, CcRequest*, ReprRequest*, CutRequest*) {
     set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }
@@ -41,6 +41,15 @@ int ksp_repr_critical(double, float*, int*) {
     return KSP_E_HIP;
 }
 int kspider_repr_sketches(const char*, const char*, double, const char*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_edges_cut(int, const ksp_edge*, uint64_t, const uint32_t*, int, double, ksp_edge*, uint64_t*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_pairwise_host_cut(const uint64_t*, const uint32_t*, const uint64_t*, uint32_t, const uint32_t*, int, double, const int*, int, ksp_edge**,
+                          uint64_t*, uint64_t*, ksp_stats*) {
     ksp::set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }

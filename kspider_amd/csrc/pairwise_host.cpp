@@ -62,8 +62,13 @@ struct ReprOpts {
     double threshold = 0.20;
     std::string out_path;   // "": PREFIX_kSpider_repr_sketches.txt
 };
+// cut: only the rows that pass a containment cut are wanted (kspider_pairwise_cut): the edges are cut on the device, directly after the join
+struct CutOpts {
+    int col = 5;
+    double cutoff = 0;
+};
 int run_pairwise(const std::string& prefix, int user_threads, const char* dist_type = nullptr, double cutoff = 0, bool ani = false,
-                 const ReprOpts* repr = nullptr) {
+                 const ReprOpts* repr = nullptr, const CutOpts* cut = nullptr) {
     int cc_col = 0, ksize = 0;
     std::shared_ptr<const std::vector<double>> ani_tab;
     if (ani) {   // before anything is read or written: the k-mer size (:44-46) and its table
@@ -178,7 +183,8 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
     std::vector<uint32_t> cc_counts, cc_labels;
     ksp::ReprRequest rq;
     std::vector<uint32_t> rq_node, rq_count;
-    if (cc_col || repr) {
+    ksp::CutRequest cq;
+    if (cc_col || repr || cut) {
         cc_counts.resize(N);
         for (uint32_t i = 0; i < N; ++i) {
             auto it = kmer_count.find(ids[i]);
@@ -186,9 +192,11 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
         }
         cc.kmer_counts = cc_counts.data(); cc.col = cc_col; cc.cutoff = cutoff; cc.labels = &cc_labels; cc.ksize = ksize;
         if (repr) { rq.kmer_counts = cc_counts.data(); rq.col = repr->col; rq.threshold = repr->threshold; rq.node = &rq_node; rq.count = &rq_count; }
+        if (cut) { cq.kmer_counts = cc_counts.data(); cq.col = cut->col; cq.cutoff = cut->cutoff; }
     }
     int rc = ksp::pairwise_postings_multi_cc(key_off.data(), post_src.data(), key_w.data(), (uint32_t)key_w.size(), N,
-                                             devices.data(), (int)devices.size(), &edges, &n_edges, &st, cc_col ? &cc : nullptr, repr ? &rq : nullptr);
+                                             devices.data(), (int)devices.size(), &edges, &n_edges, &st, cc_col ? &cc : nullptr, repr ? &rq : nullptr,
+                                             cut ? &cq : nullptr);
     const double t_device = since(t1);
     if (rc != KSP_OK) return rc;
     std::vector<ksp::EdgeRow> rows;
@@ -200,13 +208,43 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
         std::sort(zero_pairs.begin(), zero_pairs.end());
         zero_pairs.erase(std::unique(zero_pairs.begin(), zero_pairs.end()), zero_pairs.end());
         const size_t nreal = rows.size();
+        float vcrit = 0;
+        int mode = 0;
+        if (cut) ksp::cc_critical(cut->cutoff, &vcrit, &mode);
+        const bool device_drops = mode || vcrit > 0;   // (otherwise every row passes: no value is negative)
+        std::vector<std::pair<uint32_t, uint32_t>> unsure;   // kept as a shared-0 row, unless the device dropped a real row of the pair
         for (auto& zp : zero_pairs) {
+            if (cut) {   // a row that exists only with shared_kmers = 0: the same test with the same vcrit / mode, on the host
+                const float n1 = (float)cc_counts[dense(zp.first)], n2 = (float)cc_counts[dense(zp.second)];
+                const float c12 = 0.0f / n2, c21 = 0.0f / n1;
+                const float v = cut->col == 3 ? std::min(c12, c21) : cut->col == 5 ? std::max(c12, c21) : (float)((c12 + c21) / 2.0);
+                if (!(mode ? v != v : !(v < vcrit))) continue;
+            }
             auto it = std::lower_bound(rows.begin(), rows.begin() + nreal, zp,
                                        [](const ksp::EdgeRow& r, const std::pair<uint32_t, uint32_t>& k) {
                                            return r.source_1 != k.first ? r.source_1 < k.first : r.source_2 < k.second;
                                        });
-            if (it == rows.begin() + nreal || it->source_1 != zp.first || it->source_2 != zp.second)
-                rows.push_back(ksp::EdgeRow{zp.first, zp.second, 0});
+            if (it == rows.begin() + nreal || it->source_1 != zp.first || it->source_2 != zp.second) {
+                if (cut && device_drops) unsure.push_back(zp);
+                else rows.push_back(ksp::EdgeRow{zp.first, zp.second, 0});
+            }
+        }
+        if (!unsure.empty()) {
+            // Only a NaN row gets here (a source of 0 k-mers): its pair is not among the kept rows, so either it shares no weighted
+            // colour — the shared-0 row is a row of the full TSV, and kept — or the device dropped its real row.  The colours decide.
+            std::vector<uint8_t> real(unsure.size(), 0);
+            for (auto& c : ix.colors) {
+                uint32_t w = 0;
+                if (c.second.size() < 2 || !ix.colors_count.find(c.first, w) || w == 0) continue;
+                std::vector<uint32_t> members(c.second.begin(), c.second.end());
+                std::sort(members.begin(), members.end());
+                for (size_t u = 0; u < unsure.size(); ++u)
+                    if (!real[u] && std::binary_search(members.begin(), members.end(), unsure[u].first) &&
+                        std::binary_search(members.begin(), members.end(), unsure[u].second))
+                        real[u] = 1;
+            }
+            for (size_t u = 0; u < unsure.size(); ++u)
+                if (!real[u]) rows.push_back(ksp::EdgeRow{unsure[u].first, unsure[u].second, 0});
         }
         std::sort(rows.begin(), rows.end(), [](const ksp::EdgeRow& a, const ksp::EdgeRow& b) {
             return a.source_1 != b.source_1 ? a.source_1 < b.source_1 : a.source_2 < b.source_2;
@@ -237,6 +275,9 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
     }
     if (std::getenv("KSPIDER_VERBOSE"))
         std::cout << "kspider_amd: sources=" << N << " colour-entries=" << E << " pairs=" << rows.size() << std::endl;
+    if (cut && std::getenv("KSPIDER_VERBOSE"))
+        std::cout << "kspider_amd: cut at " << cut->cutoff << " on column " << cut->col << ": " << cq.n_found << " edges found on the device, " << n_edges
+                  << " kept; " << rows.size() << " rows written" << std::endl;
     if (repr) {
         // rows that only exist with shared_kmers = 0 (colours of weight 0) are rows of the TSV too: their value is 0 or NaN, which
         // passes a negative threshold only — the same text test, on the host, and the ranking redone with their counts
@@ -372,6 +413,32 @@ extern "C" int kspider_pairwise_and_repr(const char* index_prefix, int user_thre
         return KSP_E_LIMIT;
     } catch (const std::exception& e) {
         ksp::set_error(std::string("kspider_pairwise_and_repr: ") + e.what());
+        const std::string m = e.what();
+        return m.find("2^32") != std::string::npos ? KSP_E_LIMIT : KSP_E_IO;
+    }
+}
+
+extern "C" int kspider_pairwise_cut(const char* index_prefix, int user_threads, const char* dist_type, double cutoff) {
+    if (!index_prefix) { ksp::set_error("kspider_pairwise_cut: index_prefix is NULL"); return KSP_E_ARG; }
+    CutOpts opts;
+    const std::string dt = dist_type && *dist_type ? dist_type : "max_cont";
+    opts.col = dt == "min_cont" ? 3 : dt == "avg_cont" ? 4 : dt == "max_cont" ? 5 : 0;
+    if (!opts.col) {
+        ksp::set_error("kspider_pairwise_cut: distance '" + dt + "' is not min_cont, avg_cont or max_cont" + (dt == "ani" ? " (the ANI column as the cut is not offered)" : ""));
+        return KSP_E_ARG;
+    }
+    if (!(cutoff >= 0.0 && cutoff <= 1.0)) {   // (kSpider cluster's -c: a float in [0, 1]; a NaN fails both compares)
+        ksp::set_error("kspider_pairwise_cut: the cut-off is not in [0, 1]");
+        return KSP_E_ARG;
+    }
+    opts.cutoff = cutoff;
+    try {
+        return run_pairwise(index_prefix, user_threads < 1 ? 1 : user_threads, nullptr, 0, false, nullptr, &opts);
+    } catch (const std::bad_alloc&) {
+        ksp::set_error("kspider_pairwise_cut: out of host memory");
+        return KSP_E_LIMIT;
+    } catch (const std::exception& e) {
+        ksp::set_error(std::string("kspider_pairwise_cut: ") + e.what());
         const std::string m = e.what();
         return m.find("2^32") != std::string::npos ? KSP_E_LIMIT : KSP_E_IO;
     }

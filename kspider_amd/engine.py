@@ -18,6 +18,9 @@ EDGE_DTYPE = np.dtype([("source_1", "<u4"), ("source_2", "<u4"), ("shared", "<u8
 
 KSP_OK, KSP_E_ARG, KSP_E_HIP, KSP_E_IO, KSP_E_OVERFLOW, KSP_E_LIMIT = range(6)
 
+#: records per chunk of the containment cut's two passes (kCutChunkEdges in csrc/cut.hip = KSP_CUT_CHUNK_EDGES in the header)
+CUT_CHUNK_EDGES = 2048
+
 #: every symbol include/kspider_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "ksp_last_error", "ksp_device_count", "ksp_engine_create", "ksp_engine_destroy",
@@ -38,6 +41,7 @@ ABI_SYMBOLS = [
     "kspider_export", "ksp_single_linkage_rows", "ksp_single_linkage_prim", "ksp_row_distances",
     "ksp_csv_float",
     "ksp_edges_degrees", "ksp_edges_repr", "ksp_repr_critical", "kspider_repr_sketches", "kspider_pairwise_and_repr",
+    "ksp_edges_cut", "ksp_pairwise_host_cut", "kspider_pairwise_cut",
 ]
 
 
@@ -169,6 +173,12 @@ def lib():
         L.ksp_repr_critical.argtypes = [ctypes.c_double, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
         L.kspider_repr_sketches.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double, ctypes.c_char_p]
         L.kspider_pairwise_and_repr.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_double, ctypes.c_char_p]
+        L.ksp_edges_cut.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
+                                    ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+        L.ksp_pairwise_host_cut.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(Stats)]
+        L.kspider_pairwise_cut.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_double]
         _lib = L
     return _lib
 
@@ -314,6 +324,49 @@ def pairwise_and_repr(index_prefix: str, user_threads: int = 1, dist_type: str |
     (None: PREFIX_kSpider_repr_sketches.txt), counted from the edges while they are in HBM."""
     _check(lib().kspider_pairwise_and_repr(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
                                            float(threshold), os.fsencode(out_path) if out_path else None))
+
+
+def edges_cut(d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, d_out_ptr: int, dist_col: int = 5, cutoff: float = 0.0,
+              device: int = 0) -> int:
+    """The containment cut over ksp_edge records in DEVICE memory (include/kspider_amd.h): the records `kSpider cluster`
+    would keep for this column and cut-off go to d_out in their input order; returns how many.  d_out[kept:] is not written."""
+    n = ctypes.c_uint64(0)
+    _check(lib().ksp_edges_cut(device, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, int(dist_col), float(cutoff),
+                               d_out_ptr or None, ctypes.byref(n)))
+    return int(n.value)
+
+
+def pairwise_host_cut(keys: np.ndarray, offsets: np.ndarray, weights: np.ndarray | None = None, kmer_counts: np.ndarray | None = None,
+                      dist_col: int = 5, cutoff: float = 0.0, devices=(0,)):
+    """pairwise_host with the containment cut made on every device directly after its join: (kept edges sorted by
+    (source_1, source_2), edges found before the cut, stats).  kmer_counts None: the run lengths."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint32)
+    kc = None if kmer_counts is None else np.ascontiguousarray(kmer_counts, dtype=np.uint32)
+    if kc is not None and kc.size != offsets.size - 1:
+        raise ValueError("kmer_counts needs one entry per source")
+    out = ctypes.c_void_p()
+    ne = ctypes.c_uint64(0)
+    nf = ctypes.c_uint64(0)
+    st = Stats()
+    devs = (ctypes.c_int * len(devices))(*devices)
+    _check(lib().ksp_pairwise_host_cut(keys.ctypes.data, w.ctypes.data if w is not None else None, offsets.ctypes.data, offsets.size - 1,
+                                       kc.ctypes.data if kc is not None else None, int(dist_col), float(cutoff), devs, len(devs),
+                                       ctypes.byref(out), ctypes.byref(ne), ctypes.byref(nf), ctypes.byref(st)))
+    try:
+        buf = (ctypes.c_char * (ne.value * EDGE_DTYPE.itemsize)).from_address(out.value) if ne.value else b""
+        edges = np.frombuffer(buf, dtype=EDGE_DTYPE).copy()
+    finally:
+        lib().ksp_free(out)
+    return edges, int(nf.value), st.as_dict()
+
+
+def pairwise_cut(index_prefix: str, user_threads: int = 1, dist_type: str = "max_cont", cutoff: float = 0.0) -> None:
+    """`kSpider pairwise` with a minimum containment: the pairwise TSV holds only the rows `kSpider cluster -d DIST -c CUTOFF`
+    would keep, cut on the device before the sort, the copy and the text; seqToKmersNo is not affected."""
+    _check(lib().kspider_pairwise_cut(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
+                                      float(cutoff)))
 
 
 def estimate_ani(index_prefix: str, user_threads: int, scale: int) -> None:
