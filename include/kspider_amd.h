@@ -437,6 +437,42 @@ int ksp_pairwise_host_cut(const uint64_t* keys, const uint32_t* weights, const u
                           ksp_edge** out_edges, uint64_t* n_edges, uint64_t* n_found, ksp_stats* stats);
 int kspider_pairwise_cut(const char* index_prefix, int user_threads, const char* dist_type, double cutoff);
 
+/* ---- the cut-off ladder: the clusters at a list of cut-offs in one device pass ----------------------------
+ * "Kept" means for every cut-off what it means to kspider_cluster / ksp_components_edges: columns 3 / 4 / 5 against the
+ * critical float of the cut-off (a NaN is kept), the ANI column (file path only) by !(value x 100 < cutoff x 100) in double.
+ * Ordered by strictness the cut-offs an edge passes are the L least strict ones; L, 0 .. n_cutoffs, is the edge's level (a
+ * NaN: n_cutoffs), and the clustering of the cut-off at strictness rank r is the components of the edges with L > r.  The
+ * device classifies every edge once, sorts the edges of level >= 1 into one band per level and computes the components
+ * band by band, strictest first, continuing on the labels of the ranks before.  Cut-offs come in any order and may repeat;
+ * results are in the caller's order.  1 <= n_cutoffs <= KSP_SWEEP_MAX_CUTOFFS (a level fits a byte), else KSP_E_ARG.
+ * ksp_components_edges_sweep: d_edges: `n_edges` ksp_edge records in DEVICE memory, never written; d_kmer_counts and dist_col
+ *   (3 / 4 / 5) as for ksp_components_edges.  h_labels: n_cutoffs x n_nodes, row i = the labels ksp_components_edges gives for
+ *   cutoffs[i] (label = smallest node of the component); h_kept (may be NULL): edges kept per cut-off.  KSP_E_ARG for a NULL
+ *   pointer, a column other than 3 / 4 / 5 and a NaN cut-off; KSP_E_LIMIT, before anything is written, when the level bytes
+ *   (n_edges), the bands (8 bytes per edge of level >= 1) and (n_cutoffs + 1) x n_nodes labels do not fit the device's free
+ *   memory.  $KSP_SWEEP_MAX_WORKGROUPS caps the grids of both passes (tests).  KSP_SWEEP_CHUNK_EDGES: records per chunk.
+ * ksp_components_sweep: the same for HOST edges that are already classified: level[e] in 0 .. n_levels; row r of h_labels
+ *   (n_levels x n_nodes) = the components of the edges with level > r.  KSP_E_ARG for a level above n_levels and for an edge
+ *   of level >= 1 naming a node >= n_nodes (an edge of level 0 is never looked at).
+ * kspider_cluster_sweep: kspider_cluster at every cut-off of the list from ONE reading of its files (same validation, same
+ *   refusals, "ani" through PREFIX_kSpider_pairwise.ani_col.tsv): one PREFIX_kSpider_clusters_<cutoff*100>%.tsv per distinct
+ *   cut-off, name and bytes as kspider_cluster writes them (a repeated name is written once), and
+ *   PREFIX_kSpider_cluster_sweep_<dist_type>.tsv: "cutoff_percent\tedges\tclusters\tsingletons\tlargest", one row per distinct
+ *   cut-off, ascending; cutoff_percent is the text in the cluster file's name, edges the rows kept.  Every refusal comes
+ *   before any file is written; on an error no new file and no .partial is left.
+ * kspider_pairwise_and_cluster_sweep: kspider_pairwise_and_cluster with the list: the pairwise TSV of kspider_pairwise, the
+ *   ladder from the gathered, sorted edges on the first device, rows that exist only with shared_kmers = 0 classified on the
+ *   host and united into every rank they pass; the same cluster files and summary.  "ani" is refused, as there.        */
+#define KSP_SWEEP_CHUNK_EDGES 2048u
+#define KSP_SWEEP_MAX_CUTOFFS 255u
+int ksp_components_edges_sweep(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
+                               int dist_col, const double* cutoffs, uint32_t n_cutoffs, uint32_t* h_labels, uint64_t* h_kept);
+int ksp_components_sweep(int device, uint32_t n_nodes, const uint32_t* h_a, const uint32_t* h_b, const uint8_t* h_level, uint64_t n_edges,
+                         uint32_t n_levels, uint32_t* h_labels);
+int kspider_cluster_sweep(const char* index_prefix, const char* dist_type, const double* cutoffs, uint32_t n_cutoffs);
+int kspider_pairwise_and_cluster_sweep(const char* index_prefix, int user_threads, const char* dist_type, const double* cutoffs,
+                                       uint32_t n_cutoffs);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

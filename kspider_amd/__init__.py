@@ -7,6 +7,7 @@ Host-side mirror of the reference interface for this one path:
   kspider_amd.pairwise_ani(index_prefix, threads, scale[, cutoff])  pairwise + ANI column (+ `cluster -d ani`) in one pass
   kspider_amd.export(index_prefix, dist_type, newick, out_prefix)  == `kSpider export` (ks_export.py), linkage on the GPU
   kspider_amd.pairwise_cut(index_prefix, threads, dist_type, cutoff)  pairwise with a minimum containment, cut on the GPU
+  kspider_amd.cluster_sweep(index_prefix, dist_type, cutoffs)  `kSpider cluster` at a list of cut-offs in one device pass
   kspider_amd.engine                                   ctypes binding of include/kspider_amd.h
   kspider_amd.dist                                     tile sharding + edge gather for one-process-per-GPU runs
   kspider_amd.synth                                    synthetic sketch sets shaped like BASELINE.json's configs
@@ -14,8 +15,10 @@ The compute lives in kspider_amd/lib/libkspider_amd.so (hand-written HIP, gfx950
 falls back to the CPU.
 """
 from .engine import cluster, estimate_ani, export, pairwise, pairwise_ani, pairwise_bins, pairwise_sigs  # noqa: F401
+from .engine import cluster_sweep, pairwise_and_cluster_sweep  # noqa: F401
 from .engine import single_linkage_rows  # noqa: F401
 from .engine import CUT_CHUNK_EDGES, edges_cut, pairwise_cut, pairwise_host_cut  # noqa: F401
 
 __all__ = ["pairwise", "pairwise_sigs", "pairwise_bins", "cluster", "estimate_ani", "pairwise_ani", "export",
-           "single_linkage_rows", "pairwise_cut", "pairwise_host_cut", "edges_cut", "CUT_CHUNK_EDGES"]
+           "single_linkage_rows", "pairwise_cut", "pairwise_host_cut", "edges_cut", "CUT_CHUNK_EDGES",
+           "cluster_sweep", "pairwise_and_cluster_sweep"]

@@ -18,6 +18,7 @@
 //
 // Device side: min-label hooking + pointer jumping (every parent[] only ever decreases, parent[v] <= v): when
 // nothing changes any more every tree is a star whose root is the smallest node of its component.
+#include <algorithm>
 #include <charconv>
 #include <cstdint>
 #include <cstdio>
@@ -32,6 +33,7 @@
 
 #include "../../include/kspider_amd.h"
 #include "ani.h"
+#include "cc_kernels.hip.h"
 #include "edge_cut.hip.h"
 #include "engine_internal.h"
 
@@ -39,27 +41,6 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 
 namespace {
-
-__global__ void k_cc_init(u32* __restrict__ parent, u32 n) {
-    const u32 v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v < n) parent[v] = v;
-}
-// one pass over the edges: the larger of the two labels is lowered to the smaller one
-__global__ void k_cc_hook(const u32* __restrict__ a, const u32* __restrict__ b, u64 m, u32* __restrict__ parent,
-                          u32* __restrict__ changed) {
-    for (u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += (u64)gridDim.x * blockDim.x) {
-        const u32 pu = parent[a[e]], pv = parent[b[e]];
-        if (pu == pv) continue;
-        const u32 hi = pu > pv ? pu : pv, lo = pu > pv ? pv : pu;
-        if (atomicMin(&parent[hi], lo) > lo) *changed = 1;
-    }
-}
-__global__ void k_cc_jump(u32* __restrict__ parent, u32 n, u32* __restrict__ changed) {
-    const u32 v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= n) return;
-    const u32 p = parent[v], gp = parent[p];
-    if (gp != p) { parent[v] = gp; *changed = 1; }
-}
 
 // The same pass straight over the join's edge records (ksp_edge, device memory): an edge counts when its containment
 // column is not below the cut (cc_edge_kept, edge_cut.hip.h: one compare against the critical float of ksp::cc_critical).
@@ -452,64 +433,75 @@ done:
     return rc;
 }
 
+namespace {
+// column of a distance name (6 = the ANI column file), 0 when unknown
+int cluster_col(const std::string& dt) { return dt == "min_cont" ? 3 : dt == "avg_cont" ? 4 : dt == "max_cont" ? 5 : dt == "ani" ? 6 : 0; }
+
+// The inputs of `kSpider cluster`, read and validated as ks_clustering.py does (:48-61, :67-105): name_of from .namesMap, then
+// row(a, b, d) for every pairwise row, a / b its ids and d its column (col 6: its line of the ANI column file) times 100.
+template <class Row>
+void read_cluster_inputs(const std::string& prefix, const int col, std::vector<std::string>& name_of, Row&& row) {
+    std::string line;
+    {   // _kSpider_seqToKmersNo.tsv must be there and well-formed (load_seq_to_kmers, :48-53); its values are not used
+        std::ifstream f(prefix + "_kSpider_seqToKmersNo.tsv");
+        if (!f) throw std::runtime_error("cannot open " + prefix + "_kSpider_seqToKmersNo.tsv");
+        std::getline(f, line);
+        std::vector<std::string> p;
+        while (std::getline(f, line)) {
+            split_tabs(strip(line), p);
+            long long a, b;
+            if (p.size() != 3 || !parse_id(p[1], a) || !parse_id(p[2], b))
+                throw std::runtime_error("malformed row in " + prefix + "_kSpider_seqToKmersNo.tsv");
+        }
+    }
+    ksp::read_names_map(prefix, name_of);
+    std::ifstream f(prefix + "_kSpider_pairwise.tsv");
+    if (!f) throw std::runtime_error("cannot open " + prefix + "_kSpider_pairwise.tsv");
+    std::ifstream ani;
+    if (col == 6) {
+        ani.open(prefix + "_kSpider_pairwise.ani_col.tsv");
+        if (!ani) throw std::runtime_error("ANI was selected, but " + prefix + "_kSpider_pairwise.ani_col.tsv was not found");
+        std::getline(ani, line);
+    }
+    std::getline(f, line);   // header
+    std::vector<std::string> p;
+    std::string aline;
+    while (std::getline(f, line)) {
+        split_tabs(strip(line), p);
+        long long a, b;
+        double d;
+        if (p.size() < 2 || !parse_id(p[0], a) || !parse_id(p[1], b)) throw std::runtime_error("malformed row in " + prefix + "_kSpider_pairwise.tsv");
+        if (col == 6) {
+            if (!std::getline(ani, aline) || !parse_float(aline, d)) throw std::runtime_error("malformed / short " + prefix + "_kSpider_pairwise.ani_col.tsv");
+        } else if ((int)p.size() <= col || !parse_float(p[(size_t)col], d)) {
+            throw std::runtime_error("malformed row in " + prefix + "_kSpider_pairwise.tsv");
+        }
+        row(a, b, d * 100.0);
+    }
+}
+// a kept row names its nodes by id - 1: the ids must be rows of .namesMap
+void check_row_nodes(const long long a, const long long b, const u64 N) {
+    if (a < 1 || b < 1 || (u64)a > N || (u64)b > N)
+        throw std::runtime_error("pairwise row names node " + std::to_string(std::max(a, b)) + " but .namesMap has " + std::to_string(N) + " rows (ids must be 1..N)");
+}
+}  // namespace
+
 extern "C" int kspider_cluster(const char* index_prefix, const char* dist_type, double cutoff) {
     if (!index_prefix) { ksp::set_error("kspider_cluster: index_prefix is NULL"); return KSP_E_ARG; }
     const std::string prefix = index_prefix, dt = dist_type && *dist_type ? dist_type : "max_cont";
-    int col;
-    if (dt == "min_cont") col = 3;
-    else if (dt == "avg_cont") col = 4;
-    else if (dt == "max_cont") col = 5;
-    else if (dt == "ani") col = 6;
-    else { ksp::set_error("kspider_cluster: unknown distance '" + dt + "' (min_cont, avg_cont, max_cont, ani)"); return KSP_E_ARG; }
+    const int col = cluster_col(dt);
+    if (!col) { ksp::set_error("kspider_cluster: unknown distance '" + dt + "' (min_cont, avg_cont, max_cont, ani)"); return KSP_E_ARG; }
     const double threshold = cutoff * 100.0;   // (ks_clustering.py: cutoff = float(cutoff) * 100)
     try {
-        std::string line;
-        {   // _kSpider_seqToKmersNo.tsv must be there and well-formed (load_seq_to_kmers, :48-53); its values are not used
-            std::ifstream f(prefix + "_kSpider_seqToKmersNo.tsv");
-            if (!f) throw std::runtime_error("cannot open " + prefix + "_kSpider_seqToKmersNo.tsv");
-            std::getline(f, line);
-            std::vector<std::string> p;
-            while (std::getline(f, line)) {
-                split_tabs(strip(line), p);
-                long long a, b;
-                if (p.size() != 3 || !parse_id(p[1], a) || !parse_id(p[2], b))
-                    throw std::runtime_error("malformed row in " + prefix + "_kSpider_seqToKmersNo.tsv");
-            }
-        }
         std::vector<std::string> name_of;
-        ksp::read_names_map(prefix, name_of);
-        const u64 N = name_of.size();
         std::vector<u32> ea, eb;
-        {
-            std::ifstream f(prefix + "_kSpider_pairwise.tsv");
-            if (!f) throw std::runtime_error("cannot open " + prefix + "_kSpider_pairwise.tsv");
-            std::ifstream ani;
-            if (col == 6) {
-                ani.open(prefix + "_kSpider_pairwise.ani_col.tsv");
-                if (!ani) throw std::runtime_error("ANI was selected, but " + prefix + "_kSpider_pairwise.ani_col.tsv was not found");
-                std::getline(ani, line);
-            }
-            std::getline(f, line);   // header
-            std::vector<std::string> p;
-            std::string aline;
-            while (std::getline(f, line)) {
-                split_tabs(strip(line), p);
-                long long a, b;
-                double d;
-                if (p.size() < 2 || !parse_id(p[0], a) || !parse_id(p[1], b)) throw std::runtime_error("malformed row in " + prefix + "_kSpider_pairwise.tsv");
-                if (col == 6) {
-                    if (!std::getline(ani, aline) || !parse_float(aline, d)) throw std::runtime_error("malformed / short " + prefix + "_kSpider_pairwise.ani_col.tsv");
-                } else if ((int)p.size() <= col || !parse_float(p[(size_t)col], d)) {
-                    throw std::runtime_error("malformed row in " + prefix + "_kSpider_pairwise.tsv");
-                }
-                d *= 100.0;
-                if (d < threshold) continue;   // (a NaN is not below anything: kept, as in the reference)
-                if (a < 1 || b < 1 || (u64)a > N || (u64)b > N)
-                    throw std::runtime_error("pairwise row names node " + std::to_string(std::max(a, b)) + " but .namesMap has " + std::to_string(N) + " rows (ids must be 1..N)");
-                ea.push_back((u32)(a - 1));
-                eb.push_back((u32)(b - 1));
-            }
-        }
+        read_cluster_inputs(prefix, col, name_of, [&](const long long a, const long long b, const double d) {
+            if (d < threshold) return;   // (a NaN is not below anything: kept, as in the reference)
+            check_row_nodes(a, b, name_of.size());
+            ea.push_back((u32)(a - 1));
+            eb.push_back((u32)(b - 1));
+        });
+        const u64 N = name_of.size();
         std::vector<u32> label((size_t)N);
         int device = 0;
         if (const char* dv = std::getenv("KSPIDER_DEVICE")) device = std::atoi(dv);
@@ -522,6 +514,115 @@ extern "C" int kspider_cluster(const char* index_prefix, const char* dist_type, 
         return KSP_E_LIMIT;
     } catch (const std::exception& e) {
         ksp::set_error(std::string("kspider_cluster: ") + e.what());
+        return KSP_E_IO;
+    }
+}
+
+namespace ksp {
+// What both ladder calls leave on disk: one cluster file per distinct cut-off (write_cluster_file: the name and the bytes of
+// kspider_cluster) and PREFIX_kSpider_cluster_sweep_<dist>.tsv, one row per distinct cut-off, ascending.  labels: n_cutoffs
+// rows of name_of.size() node labels in the caller's order; kept[i] = the rows cut-off i keeps.  Cut-offs are distinct when
+// the text of cutoff * 100 — the file name — is.  On a failure every file this call created is removed again.
+void write_sweep_outputs(const std::string& prefix, const std::string& dist, const double* cutoffs, const uint32_t n_cutoffs, const uint32_t* labels,
+                         const uint64_t* kept, const std::vector<std::string>& name_of) {
+    const u64 N = name_of.size();
+    std::vector<u32> pick;   // one caller index per distinct cut-off, ascending
+    for (u32 i = 0; i < n_cutoffs; ++i) pick.push_back(i);
+    std::stable_sort(pick.begin(), pick.end(), [&](const u32 x, const u32 y) { return cutoffs[x] * 100.0 < cutoffs[y] * 100.0; });
+    pick.erase(std::unique(pick.begin(), pick.end(), [&](const u32 x, const u32 y) { return py_float_repr(cutoffs[x] * 100.0) == py_float_repr(cutoffs[y] * 100.0); }),
+               pick.end());
+    auto exists = [](const std::string& path) { return (bool)std::ifstream(path); };
+    std::vector<std::string> created;
+    const std::string summary = prefix + "_kSpider_cluster_sweep_" + dist + ".tsv", tmp = summary + ".partial";
+    try {
+        std::string rows = "cutoff_percent\tedges\tclusters\tsingletons\tlargest\n";
+        for (const u32 i : pick) {
+            const std::vector<u32> label(labels + (u64)i * N, labels + (u64)(i + 1) * N);
+            const std::string text = py_float_repr(cutoffs[i] * 100.0), out = prefix + "_kSpider_clusters_" + text + "%.tsv";
+            if (!exists(out)) created.push_back(out);
+            write_cluster_file(prefix, cutoffs[i] * 100.0, label, name_of);
+            std::vector<u32> size((size_t)N, 0);
+            for (u64 v = 0; v < N; ++v) ++size[label[v]];
+            u64 clusters = 0, singletons = 0, largest = 0;
+            for (u64 v = 0; v < N; ++v) {
+                clusters += size[v] != 0;
+                singletons += size[v] == 1;
+                largest = std::max<u64>(largest, size[v]);
+            }
+            rows += text + "\t" + std::to_string(kept[i]) + "\t" + std::to_string(clusters) + "\t" + std::to_string(singletons) + "\t" + std::to_string(largest) + "\n";
+        }
+        if (!exists(summary)) created.push_back(summary);
+        {
+            std::ofstream f(tmp);
+            if (!f) throw std::runtime_error("cannot write " + tmp);
+            f << rows;
+            f.flush();
+            if (!f) throw std::runtime_error("write error on " + tmp);
+        }
+        if (std::rename(tmp.c_str(), summary.c_str()) != 0) throw std::runtime_error("cannot rename " + tmp);
+    } catch (...) {
+        std::remove(tmp.c_str());
+        for (const std::string& path : created) std::remove(path.c_str());
+        throw;
+    }
+}
+}  // namespace ksp
+
+extern "C" int kspider_cluster_sweep(const char* index_prefix, const char* dist_type, const double* cutoffs, uint32_t n_cutoffs) {
+    if (!index_prefix) { ksp::set_error("kspider_cluster_sweep: index_prefix is NULL"); return KSP_E_ARG; }
+    if (!cutoffs || n_cutoffs < 1 || n_cutoffs > KSP_SWEEP_MAX_CUTOFFS) {
+        ksp::set_error("kspider_cluster_sweep: between 1 and " + std::to_string(KSP_SWEEP_MAX_CUTOFFS) + " cut-offs");
+        return KSP_E_ARG;
+    }
+    const std::string prefix = index_prefix, dt = dist_type && *dist_type ? dist_type : "max_cont";
+    const int col = cluster_col(dt);
+    if (!col) { ksp::set_error("kspider_cluster_sweep: unknown distance '" + dt + "' (min_cont, avg_cont, max_cont, ani)"); return KSP_E_ARG; }
+    const u32 K = n_cutoffs;
+    for (u32 i = 0; i < K; ++i)
+        if (cutoffs[i] != cutoffs[i]) { ksp::set_error("kspider_cluster_sweep: a cut-off is NaN"); return KSP_E_ARG; }
+    // The row test of kspider_cluster is `value * 100 < cutoff * 100 -> dropped`, in double: the rows a cut-off keeps shrink
+    // as cutoff * 100 grows, so the rank of a cut-off is its place among the thresholds, ascending, and a row's level is the
+    // number of thresholds it is not below (a NaN: all of them).
+    std::vector<u32> caller_of(K);   // rank -> caller's index
+    for (u32 i = 0; i < K; ++i) caller_of[i] = i;
+    std::stable_sort(caller_of.begin(), caller_of.end(), [&](const u32 x, const u32 y) { return cutoffs[x] * 100.0 < cutoffs[y] * 100.0; });
+    std::vector<double> threshold(K);
+    for (u32 r = 0; r < K; ++r) threshold[r] = cutoffs[caller_of[r]] * 100.0;
+    try {
+        std::vector<std::string> name_of;
+        std::vector<u32> ea, eb;
+        std::vector<uint8_t> level;
+        std::vector<u64> per_level((size_t)K + 1, 0);
+        read_cluster_inputs(prefix, col, name_of, [&](const long long a, const long long b, const double d) {
+            // the thresholds ascend: the level is the place of the first one the row is below (a NaN is below none)
+            const u32 l = d != d ? K : (u32)(std::upper_bound(threshold.begin(), threshold.end(), d) - threshold.begin());
+            ++per_level[l];
+            if (!l) return;
+            check_row_nodes(a, b, name_of.size());
+            ea.push_back((u32)(a - 1));
+            eb.push_back((u32)(b - 1));
+            level.push_back((uint8_t)l);
+        });
+        const u64 N = name_of.size();
+        std::vector<u32> by_rank((size_t)K * N), labels((size_t)K * N);
+        int device = 0;
+        if (const char* dv = std::getenv("KSPIDER_DEVICE")) device = std::atoi(dv);
+        const int rc = ksp_components_sweep(device, (u32)N, ea.data(), eb.data(), level.data(), ea.size(), K, by_rank.data());
+        if (rc) return rc;
+        std::vector<u64> kept(K);
+        u64 above = 0;
+        for (u32 r = K; r-- > 0;) {
+            above += per_level[r + 1];
+            kept[caller_of[r]] = above;   // the rows of level > r
+            std::copy(by_rank.begin() + (size_t)r * N, by_rank.begin() + (size_t)(r + 1) * N, labels.begin() + (size_t)caller_of[r] * N);
+        }
+        ksp::write_sweep_outputs(prefix, dt, cutoffs, K, labels.data(), kept.data(), name_of);
+        return KSP_OK;
+    } catch (const std::bad_alloc&) {
+        ksp::set_error("kspider_cluster_sweep: out of host memory");
+        return KSP_E_LIMIT;
+    } catch (const std::exception& e) {
+        ksp::set_error(std::string("kspider_cluster_sweep: ") + e.what());
         return KSP_E_IO;
     }
 }

@@ -76,9 +76,26 @@ struct CutRequest {
     double cutoff = 0;
     uint64_t n_found = 0;                    // out: edges before the cut, summed over the devices
 };
+// ---- the cut-off ladder: components at a list of cut-offs from one pass over the join's edges (sweep.hip) ----
+// ksp_components_edges_sweep on the CURRENT device: h_labels = n_cutoffs x n_nodes in the caller's order, h_kept may be NULL
+int sweep_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, const double* cutoffs,
+                          uint32_t n_cutoffs, uint32_t* h_labels, uint64_t* h_kept);
+// one cluster file per distinct cut-off and PREFIX_kSpider_cluster_sweep_<dist>.tsv (cluster.hip); labels: n_cutoffs rows of
+// name_of.size() node labels in the caller's order, kept[i]: the rows cut-off i keeps
+void write_sweep_outputs(const std::string& prefix, const std::string& dist, const double* cutoffs, uint32_t n_cutoffs, const uint32_t* labels,
+                         const uint64_t* kept, const std::vector<std::string>& name_of);
+// a drop-in call that also wants the components of its result at every cut-off of a ladder, taken from the edges while they are in HBM
+struct SweepRequest {
+    const uint32_t* kmer_counts = nullptr;   // per (dense) source index
+    int col = 5;                             // 3 / 4 / 5
+    const double* cutoffs = nullptr;
+    uint32_t n_cutoffs = 0;                  // 1 .. KSP_SWEEP_MAX_CUTOFFS
+    std::vector<uint32_t>* labels = nullptr; // out: n_cutoffs rows, per source index the smallest index of its component
+    std::vector<uint64_t>* kept = nullptr;   // out: edges that passed each cut-off
+};
 int pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
-                               ksp_stats* stats, CcRequest* cc, ReprRequest* repr = nullptr, CutRequest* cut = nullptr);
+                               ksp_stats* stats, CcRequest* cc, ReprRequest* repr = nullptr, CutRequest* cut = nullptr, SweepRequest* sweep = nullptr);
 }
 
 extern "C" {
@@ -89,5 +106,13 @@ int ksp_engine_source_order(const ksp_engine* e, uint32_t* h_newidx);   // (diag
  * 1 = hand-written with kept ballots, 2 = rocprim::select with the same predicate. */
 int ksp_debug_cut_times(int device, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col, double cutoff,
                         ksp_edge* d_out, int which, int reps, float* ms, uint64_t* n_kept);
+/* (tests) the two kernels of the cut-off ladder without the components: d_level[n_edges] (device) = the level of every record,
+ * cut-offs counted in order of strictness; band l = [h_band_off[l - 1], h_band_off[l]) of d_a / d_b (device, room for the edges
+ * of level >= 1), l = 1 .. n_cutoffs: the endpoints of the edges of level l, in any order. */
+int ksp_debug_sweep_bands(int device, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col, const double* cutoffs,
+                          uint32_t n_cutoffs, uint8_t* d_level, uint64_t* h_band_off, uint32_t* d_a, uint32_t* d_b);
+/* (tools/sweep_times.py) HIP-event times of `reps` runs of: which 0 = ksp_components_edges_sweep, 1 = one ksp_components_edges per cut-off. */
+int ksp_debug_sweep_times(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col,
+                          const double* cutoffs, uint32_t n_cutoffs, int which, int reps, float* ms, uint32_t* h_labels);
 }
 #endif

@@ -15,7 +15,7 @@ void set_error(const std::string& s) { g_error = s; }
 
 namespace ksp {
 int pairwise_postings_multi_cc(const uint64_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, const int*, int, ksp_edge**,
-                               uint64_t*, ksp_stats*, CcRequest*, ReprRequest*, CutRequest*) {
+                               uint64_t*, ksp_stats*, CcRequest*, ReprRequest*, CutRequest*, SweepRequest*) {
     set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }
@@ -23,6 +23,8 @@ void cc_critical(double, float* vcrit, int* mode) { *vcrit = 0; *mode = 0; }
 void read_names_map(const std::string&, std::vector<std::string>& name_of) { name_of.clear(); }
 void write_cluster_file(const std::string&, double, const std::vector<uint32_t>&, const std::vector<std::string>&) {}
 bool repr_text_passes(float, double) { return false; }
+void write_sweep_outputs(const std::string&, const std::string&, const double*, uint32_t, const uint32_t*, const uint64_t*,
+                         const std::vector<std::string>&) {}
 void write_repr_file(const std::string&, const std::vector<uint32_t>&, const uint32_t*, const uint32_t*, uint64_t) {}
 }  // namespace ksp
 

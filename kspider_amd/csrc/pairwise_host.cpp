@@ -67,8 +67,15 @@ struct CutOpts {
     int col = 5;
     double cutoff = 0;
 };
+// sweep: also cluster at every cut-off of a ladder (kspider_pairwise_and_cluster_sweep), from one pass over the edges on the device
+struct SweepOpts {
+    int col = 5;
+    std::string dist;
+    const double* cutoffs = nullptr;
+    uint32_t n_cutoffs = 0;
+};
 int run_pairwise(const std::string& prefix, int user_threads, const char* dist_type = nullptr, double cutoff = 0, bool ani = false,
-                 const ReprOpts* repr = nullptr, const CutOpts* cut = nullptr) {
+                 const ReprOpts* repr = nullptr, const CutOpts* cut = nullptr, const SweepOpts* sweep = nullptr) {
     int cc_col = 0, ksize = 0;
     std::shared_ptr<const std::vector<double>> ani_tab;
     if (ani) {   // before anything is read or written: the k-mer size (:44-46) and its table
@@ -184,7 +191,10 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
     ksp::ReprRequest rq;
     std::vector<uint32_t> rq_node, rq_count;
     ksp::CutRequest cq;
-    if (cc_col || repr || cut) {
+    ksp::SweepRequest sq;
+    std::vector<uint32_t> sq_labels;
+    std::vector<uint64_t> sq_kept;
+    if (cc_col || repr || cut || sweep) {
         cc_counts.resize(N);
         for (uint32_t i = 0; i < N; ++i) {
             auto it = kmer_count.find(ids[i]);
@@ -193,10 +203,14 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
         cc.kmer_counts = cc_counts.data(); cc.col = cc_col; cc.cutoff = cutoff; cc.labels = &cc_labels; cc.ksize = ksize;
         if (repr) { rq.kmer_counts = cc_counts.data(); rq.col = repr->col; rq.threshold = repr->threshold; rq.node = &rq_node; rq.count = &rq_count; }
         if (cut) { cq.kmer_counts = cc_counts.data(); cq.col = cut->col; cq.cutoff = cut->cutoff; }
+        if (sweep) {
+            sq.kmer_counts = cc_counts.data(); sq.col = sweep->col; sq.cutoffs = sweep->cutoffs; sq.n_cutoffs = sweep->n_cutoffs;
+            sq.labels = &sq_labels; sq.kept = &sq_kept;
+        }
     }
     int rc = ksp::pairwise_postings_multi_cc(key_off.data(), post_src.data(), key_w.data(), (uint32_t)key_w.size(), N,
                                              devices.data(), (int)devices.size(), &edges, &n_edges, &st, cc_col ? &cc : nullptr, repr ? &rq : nullptr,
-                                             cut ? &cq : nullptr);
+                                             cut ? &cq : nullptr, sweep ? &sq : nullptr);
     const double t_device = since(t1);
     if (rc != KSP_OK) return rc;
     std::vector<ksp::EdgeRow> rows;
@@ -358,6 +372,63 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
         ksp::write_cluster_file(prefix, cutoff * 100.0, node_label, name_of);
         if (std::getenv("KSPIDER_VERBOSE")) std::cout << "kspider_amd: clusters from " << cc.n_kept << " edges that pass the cut" << std::endl;
     }
+    if (sweep) {
+        // the cluster file of `kSpider cluster` at every cut-off of the ladder, from the components the device found on the join's own edge records
+        const uint32_t K = sweep->n_cutoffs;
+        std::vector<std::string> name_of;
+        ksp::read_names_map(prefix, name_of);
+        const uint64_t NN = name_of.size();
+        if (sq_labels.size() != (size_t)K * N || sq_kept.size() != K) {   // (the device pass did not run: every source is its own component)
+            sq_labels.resize((size_t)K * N);
+            for (size_t i = 0; i < sq_labels.size(); ++i) sq_labels[i] = (uint32_t)(i % N);
+            sq_kept.assign(K, 0);
+        }
+        // rows that only exist with shared_kmers = 0 (colours of weight 0) are rows of the TSV too: the same test per cut-off, on the
+        // host, and the row united into every rank it passes
+        std::vector<std::pair<uint32_t, uint32_t>> zero_ends;
+        std::vector<float> zero_val;
+        for (auto& zp : zero_pairs) {
+            auto it = std::lower_bound(rows.begin(), rows.end(), zp, [](const ksp::EdgeRow& r, const std::pair<uint32_t, uint32_t>& k) {
+                return r.source_1 != k.first ? r.source_1 < k.first : r.source_2 < k.second;
+            });
+            if (it == rows.end() || it->source_1 != zp.first || it->source_2 != zp.second || it->shared != 0) continue;   // (the pair also shares a weighted colour: an ordinary row)
+            const uint32_t a = dense(zp.first), b = dense(zp.second);
+            const float n1 = (float)cc_counts[a], n2 = (float)cc_counts[b];
+            const float c12 = 0.0f / n2, c21 = 0.0f / n1;
+            zero_ends.emplace_back(a, b);
+            zero_val.push_back(sweep->col == 3 ? std::min(c12, c21) : sweep->col == 5 ? std::max(c12, c21) : (float)((c12 + c21) / 2.0));
+        }
+        std::vector<uint32_t> node_labels((size_t)K * NN);
+        for (uint32_t i = 0; i < K; ++i) {
+            uint32_t* lab = sq_labels.data() + (size_t)i * N;
+            if (!zero_ends.empty()) {
+                float vcrit = 0;
+                int mode = 0;
+                ksp::cc_critical(sweep->cutoffs[i], &vcrit, &mode);
+                auto find = [&](uint32_t v) { while (lab[v] != v) { lab[v] = lab[lab[v]]; v = lab[v]; } return v; };
+                bool merged = false;
+                for (size_t z = 0; z < zero_ends.size(); ++z) {
+                    const float v = zero_val[z];
+                    if (!(mode ? v != v : !(v < vcrit))) continue;
+                    ++sq_kept[i];
+                    const uint32_t ra = find(zero_ends[z].first), rb = find(zero_ends[z].second);
+                    if (ra != rb) { lab[std::max(ra, rb)] = std::min(ra, rb); merged = true; }
+                }
+                if (merged) for (uint32_t s = 0; s < N; ++s) lab[s] = find(s);
+            }
+            uint32_t* node_label = node_labels.data() + (size_t)i * NN;
+            for (uint64_t v = 0; v < NN; ++v) node_label[v] = (uint32_t)v;
+            for (uint32_t s = 0; s < N; ++s) {
+                if (lab[s] == s) continue;   // (a root, or a source without a kept edge)
+                const uint64_t a = ids[s], b = ids[lab[s]];
+                if (a < 1 || b < 1 || a > NN || b > NN)
+                    throw std::runtime_error("pairwise row names node " + std::to_string(std::max(a, b)) + " but .namesMap has " + std::to_string(NN) + " rows (ids must be 1..N)");
+                node_label[a - 1] = (uint32_t)(b - 1);
+            }
+        }
+        ksp::write_sweep_outputs(prefix, sweep->dist, sweep->cutoffs, K, node_labels.data(), sq_kept.data(), name_of);
+        if (std::getenv("KSPIDER_VERBOSE")) std::cout << "kspider_amd: clusters at " << K << " cut-offs from one pass over " << n_edges << " edges" << std::endl;
+    }
     return KSP_OK;
 }
 
@@ -389,6 +460,36 @@ extern "C" int kspider_pairwise_and_cluster(const char* index_prefix, int user_t
         return run_pairwise(index_prefix, user_threads < 1 ? 1 : user_threads, dist_type ? dist_type : "", cutoff);
     } catch (const std::bad_alloc&) {
         ksp::set_error("kspider_pairwise_and_cluster: out of host memory");
+        return KSP_E_LIMIT;
+    } catch (const std::exception& e) {
+        ksp::set_error(e.what());
+        const std::string m = e.what();
+        return m.find("2^32") != std::string::npos ? KSP_E_LIMIT : KSP_E_IO;
+    }
+}
+
+extern "C" int kspider_pairwise_and_cluster_sweep(const char* index_prefix, int user_threads, const char* dist_type, const double* cutoffs,
+                                                  uint32_t n_cutoffs) {
+    if (!index_prefix) { ksp::set_error("kspider_pairwise_and_cluster_sweep: index_prefix is NULL"); return KSP_E_ARG; }
+    if (!cutoffs || n_cutoffs < 1 || n_cutoffs > KSP_SWEEP_MAX_CUTOFFS) {
+        ksp::set_error("kspider_pairwise_and_cluster_sweep: between 1 and " + std::to_string(KSP_SWEEP_MAX_CUTOFFS) + " cut-offs");
+        return KSP_E_ARG;
+    }
+    SweepOpts opts;
+    opts.dist = dist_type && *dist_type ? dist_type : "max_cont";
+    opts.col = opts.dist == "min_cont" ? 3 : opts.dist == "avg_cont" ? 4 : opts.dist == "max_cont" ? 5 : 0;
+    if (!opts.col) {
+        ksp::set_error("kspider_pairwise_and_cluster_sweep: distance '" + opts.dist + "' is not min_cont, avg_cont or max_cont (ani needs the separate ANI column file: run kspider_cluster_sweep)");
+        return KSP_E_ARG;
+    }
+    for (uint32_t i = 0; i < n_cutoffs; ++i)
+        if (cutoffs[i] != cutoffs[i]) { ksp::set_error("kspider_pairwise_and_cluster_sweep: a cut-off is NaN"); return KSP_E_ARG; }
+    opts.cutoffs = cutoffs;
+    opts.n_cutoffs = n_cutoffs;
+    try {
+        return run_pairwise(index_prefix, user_threads < 1 ? 1 : user_threads, nullptr, 0, false, nullptr, nullptr, &opts);
+    } catch (const std::bad_alloc&) {
+        ksp::set_error("kspider_pairwise_and_cluster_sweep: out of host memory");
         return KSP_E_LIMIT;
     } catch (const std::exception& e) {
         ksp::set_error(e.what());

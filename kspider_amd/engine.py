@@ -21,6 +21,10 @@ KSP_OK, KSP_E_ARG, KSP_E_HIP, KSP_E_IO, KSP_E_OVERFLOW, KSP_E_LIMIT = range(6)
 #: records per chunk of the containment cut's two passes (kCutChunkEdges in csrc/cut.hip = KSP_CUT_CHUNK_EDGES in the header)
 CUT_CHUNK_EDGES = 2048
 
+#: records per chunk of the cut-off ladder's two passes and its longest ladder (KSP_SWEEP_CHUNK_EDGES / KSP_SWEEP_MAX_CUTOFFS in the header)
+SWEEP_CHUNK_EDGES = 2048
+SWEEP_MAX_CUTOFFS = 255
+
 #: every symbol include/kspider_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "ksp_last_error", "ksp_device_count", "ksp_engine_create", "ksp_engine_destroy",
@@ -42,6 +46,7 @@ ABI_SYMBOLS = [
     "ksp_csv_float",
     "ksp_edges_degrees", "ksp_edges_repr", "ksp_repr_critical", "kspider_repr_sketches", "kspider_pairwise_and_repr",
     "ksp_edges_cut", "ksp_pairwise_host_cut", "kspider_pairwise_cut",
+    "ksp_components_edges_sweep", "ksp_components_sweep", "kspider_cluster_sweep", "kspider_pairwise_and_cluster_sweep",
 ]
 
 
@@ -179,6 +184,14 @@ def lib():
                                             ctypes.c_double, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(Stats)]
         L.kspider_pairwise_cut.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_double]
+        L.ksp_components_edges_sweep.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
+                                                 ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_components_sweep.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                           ctypes.c_uint32, ctypes.c_void_p]
+        L.kspider_cluster_sweep.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32]
+        L.kspider_pairwise_and_cluster_sweep.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32]
+        L.ksp_debug_sweep_bands.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         _lib = L
     return _lib
 
@@ -367,6 +380,71 @@ def pairwise_cut(index_prefix: str, user_threads: int = 1, dist_type: str = "max
     would keep, cut on the device before the sort, the copy and the text; seqToKmersNo is not affected."""
     _check(lib().kspider_pairwise_cut(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
                                       float(cutoff)))
+
+
+def _cutoff_array(cutoffs):
+    """(array or None, count): None stands for a NULL list, as the C ABI sees it."""
+    if cutoffs is None:
+        return None, 0
+    c = np.ascontiguousarray(np.asarray(cutoffs, dtype=np.float64).reshape(-1))
+    return c, c.size
+
+
+def cluster_sweep(index_prefix: str, dist_type: str = "max_cont", cutoffs=(0.0,)) -> None:
+    """`kSpider cluster -i PREFIX -d DIST -c C` at every cut-off of the list from one reading of the pairwise TSV and one
+    device pass: a cluster file per distinct cut-off as `cluster` writes it, plus PREFIX_kSpider_cluster_sweep_<DIST>.tsv."""
+    c, k = _cutoff_array(cutoffs)
+    _check(lib().kspider_cluster_sweep(os.fsencode(index_prefix), dist_type.encode() if dist_type is not None else None,
+                                       c.ctypes.data if c is not None and k else None, k))
+
+
+def pairwise_and_cluster_sweep(index_prefix: str, user_threads: int = 1, dist_type: str = "max_cont", cutoffs=(0.0,)) -> None:
+    """`pairwise_and_cluster` at every cut-off of the list: the pairwise TSV of `pairwise`, the clusters of every cut-off from
+    one pass over the edges while they are in HBM; the files of `cluster_sweep`."""
+    c, k = _cutoff_array(cutoffs)
+    _check(lib().kspider_pairwise_and_cluster_sweep(os.fsencode(index_prefix), int(user_threads),
+                                                    dist_type.encode() if dist_type is not None else None,
+                                                    c.ctypes.data if c is not None and k else None, k))
+
+
+def components_edges_sweep(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, dist_col: int, cutoffs,
+                           device: int = 0) -> tuple:
+    """(labels[K, n_nodes], kept[K]): `components_edges` at every cut-off of the list over ksp_edge records in DEVICE memory,
+    from one classification of the records and one continued components computation (include/kspider_amd.h)."""
+    c, k = _cutoff_array(cutoffs)
+    kept = np.zeros(max(1, k), dtype=np.uint64)
+    flat = np.empty(max(1, k * n_nodes), dtype=np.uint32)
+    _check(lib().ksp_components_edges_sweep(device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, int(dist_col),
+                                            c.ctypes.data if c is not None and k else None, k, flat.ctypes.data, kept.ctypes.data))
+    labels = flat[:k * n_nodes].reshape(k, n_nodes)
+    return labels, kept[:k]
+
+
+def components_sweep(n_nodes: int, a: np.ndarray, b: np.ndarray, level: np.ndarray, n_levels: int, device: int = 0) -> np.ndarray:
+    """labels[n_levels, n_nodes] of host edges that are already classified (level[e] in 0..n_levels): row r = the components
+    of the edges with level > r, each labelled by its smallest node."""
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    level = np.ascontiguousarray(level, dtype=np.uint8)
+    if not (a.size == b.size == level.size):
+        raise ValueError("a, b and level need one entry per edge")
+    k = max(0, int(n_levels))
+    flat = np.empty(max(1, k * n_nodes), dtype=np.uint32)
+    _check(lib().ksp_components_sweep(device, n_nodes, a.ctypes.data, b.ctypes.data, level.ctypes.data, a.size, int(n_levels), flat.ctypes.data))
+    return flat[:k * n_nodes].reshape(k, n_nodes)
+
+
+def sweep_bands(d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, dist_col: int, cutoffs, d_level_ptr: int, d_a_ptr: int, d_b_ptr: int,
+                device: int = 0) -> np.ndarray:
+    """(tests) The two kernels of the cut-off ladder without the components (ksp_debug_sweep_bands, csrc/engine_internal.h): the
+    level byte of every record to d_level, the endpoints of the edges of level l to band l of d_a / d_b; returns the K + 1 band
+    offsets (band l = [off[l - 1], off[l])).  Levels count the cut-offs in order of strictness."""
+    c, k = _cutoff_array(cutoffs)
+    off = np.zeros(max(1, k) + 1, dtype=np.uint64)
+    _check(lib().ksp_debug_sweep_bands(device, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, int(dist_col),
+                                       c.ctypes.data if c is not None and k else None, k, d_level_ptr or None, off.ctypes.data,
+                                       d_a_ptr or None, d_b_ptr or None))
+    return off[:k + 1]
 
 
 def estimate_ani(index_prefix: str, user_threads: int, scale: int) -> None:
