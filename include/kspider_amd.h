@@ -473,6 +473,56 @@ int kspider_cluster_sweep(const char* index_prefix, const char* dist_type, const
 int kspider_pairwise_and_cluster_sweep(const char* index_prefix, int user_threads, const char* dist_type, const double* cutoffs,
                                        uint32_t n_cutoffs);
 
+/* ---- the single-linkage tree of the containment graph: a maximum spanning forest on the device ---------------
+ * The clusters of kspider_cluster at EVERY cut-off are the single-linkage hierarchy of the graph whose edges are the pairwise
+ * rows, and a maximum spanning forest of that graph fixes it: at most N - 1 rows, whose components at any cut-off are the
+ * components of all rows at that cut-off.  Order of edges, a strict total order: the column value, larger first, a NaN above
+ * every number (a NaN row is kept at every cut-off), ties by record index, lower first; so the forest is unique.  Every record
+ * is an edge, whatever its `shared`, except a record with source_1 == source_2, which is skipped; a pair may repeat.
+ * Guarantee: kspider_cluster_from_tree at any cut-off in [0, 1] writes the cluster file kspider_cluster writes over the full
+ * TSV, byte for byte (tests/test_tree_gpu.py::test_tree_files).
+ * ksp_edges_forest: d_edges: `n_edges` ksp_edge records in DEVICE memory, never written; d_kmer_counts and dist_col (3 / 4 / 5)
+ *   as for ksp_components_edges, the value compared as the float the pairwise writer computes.  h_index (host, room for
+ *   min(n_nodes - 1, n_edges) entries) receives the indices of the forest's records in merge order — NaN first, then value
+ *   descending, then lower index — and *n_forest their number; nothing behind them is written.  KSP_E_ARG for a NULL pointer
+ *   with n_edges > 0, a NULL n_forest and a column other than 3 / 4 / 5; KSP_E_LIMIT for 2^32 - 1 records or more (the index is
+ *   half of the 64-bit key), and, before anything is written to the caller, when 12 bytes per record plus 16 bytes per node do
+ *   not fit the device's free memory; KSP_E_HIP with a message, never a spin, should a round not flatten in 34 jump passes or
+ *   the rounds exceed ceil(log2(n_nodes)) + 2.  n_edges = 0: *n_forest = 0, no kernel runs.  An endpoint >= n_nodes is the
+ *   caller's error, as for ksp_components_edges.  $KSP_TREE_MAX_WORKGROUPS caps the grids of the edge passes (tests).
+ *   KSP_TREE_CHUNK_EDGES: records per chunk.
+ * ksp_forest_ranked: the same forest for HOST edges whose weights the caller has ranked: a higher h_rank merges earlier, ties
+ *   go to the lower index.  KSP_E_ARG for an endpoint >= n_nodes; the other refusals as above.
+ * kspider_tree: reads what kspider_cluster reads, with the same validation and the same refusals (every row is an edge here, so
+ *   every row's ids must be rows of .namesMap), each before any file is written; "ani" goes through
+ *   PREFIX_kSpider_pairwise.ani_col.tsv.  The weight of a row is the value kspider_cluster tests, float(text) x 100, a NaN the
+ *   top; the host sorts the distinct weights into ranks, the device finds the forest.  Writes PREFIX_kSpider_tree_<dist_type>.tsv:
+ *   "source_1\tsource_2\t<dist_type>\tmerged_size", one row per forest edge with the row's two ids, the text of its value exactly
+ *   as it stands in the input and the size of the cluster that merge creates; rows by value descending (NaN first), then
+ *   (source_1, source_2).  newick != 0: also PREFIX_kSpider_tree_<dist_type>.newick, names from .namesMap, the height of a merge
+ *   1 - value clamped to [0, 1] (NaN: 0), a branch length parent height minus child height printed "%.6g", the child holding
+ *   source_1 first; clusters that never join go, in order of their smallest node, under one root at height 1 (no shared
+ *   k-mers); a single node is "name;".  Every file goes through .partial and a rename; on an error nothing new is left behind.
+ *   Device = $KSPIDER_DEVICE (default 0).
+ * kspider_pairwise_and_tree: kspider_pairwise's two TSVs, byte for byte, plus the same tree files, the forest taken from the
+ *   gathered, sorted edges on the first device; rows that exist only with shared_kmers = 0 (colours of weight 0) are united in
+ *   on the host after the device's forest, in (source_1, source_2) order.  "ani" is refused with KSP_E_ARG, as in the sibling
+ *   calls.  Works with $KSPIDER_DEVICE / $KSPIDER_DEVICES.  This path orders the rows by their FLOAT, which is finer than the
+ *   6-digit text kspider_tree reads, so among rows of equal text the two may choose different ones: both files are maximum
+ *   spanning forests for the text values and their cuts are equal, but the files are not promised to be byte-equal.
+ * kspider_cluster_from_tree: host only.  Reads .namesMap and PREFIX_kSpider_tree_<dist_type>.tsv, keeps the rows kspider_cluster
+ *   would keep (the same test on the same text; for "ani" its double test), unites them and writes
+ *   PREFIX_kSpider_clusters_<cutoff*100>%.tsv as kspider_cluster does.  KSP_E_IO for a missing or malformed file and for a row
+ *   whose id is not a row of .namesMap; KSP_E_ARG for an unknown distance.                                                  */
+#define KSP_TREE_CHUNK_EDGES 2048u
+int ksp_edges_forest(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
+                     int dist_col, uint32_t* h_index, uint32_t* n_forest);
+int ksp_forest_ranked(int device, uint32_t n_nodes, const uint32_t* h_a, const uint32_t* h_b, const uint32_t* h_rank,
+                      uint64_t n_edges, uint32_t* h_index, uint32_t* n_forest);
+int kspider_tree(const char* index_prefix, const char* dist_type, int newick);
+int kspider_pairwise_and_tree(const char* index_prefix, int user_threads, const char* dist_type, int newick);
+int kspider_cluster_from_tree(const char* index_prefix, const char* dist_type, double cutoff);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

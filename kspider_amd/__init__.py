@@ -8,6 +8,8 @@ Host-side mirror of the reference interface for this one path:
   kspider_amd.export(index_prefix, dist_type, newick, out_prefix)  == `kSpider export` (ks_export.py), linkage on the GPU
   kspider_amd.pairwise_cut(index_prefix, threads, dist_type, cutoff)  pairwise with a minimum containment, cut on the GPU
   kspider_amd.cluster_sweep(index_prefix, dist_type, cutoffs)  `kSpider cluster` at a list of cut-offs in one device pass
+  kspider_amd.tree(index_prefix, dist_type, newick)  the single-linkage tree of the pairwise TSV (maximum spanning forest on the GPU)
+  kspider_amd.cluster_from_tree(index_prefix, dist_type, cutoff)  `kSpider cluster` at any cut-off from the tree file alone
   kspider_amd.engine                                   ctypes binding of include/kspider_amd.h
   kspider_amd.dist                                     tile sharding + edge gather for one-process-per-GPU runs
   kspider_amd.synth                                    synthetic sketch sets shaped like BASELINE.json's configs
@@ -16,9 +18,11 @@ falls back to the CPU.
 """
 from .engine import cluster, estimate_ani, export, pairwise, pairwise_ani, pairwise_bins, pairwise_sigs  # noqa: F401
 from .engine import cluster_sweep, pairwise_and_cluster_sweep  # noqa: F401
+from .engine import TREE_CHUNK_EDGES, cluster_from_tree, edges_forest, forest_ranked, pairwise_and_tree, tree  # noqa: F401
 from .engine import single_linkage_rows  # noqa: F401
 from .engine import CUT_CHUNK_EDGES, edges_cut, pairwise_cut, pairwise_host_cut  # noqa: F401
 
 __all__ = ["pairwise", "pairwise_sigs", "pairwise_bins", "cluster", "estimate_ani", "pairwise_ani", "export",
            "single_linkage_rows", "pairwise_cut", "pairwise_host_cut", "edges_cut", "CUT_CHUNK_EDGES",
-           "cluster_sweep", "pairwise_and_cluster_sweep"]
+           "cluster_sweep", "pairwise_and_cluster_sweep",
+           "tree", "pairwise_and_tree", "cluster_from_tree", "edges_forest", "forest_ranked", "TREE_CHUNK_EDGES"]

@@ -2986,6 +2986,7 @@ struct MultiJob {
     ksp::ReprRequest* repr = nullptr;   // also wanted: the neighbour counts of the result and their ranking, likewise
     ksp::CutRequest* cut = nullptr;     // only the edges that pass a containment cut are wanted: cut on every device, directly after its join
     ksp::SweepRequest* sweep = nullptr; // also wanted: the components of the result at every cut-off of a ladder, from the edges on the device
+    ksp::TreeRequest* tree = nullptr;   // also wanted: the maximum spanning forest of the result (the single-linkage tree), from the edges on the device
 };
 }  // namespace
 
@@ -3005,6 +3006,8 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
     if (nd < 1 || nd > 64) { set_error("pairwise: between 1 and 64 devices"); return KSP_E_ARG; }
     if (job.cut && (job.cc || job.repr)) { set_error("pairwise: a cut together with the clustering or the ranking of the same job is not offered"); return KSP_E_ARG; }
     if (job.sweep && (job.cc || job.repr || job.cut)) { set_error("pairwise: a cut-off ladder together with the clustering, the ranking or a cut of the same job is not offered"); return KSP_E_ARG; }
+    if (job.tree && (job.cc || job.repr || job.cut || job.sweep)) { set_error("pairwise: a tree together with the clustering, the ranking, a cut or a cut-off ladder of the same job is not offered"); return KSP_E_ARG; }
+    if (job.tree && (!job.tree->index || job.tree->col < 3 || job.tree->col > 5)) { set_error("pairwise: a tree needs a column 3 / 4 / 5 and room for its result"); return KSP_E_ARG; }
     if (job.sweep && (!job.sweep->cutoffs || !job.sweep->labels || !job.sweep->kept || job.sweep->n_cutoffs < 1 || job.sweep->n_cutoffs > KSP_SWEEP_MAX_CUTOFFS)) {
         set_error("pairwise: a cut-off ladder has between 1 and 255 cut-offs");
         return KSP_E_ARG;
@@ -3280,6 +3283,19 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
                 }
                 d_cnt.release();
             }
+            if (job.tree) {   // the single-linkage tree from HBM: the maximum spanning forest of the same edge records
+                job.tree->index->assign((size_t)std::min<u64>(N ? N - 1 : 0, total) + 1, 0);
+                u32 n_forest = 0;
+                Buf d_cnt;
+                if (N && ((rc = d_cnt.ensure((size_t)N * 4)) || (rc = ksp_memcpy_h2d(d_cnt.p, job.tree->kmer_counts, (u64)N * 4)) ||
+                          (rc = tree_edges_on_device(N, d_all, total, d_cnt.as<u32>(), job.tree->col, job.tree->index->data(), &n_forest)))) {
+                    d_cnt.release();
+                    fail(rc);
+                    return;
+                }
+                d_cnt.release();
+                job.tree->index->resize(n_forest);
+            }
             if (job.repr && job.repr->node && job.repr->count) {   // representatives from HBM: neighbour counts of the same edge records
                 job.repr->node->assign((size_t)N, 0);
                 job.repr->count->assign((size_t)N, 0);
@@ -3353,7 +3369,7 @@ int ksp_debug_sttime(unsigned long long* out64, int reset) {
 }  // extern "C"
 int ksp::pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                     uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
-                                    ksp_stats* stats, CcRequest* cc, ReprRequest* repr, CutRequest* cut, SweepRequest* sweep) {
+                                    ksp_stats* stats, CcRequest* cc, ReprRequest* repr, CutRequest* cut, SweepRequest* sweep, TreeRequest* tree) {
     if (!out_edges || !n_edges || !devices || (n_keys && (!key_off || !sources))) { set_error("pairwise_postings_host: NULL argument"); return KSP_E_ARG; }
     const u64 n = n_keys ? key_off[n_keys] : 0;
     for (u64 i = 0; i < n; ++i)
@@ -3365,6 +3381,7 @@ int ksp::pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sou
     job.repr = repr;
     job.cut = cut;
     job.sweep = sweep;
+    job.tree = tree;
     return run_multi(job, devices, n_devices, out_edges, n_edges, stats);
 }
 extern "C" {

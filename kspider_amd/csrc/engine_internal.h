@@ -93,9 +93,29 @@ struct SweepRequest {
     std::vector<uint32_t>* labels = nullptr; // out: n_cutoffs rows, per source index the smallest index of its component
     std::vector<uint64_t>* kept = nullptr;   // out: edges that passed each cut-off
 };
+// ---- the single-linkage tree: a maximum spanning forest of the join's edges (tree.hip) ----
+// ksp_edges_forest on the CURRENT device; preload: a load and compare before every atomic (what ships); *rounds may be NULL
+int tree_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, uint32_t* h_index,
+                         uint32_t* n_forest, bool preload = true, uint32_t* rounds = nullptr);
+// one row of a tree file: node indices (id - 1), the weight that orders the rows (the value kspider_cluster tests, float(text) x
+// 100), the value itself (the newick heights) and its text
+struct TreeRow {
+    uint32_t a, b;
+    double weight, value;
+    std::string text;
+};
+// PREFIX_kSpider_tree_<dist>.tsv (and .newick) from the rows of a spanning forest, in any order
+void write_tree_files(const std::string& prefix, const std::string& dist, std::vector<TreeRow>& rows, const std::vector<std::string>& name_of, bool newick);
+// a drop-in call that also wants the maximum spanning forest of its result, taken from the edges while they are in HBM
+struct TreeRequest {
+    const uint32_t* kmer_counts = nullptr;   // per (dense) source index
+    int col = 5;                             // 3 / 4 / 5
+    std::vector<uint32_t>* index = nullptr;  // out: the forest's records as indices into the returned (sorted) edges, in merge order
+};
 int pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
-                               ksp_stats* stats, CcRequest* cc, ReprRequest* repr = nullptr, CutRequest* cut = nullptr, SweepRequest* sweep = nullptr);
+                               ksp_stats* stats, CcRequest* cc, ReprRequest* repr = nullptr, CutRequest* cut = nullptr, SweepRequest* sweep = nullptr,
+                               TreeRequest* tree = nullptr);
 }
 
 extern "C" {
@@ -114,5 +134,8 @@ int ksp_debug_sweep_bands(int device, const ksp_edge* d_edges, uint64_t n_edges,
 /* (tools/sweep_times.py) HIP-event times of `reps` runs of: which 0 = ksp_components_edges_sweep, 1 = one ksp_components_edges per cut-off. */
 int ksp_debug_sweep_times(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col,
                           const double* cutoffs, uint32_t n_cutoffs, int which, int reps, float* ms, uint32_t* h_labels);
+/* (tools/tree_times.py) HIP-event times of `reps` runs of ksp_edges_forest's device part: which 0 = as shipped, 1 = no load before the atomics. */
+int ksp_debug_tree_times(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col,
+                         int which, int reps, float* ms, uint32_t* h_index, uint32_t* n_forest, uint32_t* rounds);
 }
 #endif

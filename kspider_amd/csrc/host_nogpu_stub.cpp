@@ -15,7 +15,7 @@ void set_error(const std::string& s) { g_error = s; }
 
 namespace ksp {
 int pairwise_postings_multi_cc(const uint64_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, const int*, int, ksp_edge**,
-                               uint64_t*, ksp_stats*, CcRequest*, ReprRequest*, CutRequest*, SweepRequest*) {
+                               uint64_t*, ksp_stats*, CcRequest*, ReprRequest*, CutRequest*, SweepRequest*, TreeRequest*) {
     set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }
@@ -25,6 +25,7 @@ void write_cluster_file(const std::string&, double, const std::vector<uint32_t>&
 bool repr_text_passes(float, double) { return false; }
 void write_sweep_outputs(const std::string&, const std::string&, const double*, uint32_t, const uint32_t*, const uint64_t*,
                          const std::vector<std::string>&) {}
+void write_tree_files(const std::string&, const std::string&, std::vector<TreeRow>&, const std::vector<std::string>&, bool) {}
 void write_repr_file(const std::string&, const std::vector<uint32_t>&, const uint32_t*, const uint32_t*, uint64_t) {}
 }  // namespace ksp
 

@@ -74,8 +74,14 @@ struct SweepOpts {
     const double* cutoffs = nullptr;
     uint32_t n_cutoffs = 0;
 };
+// tree: also write the single-linkage tree (kspider_pairwise_and_tree): the maximum spanning forest of the edges, found on the device
+struct TreeOpts {
+    int col = 5;
+    std::string dist;
+    bool newick = false;
+};
 int run_pairwise(const std::string& prefix, int user_threads, const char* dist_type = nullptr, double cutoff = 0, bool ani = false,
-                 const ReprOpts* repr = nullptr, const CutOpts* cut = nullptr, const SweepOpts* sweep = nullptr) {
+                 const ReprOpts* repr = nullptr, const CutOpts* cut = nullptr, const SweepOpts* sweep = nullptr, const TreeOpts* tree = nullptr) {
     int cc_col = 0, ksize = 0;
     std::shared_ptr<const std::vector<double>> ani_tab;
     if (ani) {   // before anything is read or written: the k-mer size (:44-46) and its table
@@ -194,7 +200,9 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
     ksp::SweepRequest sq;
     std::vector<uint32_t> sq_labels;
     std::vector<uint64_t> sq_kept;
-    if (cc_col || repr || cut || sweep) {
+    ksp::TreeRequest tq;
+    std::vector<uint32_t> tq_index;
+    if (cc_col || repr || cut || sweep || tree) {
         cc_counts.resize(N);
         for (uint32_t i = 0; i < N; ++i) {
             auto it = kmer_count.find(ids[i]);
@@ -207,12 +215,26 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
             sq.kmer_counts = cc_counts.data(); sq.col = sweep->col; sq.cutoffs = sweep->cutoffs; sq.n_cutoffs = sweep->n_cutoffs;
             sq.labels = &sq_labels; sq.kept = &sq_kept;
         }
+        if (tree) { tq.kmer_counts = cc_counts.data(); tq.col = tree->col; tq.index = &tq_index; }
     }
     int rc = ksp::pairwise_postings_multi_cc(key_off.data(), post_src.data(), key_w.data(), (uint32_t)key_w.size(), N,
                                              devices.data(), (int)devices.size(), &edges, &n_edges, &st, cc_col ? &cc : nullptr, repr ? &rq : nullptr,
-                                             cut ? &cq : nullptr, sweep ? &sq : nullptr);
+                                             cut ? &cq : nullptr, sweep ? &sq : nullptr, tree ? &tq : nullptr);
     const double t_device = since(t1);
     if (rc != KSP_OK) return rc;
+    // the forest's rows, while the device's records are still here: the value as the writer computes it, and its text
+    auto column_value = [&](const int col, const uint64_t shared, const uint32_t a, const uint32_t b) {
+        const float n1 = (float)cc_counts[a], n2 = (float)cc_counts[b];
+        const float c12 = (float)shared / n2, c21 = (float)shared / n1;
+        return col == 3 ? std::min(c12, c21) : col == 5 ? std::max(c12, c21) : (float)((double)(c12 + c21) / 2.0);
+    };
+    struct ForestEdge { uint32_t a, b; float v; };   // dense source indices
+    std::vector<ForestEdge> forest;
+    if (tree)
+        for (const uint32_t e : tq_index) {
+            if (e >= n_edges) { ksp_free(edges); throw std::runtime_error("tree: the device named a record that does not exist"); }
+            forest.push_back(ForestEdge{edges[e].source_1, edges[e].source_2, column_value(tree->col, edges[e].shared, edges[e].source_1, edges[e].source_2)});
+        }
     std::vector<ksp::EdgeRow> rows;
     rows.reserve(n_edges + zero_pairs.size());
     for (uint64_t i = 0; i < n_edges; ++i)
@@ -429,10 +451,80 @@ int run_pairwise(const std::string& prefix, int user_threads, const char* dist_t
         ksp::write_sweep_outputs(prefix, sweep->dist, sweep->cutoffs, K, node_labels.data(), sq_kept.data(), name_of);
         if (std::getenv("KSPIDER_VERBOSE")) std::cout << "kspider_amd: clusters at " << K << " cut-offs from one pass over " << n_edges << " edges" << std::endl;
     }
+    if (tree) {
+        // the tree files of kspider_tree from the forest the device found on the join's own edge records
+        std::vector<std::string> name_of;
+        ksp::read_names_map(prefix, name_of);
+        const uint64_t NN = name_of.size();
+        // rows that only exist with shared_kmers = 0 (colours of weight 0) are rows of the TSV too: value 0 (a NaN with a source of 0
+        // k-mers), united in on the host after the device's forest, in (source_1, source_2) order
+        const size_t n_device = forest.size();
+        for (auto& zp : zero_pairs) {   // (sorted above)
+            auto it = std::lower_bound(rows.begin(), rows.end(), zp, [](const ksp::EdgeRow& r, const std::pair<uint32_t, uint32_t>& k) {
+                return r.source_1 != k.first ? r.source_1 < k.first : r.source_2 < k.second;
+            });
+            if (it == rows.end() || it->source_1 != zp.first || it->source_2 != zp.second || it->shared != 0) continue;   // (the pair also shares a weighted colour: an ordinary row)
+            const uint32_t a = dense(zp.first), b = dense(zp.second);
+            forest.push_back(ForestEdge{a, b, column_value(tree->col, 0, a, b)});
+        }
+        // Kruskal over (the device's forest) + (the shared-0 rows): an edge the device left out closes a cycle of better edges in
+        // its graph, so it does in the larger one.  Order: NaN first, then the float descending, then the device's merge order,
+        // then the shared-0 rows in (source_1, source_2) order — a stable sort of what is already in that order.
+        std::vector<uint32_t> order(forest.size());
+        for (size_t i = 0; i < order.size(); ++i) order[i] = (uint32_t)i;
+        if (forest.size() > n_device)
+            std::stable_sort(order.begin(), order.end(), [&](const uint32_t x, const uint32_t y) {
+                const float vx = forest[x].v, vy = forest[y].v;
+                const bool nx = vx != vx, ny = vy != vy;
+                if (nx || ny) return nx && !ny;
+                return vx > vy;
+            });
+        std::vector<uint32_t> parent((size_t)N);
+        for (uint32_t i = 0; i < N; ++i) parent[i] = i;
+        auto find = [&](uint32_t v) { while (parent[v] != v) { parent[v] = parent[parent[v]]; v = parent[v]; } return v; };
+        std::vector<ksp::TreeRow> tree_rows;
+        for (const uint32_t i : order) {
+            const ForestEdge& fe = forest[i];
+            const uint32_t ra = find(fe.a), rb = find(fe.b);
+            if (ra == rb) continue;
+            parent[std::max(ra, rb)] = std::min(ra, rb);
+            const uint64_t a = ids[fe.a], b = ids[fe.b];
+            if (a < 1 || b < 1 || a > NN || b > NN)
+                throw std::runtime_error("pairwise row names node " + std::to_string(std::max(a, b)) + " but .namesMap has " + std::to_string(NN) + " rows (ids must be 1..N)");
+            char buf[64];
+            buf[ksp::format_float(buf, fe.v)] = 0;
+            const double d = std::strtod(buf, nullptr);
+            tree_rows.push_back(ksp::TreeRow{(uint32_t)(a - 1), (uint32_t)(b - 1), d * 100.0, d, buf});
+        }
+        ksp::write_tree_files(prefix, tree->dist, tree_rows, name_of, tree->newick);
+        if (std::getenv("KSPIDER_VERBOSE")) std::cout << "kspider_amd: tree of " << tree_rows.size() << " merges from " << n_edges << " edges" << std::endl;
+    }
     return KSP_OK;
 }
 
 }  // namespace
+
+extern "C" int kspider_pairwise_and_tree(const char* index_prefix, int user_threads, const char* dist_type, int newick) {
+    if (!index_prefix) { ksp::set_error("kspider_pairwise_and_tree: index_prefix is NULL"); return KSP_E_ARG; }
+    TreeOpts opts;
+    opts.dist = dist_type && *dist_type ? dist_type : "max_cont";
+    opts.col = opts.dist == "min_cont" ? 3 : opts.dist == "avg_cont" ? 4 : opts.dist == "max_cont" ? 5 : 0;
+    if (!opts.col) {
+        ksp::set_error("kspider_pairwise_and_tree: distance '" + opts.dist + "' is not min_cont, avg_cont or max_cont (ani needs the separate ANI column file: run kspider_tree)");
+        return KSP_E_ARG;
+    }
+    opts.newick = newick != 0;
+    try {
+        return run_pairwise(index_prefix, user_threads < 1 ? 1 : user_threads, nullptr, 0, false, nullptr, nullptr, nullptr, &opts);
+    } catch (const std::bad_alloc&) {
+        ksp::set_error("kspider_pairwise_and_tree: out of host memory");
+        return KSP_E_LIMIT;
+    } catch (const std::exception& e) {
+        ksp::set_error(std::string("kspider_pairwise_and_tree: ") + e.what());
+        const std::string m = e.what();
+        return m.find("2^32") != std::string::npos ? KSP_E_LIMIT : KSP_E_IO;
+    }
+}
 
 extern "C" int kspider_pairwise(const char* index_prefix, int user_threads) {
     if (!index_prefix) {

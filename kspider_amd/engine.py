@@ -25,6 +25,9 @@ CUT_CHUNK_EDGES = 2048
 SWEEP_CHUNK_EDGES = 2048
 SWEEP_MAX_CUTOFFS = 255
 
+#: records per chunk of the edge passes of the single-linkage tree (KSP_TREE_CHUNK_EDGES in the header)
+TREE_CHUNK_EDGES = 2048
+
 #: every symbol include/kspider_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "ksp_last_error", "ksp_device_count", "ksp_engine_create", "ksp_engine_destroy",
@@ -47,6 +50,7 @@ ABI_SYMBOLS = [
     "ksp_edges_degrees", "ksp_edges_repr", "ksp_repr_critical", "kspider_repr_sketches", "kspider_pairwise_and_repr",
     "ksp_edges_cut", "ksp_pairwise_host_cut", "kspider_pairwise_cut",
     "ksp_components_edges_sweep", "ksp_components_sweep", "kspider_cluster_sweep", "kspider_pairwise_and_cluster_sweep",
+    "ksp_edges_forest", "ksp_forest_ranked", "kspider_tree", "kspider_pairwise_and_tree", "kspider_cluster_from_tree",
 ]
 
 
@@ -192,6 +196,13 @@ def lib():
         L.kspider_pairwise_and_cluster_sweep.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32]
         L.ksp_debug_sweep_bands.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_edges_forest.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
+                                       ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+        L.ksp_forest_ranked.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                        ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+        L.kspider_tree.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]
+        L.kspider_pairwise_and_tree.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        L.kspider_cluster_from_tree.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double]
         _lib = L
     return _lib
 
@@ -445,6 +456,55 @@ def sweep_bands(d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, dist_col
                                        c.ctypes.data if c is not None and k else None, k, d_level_ptr or None, off.ctypes.data,
                                        d_a_ptr or None, d_b_ptr or None))
     return off[:k + 1]
+
+
+def edges_forest(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, dist_col: int = 5, device: int = 0,
+                 tail: int = 0, fill: int = 0) -> np.ndarray:
+    """The record indices of the maximum spanning forest of ksp_edge records in DEVICE memory, in merge order (NaN first, then
+    value descending, then lower index): the single-linkage tree of the graph (include/kspider_amd.h).  tail / fill (tests): that
+    many entries of `fill` are kept behind the room the call may use and checked to be untouched."""
+    room = max(0, min(n_nodes - 1, n_edges))
+    out = np.full(room + tail, fill, dtype=np.uint32)
+    n = ctypes.c_uint32(0xFFFFFFFF)
+    _check(lib().ksp_edges_forest(device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, int(dist_col),
+                                  out.ctypes.data if (room + tail) else None, ctypes.byref(n)))
+    if n.value > room or (out[n.value:] != fill).any() and tail:
+        raise AssertionError("ksp_edges_forest wrote behind its forest")
+    return out[:n.value].copy()
+
+
+def forest_ranked(n_nodes: int, a: np.ndarray, b: np.ndarray, rank: np.ndarray, device: int = 0, tail: int = 0, fill: int = 0) -> np.ndarray:
+    """The same forest for host edges whose weights are already ranked: a higher rank merges earlier, ties go to the lower index."""
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    rank = np.ascontiguousarray(rank, dtype=np.uint32)
+    if not (a.size == b.size == rank.size):
+        raise ValueError("a, b and rank need one entry per edge")
+    room = max(0, min(n_nodes - 1, a.size))
+    out = np.full(room + tail, fill, dtype=np.uint32)
+    n = ctypes.c_uint32(0xFFFFFFFF)
+    _check(lib().ksp_forest_ranked(device, n_nodes, a.ctypes.data, b.ctypes.data, rank.ctypes.data, a.size,
+                                   out.ctypes.data if (room + tail) else None, ctypes.byref(n)))
+    if n.value > room or (out[n.value:] != fill).any() and tail:
+        raise AssertionError("ksp_forest_ranked wrote behind its forest")
+    return out[:n.value].copy()
+
+
+def tree(index_prefix: str, dist_type: str = "max_cont", newick: bool = False) -> None:
+    """The single-linkage tree of the pairwise TSV: PREFIX_kSpider_tree_<DIST>.tsv, one row per merge (and .newick), from the
+    maximum spanning forest the device finds; `cluster_from_tree` then writes the cluster file of any cut-off from it."""
+    _check(lib().kspider_tree(os.fsencode(index_prefix), dist_type.encode() if dist_type is not None else None, int(bool(newick))))
+
+
+def pairwise_and_tree(index_prefix: str, user_threads: int = 1, dist_type: str = "max_cont", newick: bool = False) -> None:
+    """`pairwise` plus the tree files of `tree`, the forest taken from the edges while they are in HBM."""
+    _check(lib().kspider_pairwise_and_tree(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
+                                           int(bool(newick))))
+
+
+def cluster_from_tree(index_prefix: str, dist_type: str = "max_cont", cutoff: float = 0.0) -> None:
+    """`kSpider cluster -i PREFIX -d DIST -c CUTOFF` from PREFIX_kSpider_tree_<DIST>.tsv alone (host only): the same file, byte for byte."""
+    _check(lib().kspider_cluster_from_tree(os.fsencode(index_prefix), dist_type.encode() if dist_type is not None else None, float(cutoff)))
 
 
 def estimate_ani(index_prefix: str, user_threads: int, scale: int) -> None:
