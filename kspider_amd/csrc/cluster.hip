@@ -403,7 +403,7 @@ extern "C" int kspider_cluster(const char* index_prefix, const char* dist_type, 
         std::vector<u32> ea, eb;
         read_cluster_inputs(prefix, col, name_of, [&](const long long a, const long long b, const double d, const std::string&) {
             if (d < threshold) return;   // (a NaN is not below anything: kept, as in the reference)
-            check_row_nodes(a, b, name_of.size());
+            ksp::check_row_nodes(a, b, name_of.size());
             ea.push_back((u32)(a - 1));
             eb.push_back((u32)(b - 1));
         });
@@ -504,7 +504,7 @@ extern "C" int kspider_cluster_sweep(const char* index_prefix, const char* dist_
             const u32 l = d != d ? K : (u32)(std::upper_bound(threshold.begin(), threshold.end(), d) - threshold.begin());
             ++per_level[l];
             if (!l) return;
-            check_row_nodes(a, b, name_of.size());
+            ksp::check_row_nodes(a, b, name_of.size());
             ea.push_back((u32)(a - 1));
             eb.push_back((u32)(b - 1));
             level.push_back((uint8_t)l);

@@ -106,11 +106,6 @@ void read_cluster_inputs(const std::string& prefix, const int col, std::vector<s
         }
     }
 }
-// a kept row names its nodes by id - 1: the ids must be rows of .namesMap
-void check_row_nodes(const long long a, const long long b, const uint64_t N) {
-    if (a < 1 || b < 1 || (uint64_t)a > N || (uint64_t)b > N)
-        throw std::runtime_error("pairwise row names node " + std::to_string(std::max(a, b)) + " but .namesMap has " + std::to_string(N) + " rows (ids must be 1..N)");
-}
 
 }  // namespace
 #endif

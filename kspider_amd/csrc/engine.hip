@@ -2982,11 +2982,8 @@ struct MultiJob {
     const u64* key_off = nullptr; const u32* sources = nullptr; const u32* key_weights = nullptr;
     u32 n_keys = 0, n_sources = 0;
     bool postings = false;
-    ksp::CcRequest* cc = nullptr;   // also wanted: the components of the result, from the edges while they are on the device
-    ksp::ReprRequest* repr = nullptr;   // also wanted: the neighbour counts of the result and their ranking, likewise
-    ksp::CutRequest* cut = nullptr;     // only the edges that pass a containment cut are wanted: cut on every device, directly after its join
-    ksp::SweepRequest* sweep = nullptr; // also wanted: the components of the result at every cut-off of a ladder, from the edges on the device
-    ksp::TreeRequest* tree = nullptr;   // also wanted: the maximum spanning forest of the result (the single-linkage tree), from the edges on the device
+    ksp::AfterJoin* after = nullptr;   // what is also wanted from the edges (engine_internal.h)
+    bool wants(ksp::AfterJoin::Kind k) const { return after && after->kind == k; }
 };
 }  // namespace
 
@@ -3004,15 +3001,13 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
     *out_edges = nullptr;
     *n_edges = 0;
     if (nd < 1 || nd > 64) { set_error("pairwise: between 1 and 64 devices"); return KSP_E_ARG; }
-    if (job.cut && (job.cc || job.repr)) { set_error("pairwise: a cut together with the clustering or the ranking of the same job is not offered"); return KSP_E_ARG; }
-    if (job.sweep && (job.cc || job.repr || job.cut)) { set_error("pairwise: a cut-off ladder together with the clustering, the ranking or a cut of the same job is not offered"); return KSP_E_ARG; }
-    if (job.tree && (job.cc || job.repr || job.cut || job.sweep)) { set_error("pairwise: a tree together with the clustering, the ranking, a cut or a cut-off ladder of the same job is not offered"); return KSP_E_ARG; }
-    if (job.tree && (!job.tree->index || job.tree->col < 3 || job.tree->col > 5)) { set_error("pairwise: a tree needs a column 3 / 4 / 5 and room for its result"); return KSP_E_ARG; }
-    if (job.sweep && (!job.sweep->cutoffs || !job.sweep->labels || !job.sweep->kept || job.sweep->n_cutoffs < 1 || job.sweep->n_cutoffs > KSP_SWEEP_MAX_CUTOFFS)) {
+    AfterJoin* const after = job.after;
+    if (job.wants(AfterJoin::kTree) && (after->col < 3 || after->col > 5)) { set_error("pairwise: a tree needs a column 3 / 4 / 5 and room for its result"); return KSP_E_ARG; }
+    if (job.wants(AfterJoin::kSweep) && (!after->cutoffs || after->n_cutoffs < 1 || after->n_cutoffs > KSP_SWEEP_MAX_CUTOFFS)) {
         set_error("pairwise: a cut-off ladder has between 1 and 255 cut-offs");
         return KSP_E_ARG;
     }
-    if (job.cut) job.cut->n_found = 0;
+    if (after) after->n_found = 0;
     const u32 N = job.n_sources;
     const u64 n = job.postings ? (job.n_keys ? job.key_off[job.n_keys] : 0) : (N ? job.offsets[N] : 0);
     // A sketch set of 2^30 entries or more does not fit one build (32-bit entry positions): it is cut into hash-range
@@ -3220,17 +3215,17 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
         if (sync_point()) return;
         if ((rc = join_range_grow(D.e, D.cuts[(size_t)i], D.cuts[(size_t)i + 1], D.edges, D.count, D.ms_join))) fail(rc);
         D.found = D.count;
-        if (!rc && job.cut && D.count) {   // the cut, on my own edges: what follows (gather, sort, copy) sees the kept records only
+        if (!rc && job.wants(AfterJoin::kCut) && D.count) {   // the cut, on my own edges: what follows (gather, sort, copy) sees the kept records only
             Buf d_cnt, kept;
             CutPass pass;
             u64 n_kept = 0;
-            if ((rc = d_cnt.ensure((size_t)N * 4)) || (rc = ksp_memcpy_h2d(d_cnt.p, job.cut->kmer_counts, (u64)N * 4)) ||
-                (rc = cut_count_on_device(D.edges.as<ksp_edge>(), D.count, d_cnt.as<u32>(), job.cut->col, job.cut->cutoff, pass, &n_kept)))
+            if ((rc = d_cnt.ensure((size_t)N * 4)) || (rc = ksp_memcpy_h2d(d_cnt.p, after->kmer_counts, (u64)N * 4)) ||
+                (rc = cut_count_on_device(D.edges.as<ksp_edge>(), D.count, d_cnt.as<u32>(), after->col, after->cutoff, pass, &n_kept)))
                 fail(rc);
             else if (n_kept == D.count) {}   // (every record passes: they stay where they are)
             else if (n_kept == 0) D.count = 0;
             else if ((rc = kept.ensure(n_kept * sizeof(ksp_edge))) ||   // (sized by the count pass's total, not by the input)
-                     (rc = cut_scatter_on_device(D.edges.as<ksp_edge>(), D.count, d_cnt.as<u32>(), job.cut->col, pass, kept.as<ksp_edge>())))
+                     (rc = cut_scatter_on_device(D.edges.as<ksp_edge>(), D.count, d_cnt.as<u32>(), after->col, pass, kept.as<ksp_edge>())))
                 fail(rc);
             else {
                 D.edges.release();
@@ -3244,8 +3239,8 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
         if (i == 0) {
             for (int j = 0; j < nd; ++j) edge_off[(size_t)j + 1] = edge_off[(size_t)j] + dev[(size_t)j].count;
             total = edge_off[(size_t)nd];
-            if (job.cut)
-                for (int j = 0; j < nd; ++j) job.cut->n_found += dev[(size_t)j].found;
+            if (job.wants(AfterJoin::kCut))
+                for (int j = 0; j < nd; ++j) after->n_found += dev[(size_t)j].found;
             if (nd > 1 && total && (rc = merged.ensure(total * sizeof(ksp_edge)))) fail(rc);
         }
         if (sync_point()) return;
@@ -3258,59 +3253,36 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
         if (i == 0) {
             ksp_edge* d_all = nd > 1 ? merged.as<ksp_edge>() : D.edges.as<ksp_edge>();
             if (total && (rc = sort_edges_device(d_all, total, N))) { fail(rc); return; }
-            if (job.cc && job.cc->labels) {   // clustering from HBM: the edges never travel to the host and back as text for this
-                job.cc->labels->assign((size_t)N, 0);
+            if (after && after->kind != AfterJoin::kNone && after->kind != AfterJoin::kCut) {
+                // from HBM: the same edge records, which never travel to the host and back as text for this
+                AfterJoin& A = *after;
                 Buf d_cnt;
-                if (N && ((rc = d_cnt.ensure((size_t)N * 4)) || (rc = ksp_memcpy_h2d(d_cnt.p, job.cc->kmer_counts, (u64)N * 4)) ||
-                          (rc = cc_edges_on_device(N, d_all, total, d_cnt.as<u32>(), job.cc->col, job.cc->cutoff, job.cc->labels->data(), &job.cc->n_kept,
-                                                  job.cc->ksize)))) {
-                    d_cnt.release();
-                    fail(rc);
-                    return;
+                const bool run = N && !(rc = d_cnt.ensure((size_t)N * 4)) && !(rc = ksp_memcpy_h2d(d_cnt.p, A.kmer_counts, (u64)N * 4));
+                u32 n_out = 0;   // kRepr: the sources ranked, kTree: the records of the forest
+                switch (A.kind) {
+                    case AfterJoin::kCluster:
+                        A.labels.assign((size_t)N, 0);
+                        if (run) rc = cc_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.cutoff, A.labels.data(), &A.n_kept, A.ksize);
+                        break;
+                    case AfterJoin::kSweep:   // one classification of the records, components continued from rank to rank
+                        A.labels.assign((size_t)A.n_cutoffs * N, 0);
+                        A.kept.assign(A.n_cutoffs, 0);
+                        if (run) rc = sweep_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.cutoffs, A.n_cutoffs, A.labels.data(), A.kept.data());
+                        break;
+                    case AfterJoin::kTree:
+                        A.index.assign((size_t)std::min<u64>(N ? N - 1 : 0, total) + 1, 0);
+                        if (run) rc = tree_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.index.data(), &n_out);
+                        A.index.resize(n_out);
+                        break;
+                    default:   // kRepr
+                        A.node.assign((size_t)N, 0);
+                        A.count.assign((size_t)N, 0);
+                        if (run) rc = repr_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.threshold, nullptr, A.node.data(), A.count.data(), &n_out);
+                        A.node.resize(n_out);
+                        A.count.resize(n_out);
                 }
                 d_cnt.release();
-            }
-            if (job.sweep) {   // the cut-off ladder from HBM: one classification of the same edge records, components continued from rank to rank
-                job.sweep->labels->assign((size_t)job.sweep->n_cutoffs * N, 0);
-                job.sweep->kept->assign(job.sweep->n_cutoffs, 0);
-                Buf d_cnt;
-                if (N && ((rc = d_cnt.ensure((size_t)N * 4)) || (rc = ksp_memcpy_h2d(d_cnt.p, job.sweep->kmer_counts, (u64)N * 4)) ||
-                          (rc = sweep_edges_on_device(N, d_all, total, d_cnt.as<u32>(), job.sweep->col, job.sweep->cutoffs, job.sweep->n_cutoffs,
-                                                      job.sweep->labels->data(), job.sweep->kept->data())))) {
-                    d_cnt.release();
-                    fail(rc);
-                    return;
-                }
-                d_cnt.release();
-            }
-            if (job.tree) {   // the single-linkage tree from HBM: the maximum spanning forest of the same edge records
-                job.tree->index->assign((size_t)std::min<u64>(N ? N - 1 : 0, total) + 1, 0);
-                u32 n_forest = 0;
-                Buf d_cnt;
-                if (N && ((rc = d_cnt.ensure((size_t)N * 4)) || (rc = ksp_memcpy_h2d(d_cnt.p, job.tree->kmer_counts, (u64)N * 4)) ||
-                          (rc = tree_edges_on_device(N, d_all, total, d_cnt.as<u32>(), job.tree->col, job.tree->index->data(), &n_forest)))) {
-                    d_cnt.release();
-                    fail(rc);
-                    return;
-                }
-                d_cnt.release();
-                job.tree->index->resize(n_forest);
-            }
-            if (job.repr && job.repr->node && job.repr->count) {   // representatives from HBM: neighbour counts of the same edge records
-                job.repr->node->assign((size_t)N, 0);
-                job.repr->count->assign((size_t)N, 0);
-                u32 n_ranked = 0;
-                Buf d_cnt;
-                if (N && ((rc = d_cnt.ensure((size_t)N * 4)) || (rc = ksp_memcpy_h2d(d_cnt.p, job.repr->kmer_counts, (u64)N * 4)) ||
-                          (rc = repr_edges_on_device(N, d_all, total, d_cnt.as<u32>(), job.repr->col, job.repr->threshold, nullptr,
-                                                     job.repr->node->data(), job.repr->count->data(), &n_ranked)))) {
-                    d_cnt.release();
-                    fail(rc);
-                    return;
-                }
-                d_cnt.release();
-                job.repr->node->resize(n_ranked);
-                job.repr->count->resize(n_ranked);
+                if (rc) { fail(rc); return; }
             }
             ksp_edge* out = (ksp_edge*)alloc_result(total * sizeof(ksp_edge));
             if (!out) { set_error("pairwise_host: out of pinned host memory"); fail(KSP_E_LIMIT); return; }
@@ -3369,7 +3341,7 @@ int ksp_debug_sttime(unsigned long long* out64, int reset) {
 }  // extern "C"
 int ksp::pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                     uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
-                                    ksp_stats* stats, CcRequest* cc, ReprRequest* repr, CutRequest* cut, SweepRequest* sweep, TreeRequest* tree) {
+                                    ksp_stats* stats, AfterJoin* after) {
     if (!out_edges || !n_edges || !devices || (n_keys && (!key_off || !sources))) { set_error("pairwise_postings_host: NULL argument"); return KSP_E_ARG; }
     const u64 n = n_keys ? key_off[n_keys] : 0;
     for (u64 i = 0; i < n; ++i)
@@ -3377,11 +3349,7 @@ int ksp::pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sou
     MultiJob job;
     job.postings = true;
     job.key_off = key_off; job.sources = sources; job.key_weights = key_weights; job.n_keys = n_keys; job.n_sources = n_sources;
-    job.cc = cc;
-    job.repr = repr;
-    job.cut = cut;
-    job.sweep = sweep;
-    job.tree = tree;
+    job.after = after;
     return run_multi(job, devices, n_devices, out_edges, n_edges, stats);
 }
 extern "C" {
@@ -3410,11 +3378,11 @@ int ksp_pairwise_host_cut(const uint64_t* keys, const uint32_t* weights, const u
         }
         kmer_counts = lengths.data();
     }
-    CutRequest cut;
-    cut.kmer_counts = kmer_counts; cut.col = dist_col; cut.cutoff = cutoff;
+    AfterJoin cut;
+    cut.kind = AfterJoin::kCut; cut.kmer_counts = kmer_counts; cut.col = dist_col; cut.cutoff = cutoff;
     MultiJob job;
     job.keys = keys; job.weights = weights; job.offsets = offsets; job.n_sources = n_sources;
-    job.cut = &cut;
+    job.after = &cut;
     if (n_found) *n_found = 0;
     const int rc = run_multi(job, devices, n_devices, out_edges, n_edges, stats);
     if (!rc && n_found) *n_found = cut.n_found;

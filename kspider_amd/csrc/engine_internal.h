@@ -26,15 +26,6 @@ int upload_ani_table(int ksize, double** d_table);
 void read_names_map(const std::string& prefix, std::vector<std::string>& name_of);
 void write_cluster_file(const std::string& prefix, double threshold, const std::vector<uint32_t>& label,
                         const std::vector<std::string>& name_of);
-// a drop-in call that also wants the components of its result, taken from the edges while they are in HBM
-struct CcRequest {
-    const uint32_t* kmer_counts = nullptr;   // per (dense) source index
-    int col = 0;                             // 3 / 4 / 5, 6 = ANI
-    int ksize = 0;                           // k-mer size of the ANI column (col 6)
-    double cutoff = 0;
-    std::vector<uint32_t>* labels = nullptr; // out: per source index, the smallest index of its component
-    uint64_t n_kept = 0;                     // out: edges that passed the cut
-};
 // ---- neighbour counts straight from the join's edges (repr.hip; apps/repr_sketches.cpp) ----
 // the text test of the reference on one float: "%.6g" text -> strtof -> as double -> > threshold
 bool repr_text_passes(float v, double threshold);
@@ -47,14 +38,6 @@ int repr_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_e
                          uint32_t* h_degree, uint32_t* h_node, uint32_t* h_count, uint32_t* n_ranked);
 // "id: count\n" per ranked node (id = ids[node]) to out_path through out_path.partial and a rename, or to stdout ("")
 void write_repr_file(const std::string& out_path, const std::vector<uint32_t>& ids, const uint32_t* node, const uint32_t* count, uint64_t n_ranked);
-// a drop-in call that also wants the ranking of its result, taken from the edges while they are in HBM
-struct ReprRequest {
-    const uint32_t* kmer_counts = nullptr;   // per (dense) source index
-    int col = 4;                             // 3 / 4 / 5
-    double threshold = 0.20;
-    std::vector<uint32_t>* node = nullptr;   // out: the sources with a neighbour, (count descending, index ascending)
-    std::vector<uint32_t>* count = nullptr;  // out: their counts
-};
 // ---- the containment cut on the join's edges, before they are gathered, sorted and copied (cut.hip) ----
 // what the count pass leaves for the scatter pass (device memory of the device it ran on; release() frees it)
 struct CutPass {
@@ -69,13 +52,6 @@ struct CutPass {
 int cut_count_on_device(const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, double cutoff, CutPass& pass, uint64_t* n_kept);
 // the kept records into d_out (room for *n_kept of them), in their input order; nothing behind them is written
 int cut_scatter_on_device(const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, const CutPass& pass, ksp_edge* d_out);
-// a job whose edges are cut on every device directly after its join: only the kept ones are gathered, sorted and copied
-struct CutRequest {
-    const uint32_t* kmer_counts = nullptr;   // per (dense) source index
-    int col = 5;                             // 3 / 4 / 5
-    double cutoff = 0;
-    uint64_t n_found = 0;                    // out: edges before the cut, summed over the devices
-};
 // ---- the cut-off ladder: components at a list of cut-offs from one pass over the join's edges (sweep.hip) ----
 // ksp_components_edges_sweep on the CURRENT device: h_labels = n_cutoffs x n_nodes in the caller's order, h_kept may be NULL
 int sweep_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, const double* cutoffs,
@@ -84,15 +60,6 @@ int sweep_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_
 // name_of.size() node labels in the caller's order, kept[i]: the rows cut-off i keeps
 void write_sweep_outputs(const std::string& prefix, const std::string& dist, const double* cutoffs, uint32_t n_cutoffs, const uint32_t* labels,
                          const uint64_t* kept, const std::vector<std::string>& name_of);
-// a drop-in call that also wants the components of its result at every cut-off of a ladder, taken from the edges while they are in HBM
-struct SweepRequest {
-    const uint32_t* kmer_counts = nullptr;   // per (dense) source index
-    int col = 5;                             // 3 / 4 / 5
-    const double* cutoffs = nullptr;
-    uint32_t n_cutoffs = 0;                  // 1 .. KSP_SWEEP_MAX_CUTOFFS
-    std::vector<uint32_t>* labels = nullptr; // out: n_cutoffs rows, per source index the smallest index of its component
-    std::vector<uint64_t>* kept = nullptr;   // out: edges that passed each cut-off
-};
 // ---- the single-linkage tree: a maximum spanning forest of the join's edges (tree.hip) ----
 // ksp_edges_forest on the CURRENT device; preload: a load and compare before every atomic (what ships); *rounds may be NULL
 int tree_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, uint32_t* h_index,
@@ -106,16 +73,34 @@ struct TreeRow {
 };
 // PREFIX_kSpider_tree_<dist>.tsv (and .newick) from the rows of a spanning forest, in any order
 void write_tree_files(const std::string& prefix, const std::string& dist, std::vector<TreeRow>& rows, const std::vector<std::string>& name_of, bool newick);
-// a drop-in call that also wants the maximum spanning forest of its result, taken from the edges while they are in HBM
-struct TreeRequest {
+// a kept row names its nodes by id - 1: the ids must be rows of .namesMap (throws)
+void check_row_nodes(long long a, long long b, uint64_t n_names);
+// ---- what a job wants from its edges besides the edges themselves: one kind per job ----
+// kCut: only the edges that pass a containment cut are wanted, so every device cuts its own directly after its join and only the
+// kept ones are gathered, sorted and copied.  The other kinds are taken from the sorted edges on the first device, while they
+// are in HBM: the components (cc_edges_on_device), the ranking (repr_edges_on_device), the components at every cut-off of a
+// ladder (sweep_edges_on_device), the maximum spanning forest (tree_edges_on_device).
+struct AfterJoin {
+    enum Kind { kNone, kCluster, kRepr, kCut, kSweep, kTree };
+    Kind kind = kNone;
     const uint32_t* kmer_counts = nullptr;   // per (dense) source index
-    int col = 5;                             // 3 / 4 / 5
-    std::vector<uint32_t>* index = nullptr;  // out: the forest's records as indices into the returned (sorted) edges, in merge order
+    int col = 0;                             // 3 / 4 / 5; kCluster: also 6 = ANI
+    int ksize = 0;                           // kCluster: k-mer size of the ANI column (col 6)
+    double cutoff = 0;                       // kCluster, kCut
+    double threshold = 0.20;                 // kRepr
+    const double* cutoffs = nullptr;         // kSweep
+    uint32_t n_cutoffs = 0;                  //   1 .. KSP_SWEEP_MAX_CUTOFFS
+    // out
+    std::vector<uint32_t> labels;            // kCluster: per source index, the smallest index of its component; kSweep: n_cutoffs such rows
+    uint64_t n_kept = 0;                     // kCluster: edges that passed the cut
+    std::vector<uint64_t> kept;              // kSweep: edges that passed each cut-off
+    std::vector<uint32_t> node, count;       // kRepr: the sources with a neighbour, (count descending, index ascending), and their counts
+    uint64_t n_found = 0;                    // kCut: edges before the cut, summed over the devices
+    std::vector<uint32_t> index;             // kTree: the forest's records as indices into the returned (sorted) edges, in merge order
 };
 int pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
-                               ksp_stats* stats, CcRequest* cc, ReprRequest* repr = nullptr, CutRequest* cut = nullptr, SweepRequest* sweep = nullptr,
-                               TreeRequest* tree = nullptr);
+                               ksp_stats* stats, AfterJoin* after);
 }
 
 extern "C" {

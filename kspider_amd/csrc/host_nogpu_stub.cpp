@@ -15,7 +15,7 @@ void set_error(const std::string& s) { g_error = s; }
 
 namespace ksp {
 int pairwise_postings_multi_cc(const uint64_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t, const int*, int, ksp_edge**,
-                               uint64_t*, ksp_stats*, CcRequest*, ReprRequest*, CutRequest*, SweepRequest*, TreeRequest*) {
+                               uint64_t*, ksp_stats*, AfterJoin*) {
     set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }

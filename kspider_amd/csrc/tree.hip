@@ -490,7 +490,7 @@ extern "C" int kspider_tree(const char* index_prefix, const char* dist_type, int
         std::vector<double> weight;
         std::vector<std::string> text;
         read_cluster_inputs(prefix, col, name_of, [&](const long long a, const long long b, const double d, const std::string& t) {
-            check_row_nodes(a, b, name_of.size());   // every row is an edge of the tree's graph
+            ksp::check_row_nodes(a, b, name_of.size());   // every row is an edge of the tree's graph
             ea.push_back((u32)(a - 1));
             eb.push_back((u32)(b - 1));
             weight.push_back(d);
@@ -551,7 +551,7 @@ extern "C" int kspider_cluster_from_tree(const char* index_prefix, const char* d
             long long a, b;
             double d;
             if (p.size() < 3 || !parse_id(p[0], a) || !parse_id(p[1], b) || !parse_float(p[2], d)) throw std::runtime_error("malformed row in " + path);
-            check_row_nodes(a, b, N);
+            ksp::check_row_nodes(a, b, N);
             if (d * 100.0 < threshold) continue;   // the row test of kspider_cluster on the same text (a NaN is not below anything: kept)
             const u32 ra = dsu.find((u32)(a - 1)), rb = dsu.find((u32)(b - 1));
             if (ra != rb) dsu.parent[std::max(ra, rb)] = std::min(ra, rb);

@@ -221,3 +221,31 @@ def test_components_over_device_edge_records():
         got = engine.components_edges(sk.n_sources, ed.ptr.value, m, cnt_d.ptr.value, col, cutoff)
         assert (got == want).all(), (col, cutoff, int(keep.sum()))
     eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sub", ["plain", "nan"])
+def test_pairwise_and_cluster_with_rows_of_zero_weight_colours(oracle_lib, tmp_path, sub):
+    """A row that exists only with shared_kmers = 0 (the pair 3-4 of tests/zero_weight_inputs.py; a NaN row when source 4 counts
+    0 k-mers) is united in on the host after the device's components: the same TSV as kspider_pairwise and the cluster file of
+    ks_clustering.py on that TSV, at cut-offs the row passes (0, negative; every one as a NaN) and fails."""
+    import zero_weight_inputs
+    from kspider_amd import engine
+    prefix = str(tmp_path / "z")
+    zero_weight_inputs.write(oracle_lib, prefix, sub)
+    engine.pairwise(prefix, 1)
+    tsv = open(prefix + "_kSpider_pairwise.tsv", "rb").read()
+    assert any(r.split("\t")[:3] == ["3", "4", "0"] for r in tsv.decode().split("\n")[1:-1])
+    seen = set()
+    for dist in ("min_cont", "avg_cont", "max_cont"):
+        for cutoff in (0.0, -1.0, 0.02, 0.5, 1.0):
+            os.remove(prefix + "_kSpider_pairwise.tsv")
+            engine.pairwise_and_cluster(prefix, 1, dist, cutoff)
+            assert open(prefix + "_kSpider_pairwise.tsv", "rb").read() == tsv, (sub, dist, cutoff)
+            path = ref_cluster.output_path(prefix, cutoff)
+            got = open(path, "rb").read()
+            os.remove(path)
+            assert got == open(ref_cluster.write_clusters(prefix, dist, cutoff), "rb").read(), (sub, dist, cutoff)
+            os.remove(path)
+            seen.add(got)
+    assert len(seen) >= 2

@@ -252,3 +252,32 @@ def test_files_two_steps_one_pass_exe_and_failures(oracle_lib, tmp_path, monkeyp
             f()
         assert ei.value.code == engine.KSP_E_ARG
     assert not os.path.exists(p2 + "_kSpider_pairwise.tsv")
+
+
+@pytest.mark.parametrize("sub", ["plain", "nan"])
+def test_pairwise_and_repr_with_rows_of_zero_weight_colours(oracle_lib, tmp_path, sub):
+    """A row that exists only with shared_kmers = 0 (the pair 3-4 of tests/zero_weight_inputs.py; a NaN row when source 4 counts
+    0 k-mers) is counted on the host after the device's ranking: it passes a negative threshold only (a NaN none).  The file of
+    kspider_repr_sketches over the TSV of kspider_pairwise, and the restatement's."""
+    import zero_weight_inputs
+    prefix = str(tmp_path / "z")
+    zero_weight_inputs.write(oracle_lib, prefix, sub)
+    engine.pairwise(prefix, 1)
+    tsv_path = prefix + "_kSpider_pairwise.tsv"
+    tsv = open(tsv_path, "rb").read()
+    assert any(r.split("\t")[:3] == ["3", "4", "0"] for r in tsv.decode().split("\n")[1:-1])
+    out, fused = str(tmp_path / "two_steps.txt"), prefix + "_kSpider_repr_sketches.txt"
+    seen = set()
+    for dist, col in (("min_cont", 3), ("avg_cont", 4), ("max_cont", 5)):
+        for threshold in (0.20, 0.0, -1.0):
+            engine.repr_sketches(tsv_path, dist, threshold, out)
+            want = open(out, "rb").read()
+            assert want == rr.repr_sketches(tsv.decode(), col, threshold), (sub, dist, threshold)
+            os.remove(tsv_path)
+            engine.pairwise_and_repr(prefix, 1, dist, threshold)
+            assert open(tsv_path, "rb").read() == tsv, (sub, dist, threshold)
+            assert open(fused, "rb").read() == want, (sub, dist, threshold)
+            os.remove(fused)
+            seen.add(want)
+            assert (b"3: 1\n" in want) == (threshold < 0 and sub == "plain"), (sub, dist, threshold)
+    assert len(seen) >= 2
