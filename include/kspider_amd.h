@@ -523,6 +523,51 @@ int kspider_tree(const char* index_prefix, const char* dist_type, int newick);
 int kspider_pairwise_and_tree(const char* index_prefix, int user_threads, const char* dist_type, int newick);
 int kspider_cluster_from_tree(const char* index_prefix, const char* dist_type, double cutoff);
 
+/* ---- dereplication: greedy representatives and their members, from the edges in HBM -------------------------
+ * What a user of the `repr_sketches` ranking goes on to compute: which sources to keep and, for every other source, which
+ * kept source stands for it.  A record is KEPT when its column passes the text test of `repr_sketches` ("%.6g" text -> strtof
+ * -> as double -> > threshold; on the device one compare against the critical float of ksp_repr_critical; a NaN never passes).
+ * degree[v] is what ksp_edges_degrees returns (a repeated pair counts again, a self pair adds 2).  All n_nodes nodes are
+ * ranked by (degree descending, node ascending): ksp_edges_repr's order, then the nodes of degree 0 in node order.  Walking
+ * the nodes in rank order, a node becomes a REPRESENTATIVE unless one of its kept neighbours of smaller rank is one; otherwise
+ * it becomes a MEMBER of the smallest-ranked representative among its kept neighbours (cd-hit's rule: the first
+ * representative that covers it, whatever the value), through the lowest-index kept record between the two.  Self pairs take
+ * no part in the selection.  So no two representatives share a kept record, every member shares one with its representative,
+ * every node of degree 0 is a representative, and only `via` depends on the order of the records.
+ * ksp_edges_dereplicate: d_edges: `n_edges` ksp_edge records in DEVICE memory, in any order, never written; d_kmer_counts and
+ *   dist_col (3 / 4 / 5) as for ksp_edges_degrees.  Host arrays of n_nodes entries: h_rep[v] = the representative of v (v
+ *   itself: v is one), h_via[v] = the index of the assigning record (0xFFFFFFFF for a representative), h_rank[v] = the position
+ *   of v in the order above, h_degree[v]; h_via, h_rank and h_degree may be NULL.  *n_reps = the representatives.  A record
+ *   naming a node >= n_nodes is the caller's error and is ignored.  KSP_E_ARG for a NULL pointer with n_edges > 0, a NULL
+ *   n_reps, a column other than 3 / 4 / 5 and a NaN threshold; KSP_E_LIMIT for 2^32 - 1 records or more (the index is half of
+ *   a 64-bit key and 0xFFFFFFFF is "none") and, before anything is written to the caller, when 52 bytes per node, 16 per 2 048
+ *   records and 20 per kept pair do not fit the device's free memory; KSP_E_HIP with a message, never a spin, should the
+ *   rounds exceed n_nodes + 1.  n_edges = 0, or a threshold not even +inf passes: every node is its own representative,
+ *   *n_reps = n_nodes, ranks in node order, no kernel runs.  $KSP_DEREP_MAX_WORKGROUPS caps the grids of the edge passes
+ *   (tests), $KSP_DEREP_TAIL=0 keeps the host-driven rounds to the end (same results).  KSP_DEREP_CHUNK_EDGES: entries per
+ *   chunk of the edge passes.  KSP_DEREP_TAIL_PAIRS: at that many live pairs or fewer one workgroup finishes the rounds
+ *   (UNMEASURED: DESIGN.md 7h).
+ * kspider_dereplicate: reads what kspider_cluster reads, with the same validation and the same refusals, each before any file
+ *   is written; the ids of a passing row must be rows of .namesMap.  The host applies the text test to the text as it stands,
+ *   the device makes the selection over the passing rows.  dist_type "min_cont", "avg_cont" (NULL / ""), "max_cont"; "ani", a
+ *   NaN threshold and a negative threshold are refused with KSP_E_ARG.  Writes out_path (NULL / "":
+ *   PREFIX_kSpider_dereplicated_<dist_type>.tsv) through .partial and a rename, on an error nothing is left behind:
+ *   "source\trepresentative\t<dist_type>\tneighbours\trank", one row per source in .namesMap order: both names, the text of the
+ *   assigning row's value exactly as it stands in the input ("-" for a representative), the degree, the rank.  Device =
+ *   $KSPIDER_DEVICE (default 0); with $KSPIDER_VERBOSE one line reports records kept, representatives and rounds.
+ * kspider_pairwise_and_dereplicate: kspider_pairwise's two TSVs, byte for byte, plus the same file, the selection taken from the
+ *   gathered, sorted edges on the first device (the value text is ksp_format_float of the record's float).  The same refusals.
+ *   At a threshold >= 0 a row that exists only with shared_kmers = 0 has the value 0 or NaN and never passes, so over the TSV
+ *   kspider_pairwise wrote the two calls write the same bytes.  Works with $KSPIDER_DEVICE / $KSPIDER_DEVICES.               */
+#define KSP_DEREP_CHUNK_EDGES 2048u
+#define KSP_DEREP_TAIL_PAIRS 65536u
+int ksp_edges_dereplicate(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
+                          int dist_col, double threshold, uint32_t* h_rep, uint32_t* h_via, uint32_t* h_rank, uint32_t* h_degree,
+                          uint32_t* n_reps);
+int kspider_dereplicate(const char* index_prefix, const char* dist_type, double threshold, const char* out_path);
+int kspider_pairwise_and_dereplicate(const char* index_prefix, int user_threads, const char* dist_type, double threshold,
+                                     const char* out_path);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

@@ -3274,6 +3274,11 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
                         if (run) rc = tree_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.index.data(), &n_out);
                         A.index.resize(n_out);
                         break;
+                    case AfterJoin::kDerep:   // (the ranks go to A.node; without a source nothing is asked)
+                        A.rep.assign((size_t)N, 0); A.via.assign((size_t)N, 0); A.node.assign((size_t)N, 0); A.degree.assign((size_t)N, 0);
+                        if (run) rc = derep_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.threshold, A.rep.data(), A.via.data(), A.node.data(),
+                                                            A.degree.data(), &n_out, &A.derep);
+                        break;
                     default:   // kRepr
                         A.node.assign((size_t)N, 0);
                         A.count.assign((size_t)N, 0);

@@ -75,19 +75,38 @@ struct TreeRow {
 void write_tree_files(const std::string& prefix, const std::string& dist, std::vector<TreeRow>& rows, const std::vector<std::string>& name_of, bool newick);
 // a kept row names its nodes by id - 1: the ids must be rows of .namesMap (throws)
 void check_row_nodes(long long a, long long b, uint64_t n_names);
+// ---- dereplication: greedy representatives and their members from the join's edges (derep.hip) ----
+// (repr.hip) the counting kernel and the key kernel on the caller's device buffers: d_degree[n_nodes] and the key of EVERY node
+int degree_keys_on_device(uint32_t n_nodes, const ksp_edge* d_edges, const uint32_t* d_a, const uint32_t* d_b, uint64_t n_edges, const uint32_t* d_cnt,
+                          int col, float vcrit, uint32_t* d_degree, uint64_t* d_keys);
+// what the last selection on this thread did: the rounds the host dispatched, the rounds of the tail kernel (0: it did not run)
+// and the live pairs when it took over; kept: records that became oriented pairs
+struct DerepTrace {
+    uint64_t dispatched = 0, tail = 0, live_at_tail = 0, kept = 0;
+};
+// ksp_edges_dereplicate on the CURRENT device; h_via / h_rank / h_degree may be NULL; *trace may be NULL
+int derep_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, double threshold,
+                          uint32_t* h_rep, uint32_t* h_via, uint32_t* h_rank, uint32_t* h_degree, uint32_t* n_reps, DerepTrace* trace = nullptr);
+// one source of a dereplication file: its representative (itself: a representative), the text of the assigning record's value
+struct DerepRow {
+    uint32_t rep = 0, degree = 0, rank = 0;
+    std::string text;
+};
+// out_path (through out_path.partial and a rename): "source\trepresentative\t<dist>\tneighbours\trank", one row per name
+void write_derep_file(const std::string& out_path, const std::string& dist, const std::vector<DerepRow>& rows, const std::vector<std::string>& name_of);
 // ---- what a job wants from its edges besides the edges themselves: one kind per job ----
 // kCut: only the edges that pass a containment cut are wanted, so every device cuts its own directly after its join and only the
 // kept ones are gathered, sorted and copied.  The other kinds are taken from the sorted edges on the first device, while they
 // are in HBM: the components (cc_edges_on_device), the ranking (repr_edges_on_device), the components at every cut-off of a
-// ladder (sweep_edges_on_device), the maximum spanning forest (tree_edges_on_device).
+// ladder (sweep_edges_on_device), the maximum spanning forest (tree_edges_on_device), the dereplicated set (derep_edges_on_device).
 struct AfterJoin {
-    enum Kind { kNone, kCluster, kRepr, kCut, kSweep, kTree };
+    enum Kind { kNone, kCluster, kRepr, kCut, kSweep, kTree, kDerep };
     Kind kind = kNone;
     const uint32_t* kmer_counts = nullptr;   // per (dense) source index
     int col = 0;                             // 3 / 4 / 5; kCluster: also 6 = ANI
     int ksize = 0;                           // kCluster: k-mer size of the ANI column (col 6)
     double cutoff = 0;                       // kCluster, kCut
-    double threshold = 0.20;                 // kRepr
+    double threshold = 0.20;                 // kRepr, kDerep
     const double* cutoffs = nullptr;         // kSweep
     uint32_t n_cutoffs = 0;                  //   1 .. KSP_SWEEP_MAX_CUTOFFS
     // out
@@ -97,6 +116,8 @@ struct AfterJoin {
     std::vector<uint32_t> node, count;       // kRepr: the sources with a neighbour, (count descending, index ascending), and their counts
     uint64_t n_found = 0;                    // kCut: edges before the cut, summed over the devices
     std::vector<uint32_t> index;             // kTree: the forest's records as indices into the returned (sorted) edges, in merge order
+    std::vector<uint32_t> rep, via, degree;  // kDerep: per source index its representative, the assigning record (0xFFFFFFFF: none), its neighbours;
+    DerepTrace derep;                        //   the ranks are in `node` (rank[v]); what the selection did
 };
 int pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
@@ -122,5 +143,8 @@ int ksp_debug_sweep_times(int device, uint32_t n_nodes, const ksp_edge* d_edges,
 /* (tools/tree_times.py) HIP-event times of `reps` runs of ksp_edges_forest's device part: which 0 = as shipped, 1 = no load before the atomics. */
 int ksp_debug_tree_times(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col,
                          int which, int reps, float* ms, uint32_t* h_index, uint32_t* n_forest, uint32_t* rounds);
+/* (tests) what the last ksp_edges_dereplicate / kspider_dereplicate of this thread did: out[0] the rounds the host dispatched, out[1]
+ * the rounds of the tail kernel (0: it did not run), out[2] the live pairs when it took over, out[3] the records that became oriented pairs. */
+int ksp_debug_derep_rounds(uint64_t out[4]);
 }
 #endif

@@ -27,6 +27,7 @@ void write_sweep_outputs(const std::string&, const std::string&, const double*, 
                          const std::vector<std::string>&) {}
 void write_tree_files(const std::string&, const std::string&, std::vector<TreeRow>&, const std::vector<std::string>&, bool) {}
 void write_repr_file(const std::string&, const std::vector<uint32_t>&, const uint32_t*, const uint32_t*, uint64_t) {}
+void write_derep_file(const std::string&, const std::string&, const std::vector<DerepRow>&, const std::vector<std::string>&) {}
 }  // namespace ksp
 
 extern "C" {
@@ -44,6 +45,14 @@ int ksp_repr_critical(double, float*, int*) {
     return KSP_E_HIP;
 }
 int kspider_repr_sketches(const char*, const char*, double, const char*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_edges_dereplicate(int, uint32_t, const ksp_edge*, uint64_t, const uint32_t*, int, double, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int kspider_dereplicate(const char*, const char*, double, const char*) {
     ksp::set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }

@@ -66,13 +66,14 @@ using ksp::AfterJoin;
 //   kCut      only the rows that pass a containment cut are wanted: the edges are cut on the device, directly after the join
 //   kSweep    the cluster file at every cut-off of a ladder, from one pass over the edges
 //   kTree     the single-linkage tree: the maximum spanning forest of the edges
+//   kDerep    the dereplicated set: greedy representatives in rank order and the members they stand for
 struct PairwiseJob {
     std::string prefix;
     int threads = 1;
     bool ani = false;       // also write the ANI column of `pairwise --estimate-ani` (ks_pairwise.py:29-84; k from PREFIX.extra)
     AfterJoin after;
     std::string dist;       // kSweep, kTree: the distance's name in their file names
-    std::string repr_out;   // kRepr: "" = PREFIX_kSpider_repr_sketches.txt
+    std::string repr_out;   // kRepr: "" = PREFIX_kSpider_repr_sketches.txt; kDerep: "" = PREFIX_kSpider_dereplicated_<dist>.tsv
     bool newick = false;    // kTree
     PairwiseJob(const char* index_prefix, int user_threads, AfterJoin::Kind kind = AfterJoin::kNone, int col = 0)
         : prefix(index_prefix), threads(user_threads < 1 ? 1 : user_threads) { after.kind = kind; after.col = col; }
@@ -404,6 +405,50 @@ void finish_tree(PairwiseJob& job, const Postings& P, const std::vector<ZeroRow>
     if (std::getenv("KSPIDER_VERBOSE")) std::cout << "kspider_amd: tree of " << tree_rows.size() << " merges from " << n_edges << " edges" << std::endl;
 }
 
+// the value text of every member's assigning record, while the device's records are still here: the writer's float, its text
+std::vector<std::string> derep_texts(const AfterJoin& A, const Postings& P, const ksp_edge* edges, const uint64_t n_edges) {
+    std::vector<std::string> text(A.rep.size());
+    for (size_t v = 0; v < A.rep.size(); ++v) {
+        if (A.rep[v] == v) continue;
+        const uint32_t e = A.via[v];
+        if (e >= n_edges) throw std::runtime_error("dereplicate: the device named a record that does not exist");
+        char buf[64];
+        buf[ksp::format_float(buf, column_value(A.col, edges[e].shared, P.counts[edges[e].source_1], P.counts[edges[e].source_2]))] = 0;
+        text[v] = buf;
+    }
+    return text;
+}
+
+// No host fix-up: at a threshold >= 0 a shared-0 row has the value 0 or NaN and never passes.  The device ranked the sources of
+// the index; a row of .namesMap without one has no neighbour and follows them, in node order, as every node of degree 0 does.
+void finish_derep(PairwiseJob& job, const Postings& P, const std::vector<std::string>& text, const std::vector<std::string>& name_of) {
+    const AfterJoin& A = job.after;
+    const uint64_t NN = name_of.size();
+    std::vector<ksp::DerepRow> rows((size_t)NN);
+    std::vector<uint8_t> seen((size_t)NN, 0);
+    uint32_t with_neighbour = 0, reps = 0;
+    for (uint32_t i = 0; i < (uint32_t)P.ids.size(); ++i) {
+        ksp::check_row_nodes(P.ids[i], P.ids[A.rep[i]], NN);
+        ksp::DerepRow& r = rows[P.ids[i] - 1];
+        r.rep = P.ids[A.rep[i]] - 1;
+        r.degree = A.degree[i];
+        r.rank = A.node[i];
+        r.text = text[i];
+        seen[P.ids[i] - 1] = 1;
+        with_neighbour += A.degree[i] != 0;
+    }
+    uint32_t next = with_neighbour;   // (index order is id order: the sources with a neighbour hold the ranks below this in both orders)
+    for (uint64_t v = 0; v < NN; ++v) {
+        if (!seen[v]) rows[v].rep = (uint32_t)v;
+        if (rows[v].degree == 0) rows[v].rank = next++;
+        reps += rows[v].rep == v;
+    }
+    ksp::write_derep_file(job.repr_out.empty() ? job.prefix + "_kSpider_dereplicated_" + job.dist + ".tsv" : job.repr_out, job.dist, rows, name_of);
+    if (std::getenv("KSPIDER_VERBOSE"))
+        std::cout << "kspider_amd: dereplicated " << NN << " sources: " << A.derep.kept << " records kept, " << reps << " representatives, " << A.derep.dispatched
+                  << " rounds and " << A.derep.tail << " in the tail" << std::endl;
+}
+
 // Mirrors src/pairwise.cpp:123-276 phase by phase (the head of this file), with what job.after asks for between the join and the files.
 int run_job(PairwiseJob& job) {
     AfterJoin& A = job.after;
@@ -442,6 +487,12 @@ int run_job(PairwiseJob& job) {
     if (rc != KSP_OK) return rc;
     std::vector<ForestEdge> forest;
     if (A.kind == AfterJoin::kTree) forest = device_forest(A, P, edges.get(), n_edges);
+    std::vector<std::string> derep_text, derep_names;
+    if (A.kind == AfterJoin::kDerep) {   // every source must be a row of .namesMap: refused before the TSV is written
+        ksp::read_names_map(job.prefix, derep_names);
+        for (const uint32_t id : P.ids) ksp::check_row_nodes(id, id, derep_names.size());
+        derep_text = derep_texts(A, P, edges.get(), n_edges);
+    }
     std::vector<ksp::EdgeRow> rows;
     const std::vector<ZeroRow> zero_rows = merge_rows(ix, P, A, edges.get(), n_edges, rows);
     edges.reset();
@@ -470,6 +521,7 @@ int run_job(PairwiseJob& job) {
         case AfterJoin::kCluster: finish_cluster(job, P, zero_rows, n_edges, ani_tab ? ani_tab->data() : nullptr); break;
         case AfterJoin::kSweep: finish_sweep(job, P, zero_rows, n_edges); break;
         case AfterJoin::kTree: finish_tree(job, P, zero_rows, n_edges, forest); break;
+        case AfterJoin::kDerep: finish_derep(job, P, derep_text, derep_names); break;
     }
     return KSP_OK;
 }
@@ -560,6 +612,20 @@ extern "C" int kspider_pairwise_and_repr(const char* index_prefix, int user_thre
     job.after.threshold = threshold;
     if (out_path) job.repr_out = out_path;
     return guarded("kspider_pairwise_and_repr", true, job);
+}
+
+extern "C" int kspider_pairwise_and_dereplicate(const char* index_prefix, int user_threads, const char* dist_type, double threshold, const char* out_path) {
+    if (!index_prefix) { ksp::set_error("kspider_pairwise_and_dereplicate: index_prefix is NULL"); return KSP_E_ARG; }
+    if (threshold != threshold) { ksp::set_error("kspider_pairwise_and_dereplicate: the threshold is NaN"); return KSP_E_ARG; }
+    if (threshold < 0) { ksp::set_error("kspider_pairwise_and_dereplicate: the threshold is negative (a row without shared k-mers would pass)"); return KSP_E_ARG; }
+    std::string dt;
+    const int col = dist_column(dist_type, "avg_cont", &dt);
+    if (!col) { ksp::set_error("kspider_pairwise_and_dereplicate: distance '" + dt + "' is not min_cont, avg_cont or max_cont"); return KSP_E_ARG; }
+    PairwiseJob job(index_prefix, user_threads, AfterJoin::kDerep, col);
+    job.dist = dt;
+    job.after.threshold = threshold;
+    if (out_path) job.repr_out = out_path;
+    return guarded("kspider_pairwise_and_dereplicate", true, job);
 }
 
 extern "C" int kspider_pairwise_cut(const char* index_prefix, int user_threads, const char* dist_type, double cutoff) {

@@ -289,6 +289,22 @@ int repr_edges_on_device(const uint32_t n_nodes, const ksp_edge* d_edges, const 
     return degrees_on_device(n_nodes, d_edges, nullptr, nullptr, n_edges, d_cnt, col, vcrit, h_degree, h_node, h_count, n_ranked);
 }
 
+// (derep.hip) the counting kernel and the key kernel on the caller's buffers of the CURRENT device, nothing read back: d_degree
+// (n_nodes counters, zeroed here) and d_keys, the key of EVERY node, not only of those with a neighbour.  Records cut by vcrit
+// (d_edges) or (d_a, d_b) pairs, as in degrees_on_device.
+int degree_keys_on_device(const uint32_t n_nodes, const ksp_edge* d_edges, const uint32_t* d_a, const uint32_t* d_b, const uint64_t n_edges,
+                          const uint32_t* d_cnt, const int col, const float vcrit, uint32_t* d_degree, uint64_t* d_keys) {
+    int rc = KSP_OK;
+    RP_HIP(hipMemsetAsync(d_degree, 0, (size_t)n_nodes * 4, nullptr));
+    if (d_edges) rc = launch_degree<true>(d_edges, nullptr, nullptr, n_edges, n_nodes, d_cnt, col, vcrit, d_degree);
+    else rc = launch_degree<false>(nullptr, d_a, d_b, n_edges, n_nodes, nullptr, 0, 0.0f, d_degree);
+    if (rc) goto done;
+    hipLaunchKernelGGL(k_degree_keys, dim3((unsigned)(((u64)n_nodes + 255) / 256)), dim3(256), 0, nullptr, (const u32*)d_degree, n_nodes, (u64*)d_keys);
+    RP_HIP(hipGetLastError());
+done:
+    return rc;
+}
+
 void write_repr_file(const std::string& out_path, const std::vector<uint32_t>& ids, const uint32_t* node, const uint32_t* count, const uint64_t n_ranked) {
     std::string text;
     text.reserve((size_t)n_ranked * 16);

@@ -28,6 +28,11 @@ SWEEP_MAX_CUTOFFS = 255
 #: records per chunk of the edge passes of the single-linkage tree (KSP_TREE_CHUNK_EDGES in the header)
 TREE_CHUNK_EDGES = 2048
 
+#: entries per chunk of the dereplication's edge passes, and the live pairs at which one workgroup finishes the rounds
+#: (KSP_DEREP_CHUNK_EDGES / KSP_DEREP_TAIL_PAIRS in the header)
+DEREP_CHUNK_EDGES = 2048
+DEREP_TAIL_PAIRS = 65536
+
 #: every symbol include/kspider_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "ksp_last_error", "ksp_device_count", "ksp_engine_create", "ksp_engine_destroy",
@@ -51,6 +56,7 @@ ABI_SYMBOLS = [
     "ksp_edges_cut", "ksp_pairwise_host_cut", "kspider_pairwise_cut",
     "ksp_components_edges_sweep", "ksp_components_sweep", "kspider_cluster_sweep", "kspider_pairwise_and_cluster_sweep",
     "ksp_edges_forest", "ksp_forest_ranked", "kspider_tree", "kspider_pairwise_and_tree", "kspider_cluster_from_tree",
+    "ksp_edges_dereplicate", "kspider_dereplicate", "kspider_pairwise_and_dereplicate",
 ]
 
 
@@ -203,6 +209,12 @@ def lib():
         L.kspider_tree.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]
         L.kspider_pairwise_and_tree.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.kspider_cluster_from_tree.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double]
+        L.ksp_edges_dereplicate.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.POINTER(ctypes.c_uint32)]
+        L.kspider_dereplicate.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double, ctypes.c_char_p]
+        L.kspider_pairwise_and_dereplicate.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_double, ctypes.c_char_p]
+        L.ksp_debug_derep_rounds.argtypes = [ctypes.c_void_p]
         _lib = L
     return _lib
 
@@ -500,6 +512,45 @@ def pairwise_and_tree(index_prefix: str, user_threads: int = 1, dist_type: str =
     """`pairwise` plus the tree files of `tree`, the forest taken from the edges while they are in HBM."""
     _check(lib().kspider_pairwise_and_tree(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
                                            int(bool(newick))))
+
+
+def edges_dereplicate(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, dist_col: int = 4, threshold: float = 0.20,
+                      device: int = 0, tail: int = 0, fill: int = 0) -> dict:
+    """The dereplicated set of ksp_edge records in DEVICE memory (include/kspider_amd.h): {"rep", "via", "rank", "degree"}, one entry
+    per node, and "n_reps".  rep[v] == v: v is a representative (via[v] = 0xFFFFFFFF); otherwise rep[v] stands for v through record
+    via[v].  tail / fill (tests): that many entries of `fill` are kept behind every array and checked to be untouched."""
+    out = {k: np.full(n_nodes + tail, fill, dtype=np.uint32) for k in ("rep", "via", "rank", "degree")}
+    n = ctypes.c_uint32(0xFFFFFFFF)
+    _check(lib().ksp_edges_dereplicate(device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, int(dist_col), float(threshold),
+                                       *[out[k].ctypes.data if (n_nodes + tail) else None for k in ("rep", "via", "rank", "degree")], ctypes.byref(n)))
+    for k, a in out.items():
+        if tail and (a[n_nodes:] != fill).any():
+            raise AssertionError(f"ksp_edges_dereplicate wrote behind {k}")
+    res = {k: a[:n_nodes].copy() for k, a in out.items()}
+    res["n_reps"] = int(n.value)
+    return res
+
+
+def derep_rounds() -> dict:
+    """(tests) What the last dereplication of this thread did (ksp_debug_derep_rounds, csrc/engine_internal.h): the rounds the host
+    dispatched, the rounds of the single-workgroup tail (0: it did not run), the live pairs when it took over, the records kept as pairs."""
+    out = np.zeros(4, dtype=np.uint64)
+    _check(lib().ksp_debug_derep_rounds(out.ctypes.data))
+    return dict(dispatched=int(out[0]), tail=int(out[1]), live_at_tail=int(out[2]), kept=int(out[3]))
+
+
+def dereplicate(index_prefix: str, dist_type: str = "avg_cont", threshold: float = 0.20, out_path: str | None = None) -> None:
+    """The dereplicated set of the pairwise TSV: PREFIX_kSpider_dereplicated_<DIST>.tsv (or out_path), one row per source of .namesMap
+    with its representative, the value of the row that assigns it, its neighbour count and its rank; the selection runs on the GPU."""
+    _check(lib().kspider_dereplicate(os.fsencode(index_prefix), dist_type.encode() if dist_type is not None else None, float(threshold),
+                                     os.fsencode(out_path) if out_path else None))
+
+
+def pairwise_and_dereplicate(index_prefix: str, user_threads: int = 1, dist_type: str = "avg_cont", threshold: float = 0.20,
+                             out_path: str | None = None) -> None:
+    """`pairwise` plus the file of `dereplicate`, the selection taken from the edges while they are in HBM."""
+    _check(lib().kspider_pairwise_and_dereplicate(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
+                                                  float(threshold), os.fsencode(out_path) if out_path else None))
 
 
 def cluster_from_tree(index_prefix: str, dist_type: str = "max_cont", cutoff: float = 0.0) -> None:
