@@ -138,9 +138,14 @@ void node_labels_of(const std::vector<uint32_t>& ids, const uint32_t* lab, const
 }
 
 // src/pairwise.cpp:127-181: the index, PREFIX_kSpider_seqToKmersNo.tsv and the k-mer counts, with the reference's progress lines
-int load_inputs(const PairwiseJob& job, ksp::IndexData& ix, std::unordered_map<uint32_t, uint32_t>& kmer_count) {
+int load_inputs(const PairwiseJob& job, ksp::IndexData& ix, std::unordered_map<uint32_t, uint32_t>& kmer_count, std::vector<std::string>& derep_names) {
     auto t0 = Clock::now();
     ksp::load_index(job.prefix, ix);
+    if (job.after.kind == AfterJoin::kDerep) {   // every source must be a row of .namesMap: refused before any file is written
+        ksp::read_names_map(job.prefix, derep_names);
+        for (auto& c : ix.colors)
+            for (uint32_t g : c.second) ksp::check_row_nodes(g, g, derep_names.size());
+    }
     if (job.after.kind == AfterJoin::kRepr)   // the reference tool reads the ids with stoi: refused before any file is written
         for (auto& c : ix.colors)
             for (uint32_t g : c.second)
@@ -459,7 +464,8 @@ int run_job(PairwiseJob& job) {
     }
     ksp::IndexData ix;
     std::unordered_map<uint32_t, uint32_t> kmer_count;
-    int rc = load_inputs(job, ix, kmer_count);
+    std::vector<std::string> derep_text, derep_names;
+    int rc = load_inputs(job, ix, kmer_count, derep_names);
     if (rc != KSP_OK) return rc;
 
     auto t0 = Clock::now();
@@ -487,12 +493,7 @@ int run_job(PairwiseJob& job) {
     if (rc != KSP_OK) return rc;
     std::vector<ForestEdge> forest;
     if (A.kind == AfterJoin::kTree) forest = device_forest(A, P, edges.get(), n_edges);
-    std::vector<std::string> derep_text, derep_names;
-    if (A.kind == AfterJoin::kDerep) {   // every source must be a row of .namesMap: refused before the TSV is written
-        ksp::read_names_map(job.prefix, derep_names);
-        for (const uint32_t id : P.ids) ksp::check_row_nodes(id, id, derep_names.size());
-        derep_text = derep_texts(A, P, edges.get(), n_edges);
-    }
+    if (A.kind == AfterJoin::kDerep) derep_text = derep_texts(A, P, edges.get(), n_edges);
     std::vector<ksp::EdgeRow> rows;
     const std::vector<ZeroRow> zero_rows = merge_rows(ix, P, A, edges.get(), n_edges, rows);
     edges.reset();

@@ -150,3 +150,116 @@ def boundary_case(col):
 def permuted(e, seed):
     p = np.random.default_rng(seed).permutation(len(e))
     return e[p], p
+
+
+HOSTILE = dict(stars=30, leaves=5, repeated=220, first_dropped=60, zero_count=24)
+
+
+def hostile(seed, n_nodes, n_records):
+    """(edges, k-mer counts, meta): a multigraph no writer of ours produces, seeded, every record at a random position.
+
+      stars      30 disjoint stars of 5 leaves whose centres are joined in a ring: 30 nodes of degree 7 that no other record
+                 names, ranked by id alone
+      repeated   220 pairs 2 .. 6 times each, in both orientations, every copy with its own `shared`; at 0.20 some copies are
+                 kept and some dropped in every column, and the lowest-index copy of the first 60 is dropped
+      self       about 2 % of the records, kept and dropped
+      outside    about 1 % of the records with one end >= n_nodes, on either side: n_nodes itself, 2^31, 0xFFFFFFFF, others
+      zero       24 nodes counting 0 k-mers, each with a record that is infinite in avg and max, a NaN record and a record to
+                 the next of them that is infinite in every column; the random records that name them add more
+      rest       random ends among the nodes of no star, values around the threshold: test_derep_gpu._random_case
+
+    meta: centres, repeated (the pairs (a, b), a < b), first_dropped (the first of them), zero, star_nodes, n_self, n_outside."""
+    H = HOSTILE
+    rng = np.random.default_rng([seed, n_nodes, n_records])
+    perm = rng.permutation(n_nodes)
+    n_star = H["stars"] * (H["leaves"] + 1)
+    star_nodes, zero, plain = perm[:n_star], perm[n_star:n_star + H["zero_count"]], perm[n_star + H["zero_count"]:]
+    assert len(plain) >= 2 * H["repeated"]
+    cnt = rng.integers(3000, 4001, size=n_nodes).astype(np.uint32)
+    cnt[zero] = 0
+    centres, leaves = np.sort(star_nodes[:H["stars"]]), star_nodes[H["stars"]:].reshape(H["stars"], H["leaves"])
+    s1, s2, frac, bump = [], [], [], []
+
+    def add(a, b, f, k=0):
+        s1.append(int(a)), s2.append(int(b)), frac.append(float(f)), bump.append(k)
+
+    keep, drop = (lambda: rng.uniform(0.3, 0.45)), (lambda: rng.uniform(0.02, 0.15))   # kept / dropped in all three columns
+    for c in range(H["stars"]):
+        for leaf in leaves[c]:
+            add(*((centres[c], leaf) if rng.random() < 0.5 else (leaf, centres[c])), keep())
+        add(centres[c], centres[(c + 1) % H["stars"]], keep())
+    pair_nodes = rng.choice(plain, size=(H["repeated"], 2), replace=False)        # (no node twice: the pairs are distinct)
+    copies = []                                                                  # per pair: the logical indices of its copies
+    for a, b in pair_nodes:
+        k = int(rng.integers(2, 7))
+        copies.append(list(range(len(s1), len(s1) + k)))
+        for j in range(k):
+            flip = j % 2 if j < 2 else rng.random() < 0.5                          # both orientations
+            add(*((b, a) if flip else (a, b)), 0.0, j)
+    n_self, n_out = max(2, n_records // 50), max(4, n_records // 100)
+    for j in range(n_self):
+        v = rng.choice(plain)
+        add(v, v, keep() if j % 2 else drop())
+    inside = np.concatenate([plain, zero])
+    beyond = [0xFFFFFFFF, 0xFFFFFFFF, n_nodes, n_nodes, 1 << 31] + rng.integers(n_nodes, 1 << 32, size=n_out, dtype=np.uint64).tolist()
+    first_out = len(s1)
+    for j in range(n_out):
+        v = rng.choice(inside)
+        add(*((beyond[j], v) if j % 2 else (v, beyond[j])), keep())
+    forced = {}                                                                  # logical index -> `shared`, whatever the counts
+    for i, z in enumerate(zero):                                                 # inf in avg and max, NaN, inf in all three columns
+        for a, b, sh in ((z, rng.choice(plain), int(rng.integers(1, 1500))), (rng.choice(plain), z, 0), (z, zero[(i + 1) % len(zero)], int(rng.integers(1, 1500)))):
+            forced[len(s1)] = sh
+            add(a, b, 0.0)
+    n_fill = n_records - len(s1)
+    assert n_fill > n_records // 4
+    fa, fb = rng.choice(inside, size=n_fill), rng.choice(inside, size=n_fill)
+    planted = {(min(int(x), int(y)), max(int(x), int(y))) for x, y in pair_nodes}
+    for a, b, f in zip(fa, fb, rng.uniform(0.02, 0.4, size=n_fill)):
+        if (min(int(a), int(b)), max(int(a), int(b))) in planted:                 # (no random copy of a planted pair)
+            b = zero[0]
+        add(a, b, f)
+    pos = rng.permutation(n_records)                                             # logical record j stands at pos[j]
+    frac = np.array(frac)
+    for p, idx in enumerate(copies):                                             # kept / dropped by the order of the positions
+        by_pos = sorted(idx, key=lambda j: pos[j])
+        flags = ([False, True] if p < H["first_dropped"] else [True, False]) + [bool(rng.random() < 0.5) for _ in by_pos[2:]]
+        for j, kept in zip(by_pos, flags):
+            frac[j] = keep() if kept else drop()
+    a, b = np.array(s1, dtype=np.uint64), np.array(s2, dtype=np.uint64)
+    ca, cb = (np.where(x < n_nodes, cnt[np.minimum(x, n_nodes - 1).astype(np.int64)], 1).astype(np.float64) for x in (a, b))
+    with np.errstate(divide="ignore"):
+        shared = (frac * 2.0 / (1.0 / ca + 1.0 / cb)).astype(np.uint64) + np.array(bump, dtype=np.uint64)
+    for idx in copies:                                                           # every copy its own `shared`
+        seen = set()
+        for j in idx:
+            while int(shared[j]) in seen:
+                shared[j] += 7
+            seen.add(int(shared[j]))
+    nil = (ca == 0) | (cb == 0)                                                 # an end of 0 k-mers: 0 shared (NaN, 0) or some (inf)
+    shared[nil] = rng.integers(0, 1500, size=int(nil.sum())) * (rng.random(int(nil.sum())) < 0.7)
+    shared[first_out:first_out + n_out] = KEEP
+    for j, sh in forced.items():
+        shared[j] = sh
+    e = np.zeros(n_records, dtype=EDGE_DTYPE)
+    e["source_1"][pos], e["source_2"][pos], e["shared"][pos] = a, b, shared
+    meta = dict(centres=centres.tolist(), star_nodes=sorted(star_nodes.tolist()), zero=sorted(zero.tolist()), n_self=n_self, n_outside=n_out,
+                repeated=[tuple(sorted((int(x), int(y)))) for x, y in pair_nodes])
+    meta["first_dropped"] = meta["repeated"][:H["first_dropped"]]
+    return e, cnt, meta
+
+
+def via_after_permutation(e2, kept2, res, res2):
+    """res over some records, res2 over the same records in the order e2 (kept2: its kept indices, ascending): rep, rank and
+    degree are equal, and every member's via is the lowest kept index of e2 that names the member and its representative."""
+    for k in ("rep", "rank", "degree"):
+        assert (res[k] == res2[k]).all(), k
+    first = {}
+    s1, s2 = e2["source_1"].tolist(), e2["source_2"].tolist()
+    for i in kept2:
+        first.setdefault((min(s1[i], s2[i]), max(s1[i], s2[i])), int(i))
+    rep = res["rep"].tolist()
+    members = [v for v in range(len(rep)) if rep[v] != v]
+    assert members
+    for v in members:
+        assert int(res2["via"][v]) == first[min(v, rep[v]), max(v, rep[v])], v

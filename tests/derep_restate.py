@@ -69,8 +69,9 @@ def render(dist, names, res, texts):
 
 
 def dereplicated_tsv(tsv_text, names, col=4, threshold=0.20, dist="avg_cont"):
-    """What kspider_dereplicate writes for this pairwise TSV: ids are 1-based rows of `names`; `via` counts the kept rows."""
-    rows = [l.split("\t") for l in tsv_text.split("\n")[1:] if l]
+    """What kspider_dereplicate writes for this pairwise TSV: ids are 1-based rows of `names`; `via` counts the kept rows.  A
+    field is read without the blanks around it, as the loader of `kSpider cluster` reads it (strip), and printed so."""
+    rows = [[x.strip() for x in l.split("\t")] for l in tsv_text.split("\n")[1:] if l]
     kept = [r for r in rows if rr.text_passes(r[col], threshold)]
     res = select(len(names), [(int(r[0]) - 1, int(r[1]) - 1, i) for i, r in enumerate(kept)])
     return render(dist, names, res, [r[col] for r in kept])

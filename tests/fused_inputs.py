@@ -307,6 +307,26 @@ def cutoffs(rows: list, col: int, outside: bool) -> list:
     return out
 
 
+def derep_thresholds(rows: list, col: int) -> list:
+    """The thresholds of the dereplication calls for a column, from the reference TSV: its quartile values, the float above
+    the middle one (as `cutoffs` makes it), then 0.0, 0.20, 1.0 (above every finite value), 2.0 (only an infinite value passes)
+    and +inf (nothing passes).  No negative one: the calls refuse them."""
+    picks = quartiles(rows, col)
+    out = list(picks)
+    if picks:
+        out.append(float(np.nextafter(picks[len(picks) // 2], 2.0)))
+    for t in (0.0, 0.20, 1.0, 2.0, math.inf):
+        if t not in out:
+            out.append(t)
+    return out
+
+
+def names_beyond(rows: list, col: int, t: float, n_names: int) -> bool:
+    """A row that passes the text test at t names an id above n_names: what kspider_dereplicate refuses."""
+    import repr_restate as rr
+    return any(rr.text_passes(r[col], t) and max(int(r[0]), int(r[1])) > n_names for r in rows)
+
+
 def unsure_cut(rows: list) -> float:
     """The column-3 cut at which the `unsure` pairs are looked at: the middle quartile value."""
     picks = quartiles(rows, 3)

@@ -1,7 +1,8 @@
 """The dereplication's definition without a GPU: the restatement of tests/derep_restate.py on hand-written
 graphs with hand-written answers, the four consequences as predicates on random graphs, the file renderer, and the shapes of
 the inputs tests/test_derep_gpu.py hands to the device — the live-pair counts of its tail cases by the round simulation of
-tests/derep_inputs.py, and its boundary floats."""
+tests/derep_inputs.py, its boundary floats, and what its hostile multigraphs plant: repeated pairs in both orientations whose first
+copy is dropped, self pairs, ends out of range, nodes of 0 k-mers, stars whose centres tie."""
 import numpy as np
 import pytest
 
@@ -126,3 +127,64 @@ def test_shapes_of_the_gpu_inputs():
         assert ["%.6g" % v for v in vals.tolist()][:3] == ["0.2", "0.199999", "nan"], col
         assert vals[0] < np.float32(0.2) and vals[3] >= 0.5
         assert dr.kept_records(e, cnt, col, 0.20) == [0, 3]
+
+
+C = engine.DEREP_CHUNK_EDGES
+HOSTILE_SIZES = ((700, 3 * C - 7), (20000, 2 * C + 1))           # (nodes, records) of tests/test_derep_gpu.py
+
+
+@pytest.mark.parametrize("n_nodes,n_records", HOSTILE_SIZES)
+def test_hostile_multigraph_plants_what_it_says(n_nodes, n_records):
+    e, cnt, meta = di.hostile(11, n_nodes, n_records)
+    e_again, cnt_again, _ = di.hostile(11, n_nodes, n_records)
+    assert len(e) == n_records and (e == e_again).all() and (cnt == cnt_again).all() and (di.hostile(12, n_nodes, n_records)[0] != e).any()
+    s1, s2 = e["source_1"].astype(np.int64), e["source_2"].astype(np.int64)
+    outside = (s1 >= n_nodes) | (s2 >= n_nodes)
+    assert 0.008 * n_records <= outside.sum() == meta["n_outside"] <= 0.012 * n_records
+    assert (s1 == 0xFFFFFFFF).any() and (s2 == 0xFFFFFFFF).any() and (s1 == n_nodes).any() and (s2 == n_nodes).any()
+    assert not ((s1 >= n_nodes) & (s2 >= n_nodes)).any()
+    selfs = np.nonzero((s1 == s2) & ~outside)[0]
+    assert 0.018 * n_records <= meta["n_self"] <= len(selfs) <= 0.03 * n_records       # (the random records add a few)
+    assert len(meta["zero"]) >= 20 and (cnt[meta["zero"]] == 0).all() and (cnt == 0).sum() == len(meta["zero"])
+    where = {}
+    for i, (a, b) in enumerate(zip(s1.tolist(), s2.tolist())):
+        where.setdefault((min(a, b), max(a, b)), []).append(i)
+    assert len(meta["repeated"]) == len(set(meta["repeated"])) >= 200
+    for col in (3, 4, 5):
+        kept = dr.kept_records(e, cnt, col, 0.20, n_nodes)
+        kept_set = set(kept)
+        assert any(i in kept_set for i in selfs.tolist()) and any(i not in kept_set for i in selfs.tolist())
+        vals = rr.column_values(e[~outside], cnt, col)
+        assert np.isinf(vals).any() and np.isnan(vals).any()
+        first_dropped = 0
+        for pair in meta["repeated"]:
+            idx = where[pair]
+            flags = [i in kept_set for i in idx]
+            assert 2 <= len(idx) <= 6 and True in flags and False in flags, pair
+            assert len({(int(s1[i]), int(s2[i])) for i in idx}) == 2                     # both orientations
+            assert len({int(e["shared"][i]) for i in idx}) == len(idx)                   # every copy its own `shared`
+            first_dropped += not flags[0]
+        assert first_dropped >= 50 and all(where[p][0] not in kept_set for p in meta["first_dropped"])
+        # the stars: no other record names their nodes, every centre has its 5 leaves and 2 ring neighbours, the ranks follow the ids
+        res = dr.dereplicate(e, cnt, col, 0.20, n_nodes)
+        di.consequences(n_nodes, e, np.array(kept, dtype=np.int64), res)
+        centres = meta["centres"]
+        assert len(centres) == 30 and centres == sorted(centres) and (res["degree"][centres] == 7).all()
+        assert (np.diff(res["rank"][centres].astype(np.int64)) > 0).all()
+        assert (res["degree"][sorted(set(meta["star_nodes"]) - set(centres))] == 1).all()
+        assert 1 < res["n_reps"] < n_nodes and len(kept) > n_records // 4
+    # copies of one pair in different 512-entry wave ranges and in different chunks
+    assert sum(len({i // 512 for i in where[p]}) > 1 for p in meta["repeated"]) >= 150
+    assert sum(len({i // C for i in where[p]}) > 1 for p in meta["repeated"]) >= 100
+
+
+@pytest.mark.parametrize("n_nodes,n_records", HOSTILE_SIZES)
+def test_hostile_multigraph_permuted(n_nodes, n_records):
+    e, cnt, _ = di.hostile(11, n_nodes, n_records)
+    e2, _ = di.permuted(e, 3)
+    for col in (3, 4, 5):
+        res, res2 = dr.dereplicate(e, cnt, col, 0.20, n_nodes), dr.dereplicate(e2, cnt, col, 0.20, n_nodes)
+        kept2 = dr.kept_records(e2, cnt, col, 0.20, n_nodes)
+        di.consequences(n_nodes, e2, np.array(kept2, dtype=np.int64), res2)
+        di.via_after_permutation(e2, kept2, res, res2)
+        assert (res["via"] != res2["via"]).any()

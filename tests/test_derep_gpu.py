@@ -4,7 +4,9 @@ hundreds of rounds, with the single-workgroup tail and without it; the tail's sw
 pairs; a representative of smaller rank that is decided later than the one that knocks the node out; stars, a clique,
 isolated nodes, self pairs, an endpoint out of range; the boundary floats of the text test; the sizes where a ballot and a
 chunk begin and end and a grid so small that every workgroup loops; random graphs on both sides of the counting kernel's
-LDS switch; the join's own records and the file-writing calls on a 400-source index.  Every output array has sentinels behind
+LDS switch; seeded multigraphs (tests/derep_inputs.hostile: repeated pairs in both orientations, self pairs, ends out of range, nodes
+of 0 k-mers, tied stars) in two sizes, every column, both round modes and a second record order; the join's own records and the
+file-writing calls on a 400-source index; a pairwise TSV written by hand.  Every output array has sentinels behind
 it and d_edges is compared after every call.  The inputs come from tests/derep_inputs.py, whose shapes
 tests/test_derep_cpu.py checks without a GPU."""
 import functools
@@ -208,6 +210,33 @@ def test_random_graphs_on_both_sides_of_the_lds_switch(n_nodes):
         assert (seen[0][k] == seen[1][k]).all(), k
 
 
+@functools.lru_cache(maxsize=None)
+def _hostile_case(n_nodes, n_records):
+    e, cnt, _ = di.hostile(11, n_nodes, n_records)
+    e2, _ = di.permuted(e, 3)
+    want = {(k, col): dr.dereplicate(ee, cnt, col, 0.20, n_nodes) for k, ee in enumerate((e, e2)) for col in (3, 4, 5)}
+    kept2 = {col: dr.kept_records(e2, cnt, col, 0.20, n_nodes) for col in (3, 4, 5)}
+    return e, e2, cnt, want, kept2
+
+
+@pytest.mark.parametrize("tail", ["1", "0"])
+@pytest.mark.parametrize("n_nodes,n_records", [(700, 3 * C - 7), (20000, 2 * C + 1)])
+def test_hostile_multigraphs(monkeypatch, n_nodes, n_records, tail):
+    """Dense on 700 nodes (several rounds) and beyond the counting kernel's LDS switch on 20 000; with the tail, and with host-driven
+    rounds on a grid of 2 workgroups.  The 64-bit atomicMin of (rank, index) decides among 2 .. 6 copies of a pair whose first
+    copy is often dropped; what tests/test_derep_cpu.py shows about the inputs holds for the restatement alone."""
+    monkeypatch.setenv("KSP_DEREP_TAIL", tail)
+    if tail == "0":
+        monkeypatch.setenv("KSP_DEREP_MAX_WORKGROUPS", "2")
+    e, e2, cnt, want, kept2 = _hostile_case(n_nodes, n_records)
+    for col in (3, 4, 5):
+        got, r = _check(n_nodes, e, cnt, col, want=want[0, col])
+        assert (r["tail"] > 0) == (tail == "1") and r["dispatched"] >= 1, r
+        got2, _ = _check(n_nodes, e2, cnt, col, want=want[1, col])
+        di.consequences(n_nodes, e2, np.array(kept2[col], dtype=np.int64), got2)
+        di.via_after_permutation(e2, kept2[col], got, got2)
+
+
 def test_rank_of_the_nodes_with_a_neighbour_is_the_order_of_edges_repr():
     e, cnt = _random_case(3000, 7, 1000)
     ed, cd = engine.DeviceBuffer.from_numpy(e), engine.DeviceBuffer.from_numpy(cnt)
@@ -321,3 +350,42 @@ def test_exe_and_refusals(full):
     with pytest.raises(engine.KspError) as ei:
         engine.pairwise_and_dereplicate(prefix, 1, None, 0.2)
     assert ei.value.code == engine.KSP_E_IO and sorted(os.listdir(d)) == before
+
+
+HAND_ROWS = (                       # source_1, source_2, shared_kmers, min, avg, max: all three columns carry the row's value
+    ("2", "1", "0.1"),              # the pair 1 - 2 three times, both orientations, the failing value first
+    ("1", "2", "0.200001"),
+    ("2", "1", "inf"),
+    ("3", "3", "0.5"),              # two self rows, one passes
+    ("4", "4", "1e-1"),
+    ("3", "4", "nan"),
+    ("4", "3", "-nan"),
+    ("5", "3", "0.2"),              # reads as 0.2f, above 0.20
+    ("5", "1", "0.200001 "),        # a blank behind the value
+    ("6", "5", "inf"),
+    ("6", "2", "0.3"),
+    ("9", "1", "0.1"),              # fails: the id beyond .namesMap is never looked at
+)
+
+
+def test_a_tsv_no_writer_of_ours_produced(tmp_path):
+    prefix = str(tmp_path / "hand")
+    names = [f"g{i}" for i in range(1, 8)]
+    with open(prefix + ".namesMap", "w") as f:
+        f.write(f"{len(names)}\n" + "".join(f"{i + 1} {n}\n" for i, n in enumerate(names)))
+    with open(prefix + "_kSpider_seqToKmersNo.tsv", "w") as f:
+        f.write("ID\tseq\tkmers\n" + "".join(f"{i + 1}\t{i + 1}\t{100 + i}\n" for i in range(len(names))))
+    text = "source_1\tsource_2\tshared_kmers\tmin_containment\tavg_containment\tmax_containment\n" + \
+           "".join(f"{a}\t{b}\t7\t{v}\t{v}\t{v}\n" for a, b, v in HAND_ROWS)
+    assert len(HAND_ROWS) == 12
+    with open(prefix + "_kSpider_pairwise.tsv", "w") as f:
+        f.write(text)
+    for dist, col in DISTS.items():
+        want = dr.dereplicated_tsv(text, names, col, 0.20, dist)
+        engine.dereplicate(prefix, dist, 0.20)
+        assert _read(prefix + f"_kSpider_dereplicated_{dist}.tsv") == want, dist
+    # by hand: 1 has the rows to 2 (twice), 5; 5 has 3, 1, 6; 2 has 1 (twice), 6; 3 has its self row (2) and 5; 6 has 5, 2
+    rows = [l.split("\t") for l in want.decode().split("\n")[1:-1]]
+    assert [r[3] for r in rows] == ["3", "3", "3", "0", "3", "2", "0"]
+    assert [r[4] for r in rows] == ["0", "1", "2", "5", "3", "4", "6"]
+    assert [r[1] for r in rows] == ["g1", "g1", "g3", "g4", "g1", "g6", "g7"] and rows[1][2] == "0.200001" and rows[4][2] == "0.200001"

@@ -1,7 +1,9 @@
 """What tests/test_fused_random_gpu.py relies on, shown with the oracle alone: per (shape, seed) of fused_inputs.CASES the index is
 written, oracle.ref_pairwise writes the TSV, and the rows that make the GPU test mean something are counted there — rows that
 exist only with shared_kmers = 0 in both NaN positions, infinite values, zero pairs that are real rows, the cut's `unsure`
-pairs, components and a ranking that differ with and without the shared-0 rows, and cut-offs that cut."""
+pairs, components and a ranking that differ with and without the shared-0 rows, and cut-offs that cut; and, for the "derep" kind,
+what tests/derep_restate.py makes of that TSV: rows of degree 0 with and without a source interleaved by id, more kept rows than
+one chunk, members with a choice of representatives, rank ties, members through an infinite value."""
 import os
 import shutil
 
@@ -9,8 +11,10 @@ import numpy as np
 import pytest
 
 import cut_restate as cr
+import derep_restate as dr
 import fused_inputs as fz
 import repr_restate as rr
+from kspider_amd import engine
 from oracle import ref_cluster
 
 
@@ -175,3 +179,101 @@ def test_variant_with_counts_has_no_nan_row(cases, oracle_lib, shape, seed):
     rows = fz.rows_of(tsv)
     assert len(rows) == len(cases[shape, seed]["rows"]) and any(r[2] == "0" for r in rows)
     assert all(0.0 <= float(t) <= 1.0 for r in rows for t in r[3:])
+
+
+def _derep(case, dist, t):
+    """(kept rows of the oracle TSV, the rows of the restatement's file as dicts) for a distance and a threshold."""
+    fi, col = case["fi"], fz.DISTS[dist]
+    names = [f"genome_{i + 1}" for i in range(fi.NN)]
+    out = dr.dereplicated_tsv(case["tsv"].decode(), names, col, t, dist).decode().split("\n")
+    assert out[0] == f"source\trepresentative\t{dist}\tneighbours\trank" and out[-1] == "" and len(out) == fi.NN + 2
+    table = []
+    for v, line in enumerate(out[1:-1]):
+        name, rep, text, degree, rank = line.split("\t")
+        assert name == names[v]
+        table.append(dict(id=v + 1, rep=int(rep[len("genome_"):]), text=text, degree=int(degree), rank=int(rank)))
+    assert sorted(r["rank"] for r in table) == list(range(fi.NN))
+    return [r for r in case["rows"] if rr.text_passes(r[col], t)], table
+
+
+def _between(flags):
+    """Some True entry lies between two False ones."""
+    return any(f and False in flags[:i] and False in flags[i + 1:] for i, f in enumerate(flags))
+
+
+@pytest.mark.parametrize("shape,seed", fz.CASES)
+def test_dereplication_rows_the_gpu_test_relies_on(cases, shape, seed):
+    """Inequalities on the restatement of the oracle's TSV, per shape: what makes the "derep" kind of
+    tests/test_fused_random_gpu.py exercise the finisher's renumbering of the degree-0 rows, the device's chunk loop, the
+    assignment's choice, the id tie-break of the ranks and the infinite values."""
+    case = cases[shape, seed]
+    fi, NN = case["fi"], case["fi"].NN
+    is_rep = lambda r: r["rep"] == r["id"]
+    for dist, col in fz.DISTS.items():
+        ladder = fz.derep_thresholds(case["rows"], col)
+        assert {0.0, 0.20, 1.0, 2.0} <= set(ladder) and ladder[-1] == float("inf") and len(set(ladder)) == len(ladder) and min(ladder) >= 0
+        # degree-0 rows of sources and rows without a source, interleaved by id in both ways
+        kept, table = _derep(case, dist, 0.20)
+        lone = [r["id"] in fi.ids for r in table if r["degree"] == 0]
+        print(f"{shape}/{seed} {dist} at 0.20: {len(kept)} kept, {sum(lone)} degree-0 sources, {len(lone) - sum(lone)} rows without a source")
+        assert _between(lone) and _between([not f for f in lone]), dist
+        assert all(is_rep(r) and r["text"] == "-" for r in table if r["degree"] == 0)
+        kept, table = _derep(case, dist, float("inf"))
+        assert not kept and all(is_rep(r) for r in table) and [r["rank"] for r in table] == list(range(NN))
+        if shape == "mixed":
+            kept, table = _derep(case, dist, 0.0)
+            reps = {r["id"] for r in table if is_rep(r)}
+            nbrs = {}
+            for r in kept:
+                a, b = int(r[0]), int(r[1])
+                nbrs.setdefault(a, set()).add(b)
+                nbrs.setdefault(b, set()).add(a)
+            choice = sum(len(nbrs[r["id"]] & reps) >= 2 for r in table if not is_rep(r))
+            degrees = [r["degree"] for r in table if r["degree"] > 0]
+            print(f"{shape}/{seed} {dist} at 0.0: {len(kept)} kept, {len(reps)} representatives of {NN}, {choice} members with a choice, "
+                  f"largest degree {max(degrees)}")
+            assert len(kept) > engine.DEREP_CHUNK_EDGES
+            assert NN / 4 <= len(reps) <= NN / 2
+            assert choice >= 20
+            assert len(set(degrees)) < len(degrees)                                  # two sources of one degree: the id breaks the tie
+            if dist == "min_cont":
+                assert 1 <= len(_derep(case, dist, 0.20)[0]) <= 50
+            else:
+                kept, table = _derep(case, dist, 2.0)
+                assert len(kept) >= 100 and all(r[col] == "inf" for r in kept)
+                assert sum(r["text"] == "inf" for r in table) >= 50
+            # what the GPU test reads from the written file at 0.0: the planted ids
+            assert fi.rank_flip[0] in fi.ids and set(range(1, NN + 1)) - set(fi.ids)
+    if shape == "tiny":
+        assert any(r["text"] == "inf" for dist, col in fz.DISTS.items() for t in fz.derep_thresholds(case["rows"], col)
+                   for r in _derep(case, dist, t)[1])
+    if shape == "no_counts":
+        for dist, col in fz.DISTS.items():
+            at0, at2 = _derep(case, dist, 0.0)[0], _derep(case, dist, 2.0)[0]
+            assert at0 and at0 == at2 and all(r[col] == "inf" for r in at0)
+    if shape == "one_edge":
+        for dist, col in fz.DISTS.items():
+            kept, table = _derep(case, dist, 0.0)
+            assert len(kept) == 1 and sum(not is_rep(r) for r in table) == 1
+            above = float(np.nextafter(np.float32(rr.strtof(kept[0][col])), np.float32(2.0)))
+            ladder = fz.derep_thresholds(case["rows"], col)
+            up = min(t for t in ladder if t >= above)
+            assert up < float("inf") and all(is_rep(r) for r in _derep(case, dist, up)[1])
+    if shape == "all_zero":
+        for dist in fz.DISTS:
+            kept, table = _derep(case, dist, 0.0)
+            assert not kept and all(is_rep(r) for r in table) and [r["rank"] for r in table] == list(range(NN))
+
+
+def test_a_short_names_map_gives_both_outcomes_on_a_tiny_case(cases):
+    """.namesMap cut to one row fewer than the largest source id, as tests/test_fused_random_gpu.py cuts it: on one "tiny" case at
+    least a passing row names the missing id at some threshold of the ladder and none does at another.  (On "tiny" seed 1 the
+    largest id has rows with shared_kmers = 0 only, which pass no threshold >= 0: that case shows the second outcome alone.)"""
+    both = 0
+    for (shape, seed), case in cases.items():
+        if shape == "tiny":
+            short = max(case["fi"].ids) - 1
+            seen = {fz.names_beyond(case["rows"], col, t, short) for col in fz.DISTS.values() for t in fz.derep_thresholds(case["rows"], col)}
+            assert False in seen
+            both += seen == {True, False}
+    assert both >= 1

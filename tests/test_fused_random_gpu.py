@@ -4,7 +4,12 @@ shared_kmers = 0 on either side of a source of 0 k-mers, infinite values, the cu
 workers and with postings slices.  Every expected file comes from the reference side: oracle.ref_pairwise, oracle.ref_cluster
 and the restatements under tests/; nothing expected is made by the code under test.
 
-One test is one kind of call on one index in one mode.  The "all_zero" index (no posting at all) comes last."""
+One test is one kind of call on one index in one mode.  The "all_zero" index (no posting at all) comes last.
+
+The "derep" kind runs kspider_pairwise_and_dereplicate and, on the oracle's own TSV, kspider_dereplicate at every threshold of
+fused_inputs.derep_thresholds against tests/derep_restate.py: degree-0 sources interleaved with .namesMap rows that are no source,
+infinite values as members' texts, an index without a posting; it has one mode of its own, "notail" (host-driven rounds on a grid
+of one workgroup).  What the restatement shows about these indexes is in tests/test_fused_inputs_cpu.py."""
 import glob
 import os
 import shutil
@@ -14,6 +19,7 @@ import pytest
 
 import ani_restate
 import cut_restate as cr
+import derep_restate as dr
 import fused_inputs as fz
 import repr_restate as rr
 import tree_restate as tr
@@ -24,7 +30,8 @@ pytestmark = pytest.mark.gpu
 
 SCALE = 1000
 MODES = {"one": {}, "two": {"KSPIDER_DEVICES": "0,0"}, "three": {"KSPIDER_DEVICES": "0,0,0"}, "slices": {"KSP_SLICES": "3"}}
-KINDS = ("pairwise", "cut", "cluster", "sweep", "repr", "tree", "ani")
+DEREP_MODES = {"notail": {"KSP_DEREP_TAIL": "0", "KSP_DEREP_MAX_WORKGROUPS": "1"}}      # the "derep" kind only, "tiny" and "mixed"
+KINDS = ("pairwise", "cut", "cluster", "sweep", "repr", "tree", "ani", "derep")
 
 
 def _params():
@@ -35,6 +42,8 @@ def _params():
             for kind in KINDS:
                 if kind != "ani" or full:
                     out.append(pytest.param(shape, seed, mode, kind, id=f"{shape}{seed}-{mode}-{kind}"))
+        for mode in (DEREP_MODES if full else ()):
+            out.append(pytest.param(shape, seed, mode, "derep", id=f"{shape}{seed}-{mode}-derep"))
     return out
 
 
@@ -241,12 +250,148 @@ def _ani(case, tmp_path, counted):
         assert _read(os.path.join(os.path.dirname(prefix), name)) == data, c
 
 
+def _names(n):
+    return [f"genome_{i + 1}" for i in range(n)]
+
+
+def _want_derep(case, dist, t, n_names=None):
+    """The restatement's file for the reference TSV: computed once per (distance, threshold, rows of .namesMap)."""
+    n = case["fi"].NN if n_names is None else n_names
+    memo = case.setdefault("derep", {})
+    if (dist, t, n) not in memo:
+        memo[dist, t, n] = dr.dereplicated_tsv(case["tsv"].decode(), _names(n), fz.DISTS[dist], t, dist)
+    return memo[dist, t, n]
+
+
+def _derep_files(prefix):
+    return sorted(os.path.basename(p) for p in glob.glob(prefix + "_kSpider_dereplicated_*"))
+
+
+def _derep_table(data):
+    """{id: (representative id, text, degree, rank)} of a dereplicated file whose names are genome_<id>."""
+    cut = len("genome_")
+    return {int(p[0][cut:]): (int(p[1][cut:]), p[2], int(p[3]), int(p[4])) for p in (l.split("\t") for l in data.decode().split("\n")[1:-1])}
+
+
+def _derep(case, tmp_path):
+    fi, rows = case["fi"], case["rows"]
+    prefix = _fresh(case, tmp_path)
+    shutil.copytree(case["dir"] / "full", tmp_path / "tsv")              # the oracle's own TSV: its shared-0, NaN and inf rows
+    full_prefix = str(tmp_path / "tsv" / "ix")
+    for dist, col in fz.DISTS.items():
+        name = f"ix_kSpider_dereplicated_{dist}.tsv"
+        for t in fz.derep_thresholds(rows, col):
+            want = _want_derep(case, dist, t)
+            _forget(prefix, "_kSpider_dereplicated_*")
+            engine.pairwise_and_dereplicate(prefix, 2, dist, t)
+            _check_tsvs(case, prefix)
+            assert _derep_files(prefix) == [name], (dist, t)
+            got = _read(prefix + f"_kSpider_dereplicated_{dist}.tsv")
+            assert got == want, (dist, t)
+            engine.dereplicate(full_prefix, dist, t)
+            assert _derep_files(full_prefix) == [name], (dist, t)
+            assert _read(full_prefix + f"_kSpider_dereplicated_{dist}.tsv") == want, (dist, t)
+            os.remove(full_prefix + f"_kSpider_dereplicated_{dist}.tsv")
+            if fi.shape == "mixed" and t in (0.0, 2.0):
+                _check_mixed_rows(fi, rows, col, t, _derep_table(got))
+    # out_path: the same bytes there, and no file of the default name
+    (tmp_path / "elsewhere").mkdir()
+    out = str(tmp_path / "elsewhere" / "mine.tsv")
+    _forget(prefix, "_kSpider_dereplicated_*")
+    engine.pairwise_and_dereplicate(prefix, 2, "avg_cont", 0.0, out)
+    _check_tsvs(case, prefix)
+    assert _read(out) == _want_derep(case, "avg_cont", 0.0) and _derep_files(prefix) == []
+    assert sorted(os.listdir(tmp_path / "elsewhere")) == ["mine.tsv"]
+
+
+def _check_mixed_rows(fi, rows, col, t, table):
+    """Read from the written file (not from a trace): at 0.0 the planted source of the rank flip has its neighbours and a row
+    of .namesMap without a source ranks among the degree-0 rows; at 2.0 the source without a count entry stands, wherever it has a
+    real row among this column's infinite values, with neighbours: a representative, or a member through an "inf" text."""
+    assert sorted(table) == list(range(1, fi.NN + 1))
+    connected = sum(deg > 0 for _, _, deg, _ in table.values())
+    if t == 0.0:
+        assert table[fi.rank_flip[0]][2] >= 2                          # (an island is a triangle of real rows)
+        lone = [v for v in table if v not in fi.ids]
+        assert lone and all(table[v][:3] == (v, "-", 0) and table[v][3] >= connected for v in lone)
+    else:
+        nc, = fi.no_count
+        if any(r[2] != "0" and r[col] == "inf" and str(nc) in r[:2] for r in rows):
+            rep, text, deg, _ = table[nc]
+            assert deg > 0 and text == ("-" if rep == nc else "inf")
+
+
+@pytest.mark.parametrize("seed", [seed for shape, seed in fz.CASES if shape == "tiny"])
+def test_derep_refuses_an_id_beyond_names_map(cases, tmp_path, seed):
+    """.namesMap one row shorter than the largest source id.  The fused call refuses before any TSV is written; the TSV call
+    refuses exactly when a passing row names the missing id and otherwise writes the restatement's file for the shorter list."""
+    case = cases["tiny", seed]
+    fi, rows = case["fi"], case["rows"]
+    short = max(fi.ids) - 1
+    prefix = _fresh(case, tmp_path)
+    shutil.copytree(case["dir"] / "full", tmp_path / "tsv")
+    full_prefix = str(tmp_path / "tsv" / "ix")
+    for p in (prefix, full_prefix):
+        with open(p + ".namesMap", "w") as f:
+            f.write(f"{short}\n" + "".join(f"{i + 1} genome_{i + 1}\n" for i in range(short)))
+    before = sorted(os.listdir(os.path.dirname(prefix)))
+    for dist in fz.DISTS:
+        with pytest.raises(engine.KspError) as ei:
+            engine.pairwise_and_dereplicate(prefix, 2, dist, 0.20)
+        assert ei.value.code == engine.KSP_E_IO and sorted(os.listdir(os.path.dirname(prefix))) == before
+    before = sorted(os.listdir(os.path.dirname(full_prefix)))
+    outcomes = set()
+    for dist, col in fz.DISTS.items():
+        out = full_prefix + f"_kSpider_dereplicated_{dist}.tsv"
+        for t in fz.derep_thresholds(rows, col):
+            names_it = fz.names_beyond(rows, col, t, short)
+            outcomes.add(names_it)
+            if names_it:
+                with pytest.raises(engine.KspError) as ei:
+                    engine.dereplicate(full_prefix, dist, t)
+                assert ei.value.code == engine.KSP_E_IO and "namesMap" in str(ei.value), (dist, t)
+            else:
+                engine.dereplicate(full_prefix, dist, t)
+                assert _read(out) == _want_derep(case, dist, t, short), (dist, t)
+                os.remove(out)
+            assert sorted(os.listdir(os.path.dirname(full_prefix))) == before, (dist, t)
+    assert False in outcomes                  # (and True for one seed at least: tests/test_fused_inputs_cpu.py)
+
+
+def test_derep_calls_in_one_sequence(cases, tmp_path, monkeypatch):
+    """One "mixed" prefix, one process: the fused call, another fused kind, the fused call with two workers, the TSV call on what
+    they left — every file is the one-shot expectation."""
+    case = cases["mixed", 1]
+    prefix = _fresh(case, tmp_path)
+    folder = os.path.dirname(prefix)
+    engine.pairwise_and_dereplicate(prefix, 2, "avg_cont", 0.0)
+    _check_tsvs(case, prefix)
+    assert _read(prefix + "_kSpider_dereplicated_avg_cont.tsv") == _want_derep(case, "avg_cont", 0.0)
+    _forget(prefix)
+    engine.pairwise_and_cluster(prefix, 2, "max_cont", 0.0)
+    _check_tsvs(case, prefix)
+    cname, cdata = _want_clusters(case, "max_cont", 0.0)
+    assert _read(os.path.join(folder, cname)) == cdata
+    _forget(prefix)
+    monkeypatch.setenv("KSPIDER_DEVICES", "0,0")
+    engine.pairwise_and_dereplicate(prefix, 2, "min_cont", 0.20)
+    monkeypatch.delenv("KSPIDER_DEVICES")
+    _check_tsvs(case, prefix)
+    engine.dereplicate(prefix, "max_cont", 2.0)
+    _check_tsvs(case, prefix)
+    want = {f"ix_kSpider_dereplicated_{d}.tsv": _want_derep(case, d, t) for d, t in (("avg_cont", 0.0), ("min_cont", 0.20), ("max_cont", 2.0))}
+    assert _derep_files(prefix) == sorted(want)
+    for name, data in want.items():
+        assert _read(os.path.join(folder, name)) == data, name
+    assert _read(os.path.join(folder, cname)) == cdata and len(set(want.values())) == 3
+
+
 @pytest.mark.parametrize("shape,seed,mode,kind", _params())
 def test_fused_call(cases, tmp_path, monkeypatch, shape, seed, mode, kind):
-    for name, value in MODES[mode].items():
+    for name, value in {**MODES, **DEREP_MODES}[mode].items():
         monkeypatch.setenv(name, value)
     case = cases[shape, seed]
     if kind == "ani":
         _ani(case, tmp_path, cases[shape, seed, "counted"])
     else:
-        {"pairwise": _pairwise, "cut": _cut, "cluster": _cluster, "sweep": _sweep, "repr": _repr, "tree": _tree}[kind](case, tmp_path)
+        {"pairwise": _pairwise, "cut": _cut, "cluster": _cluster, "sweep": _sweep, "repr": _repr, "tree": _tree, "derep": _derep}[kind](case, tmp_path)
