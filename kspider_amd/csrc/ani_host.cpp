@@ -22,6 +22,7 @@
 #include "ani.h"
 #include "engine_internal.h"
 #include "index_io.h"
+#include "partial_file.h"
 
 namespace ksp {
 
@@ -165,17 +166,13 @@ void split_lines(const std::string& s, std::vector<std::pair<size_t, size_t>>& l
 }
 
 void write_through_partial(const std::string& path, const std::vector<std::string>& parts) {
-    const std::string tmp = path + ".partial";
-    {
-        std::ofstream f(tmp, std::ios::binary);
-        if (!f) throw std::runtime_error("cannot write " + tmp);
-        f << "avg_ani\n";
-        for (auto& s : parts)
-            if (!s.empty() && !f.write(s.data(), (std::streamsize)s.size())) break;
-        f.flush();
-        if (!f) { f.close(); std::remove(tmp.c_str()); throw std::runtime_error("write failed on " + tmp); }
-    }
-    if (std::rename(tmp.c_str(), path.c_str()) != 0) { std::remove(tmp.c_str()); throw std::runtime_error("cannot rename " + tmp); }
+    std::ofstream f;
+    PartialFiles files;
+    files.open(path, f);
+    f << "avg_ani\n";
+    for (auto& s : parts)
+        if (!s.empty() && !f.write(s.data(), (std::streamsize)s.size())) break;
+    files.commit();
 }
 
 template <class F>

@@ -35,8 +35,10 @@
 #include "ani.h"
 #include "cc_kernels.hip.h"
 #include "cluster_inputs.h"
+#include "device_call.h"
 #include "edge_cut.hip.h"
 #include "engine_internal.h"
+#include "partial_file.h"
 
 typedef uint32_t u32;
 typedef uint64_t u64;
@@ -117,16 +119,6 @@ __global__ void k_cc_hook_kept(const ksp_edge* __restrict__ ed, u64 m, const uns
     }
 }
 
-#define CL_HIP(call)                                                                     \
-    do {                                                                                 \
-        hipError_t err__ = (call);                                                       \
-        if (err__ != hipSuccess) {                                                       \
-            ksp::set_error(std::string(#call) + ": " + hipGetErrorString(err__));        \
-            rc = KSP_E_HIP;                                                              \
-            goto done;                                                                   \
-        }                                                                                \
-    } while (0)
-
 }  // namespace
 
 extern "C" int ksp_components(int device, uint32_t n_nodes, const uint32_t* h_a, const uint32_t* h_b, uint64_t n_edges,
@@ -135,21 +127,13 @@ extern "C" int ksp_components(int device, uint32_t n_nodes, const uint32_t* h_a,
     for (u64 e = 0; e < n_edges; ++e)
         if (h_a[e] >= n_nodes || h_b[e] >= n_nodes) { ksp::set_error("ksp_components: node index out of range"); return KSP_E_ARG; }
     int rc = KSP_OK;
+    ksp::DeviceArena A;
     u32 *d_a = nullptr, *d_b = nullptr, *d_parent = nullptr, *d_changed = nullptr;
     u32 h_changed = 1;
-    int ndev = 0;
-    CL_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) { ksp::set_error("ksp_components: no such device"); return KSP_E_HIP; }
-    CL_HIP(hipSetDevice(device));
+    if ((rc = ksp::set_device("ksp_components", device))) return rc;
     if (n_nodes == 0) return KSP_OK;
-    CL_HIP(hipMalloc((void**)&d_parent, (size_t)n_nodes * 4));
-    CL_HIP(hipMalloc((void**)&d_changed, 4));
-    if (n_edges) {
-        CL_HIP(hipMalloc((void**)&d_a, n_edges * 4));
-        CL_HIP(hipMalloc((void**)&d_b, n_edges * 4));
-        CL_HIP(hipMemcpy(d_a, h_a, n_edges * 4, hipMemcpyHostToDevice));
-        CL_HIP(hipMemcpy(d_b, h_b, n_edges * 4, hipMemcpyHostToDevice));
-    }
+    if ((rc = A.alloc(&d_parent, (size_t)n_nodes)) || (rc = A.alloc(&d_changed, 1))) return rc;
+    if (n_edges && (rc = ksp::upload_pairs(A, h_a, h_b, n_edges, &d_a, &d_b))) return rc;
     {
         const unsigned gn = (n_nodes + 255) / 256;
         const unsigned ge = (unsigned)std::min<u64>((n_edges + 255) / 256, 1u << 16);
@@ -157,20 +141,16 @@ extern "C" int ksp_components(int device, uint32_t n_nodes, const uint32_t* h_a,
         // every round at least halves the depth of every tree and merges what an edge connects: O(log n) rounds;
         // the bound only guards against a defect
         for (int round = 0; n_edges && h_changed && round < 10000; ++round) {
-            CL_HIP(hipMemsetAsync(d_changed, 0, 4, nullptr));
+            KSP_TRY_HIP(hipMemsetAsync(d_changed, 0, 4, nullptr));
             hipLaunchKernelGGL(k_cc_hook, dim3(ge), dim3(256), 0, nullptr, d_a, d_b, n_edges, d_parent, d_changed);
             hipLaunchKernelGGL(k_cc_jump, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes, d_changed);
             hipLaunchKernelGGL(k_cc_jump, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes, d_changed);
-            CL_HIP(hipMemcpy(&h_changed, d_changed, 4, hipMemcpyDeviceToHost));
+            KSP_TRY_HIP(hipMemcpy(&h_changed, d_changed, 4, hipMemcpyDeviceToHost));
         }
         if (n_edges && h_changed) { ksp::set_error("ksp_components: did not converge"); rc = KSP_E_HIP; goto done; }
-        CL_HIP(hipMemcpy(h_label, d_parent, (size_t)n_nodes * 4, hipMemcpyDeviceToHost));
+        KSP_TRY_HIP(hipMemcpy(h_label, d_parent, (size_t)n_nodes * 4, hipMemcpyDeviceToHost));
     }
 done:
-    if (d_a) (void)hipFree(d_a);
-    if (d_b) (void)hipFree(d_b);
-    if (d_parent) (void)hipFree(d_parent);
-    if (d_changed) (void)hipFree(d_changed);
     return rc;
 }
 
@@ -203,26 +183,21 @@ void cc_critical(const double cutoff, float* vcrit, int* mode) {
     std::memcpy(vcrit, &hi, 4);
 }
 
-// the ANI table of ksize (ani.h) in device memory of the current device; the caller frees *d_table
-int upload_ani_table(const int ksize, double** d_table) {
+// the ANI table of ksize (ani.h) in device memory of the current device, owned by the arena
+static int upload_ani_table(const int ksize, DeviceArena& A, double** d_table) {
     int rc = KSP_OK;
     *d_table = nullptr;
     if (ksize < 1) { set_error("ANI: k-mer size < 1"); return KSP_E_ARG; }
-    {
-        std::shared_ptr<const std::vector<double>> t;
-        try {
-            t = ani_table(ksize);
-        } catch (const std::exception&) {
-            set_error("ANI: cannot build the table on the host (out of memory?)");
-            return KSP_E_LIMIT;
-        }
-        CL_HIP(hipMalloc((void**)d_table, (size_t)kAniTableSize * sizeof(double)));
-        CL_HIP(hipMemcpy(*d_table, t->data(), (size_t)kAniTableSize * sizeof(double), hipMemcpyHostToDevice));
+    std::shared_ptr<const std::vector<double>> t;
+    try {
+        t = ani_table(ksize);
+    } catch (const std::exception&) {
+        set_error("ANI: cannot build the table on the host (out of memory?)");
+        return KSP_E_LIMIT;
     }
-    return KSP_OK;
+    if ((rc = A.alloc(d_table, (size_t)kAniTableSize))) return rc;
+    KSP_TRY_HIP(hipMemcpy(*d_table, t->data(), (size_t)kAniTableSize * sizeof(double), hipMemcpyHostToDevice));
 done:
-    if (*d_table) (void)hipFree(*d_table);
-    *d_table = nullptr;
     return rc;
 }
 
@@ -230,6 +205,7 @@ done:
 int cc_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, double cutoff,
                        uint32_t* h_label, uint64_t* n_kept, int ksize) {
     int rc = KSP_OK;
+    DeviceArena A;
     u32 *d_parent = nullptr, *d_changed = nullptr;   // d_changed: [0] changed, [1] NaN ANI seen, [2..3] kept edges
     unsigned long long* d_kept = nullptr;
     double* d_table = nullptr;
@@ -240,29 +216,27 @@ int cc_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edg
     if (col != 6) cc_critical(cutoff, &vcrit, &mode);
     if (n_kept) *n_kept = 0;
     if (n_nodes == 0) return KSP_OK;
-    CL_HIP(hipMalloc((void**)&d_parent, (size_t)n_nodes * 4));
-    CL_HIP(hipMalloc((void**)&d_changed, 16));
+    if ((rc = A.alloc(&d_parent, (size_t)n_nodes)) || (rc = A.alloc(&d_changed, 4))) return rc;
     d_kept = reinterpret_cast<unsigned long long*>(d_changed + 2);
     {
         const unsigned gn = (n_nodes + 255) / 256;
         const unsigned ge = (unsigned)std::min<u64>((n_edges + 255) / 256, 1u << 16);
         hipLaunchKernelGGL(k_cc_init, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes);
         if (col == 6 && n_edges) {   // the ANI cut of every edge, once: a bit per edge
-            if ((rc = upload_ani_table(ksize, &d_table))) goto done;
-            CL_HIP(hipMalloc((void**)&d_keep, (n_edges + 63) / 64 * 8));
-            CL_HIP(hipMemsetAsync(d_changed, 0, 16, nullptr));
+            if ((rc = upload_ani_table(ksize, A, &d_table))) goto done;
+            if ((rc = A.alloc(&d_keep, (size_t)((n_edges + 63) / 64)))) goto done;
+            KSP_TRY_HIP(hipMemsetAsync(d_changed, 0, 16, nullptr));
             hipLaunchKernelGGL(k_ani_keep, dim3((unsigned)std::min<u64>((n_edges + 255) / 256, 2048)), dim3(256), 0, nullptr, d_edges, n_edges, d_cnt,
                                d_table, cutoff * 100.0, d_keep, d_changed + 1, d_kept);
-            CL_HIP(hipGetLastError());
+            KSP_TRY_HIP(hipGetLastError());
             u32 head[4] = {0, 0, 0, 0};   // [1] NaN seen, [2..3] kept edges
-            CL_HIP(hipMemcpy(head, d_changed, 16, hipMemcpyDeviceToHost));
+            KSP_TRY_HIP(hipMemcpy(head, d_changed, 16, hipMemcpyDeviceToHost));
             if (head[1]) { set_error("components: an edge has a NaN containment (0 shared k-mers of a source with 0 k-mers): it has no ANI"); rc = KSP_E_ARG; goto done; }
             if (n_kept) { unsigned long long k; std::memcpy(&k, head + 2, 8); *n_kept = k; }
-            (void)hipFree(d_table);
-            d_table = nullptr;
+            (void)A.release(d_table);   // (not held through the rounds)
         }
         for (int round = 0; n_edges && h_changed && round < 10000; ++round) {
-            CL_HIP(hipMemsetAsync(d_changed, 0, 16, nullptr));
+            KSP_TRY_HIP(hipMemsetAsync(d_changed, 0, 16, nullptr));
             if (col == 6)
                 hipLaunchKernelGGL(k_cc_hook_kept, dim3(ge), dim3(256), 0, nullptr, d_edges, n_edges, d_keep, d_parent, d_changed);
             else
@@ -270,17 +244,13 @@ int cc_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edg
                                    round == 0 ? d_kept : nullptr);
             hipLaunchKernelGGL(k_cc_jump, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes, d_changed);
             hipLaunchKernelGGL(k_cc_jump, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes, d_changed);
-            CL_HIP(hipMemcpy(&h_changed, d_changed, 4, hipMemcpyDeviceToHost));
-            if (round == 0 && n_kept && col != 6) { unsigned long long k = 0; CL_HIP(hipMemcpy(&k, d_kept, 8, hipMemcpyDeviceToHost)); *n_kept = k; }
+            KSP_TRY_HIP(hipMemcpy(&h_changed, d_changed, 4, hipMemcpyDeviceToHost));
+            if (round == 0 && n_kept && col != 6) { unsigned long long k = 0; KSP_TRY_HIP(hipMemcpy(&k, d_kept, 8, hipMemcpyDeviceToHost)); *n_kept = k; }
         }
         if (n_edges && h_changed) { set_error("components: did not converge"); rc = KSP_E_HIP; goto done; }
-        CL_HIP(hipMemcpy(h_label, d_parent, (size_t)n_nodes * 4, hipMemcpyDeviceToHost));
+        KSP_TRY_HIP(hipMemcpy(h_label, d_parent, (size_t)n_nodes * 4, hipMemcpyDeviceToHost));
     }
 done:
-    if (d_parent) (void)hipFree(d_parent);
-    if (d_changed) (void)hipFree(d_changed);
-    if (d_table) (void)hipFree(d_table);
-    if (d_keep) (void)hipFree(d_keep);
     return rc;
 }
 
@@ -297,22 +267,18 @@ void write_cluster_file(const std::string& prefix, const double threshold, const
         for (u64 v = 0; v < N; ++v) order[cur[label[v]]++] = (u32)v;
     }
     const std::string out = prefix + "_kSpider_clusters_" + py_float_repr(threshold) + "%.tsv";
-    const std::string tmp = out + ".partial";
-    {
-        std::ofstream f(tmp);
-        if (!f) throw std::runtime_error("cannot write " + tmp);
-        for (u64 r = 0; r < N; ++r) {
-            if (count[r + 1] == count[r]) continue;
-            for (u32 i = count[r]; i < count[r + 1]; ++i) {
-                if (i != count[r]) f << ',';
-                f << name_of[order[i]];
-            }
-            f << '\n';
+    std::ofstream f;
+    PartialFiles files;
+    files.open(out, f);
+    for (u64 r = 0; r < N; ++r) {
+        if (count[r + 1] == count[r]) continue;
+        for (u32 i = count[r]; i < count[r + 1]; ++i) {
+            if (i != count[r]) f << ',';
+            f << name_of[order[i]];
         }
-        f.flush();
-        if (!f) { std::remove(tmp.c_str()); throw std::runtime_error("write error on " + tmp); }
+        f << '\n';
     }
-    if (std::rename(tmp.c_str(), out.c_str()) != 0) { std::remove(tmp.c_str()); throw std::runtime_error("cannot rename " + tmp); }
+    files.commit();
 }
 
 // PREFIX.namesMap -> name of node index v = id - 1 (ks_clustering.py:56-61); ids must be 1..N
@@ -349,9 +315,7 @@ extern "C" int ksp_components_edges(int device, uint32_t n_nodes, const ksp_edge
                                     int dist_col, double cutoff, uint32_t* h_label) {
     if ((n_edges && (!d_edges || !d_kmer_counts)) || (n_nodes && !h_label)) { ksp::set_error("ksp_components_edges: NULL argument"); return KSP_E_ARG; }
     if (dist_col < 3 || dist_col > 5) { ksp::set_error("ksp_components_edges: dist_col is 3 (min), 4 (avg) or 5 (max containment)"); return KSP_E_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { ksp::set_error("ksp_components_edges: no such device"); return KSP_E_HIP; }
-    if (hipSetDevice(device) != hipSuccess) { ksp::set_error("ksp_components_edges: hipSetDevice"); return KSP_E_HIP; }
+    if (const int rc = ksp::set_device("ksp_components_edges", device)) return rc;
     return ksp::cc_edges_on_device(n_nodes, d_edges, n_edges, d_kmer_counts, dist_col, cutoff, h_label, nullptr);
 }
 
@@ -359,36 +323,31 @@ extern "C" int ksp_components_edges_ani(int device, uint32_t n_nodes, const ksp_
                                         int ksize, double cutoff, uint32_t* h_label) {
     if ((n_edges && (!d_edges || !d_kmer_counts)) || (n_nodes && !h_label)) { ksp::set_error("ksp_components_edges_ani: NULL argument"); return KSP_E_ARG; }
     if (ksize < 1) { ksp::set_error("ksp_components_edges_ani: ksize < 1"); return KSP_E_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { ksp::set_error("ksp_components_edges_ani: no such device"); return KSP_E_HIP; }
-    if (hipSetDevice(device) != hipSuccess) { ksp::set_error("ksp_components_edges_ani: hipSetDevice"); return KSP_E_HIP; }
+    if (const int rc = ksp::set_device("ksp_components_edges_ani", device)) return rc;
     return ksp::cc_edges_on_device(n_nodes, d_edges, n_edges, d_kmer_counts, 6, cutoff, h_label, nullptr, ksize);
 }
 
 extern "C" int ksp_edges_ani(int device, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int ksize, double* d_ani) {
     if (n_edges && (!d_edges || !d_kmer_counts || !d_ani)) { ksp::set_error("ksp_edges_ani: NULL argument"); return KSP_E_ARG; }
     if (ksize < 1) { ksp::set_error("ksp_edges_ani: ksize < 1"); return KSP_E_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { ksp::set_error("ksp_edges_ani: no such device"); return KSP_E_HIP; }
-    if (hipSetDevice(device) != hipSuccess) { ksp::set_error("ksp_edges_ani: hipSetDevice"); return KSP_E_HIP; }
+    if (const int rc = ksp::set_device("ksp_edges_ani", device)) return rc;
     if (n_edges == 0) return KSP_OK;
     int rc = KSP_OK;
+    ksp::DeviceArena A;
     double* d_table = nullptr;
     u32* d_nan = nullptr;
     u32 h_nan = 0;
-    if ((rc = ksp::upload_ani_table(ksize, &d_table))) return rc;
-    CL_HIP(hipMalloc((void**)&d_nan, 4));
-    CL_HIP(hipMemsetAsync(d_nan, 0, 4, nullptr));
+    if ((rc = ksp::upload_ani_table(ksize, A, &d_table))) return rc;
+    if ((rc = A.alloc(&d_nan, 1))) return rc;
+    KSP_TRY_HIP(hipMemsetAsync(d_nan, 0, 4, nullptr));
     {   // a gather per edge: grid-stride over at most 8 workgroups per CU
         const unsigned g = (unsigned)std::min<u64>((n_edges + 255) / 256, 2048);
         hipLaunchKernelGGL(k_edges_ani, dim3(g), dim3(256), 0, nullptr, d_edges, n_edges, d_kmer_counts, d_table, d_ani, d_nan);
-        CL_HIP(hipGetLastError());
-        CL_HIP(hipMemcpy(&h_nan, d_nan, 4, hipMemcpyDeviceToHost));
+        KSP_TRY_HIP(hipGetLastError());
+        KSP_TRY_HIP(hipMemcpy(&h_nan, d_nan, 4, hipMemcpyDeviceToHost));
         if (h_nan) { ksp::set_error("ksp_edges_ani: an edge has a NaN containment (0 shared k-mers of a source with 0 k-mers): it has no ANI"); rc = KSP_E_ARG; }
     }
 done:
-    if (d_table) (void)hipFree(d_table);
-    if (d_nan) (void)hipFree(d_nan);
     return rc;
 }
 
@@ -409,9 +368,7 @@ extern "C" int kspider_cluster(const char* index_prefix, const char* dist_type, 
         });
         const u64 N = name_of.size();
         std::vector<u32> label((size_t)N);
-        int device = 0;
-        if (const char* dv = std::getenv("KSPIDER_DEVICE")) device = std::atoi(dv);
-        const int rc = ksp_components(device, (u32)N, ea.data(), eb.data(), ea.size(), label.data());
+        const int rc = ksp_components(ksp::device_from_env(), (u32)N, ea.data(), eb.data(), ea.size(), label.data());
         if (rc) return rc;
         ksp::write_cluster_file(prefix, threshold, label, name_of);
         return KSP_OK;
@@ -439,7 +396,7 @@ void write_sweep_outputs(const std::string& prefix, const std::string& dist, con
                pick.end());
     auto exists = [](const std::string& path) { return (bool)std::ifstream(path); };
     std::vector<std::string> created;
-    const std::string summary = prefix + "_kSpider_cluster_sweep_" + dist + ".tsv", tmp = summary + ".partial";
+    const std::string summary = prefix + "_kSpider_cluster_sweep_" + dist + ".tsv";
     try {
         std::string rows = "cutoff_percent\tedges\tclusters\tsingletons\tlargest\n";
         for (const u32 i : pick) {
@@ -458,16 +415,8 @@ void write_sweep_outputs(const std::string& prefix, const std::string& dist, con
             rows += text + "\t" + std::to_string(kept[i]) + "\t" + std::to_string(clusters) + "\t" + std::to_string(singletons) + "\t" + std::to_string(largest) + "\n";
         }
         if (!exists(summary)) created.push_back(summary);
-        {
-            std::ofstream f(tmp);
-            if (!f) throw std::runtime_error("cannot write " + tmp);
-            f << rows;
-            f.flush();
-            if (!f) throw std::runtime_error("write error on " + tmp);
-        }
-        if (std::rename(tmp.c_str(), summary.c_str()) != 0) throw std::runtime_error("cannot rename " + tmp);
+        write_file_atomically(summary, rows);
     } catch (...) {
-        std::remove(tmp.c_str());
         for (const std::string& path : created) std::remove(path.c_str());
         throw;
     }
@@ -511,9 +460,7 @@ extern "C" int kspider_cluster_sweep(const char* index_prefix, const char* dist_
         });
         const u64 N = name_of.size();
         std::vector<u32> by_rank((size_t)K * N), labels((size_t)K * N);
-        int device = 0;
-        if (const char* dv = std::getenv("KSPIDER_DEVICE")) device = std::atoi(dv);
-        const int rc = ksp_components_sweep(device, (u32)N, ea.data(), eb.data(), level.data(), ea.size(), K, by_rank.data());
+        const int rc = ksp_components_sweep(ksp::device_from_env(), (u32)N, ea.data(), eb.data(), level.data(), ea.size(), K, by_rank.data());
         if (rc) return rc;
         std::vector<u64> kept(K);
         u64 above = 0;

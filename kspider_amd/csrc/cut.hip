@@ -23,6 +23,7 @@
 #include <rocprim/device/device_select.hpp>
 
 #include "../../include/kspider_amd.h"
+#include "device_call.h"
 #include "edge_cut.hip.h"
 #include "engine_internal.h"
 
@@ -134,29 +135,12 @@ __global__ __launch_bounds__(kCutThreads) void k_cut_scatter(const ksp_edge* __r
     }
 }
 
-#define CUT_HIP(call)                                                                    \
-    do {                                                                                 \
-        hipError_t err__ = (call);                                                       \
-        if (err__ != hipSuccess) {                                                       \
-            ksp::set_error(std::string(#call) + ": " + hipGetErrorString(err__));        \
-            rc = KSP_E_HIP;                                                              \
-            goto done;                                                                   \
-        }                                                                                \
-    } while (0)
-
-// workgroups of both passes: one per chunk up to 8 per CU (32 waves: a full CU), the rest by the chunk loop
+// workgroups of both passes: one per chunk up to 8 per CU (32 waves: a full CU), the rest by the chunk loop.  (No list of 0
+// chunks gets here — every caller has returned or refused n_edges == 0 before — so the at-least-1 of grid_of changes no launch.)
 int cut_grid(const u64 n_chunks, unsigned* grid) {
-    int device = 0, cus = 0;
-    if (hipGetDevice(&device) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
-        ksp::set_error("cut: cannot read the device's CU count");
-        return KSP_E_HIP;
-    }
-    u64 cap = 8ull * (u64)std::max(cus, 1);
-    if (const char* mw = std::getenv("KSP_CUT_MAX_WORKGROUPS")) {   // tests / diagnostics: a small grid, so that every workgroup loops
-        const long long v = std::atoll(mw);
-        if (v >= 1) cap = (u64)v;
-    }
-    *grid = (unsigned)std::min<u64>(std::min<u64>(n_chunks, cap), 0x7FFFFFFFull);
+    ksp::WorkgroupCap g;
+    if (const int rc = ksp::workgroup_cap("KSP_CUT_MAX_WORKGROUPS", "cut", g)) return rc;
+    *grid = g.grid_of(n_chunks);
     return KSP_OK;
 }
 
@@ -173,13 +157,6 @@ struct CutKeptFn {   // the same predicate as a functor: the library yardstick o
     int mode;
     __device__ bool operator()(const ksp_edge& x) const { return cc_edge_kept(x, cnt, col, vcrit, mode); }
 };
-
-int set_device(const char* who, const int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { ksp::set_error(std::string(who) + ": no such device"); return KSP_E_HIP; }
-    if (hipSetDevice(device) != hipSuccess) { ksp::set_error(std::string(who) + ": hipSetDevice"); return KSP_E_HIP; }
-    return KSP_OK;
-}
 
 int check_cut_args(const char* who, const ksp_edge* d_edges, const u64 n_edges, const u32* d_kmer_counts, const int dist_col, const double cutoff,
                    const ksp_edge* d_out) {
@@ -209,6 +186,7 @@ void CutPass::release() {
 int cut_count_on_device(const ksp_edge* d_edges, const uint64_t n_edges, const uint32_t* d_cnt, const int col, const double cutoff, CutPass& pass,
                         uint64_t* n_kept) {
     int rc = KSP_OK;
+    DeviceArena A;   // (the pass outlives this call: its two arrays are its own)
     u64* d_count = nullptr;
     void* d_tmp = nullptr;
     size_t tb = 0;
@@ -220,26 +198,24 @@ int cut_count_on_device(const ksp_edge* d_edges, const uint64_t n_edges, const u
     cc_critical(cutoff, &pass.vcrit, &pass.mode);
     pass.n_chunks = (n_edges + kCutChunkEdges - 1) / kCutChunkEdges;
     if ((rc = cut_grid(pass.n_chunks, &grid))) return rc;
-    CUT_HIP(hipMalloc((void**)&d_count, (size_t)(pass.n_chunks + 1) * 8));
-    CUT_HIP(hipMalloc((void**)&pass.d_off, (size_t)(pass.n_chunks + 1) * 8));
-    CUT_HIP(hipMemsetAsync(d_count + pass.n_chunks, 0, 8, nullptr));   // (the scan's last output is then the total)
+    if ((rc = A.alloc(&d_count, (size_t)(pass.n_chunks + 1)))) goto done;
+    KSP_TRY_HIP(hipMalloc((void**)&pass.d_off, (size_t)(pass.n_chunks + 1) * 8));
+    KSP_TRY_HIP(hipMemsetAsync(d_count + pass.n_chunks, 0, 8, nullptr));   // (the scan's last output is then the total)
     if (cut_keep_ballots()) {
-        CUT_HIP(hipMalloc((void**)&pass.d_ballots, (size_t)((n_edges + 63) / 64) * 8));
+        KSP_TRY_HIP(hipMalloc((void**)&pass.d_ballots, (size_t)((n_edges + 63) / 64) * 8));
         hipLaunchKernelGGL(k_cut_count<true>, dim3(grid), dim3(kCutThreads), 0, nullptr, d_edges, n_edges, pass.n_chunks, d_cnt, col, pass.vcrit, pass.mode,
                            d_count, pass.d_ballots);
     } else {
         hipLaunchKernelGGL(k_cut_count<false>, dim3(grid), dim3(kCutThreads), 0, nullptr, d_edges, n_edges, pass.n_chunks, d_cnt, col, pass.vcrit, pass.mode,
                            d_count, (unsigned long long*)nullptr);
     }
-    CUT_HIP(hipGetLastError());
-    CUT_HIP(rocprim::exclusive_scan(nullptr, tb, d_count, pass.d_off, (u64)0, (size_t)(pass.n_chunks + 1), rocprim::plus<u64>(), (hipStream_t) nullptr));
-    CUT_HIP(hipMalloc(&d_tmp, tb ? tb : 8));
-    CUT_HIP(rocprim::exclusive_scan(d_tmp, tb, d_count, pass.d_off, (u64)0, (size_t)(pass.n_chunks + 1), rocprim::plus<u64>(), (hipStream_t) nullptr));
-    CUT_HIP(hipMemcpy(&total, pass.d_off + pass.n_chunks, 8, hipMemcpyDeviceToHost));
+    KSP_TRY_HIP(hipGetLastError());
+    KSP_TRY_HIP(rocprim::exclusive_scan(nullptr, tb, d_count, pass.d_off, (u64)0, (size_t)(pass.n_chunks + 1), rocprim::plus<u64>(), (hipStream_t) nullptr));
+    if ((rc = A.alloc_bytes(&d_tmp, tb ? tb : 8))) goto done;
+    KSP_TRY_HIP(rocprim::exclusive_scan(d_tmp, tb, d_count, pass.d_off, (u64)0, (size_t)(pass.n_chunks + 1), rocprim::plus<u64>(), (hipStream_t) nullptr));
+    KSP_TRY_HIP(hipMemcpy(&total, pass.d_off + pass.n_chunks, 8, hipMemcpyDeviceToHost));
     *n_kept = total;
 done:
-    if (d_count) (void)hipFree(d_count);
-    if (d_tmp) (void)hipFree(d_tmp);
     if (rc) pass.release();
     return rc;
 }
@@ -256,8 +232,8 @@ int cut_scatter_on_device(const ksp_edge* d_edges, const uint64_t n_edges, const
     else
         hipLaunchKernelGGL(k_cut_scatter<false>, dim3(grid), dim3(kCutThreads), 0, nullptr, d_edges, n_edges, pass.n_chunks, d_cnt, col, pass.vcrit, pass.mode,
                            pass.d_off, (const unsigned long long*)nullptr, d_out);
-    CUT_HIP(hipGetLastError());
-    CUT_HIP(hipDeviceSynchronize());
+    KSP_TRY_HIP(hipGetLastError());
+    KSP_TRY_HIP(hipDeviceSynchronize());
 done:
     return rc;
 }
@@ -267,7 +243,7 @@ extern "C" int ksp_edges_cut(int device, const ksp_edge* d_edges, uint64_t n_edg
                              ksp_edge* d_out, uint64_t* n_kept) {
     if (!n_kept) { ksp::set_error("ksp_edges_cut: NULL argument"); return KSP_E_ARG; }
     if (const int rc = check_cut_args("ksp_edges_cut", d_edges, n_edges, d_kmer_counts, dist_col, cutoff, d_out)) return rc;
-    if (const int rc = set_device("ksp_edges_cut", device)) return rc;
+    if (const int rc = ksp::set_device("ksp_edges_cut", device)) return rc;
     *n_kept = 0;
     if (n_edges == 0) return KSP_OK;   // no kernel runs
     ksp::CutPass pass;
@@ -284,8 +260,9 @@ extern "C" int ksp_debug_cut_times(int device, const ksp_edge* d_edges, uint64_t
                                    ksp_edge* d_out, int which, int reps, float* ms, uint64_t* n_kept) {
     if (!n_kept || !ms || reps < 1 || which < 0 || which > 2 || n_edges == 0) { ksp::set_error("ksp_debug_cut_times: bad argument"); return KSP_E_ARG; }
     if (const int rc = check_cut_args("ksp_debug_cut_times", d_edges, n_edges, d_kmer_counts, dist_col, cutoff, d_out)) return rc;
-    if (const int rc = set_device("ksp_debug_cut_times", device)) return rc;
+    if (const int rc = ksp::set_device("ksp_debug_cut_times", device)) return rc;
     int rc = KSP_OK;
+    ksp::DeviceArena A;
     float vcrit = 0;
     int mode = 0;
     ksp::cc_critical(cutoff, &vcrit, &mode);
@@ -298,50 +275,44 @@ extern "C" int ksp_debug_cut_times(int device, const ksp_edge* d_edges, uint64_t
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     const CutKeptFn fn{d_kmer_counts, dist_col, vcrit, mode};
     if ((rc = cut_grid(n_chunks, &grid))) return rc;
-    CUT_HIP(hipEventCreate(&ev0));
-    CUT_HIP(hipEventCreate(&ev1));
-    CUT_HIP(hipMalloc((void**)&d_count, (size_t)(n_chunks + 1) * 8));
-    CUT_HIP(hipMalloc((void**)&d_off, (size_t)(n_chunks + 1) * 8));
-    CUT_HIP(hipMalloc((void**)&d_ballots, (size_t)((n_edges + 63) / 64) * 8));
-    CUT_HIP(hipMalloc((void**)&d_nsel, 8));
-    CUT_HIP(hipMemset(d_count + n_chunks, 0, 8));
-    CUT_HIP(rocprim::exclusive_scan(nullptr, tb_scan, d_count, d_off, (u64)0, (size_t)(n_chunks + 1), rocprim::plus<u64>(), (hipStream_t) nullptr));
-    CUT_HIP(rocprim::select(nullptr, tb_sel, d_edges, d_out, d_nsel, (size_t)n_edges, fn, (hipStream_t) nullptr));
-    CUT_HIP(hipMalloc(&d_tmp, std::max<size_t>(std::max(tb_scan, tb_sel), 8)));
+    KSP_TRY_HIP(hipEventCreate(&ev0));
+    KSP_TRY_HIP(hipEventCreate(&ev1));
+    if ((rc = A.alloc(&d_count, (size_t)(n_chunks + 1))) || (rc = A.alloc(&d_off, (size_t)(n_chunks + 1))) ||
+        (rc = A.alloc(&d_ballots, (size_t)((n_edges + 63) / 64))) || (rc = A.alloc(&d_nsel, 1)))
+        goto done;
+    KSP_TRY_HIP(hipMemset(d_count + n_chunks, 0, 8));
+    KSP_TRY_HIP(rocprim::exclusive_scan(nullptr, tb_scan, d_count, d_off, (u64)0, (size_t)(n_chunks + 1), rocprim::plus<u64>(), (hipStream_t) nullptr));
+    KSP_TRY_HIP(rocprim::select(nullptr, tb_sel, d_edges, d_out, d_nsel, (size_t)n_edges, fn, (hipStream_t) nullptr));
+    if ((rc = A.alloc_bytes(&d_tmp, std::max<size_t>(std::max(tb_scan, tb_sel), 8)))) goto done;
     for (int r = 0; r < reps; ++r) {
         unsigned long long total = 0;
-        CUT_HIP(hipEventRecord(ev0, nullptr));
+        KSP_TRY_HIP(hipEventRecord(ev0, nullptr));
         if (which == 2) {
-            CUT_HIP(rocprim::select(d_tmp, tb_sel, d_edges, d_out, d_nsel, (size_t)n_edges, fn, (hipStream_t) nullptr));
-            CUT_HIP(hipMemcpy(&total, d_nsel, 8, hipMemcpyDeviceToHost));
+            KSP_TRY_HIP(rocprim::select(d_tmp, tb_sel, d_edges, d_out, d_nsel, (size_t)n_edges, fn, (hipStream_t) nullptr));
+            KSP_TRY_HIP(hipMemcpy(&total, d_nsel, 8, hipMemcpyDeviceToHost));
         } else {
             if (which == 1)
                 hipLaunchKernelGGL(k_cut_count<true>, dim3(grid), dim3(kCutThreads), 0, nullptr, d_edges, n_edges, n_chunks, d_kmer_counts, dist_col, vcrit, mode, d_count, d_ballots);
             else
                 hipLaunchKernelGGL(k_cut_count<false>, dim3(grid), dim3(kCutThreads), 0, nullptr, d_edges, n_edges, n_chunks, d_kmer_counts, dist_col, vcrit, mode, d_count,
                                    (unsigned long long*)nullptr);
-            CUT_HIP(rocprim::exclusive_scan(d_tmp, tb_scan, d_count, d_off, (u64)0, (size_t)(n_chunks + 1), rocprim::plus<u64>(), (hipStream_t) nullptr));
-            CUT_HIP(hipMemcpy(&total, d_off + n_chunks, 8, hipMemcpyDeviceToHost));
+            KSP_TRY_HIP(rocprim::exclusive_scan(d_tmp, tb_scan, d_count, d_off, (u64)0, (size_t)(n_chunks + 1), rocprim::plus<u64>(), (hipStream_t) nullptr));
+            KSP_TRY_HIP(hipMemcpy(&total, d_off + n_chunks, 8, hipMemcpyDeviceToHost));
             if (which == 1)
                 hipLaunchKernelGGL(k_cut_scatter<true>, dim3(grid), dim3(kCutThreads), 0, nullptr, d_edges, n_edges, n_chunks, d_kmer_counts, dist_col, vcrit, mode, d_off,
                                    d_ballots, d_out);
             else
                 hipLaunchKernelGGL(k_cut_scatter<false>, dim3(grid), dim3(kCutThreads), 0, nullptr, d_edges, n_edges, n_chunks, d_kmer_counts, dist_col, vcrit, mode, d_off,
                                    (const unsigned long long*)nullptr, d_out);
-            CUT_HIP(hipGetLastError());
+            KSP_TRY_HIP(hipGetLastError());
         }
-        CUT_HIP(hipEventRecord(ev1, nullptr));
-        CUT_HIP(hipEventSynchronize(ev1));
-        CUT_HIP(hipEventElapsedTime(&ms[r], ev0, ev1));
+        KSP_TRY_HIP(hipEventRecord(ev1, nullptr));
+        KSP_TRY_HIP(hipEventSynchronize(ev1));
+        KSP_TRY_HIP(hipEventElapsedTime(&ms[r], ev0, ev1));
         *n_kept = total;
     }
 done:
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
-    if (d_count) (void)hipFree(d_count);
-    if (d_off) (void)hipFree(d_off);
-    if (d_ballots) (void)hipFree(d_ballots);
-    if (d_nsel) (void)hipFree(d_nsel);
-    if (d_tmp) (void)hipFree(d_tmp);
     return rc;
 }

@@ -46,8 +46,10 @@
 
 #include "../../include/kspider_amd.h"
 #include "cluster_inputs.h"
+#include "device_call.h"
 #include "edge_cut.hip.h"
 #include "engine_internal.h"
+#include "partial_file.h"
 
 typedef uint32_t u32;
 typedef uint64_t u64;
@@ -358,41 +360,7 @@ __global__ void k_derep_finish(const u32* __restrict__ state, const unsigned lon
     via[v] = e;
 }
 
-#define DR_HIP(call)                                                                     \
-    do {                                                                                 \
-        hipError_t err__ = (call);                                                       \
-        if (err__ != hipSuccess) {                                                       \
-            ksp::set_error(std::string(#call) + ": " + hipGetErrorString(err__));        \
-            rc = KSP_E_HIP;                                                              \
-            goto done;                                                                   \
-        }                                                                                \
-    } while (0)
-
-// workgroups of the edge passes: one per chunk up to 8 per CU, the rest by the chunk loop; cap_env: $KSP_DEREP_MAX_WORKGROUPS
-struct DerepGrid {
-    u64 cap = 1;
-    unsigned of(const u64 n_chunks) const { return (unsigned)std::max<u64>(1, std::min<u64>(std::min<u64>(n_chunks, cap), 0x7FFFFFFFull)); }
-};
-int derep_grid(DerepGrid& g) {
-    const char* mw = std::getenv("KSP_DEREP_MAX_WORKGROUPS");
-    const long long cap_env = mw ? std::atoll(mw) : 0;
-    int device = 0, cus = 0;
-    if (hipGetDevice(&device) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
-        ksp::set_error("dereplicate: cannot read the device's CU count");
-        return KSP_E_HIP;
-    }
-    g.cap = cap_env >= 1 ? (u64)cap_env : 8ull * (u64)std::max(cus, 1);
-    return KSP_OK;
-}
-
-int derep_set_device(const char* who, const int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { ksp::set_error(std::string(who) + ": no such device"); return KSP_E_HIP; }
-    if (hipSetDevice(device) != hipSuccess) { ksp::set_error(std::string(who) + ": hipSetDevice"); return KSP_E_HIP; }
-    return KSP_OK;
-}
-
-// what one call holds on the device
+// what one call holds on the device (memory of the call's DeviceArena)
 struct DerepBufs {
     // per node (52 bytes)
     u32 *degree = nullptr, *rank = nullptr, *state = nullptr, *blocked = nullptr, *rep = nullptr, *via = nullptr, *waiting = nullptr;
@@ -405,31 +373,15 @@ struct DerepBufs {
     unsigned long long* counts = nullptr;   // [0] live pairs of a pass, [1] (as u32) undecided nodes / waiting nodes, [2] (as 2 x u32) the tail's out[]
     void* tmp = nullptr;                    // the library's scratch: the larger of the sort's and the scan's
     size_t tmp_bytes = 0;
-    ~DerepBufs() {
-        for (void* p : {(void*)degree, (void*)rank, (void*)state, (void*)blocked, (void*)rep, (void*)via, (void*)waiting, (void*)keys, (void*)sorted, (void*)best,
-                        (void*)chunk_count, (void*)chunk_off, (void*)lo, (void*)hi, (void*)index, (void*)live_lo[0], (void*)live_lo[1], (void*)live_hi[0],
-                        (void*)live_hi[1], (void*)counts, tmp})
-            if (p) (void)hipFree(p);
-    }
 };
-
-int derep_fits(const u64 bytes, const char* what) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { ksp::set_error("dereplicate: hipMemGetInfo"); return KSP_E_HIP; }
-    if (bytes > (u64)free_b) {
-        ksp::set_error("dereplicate: needs " + std::to_string(bytes) + " bytes of device memory (" + what + "), " + std::to_string(free_b) + " are free");
-        return KSP_E_LIMIT;
-    }
-    return KSP_OK;
-}
 
 // exclusive scan of B.chunk_count[0 .. n_chunks] (the entry behind the last chunk is 0) into B.chunk_off; *total = the sum
 int derep_scan(DerepBufs& B, const u64 n_chunks, u64* total) {
     int rc = KSP_OK;
     size_t tb = B.tmp_bytes;
-    DR_HIP(hipMemsetAsync(B.chunk_count + n_chunks, 0, 8, nullptr));
-    DR_HIP(rocprim::exclusive_scan(B.tmp, tb, B.chunk_count, B.chunk_off, (u64)0, (size_t)(n_chunks + 1), rocprim::plus<u64>(), (hipStream_t) nullptr));
-    DR_HIP(hipMemcpy(total, B.chunk_off + n_chunks, 8, hipMemcpyDeviceToHost));
+    KSP_TRY_HIP(hipMemsetAsync(B.chunk_count + n_chunks, 0, 8, nullptr));
+    KSP_TRY_HIP(rocprim::exclusive_scan(B.tmp, tb, B.chunk_count, B.chunk_off, (u64)0, (size_t)(n_chunks + 1), rocprim::plus<u64>(), (hipStream_t) nullptr));
+    KSP_TRY_HIP(hipMemcpy(total, B.chunk_off + n_chunks, 8, hipMemcpyDeviceToHost));
 done:
     return rc;
 }
@@ -440,7 +392,8 @@ int derep_on_device(const u32 N, const ksp_edge* d_edges, const u32* d_a, const 
                     u32* h_rep, u32* h_via, u32* h_rank, u32* h_degree, u32* n_reps, ksp::DerepTrace& T) {
     int rc = KSP_OK;
     DerepBufs B;
-    DerepGrid G;
+    ksp::DeviceArena A;
+    ksp::WorkgroupCap G;   // of the edge passes: one workgroup per chunk up to 8 per CU, the rest by the chunk loop
     const u64 n_chunks = (n + kDerepChunk - 1) / kDerepChunk;
     const unsigned gn = (unsigned)(((u64)N + 255) / 256);
     const char* tail_env = std::getenv("KSP_DEREP_TAIL");   // "0": host-driven rounds to the end (tests)
@@ -448,50 +401,44 @@ int derep_on_device(const u32 N, const ksp_edge* d_edges, const u32* d_a, const 
     size_t tb_sort = 0, tb_scan = 0;
     u64 n_pairs = 0;
     std::vector<u32> rep, via;
-    if ((rc = derep_grid(G))) return rc;
+    if ((rc = ksp::workgroup_cap("KSP_DEREP_MAX_WORKGROUPS", "dereplicate", G))) return rc;
     // ---- the arrays per node and per chunk, and the library's scratch: sized and checked first
-    DR_HIP(rocprim::radix_sort_keys(nullptr, tb_sort, (u64*)nullptr, (u64*)nullptr, (size_t)N, 0, 64, (hipStream_t) nullptr));
-    DR_HIP(rocprim::exclusive_scan(nullptr, tb_scan, (u64*)nullptr, (u64*)nullptr, (u64)0, (size_t)(n_chunks + 1), rocprim::plus<u64>(), (hipStream_t) nullptr));
+    KSP_TRY_HIP(rocprim::radix_sort_keys(nullptr, tb_sort, (u64*)nullptr, (u64*)nullptr, (size_t)N, 0, 64, (hipStream_t) nullptr));
+    KSP_TRY_HIP(rocprim::exclusive_scan(nullptr, tb_scan, (u64*)nullptr, (u64*)nullptr, (u64)0, (size_t)(n_chunks + 1), rocprim::plus<u64>(), (hipStream_t) nullptr));
     B.tmp_bytes = std::max<size_t>(std::max(tb_sort, tb_scan), 8);
-    if ((rc = derep_fits(52ull * N + 16ull * (n_chunks + 1) + B.tmp_bytes + 32, "52 per node, 16 per 2 048 records, the sort's scratch"))) return rc;
-    for (u32** p : {&B.degree, &B.rank, &B.state, &B.blocked, &B.rep, &B.via, &B.waiting}) DR_HIP(hipMalloc((void**)p, (size_t)N * 4));
-    DR_HIP(hipMalloc((void**)&B.keys, (size_t)N * 8));
-    DR_HIP(hipMalloc((void**)&B.sorted, (size_t)N * 8));
-    DR_HIP(hipMalloc((void**)&B.best, (size_t)N * 8));
-    DR_HIP(hipMalloc((void**)&B.chunk_count, (size_t)(n_chunks + 1) * 8));
-    DR_HIP(hipMalloc((void**)&B.chunk_off, (size_t)(n_chunks + 1) * 8));
-    DR_HIP(hipMalloc((void**)&B.counts, 32));
-    DR_HIP(hipMalloc(&B.tmp, B.tmp_bytes));
+    if ((rc = ksp::device_fits("dereplicate", 52ull * N + 16ull * (n_chunks + 1) + B.tmp_bytes + 32, "52 per node, 16 per 2 048 records, the sort's scratch"))) return rc;
+    for (u32** p : {&B.degree, &B.rank, &B.state, &B.blocked, &B.rep, &B.via, &B.waiting})
+        if ((rc = A.alloc(p, (size_t)N))) return rc;
+    if ((rc = A.alloc(&B.keys, (size_t)N)) || (rc = A.alloc(&B.sorted, (size_t)N)) || (rc = A.alloc(&B.best, (size_t)N))) return rc;
+    if ((rc = A.alloc(&B.chunk_count, (size_t)(n_chunks + 1))) || (rc = A.alloc(&B.chunk_off, (size_t)(n_chunks + 1)))) return rc;
+    if ((rc = A.alloc(&B.counts, 4)) || (rc = A.alloc_bytes(&B.tmp, B.tmp_bytes))) return rc;
     // ---- degrees and the rank of every node
     if ((rc = ksp::degree_keys_on_device(N, d_edges, d_a, d_b, n, d_cnt, col, vcrit, B.degree, B.keys))) return rc;
     {
         size_t tb = B.tmp_bytes;
-        DR_HIP(rocprim::radix_sort_keys(B.tmp, tb, B.keys, B.sorted, (size_t)N, 0, 64, (hipStream_t) nullptr));
+        KSP_TRY_HIP(rocprim::radix_sort_keys(B.tmp, tb, B.keys, B.sorted, (size_t)N, 0, 64, (hipStream_t) nullptr));
     }
     hipLaunchKernelGGL(k_derep_rank, dim3(gn), dim3(256), 0, nullptr, (const u64*)B.sorted, N, B.rank);
     hipLaunchKernelGGL(k_derep_init, dim3(gn), dim3(256), 0, nullptr, B.state, B.blocked, B.best, N);
-    DR_HIP(hipGetLastError());
+    KSP_TRY_HIP(hipGetLastError());
     // ---- the oriented kept pairs
-    if (d_edges) hipLaunchKernelGGL(k_derep_count<true>, dim3(G.of(n_chunks)), dim3(kDerepThreads), 0, nullptr, d_edges, d_a, d_b, n, n_chunks, N, d_cnt, col, vcrit, B.chunk_count);
-    else hipLaunchKernelGGL(k_derep_count<false>, dim3(G.of(n_chunks)), dim3(kDerepThreads), 0, nullptr, d_edges, d_a, d_b, n, n_chunks, N, d_cnt, col, vcrit, B.chunk_count);
-    DR_HIP(hipGetLastError());
+    if (d_edges) hipLaunchKernelGGL(k_derep_count<true>, dim3(G.grid_of(n_chunks)), dim3(kDerepThreads), 0, nullptr, d_edges, d_a, d_b, n, n_chunks, N, d_cnt, col, vcrit, B.chunk_count);
+    else hipLaunchKernelGGL(k_derep_count<false>, dim3(G.grid_of(n_chunks)), dim3(kDerepThreads), 0, nullptr, d_edges, d_a, d_b, n, n_chunks, N, d_cnt, col, vcrit, B.chunk_count);
+    KSP_TRY_HIP(hipGetLastError());
     if ((rc = derep_scan(B, n_chunks, &n_pairs))) return rc;
     if (n_pairs > n) { ksp::set_error("dereplicate: more kept pairs than records"); return KSP_E_HIP; }
     T.kept = n_pairs;
     if (n_pairs) {
         const u64 half = n_pairs / 2;
-        if ((rc = derep_fits(12ull * n_pairs + 16ull * half, "12 per kept pair, 8 more for the live lists"))) return rc;
-        DR_HIP(hipMalloc((void**)&B.lo, (size_t)n_pairs * 4));
-        DR_HIP(hipMalloc((void**)&B.hi, (size_t)n_pairs * 4));
-        DR_HIP(hipMalloc((void**)&B.index, (size_t)n_pairs * 4));
+        if ((rc = ksp::device_fits("dereplicate", 12ull * n_pairs + 16ull * half, "12 per kept pair, 8 more for the live lists"))) return rc;
+        for (u32** p : {&B.lo, &B.hi, &B.index})
+            if ((rc = A.alloc(p, (size_t)n_pairs))) return rc;
         if (half)
-            for (int i = 0; i < 2; ++i) {
-                DR_HIP(hipMalloc((void**)&B.live_lo[i], (size_t)half * 4));
-                DR_HIP(hipMalloc((void**)&B.live_hi[i], (size_t)half * 4));
-            }
-        if (d_edges) hipLaunchKernelGGL(k_derep_scatter<true>, dim3(G.of(n_chunks)), dim3(kDerepThreads), 0, nullptr, d_edges, d_a, d_b, n, n_chunks, N, d_cnt, col, vcrit, (const u64*)B.chunk_off, (const u32*)B.rank, B.lo, B.hi, B.index);
-        else hipLaunchKernelGGL(k_derep_scatter<false>, dim3(G.of(n_chunks)), dim3(kDerepThreads), 0, nullptr, d_edges, d_a, d_b, n, n_chunks, N, d_cnt, col, vcrit, (const u64*)B.chunk_off, (const u32*)B.rank, B.lo, B.hi, B.index);
-        DR_HIP(hipGetLastError());
+            for (int i = 0; i < 2; ++i)
+                if ((rc = A.alloc(&B.live_lo[i], (size_t)half)) || (rc = A.alloc(&B.live_hi[i], (size_t)half))) return rc;
+        if (d_edges) hipLaunchKernelGGL(k_derep_scatter<true>, dim3(G.grid_of(n_chunks)), dim3(kDerepThreads), 0, nullptr, d_edges, d_a, d_b, n, n_chunks, N, d_cnt, col, vcrit, (const u64*)B.chunk_off, (const u32*)B.rank, B.lo, B.hi, B.index);
+        else hipLaunchKernelGGL(k_derep_scatter<false>, dim3(G.grid_of(n_chunks)), dim3(kDerepThreads), 0, nullptr, d_edges, d_a, d_b, n, n_chunks, N, d_cnt, col, vcrit, (const u64*)B.chunk_off, (const u32*)B.rank, B.lo, B.hi, B.index);
+        KSP_TRY_HIP(hipGetLastError());
     }
     // ---- the rounds
     {
@@ -505,14 +452,14 @@ int derep_on_device(const u32 N, const ksp_edge* d_edges, const u32* d_a, const 
             int rc = KSP_OK;
             const u64 chunks = (len + kDerepChunk - 1) / kDerepChunk;
             u64 kept = 0;
-            hipLaunchKernelGGL(k_derep_live_count, dim3(G.of(chunks)), dim3(kDerepThreads), 0, nullptr, cur_lo, cur_hi, len, chunks, (const u32*)B.state, B.chunk_count);
-            DR_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_derep_live_count, dim3(G.grid_of(chunks)), dim3(kDerepThreads), 0, nullptr, cur_lo, cur_hi, len, chunks, (const u32*)B.state, B.chunk_count);
+            KSP_TRY_HIP(hipGetLastError());
             if ((rc = derep_scan(B, chunks, &kept))) return rc;
             if (kept > n_pairs / 2) { ksp::set_error("dereplicate: a compaction kept more pairs than its list holds"); return KSP_E_HIP; }
             if (kept)
-                hipLaunchKernelGGL(k_derep_live_scatter, dim3(G.of(chunks)), dim3(kDerepThreads), 0, nullptr, cur_lo, cur_hi, len, chunks, (const u32*)B.state,
+                hipLaunchKernelGGL(k_derep_live_scatter, dim3(G.grid_of(chunks)), dim3(kDerepThreads), 0, nullptr, cur_lo, cur_hi, len, chunks, (const u32*)B.state,
                                    (const u64*)B.chunk_off, B.live_lo[next_buf], B.live_hi[next_buf]);
-            DR_HIP(hipGetLastError());
+            KSP_TRY_HIP(hipGetLastError());
             cur_lo = B.live_lo[next_buf];
             cur_hi = B.live_hi[next_buf];
             next_buf ^= 1;
@@ -526,11 +473,11 @@ int derep_on_device(const u32 N, const ksp_edge* d_edges, const u32* d_a, const 
             if (++round > max_rounds) { ksp::set_error("dereplicate: more than " + std::to_string(max_rounds) + " rounds"); return KSP_E_HIP; }
             unsigned long long h_counts[2] = {0, 0};
             const u64 chunks = (len + kDerepChunk - 1) / kDerepChunk;
-            DR_HIP(hipMemsetAsync(B.counts, 0, 16, nullptr));
-            if (len) hipLaunchKernelGGL(k_derep_pairs, dim3(G.of(chunks)), dim3(kDerepThreads), 0, nullptr, cur_lo, cur_hi, len, chunks, B.state, B.blocked, (u32)round, B.counts);
+            KSP_TRY_HIP(hipMemsetAsync(B.counts, 0, 16, nullptr));
+            if (len) hipLaunchKernelGGL(k_derep_pairs, dim3(G.grid_of(chunks)), dim3(kDerepThreads), 0, nullptr, cur_lo, cur_hi, len, chunks, B.state, B.blocked, (u32)round, B.counts);
             hipLaunchKernelGGL(k_derep_nodes, dim3(gn), dim3(256), 0, nullptr, B.state, (const u32*)B.blocked, N, (u32)round, d_undecided);
-            DR_HIP(hipGetLastError());
-            DR_HIP(hipMemcpy(h_counts, B.counts, 16, hipMemcpyDeviceToHost));
+            KSP_TRY_HIP(hipGetLastError());
+            KSP_TRY_HIP(hipMemcpy(h_counts, B.counts, 16, hipMemcpyDeviceToHost));
             ++T.dispatched;
             const u64 live = h_counts[0];
             const u32 undecided = (u32)h_counts[1];
@@ -542,16 +489,16 @@ int derep_on_device(const u32 N, const ksp_edge* d_edges, const u32* d_a, const 
             if (live <= len / 2 && (rc = compact())) return rc;
             if (use_tail && live <= KSP_DEREP_TAIL_PAIRS) {   // (the list is then shorter than twice that)
                 u32 h_out[2] = {0, 0}, waiting = 0;
-                DR_HIP(hipMemsetAsync(d_undecided, 0, 4, nullptr));
+                KSP_TRY_HIP(hipMemsetAsync(d_undecided, 0, 4, nullptr));
                 hipLaunchKernelGGL(k_derep_waiting, dim3(gn), dim3(256), 0, nullptr, (const u32*)B.state, N, B.waiting, d_undecided);
-                DR_HIP(hipGetLastError());
-                DR_HIP(hipMemcpy(&waiting, d_undecided, 4, hipMemcpyDeviceToHost));
+                KSP_TRY_HIP(hipGetLastError());
+                KSP_TRY_HIP(hipMemcpy(&waiting, d_undecided, 4, hipMemcpyDeviceToHost));
                 if (waiting != undecided) { ksp::set_error("dereplicate: the tail's node list does not match the count of the round before"); return KSP_E_HIP; }
                 T.live_at_tail = live;   // (the list it is handed may still hold dead pairs: fewer than as many again)
                 hipLaunchKernelGGL(k_derep_tail, dim3(1), dim3(kTailThreads), 0, nullptr, cur_lo, cur_hi, (u32)len, (const u32*)B.waiting, waiting, B.state, B.blocked,
                                    (u32)round, d_tail_out);
-                DR_HIP(hipGetLastError());
-                DR_HIP(hipMemcpy(h_out, d_tail_out, 8, hipMemcpyDeviceToHost));
+                KSP_TRY_HIP(hipGetLastError());
+                KSP_TRY_HIP(hipMemcpy(h_out, d_tail_out, 8, hipMemcpyDeviceToHost));
                 T.tail = h_out[0];
                 if (h_out[1]) { ksp::set_error("dereplicate: the tail left " + std::to_string(h_out[1]) + " nodes undecided after " + std::to_string(h_out[0]) + " rounds"); return KSP_E_HIP; }
                 break;
@@ -561,23 +508,23 @@ int derep_on_device(const u32 N, const ksp_edge* d_edges, const u32* d_a, const 
     // ---- the assignment, with the final states, over ALL oriented pairs
     if (n_pairs) {
         const u64 chunks = (n_pairs + kDerepChunk - 1) / kDerepChunk;
-        hipLaunchKernelGGL(k_derep_assign, dim3(G.of(chunks)), dim3(kDerepThreads), 0, nullptr, (const u32*)B.lo, (const u32*)B.hi, (const u32*)B.index, n_pairs, chunks,
+        hipLaunchKernelGGL(k_derep_assign, dim3(G.grid_of(chunks)), dim3(kDerepThreads), 0, nullptr, (const u32*)B.lo, (const u32*)B.hi, (const u32*)B.index, n_pairs, chunks,
                            (const u32*)B.state, (const u32*)B.rank, B.best);
     }
     hipLaunchKernelGGL(k_derep_finish, dim3(gn), dim3(256), 0, nullptr, (const u32*)B.state, (const unsigned long long*)B.best, (const u64*)B.sorted, N, B.rep, B.via);
-    DR_HIP(hipGetLastError());
+    KSP_TRY_HIP(hipGetLastError());
     rep.resize(N);
     via.resize(N);
-    DR_HIP(hipMemcpy(rep.data(), B.rep, (size_t)N * 4, hipMemcpyDeviceToHost));
-    DR_HIP(hipMemcpy(via.data(), B.via, (size_t)N * 4, hipMemcpyDeviceToHost));
+    KSP_TRY_HIP(hipMemcpy(rep.data(), B.rep, (size_t)N * 4, hipMemcpyDeviceToHost));
+    KSP_TRY_HIP(hipMemcpy(via.data(), B.via, (size_t)N * 4, hipMemcpyDeviceToHost));
     {
         u32 reps = 0;
         for (u32 v = 0; v < N; ++v) {
             if (rep[v] == kNone || rep[v] >= N || (via[v] != kNone && via[v] >= n)) { ksp::set_error("dereplicate: node " + std::to_string(v) + " was left without a representative"); return KSP_E_HIP; }
             reps += rep[v] == v;
         }
-        if (h_rank) DR_HIP(hipMemcpy(h_rank, B.rank, (size_t)N * 4, hipMemcpyDeviceToHost));
-        if (h_degree) DR_HIP(hipMemcpy(h_degree, B.degree, (size_t)N * 4, hipMemcpyDeviceToHost));
+        if (h_rank) KSP_TRY_HIP(hipMemcpy(h_rank, B.rank, (size_t)N * 4, hipMemcpyDeviceToHost));
+        if (h_degree) KSP_TRY_HIP(hipMemcpy(h_degree, B.degree, (size_t)N * 4, hipMemcpyDeviceToHost));
         std::memcpy(h_rep, rep.data(), (size_t)N * 4);
         if (h_via) std::memcpy(h_via, via.data(), (size_t)N * 4);
         *n_reps = reps;
@@ -628,15 +575,7 @@ void write_derep_file(const std::string& out_path, const std::string& dist, cons
         const DerepRow& r = rows[v];
         text += name_of[v] + "\t" + name_of[r.rep] + "\t" + (r.rep == v ? std::string("-") : r.text) + "\t" + std::to_string(r.degree) + "\t" + std::to_string(r.rank) + "\n";
     }
-    const std::string tmp = out_path + ".partial";
-    {
-        std::ofstream f(tmp, std::ios::binary);
-        if (!f) throw std::runtime_error("cannot write " + tmp);
-        f.write(text.data(), (std::streamsize)text.size());
-        f.flush();
-        if (!f) { std::remove(tmp.c_str()); throw std::runtime_error("write error on " + tmp); }
-    }
-    if (std::rename(tmp.c_str(), out_path.c_str()) != 0) { std::remove(tmp.c_str()); throw std::runtime_error("cannot rename " + tmp); }
+    write_file_atomically(out_path, text);
 }
 }  // namespace ksp
 
@@ -647,7 +586,7 @@ extern "C" int ksp_edges_dereplicate(int device, uint32_t n_nodes, const ksp_edg
     if (dist_col < 3 || dist_col > 5) { ksp::set_error(std::string(who) + ": dist_col is 3 (min), 4 (avg) or 5 (max containment)"); return KSP_E_ARG; }
     if (threshold != threshold) { ksp::set_error(std::string(who) + ": the threshold is NaN"); return KSP_E_ARG; }
     if (n_edges >= 0xFFFFFFFFull) { ksp::set_error(std::string(who) + ": 2^32 - 1 records or more (a record's index is half of its 64-bit key)"); return KSP_E_LIMIT; }
-    if (const int rc = derep_set_device(who, device)) return rc;
+    if (const int rc = ksp::set_device(who, device)) return rc;
     return ksp::derep_edges_on_device(n_nodes, d_edges, n_edges, d_kmer_counts, dist_col, threshold, h_rep, h_via, h_rank, h_degree, n_reps);
 }
 
@@ -672,6 +611,7 @@ extern "C" int kspider_dereplicate(const char* index_prefix, const char* dist_ty
     }
     if (const int rc = check_threshold(who, threshold)) return rc;
     int rc = KSP_OK;
+    ksp::DeviceArena A;
     u32 *d_a = nullptr, *d_b = nullptr;
     g_trace = ksp::DerepTrace();
     try {
@@ -692,15 +632,10 @@ extern "C" int kspider_dereplicate(const char* index_prefix, const char* dist_ty
         std::vector<u32> rep((size_t)N), via((size_t)N), rank((size_t)N), degree((size_t)N);
         u32 n_reps = 0;
         ksp::DerepTrace T;
-        int device = 0;
-        if (const char* dv = std::getenv("KSPIDER_DEVICE")) device = std::atoi(dv);
         if (M && N) {
-            if ((rc = derep_set_device(who, device))) return rc;
-            DR_HIP(hipMalloc((void**)&d_a, M * 4));
-            DR_HIP(hipMalloc((void**)&d_b, M * 4));
-            DR_HIP(hipMemcpy(d_a, ea.data(), M * 4, hipMemcpyHostToDevice));
-            DR_HIP(hipMemcpy(d_b, eb.data(), M * 4, hipMemcpyHostToDevice));
-            if ((rc = derep_on_device(N, nullptr, d_a, d_b, M, nullptr, 0, 0.0f, rep.data(), via.data(), rank.data(), degree.data(), &n_reps, T))) goto done;
+            if ((rc = ksp::set_device(who, ksp::device_from_env()))) return rc;
+            if ((rc = ksp::upload_pairs(A, ea.data(), eb.data(), M, &d_a, &d_b))) return rc;
+            if ((rc = derep_on_device(N, nullptr, d_a, d_b, M, nullptr, 0, 0.0f, rep.data(), via.data(), rank.data(), degree.data(), &n_reps, T))) return rc;
         } else {
             derep_identity(N, rep.data(), via.data(), rank.data(), degree.data(), &n_reps);
         }
@@ -724,8 +659,5 @@ extern "C" int kspider_dereplicate(const char* index_prefix, const char* dist_ty
         ksp::set_error(std::string(who) + ": " + m);
         rc = m.find("2^32") != std::string::npos ? KSP_E_LIMIT : KSP_E_IO;
     }
-done:
-    if (d_a) (void)hipFree(d_a);
-    if (d_b) (void)hipFree(d_b);
     return rc;
 }

@@ -22,7 +22,6 @@ void cc_critical(double cutoff, float* vcrit, int* mode);
 // ANI of `pairwise --estimate-ani` for k-mer size ksize (ani.h; KSP_E_ARG if an edge has a NaN containment)
 int cc_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, double cutoff,
                        uint32_t* h_label, uint64_t* n_kept, int ksize = 0);
-int upload_ani_table(int ksize, double** d_table);
 void read_names_map(const std::string& prefix, std::vector<std::string>& name_of);
 void write_cluster_file(const std::string& prefix, double threshold, const std::vector<uint32_t>& label,
                         const std::vector<std::string>& name_of);

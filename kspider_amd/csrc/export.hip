@@ -45,7 +45,9 @@
 
 #include "../../include/kspider_amd.h"
 #include "ani.h"
+#include "device_call.h"
 #include "engine_internal.h"
+#include "partial_file.h"
 
 typedef uint32_t u32;
 typedef uint64_t u64;
@@ -191,16 +193,6 @@ __global__ __launch_bounds__(kPrimThreads) void k_prim_single(const double* __re
     }
 }
 
-#define EX_HIP(call)                                                                     \
-    do {                                                                                 \
-        hipError_t err__ = (call);                                                       \
-        if (err__ != hipSuccess) {                                                       \
-            ksp::set_error(std::string(#call) + ": " + hipGetErrorString(err__));        \
-            rc = KSP_E_HIP;                                                              \
-            goto done;                                                                   \
-        }                                                                                \
-    } while (0)
-
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
@@ -216,18 +208,6 @@ struct Phases {   // $KSP_EXPORT_TIMES=1: one line of phase times on stderr
         t = Clock::now();
     }
 };
-
-int device_from_env() {
-    const char* dv = std::getenv("KSPIDER_DEVICE");
-    return dv ? std::atoi(dv) : 0;
-}
-
-bool bytes_fit(u64 need, u64* free_out) {
-    size_t fr = 0, total = 0;
-    if (hipMemGetInfo(&fr, &total) != hipSuccess) return false;
-    *free_out = fr;
-    return need <= fr;
-}
 
 // scipy's linkage after mst_single_linkage's loop: stable sort of the (x, y, height) rows by height, union-find relabel
 bool relabel(u32 n, const std::vector<double>& prim, double* Z) {
@@ -273,6 +253,7 @@ hipError_t launch_row_distances(u32 n, const double* d_rows, double* d_dist, u32
 // not changed.  KSP_E_ARG when a distance is not finite.
 int single_linkage_on_device(u32 n, const double* d_rows, double* h_Z, double* h_prim, Phases* ph) {
     int rc = KSP_OK;
+    ksp::DeviceArena A;
     double *d_dist = nullptr, *d_prim = nullptr, *d_D = nullptr;
     u32* d_near = nullptr;
     std::vector<u32> near(h_prim ? n : 0);
@@ -282,15 +263,13 @@ int single_linkage_on_device(u32 n, const double* d_rows, double* h_Z, double* h
     const u64 nn = (u64)n * n;
     const char* lds_env = std::getenv("KSP_PRIM_LDS");   // "0": keep D[] in global memory at every size (tests)
     const bool use_lds = n <= kPrimLdsNodes && !(lds_env && std::strcmp(lds_env, "0") == 0);
-    EX_HIP(hipMalloc((void**)&d_dist, nn * sizeof(double)));
-    EX_HIP(hipMalloc((void**)&d_prim, prim.size() * sizeof(double)));
-    EX_HIP(hipMalloc((void**)&d_flags, sizeof flags));
-    EX_HIP(hipMemsetAsync(d_flags, 0, sizeof flags, nullptr));
-    if (!use_lds) EX_HIP(hipMalloc((void**)&d_D, (u64)n * sizeof(double)));
-    if (h_prim) EX_HIP(hipMalloc((void**)&d_near, (u64)n * sizeof(u32)));
+    if ((rc = A.alloc(&d_dist, (size_t)nn)) || (rc = A.alloc(&d_prim, prim.size())) || (rc = A.alloc(&d_flags, 2))) return rc;
+    KSP_TRY_HIP(hipMemsetAsync(d_flags, 0, sizeof flags, nullptr));
+    if (!use_lds && (rc = A.alloc(&d_D, (size_t)n))) return rc;
+    if (h_prim && (rc = A.alloc(&d_near, (size_t)n))) return rc;
     {
-        EX_HIP(launch_row_distances(n, d_rows, d_dist, d_flags));
-        EX_HIP(hipMemcpy(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost));
+        KSP_TRY_HIP(launch_row_distances(n, d_rows, d_dist, d_flags));
+        KSP_TRY_HIP(hipMemcpy(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost));
         if (ph) ph->mark("k_row_dist+sqrt");
         if (flags[0]) {
             ksp::set_error("single linkage: a distance between two rows is not finite (scipy's linkage refuses it)");
@@ -298,12 +277,12 @@ int single_linkage_on_device(u32 n, const double* d_rows, double* h_Z, double* h
             goto done;
         }
         const size_t lds = use_lds ? (size_t)n * sizeof(double) : 0;
-        if (use_lds) EX_HIP(hipFuncSetAttribute((const void*)k_prim_single, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (use_lds) KSP_TRY_HIP(hipFuncSetAttribute((const void*)k_prim_single, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_prim_single, dim3(1), dim3(kPrimThreads), lds, nullptr, d_dist, n, d_D, use_lds ? 1 : 0, d_prim, d_flags + 1, d_near);
-        EX_HIP(hipGetLastError());
-        EX_HIP(hipMemcpy(prim.data(), d_prim, prim.size() * sizeof(double), hipMemcpyDeviceToHost));
-        EX_HIP(hipMemcpy(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost));
-        if (h_prim) EX_HIP(hipMemcpy(near.data(), d_near, (u64)n * sizeof(u32), hipMemcpyDeviceToHost));
+        KSP_TRY_HIP(hipGetLastError());
+        KSP_TRY_HIP(hipMemcpy(prim.data(), d_prim, prim.size() * sizeof(double), hipMemcpyDeviceToHost));
+        KSP_TRY_HIP(hipMemcpy(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost));
+        if (h_prim) KSP_TRY_HIP(hipMemcpy(near.data(), d_near, (u64)n * sizeof(u32), hipMemcpyDeviceToHost));
         if (ph) ph->mark("k_prim_single");
     }
     if (flags[1] || (h_Z && !relabel(n, prim, h_Z))) {
@@ -319,19 +298,7 @@ int single_linkage_on_device(u32 n, const double* d_rows, double* h_Z, double* h
             h_prim[4 * k + 3] = (double)near[y];
         }
 done:
-    if (d_dist) (void)hipFree(d_dist);
-    if (d_prim) (void)hipFree(d_prim);
-    if (d_D) (void)hipFree(d_D);
-    if (d_flags) (void)hipFree(d_flags);
-    if (d_near) (void)hipFree(d_near);
     return rc;
-}
-
-int select_device(int device, const char* who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { ksp::set_error(std::string(who) + ": no such device"); return KSP_E_HIP; }
-    if (hipSetDevice(device) != hipSuccess) { ksp::set_error(std::string(who) + ": hipSetDevice"); return KSP_E_HIP; }
-    return KSP_OK;
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -498,33 +465,6 @@ std::string csv_field(const std::string& s) {
         if (c == '"') q += '"';
     }
     return q + "\"";
-}
-
-struct PartialFiles {   // every output goes to PATH.partial; all are renamed at the end, or all removed
-    std::vector<std::string> paths;
-    bool done = false;
-    std::string open(const std::string& path, std::ofstream& f) {
-        paths.push_back(path);
-        const std::string tmp = path + ".partial";
-        f.open(tmp, std::ios::binary | std::ios::trunc);
-        if (!f) throw std::runtime_error("cannot write " + tmp);
-        return tmp;
-    }
-    void commit() {
-        for (auto& p : paths)
-            if (std::rename((p + ".partial").c_str(), p.c_str()) != 0) throw std::runtime_error("cannot rename " + p + ".partial");
-        done = true;
-    }
-    ~PartialFiles() {
-        if (done) return;
-        for (auto& p : paths) std::remove((p + ".partial").c_str());
-    }
-};
-
-void close_checked(std::ofstream& f, const std::string& what) {
-    f.flush();
-    if (!f) throw std::runtime_error("write error on " + what);
-    f.close();
 }
 
 struct Refusal : std::runtime_error {
@@ -738,50 +678,44 @@ int export_impl(const std::string& prefix, const std::string& dt, bool newick, c
             }
         });
         if (bad) throw Refusal(KSP_E_ARG, "--newick: a distance 1 - value is not finite (scipy's linkage refuses it)");
-        if (int rc = select_device(device_from_env(), "kspider_export")) throw Refusal(rc, ksp_last_error());
+        if (int rc = ksp::set_device("kspider_export", ksp::device_from_env())) throw Refusal(rc, ksp_last_error());
         const u64 nn = (u64)N * N;
         u64 fr = 0;
-        if (!bytes_fit(2 * nn * sizeof(double) + E * 16 + ((u64)N * 4 + 64) * sizeof(double), &fr))
+        if (ksp::device_fits("kspider_export", 2 * nn * sizeof(double) + E * 16 + ((u64)N * 4 + 64) * sizeof(double), "", &fr))
             throw Refusal(KSP_E_LIMIT, "--newick: the two " + std::to_string(N) + " x " + std::to_string(N) +
                                            " double matrices do not fit the device's free memory (" + std::to_string(fr >> 20) + " MiB)");
         int rc = KSP_OK;
+        ksp::DeviceArena A;
         double *d_M = nullptr, *d_m = nullptr;
         u32 *d_p = nullptr, *d_q = nullptr;
         Z.resize(4 * (u64)(N - 1));
         {
             std::vector<u32> p(E), q(E);
             for (u64 e = 0; e < E; ++e) { p[e] = pos_of[rows[e].id1]; q[e] = pos_of[rows[e].id2]; }
-            EX_HIP(hipMalloc((void**)&d_M, nn * sizeof(double)));
-            EX_HIP(hipMemsetAsync(d_M, 0, nn * sizeof(double), nullptr));
+            if ((rc = A.alloc(&d_M, (size_t)nn))) goto done;
+            KSP_TRY_HIP(hipMemsetAsync(d_M, 0, nn * sizeof(double), nullptr));
             if (E) {
-                EX_HIP(hipMalloc((void**)&d_p, E * 4));
-                EX_HIP(hipMalloc((void**)&d_q, E * 4));
-                EX_HIP(hipMalloc((void**)&d_m, E * 8));
-                EX_HIP(hipMemcpy(d_p, p.data(), E * 4, hipMemcpyHostToDevice));
-                EX_HIP(hipMemcpy(d_q, q.data(), E * 4, hipMemcpyHostToDevice));
-                EX_HIP(hipMemcpy(d_m, m.data(), E * 8, hipMemcpyHostToDevice));
+                if ((rc = ksp::upload_pairs(A, p.data(), q.data(), E, &d_p, &d_q)) || (rc = A.alloc(&d_m, (size_t)E))) goto done;
+                KSP_TRY_HIP(hipMemcpy(d_m, m.data(), E * 8, hipMemcpyHostToDevice));
                 hipLaunchKernelGGL(k_scatter, dim3((unsigned)std::min<u64>((E + 255) / 256, 8192)), dim3(256), 0, nullptr, d_p, d_q, d_m, E, N, d_M);
-                EX_HIP(hipGetLastError());
-                EX_HIP(hipFree(d_p)); d_p = nullptr;
-                EX_HIP(hipFree(d_q)); d_q = nullptr;
-                EX_HIP(hipFree(d_m)); d_m = nullptr;
+                KSP_TRY_HIP(hipGetLastError());
+                KSP_TRY_HIP(A.release(d_p));   // (the cells are in the matrix: the distance matrix gets their room)
+                KSP_TRY_HIP(A.release(d_q));
+                KSP_TRY_HIP(A.release(d_m));
             }
-            if (ph.on) { EX_HIP(hipDeviceSynchronize()); ph.mark("h2d+scatter"); }
+            if (ph.on) { KSP_TRY_HIP(hipDeviceSynchronize()); ph.mark("h2d+scatter"); }
             rc = single_linkage_on_device(N, d_M, Z.data(), nullptr, &ph);
         }
     done:
-        if (d_M) (void)hipFree(d_M);
-        if (d_p) (void)hipFree(d_p);
-        if (d_q) (void)hipFree(d_q);
-        if (d_m) (void)hipFree(d_m);
         if (rc) throw Refusal(rc, ksp_last_error());
     }
 
     // ---- text outputs ----
-    PartialFiles files;
+    std::ofstream f_pw, f_dm, f_nw;
+    ksp::PartialFiles files;
     {   // named pairwise TSV, in row order
-        std::ofstream f;
-        const std::string tmp = files.open(out_pw, f);
+        std::ofstream& f = f_pw;
+        files.open(out_pw, f);
         f << (col == 0 ? std::string("source1\tsource2\tani\n") : "grp1\tgrp2\t" + dt + "\n");
         const u64 B = 1 << 20;
         for (u64 b0 = 0; b0 < E; b0 += B) {
@@ -802,11 +736,10 @@ int export_impl(const std::string& prefix, const std::string& dt, bool newick, c
             });
             for (auto& s : part) f.write(s.data(), (std::streamsize)s.size());
         }
-        close_checked(f, tmp);
     }
     {   // distance matrix, row by row from the CSR
-        std::ofstream f;
-        const std::string tmp = files.open(out_dm, f);
+        std::ofstream& f = f_dm;
+        files.open(out_dm, f);
         std::string head;
         for (u32 p = 0; p < N; ++p) { head += '\t'; head += csv_field(nodes[p]); }
         head += '\n';
@@ -835,15 +768,12 @@ int export_impl(const std::string& prefix, const std::string& dt, bool newick, c
             });
             for (u32 i = 0; i < r1 - r0; ++i) f.write(text[i].data(), (std::streamsize)text[i].size());
         }
-        close_checked(f, tmp);
     }
     ph.mark("text outputs");
     if (newick) {
-        std::ofstream f;
-        const std::string tmp = files.open(out_nw, f);
+        files.open(out_nw, f_nw);
         const std::string t = newick_text(N, Z.data(), nodes);
-        f.write(t.data(), (std::streamsize)t.size());
-        close_checked(f, tmp);
+        f_nw.write(t.data(), (std::streamsize)t.size());
         ph.mark("newick");
     }
     files.commit();
@@ -865,9 +795,8 @@ template <class F>
 int linkage_entry(const char* who, int device, uint32_t n, const double* d_rows, bool has_output, F&& run) {
     if (n > kMaxNodes) { ksp::set_error(std::string(who) + ": n above the limit of 65536"); return KSP_E_LIMIT; }
     if (n < 2 || !d_rows || !has_output) { ksp::set_error(std::string(who) + ": n < 2 or NULL argument"); return KSP_E_ARG; }
-    if (int rc = select_device(device, who)) return rc;
-    u64 fr = 0;
-    if (!bytes_fit((u64)n * n * sizeof(double) + ((u64)n * 4 + 64) * sizeof(double), &fr)) {
+    if (int rc = ksp::set_device(who, device)) return rc;
+    if (ksp::device_fits(who, (u64)n * n * sizeof(double) + ((u64)n * 4 + 64) * sizeof(double), "")) {
         ksp::set_error(std::string(who) + ": the n x n distance matrix does not fit the device's free memory");
         return KSP_E_LIMIT;
     }
@@ -881,23 +810,21 @@ int linkage_entry(const char* who, int device, uint32_t n, const double* d_rows,
 
 int row_distances_on_device(u32 n, const double* d_rows, double* h_dist) {
     int rc = KSP_OK;
+    ksp::DeviceArena A;
     double* d_dist = nullptr;
     u32* d_flag = nullptr;
     u32 flag = 0;
-    EX_HIP(hipMalloc((void**)&d_dist, (u64)n * n * sizeof(double)));
-    EX_HIP(hipMalloc((void**)&d_flag, sizeof flag));
-    EX_HIP(hipMemsetAsync(d_flag, 0, sizeof flag, nullptr));
-    EX_HIP(launch_row_distances(n, d_rows, d_dist, d_flag));
-    EX_HIP(hipMemcpy(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost));
+    if ((rc = A.alloc(&d_dist, (size_t)n * n)) || (rc = A.alloc(&d_flag, 1))) return rc;
+    KSP_TRY_HIP(hipMemsetAsync(d_flag, 0, sizeof flag, nullptr));
+    KSP_TRY_HIP(launch_row_distances(n, d_rows, d_dist, d_flag));
+    KSP_TRY_HIP(hipMemcpy(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost));
     if (flag) {
         ksp::set_error("row distances: a distance between two rows is not finite (scipy's linkage refuses it)");
         rc = KSP_E_ARG;
         goto done;
     }
-    EX_HIP(hipMemcpy(h_dist, d_dist, (u64)n * n * sizeof(double), hipMemcpyDeviceToHost));
+    KSP_TRY_HIP(hipMemcpy(h_dist, d_dist, (u64)n * n * sizeof(double), hipMemcpyDeviceToHost));
 done:
-    if (d_dist) (void)hipFree(d_dist);
-    if (d_flag) (void)hipFree(d_flag);
     return rc;
 }
 }  // namespace

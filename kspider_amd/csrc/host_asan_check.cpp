@@ -1,15 +1,93 @@
 // Driver of the sanitizer build (make asan): runs one host entry point on one input and prints its return code.
 //   host_asan_check index PREFIX | info PREFIX | sigs DIR KSIZE OUTPREFIX | bins DIR OUTPREFIX
 //                   | cut PREFIX DIST CUTOFF | edges_cut X | host_cut X   (the last two: the entry point with nothing to do)
+//                   | partial DIR   (partial_file.h itself in DIR, which holds only the directory d.tsv with a file in it: one
+//                                    "ok" / "FAIL" line per case)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
+#include <sstream>
+#include <stdexcept>
+#include <string>
 
 #include "../../include/kspider_amd.h"
+#include "partial_file.h"
+
+namespace {
+bool exists(const std::string& path) { return (bool)std::ifstream(path); }
+std::string partial_of(const std::string& path) { return path + ".partial"; }   // (spelled out here: the helper's own is what is checked)
+bool holds(const std::string& path, const std::string& text) {
+    std::ifstream f(path, std::ios::binary);
+    std::ostringstream ss;
+    ss << f.rdbuf();
+    return f && ss.str() == text;
+}
+void report(const char* name, const bool ok) { std::printf("%s %s\n", ok ? "ok" : "FAIL", name); }
+
+int check_partial_files(const std::string& dir) {
+    const std::string a = dir + "/a.tsv", b = dir + "/b.tsv";
+    {   // two files opened and committed
+        {
+            std::ofstream fa, fb;
+            ksp::PartialFiles files;
+            files.open(a, fa);
+            files.open(b, fb);
+            fa << "first\n";
+            fb << "second\r\n\n";
+            files.commit();
+        }
+        report("committed", holds(a, "first\n") && holds(b, "second\r\n\n") && !exists(partial_of(a)) && !exists(partial_of(b)));
+        std::remove(a.c_str());
+        std::remove(b.c_str());
+    }
+    {   // two files opened, an exception before the commit
+        bool thrown = false, seen = false;
+        try {
+            std::ofstream fa, fb;
+            ksp::PartialFiles files;
+            files.open(a, fa);
+            files.open(b, fb);
+            fa << "first\n";
+            fa.flush();
+            seen = exists(partial_of(a)) && exists(partial_of(b));
+            throw std::runtime_error("stop");
+        } catch (const std::runtime_error&) {
+            thrown = true;
+        }
+        report("abandoned", thrown && seen && !exists(a) && !exists(b) && !exists(partial_of(a)) && !exists(partial_of(b)));
+    }
+    {   // a directory that does not exist
+        const std::string c = dir + "/missing/c.tsv";
+        bool thrown = false;
+        try {
+            std::ofstream f;
+            ksp::PartialFiles files;
+            files.open(c, f);
+            files.commit();
+        } catch (const std::runtime_error&) {
+            thrown = true;
+        }
+        report("no directory", thrown && !exists(c) && !exists(partial_of(c)) && !exists(dir + "/missing"));
+    }
+    {   // a rename that fails: the final name is a directory that is not empty (DIR/d.tsv/keep, made by the caller)
+        const std::string d = dir + "/d.tsv";
+        bool thrown = false;
+        try {
+            ksp::write_file_atomically(d, "text\n");
+        } catch (const std::runtime_error&) {
+            thrown = true;
+        }
+        report("rename refused", thrown && !exists(partial_of(d)) && exists(d + "/keep"));
+    }
+    return 0;
+}
+}  // namespace
 
 int main(int argc, char** argv) {
     if (argc < 3) return 64;
     int rc = -1;
+    if (!std::strcmp(argv[1], "partial")) return check_partial_files(argv[2]);
     if (!std::strcmp(argv[1], "index")) rc = kspider_pairwise(argv[2], 2);
     else if (!std::strcmp(argv[1], "info")) { uint64_t out[6]; rc = ksp_index_info(argv[2], out); if (!rc) std::printf("info %llu %llu %llu %llu %llu %llu\n", (unsigned long long)out[0], (unsigned long long)out[1], (unsigned long long)out[2], (unsigned long long)out[3], (unsigned long long)out[4], (unsigned long long)out[5]); }
     else if (!std::strcmp(argv[1], "sigs") && argc >= 5) rc = kspider_pairwise_sigs(argv[2], std::atoi(argv[3]), argv[4], 2);

@@ -15,6 +15,7 @@
 // kWidth (16 with SSE2, 8 without) and the optional trailer are detected from the file
 // sizes and the cloned control bytes; anything inconsistent is an error, never a guess.
 #include "index_io.h"
+#include "partial_file.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -331,33 +332,28 @@ void format_rows(const std::vector<EdgeRow>& rows, size_t lo, size_t hi,
 void write_pairwise_tsv(const std::string& prefix, const std::vector<EdgeRow>& rows,
                         const std::unordered_map<uint32_t, uint32_t>& kmer_count, int threads) {
     const std::string path = prefix + "_kSpider_pairwise.tsv";
-    const std::string tmp = path + ".partial";
     const size_t T = (size_t)std::max(1, std::min(threads, 64));
     const size_t chunk = 1 << 16;
-    {
-        std::ofstream f(tmp, std::ios::binary);
-        if (!f) throw std::runtime_error("kspider_amd: cannot write " + path);
-        f << "source_1\tsource_2\tshared_kmers\tmin_containment\tavg_containment\tmax_containment\n";
-        // format T chunks at a time in parallel, write them in order
-        for (size_t base = 0; base < rows.size(); base += chunk * T) {
-            std::vector<std::string> parts(T);
-            std::vector<std::thread> th;
-            for (size_t t = 0; t < T; ++t) {
-                size_t lo = std::min(rows.size(), base + t * chunk), hi = std::min(rows.size(), lo + chunk);
-                if (lo >= hi) break;
-                if (T == 1) format_rows(rows, lo, hi, kmer_count, parts[t]);
-                else th.emplace_back(format_rows, std::cref(rows), lo, hi, std::cref(kmer_count), std::ref(parts[t]));
-            }
-            for (auto& x : th) x.join();
-            for (auto& s : parts)
-                if (!s.empty() && !f.write(s.data(), (std::streamsize)s.size()))
-                    throw std::runtime_error("kspider_amd: write failed on " + path);
+    std::ofstream f;
+    PartialFiles files;   // never a partial TSV under the final name
+    files.open(path, f);
+    f << "source_1\tsource_2\tshared_kmers\tmin_containment\tavg_containment\tmax_containment\n";
+    // format T chunks at a time in parallel, write them in order
+    for (size_t base = 0; base < rows.size(); base += chunk * T) {
+        std::vector<std::string> parts(T);
+        std::vector<std::thread> th;
+        for (size_t t = 0; t < T; ++t) {
+            size_t lo = std::min(rows.size(), base + t * chunk), hi = std::min(rows.size(), lo + chunk);
+            if (lo >= hi) break;
+            if (T == 1) format_rows(rows, lo, hi, kmer_count, parts[t]);
+            else th.emplace_back(format_rows, std::cref(rows), lo, hi, std::cref(kmer_count), std::ref(parts[t]));
         }
-        f.flush();
-        if (!f) throw std::runtime_error("kspider_amd: write failed on " + path);
+        for (auto& x : th) x.join();
+        for (auto& s : parts)
+            if (!s.empty() && !f.write(s.data(), (std::streamsize)s.size()))
+                throw std::runtime_error("write error on " + path);
     }
-    // never leave a partial TSV under the final name
-    if (std::rename(tmp.c_str(), path.c_str()) != 0) throw std::runtime_error("kspider_amd: cannot rename " + tmp);
+    files.commit();
 }
 
 }  // namespace ksp

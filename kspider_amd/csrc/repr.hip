@@ -36,8 +36,10 @@
 #include <rocprim/device/device_select.hpp>
 
 #include "../../include/kspider_amd.h"
+#include "device_call.h"
 #include "edge_cut.hip.h"
 #include "engine_internal.h"
+#include "partial_file.h"
 
 typedef uint32_t u32;
 typedef uint64_t u64;
@@ -120,16 +122,6 @@ struct HasNeighbour {
     __host__ __device__ bool operator()(const u64& key) const { return (key >> 32) != 0xFFFFFFFFull; }   // (count != 0)
 };
 
-#define RP_HIP(call)                                                                     \
-    do {                                                                                 \
-        hipError_t err__ = (call);                                                       \
-        if (err__ != hipSuccess) {                                                       \
-            ksp::set_error(std::string(#call) + ": " + hipGetErrorString(err__));        \
-            rc = KSP_E_HIP;                                                              \
-            goto done;                                                                   \
-        }                                                                                \
-    } while (0)
-
 template <bool kRecords>
 int launch_degree(const ksp_edge* d_edges, const u32* d_a, const u32* d_b, const u64 m, const u32 n_nodes, const u32* d_cnt, const int col,
                   const float vcrit, u32* d_degree) {
@@ -137,19 +129,19 @@ int launch_degree(const ksp_edge* d_edges, const u32* d_a, const u32* d_b, const
     int device = 0, cus = 0;
     const char* lds_env = std::getenv("KSP_DEGREE_LDS");   // "0": global counters at every size (tests)
     const bool use_lds = n_nodes <= kDegreeLdsNodes && !(lds_env && std::strcmp(lds_env, "0") == 0);
-    RP_HIP(hipGetDevice(&device));
-    RP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    KSP_TRY_HIP(hipGetDevice(&device));
+    KSP_TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     if (cus < 1) cus = 1;
     if (use_lds) {
         const size_t lds = (size_t)n_nodes * sizeof(u32);
         const unsigned grid = (unsigned)std::min<u64>((m + kDegreeEdgesPerGroup - 1) / kDegreeEdgesPerGroup, 2ull * (u64)cus);
-        RP_HIP(hipFuncSetAttribute((const void*)k_degree<true, kRecords>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        KSP_TRY_HIP(hipFuncSetAttribute((const void*)k_degree<true, kRecords>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((k_degree<true, kRecords>), dim3(grid), dim3(kDegreeThreads), lds, nullptr, d_edges, d_a, d_b, m, n_nodes, d_cnt, col, vcrit, d_degree);
     } else {
         const unsigned grid = (unsigned)std::min<u64>((m + kDegreeThreads - 1) / kDegreeThreads, 2ull * (u64)cus);
         hipLaunchKernelGGL((k_degree<false, kRecords>), dim3(grid), dim3(kDegreeThreads), 0, nullptr, d_edges, d_a, d_b, m, n_nodes, d_cnt, col, vcrit, d_degree);
     }
-    RP_HIP(hipGetLastError());
+    KSP_TRY_HIP(hipGetLastError());
 done:
     return rc;
 }
@@ -159,38 +151,36 @@ done:
 int degrees_on_device(const u32 n_nodes, const ksp_edge* d_edges, const u32* d_a, const u32* d_b, const u64 n_edges, const u32* d_cnt, const int col,
                       const float vcrit, u32* h_degree, u32* h_node, u32* h_count, u32* n_ranked) {
     int rc = KSP_OK;
+    ksp::DeviceArena A;
     u32* d_degree = nullptr;
     u64 *d_keys = nullptr, *d_sel = nullptr, *d_sorted = nullptr;
     unsigned long long* d_nsel = nullptr;
     void* d_tmp = nullptr;
-    RP_HIP(hipMalloc((void**)&d_degree, (size_t)n_nodes * 4));
-    RP_HIP(hipMemsetAsync(d_degree, 0, (size_t)n_nodes * 4, nullptr));
+    if ((rc = A.alloc(&d_degree, (size_t)n_nodes))) goto done;
+    KSP_TRY_HIP(hipMemsetAsync(d_degree, 0, (size_t)n_nodes * 4, nullptr));
     if (d_edges) rc = launch_degree<true>(d_edges, nullptr, nullptr, n_edges, n_nodes, d_cnt, col, vcrit, d_degree);
     else rc = launch_degree<false>(nullptr, d_a, d_b, n_edges, n_nodes, nullptr, 0, 0.0f, d_degree);
     if (rc) goto done;
-    if (h_degree) RP_HIP(hipMemcpy(h_degree, d_degree, (size_t)n_nodes * 4, hipMemcpyDeviceToHost));
+    if (h_degree) KSP_TRY_HIP(hipMemcpy(h_degree, d_degree, (size_t)n_nodes * 4, hipMemcpyDeviceToHost));
     if (h_node) {
         unsigned long long nsel = 0;
         size_t tb = 0;
         *n_ranked = 0;
-        RP_HIP(hipMalloc((void**)&d_keys, (size_t)n_nodes * 8));
-        RP_HIP(hipMalloc((void**)&d_sel, (size_t)n_nodes * 8));
-        RP_HIP(hipMalloc((void**)&d_nsel, 8));
+        if ((rc = A.alloc(&d_keys, (size_t)n_nodes)) || (rc = A.alloc(&d_sel, (size_t)n_nodes)) || (rc = A.alloc(&d_nsel, 1))) goto done;
         hipLaunchKernelGGL(k_degree_keys, dim3((unsigned)(((u64)n_nodes + 255) / 256)), dim3(256), 0, nullptr, d_degree, n_nodes, d_keys);
-        RP_HIP(hipGetLastError());
-        RP_HIP(rocprim::select(nullptr, tb, d_keys, d_sel, d_nsel, (size_t)n_nodes, HasNeighbour(), (hipStream_t) nullptr));
-        RP_HIP(hipMalloc(&d_tmp, tb ? tb : 8));
-        RP_HIP(rocprim::select(d_tmp, tb, d_keys, d_sel, d_nsel, (size_t)n_nodes, HasNeighbour(), (hipStream_t) nullptr));
-        RP_HIP(hipMemcpy(&nsel, d_nsel, 8, hipMemcpyDeviceToHost));
-        (void)hipFree(d_tmp);
-        d_tmp = nullptr;
+        KSP_TRY_HIP(hipGetLastError());
+        KSP_TRY_HIP(rocprim::select(nullptr, tb, d_keys, d_sel, d_nsel, (size_t)n_nodes, HasNeighbour(), (hipStream_t) nullptr));
+        if ((rc = A.alloc_bytes(&d_tmp, tb ? tb : 8))) goto done;
+        KSP_TRY_HIP(rocprim::select(d_tmp, tb, d_keys, d_sel, d_nsel, (size_t)n_nodes, HasNeighbour(), (hipStream_t) nullptr));
+        KSP_TRY_HIP(hipMemcpy(&nsel, d_nsel, 8, hipMemcpyDeviceToHost));
+        (void)A.release(d_tmp);   // (the select's scratch goes before the sort's comes: the peak stays the larger of the two)
         if (nsel) {
             std::vector<u64> keys((size_t)nsel);
-            RP_HIP(hipMalloc((void**)&d_sorted, (size_t)nsel * 8));
-            RP_HIP(rocprim::radix_sort_keys(nullptr, tb, d_sel, d_sorted, (size_t)nsel, 0, 64, (hipStream_t) nullptr));
-            RP_HIP(hipMalloc(&d_tmp, tb ? tb : 8));
-            RP_HIP(rocprim::radix_sort_keys(d_tmp, tb, d_sel, d_sorted, (size_t)nsel, 0, 64, (hipStream_t) nullptr));
-            RP_HIP(hipMemcpy(keys.data(), d_sorted, (size_t)nsel * 8, hipMemcpyDeviceToHost));
+            if ((rc = A.alloc(&d_sorted, (size_t)nsel))) goto done;
+            KSP_TRY_HIP(rocprim::radix_sort_keys(nullptr, tb, d_sel, d_sorted, (size_t)nsel, 0, 64, (hipStream_t) nullptr));
+            if ((rc = A.alloc_bytes(&d_tmp, tb ? tb : 8))) goto done;
+            KSP_TRY_HIP(rocprim::radix_sort_keys(d_tmp, tb, d_sel, d_sorted, (size_t)nsel, 0, 64, (hipStream_t) nullptr));
+            KSP_TRY_HIP(hipMemcpy(keys.data(), d_sorted, (size_t)nsel * 8, hipMemcpyDeviceToHost));
             for (size_t i = 0; i < keys.size(); ++i) {
                 h_node[i] = (u32)keys[i];
                 h_count[i] = ~(u32)(keys[i] >> 32);
@@ -199,20 +189,7 @@ int degrees_on_device(const u32 n_nodes, const ksp_edge* d_edges, const u32* d_a
         *n_ranked = (u32)nsel;
     }
 done:
-    if (d_degree) (void)hipFree(d_degree);
-    if (d_keys) (void)hipFree(d_keys);
-    if (d_sel) (void)hipFree(d_sel);
-    if (d_sorted) (void)hipFree(d_sorted);
-    if (d_nsel) (void)hipFree(d_nsel);
-    if (d_tmp) (void)hipFree(d_tmp);
     return rc;
-}
-
-int set_device(const char* who, const int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { ksp::set_error(std::string(who) + ": no such device"); return KSP_E_HIP; }
-    if (hipSetDevice(device) != hipSuccess) { ksp::set_error(std::string(who) + ": hipSetDevice"); return KSP_E_HIP; }
-    return KSP_OK;
 }
 
 int check_edges_args(const char* who, const ksp_edge* d_edges, const u64 n_edges, const u32* d_kmer_counts, const int dist_col, const double threshold) {
@@ -295,12 +272,12 @@ int repr_edges_on_device(const uint32_t n_nodes, const ksp_edge* d_edges, const 
 int degree_keys_on_device(const uint32_t n_nodes, const ksp_edge* d_edges, const uint32_t* d_a, const uint32_t* d_b, const uint64_t n_edges,
                           const uint32_t* d_cnt, const int col, const float vcrit, uint32_t* d_degree, uint64_t* d_keys) {
     int rc = KSP_OK;
-    RP_HIP(hipMemsetAsync(d_degree, 0, (size_t)n_nodes * 4, nullptr));
+    KSP_TRY_HIP(hipMemsetAsync(d_degree, 0, (size_t)n_nodes * 4, nullptr));
     if (d_edges) rc = launch_degree<true>(d_edges, nullptr, nullptr, n_edges, n_nodes, d_cnt, col, vcrit, d_degree);
     else rc = launch_degree<false>(nullptr, d_a, d_b, n_edges, n_nodes, nullptr, 0, 0.0f, d_degree);
     if (rc) goto done;
     hipLaunchKernelGGL(k_degree_keys, dim3((unsigned)(((u64)n_nodes + 255) / 256)), dim3(256), 0, nullptr, (const u32*)d_degree, n_nodes, (u64*)d_keys);
-    RP_HIP(hipGetLastError());
+    KSP_TRY_HIP(hipGetLastError());
 done:
     return rc;
 }
@@ -318,15 +295,7 @@ void write_repr_file(const std::string& out_path, const std::vector<uint32_t>& i
         if (std::fwrite(text.data(), 1, text.size(), stdout) != text.size() || std::fflush(stdout) != 0) throw std::runtime_error("write error on stdout");
         return;
     }
-    const std::string tmp = out_path + ".partial";
-    {
-        std::ofstream f(tmp, std::ios::binary);
-        if (!f) throw std::runtime_error("cannot write " + tmp);
-        f.write(text.data(), (std::streamsize)text.size());
-        f.flush();
-        if (!f) { std::remove(tmp.c_str()); throw std::runtime_error("write error on " + tmp); }
-    }
-    if (std::rename(tmp.c_str(), out_path.c_str()) != 0) { std::remove(tmp.c_str()); throw std::runtime_error("cannot rename " + tmp); }
+    write_file_atomically(out_path, text);
 }
 }  // namespace ksp
 
@@ -341,7 +310,7 @@ extern "C" int ksp_edges_degrees(int device, uint32_t n_nodes, const ksp_edge* d
                                  int dist_col, double threshold, uint32_t* h_degree) {
     if (const int rc = check_edges_args("ksp_edges_degrees", d_edges, n_edges, d_kmer_counts, dist_col, threshold)) return rc;
     if (n_nodes && !h_degree) { ksp::set_error("ksp_edges_degrees: NULL argument"); return KSP_E_ARG; }
-    if (const int rc = set_device("ksp_edges_degrees", device)) return rc;
+    if (const int rc = ksp::set_device("ksp_edges_degrees", device)) return rc;
     return ksp::repr_edges_on_device(n_nodes, d_edges, n_edges, d_kmer_counts, dist_col, threshold, h_degree, nullptr, nullptr, nullptr);
 }
 
@@ -349,7 +318,7 @@ extern "C" int ksp_edges_repr(int device, uint32_t n_nodes, const ksp_edge* d_ed
                               int dist_col, double threshold, uint32_t* h_node, uint32_t* h_count, uint32_t* n_ranked) {
     if (const int rc = check_edges_args("ksp_edges_repr", d_edges, n_edges, d_kmer_counts, dist_col, threshold)) return rc;
     if (!n_ranked || (n_nodes && (!h_node || !h_count))) { ksp::set_error("ksp_edges_repr: NULL argument"); return KSP_E_ARG; }
-    if (const int rc = set_device("ksp_edges_repr", device)) return rc;
+    if (const int rc = ksp::set_device("ksp_edges_repr", device)) return rc;
     return ksp::repr_edges_on_device(n_nodes, d_edges, n_edges, d_kmer_counts, dist_col, threshold, nullptr, h_node, h_count, n_ranked);
 }
 
@@ -360,6 +329,7 @@ extern "C" int kspider_repr_sketches(const char* pairwise_tsv, const char* dist_
     if (const int rc = dist_column("kspider_repr_sketches", dist_type, &col)) return rc;
     const std::string path = pairwise_tsv;
     int rc = KSP_OK;
+    ksp::DeviceArena A;
     u32 *d_a = nullptr, *d_b = nullptr;
     try {
         // the rows that pass the text test, as the reference reads them: columns 0 and 1 and the chosen column
@@ -414,15 +384,10 @@ extern "C" int kspider_repr_sketches(const char* pairwise_tsv, const char* dist_
         const u64 M = ea.size();
         std::vector<u32> node((size_t)N), count((size_t)N);
         u32 n_ranked = 0;
-        int device = 0;
-        if (const char* dv = std::getenv("KSPIDER_DEVICE")) device = std::atoi(dv);
-        if ((rc = set_device("kspider_repr_sketches", device))) return rc;
+        if ((rc = ksp::set_device("kspider_repr_sketches", ksp::device_from_env()))) return rc;
         if (M) {
-            RP_HIP(hipMalloc((void**)&d_a, M * 4));
-            RP_HIP(hipMalloc((void**)&d_b, M * 4));
-            RP_HIP(hipMemcpy(d_a, ea.data(), M * 4, hipMemcpyHostToDevice));
-            RP_HIP(hipMemcpy(d_b, eb.data(), M * 4, hipMemcpyHostToDevice));
-            if ((rc = degrees_on_device(N, nullptr, d_a, d_b, M, nullptr, 0, 0.0f, nullptr, node.data(), count.data(), &n_ranked))) goto done;
+            if ((rc = ksp::upload_pairs(A, ea.data(), eb.data(), M, &d_a, &d_b))) return rc;
+            if ((rc = degrees_on_device(N, nullptr, d_a, d_b, M, nullptr, 0, 0.0f, nullptr, node.data(), count.data(), &n_ranked))) return rc;
         }
         ksp::write_repr_file(out_path && *out_path ? out_path : "", ids, node.data(), count.data(), n_ranked);
     } catch (const RowError& e) {
@@ -435,8 +400,5 @@ extern "C" int kspider_repr_sketches(const char* pairwise_tsv, const char* dist_
         ksp::set_error(std::string("kspider_repr_sketches: ") + e.what());
         rc = KSP_E_IO;
     }
-done:
-    if (d_a) (void)hipFree(d_a);
-    if (d_b) (void)hipFree(d_b);
     return rc;
 }

@@ -25,6 +25,7 @@
 
 #include "../../include/kspider_amd.h"
 #include "cc_kernels.hip.h"
+#include "device_call.h"
 #include "edge_cut.hip.h"
 #include "engine_internal.h"
 
@@ -159,16 +160,6 @@ __global__ __launch_bounds__(kSweepThreads) void k_sweep_scatter(const In in, co
     }
 }
 
-#define SW_HIP(call)                                                                     \
-    do {                                                                                 \
-        hipError_t err__ = (call);                                                       \
-        if (err__ != hipSuccess) {                                                       \
-            ksp::set_error(std::string(#call) + ": " + hipGetErrorString(err__));        \
-            rc = KSP_E_HIP;                                                              \
-            goto done;                                                                   \
-        }                                                                                \
-    } while (0)
-
 // The ladder of one call: the cut-offs in order of strictness.
 struct Ladder {
     u32 K = 0, n0 = 0;                // cut-offs; those of mode 0
@@ -190,37 +181,11 @@ void make_ladder(const double* cutoffs, const u32 K, Ladder& L) {
     }
 }
 
-// workgroups of both passes: one per chunk up to 8 per CU, the rest by the chunk loop; `cap_env` = $KSP_SWEEP_MAX_WORKGROUPS of this call
-long long sweep_cap_from_env() {
-    const char* mw = std::getenv("KSP_SWEEP_MAX_WORKGROUPS");   // tests / diagnostics: a small grid, so that every workgroup loops
-    return mw ? std::atoll(mw) : 0;
-}
-int sweep_grid(const u64 n_chunks, const long long cap_env, unsigned* grid) {
-    int device = 0, cus = 0;
-    if (hipGetDevice(&device) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
-        ksp::set_error("sweep: cannot read the device's CU count");
-        return KSP_E_HIP;
-    }
-    const u64 cap = cap_env >= 1 ? (u64)cap_env : 8ull * (u64)std::max(cus, 1);
-    *grid = (unsigned)std::max<u64>(1, std::min<u64>(std::min<u64>(n_chunks, cap), 0x7FFFFFFFull));
-    return KSP_OK;
-}
-
-int set_device(const char* who, const int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { ksp::set_error(std::string(who) + ": no such device"); return KSP_E_HIP; }
-    if (hipSetDevice(device) != hipSuccess) { ksp::set_error(std::string(who) + ": hipSetDevice"); return KSP_E_HIP; }
-    return KSP_OK;
-}
-
-// `bytes` more of device memory, or KSP_E_LIMIT
-int sweep_fits(const char* who, const u64 bytes) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { ksp::set_error(std::string(who) + ": hipMemGetInfo"); return KSP_E_HIP; }
-    if (bytes > (u64)free_b) {
-        ksp::set_error(std::string(who) + ": needs " + std::to_string(bytes) + " bytes of device memory, " + std::to_string(free_b) + " are free");
-        return KSP_E_LIMIT;
-    }
+// workgroups of both passes: one per chunk up to 8 per CU, the rest by the chunk loop; $KSP_SWEEP_MAX_WORKGROUPS (tests)
+int sweep_grid(const u64 n_chunks, unsigned* grid) {
+    ksp::WorkgroupCap g;
+    if (const int rc = ksp::workgroup_cap("KSP_SWEEP_MAX_WORKGROUPS", "sweep", g)) return rc;
+    *grid = g.grid_of(n_chunks);
     return KSP_OK;
 }
 
@@ -235,7 +200,7 @@ void band_offsets(const unsigned long long* hist, const u32 K, u64* off, unsigne
 }
 
 // Levels and histogram of the records on the CURRENT device: d_level[n], h_hist[K + 1].  d_meta is written here.
-int level_on_device(const ksp_edge* d_edges, const u64 n, const u32* d_cnt, const int col, const Ladder& L, const long long cap_env, SweepMeta* d_meta,
+int level_on_device(const ksp_edge* d_edges, const u64 n, const u32* d_cnt, const int col, const Ladder& L, SweepMeta* d_meta,
                     uint8_t* d_level, unsigned long long* h_hist) {
     int rc = KSP_OK;
     unsigned grid = 1;
@@ -244,29 +209,28 @@ int level_on_device(const ksp_edge* d_edges, const u64 n, const u32* d_cnt, cons
     std::memset(hm.data(), 0, sizeof(SweepMeta));
     std::memcpy(hm[0].crit, L.crit, sizeof(float) * L.n0);
     std::fill(h_hist, h_hist + L.K + 1, 0ull);
-    SW_HIP(hipMemcpy(d_meta, hm.data(), sizeof(SweepMeta), hipMemcpyHostToDevice));
+    KSP_TRY_HIP(hipMemcpy(d_meta, hm.data(), sizeof(SweepMeta), hipMemcpyHostToDevice));
     if (n == 0) return KSP_OK;
-    if ((rc = sweep_grid(n_chunks, cap_env, &grid))) return rc;
+    if ((rc = sweep_grid(n_chunks, &grid))) return rc;
     hipLaunchKernelGGL(k_sweep_level, dim3(grid), dim3(kSweepThreads), 0, nullptr, d_edges, n, n_chunks, d_cnt, col, (const SweepMeta*)d_meta, L.n0, L.K, d_level,
                        d_meta->hist);
-    SW_HIP(hipGetLastError());
-    SW_HIP(hipMemcpy(h_hist, d_meta->hist, sizeof(unsigned long long) * (L.K + 1), hipMemcpyDeviceToHost));
+    KSP_TRY_HIP(hipGetLastError());
+    KSP_TRY_HIP(hipMemcpy(h_hist, d_meta->hist, sizeof(unsigned long long) * (L.K + 1), hipMemcpyDeviceToHost));
 done:
     return rc;
 }
 
 // The edges of level >= 1 into their bands on the CURRENT device; h_cursor[K + 1] = the band offsets (band_offsets).
 template <class In>
-int scatter_on_device(const In in, const uint8_t* d_level, const u64 n, const u32 K, const unsigned long long* h_cursor, const long long cap_env,
-                      SweepMeta* d_meta, u32* d_a, u32* d_b) {
+int scatter_on_device(const In in, const uint8_t* d_level, const u64 n, const u32 K, const unsigned long long* h_cursor, SweepMeta* d_meta, u32* d_a, u32* d_b) {
     int rc = KSP_OK;
     unsigned grid = 1;
     const u64 n_chunks = (n + kSweepChunkEdges - 1) / kSweepChunkEdges;
     if (n == 0) return KSP_OK;
-    if ((rc = sweep_grid(n_chunks, cap_env, &grid))) return rc;
-    SW_HIP(hipMemcpy(d_meta->cursor, h_cursor, sizeof(unsigned long long) * (K + 1), hipMemcpyHostToDevice));
+    if ((rc = sweep_grid(n_chunks, &grid))) return rc;
+    KSP_TRY_HIP(hipMemcpy(d_meta->cursor, h_cursor, sizeof(unsigned long long) * (K + 1), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_sweep_scatter<In>, dim3(grid), dim3(kSweepThreads), 0, nullptr, in, d_level, n, n_chunks, d_meta->cursor, d_a, d_b);
-    SW_HIP(hipGetLastError());
+    KSP_TRY_HIP(hipGetLastError());
 done:
     return rc;
 }
@@ -278,7 +242,7 @@ int ranks_on_device(const u32 N, const u32* d_a, const u32* d_b, const u64* off,
     const unsigned gn = (N + 255) / 256;
     u32* d_changed = d_meta->changed;
     hipLaunchKernelGGL(k_cc_init, dim3(gn), dim3(256), 0, nullptr, d_parent, N);
-    SW_HIP(hipGetLastError());
+    KSP_TRY_HIP(hipGetLastError());
     // Why continuing on the parent[] of the ranks above is sound, although their edges are never looked at again.
     //   * Before every hook pass every tree is a star: true at the start, and below no hook pass starts before a jump pass
     //     has found nothing left to do.
@@ -300,20 +264,20 @@ int ranks_on_device(const u32 N, const u32* d_a, const u32* d_b, const u64* off,
             const unsigned ge = (unsigned)std::min<u64>((m + 255) / 256, 1u << 16);
             u32 h_changed[2] = {1, 0};
             for (int round = 0; h_changed[0] && round < 10000; ++round) {
-                SW_HIP(hipMemsetAsync(d_changed, 0, 16, nullptr));
+                KSP_TRY_HIP(hipMemsetAsync(d_changed, 0, 16, nullptr));
                 hipLaunchKernelGGL(k_cc_hook, dim3(ge), dim3(256), 0, nullptr, d_a + lo, d_b + lo, m, d_parent, d_changed);
                 h_changed[1] = 1;
                 for (int flat = 0; h_changed[1] && flat < 64; ++flat) {
-                    if (flat) SW_HIP(hipMemsetAsync(d_changed + 1, 0, 4, nullptr));
+                    if (flat) KSP_TRY_HIP(hipMemsetAsync(d_changed + 1, 0, 4, nullptr));
                     hipLaunchKernelGGL(k_cc_jump, dim3(gn), dim3(256), 0, nullptr, d_parent, N, d_changed + 2);
                     hipLaunchKernelGGL(k_cc_jump, dim3(gn), dim3(256), 0, nullptr, d_parent, N, d_changed + 1);
-                    SW_HIP(hipMemcpy(h_changed, d_changed, 8, hipMemcpyDeviceToHost));
+                    KSP_TRY_HIP(hipMemcpy(h_changed, d_changed, 8, hipMemcpyDeviceToHost));
                 }
                 if (h_changed[1]) { ksp::set_error("sweep: the trees did not flatten"); rc = KSP_E_HIP; goto done; }
             }
             if (h_changed[0]) { ksp::set_error("sweep: did not converge"); rc = KSP_E_HIP; goto done; }
         }
-        SW_HIP(hipMemcpyAsync(d_rows + (u64)row_of_rank[r] * N, d_parent, (size_t)N * 4, hipMemcpyDeviceToDevice, nullptr));
+        KSP_TRY_HIP(hipMemcpyAsync(d_rows + (u64)row_of_rank[r] * N, d_parent, (size_t)N * 4, hipMemcpyDeviceToDevice, nullptr));
     }
 done:
     return rc;
@@ -332,16 +296,12 @@ int check_sweep_args(const char* who, const ksp_edge* d_edges, const u64 n_edges
     return KSP_OK;
 }
 
-// what one call holds on the device
+// what one call holds on the device (memory of the call's DeviceArena)
 struct SweepBufs {
     SweepMeta* meta = nullptr;
     uint8_t* level = nullptr;
     u32 *a = nullptr, *b = nullptr, *parent = nullptr, *rows = nullptr;
     u32 *in_a = nullptr, *in_b = nullptr;   // (host-classified form: the uploaded lists)
-    ~SweepBufs() {
-        for (void* p : {(void*)meta, (void*)level, (void*)a, (void*)b, (void*)parent, (void*)rows, (void*)in_a, (void*)in_b})
-            if (p) (void)hipFree(p);
-    }
 };
 
 }  // namespace
@@ -352,30 +312,28 @@ int sweep_edges_on_device(const uint32_t n_nodes, const ksp_edge* d_edges, const
                           const double* cutoffs, const uint32_t n_cutoffs, uint32_t* h_labels, uint64_t* h_kept) {
     int rc = KSP_OK;
     const u32 N = n_nodes, K = n_cutoffs;
-    const long long cap_env = sweep_cap_from_env();
     Ladder L;
     SweepBufs B;
+    ksp::DeviceArena A;
     unsigned long long hist[kSweepLevels] = {}, cursor[kSweepLevels] = {};
     u64 off[kSweepLevels] = {};
     make_ladder(cutoffs, K, L);
-    if ((rc = sweep_fits("sweep", (u64)sizeof(SweepMeta) + n_edges + ((u64)K + 1) * N * 4))) return rc;
-    SW_HIP(hipMalloc((void**)&B.meta, sizeof(SweepMeta)));
-    if (n_edges) SW_HIP(hipMalloc((void**)&B.level, (size_t)n_edges));
-    if ((rc = level_on_device(d_edges, n_edges, d_cnt, col, L, cap_env, B.meta, B.level, hist))) goto done;
+    if ((rc = device_fits("sweep", (u64)sizeof(SweepMeta) + n_edges + ((u64)K + 1) * N * 4, ""))) return rc;
+    if ((rc = A.alloc(&B.meta, 1))) goto done;
+    if (n_edges && (rc = A.alloc(&B.level, (size_t)n_edges))) goto done;
+    if ((rc = level_on_device(d_edges, n_edges, d_cnt, col, L, B.meta, B.level, hist))) goto done;
     band_offsets(hist, K, off, cursor);
-    if ((rc = sweep_fits("sweep", off[K] * 8 + ((u64)K + 1) * N * 4))) goto done;
+    if ((rc = device_fits("sweep", off[K] * 8 + ((u64)K + 1) * N * 4, ""))) goto done;
     if (off[K]) {
-        SW_HIP(hipMalloc((void**)&B.a, (size_t)off[K] * 4));
-        SW_HIP(hipMalloc((void**)&B.b, (size_t)off[K] * 4));
-        if ((rc = scatter_on_device(SweepRecords{d_edges}, B.level, n_edges, K, cursor, cap_env, B.meta, B.a, B.b))) goto done;
+        if ((rc = A.alloc(&B.a, (size_t)off[K])) || (rc = A.alloc(&B.b, (size_t)off[K]))) goto done;
+        if ((rc = scatter_on_device(SweepRecords{d_edges}, B.level, n_edges, K, cursor, B.meta, B.a, B.b))) goto done;
     }
     if (N) {
-        SW_HIP(hipMalloc((void**)&B.parent, (size_t)N * 4));
-        SW_HIP(hipMalloc((void**)&B.rows, (size_t)K * N * 4));
+        if ((rc = A.alloc(&B.parent, (size_t)N)) || (rc = A.alloc(&B.rows, (size_t)K * N))) goto done;
         if ((rc = ranks_on_device(N, B.a, B.b, off, K, L.caller_of, B.meta, B.parent, B.rows))) goto done;
-        SW_HIP(hipMemcpy(h_labels, B.rows, (size_t)K * N * 4, hipMemcpyDeviceToHost));
+        KSP_TRY_HIP(hipMemcpy(h_labels, B.rows, (size_t)K * N * 4, hipMemcpyDeviceToHost));
     } else {
-        SW_HIP(hipDeviceSynchronize());
+        KSP_TRY_HIP(hipDeviceSynchronize());
     }
     if (h_kept)
         for (u32 r = 0; r < K; ++r) h_kept[L.caller_of[r]] = off[K] - off[r];   // the edges of level > r
@@ -388,7 +346,7 @@ extern "C" int ksp_components_edges_sweep(int device, uint32_t n_nodes, const ks
                                           int dist_col, const double* cutoffs, uint32_t n_cutoffs, uint32_t* h_labels, uint64_t* h_kept) {
     if (const int rc = check_sweep_args("ksp_components_edges_sweep", d_edges, n_edges, d_kmer_counts, dist_col, cutoffs, n_cutoffs)) return rc;
     if (n_nodes && !h_labels) { ksp::set_error("ksp_components_edges_sweep: NULL argument"); return KSP_E_ARG; }
-    if (const int rc = set_device("ksp_components_edges_sweep", device)) return rc;
+    if (const int rc = ksp::set_device("ksp_components_edges_sweep", device)) return rc;
     return ksp::sweep_edges_on_device(n_nodes, d_edges, n_edges, d_kmer_counts, dist_col, cutoffs, n_cutoffs, h_labels, h_kept);
 }
 
@@ -407,32 +365,26 @@ extern "C" int ksp_components_sweep(int device, uint32_t n_nodes, const uint32_t
         if (h_level[e] && (h_a[e] >= N || h_b[e] >= N)) { ksp::set_error("ksp_components_sweep: node index out of range"); return KSP_E_ARG; }
         ++hist[h_level[e]];
     }
-    if (const int rc = set_device("ksp_components_sweep", device)) return rc;
+    if (const int rc = ksp::set_device("ksp_components_sweep", device)) return rc;
     if (N == 0) return KSP_OK;
     int rc = KSP_OK;
-    const long long cap_env = sweep_cap_from_env();
     SweepBufs B;
+    ksp::DeviceArena A;
     std::vector<u32> row_of_rank(K);
     std::iota(row_of_rank.begin(), row_of_rank.end(), 0u);
     band_offsets(hist, K, off, cursor);
-    if ((rc = sweep_fits("ksp_components_sweep", (u64)sizeof(SweepMeta) + n_edges * 9 + off[K] * 8 + ((u64)K + 1) * N * 4))) return rc;
-    SW_HIP(hipMalloc((void**)&B.meta, sizeof(SweepMeta)));
-    SW_HIP(hipMemset(B.meta, 0, sizeof(SweepMeta)));
+    if ((rc = ksp::device_fits("ksp_components_sweep", (u64)sizeof(SweepMeta) + n_edges * 9 + off[K] * 8 + ((u64)K + 1) * N * 4, ""))) return rc;
+    if ((rc = A.alloc(&B.meta, 1))) goto done;
+    KSP_TRY_HIP(hipMemset(B.meta, 0, sizeof(SweepMeta)));
     if (off[K]) {
-        SW_HIP(hipMalloc((void**)&B.in_a, (size_t)n_edges * 4));
-        SW_HIP(hipMalloc((void**)&B.in_b, (size_t)n_edges * 4));
-        SW_HIP(hipMalloc((void**)&B.level, (size_t)n_edges));
-        SW_HIP(hipMalloc((void**)&B.a, (size_t)off[K] * 4));
-        SW_HIP(hipMalloc((void**)&B.b, (size_t)off[K] * 4));
-        SW_HIP(hipMemcpy(B.in_a, h_a, (size_t)n_edges * 4, hipMemcpyHostToDevice));
-        SW_HIP(hipMemcpy(B.in_b, h_b, (size_t)n_edges * 4, hipMemcpyHostToDevice));
-        SW_HIP(hipMemcpy(B.level, h_level, (size_t)n_edges, hipMemcpyHostToDevice));
-        if ((rc = scatter_on_device(SweepArrays{B.in_a, B.in_b}, B.level, n_edges, K, cursor, cap_env, B.meta, B.a, B.b))) goto done;
+        if ((rc = ksp::upload_pairs(A, h_a, h_b, n_edges, &B.in_a, &B.in_b))) goto done;
+        if ((rc = A.alloc(&B.level, (size_t)n_edges)) || (rc = A.alloc(&B.a, (size_t)off[K])) || (rc = A.alloc(&B.b, (size_t)off[K]))) goto done;
+        KSP_TRY_HIP(hipMemcpy(B.level, h_level, (size_t)n_edges, hipMemcpyHostToDevice));
+        if ((rc = scatter_on_device(SweepArrays{B.in_a, B.in_b}, B.level, n_edges, K, cursor, B.meta, B.a, B.b))) goto done;
     }
-    SW_HIP(hipMalloc((void**)&B.parent, (size_t)N * 4));
-    SW_HIP(hipMalloc((void**)&B.rows, (size_t)K * N * 4));
+    if ((rc = A.alloc(&B.parent, (size_t)N)) || (rc = A.alloc(&B.rows, (size_t)K * N))) goto done;
     if ((rc = ranks_on_device(N, B.a, B.b, off, K, row_of_rank.data(), B.meta, B.parent, B.rows))) goto done;
-    SW_HIP(hipMemcpy(h_labels, B.rows, (size_t)K * N * 4, hipMemcpyDeviceToHost));
+    KSP_TRY_HIP(hipMemcpy(h_labels, B.rows, (size_t)K * N * 4, hipMemcpyDeviceToHost));
 done:
     return rc;
 }
@@ -444,19 +396,19 @@ extern "C" int ksp_debug_sweep_bands(int device, const ksp_edge* d_edges, uint64
                                      const double* cutoffs, uint32_t n_cutoffs, uint8_t* d_level, uint64_t* h_band_off, uint32_t* d_a, uint32_t* d_b) {
     if (const int rc = check_sweep_args("ksp_debug_sweep_bands", d_edges, n_edges, d_kmer_counts, dist_col, cutoffs, n_cutoffs)) return rc;
     if (!h_band_off || (n_edges && (!d_level || !d_a || !d_b))) { ksp::set_error("ksp_debug_sweep_bands: NULL argument"); return KSP_E_ARG; }
-    if (const int rc = set_device("ksp_debug_sweep_bands", device)) return rc;
+    if (const int rc = ksp::set_device("ksp_debug_sweep_bands", device)) return rc;
     int rc = KSP_OK;
-    const long long cap_env = sweep_cap_from_env();
     Ladder L;
     SweepBufs B;
+    ksp::DeviceArena A;
     unsigned long long hist[kSweepLevels] = {}, cursor[kSweepLevels] = {};
     u64 off[kSweepLevels] = {};
     make_ladder(cutoffs, n_cutoffs, L);
-    SW_HIP(hipMalloc((void**)&B.meta, sizeof(SweepMeta)));
-    if ((rc = level_on_device(d_edges, n_edges, d_kmer_counts, dist_col, L, cap_env, B.meta, d_level, hist))) goto done;
+    if ((rc = A.alloc(&B.meta, 1))) goto done;
+    if ((rc = level_on_device(d_edges, n_edges, d_kmer_counts, dist_col, L, B.meta, d_level, hist))) goto done;
     band_offsets(hist, n_cutoffs, off, cursor);
-    if (off[n_cutoffs] && (rc = scatter_on_device(SweepRecords{d_edges}, d_level, n_edges, n_cutoffs, cursor, cap_env, B.meta, d_a, d_b))) goto done;
-    SW_HIP(hipDeviceSynchronize());
+    if (off[n_cutoffs] && (rc = scatter_on_device(SweepRecords{d_edges}, d_level, n_edges, n_cutoffs, cursor, B.meta, d_a, d_b))) goto done;
+    KSP_TRY_HIP(hipDeviceSynchronize());
     std::copy(off, off + n_cutoffs + 1, h_band_off);
 done:
     return rc;
@@ -469,21 +421,21 @@ extern "C" int ksp_debug_sweep_times(int device, uint32_t n_nodes, const ksp_edg
                                      int dist_col, const double* cutoffs, uint32_t n_cutoffs, int which, int reps, float* ms, uint32_t* h_labels) {
     if (!ms || reps < 1 || which < 0 || which > 1 || !h_labels || !n_nodes) { ksp::set_error("ksp_debug_sweep_times: bad argument"); return KSP_E_ARG; }
     if (const int rc = check_sweep_args("ksp_debug_sweep_times", d_edges, n_edges, d_kmer_counts, dist_col, cutoffs, n_cutoffs)) return rc;
-    if (const int rc = set_device("ksp_debug_sweep_times", device)) return rc;
+    if (const int rc = ksp::set_device("ksp_debug_sweep_times", device)) return rc;
     int rc = KSP_OK;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    SW_HIP(hipEventCreate(&ev0));
-    SW_HIP(hipEventCreate(&ev1));
+    KSP_TRY_HIP(hipEventCreate(&ev0));
+    KSP_TRY_HIP(hipEventCreate(&ev1));
     for (int r = 0; r < reps; ++r) {
-        SW_HIP(hipEventRecord(ev0, nullptr));
+        KSP_TRY_HIP(hipEventRecord(ev0, nullptr));
         if (which == 0) rc = ksp::sweep_edges_on_device(n_nodes, d_edges, n_edges, d_kmer_counts, dist_col, cutoffs, n_cutoffs, h_labels, nullptr);
         else
             for (u32 i = 0; i < n_cutoffs && !rc; ++i)
                 rc = ksp::cc_edges_on_device(n_nodes, d_edges, n_edges, d_kmer_counts, dist_col, cutoffs[i], h_labels + (u64)i * n_nodes, nullptr);
         if (rc) goto done;
-        SW_HIP(hipEventRecord(ev1, nullptr));
-        SW_HIP(hipEventSynchronize(ev1));
-        SW_HIP(hipEventElapsedTime(&ms[r], ev0, ev1));
+        KSP_TRY_HIP(hipEventRecord(ev1, nullptr));
+        KSP_TRY_HIP(hipEventSynchronize(ev1));
+        KSP_TRY_HIP(hipEventElapsedTime(&ms[r], ev0, ev1));
     }
 done:
     if (ev0) (void)hipEventDestroy(ev0);

@@ -31,8 +31,10 @@
 
 #include "../../include/kspider_amd.h"
 #include "cluster_inputs.h"
+#include "device_call.h"
 #include "edge_cut.hip.h"
 #include "engine_internal.h"
+#include "partial_file.h"
 
 typedef uint32_t u32;
 typedef uint64_t u64;
@@ -145,66 +147,30 @@ __global__ void k_tree_jump(u32* __restrict__ parent, const u32 n, u32* __restri
     if (gp != p) { parent[v] = gp; *changed = 1; }
 }
 
-#define TR_HIP(call)                                                                     \
-    do {                                                                                 \
-        hipError_t err__ = (call);                                                       \
-        if (err__ != hipSuccess) {                                                       \
-            ksp::set_error(std::string(#call) + ": " + hipGetErrorString(err__));        \
-            rc = KSP_E_HIP;                                                              \
-            goto done;                                                                   \
-        }                                                                                \
-    } while (0)
-
 // workgroups of the edge passes: one per chunk up to 8 per CU, the rest by the chunk loop; $KSP_TREE_MAX_WORKGROUPS (tests)
 int tree_grid(const u64 n_chunks, unsigned* grid) {
-    const char* mw = std::getenv("KSP_TREE_MAX_WORKGROUPS");
-    const long long cap_env = mw ? std::atoll(mw) : 0;
-    int device = 0, cus = 0;
-    if (hipGetDevice(&device) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
-        ksp::set_error("tree: cannot read the device's CU count");
-        return KSP_E_HIP;
-    }
-    const u64 cap = cap_env >= 1 ? (u64)cap_env : 8ull * (u64)std::max(cus, 1);
-    *grid = (unsigned)std::max<u64>(1, std::min<u64>(std::min<u64>(n_chunks, cap), 0x7FFFFFFFull));
+    ksp::WorkgroupCap g;
+    if (const int rc = ksp::workgroup_cap("KSP_TREE_MAX_WORKGROUPS", "tree", g)) return rc;
+    *grid = g.grid_of(n_chunks);
     return KSP_OK;
 }
 
-int tree_set_device(const char* who, const int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { ksp::set_error(std::string(who) + ": no such device"); return KSP_E_HIP; }
-    if (hipSetDevice(device) != hipSuccess) { ksp::set_error(std::string(who) + ": hipSetDevice"); return KSP_E_HIP; }
-    return KSP_OK;
-}
-
-// what one call holds on the device: 12 bytes per record, 16 bytes per node
+// what one call holds on the device (memory of the call's DeviceArena): 12 bytes per record, 16 bytes per node
 struct TreeBufs {
     u32 *a = nullptr, *b = nullptr, *key = nullptr;   // the records as a structure of arrays
     u32 *parent = nullptr, *next = nullptr;           // the labels and the array the pick kernel writes; swapped every round
     unsigned long long* best = nullptr;               // per root: the best word offered this round; per non-root: the record that merged it
     u32* flags = nullptr;                             // [0] a record was chosen this round, [1] a jump pass changed a parent
-    ~TreeBufs() {
-        for (void* p : {(void*)a, (void*)b, (void*)key, (void*)parent, (void*)next, (void*)best, (void*)flags})
-            if (p) (void)hipFree(p);
-    }
 };
-int tree_alloc(const char* who, const u32 N, const u64 n, TreeBufs& B) {
+int tree_alloc(const char* who, const u32 N, const u64 n, ksp::DeviceArena& A, TreeBufs& B) {
     int rc = KSP_OK;
-    size_t free_b = 0, total_b = 0;
-    const u64 bytes = 12ull * n + 16ull * N + 8;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { ksp::set_error(std::string(who) + ": hipMemGetInfo"); return KSP_E_HIP; }
-    if (bytes > (u64)free_b) {
-        ksp::set_error(std::string(who) + ": needs " + std::to_string(bytes) + " bytes of device memory (12 per record, 16 per node), " + std::to_string(free_b) + " are free");
-        return KSP_E_LIMIT;
-    }
-    TR_HIP(hipMalloc((void**)&B.a, (size_t)n * 4));
-    TR_HIP(hipMalloc((void**)&B.b, (size_t)n * 4));
-    TR_HIP(hipMalloc((void**)&B.key, (size_t)n * 4));
-    TR_HIP(hipMalloc((void**)&B.parent, (size_t)N * 4));
-    TR_HIP(hipMalloc((void**)&B.next, (size_t)N * 4));
-    TR_HIP(hipMalloc((void**)&B.best, (size_t)N * 8));
-    TR_HIP(hipMalloc((void**)&B.flags, 8));
-done:
-    return rc;
+    if ((rc = ksp::device_fits(who, 12ull * n + 16ull * N + 8, "12 per record, 16 per node"))) return rc;
+    for (u32** p : {&B.a, &B.b, &B.key})
+        if ((rc = A.alloc(p, (size_t)n))) return rc;
+    for (u32** p : {&B.parent, &B.next})
+        if ((rc = A.alloc(p, (size_t)N))) return rc;
+    if ((rc = A.alloc(&B.best, (size_t)N)) || (rc = A.alloc(&B.flags, 2))) return rc;
+    return KSP_OK;
 }
 
 // The rounds over B.a / B.b / B.key (n records, N nodes) on the CURRENT device; the forest's record indices in merge order to
@@ -220,24 +186,24 @@ int tree_rounds(const u32 N, const u64 n, TreeBufs& B, const bool preload, u32* 
     int round = 0;
     if ((rc = tree_grid(n_chunks, &ge))) return rc;
     hipLaunchKernelGGL(k_tree_init, dim3(gn), dim3(256), 0, nullptr, B.parent, B.best, N);
-    TR_HIP(hipGetLastError());
+    KSP_TRY_HIP(hipGetLastError());
     for (; h_flags[0] && round < max_rounds; ++round) {
-        TR_HIP(hipMemsetAsync(B.flags, 0, 8, nullptr));
+        KSP_TRY_HIP(hipMemsetAsync(B.flags, 0, 8, nullptr));
         if (round) hipLaunchKernelGGL(k_tree_clear, dim3(gn), dim3(256), 0, nullptr, (const u32*)B.parent, B.best, N);
         if (preload) hipLaunchKernelGGL(k_tree_offer<true>, dim3(ge), dim3(kTreeThreads), 0, nullptr, (const u32*)B.a, (const u32*)B.b, (const u32*)B.key, n, n_chunks, (const u32*)B.parent, B.best);
         else hipLaunchKernelGGL(k_tree_offer<false>, dim3(ge), dim3(kTreeThreads), 0, nullptr, (const u32*)B.a, (const u32*)B.b, (const u32*)B.key, n, n_chunks, (const u32*)B.parent, B.best);
         hipLaunchKernelGGL(k_tree_pick, dim3(gn), dim3(256), 0, nullptr, (const u32*)B.a, (const u32*)B.b, (const u32*)B.parent, (const unsigned long long*)B.best, B.next, N, B.flags);
-        TR_HIP(hipGetLastError());
+        KSP_TRY_HIP(hipGetLastError());
         std::swap(B.parent, B.next);
-        TR_HIP(hipMemcpy(h_flags, B.flags, 4, hipMemcpyDeviceToHost));
+        KSP_TRY_HIP(hipMemcpy(h_flags, B.flags, 4, hipMemcpyDeviceToHost));
         if (!h_flags[0]) continue;   // (nothing chosen: nothing hooked, every tree is still a star)
         // Increasing weights along a path hook a whole chain of roots in one round: flattened completely before the next one,
         // so that parent[x] is the label of x again
         h_flags[1] = 1;
         for (int pass = 0; h_flags[1] && pass < kTreeMaxJumps; ++pass) {
-            TR_HIP(hipMemsetAsync(B.flags + 1, 0, 4, nullptr));
+            KSP_TRY_HIP(hipMemsetAsync(B.flags + 1, 0, 4, nullptr));
             hipLaunchKernelGGL(k_tree_jump, dim3(gn), dim3(256), 0, nullptr, B.parent, N, B.flags + 1);
-            TR_HIP(hipMemcpy(h_flags + 1, B.flags + 1, 4, hipMemcpyDeviceToHost));
+            KSP_TRY_HIP(hipMemcpy(h_flags + 1, B.flags + 1, 4, hipMemcpyDeviceToHost));
         }
         if (h_flags[1]) { ksp::set_error("tree: the hooked roots did not flatten in " + std::to_string(kTreeMaxJumps) + " jump passes"); rc = KSP_E_HIP; goto done; }
     }
@@ -246,8 +212,8 @@ int tree_rounds(const u32 N, const u64 n, TreeBufs& B, const bool preload, u32* 
     {   // the forest: the word of every non-root, best first
         std::vector<u32> parent(N);
         std::vector<unsigned long long> best(N);
-        TR_HIP(hipMemcpy(parent.data(), B.parent, (size_t)N * 4, hipMemcpyDeviceToHost));
-        TR_HIP(hipMemcpy(best.data(), B.best, (size_t)N * 8, hipMemcpyDeviceToHost));
+        KSP_TRY_HIP(hipMemcpy(parent.data(), B.parent, (size_t)N * 4, hipMemcpyDeviceToHost));
+        KSP_TRY_HIP(hipMemcpy(best.data(), B.best, (size_t)N * 8, hipMemcpyDeviceToHost));
         u64 m = 0;
         for (u32 v = 0; v < N; ++v)
             if (parent[v] != v) best[m++] = best[v];
@@ -276,12 +242,13 @@ int tree_edges_on_device(const uint32_t n_nodes, const ksp_edge* d_edges, const 
     if (rounds) *rounds = 0;
     if (n_edges == 0 || n_nodes == 0) { *n_forest = 0; return KSP_OK; }
     TreeBufs B;
+    ksp::DeviceArena A;
     unsigned grid = 1;
     const u64 n_chunks = (n_edges + kTreeChunkEdges - 1) / kTreeChunkEdges;
-    if ((rc = tree_alloc("tree", n_nodes, n_edges, B))) return rc;
+    if ((rc = tree_alloc("tree", n_nodes, n_edges, A, B))) return rc;
     if ((rc = tree_grid(n_chunks, &grid))) return rc;
     hipLaunchKernelGGL(k_tree_prep, dim3(grid), dim3(kTreeThreads), 0, nullptr, d_edges, n_edges, n_chunks, d_cnt, col, B.a, B.b, B.key);
-    TR_HIP(hipGetLastError());
+    KSP_TRY_HIP(hipGetLastError());
     rc = tree_rounds(n_nodes, n_edges, B, preload, h_index, n_forest, rounds);
 done:
     return rc;
@@ -292,7 +259,7 @@ extern "C" int ksp_edges_forest(int device, uint32_t n_nodes, const ksp_edge* d_
                                 uint32_t* h_index, uint32_t* n_forest) {
     if (const int rc = check_forest_args("ksp_edges_forest", n_edges, !d_edges || !d_kmer_counts, h_index, n_forest)) return rc;
     if (dist_col < 3 || dist_col > 5) { ksp::set_error("ksp_edges_forest: dist_col is 3 (min), 4 (avg) or 5 (max containment)"); return KSP_E_ARG; }
-    if (const int rc = tree_set_device("ksp_edges_forest", device)) return rc;
+    if (const int rc = ksp::set_device("ksp_edges_forest", device)) return rc;
     return ksp::tree_edges_on_device(n_nodes, d_edges, n_edges, d_kmer_counts, dist_col, h_index, n_forest);
 }
 
@@ -301,14 +268,15 @@ extern "C" int ksp_forest_ranked(int device, uint32_t n_nodes, const uint32_t* h
     if (const int rc = check_forest_args("ksp_forest_ranked", n_edges, !h_a || !h_b || !h_rank, h_index, n_forest)) return rc;
     for (u64 e = 0; e < n_edges; ++e)
         if (h_a[e] >= n_nodes || h_b[e] >= n_nodes) { ksp::set_error("ksp_forest_ranked: node index out of range"); return KSP_E_ARG; }
-    if (const int rc = tree_set_device("ksp_forest_ranked", device)) return rc;
+    if (const int rc = ksp::set_device("ksp_forest_ranked", device)) return rc;
     if (n_edges == 0) { *n_forest = 0; return KSP_OK; }
     int rc = KSP_OK;
     TreeBufs B;
-    if ((rc = tree_alloc("ksp_forest_ranked", n_nodes, n_edges, B))) return rc;
-    TR_HIP(hipMemcpy(B.a, h_a, (size_t)n_edges * 4, hipMemcpyHostToDevice));
-    TR_HIP(hipMemcpy(B.b, h_b, (size_t)n_edges * 4, hipMemcpyHostToDevice));
-    TR_HIP(hipMemcpy(B.key, h_rank, (size_t)n_edges * 4, hipMemcpyHostToDevice));
+    ksp::DeviceArena A;
+    if ((rc = tree_alloc("ksp_forest_ranked", n_nodes, n_edges, A, B))) return rc;
+    KSP_TRY_HIP(hipMemcpy(B.a, h_a, (size_t)n_edges * 4, hipMemcpyHostToDevice));
+    KSP_TRY_HIP(hipMemcpy(B.b, h_b, (size_t)n_edges * 4, hipMemcpyHostToDevice));
+    KSP_TRY_HIP(hipMemcpy(B.key, h_rank, (size_t)n_edges * 4, hipMemcpyHostToDevice));
     rc = tree_rounds(n_nodes, n_edges, B, true, h_index, n_forest, nullptr);
 done:
     return rc;
@@ -321,17 +289,17 @@ extern "C" int ksp_debug_tree_times(int device, uint32_t n_nodes, const ksp_edge
                                     int which, int reps, float* ms, uint32_t* h_index, uint32_t* n_forest, uint32_t* rounds) {
     if (!ms || reps < 1 || which < 0 || which > 1 || !rounds || !n_nodes || dist_col < 3 || dist_col > 5) { ksp::set_error("ksp_debug_tree_times: bad argument"); return KSP_E_ARG; }
     if (const int rc = check_forest_args("ksp_debug_tree_times", n_edges, !d_edges || !d_kmer_counts, h_index, n_forest)) return rc;
-    if (const int rc = tree_set_device("ksp_debug_tree_times", device)) return rc;
+    if (const int rc = ksp::set_device("ksp_debug_tree_times", device)) return rc;
     int rc = KSP_OK;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    TR_HIP(hipEventCreate(&ev0));
-    TR_HIP(hipEventCreate(&ev1));
+    KSP_TRY_HIP(hipEventCreate(&ev0));
+    KSP_TRY_HIP(hipEventCreate(&ev1));
     for (int r = 0; r < reps; ++r) {
-        TR_HIP(hipEventRecord(ev0, nullptr));
+        KSP_TRY_HIP(hipEventRecord(ev0, nullptr));
         if ((rc = ksp::tree_edges_on_device(n_nodes, d_edges, n_edges, d_kmer_counts, dist_col, h_index, n_forest, which == 0, rounds))) goto done;
-        TR_HIP(hipEventRecord(ev1, nullptr));
-        TR_HIP(hipEventSynchronize(ev1));
-        TR_HIP(hipEventElapsedTime(&ms[r], ev0, ev1));
+        KSP_TRY_HIP(hipEventRecord(ev1, nullptr));
+        KSP_TRY_HIP(hipEventSynchronize(ev1));
+        KSP_TRY_HIP(hipEventElapsedTime(&ms[r], ev0, ev1));
     }
 done:
     if (ev0) (void)hipEventDestroy(ev0);
@@ -426,18 +394,6 @@ void write_newick(std::ostream& f, const std::vector<ksp::TreeRow>& rows, const 
     f << ";\n";
 }
 
-void write_through_partial(const std::string& out, const std::function<void(std::ostream&)>& body) {
-    const std::string tmp = out + ".partial";
-    {
-        std::ofstream f(tmp);
-        if (!f) throw std::runtime_error("cannot write " + tmp);
-        body(f);
-        f.flush();
-        if (!f) { std::remove(tmp.c_str()); throw std::runtime_error("write error on " + tmp); }
-    }
-    if (std::rename(tmp.c_str(), out.c_str()) != 0) { std::remove(tmp.c_str()); throw std::runtime_error("cannot rename " + tmp); }
-}
-
 }  // namespace
 
 namespace ksp {
@@ -467,10 +423,14 @@ void write_tree_files(const std::string& prefix, const std::string& dist, std::v
     std::vector<std::string> created;
     try {
         if (!exists(tsv)) created.push_back(tsv);
-        write_through_partial(tsv, [&](std::ostream& f) { f << table; });
+        write_file_atomically(tsv, table);
         if (newick) {
             if (!exists(nwk)) created.push_back(nwk);
-            write_through_partial(nwk, [&](std::ostream& f) { write_newick(f, rows, name_of); });
+            std::ofstream f;
+            PartialFiles files;
+            files.open(nwk, f);
+            write_newick(f, rows, name_of);
+            files.commit();
         }
     } catch (...) {
         for (const std::string& path : created) std::remove(path.c_str());
@@ -508,9 +468,7 @@ extern "C" int kspider_tree(const char* index_prefix, const char* dist_type, int
             rank[(size_t)e] = weight[(size_t)e] != weight[(size_t)e] ? (u32)distinct.size() : (u32)(std::lower_bound(distinct.begin(), distinct.end(), weight[(size_t)e]) - distinct.begin());
         std::vector<u32> index((size_t)std::min<u64>(N ? N - 1 : 0, n) + 1);
         u32 n_forest = 0;
-        int device = 0;
-        if (const char* dv = std::getenv("KSPIDER_DEVICE")) device = std::atoi(dv);
-        const int rc = ksp_forest_ranked(device, (u32)N, ea.data(), eb.data(), rank.data(), n, index.data(), &n_forest);
+        const int rc = ksp_forest_ranked(ksp::device_from_env(), (u32)N, ea.data(), eb.data(), rank.data(), n, index.data(), &n_forest);
         if (rc) return rc;
         std::vector<ksp::TreeRow> rows;
         for (u32 i = 0; i < n_forest; ++i) {

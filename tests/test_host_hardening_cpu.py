@@ -185,6 +185,20 @@ def test_malformed_signature_and_bin_corpus(exe, oracle_lib, tmp_path):
         assert rc == KSP_E_IO, (name, line)
 
 
+def test_partial_files_commit_or_leave_nothing(exe, tmp_path):
+    """kspider_amd/csrc/partial_file.h, the one place that writes through PATH.partial and renames, driven directly by the
+    sanitizer build: committed files hold their bytes; an exception before the commit, a directory that is not there and a
+    rename that fails (the final name is a directory that is not empty) leave no .partial and no final file behind."""
+    (tmp_path / "d.tsv").mkdir()
+    (tmp_path / "d.tsv" / "keep").write_text("x")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    p = subprocess.run([exe, "partial", str(tmp_path)], capture_output=True, text=True, env=env, timeout=120)
+    assert "AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr and "LeakSanitizer" not in p.stderr, p.stderr[-3000:]
+    assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
+    assert p.stdout.splitlines() == ["ok committed", "ok abandoned", "ok no directory", "ok rename refused"], p.stdout
+    assert sorted(os.listdir(tmp_path)) == ["d.tsv"] and os.listdir(tmp_path / "d.tsv") == ["keep"]
+
+
 def test_multi_device_barrier_returns_on_an_injected_failure_at_every_stage(exe):
     """run_multi's host threads (one per device; kspider_amd/csrc/engine.hip) meet at ksp::FailBarrier sync points.  A
     failure injected into any worker at any of the 12 stages must make EVERY worker return at the sync point behind
