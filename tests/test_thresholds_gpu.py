@@ -2,6 +2,9 @@
 threshold at N - 1, N and N + 1.  Each case compares the whole edge set with a reference (the oracle, or a closed form
 for inputs built by construction) and proves which side of the threshold it took, from the build's stats or from a
 restatement of the bucket function (tests/edge_inputs.py).  Random and config-shaped inputs almost never land here."""
+import os
+import shutil
+
 import numpy as np
 import pytest
 
@@ -471,6 +474,63 @@ def test_counter_width_weighted(oracle_lib, monkeypatch, total):
         assert st["weighted"] and st["n_blocks"] == 2, st
     edges, _ = _run(monkeypatch, {}, keys, offsets, w)   # (default mode: the source order on)
     _same(edges, want, (total, "default"))
+
+
+def _three_weights(total):
+    return [total // 3, total // 3, total - 2 * (total // 3)]
+
+
+@pytest.mark.parametrize("total", [2**31 - 1, 2**31, 2**31 + 1, 2**32 - 2, 2**32 - 1])
+def test_weight_sums_at_the_top_of_the_contract(oracle_lib, monkeypatch, total):
+    """The input of test_counter_width_weighted with weight sums up to 2^32 - 1, the largest the contract of the weighted calls
+    admits (include/kspider_amd.h: every source's weights sum to less than 2^32): the sum fills a 32-bit pair counter, the
+    per-source bound and the blocks' maxima, which only ever choose the counter width.  Through the weighted sketches and through
+    the inverted index the drop-in path feeds the engine."""
+    keys, offsets = E.pair_input(3, 129, 0, 128)
+    w3 = _three_weights(total)
+    w = np.array(w3 + w3, dtype=np.uint32)
+    assert int(w[:3].astype(np.int64).sum()) == total < 2**32
+    want = _edges([(0, 128, total)])
+    assert (_weighted_ref(oracle_lib, keys, offsets, w) == want).all()
+    key_off = np.array([0, 2, 4, 6], dtype=np.uint64)
+    holders = np.array([0, 128] * 3, dtype=np.uint32)
+    for env in ({"KSP_REORDER": "0"}, {"KSP_REORDER": "0", "KSP_NO_SCHED": "1"}, {"KSP_REORDER": "0", "KSP_KEY_GROUPS": "0"}, {}):
+        edges, st = _run(monkeypatch, env, keys, offsets, w)
+        _same(edges, want, (total, env, "sketches"))
+        assert st["weighted"] and (st["n_blocks"] == 2 or not env), st
+        edges, st = engine.pairwise_postings_host(key_off, holders, np.array(w3, dtype=np.uint32), 129)
+        _same(edges, want, (total, env, "postings"))
+
+
+def _limit_index(oracle_lib, prefix, total):
+    """Groups 1 and 2 share three colours whose weights sum to `total`; groups 3 and 4 share one of weight 7."""
+    w3 = _three_weights(total)
+    oracle_lib.write_index(prefix, np.array([0, 2, 4, 6, 8]), np.array([1, 2, 2, 1, 1, 2, 3, 4]), np.array(w3 + [7], dtype=np.uint32),
+                           np.array([1, 2, 3, 4]), np.array([2**32 - 1, 2**32 - 1, 100, 50], dtype=np.uint32))
+
+
+def test_drop_in_weight_sum_limit(oracle_lib, tmp_path):
+    """A group whose colour weights sum to exactly 2^32 - 1 is served; at exactly 2^32 the call is refused with KSP_E_LIMIT and a
+    message that names the limit and the group, leaves nothing behind, and the next call is right."""
+    (tmp_path / "top").mkdir()
+    (tmp_path / "over").mkdir()
+    top, over = str(tmp_path / "top" / "ix"), str(tmp_path / "over" / "ix")
+    _limit_index(oracle_lib, top, 2**32 - 1)
+    _limit_index(oracle_lib, over, 2**32)
+    shutil.copytree(tmp_path / "top", tmp_path / "ref")
+    oracle_lib.ref_pairwise(str(tmp_path / "ref" / "ix"), 1)
+    with open(str(tmp_path / "ref" / "ix") + "_kSpider_pairwise.tsv", "rb") as f:
+        want = f.read()
+    assert want.split(b"\n")[1].split(b"\t")[:3] == [b"1", b"2", b"4294967295"] and want.count(b"\n") == 3
+    before = sorted(os.listdir(tmp_path / "over"))
+    with pytest.raises(engine.KspError) as ei:
+        engine.pairwise(over, 2)
+    assert ei.value.code == engine.KSP_E_LIMIT and "2^32" in str(ei.value) and "group 1" in str(ei.value), str(ei.value)
+    assert sorted(os.listdir(tmp_path / "over")) == before
+    engine.pairwise(top, 2)
+    with open(top + "_kSpider_pairwise.tsv", "rb") as f:
+        assert f.read() == want
+    assert not [n for n in os.listdir(tmp_path / "top") if n.endswith(".partial")]
 
 
 # ---- u16 / u32 source tags at 65 536 sources ------------------------------------------------------------------------
