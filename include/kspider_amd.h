@@ -568,6 +568,65 @@ int kspider_dereplicate(const char* index_prefix, const char* dist_type, double 
 int kspider_pairwise_and_dereplicate(const char* index_prefix, int user_threads, const char* dist_type, double threshold,
                                      const char* out_path);
 
+/* ---- top-k neighbours: each source's best hits, from the edges in HBM ----------------------------------------
+ * The question asked first of a containment matrix: for this source, which are its closest ones, and how close?  The one
+ * result that is bounded (n_nodes x k) however dense the graph is.
+ * ENTRIES: an entry of node v is a record that names v and is no self pair (source_1 != source_2).  Every such record is an
+ * entry of both of its ends, whatever its `shared`; a pair that repeats is listed again; a record naming a node >= n_nodes is
+ * the caller's error and is ignored, as in ksp_components_edges.  ORDER of the entries of v: (1) value descending, (2) a NaN
+ * below every number — a source without k-mers is never somebody's best hit; note that the tree above puts a NaN on TOP,
+ * because a NaN row is kept at every cut-off: here the opposite is right — (3) ties by record index, lower first.  A strict
+ * total order, so the result is unique.  VALUE: the float of column 3, 4 or 5 in single precision exactly as the pairwise
+ * writer computes it; +inf is a number and sorts first.  RESULT: h_count[v] = min(k, entries of v); h_index[v * k + i] for
+ * i < h_count[v] is the record index of the i-th entry in that order; every slot behind h_count[v] is 0xFFFFFFFF.
+ * ksp_edges_topk: d_edges: `n_edges` ksp_edge records in DEVICE memory, in any order, never written; d_kmer_counts and dist_col
+ *   (3 / 4 / 5) as for ksp_components_edges.  h_index (host, n_nodes x k entries) and h_count (host, n_nodes entries).
+ *   KSP_E_ARG for k == 0 or k > KSP_TOPK_MAX_K, a NULL pointer with n_edges > 0, a NULL h_count (or h_index with n_nodes > 0)
+ *   and a column other than 3 / 4 / 5; KSP_E_LIMIT for 2^32 - 1 records or more (the index is half of the 64-bit key and
+ *   0xFFFFFFFF is "none") and, before anything is written to the caller, when
+ *       16 * n_edges + (32 + 4 * k) * n_nodes + 64 bytes + the scratch of rocPRIM's scan over n_nodes + 1 values
+ *   do not fit the device's free memory: one 8-byte key per entry and at most two entries per record; per node its number of
+ *   entries (4), its 64-bit offset (8), its cursor (4), a slot in each of the three class lists (12), its count (4) and its k
+ *   indices.  (ksp_topk_ranked: 12 bytes per edge more, for the uploaded edges.  KSP_TOPK_SELECT=library: 8 bytes per entry
+ *   more, and the sort's scratch.)  Nothing is written to the caller's arrays unless the whole call succeeded.  n_edges = 0:
+ *   all counts 0, all slots 0xFFFFFFFF, no kernel runs.  A node is selected by one of three kernels, by its number of entries
+ *   n and nothing else: n <= KSP_TOPK_WAVE_ENTRIES by one wave, n <= KSP_TOPK_LDS_ENTRIES by one workgroup that sorts the
+ *   segment in LDS (32 KiB, so that two workgroups fit a CU with room to spare), anything larger by one workgroup that keeps
+ *   the best k in LDS and streams the segment through the other KSP_TOPK_LDS_ENTRIES - k slots.  $KSP_TOPK_MAX_WORKGROUPS
+ *   caps every grid (tests); $KSP_TOPK_SELECT=library replaces the three kernels by rocPRIM's segmented radix sort (tests and
+ *   timing: the same result; fewer than 2^32 - 1 entries), any other value than that, "kernels" or "" is KSP_E_ARG.
+ *   KSP_TOPK_CHUNK_EDGES: records per chunk of the edge passes.  The class limits are UNMEASURED design choices: DESIGN.md 7j.
+ * ksp_topk_ranked: the same selection for HOST edges whose values the caller has ranked: a higher h_rank is better, ties go to
+ *   the lower index.  KSP_E_ARG for an endpoint >= n_nodes; the other refusals as above.  The same select kernels run.
+ * kspider_topk: reads what kspider_tree reads, with the same validation and the same refusals (every row is an entry, so every
+ *   row's ids must be rows of .namesMap), each before any file is written; "ani" goes through
+ *   PREFIX_kSpider_pairwise.ani_col.tsv; dist_type NULL / "": "max_cont".  The weight of a row is its text read as a double, a
+ *   NaN the lowest; the host sorts the distinct weights into ranks, the device selects.  Writes out_path (NULL / "":
+ *   PREFIX_kSpider_topk_<dist_type>.tsv) through .partial and a rename, on an error nothing is left behind:
+ *   "source\thit\tneighbour\t<dist_type>", one row per hit, the sources in .namesMap order and their hits 1, 2, ... in order:
+ *   both names from .namesMap, the value as the text stands in the input.  A source without entries has no row.  KSP_E_ARG for
+ *   k == 0, k > KSP_TOPK_MAX_K and an unknown distance.  Device = $KSPIDER_DEVICE (default 0); with $KSPIDER_VERBOSE one line
+ *   reports the records, the hits written and the nodes per class.
+ * kspider_pairwise_and_topk: kspider_pairwise's two TSVs, byte for byte, plus the same file, the selection taken from the
+ *   gathered, sorted edges on the first device (the value text is ksp_format_float of the record's float).  Rows that exist
+ *   only with shared_kmers = 0 (colours of weight 0) are merged in on the host by the same order, with their place in the
+ *   (source_1, source_2) order of all rows as the index.  Every source of the index must be a row of .namesMap.  "ani" is
+ *   refused with KSP_E_ARG, as in the sibling calls.  Works with $KSPIDER_DEVICE / $KSPIDER_DEVICES.  This path orders by the
+ *   FLOAT, which is finer than the 6-digit text kspider_topk reads, so among rows of equal text the two may choose or order
+ *   differently.  Promised instead: per source both files have the same number of rows and the same column of value texts,
+ *   line by line, and a row whose neighbour differs carries a value text that occurs more than once among that source's rows
+ *   of the TSV (tests/test_topk_gpu.py::test_files).                                                                        */
+#define KSP_TOPK_CHUNK_EDGES 2048u
+#define KSP_TOPK_WAVE_ENTRIES 64u
+#define KSP_TOPK_LDS_ENTRIES 4096u
+#define KSP_TOPK_MAX_K 1024u
+int ksp_edges_topk(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
+                   int dist_col, uint32_t k, uint32_t* h_index /* n_nodes x k */, uint32_t* h_count /* n_nodes */);
+int ksp_topk_ranked(int device, uint32_t n_nodes, const uint32_t* h_a, const uint32_t* h_b, const uint32_t* h_rank,
+                    uint64_t n_edges, uint32_t k, uint32_t* h_index, uint32_t* h_count);
+int kspider_topk(const char* index_prefix, const char* dist_type, uint32_t k, const char* out_path);
+int kspider_pairwise_and_topk(const char* index_prefix, int user_threads, const char* dist_type, uint32_t k, const char* out_path);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

@@ -3003,6 +3003,7 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
     if (nd < 1 || nd > 64) { set_error("pairwise: between 1 and 64 devices"); return KSP_E_ARG; }
     AfterJoin* const after = job.after;
     if (job.wants(AfterJoin::kTree) && (after->col < 3 || after->col > 5)) { set_error("pairwise: a tree needs a column 3 / 4 / 5 and room for its result"); return KSP_E_ARG; }
+    if (job.wants(AfterJoin::kTopk) && (after->col < 3 || after->col > 5 || after->k < 1 || after->k > KSP_TOPK_MAX_K)) { set_error("pairwise: top-k needs a column 3 / 4 / 5 and 1 <= k <= KSP_TOPK_MAX_K"); return KSP_E_ARG; }
     if (job.wants(AfterJoin::kSweep) && (!after->cutoffs || after->n_cutoffs < 1 || after->n_cutoffs > KSP_SWEEP_MAX_CUTOFFS)) {
         set_error("pairwise: a cut-off ladder has between 1 and 255 cut-offs");
         return KSP_E_ARG;
@@ -3278,6 +3279,10 @@ static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge**
                         A.rep.assign((size_t)N, 0); A.via.assign((size_t)N, 0); A.node.assign((size_t)N, 0); A.degree.assign((size_t)N, 0);
                         if (run) rc = derep_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.threshold, A.rep.data(), A.via.data(), A.node.data(),
                                                             A.degree.data(), &n_out, &A.derep);
+                        break;
+                    case AfterJoin::kTopk:   // (index: n_sources x k record indices, count: the hits of every source)
+                        A.index.assign((size_t)N * A.k, 0xFFFFFFFFu); A.count.assign((size_t)N, 0);
+                        if (run) rc = topk_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.k, A.index.data(), A.count.data(), &A.topk);
                         break;
                     default:   // kRepr
                         A.node.assign((size_t)N, 0);

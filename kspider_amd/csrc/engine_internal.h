@@ -93,13 +93,27 @@ struct DerepRow {
 };
 // out_path (through out_path.partial and a rename): "source\trepresentative\t<dist>\tneighbours\trank", one row per name
 void write_derep_file(const std::string& out_path, const std::string& dist, const std::vector<DerepRow>& rows, const std::vector<std::string>& name_of);
+// ---- top-k neighbours: each source's best hits from the join's edges (topk.hip) ----
+// what the last selection on this thread did: the nodes selected by the wave, workgroup and stream kernels (all 0 with
+// KSP_TOPK_SELECT=library) and the refills of the stream kernel, summed over its nodes
+struct TopkTrace {
+    uint64_t wave = 0, workgroup = 0, stream = 0, refills = 0;
+};
+// ksp_edges_topk on the CURRENT device (1 <= k <= KSP_TOPK_MAX_K, h_index n_nodes x k, h_count n_nodes); *trace may be NULL
+int topk_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, uint32_t k, uint32_t* h_index,
+                         uint32_t* h_count, TopkTrace* trace = nullptr);
+// out_path (through out_path.partial and a rename): "source\thit\tneighbour\t<dist>", one row per hit, the sources in the order of
+// the names; count[v]: the hits of name v, neighbour / text: the other end and the value text of every hit, flat in that order
+void write_topk_file(const std::string& out_path, const std::string& dist, const std::vector<std::string>& name_of, const std::vector<uint32_t>& count,
+                     const std::vector<uint32_t>& neighbour, const std::vector<std::string>& text);
 // ---- what a job wants from its edges besides the edges themselves: one kind per job ----
 // kCut: only the edges that pass a containment cut are wanted, so every device cuts its own directly after its join and only the
 // kept ones are gathered, sorted and copied.  The other kinds are taken from the sorted edges on the first device, while they
 // are in HBM: the components (cc_edges_on_device), the ranking (repr_edges_on_device), the components at every cut-off of a
-// ladder (sweep_edges_on_device), the maximum spanning forest (tree_edges_on_device), the dereplicated set (derep_edges_on_device).
+// ladder (sweep_edges_on_device), the maximum spanning forest (tree_edges_on_device), the dereplicated set (derep_edges_on_device),
+// the k best hits of every source (topk_edges_on_device).
 struct AfterJoin {
-    enum Kind { kNone, kCluster, kRepr, kCut, kSweep, kTree, kDerep };
+    enum Kind { kNone, kCluster, kRepr, kCut, kSweep, kTree, kDerep, kTopk };
     Kind kind = kNone;
     const uint32_t* kmer_counts = nullptr;   // per (dense) source index
     int col = 0;                             // 3 / 4 / 5; kCluster: also 6 = ANI
@@ -108,6 +122,7 @@ struct AfterJoin {
     double threshold = 0.20;                 // kRepr, kDerep
     const double* cutoffs = nullptr;         // kSweep
     uint32_t n_cutoffs = 0;                  //   1 .. KSP_SWEEP_MAX_CUTOFFS
+    uint32_t k = 0;                          // kTopk: 1 .. KSP_TOPK_MAX_K
     // out
     std::vector<uint32_t> labels;            // kCluster: per source index, the smallest index of its component; kSweep: n_cutoffs such rows
     uint64_t n_kept = 0;                     // kCluster: edges that passed the cut
@@ -117,6 +132,8 @@ struct AfterJoin {
     std::vector<uint32_t> index;             // kTree: the forest's records as indices into the returned (sorted) edges, in merge order
     std::vector<uint32_t> rep, via, degree;  // kDerep: per source index its representative, the assigning record (0xFFFFFFFF: none), its neighbours;
     DerepTrace derep;                        //   the ranks are in `node` (rank[v]); what the selection did
+    TopkTrace topk;                          // kTopk: per source index its hits in `index` (n_sources x k records of the returned edges) and
+                                             //   their number in `count`; what the selection did
 };
 int pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
@@ -145,5 +162,12 @@ int ksp_debug_tree_times(int device, uint32_t n_nodes, const ksp_edge* d_edges, 
 /* (tests) what the last ksp_edges_dereplicate / kspider_dereplicate of this thread did: out[0] the rounds the host dispatched, out[1]
  * the rounds of the tail kernel (0: it did not run), out[2] the live pairs when it took over, out[3] the records that became oriented pairs. */
 int ksp_debug_derep_rounds(uint64_t out[4]);
+/* (tests) what the last ksp_edges_topk / ksp_topk_ranked / kspider_topk of this thread did: out[0] / out[1] / out[2] the nodes selected by
+ * the wave, workgroup and stream kernels (0 with KSP_TOPK_SELECT=library), out[3] the refills of the stream kernel over all its nodes. */
+int ksp_debug_topk_classes(uint64_t out[4]);
+/* (tools/topk_times.py) HIP-event times of `reps` runs of ksp_edges_topk's device part: which 0 = the hand-written select kernels,
+ * 1 = rocprim::segmented_radix_sort_keys and a gather (KSP_TOPK_SELECT=library). */
+int ksp_debug_topk_times(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col,
+                         uint32_t k, int which, int reps, float* ms, uint32_t* h_index, uint32_t* h_count);
 }
 #endif

@@ -28,6 +28,8 @@ void write_sweep_outputs(const std::string&, const std::string&, const double*, 
 void write_tree_files(const std::string&, const std::string&, std::vector<TreeRow>&, const std::vector<std::string>&, bool) {}
 void write_repr_file(const std::string&, const std::vector<uint32_t>&, const uint32_t*, const uint32_t*, uint64_t) {}
 void write_derep_file(const std::string&, const std::string&, const std::vector<DerepRow>&, const std::vector<std::string>&) {}
+void write_topk_file(const std::string&, const std::string&, const std::vector<std::string>&, const std::vector<uint32_t>&, const std::vector<uint32_t>&,
+                     const std::vector<std::string>&) {}
 }  // namespace ksp
 
 extern "C" {
@@ -53,6 +55,18 @@ int ksp_edges_dereplicate(int, uint32_t, const ksp_edge*, uint64_t, const uint32
     return KSP_E_HIP;
 }
 int kspider_dereplicate(const char*, const char*, double, const char*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_edges_topk(int, uint32_t, const ksp_edge*, uint64_t, const uint32_t*, int, uint32_t, uint32_t*, uint32_t*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_topk_ranked(int, uint32_t, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t, uint32_t, uint32_t*, uint32_t*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int kspider_topk(const char*, const char*, uint32_t, const char*) {
     ksp::set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }

@@ -67,13 +67,15 @@ using ksp::AfterJoin;
 //   kSweep    the cluster file at every cut-off of a ladder, from one pass over the edges
 //   kTree     the single-linkage tree: the maximum spanning forest of the edges
 //   kDerep    the dereplicated set: greedy representatives in rank order and the members they stand for
+//   kTopk     the k best hits of every source
 struct PairwiseJob {
     std::string prefix;
     int threads = 1;
     bool ani = false;       // also write the ANI column of `pairwise --estimate-ani` (ks_pairwise.py:29-84; k from PREFIX.extra)
     AfterJoin after;
     std::string dist;       // kSweep, kTree: the distance's name in their file names
-    std::string repr_out;   // kRepr: "" = PREFIX_kSpider_repr_sketches.txt; kDerep: "" = PREFIX_kSpider_dereplicated_<dist>.tsv
+    std::string repr_out;   // kRepr: "" = PREFIX_kSpider_repr_sketches.txt; kDerep: "" = PREFIX_kSpider_dereplicated_<dist>.tsv;
+                            // kTopk: "" = PREFIX_kSpider_topk_<dist>.tsv
     bool newick = false;    // kTree
     PairwiseJob(const char* index_prefix, int user_threads, AfterJoin::Kind kind = AfterJoin::kNone, int col = 0)
         : prefix(index_prefix), threads(user_threads < 1 ? 1 : user_threads) { after.kind = kind; after.col = col; }
@@ -94,6 +96,8 @@ struct Postings {
 // a row that exists only with shared_kmers = 0 (the pair shares colours of weight 0 and no other), by its source indices
 struct ZeroRow { uint32_t a, b; };
 struct ForestEdge { uint32_t a, b; float v; };   // source indices and the column's value
+// kTopk: per source index the number of its hits; the other end (a source index) and the column's value of every hit, flat in source order
+struct TopkHits { std::vector<uint32_t> count, neighbour; std::vector<float> value; };
 
 // column 3 / 4 / 5 of a row as the TSV writer computes it (index_io.cpp format_rows = src/pairwise.cpp:260-264; beside
 // ksp::row_min_max, whose min + max is not c12 + c21 when one of them is a NaN)
@@ -141,7 +145,7 @@ void node_labels_of(const std::vector<uint32_t>& ids, const uint32_t* lab, const
 int load_inputs(const PairwiseJob& job, ksp::IndexData& ix, std::vector<std::string>& derep_names) {
     auto t0 = Clock::now();
     ksp::load_index(job.prefix, ix);
-    if (job.after.kind == AfterJoin::kDerep) {   // every source must be a row of .namesMap: refused before any file is written
+    if (job.after.kind == AfterJoin::kDerep || job.after.kind == AfterJoin::kTopk) {   // every source must be a row of .namesMap: refused before any file is written
         ksp::read_names_map(job.prefix, derep_names);
         for (auto& c : ix.colors)
             for (uint32_t g : c.second) ksp::check_row_nodes(g, g, derep_names.size());
@@ -457,6 +461,84 @@ void finish_derep(PairwiseJob& job, const Postings& P, const std::vector<std::st
                   << " rounds and " << A.derep.tail << " in the tail" << std::endl;
 }
 
+// the order of the top-k definition on (value, place among all rows): value descending, a NaN below every number, lower place first
+bool topk_before(const float vx, const uint64_t ix, const float vy, const uint64_t iy) {
+    const bool nx = vx != vx, ny = vy != vy;
+    if (nx != ny) return ny;
+    if (!nx && vx != vy) return vx > vy;
+    return ix < iy;
+}
+
+// The hits of every source, while the device's records are still here: the device's selection among its records, and the
+// shared-0 rows (value 0, or NaN beside a source of 0 k-mers) merged in by the same order, the index of a row being its place
+// in the (source_1, source_2) order of ALL rows — which keeps the device's records in the order of their own indices.
+TopkHits device_topk(const AfterJoin& A, const Postings& P, const ksp_edge* edges, const uint64_t n_edges, const std::vector<ZeroRow>& zero_rows) {
+    const uint32_t N = (uint32_t)P.ids.size(), k = A.k;
+    TopkHits H;
+    H.count.assign(N, 0);
+    std::vector<std::vector<uint32_t>> zero_of;   // per source index: its shared-0 rows
+    std::vector<uint64_t> zero_place;             // per shared-0 row: its place among all rows
+    if (!zero_rows.empty()) {
+        zero_of.resize(N);
+        zero_place.resize(zero_rows.size());
+        for (size_t z = 0; z < zero_rows.size(); ++z) {
+            const ZeroRow& r = zero_rows[z];
+            zero_of[r.a].push_back((uint32_t)z);
+            zero_of[r.b].push_back((uint32_t)z);
+            zero_place[z] = z + (uint64_t)(std::lower_bound(edges, edges + n_edges, r, [](const ksp_edge& e, const ZeroRow& q) {
+                                               return e.source_1 != q.a ? e.source_1 < q.a : e.source_2 < q.b;
+                                           }) - edges);
+        }
+    }
+    auto place_of = [&](const uint32_t e) -> uint64_t {   // of a device record: the shared-0 rows before it are counted in
+        if (zero_rows.empty()) return e;
+        return e + (uint64_t)(std::lower_bound(zero_rows.begin(), zero_rows.end(), edges[e], [](const ZeroRow& q, const ksp_edge& x) {
+                                  return q.a != x.source_1 ? q.a < x.source_1 : q.b < x.source_2;
+                              }) - zero_rows.begin());
+    };
+    struct Cand { float v; uint64_t place; uint32_t nb; };
+    std::vector<Cand> cand;
+    for (uint32_t i = 0; i < N; ++i) {
+        cand.clear();
+        if (A.count[i] > k) throw std::runtime_error("topk: the device named more hits than were asked");
+        for (uint32_t j = 0; j < A.count[i]; ++j) {
+            const uint32_t e = A.index[(size_t)i * k + j];
+            if (e >= n_edges || (edges[e].source_1 != i && edges[e].source_2 != i)) throw std::runtime_error("topk: the device named a record that is no entry of the source");
+            const ksp_edge& x = edges[e];
+            cand.push_back(Cand{column_value(A.col, x.shared, P.counts[x.source_1], P.counts[x.source_2]), place_of(e), x.source_1 == i ? x.source_2 : x.source_1});
+        }
+        if (!zero_rows.empty() && !zero_of[i].empty()) {
+            for (const uint32_t z : zero_of[i]) {
+                const ZeroRow& r = zero_rows[z];
+                cand.push_back(Cand{column_value(A.col, 0, P.counts[r.a], P.counts[r.b]), zero_place[z], r.a == i ? r.b : r.a});
+            }
+            std::sort(cand.begin(), cand.end(), [](const Cand& x, const Cand& y) { return topk_before(x.v, x.place, y.v, y.place); });
+            if (cand.size() > k) cand.resize(k);
+        }
+        H.count[i] = (uint32_t)cand.size();
+        for (const Cand& c : cand) { H.neighbour.push_back(c.nb); H.value.push_back(c.v); }
+    }
+    return H;
+}
+
+// the file: the sources of the index are rows of .namesMap (checked before the first file); a row without a source has no hit
+void finish_topk(PairwiseJob& job, const Postings& P, const TopkHits& H, const std::vector<std::string>& name_of, const uint64_t n_edges) {
+    const AfterJoin& A = job.after;
+    std::vector<uint32_t> count(name_of.size(), 0), neighbour;
+    std::vector<std::string> text;
+    for (uint32_t i = 0; i < (uint32_t)P.ids.size(); ++i) count[P.ids[i] - 1] = H.count[i];   // (index order is id order: the flat hits stay in place)
+    for (size_t h = 0; h < H.neighbour.size(); ++h) {
+        char buf[64];
+        buf[ksp::format_float(buf, H.value[h])] = 0;
+        neighbour.push_back(P.ids[H.neighbour[h]] - 1);
+        text.push_back(buf);
+    }
+    ksp::write_topk_file(job.repr_out.empty() ? job.prefix + "_kSpider_topk_" + job.dist + ".tsv" : job.repr_out, job.dist, name_of, count, neighbour, text);
+    if (std::getenv("KSPIDER_VERBOSE"))
+        std::cout << "kspider_amd: top " << A.k << " of " << n_edges << " records: " << neighbour.size() << " hits written; nodes selected by wave / workgroup / stream kernel: "
+                  << A.topk.wave << " / " << A.topk.workgroup << " / " << A.topk.stream << std::endl;
+}
+
 // Mirrors src/pairwise.cpp:123-276 phase by phase (the head of this file), with what job.after asks for between the join and the files.
 int run_job(PairwiseJob& job) {
     AfterJoin& A = job.after;
@@ -502,6 +584,8 @@ int run_job(PairwiseJob& job) {
     if (A.kind == AfterJoin::kDerep) derep_text = derep_texts(A, P, edges.get(), n_edges);
     std::vector<ksp::EdgeRow> rows;
     const std::vector<ZeroRow> zero_rows = merge_rows(ix, P, A, edges.get(), n_edges, rows);
+    TopkHits topk_hits;
+    if (A.kind == AfterJoin::kTopk) topk_hits = device_topk(A, P, edges.get(), n_edges, zero_rows);
     edges.reset();
     if (job.ani && (rc = refuse_nan_rows(rows, kmer_count)) != KSP_OK) return rc;   // before anything of it is written
     std::cout << "pairwise hashmap construction: " << t_transpose + since(t0) << " secs" << std::endl;
@@ -529,6 +613,7 @@ int run_job(PairwiseJob& job) {
         case AfterJoin::kSweep: finish_sweep(job, P, zero_rows, n_edges); break;
         case AfterJoin::kTree: finish_tree(job, P, zero_rows, n_edges, forest); break;
         case AfterJoin::kDerep: finish_derep(job, P, derep_text, derep_names); break;
+        case AfterJoin::kTopk: finish_topk(job, P, topk_hits, derep_names, n_edges); break;
     }
     return KSP_OK;
 }
@@ -633,6 +718,22 @@ extern "C" int kspider_pairwise_and_dereplicate(const char* index_prefix, int us
     job.after.threshold = threshold;
     if (out_path) job.repr_out = out_path;
     return guarded("kspider_pairwise_and_dereplicate", true, job);
+}
+
+extern "C" int kspider_pairwise_and_topk(const char* index_prefix, int user_threads, const char* dist_type, uint32_t k, const char* out_path) {
+    if (!index_prefix) { ksp::set_error("kspider_pairwise_and_topk: index_prefix is NULL"); return KSP_E_ARG; }
+    if (k == 0 || k > KSP_TOPK_MAX_K) { ksp::set_error("kspider_pairwise_and_topk: k is 1 .. " + std::to_string(KSP_TOPK_MAX_K)); return KSP_E_ARG; }
+    std::string dt;
+    const int col = dist_column(dist_type, "max_cont", &dt);
+    if (!col) {
+        ksp::set_error("kspider_pairwise_and_topk: distance '" + dt + "' is not min_cont, avg_cont or max_cont (ani needs the separate ANI column file: run kspider_topk)");
+        return KSP_E_ARG;
+    }
+    PairwiseJob job(index_prefix, user_threads, AfterJoin::kTopk, col);
+    job.dist = dt;
+    job.after.k = k;
+    if (out_path) job.repr_out = out_path;
+    return guarded("kspider_pairwise_and_topk", true, job);
 }
 
 extern "C" int kspider_pairwise_cut(const char* index_prefix, int user_threads, const char* dist_type, double cutoff) {

@@ -33,6 +33,13 @@ TREE_CHUNK_EDGES = 2048
 DEREP_CHUNK_EDGES = 2048
 DEREP_TAIL_PAIRS = 65536
 
+#: top-k neighbours (KSP_TOPK_* in the header): records per chunk of the edge passes; the entries up to which a node is selected
+#: by one wave, and by one workgroup in LDS (anything larger is streamed); the largest k
+TOPK_CHUNK_EDGES = 2048
+TOPK_WAVE_ENTRIES = 64
+TOPK_LDS_ENTRIES = 4096
+TOPK_MAX_K = 1024
+
 #: every symbol include/kspider_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "ksp_last_error", "ksp_device_count", "ksp_engine_create", "ksp_engine_destroy",
@@ -57,6 +64,7 @@ ABI_SYMBOLS = [
     "ksp_components_edges_sweep", "ksp_components_sweep", "kspider_cluster_sweep", "kspider_pairwise_and_cluster_sweep",
     "ksp_edges_forest", "ksp_forest_ranked", "kspider_tree", "kspider_pairwise_and_tree", "kspider_cluster_from_tree",
     "ksp_edges_dereplicate", "kspider_dereplicate", "kspider_pairwise_and_dereplicate",
+    "ksp_edges_topk", "ksp_topk_ranked", "kspider_topk", "kspider_pairwise_and_topk",
 ]
 
 
@@ -215,6 +223,13 @@ def lib():
         L.kspider_dereplicate.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double, ctypes.c_char_p]
         L.kspider_pairwise_and_dereplicate.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_double, ctypes.c_char_p]
         L.ksp_debug_derep_rounds.argtypes = [ctypes.c_void_p]
+        L.ksp_edges_topk.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32,
+                                     ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_topk_ranked.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                      ctypes.c_void_p, ctypes.c_void_p]
+        L.kspider_topk.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p]
+        L.kspider_pairwise_and_topk.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p]
+        L.ksp_debug_topk_classes.argtypes = [ctypes.c_void_p]
         _lib = L
     return _lib
 
@@ -551,6 +566,66 @@ def pairwise_and_dereplicate(index_prefix: str, user_threads: int = 1, dist_type
     """`pairwise` plus the file of `dereplicate`, the selection taken from the edges while they are in HBM."""
     _check(lib().kspider_pairwise_and_dereplicate(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
                                                   float(threshold), os.fsencode(out_path) if out_path else None))
+
+
+def _topk_k(k) -> int:
+    k = int(k)
+    if not 0 <= k <= 0xFFFFFFFF:
+        raise ValueError("k does not fit 32 bits")
+    return k
+
+
+def _topk_out(who, n_nodes, k, tail, fill, call):
+    room = n_nodes * k
+    index = np.full(room + tail, fill, dtype=np.uint32)
+    count = np.full(n_nodes + tail, fill, dtype=np.uint32)
+    _check(call(index.ctypes.data if (room + tail) else None, count.ctypes.data if (n_nodes + tail) else None))
+    if tail and ((index[room:] != fill).any() or (count[n_nodes:] != fill).any()):
+        raise AssertionError(f"{who} wrote behind its arrays")
+    return index[:room].reshape(n_nodes, k).copy(), count[:n_nodes].copy()
+
+
+def edges_topk(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, dist_col: int = 5, k: int = 5, device: int = 0,
+               tail: int = 0, fill: int = 0) -> tuple:
+    """The k best hits of every node among ksp_edge records in DEVICE memory (include/kspider_amd.h): (index, count), index[v, i] for
+    i < count[v] the record index of the i-th entry of v by (value descending, NaN last, lower index first), 0xFFFFFFFF behind.
+    tail / fill (tests): that many entries of `fill` are kept behind both arrays and checked to be untouched."""
+    k = _topk_k(k)
+    return _topk_out("ksp_edges_topk", n_nodes, k, tail, fill, lambda pi, pc: lib().ksp_edges_topk(
+        device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, int(dist_col), k, pi, pc))
+
+
+def topk_ranked(n_nodes: int, a: np.ndarray, b: np.ndarray, rank: np.ndarray, k: int = 5, device: int = 0, tail: int = 0, fill: int = 0) -> tuple:
+    """The same selection for host edges whose values are already ranked: a higher rank is better, ties go to the lower index."""
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    rank = np.ascontiguousarray(rank, dtype=np.uint32)
+    if not (a.size == b.size == rank.size):
+        raise ValueError("a, b and rank need one entry per edge")
+    k = _topk_k(k)
+    return _topk_out("ksp_topk_ranked", n_nodes, k, tail, fill, lambda pi, pc: lib().ksp_topk_ranked(
+        device, n_nodes, a.ctypes.data, b.ctypes.data, rank.ctypes.data, a.size, k, pi, pc))
+
+
+def topk_classes() -> dict:
+    """(tests) What the last top-k selection of this thread did (ksp_debug_topk_classes, csrc/engine_internal.h): the nodes selected by
+    the wave, workgroup and stream kernels, and the refills of the stream kernel over all its nodes."""
+    out = np.zeros(4, dtype=np.uint64)
+    _check(lib().ksp_debug_topk_classes(out.ctypes.data))
+    return dict(wave=int(out[0]), workgroup=int(out[1]), stream=int(out[2]), refills=int(out[3]))
+
+
+def topk(index_prefix: str, dist_type: str = "max_cont", k: int = 5, out_path: str | None = None) -> None:
+    """The k best hits of every source of the pairwise TSV: PREFIX_kSpider_topk_<DIST>.tsv (or out_path), one row per hit with both
+    names of .namesMap and the value as it stands in the TSV; the selection runs on the GPU."""
+    _check(lib().kspider_topk(os.fsencode(index_prefix), dist_type.encode() if dist_type is not None else None, _topk_k(k),
+                              os.fsencode(out_path) if out_path else None))
+
+
+def pairwise_and_topk(index_prefix: str, user_threads: int = 1, dist_type: str = "max_cont", k: int = 5, out_path: str | None = None) -> None:
+    """`pairwise` plus the file of `topk`, the selection taken from the edges while they are in HBM."""
+    _check(lib().kspider_pairwise_and_topk(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
+                                           _topk_k(k), os.fsencode(out_path) if out_path else None))
 
 
 def cluster_from_tree(index_prefix: str, dist_type: str = "max_cont", cutoff: float = 0.0) -> None:
