@@ -158,6 +158,11 @@ int ksp_engine_join_to_host(ksp_engine* e, uint64_t tile_begin, uint64_t tile_en
                             uint64_t* h_count, void* stream);
 
 int ksp_engine_get_stats(const ksp_engine* e, ksp_stats* out);
+/* How the last build made its block lists (diagnostics / tests): 0 no lists (nothing built, an empty build, assembled
+ * slices), 1 the keyed split straight from the per-key group records, 2 the compacting chain (group records packed into
+ * rank order first: KSP_MOVE=1, weighted or sparse inputs, more than 256 blocks), 3 the entries sorted by block,
+ * 4 the bucket-resident stage 1 (KSP_FUSED=1).                                                                        */
+int ksp_engine_lists_path(const ksp_engine* e, int* out);
 /* Per-phase HIP-event times of stage 1 (the reference's own phase timers, src/pairwise.cpp:131-133,155,181,
  * 239, print wall-clock seconds per phase; this is their device-side counterpart).  set_profiling(1) makes
  * every later build record one event per phase start; phase_times returns the phases of the last build:

@@ -154,6 +154,11 @@ struct ksp_engine {
     bool rank1_ok = false;        // R1 holds a rank per kept entry (sort path, postings input; the bucket grouping only writes crank)
     ksp::Buf pmask;               // the membership mask of every list word at its list position (written by k_ms_place)
     bool pmask_on = false;        // ... of the lists the engine holds
+    bool move_forced = false;     // KSP_MOVE=1 when the engine was created: always the compacting chain (k_move_groups), never the keyed split
+    bool keyed_off = false;       // a build needed the group records in rank order (match records, no positional masks): the compacting chain from now on
+    bool keyed_lists = false;     // this build's lists came from the keyed split (k_msk_*): tile flags and diagonal work were written with them
+    bool masks_in_gm = false;     // ... and its posting words index the masks where k_key_groups parked them (gm), not mm
+    int lists_path = 0;           // how the last build made its block lists (ksp_engine_lists_path)
     bool scal_fresh = false;      // h_scal[1 .. 11] hold the finished build's values (read back before its last kernels were queued)
     u64 gp_stride = 0;            // gp: gp_stride record values (u64), then as many blocks, ranks and sorted blocks (u32)
     bool reorder = true;          // order the sources by shared-key label before cutting blocks (KSP_REORDER=0: off)
@@ -241,6 +246,8 @@ struct ksp_engine {
 namespace ksp {
 
 static inline unsigned grid_for(u64 n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
+// the 128-bit masks the posting words of the engine's lists index
+static inline uint4* list_masks(const ksp_engine* e) { return e->masks_in_gm ? e->gm.as<uint4>() : e->mm.as<uint4>(); }
 
 // wait for the read-back behind which e->ev_rb was recorded (later kernels may already be queued on the stream)
 static inline hipError_t wait_readback(ksp_engine* e) {
@@ -642,16 +649,78 @@ template <class V> int Stage1<V>::lists_by_key(bool& done) {
         if (huge_list)
             hipLaunchKernelGGL((k_key_groups_huge<V, W>), dim3(256), dim3(256), 0, st, VA, firstp, newidx, nb, gsum, blk0,
                                info0, mask0, tmp_blk, tmp_info, tmp_mask, wkey, d_kovf, huge_list);
-        {   // goff = exclusive prefix sums of gsum, the totals to scal[1] / scal[7] (stage1_kernels: k_pair_*)
-            const u32 ntiles = grid_for(U, PS_TILE);
-            if ((rc = e->tmp.ensure(((size_t)ntiles + 2) * 8))) return rc;
-            hipLaunchKernelGGL(k_pair_tile_sums, dim3(ntiles), dim3(PS_THREADS), 0, st, gsum, U, (u64*)e->tmp.p);
-            hipLaunchKernelGGL(k_pair_scan_tiles, dim3(ntiles), dim3(PS_THREADS), 0, st, gsum, goff, U, (const u64*)e->tmp.p, scal);
+        const u32 ntiles = grid_for(U, PS_TILE);   // (stage1_kernels: k_pair_*)
+        if ((rc = e->tmp.ensure(((size_t)ntiles + 2) * 8))) return rc;
+        hipLaunchKernelGGL(k_pair_tile_sums, dim3(ntiles), dim3(PS_THREADS), 0, st, gsum, U, (u64*)e->tmp.p);
+        const u64 Kcap = m;
+        const char* msv = std::getenv("KSP_MS");   // 0: the library sort, 1024: the large tables (diagnostic / tests)
+        // The keyed split (stage1_kernels: k_msk_*) makes the lists from the parked records as they are: unweighted whole
+        // builds of up to 256 blocks whose lists get positional masks.  Its histogram carries the totals to the host; a build
+        // that turns out to need the records in rank order (match records, sparse sharing) goes on with the compacting chain
+        // below, and so does every later build of this engine.
+        bool totals_known = false;
+        if (!W && phase == 0 && !post_in && nb <= 256 && !e->keyed_off && !e->move_forced && !(msv && (std::atoi(msv) == 0 || std::atoi(msv) == 1024)) &&
+            (u64)U + m / 4 + 16 < (1u << 29)) {
+            const u32 kchunks = grid_for(U, MSK_KEYS);
+            const u64 Tt = (u64)nb * (nb + 1) / 2;
+            const size_t bit_words = (size_t)(((Tt + 63) / 64) * 2 + 2);
+            if ((rc = e->dwork.ensure(((size_t)nb + 2) * 8))) return rc;
+            if ((rc = e->tbits.ensure(bit_words * 4 + Tt + 64))) return rc;
+            if ((rc = e->ms_hist.ensure(((size_t)kchunks * 513 + 512) * 4 + 4096))) return rc;
+            if (!e->pre_zeroed_work) { KSP_HIP(hipMemsetAsync(e->dwork.p, 0, ((size_t)nb + 2) * 8, st)); e->pre_zeroed_work = true; }
+            if (!e->pre_zeroed_bits) { KSP_HIP(hipMemsetAsync(e->tbits.p, 0, bit_words * 4 + Tt + 64, st)); e->pre_zeroed_bits = true; }
+            u32* hist = e->ms_hist.as<u32>();
+            u32 *wk = hist + (size_t)kchunks * 256, *hold = wk + (size_t)kchunks * 256, *tot = hold + kchunks;
+            unsigned char* flags = (unsigned char*)e->tbits.p + bit_words * 4;
+            phase_mark(e, st, "block lists");
+            const Rider rbk = ride_readback(e, st, scal + 1, e->h_scal + 1, 11);   // [1] groups ... [11] overflow: with k_msk_hist
+            hipLaunchKernelGGL(k_msk_hist, dim3(kchunks), dim3(MS_THREADS), 0, st, gsum, firstp, blk0, info0, mask0, tmp_blk, tmp_info, U, nb,
+                               (const u64*)e->tmp.p, ntiles, scal, hist, wk, hold, flags, rbk);
+            hipLaunchKernelGGL(k_msk_scan, dim3(nb + 1), dim3(256), 0, st, hist, wk, hold, kchunks, scal, tot, blk_raw, blk_pos, nb,
+                               e->dwork.as<unsigned long long>());
+            KSP_HIP(wait_readback(e));
+            if ((u32)e->h_scal[11]) {
+                e->key_groups_off = true;   // a key with thousands of holders: this engine sorts by block from now on
+                return KSP_OK;
+            }
+            const u64 K = std::max<u64>(1, e->h_scal[1]);
+            if (sched_wants_matches(e, K, true) || m < 4 * K) {
+                e->keyed_off = true;
+                totals_known = true;   // (dwork and the tile flags are the compacting chain's to fill)
+                KSP_HIP(hipMemsetAsync(e->dwork.p, 0, ((size_t)nb + 2) * 8, st));
+                KSP_HIP(hipMemsetAsync(e->tbits.p, 0, bit_words * 4 + Tt + 64, st));
+            } else {
+                e->pre_zeroed_work = e->pre_zeroed_bits = false;
+                e->have_dwork = true;
+                e->keyed_lists = true;
+                e->masks_in_gm = true;
+                e->sched_early = false;
+                if (e->early_ok && !e->profiling && e->n_kept && !std::getenv("KSP_DEBUG_LATE_SCHED")) {   // early work list, as below
+                    e->h_scal_words = e->h_scal[1];
+                    e->h_scal_keys = e->h_scal[2];
+                    if ((rc = launch_sched_kernels(e, st, true, true))) return rc;
+                    if (!e->blk_staged && (rc = stage_block_tables(e, st))) return rc;
+                    if (!(e->sched_signalled && e->blk_staged)) { e->sched_signalled = false; KSP_HIP(hipEventRecord(e->ev_sched, st)); }
+                    e->sched_early = true;
+                }
+                if ((rc = e->pmask.ensure((Kcap + (u64)nb * (WIN + 4) + 4 * WIN) * 16))) return rc;
+                hipLaunchKernelGGL(k_msk_place, dim3(kchunks), dim3(MS_THREADS), 0, st, gsum, firstp, blk0, info0, mask0, tmp_blk, tmp_info, U,
+                                   scal, hist, blk_pos, nb, e->bkeys.as<u32>(), e->info.as<u32>(), e->pmask.as<uint4>(), blk_raw, PAD);
+                e->pmask_on = true;
+                shrink_cells_and_index(K);
+                KSP_HIP(hipGetLastError());
+                e->scal_fresh = true;
+                e->lists_path = 1;
+                done = true;
+                return KSP_OK;
+            }
         }
+        // goff = exclusive prefix sums of gsum, the totals to scal[1] / scal[7]
+        hipLaunchKernelGGL(k_pair_scan_tiles, dim3(ntiles), dim3(PS_THREADS), 0, st, gsum, goff, U, (const u64*)e->tmp.p, scal);
         // the number of groups sizes the sort of the groups and what follows; the records themselves are packed (k_move_groups)
         // while the host waits for it: their arrays take the bound K <= m
-        const Rider rb = ride_readback(e, st, scal + 1, e->h_scal + 1, 11);   // [1] groups ... [11] overflow: with k_move_groups
-        const u64 Kcap = m;
+        const Rider rb = totals_known ? Rider{nullptr, nullptr, nullptr, 0, 0}
+                                      : ride_readback(e, st, scal + 1, e->h_scal + 1, 11);   // [1] groups ... [11] overflow: with k_move_groups
         if ((rc = e->gp.ensure((Kcap + 4) * 20))) return rc;
         e->gp_stride = Kcap + 4;
         u64* rec_val = e->gp.as<u64>();
@@ -659,7 +728,7 @@ template <class V> int Stage1<V>::lists_by_key(bool& done) {
         unsigned long long* work = nullptr;
         {
             // (the diagonal work and holder sums of the join's schedule come with the move when the blocks fit its LDS table)
-            phase_mark(e, st, "block lists");
+            if (!totals_known) phase_mark(e, st, "block lists");
             if (nb <= KG_WORK && phase != 2) {
                 if ((rc = e->dwork.ensure(((size_t)nb + 2) * 8))) return rc;
                 if (!e->pre_zeroed_work) KSP_HIP(hipMemsetAsync(e->dwork.p, 0, ((size_t)nb + 2) * 8, st));
@@ -672,14 +741,13 @@ template <class V> int Stage1<V>::lists_by_key(bool& done) {
                                blk0, info0, mask0, tmp_blk, tmp_info, tmp_mask, rec_blk, rec_val, rec_rank, e->mm.as<uint4>(),
                                U, work, nb, d_kovf, rb);
         }
-        KSP_HIP(wait_readback(e));
+        if (!totals_known) KSP_HIP(wait_readback(e));
         if ((u32)e->h_scal[11]) {
             e->key_groups_off = true;   // a key with thousands of holders: this engine sorts by block from now on
         } else {
             const u64 K = std::max<u64>(1, e->h_scal[1]);
             u64* sval = (u64*)KA;             // (the per-key counts and offsets are dead once the records are packed)
             e->have_dwork = work != nullptr;
-            const char* msv = std::getenv("KSP_MS");   // 0: the library sort (diagnostic / tests)
             // (up to 256 blocks; the 1 024-block tables are slower than the library's two radix passes — C3: block lists 1.04 -> 1.38 ms
             //  for 0.23 ms of join, C4 4.1 -> 5.3 — and only run when KSP_MS=1024 asks for them: tests)
             const u32 ms_max = (msv && std::atoi(msv) == 1024) ? MS_MAXB : 256u;
@@ -742,6 +810,7 @@ template <class V> int Stage1<V>::lists_by_key(bool& done) {
             KSP_HIP(hipGetLastError());
             e->scal_fresh = phase == 0;   // (h_scal[1] .. [11] are this build's: build_common need not fetch them again)
             e->have_rank_pairs = true;   // rec_rank / rec_blk: (rank, block) of every list word in rank order
+            e->lists_path = 2;
             done = true;
             return KSP_OK;
         }
@@ -752,6 +821,7 @@ template <class V> int Stage1<V>::lists_by_key(bool& done) {
 // The block lists by sorting the kept entries by block (the fallback of lists_by_key, and inputs beyond its limits).
 template <class V> int Stage1<V>::lists_by_sort() {
     int rc;
+    e->lists_path = 3;
     // ---- the block lists by sorting the entries by block -------------------------------------------------
     if (!e->rank1_ok) {   // (the grouping wrote crank[] only: a rank per entry from first[])
         const u32* fp = (phase == 3 || e->post_slice) ? e->post_off : (const u32*)e->FK.p;
@@ -1290,6 +1360,7 @@ template <class V> int Stage1<V>::fused_middle() {
     e->fused_flags = true;
     e->pre_zeroed_bits = false;
     e->scal_fresh = true;
+    e->lists_path = 4;
     return S1_DONE;
 }
 
@@ -1401,6 +1472,9 @@ template <class V>
 static int build_impl(ksp_engine* e, const u64* d_keys, const u32* d_w, hipStream_t st, const int phase) {
     Stage1<V> c(e, d_keys, d_w, st, phase);
     int rc;
+    e->keyed_lists = false;
+    e->masks_in_gm = false;
+    e->lists_path = 0;
     if ((rc = c.setup())) return rc;
     if (phase == 3 || phase == 4) {
         if ((rc = c.from_postings())) return rc;
@@ -1489,7 +1563,7 @@ static int launch_sched_kernels(ksp_engine* e, hipStream_t st, const bool with_t
     const size_t bit_words = (size_t)(((T + 63) / 64) * 2 + 2);
     if ((rc = e->tbits.ensure(bit_words * 4 + T + 64))) return rc;   // packed bitmap, then one flag byte per tile
     if ((rc = e->dwork.ensure(((size_t)nb + 2) * 8))) return rc;
-    const bool fused = e->fused_flags;        // the bucket-resident build wrote the tile flags and the diagonal work with its lists
+    const bool fused = e->fused_flags || e->keyed_lists;   // the bucket-resident build / the keyed split wrote the tile flags and the diagonal work with the lists
     const bool ranked = e->have_rank_pairs;   // the key-by-key build left the pairs in rank order: nothing to sort
     if (!ranked && !fused) {
         if ((rc = e->KA.ensure((K + 4) * 8))) return rc;
@@ -1506,7 +1580,7 @@ static int launch_sched_kernels(ksp_engine* e, hipStream_t st, const bool with_t
         KSP_HIP(hipMemsetAsync(e->dwork.p, 0, ((size_t)nb + 2) * 8, st));
         const u32 shares = (u32)std::min<u64>(64, std::max<u64>(1, 2048 / nb));
         hipLaunchKernelGGL(k_list_pairs, dim3(nb, shares), dim3(256), 0, st, e->bkeys.as<u32>(), e->info.as<u32>(),
-                           e->mm.as<uint4>(), e->blk_raw.as<u32>(), e->blk_pos.as<u32>(), pr, pb,
+                           list_masks(e), e->blk_raw.as<u32>(), e->blk_pos.as<u32>(), pr, pb,
                            e->dwork.as<unsigned long long>());
     }
     if (!ranked && !fused) {
@@ -1612,6 +1686,7 @@ int ksp_engine_create(int device, ksp_engine** out) {
     }
     ksp_engine* e = new ksp_engine();
     e->device = device;
+    if (const char* mv = std::getenv("KSP_MOVE")) e->move_forced = std::atoi(mv) != 0;   // (once per engine, not per build)
     hipError_t err = hipHostMalloc((void**)&e->h_count, 64);
     if (err == hipSuccess) std::memset(e->h_count, 0, 64);   // ([7]: the sequence number of the early work list's copy-out)
     if (err == hipSuccess) err = hipHostMalloc((void**)&e->h_scal, 128);
@@ -1890,7 +1965,7 @@ static int build_common(ksp_engine* e, const uint64_t* d_keys, const uint32_t* d
     e->built = false;
     e->slice_ready = false;
     e->post_slice = false;
-    e->sched_on = false; e->collect = false; e->have_bits = false; e->matches_on = false; e->pmask_on = false;   // (nothing of the previous build's work list survives)
+    e->sched_on = false; e->collect = false; e->have_bits = false; e->matches_on = false; e->pmask_on = false; e->lists_path = 0;   // (nothing of the previous build's work list survives)
     e->act_tid.clear(); e->act_rec.clear();
     e->part_fail = 0;   // (stats: partition_fallback describes this build)
     if (const char* ro = std::getenv("KSP_REORDER")) e->reorder = std::atoi(ro) != 0;   // diagnostic / tests
@@ -2027,7 +2102,7 @@ static int build_postings_common(ksp_engine* e, const uint64_t* h_key_off, const
     KSP_HIP(hipSetDevice(e->device));
     e->built = false;
     e->slice_ready = false;
-    e->sched_on = false; e->collect = false; e->have_bits = false; e->matches_on = false; e->pmask_on = false;
+    e->sched_on = false; e->collect = false; e->have_bits = false; e->matches_on = false; e->pmask_on = false; e->lists_path = 0;
     e->act_tid.clear(); e->act_rec.clear();
     e->ph_n = 0;
     e->slice_phase = 0;
@@ -2361,6 +2436,9 @@ int ksp_engine_assemble(ksp_engine* e, uint32_t nparts, const uint64_t* h_sizes 
     e->h_scal_keys = utot;
     e->have_rank_pairs = false;   // (the assembled lists: pairs from the lists themselves)
     e->have_dwork = false;
+    e->keyed_lists = false;
+    e->masks_in_gm = false;
+    e->lists_path = 0;
     if ((rc = launch_sched_kernels(e, st))) return rc;
     KSP_HIP(hipEventRecord(e->ev[1], st));
     KSP_HIP(hipStreamSynchronize(st));
@@ -2451,7 +2529,7 @@ int ksp_engine_join_launch(ksp_engine* e, uint64_t tile_begin, uint64_t tile_end
     a.brk = e->bkeys.as<u32>();
     a.info = e->info.as<u32>();
     a.bw = e->weighted ? e->bw.as<u32>() : nullptr;
-    a.bigmask = e->mm.as<uint4>();
+    a.bigmask = list_masks(e);
     a.pmask = e->pmask_on ? e->pmask.as<uint4>() : nullptr;
     a.blk_raw = e->blk_raw.as<u32>();
     a.blk_pos = e->blk_pos.as<u32>();
@@ -2843,6 +2921,12 @@ int ksp_engine_phase_times(const ksp_engine* e, const char** names, float* ms, i
     const int n = std::min(cap, e->ph_n);
     for (int i = 0; i < n; ++i) { names[i] = e->ph_name[i]; ms[i] = e->ph_ms[i]; }
     return n;
+}
+
+int ksp_engine_lists_path(const ksp_engine* e, int* out) {
+    if (!e || !out) { set_error("lists_path: NULL argument"); return KSP_E_ARG; }
+    *out = e->built ? e->lists_path : 0;
+    return KSP_OK;
 }
 
 int ksp_engine_get_stats(const ksp_engine* e, ksp_stats* out) {

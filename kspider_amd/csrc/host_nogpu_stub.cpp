@@ -80,6 +80,10 @@ int ksp_pairwise_host_cut(const uint64_t*, const uint32_t*, const uint64_t*, uin
     return KSP_E_HIP;
 }
 void ksp_free(void* p) { std::free(p); }
+int ksp_engine_lists_path(const ksp_engine*, int*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
 int ksp_pairwise_host_multi(const uint64_t*, const uint32_t*, const uint64_t*, uint32_t, const int*, int, ksp_edge**,
                             uint64_t*, ksp_stats*) {
     ksp::set_error("host-only sanitizer build: no HIP engine");

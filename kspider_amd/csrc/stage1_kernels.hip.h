@@ -1574,6 +1574,310 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_place(const u32* __restrict__
     }
 }
 
+// ---- the same split straight from the parked per-key records (up to 256 blocks, positional masks) ------------------
+// k_move_groups packs the parked records of k_key_groups into rank order only for k_ms_place to move them again.  A key
+// has at most one group per block, so the order the lists want inside a block — ranks ascending — is key order: a chunk
+// is MSK_KEYS consecutive keys (the grid comes from the key count: nothing here waits for the number of groups), and the
+// three kernels read blk0 / info0 / mask0 and the parked slots themselves.  k_msk_hist also does what k_move_groups and
+// k_tile_flags did for the join's schedule (diagonal work, holders, one flag per block pair of a key) and sends the
+// totals of the group counts to the host; the masks stay where k_key_groups left them (gmask: mask0, then the parked
+// masks from n_keys + 4) and the posting words index them there.
+constexpr u32 MSK_KEYS = 1024, MSK_PER = MSK_KEYS / MS_THREADS;
+__device__ inline u64 tile_row_start_dev(u64 r, u64 nb);
+// hist / wk: per chunk the records and the diagonal work C(members, 2) of every block; hold: per chunk the members of all
+// its groups.  tsum: the tile sums of gsum (k_pair_tile_sums); workgroup 0 adds them up — scal[1] groups, scal[7] masks —
+// and carries words [1] .. [11] of the scalar block to the host (rider: src = scal + 1, 11 words).
+__global__ __launch_bounds__(MS_THREADS) void k_msk_hist(const u64* __restrict__ gsum, const u32* __restrict__ first,
+                                                          const u32* __restrict__ blk0, const u32* __restrict__ info0,
+                                                          const uint4* __restrict__ gmask, const u32* __restrict__ tmp_blk,
+                                                          const u32* __restrict__ tmp_info, const u32 n_keys, const u32 nb,
+                                                          const u64* __restrict__ tsum, const u32 ntiles, u64* scal,
+                                                          u32* __restrict__ hist, u32* __restrict__ wk, u32* __restrict__ hold,
+                                                          unsigned char* __restrict__ flags, const Rider rider) {
+    __shared__ u32 s_h[256], s_w[256], s_red[2 * MS_THREADS / 64], s_hold;
+    const u32 tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (blockIdx.x == 0) {
+        u32 lo = 0, hi = 0;
+        for (u32 j = tid; j < ntiles; j += MS_THREADS) { const u64 x = tsum[j]; lo += (u32)x; hi += (u32)(x >> 32); }
+        lo = wave_scan_add(lo); hi = wave_scan_add(hi);
+        if (lane == 63) { s_red[wv] = lo; s_red[MS_THREADS / 64 + wv] = hi; }
+        __syncthreads();
+        if (tid < 64) {
+            u64 groups = 0, masks = 0;
+            for (u32 w = 0; w < MS_THREADS / 64; ++w) { groups += s_red[w]; masks += s_red[MS_THREADS / 64 + w]; }
+            if (tid == 0) {
+                scal[1] = groups;
+                scal[7] = masks;
+                reinterpret_cast<u32*>(scal + 15)[0] = 0;   // k_msk_scan's "workgroups done"
+            }
+            if (rider.words) {
+                if (tid < rider.words) {
+                    const u64 v = tid == 0 ? groups : tid == 6 ? masks : rider.src[tid];
+                    __hip_atomic_store(rider.dst_host + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+                __threadfence_system();
+                if (tid == 0) __hip_atomic_store(rider.flag_host, rider.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+    if (reinterpret_cast<const u32*>(scal + 11)[0]) return;   // a key with too many holders: its records were never parked (the build sorts by block)
+    const u32 c0 = blockIdx.x * MSK_KEYS;
+    s_h[tid] = 0; s_w[tid] = 0;
+    if (tid == 0) s_hold = 0;
+    __syncthreads();
+    u32 kk[MSK_PER], bf[MSK_PER], inf0[MSK_PER], fa0[MSK_PER];
+#pragma unroll
+    for (u32 q = 0; q < MSK_PER; ++q) {   // (all of a thread's per-key words in flight together: none waits for the count)
+        const u32 r = min(c0 + q * MS_THREADS + tid, n_keys - 1);
+        kk[q] = c0 + q * MS_THREADS + tid < n_keys ? (u32)gsum[r] : 0u;
+        bf[q] = blk0[r];
+        inf0[q] = info0[r];
+        fa0[q] = first[r];
+    }
+    u32 holders = 0;
+#pragma unroll
+    for (u32 q = 0; q < MSK_PER; ++q) {
+        const u32 k = kk[q];
+        if (!k) continue;
+        const u32 r = c0 + q * MS_THREADS + tid;
+        const u32 fa = fa0[q];
+        for (u32 j = 0; j < k; ++j) {
+            const u32 inf = j ? tmp_info[fa + j] : inf0[q], blk = j ? tmp_blk[fa + j] : bf[q];
+            u32 cnt;
+            if (inf >= PM_BIG) {
+                const uint4 mk = j ? gmask[n_keys + 4 + (inf & ~PM_BIG)] : gmask[r];
+                cnt = __popc(mk.x) + __popc(mk.y) + __popc(mk.z) + __popc(mk.w);
+            } else cnt = (inf >> 29) + 1;
+            atomicAdd(&s_h[blk & 255u], 1u);
+            holders += cnt;
+            if (cnt > 1) atomicAdd(&s_w[blk & 255u], cnt * (cnt - 1) / 2);
+            for (u32 i = 0; i < j; ++i) {   // every pair of a key's blocks is a tile with something to count
+                const u32 I = i ? tmp_blk[fa + i] : bf[q], A = min(I, blk), B = max(I, blk);
+                const u64 t = tile_row_start_dev(A, nb) + (B - A);
+                if (!flags[t]) flags[t] = 1;
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) holders += __shfl_down(holders, o);
+    if (lane == 0 && holders) atomicAdd(&s_hold, holders);
+    __syncthreads();
+    hist[(size_t)blockIdx.x * 256 + tid] = s_h[tid];
+    wk[(size_t)blockIdx.x * 256 + tid] = s_w[tid];
+    if (tid == 0) hold[blockIdx.x] = s_hold;
+}
+// k_ms_scan over the rows of k_msk_hist (`chunks` from the host), one workgroup per block and one more: workgroup b also
+// adds up its block's column of the diagonal work, workgroup nb the holders — work[0 .. nb], as k_move_groups summed them
+__global__ __launch_bounds__(256) void k_msk_scan(u32* __restrict__ hist, const u32* __restrict__ wk, const u32* __restrict__ hold,
+                                                  const u32 chunks, u64* __restrict__ scal, u32* __restrict__ tot,
+                                                  u32* __restrict__ blk_raw, u32* __restrict__ blk_pos, const u32 nb,
+                                                  unsigned long long* __restrict__ work) {
+    __shared__ u32 s_w[4], s_last;
+    __shared__ unsigned long long s_work;
+    if (reinterpret_cast<const u32*>(scal + 11)[0]) return;
+    const u32 per = (chunks + 255u) / 256u;
+    const u32 b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const u32 c0 = min(chunks, tid * per), c1 = min(chunks, c0 + per);
+    if (tid == 0) s_work = 0;
+    __syncthreads();
+    if (b == nb) {   // the holders of all groups
+        unsigned long long h = 0;
+        for (u32 c = tid; c < chunks; c += 256) h += hold[c];
+        for (int o = 32; o > 0; o >>= 1) h += __shfl_down(h, o);
+        if (lane == 0 && h) atomicAdd(&s_work, h);
+        __syncthreads();
+        if (tid == 0) work[nb] = s_work;
+        return;
+    }
+    u32 sum = 0;
+    unsigned long long dw = 0;
+    for (u32 cb = c0; cb < c1; cb += MS_PER) {
+        u32 h[MS_PER], w[MS_PER];
+#pragma unroll
+        for (u32 i = 0; i < MS_PER; ++i) {
+            h[i] = cb + i < c1 ? hist[(size_t)(cb + i) * 256 + b] : 0u;
+            w[i] = cb + i < c1 ? wk[(size_t)(cb + i) * 256 + b] : 0u;
+        }
+#pragma unroll
+        for (u32 i = 0; i < MS_PER; ++i) { sum += h[i]; dw += w[i]; }
+    }
+    u32 inc = sum;
+    inc = wave_scan_add(inc);
+    if (lane == 63) s_w[wv] = inc;
+    for (int o = 32; o > 0; o >>= 1) dw += __shfl_down(dw, o);
+    if (lane == 0 && dw) atomicAdd(&s_work, dw);
+    __syncthreads();
+    u32 run = inc - sum, total = 0;
+    for (u32 w = 0; w < 4; ++w) { if (w < wv) run += s_w[w]; total += s_w[w]; }
+    for (u32 cb = c0; cb < c1; cb += MS_PER) {
+        u32 h[MS_PER];
+#pragma unroll
+        for (u32 i = 0; i < MS_PER; ++i) h[i] = cb + i < c1 ? hist[(size_t)(cb + i) * 256 + b] : 0u;
+#pragma unroll
+        for (u32 i = 0; i < MS_PER; ++i) {
+            if (cb + i < c1) hist[(size_t)(cb + i) * 256 + b] = run;
+            run += h[i];
+        }
+    }
+    if (tid == 0) {
+        work[b] = s_work;
+        tot[b] = total;
+        __threadfence();
+        s_last = atomicAdd(reinterpret_cast<u32*>(scal + 15), 1u) == nb - 1 ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+    __shared__ u32 s_t[256];
+    for (u32 i = tid; i < nb; i += 256) s_t[i] = __hip_atomic_load(&tot[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (tid != 0) return;
+    u32 raw = 0, pos = 0;
+    for (u32 bb = 0; bb < nb; ++bb) {
+        const u32 t = s_t[bb];
+        blk_raw[bb] = raw;
+        blk_pos[bb] = pos;
+        pos = ((pos + t + 3u) & ~3u) + WIN;
+        raw += t;
+    }
+    blk_raw[nb] = raw;
+    blk_pos[nb] = pos;
+    scal[3] = pos;
+}
+// k_ms_place over a chunk of keys: a scan of the group counts gives every record its place in key order, the records
+// are laid out in LDS in that order — a batch of MS_CHUNK at a time; a key can sit in every block, so a chunk may hold
+// several batches — and ranked as k_ms_place ranks them.  Ranks and posting words go to the padded lists, the mask of
+// every word to its list position; a posting word with a mask names it by its index in gmask.
+__global__ __launch_bounds__(MS_THREADS, 5) void k_msk_place(const u64* __restrict__ gsum, const u32* __restrict__ first,
+                                                           const u32* __restrict__ blk0, const u32* __restrict__ info0,
+                                                           const uint4* __restrict__ gmask, const u32* __restrict__ tmp_blk,
+                                                           const u32* __restrict__ tmp_info, const u32 n_keys,
+                                                           const u64* __restrict__ scal, const u32* __restrict__ base,
+                                                           const u32* __restrict__ blk_pos, const u32 nb, u32* __restrict__ brk,
+                                                           u32* __restrict__ info, uint4* __restrict__ pmask,
+                                                           const u32* __restrict__ blk_raw, const u32 padv) {
+    constexpr u32 NWV = MS_THREADS / 64, NSL = MS_ROUNDS * NWV, MB = 256;
+    static_assert(MB == MS_THREADS, "one block of the tables per thread");
+    __shared__ unsigned short s_cnt[NSL][MB];   // as k_ms_place
+    __shared__ u32 s_dst[MB];                   // next place of this chunk's records of block b in the padded list
+    __shared__ u32 s_inf[MS_CHUNK];             // the batch: posting word, block, key (index inside the chunk)
+    __shared__ unsigned char s_blk[MS_CHUNK];
+    __shared__ unsigned short s_key[MS_CHUNK];
+    u32* const s_off = s_inf;                   // (before the first batch) group count of every key of the chunk; then: its records before the key
+    static_assert(MSK_KEYS <= MS_CHUNK, "the key offsets borrow the batch's words");   // (five workgroups per CU: under 32 KB of LDS)
+    __shared__ u32 s_ws[NWV];
+    if (reinterpret_cast<const u32*>(scal + 11)[0]) return;
+    const u32 tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (u32 b = blockIdx.x; b <= nb; b += gridDim.x) {   // (the padding words, as in k_ms_place)
+        const u32 lo = b < nb ? blk_pos[b] + (blk_raw[b + 1] - blk_raw[b]) : blk_pos[nb];
+        const u32 hi = b < nb ? blk_pos[b + 1] : blk_pos[nb] + 4u * WIN;
+        for (u32 i = lo + tid; i < hi; i += MS_THREADS) brk[i] = padv;
+    }
+    const u32 c0 = blockIdx.x * MSK_KEYS;
+    u32 kk[MSK_PER], bf[MSK_PER], inf0[MSK_PER], fa[MSK_PER], off[MSK_PER];
+#pragma unroll
+    for (u32 q = 0; q < MSK_PER; ++q) {
+        const u32 r = c0 + q * MS_THREADS + tid;
+        kk[q] = r < n_keys ? (u32)gsum[r] : 0u;
+        s_off[q * MS_THREADS + tid] = kk[q];
+    }
+#pragma unroll
+    for (u32 q = 0; q < MSK_PER; ++q) {   // (in flight with the counts)
+        const u32 r = min(c0 + q * MS_THREADS + tid, n_keys - 1);
+        bf[q] = blk0[r];
+        inf0[q] = info0[r];
+        fa[q] = first[r];
+    }
+    s_dst[tid] = (tid < nb ? blk_pos[tid] : 0u) + base[(size_t)blockIdx.x * MB + tid];
+    __syncthreads();
+    u32 n;
+    {   // exclusive sums of the counts in key order: every thread MSK_PER consecutive keys
+        u32 a[MSK_PER], sum = 0;
+#pragma unroll
+        for (u32 i = 0; i < MSK_PER; ++i) { a[i] = s_off[tid * MSK_PER + i]; sum += a[i]; }
+        const u32 inc = wave_scan_add(sum);
+        if (lane == 63) s_ws[wv] = inc;
+        __syncthreads();
+        u32 run = inc - sum;
+        n = 0;
+        for (u32 w = 0; w < NWV; ++w) { if (w < wv) run += s_ws[w]; n += s_ws[w]; }
+#pragma unroll
+        for (u32 i = 0; i < MSK_PER; ++i) { s_off[tid * MSK_PER + i] = run; run += a[i]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (u32 q = 0; q < MSK_PER; ++q) off[q] = s_off[q * MS_THREADS + tid];
+    __syncthreads();   // (the offsets are in registers: their words become the first batch)
+    for (u32 g0 = 0; g0 < n; g0 += MS_CHUNK) {
+        for (u32 i = tid; i < NSL * MB / 2; i += MS_THREADS) reinterpret_cast<u32*>(&s_cnt[0][0])[i] = 0;
+#pragma unroll
+        for (u32 q = 0; q < MSK_PER; ++q) {
+            if (off[q] >= g0 + MS_CHUNK || off[q] + kk[q] <= g0) continue;
+            const u32 r = c0 + q * MS_THREADS + tid;
+            const u32 j0 = off[q] < g0 ? g0 - off[q] : 0u, j1 = min(kk[q], g0 + MS_CHUNK - off[q]);
+            for (u32 j = j0; j < j1; ++j) {
+                u32 inf = j ? tmp_info[fa[q] + j] : inf0[q];
+                const u32 blk = j ? tmp_blk[fa[q] + j] : bf[q];
+                if (inf >= PM_BIG) inf = PM_BIG | (j ? n_keys + 4 + (inf & ~PM_BIG) : r);
+                const u32 s = off[q] + j - g0;
+                s_inf[s] = inf;
+                s_blk[s] = (unsigned char)blk;
+                s_key[s] = (unsigned short)(q * MS_THREADS + tid);
+            }
+        }
+        __syncthreads();
+        u32 blk[MS_ROUNDS], rk[MS_ROUNDS];
+#pragma unroll
+        for (u32 k = 0; k < MS_ROUNDS; ++k) {
+            const u32 g = k * MS_THREADS + tid;
+            blk[k] = g0 + g < n ? (u32)s_blk[g] : ~0u;
+        }
+#pragma unroll
+        for (u32 k = 0; k < MS_ROUNDS; ++k) {
+            unsigned long long m = __ballot(blk[k] != ~0u);
+#pragma unroll
+            for (u32 bit = 0; bit < 8; ++bit) {
+                const unsigned long long bal = __ballot((blk[k] >> bit) & 1u);
+                m &= ((blk[k] >> bit) & 1u) ? bal : ~bal;
+            }
+            const unsigned long long below = m & ((1ull << lane) - 1ull);
+            rk[k] = (u32)__popcll(below);
+            if (blk[k] != ~0u && below == 0) s_cnt[k * NWV + wv][blk[k]] = (unsigned short)__popcll(m);
+        }
+        __syncthreads();
+        u32 tot_b = 0;
+        for (u32 sl = 0; sl < NSL; ++sl) {   // (one block per thread: MB == MS_THREADS)
+            const u32 c = s_cnt[sl][tid];
+            s_cnt[sl][tid] = (unsigned short)tot_b;
+            tot_b += c;
+        }
+        __syncthreads();
+#pragma unroll
+        for (u32 k = 0; k < MS_ROUNDS; ++k) {
+            if (blk[k] == ~0u) continue;
+            const u32 g = k * MS_THREADS + tid;
+            const u32 dst = s_dst[blk[k]] + s_cnt[k * NWV + wv][blk[k]] + rk[k];
+            const u32 inf = s_inf[g];
+            brk[dst] = c0 + s_key[g];
+            info[dst] = inf;
+            uint4 m;
+            if (inf >= PM_BIG) m = gmask[inf & ~PM_BIG];
+            else {
+                u32 w4[4] = {0, 0, 0, 0};
+                const u32 cnt = (inf >> 29) + 1;
+                for (u32 x = 0; x < cnt; ++x) {
+                    const u32 id = (inf >> (7 * x)) & 127u;
+#pragma unroll
+                    for (int z = 0; z < 4; ++z) w4[z] |= (id >> 5) == (u32)z ? (1u << (id & 31)) : 0u;
+                }
+                m = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+            }
+            pmask[dst] = m;
+        }
+        __syncthreads();   // (s_dst is read above, advanced below)
+        s_dst[tid] += tot_b;
+    }
+}
+
 // 1 when entry e opens a new (block, rank) group; evaluated on the fly by the scan and the passes after it
 // (two neighbouring loads of two arrays) instead of being written out by a pass of its own
 template <class V>

@@ -40,6 +40,9 @@ TOPK_WAVE_ENTRIES = 64
 TOPK_LDS_ENTRIES = 4096
 TOPK_MAX_K = 1024
 
+#: ksp_engine_lists_path / Engine.lists_path
+LISTS_NONE, LISTS_KEYED, LISTS_COMPACTED, LISTS_SORTED, LISTS_FUSED = 0, 1, 2, 3, 4
+
 #: every symbol include/kspider_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "ksp_last_error", "ksp_device_count", "ksp_engine_create", "ksp_engine_destroy",
@@ -52,7 +55,7 @@ ABI_SYMBOLS = [
     "ksp_engine_edge_bound", "ksp_engine_slice_labels", "ksp_engine_slice_finish",
     "ksp_engine_slice_bounds", "ksp_engine_slice_set_bounds", "ksp_engine_balanced_cuts",
     "ksp_engine_build_postings", "ksp_engine_build_postings_slice", "ksp_pairwise_postings_host",
-    "ksp_engine_set_profiling", "ksp_engine_phase_times",
+    "ksp_engine_set_profiling", "ksp_engine_phase_times", "ksp_engine_lists_path",
     "ksp_pairwise_host_multi", "ksp_pairwise_postings_host_multi",
     "kspider_cluster", "ksp_components", "ksp_components_edges", "kspider_pairwise_and_cluster",
     "kspider_estimate_ani", "kspider_pairwise_ani", "kspider_pairwise_ani_and_cluster", "ksp_edges_ani",
@@ -165,6 +168,7 @@ def lib():
                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(Stats)]
         L.ksp_free.restype = None
         L.ksp_engine_set_profiling.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.ksp_engine_lists_path.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
         L.ksp_engine_phase_times.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p),
                                              ctypes.POINTER(ctypes.c_float), ctypes.c_int]
         L.kspider_cluster.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double]
@@ -931,6 +935,12 @@ class Engine:
         ms = (ctypes.c_float * 24)()
         n = lib().ksp_engine_phase_times(self._h, names, ms, 24)
         return [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+    def lists_path(self) -> int:
+        """How the last build made its block lists: LISTS_NONE / KEYED / COMPACTED / SORTED / FUSED."""
+        v = ctypes.c_int(0)
+        _check(lib().ksp_engine_lists_path(self._h, ctypes.byref(v)))
+        return int(v.value)
 
     def stats(self) -> dict:
         st = Stats()
