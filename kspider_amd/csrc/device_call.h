@@ -1,6 +1,7 @@
 // What every consumer of the join's edges does on the host before its first kernel launch (cluster.hip, export.hip, repr.hip,
 // cut.hip, sweep.hip, tree.hip, derep.hip): check a HIP call, choose the device, size a grid of chunk-loop workgroups, ask
-// whether an allocation fits, and own device memory until the call returns.  Host code only: no kernel, nothing __device__.
+// whether an allocation fits, and own device memory until the call returns.  Also the growing device buffer and the HIP check
+// of the engine and of the multi-device job (engine.hip, multi.hip).  Host code only: no kernel, nothing __device__.
 #ifndef KSPIDER_DEVICE_CALL_H
 #define KSPIDER_DEVICE_CALL_H
 #include <algorithm>
@@ -24,7 +25,33 @@
         }                                                                                \
     } while (0)
 
+// a failing HIP call of a function that returns a KSP_* code: the error text and KSP_E_HIP
+#define KSP_HIP(call)                                                                              \
+    do {                                                                                           \
+        hipError_t err__ = (call);                                                                 \
+        if (err__ != hipSuccess) {                                                                 \
+            ksp::set_error(std::string(#call) + ": " + hipGetErrorString(err__));                  \
+            return KSP_E_HIP;                                                                      \
+        }                                                                                          \
+    } while (0)
+
 namespace ksp {
+
+// device memory of the current device that grows when more is asked for (what it held is not kept) and is freed by release()
+struct Buf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int ensure(size_t need) {
+        if (need <= bytes) return KSP_OK;
+        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
+        size_t want = need + need / 8 + 256;
+        KSP_HIP(hipMalloc(&p, want));
+        bytes = want;
+        return KSP_OK;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    template <class T> T* as() const { return (T*)p; }
+};
 
 // `device` becomes the current device of the calling thread, or KSP_E_HIP with "WHO: no such device"
 inline int set_device(const char* who, const int device) {

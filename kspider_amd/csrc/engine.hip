@@ -21,12 +21,7 @@
 //
 // Integer set intersection: no MFMA.  See DESIGN.md for the data layout, the measurements and the history.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <condition_variable>
-#include <mutex>
-#include <set>
-#include <thread>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -43,8 +38,8 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "../../include/kspider_amd.h"
+#include "device_call.h"
 #include "engine_internal.h"
-#include "host_sync.h"
 
 typedef uint64_t u64;
 typedef uint32_t u32;
@@ -52,17 +47,8 @@ typedef uint8_t u8;
 
 namespace ksp {
 
-thread_local std::string g_error;
+static thread_local std::string g_error;
 void set_error(const std::string& s) { g_error = s; }
-
-#define KSP_HIP(call)                                                                              \
-    do {                                                                                           \
-        hipError_t err__ = (call);                                                                 \
-        if (err__ != hipSuccess) {                                                                 \
-            ksp::set_error(std::string(#call) + ": " + hipGetErrorString(err__));                  \
-            return KSP_E_HIP;                                                                      \
-        }                                                                                          \
-    } while (0)
 
 constexpr int TB = 128;       // sources per block (tile edge)
 constexpr int NP = 64;        // value-range parts per block (intra-tile work items)
@@ -77,26 +63,11 @@ constexpr u32 INLINE_MAX = 4;         // sources whose 7-bit ids fit into the po
 #include "fused_kernels.hip.h"
 #include "join_kernels.hip.h"
 
+}  // namespace ksp
+
 // ------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t need) {
-        if (need <= bytes) return KSP_OK;
-        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
-        size_t want = need + need / 8 + 256;
-        KSP_HIP(hipMalloc(&p, want));
-        bytes = want;
-        return KSP_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    template <class T> T* as() const { return (T*)p; }
-};
-
-}  // namespace ksp
-
 struct ksp_engine {
     int device = 0;
     // inputs / geometry
@@ -2971,452 +2942,6 @@ int ksp_memcpy_d2h(void* h, const void* d, uint64_t bytes) {
     return KSP_OK;
 }
 
-// results handed to the caller live in pinned host memory (the device-to-host copy runs at the full link
-// rate straight into the buffer the caller gets); ksp_free tells them from malloc'ed blocks by this registry
-static std::mutex g_pinned_mu;
-static std::set<void*> g_pinned;
-static void* alloc_result(size_t bytes) {
-    void* p = nullptr;
-    if (hipHostMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> g(g_pinned_mu);
-    g_pinned.insert(p);
-    return p;
-}
-void ksp_free(void* p) {
-    if (!p) return;
-    {
-        std::lock_guard<std::mutex> g(g_pinned_mu);
-        auto it = g_pinned.find(p);
-        if (it != g_pinned.end()) { g_pinned.erase(it); (void)hipHostFree(p); return; }
-    }
-    std::free(p);
-}
-
-// ---- collecting the result: join -> [gather to the first device over xGMI] -> device sort -> pinned host ----
-// edges of tiles [t0, t1) of a built engine into a device buffer that grows to the size the join reports
-static int join_range_grow(ksp_engine* e, u64 t0, u64 t1, Buf& buf, u64& count, float& ms_join) {
-    count = 0;
-    if (t0 >= t1) return KSP_OK;
-    int rc;
-    if (buf.bytes < sizeof(ksp_edge)) {
-        const u64 first = std::min<u64>(ksp_engine_edge_bound(e, t0, t1) + 1, 1ull << 26);   // at most 1 GiB to begin with
-        if ((rc = buf.ensure(first * sizeof(ksp_edge)))) return rc;
-    }
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        u64 cnt = 0;
-        rc = ksp_engine_join(e, t0, t1, buf.as<ksp_edge>(), buf.bytes / sizeof(ksp_edge), &cnt, nullptr);
-        ms_join += e->st.ms_join;
-        if (rc == KSP_OK) { count = cnt; return KSP_OK; }
-        if (rc != KSP_E_OVERFLOW) return rc;
-        if ((rc = buf.ensure((cnt + cnt / 16 + 1024) * sizeof(ksp_edge)))) {   // (the count the join reported, plus slack)
-            set_error("pairwise_host: the edges of this tile range do not fit in device memory");
-            return KSP_E_LIMIT;
-        }
-    }
-    set_error("pairwise_host: edge count kept growing between joins");
-    return KSP_E_HIP;
-}
-
-__global__ void k_edge_split(const ksp_edge* __restrict__ ed, u64 n, u64* __restrict__ key, u64* __restrict__ val) {
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
-        const ksp_edge x = ed[i];
-        key[i] = ((u64)x.source_1 << 32) | x.source_2;
-        val[i] = x.shared;
-    }
-}
-__global__ void k_edge_merge(const u64* __restrict__ key, const u64* __restrict__ val, u64 n, ksp_edge* __restrict__ ed) {
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
-        ksp_edge x;
-        x.source_1 = (u32)(key[i] >> 32);
-        x.source_2 = (u32)key[i];
-        x.shared = val[i];
-        ed[i] = x;
-    }
-}
-// rows in (source_1, source_2) order — the order the TSV writer emits (the reference's own order is hash-map
-// iteration order, src/pairwise.cpp:253) — by one device radix sort over the significant key bits
-static int sort_edges_device(ksp_edge* d_edges, u64 n, u32 n_sources) {
-    if (n < 2) return KSP_OK;
-    Buf k0, k1, v0, v1, tmp;
-    int rc = KSP_OK;
-    do {
-        if ((rc = k0.ensure(n * 8)) || (rc = k1.ensure(n * 8)) || (rc = v0.ensure(n * 8)) || (rc = v1.ensure(n * 8))) break;
-        const unsigned grid = (unsigned)std::min<u64>((n + 255) / 256, 1u << 20);
-        hipLaunchKernelGGL(k_edge_split, dim3(grid), dim3(256), 0, nullptr, d_edges, n, k0.as<u64>(), v0.as<u64>());
-        int sbits = 1;
-        while (sbits < 32 && (n_sources >> sbits)) ++sbits;
-        size_t tb = 0;
-        hipError_t err = rocprim::radix_sort_pairs(nullptr, tb, k0.as<u64>(), k1.as<u64>(), v0.as<u64>(), v1.as<u64>(), (size_t)n, 0, 32 + sbits, (hipStream_t) nullptr);
-        if (err == hipSuccess && !(rc = tmp.ensure(tb)))
-            err = rocprim::radix_sort_pairs(tmp.p, tb, k0.as<u64>(), k1.as<u64>(), v0.as<u64>(), v1.as<u64>(), (size_t)n, 0, 32 + sbits, (hipStream_t) nullptr);
-        if (rc) break;
-        if (err != hipSuccess) { set_error(std::string("sort_edges: ") + hipGetErrorString(err)); rc = KSP_E_HIP; break; }
-        hipLaunchKernelGGL(k_edge_merge, dim3(grid), dim3(256), 0, nullptr, k1.as<u64>(), v1.as<u64>(), n, d_edges);
-        err = hipDeviceSynchronize();
-        if (err != hipSuccess) { set_error(std::string("sort_edges: ") + hipGetErrorString(err)); rc = KSP_E_HIP; }
-    } while (0);
-    k0.release(); k1.release(); v0.release(); v1.release(); tmp.release();
-    return rc;
-}
-
-namespace {
-struct MultiJob {
-    // input (host): sketches (keys / weights / offsets) or an inverted index (key_off / sources / key_weights)
-    const u64* keys = nullptr; const u32* weights = nullptr; const u64* offsets = nullptr;
-    const u64* key_off = nullptr; const u32* sources = nullptr; const u32* key_weights = nullptr;
-    u32 n_keys = 0, n_sources = 0;
-    bool postings = false;
-    ksp::AfterJoin* after = nullptr;   // what is also wanted from the edges (engine_internal.h)
-    bool wants(ksp::AfterJoin::Kind k) const { return after && after->kind == k; }
-};
-}  // namespace
-
-// The whole job on `nd` devices, one host thread + one engine per device (the reference entry points call this
-// with the devices of $KSPIDER_DEVICES; nd = 1 is the single-GPU path):
-//   stage 1   device i builds its slice — sketch input: its 1/nd share of the hash range; postings input (the reference's
-//             entry point): 1/nd of the colours (whole keys, cut by memberships) — the labels are MIN-combined and the
-//             slices exchanged device to device (peer copies over xGMI), then every device assembles the full lists:
-//             the same exchange kspider_amd/dist.py does with RCCL collectives between processes.  Inputs of 2^30
-//             entries or more are cut into more slices than there are devices (several workers per device).
-//   stage 2   device i joins the tile range [cuts[i], cuts[i+1]) of equal estimated work (same cuts everywhere:
-//             checked), the edges are gathered to the first device (peer copies), sorted there and copied into
-//             pinned host memory.
-static int run_multi(const MultiJob& job, const int* devices, int nd, ksp_edge** out_edges, uint64_t* n_edges, ksp_stats* stats) {
-    *out_edges = nullptr;
-    *n_edges = 0;
-    if (nd < 1 || nd > 64) { set_error("pairwise: between 1 and 64 devices"); return KSP_E_ARG; }
-    AfterJoin* const after = job.after;
-    if (job.wants(AfterJoin::kTree) && (after->col < 3 || after->col > 5)) { set_error("pairwise: a tree needs a column 3 / 4 / 5 and room for its result"); return KSP_E_ARG; }
-    if (job.wants(AfterJoin::kTopk) && (after->col < 3 || after->col > 5 || after->k < 1 || after->k > KSP_TOPK_MAX_K)) { set_error("pairwise: top-k needs a column 3 / 4 / 5 and 1 <= k <= KSP_TOPK_MAX_K"); return KSP_E_ARG; }
-    if (job.wants(AfterJoin::kSweep) && (!after->cutoffs || after->n_cutoffs < 1 || after->n_cutoffs > KSP_SWEEP_MAX_CUTOFFS)) {
-        set_error("pairwise: a cut-off ladder has between 1 and 255 cut-offs");
-        return KSP_E_ARG;
-    }
-    if (after) after->n_found = 0;
-    const u32 N = job.n_sources;
-    const u64 n = job.postings ? (job.n_keys ? job.key_off[job.n_keys] : 0) : (N ? job.offsets[N] : 0);
-    // A sketch set of 2^30 entries or more does not fit one build (32-bit entry positions): it is cut into hash-range
-    // slices of at most ~0.9 * 2^30 entries, built one engine each and assembled — the multi-GPU machinery with several
-    // workers per device ($KSP_SLICES forces a slice count: tests).
-    std::vector<int> expanded;
-    std::vector<u32> pk_cut;   // postings input in slices: slice s holds the keys [pk_cut[s], pk_cut[s + 1])
-    if (!job.postings) {
-        u64 want = n < (1ull << 30) ? 1 : n / 900000000ull + 1;   // (equal shares of the hash range: ~equal sizes for hashes)
-        if (const char* sl = std::getenv("KSP_SLICES")) want = std::max<u64>(want, (u64)std::max(1, std::atoi(sl)));
-        if (want > (u64)nd) {
-            if (want > 64) { set_error("pairwise_host: more than 2^35 key entries"); return KSP_E_LIMIT; }
-            for (u64 i = 0; i < want; ++i) expanded.push_back(devices[i % (u64)nd]);
-            devices = expanded.data();
-            nd = (int)want;
-        }
-    } else {
-        // An inverted index (the reference's colour -> sources map, src/pairwise.cpp:95-111, which has no size limit): slices
-        // of whole keys with fewer than 2^30 memberships each — one per device of the job, more (built side by side on the
-        // devices there are) when the index is larger than that, $KSP_SLICES forces a count (tests).  Every device then
-        // builds 1 / nd of the colours instead of all of them.
-        u64 want = n < (1ull << 30) ? 1 : n / 900000000ull + 1;
-        if (const char* sl = std::getenv("KSP_SLICES")) want = std::max<u64>(want, (u64)std::max(1, std::atoi(sl)));
-        want = std::max<u64>(want, (u64)nd);
-        if (want > (u64)job.n_keys && n < (1ull << 30)) want = 1;   // (fewer colours than slices: every device builds the few there are, the tiles are still shared)
-        if (want > 1) {
-            if (want > 64) { set_error("pairwise: more than 2^35 colour memberships"); return KSP_E_LIMIT; }
-            if (want > (u64)nd) {
-                for (u64 i = 0; i < want; ++i) expanded.push_back(devices[i % (u64)nd]);
-                devices = expanded.data();
-                nd = (int)want;
-            }
-            pk_cut.assign((size_t)nd + 1, 0);
-            u32 k = 0;
-            for (int sidx = 1; sidx < nd; ++sidx) {   // cut where the memberships reach s / nd of all (whole keys, no empty slice)
-                const u64 goal = n / (u64)nd * (u64)sidx;
-                while (k < job.n_keys && job.key_off[k] < goal) ++k;
-                k = std::max<u32>(k, pk_cut[(size_t)sidx - 1] + 1);
-                k = std::min<u32>(k, job.n_keys - (u32)(nd - sidx));
-                pk_cut[(size_t)sidx] = k;
-            }
-            pk_cut[(size_t)nd] = job.n_keys;
-            for (int sidx = 0; sidx < nd; ++sidx)
-                if (job.key_off[pk_cut[(size_t)sidx + 1]] - job.key_off[pk_cut[(size_t)sidx]] >= (1ull << 30)) {
-                    set_error("pairwise: one colour range holds 2^30 memberships or more (a single colour that large?)");
-                    return KSP_E_LIMIT;
-                }
-        }
-    }
-    const bool sliced = job.postings ? !pk_cut.empty() : nd > 1;
-    struct Dev {
-        ksp_engine* e = nullptr;
-        void *d_a = nullptr, *d_b = nullptr;      // keys + weights, or sources + key weights
-        Buf edges, labels, gather[6], exp[6];
-        u64 count = 0, found = 0, sizes[4] = {0, 0, 0, 0};   // count: edges I hand on; found: edges of my join (the same without a cut)
-        std::vector<u64> cuts;
-        float ms_join = 0;
-        int rc = KSP_OK;
-        bool borrowed = false;                    // d_a / d_b belong to another worker on the same device
-        std::string err;
-    };
-    std::vector<Dev> dev((size_t)nd);
-    FailBarrier bar(nd);   // (the failure decision is latched once per barrier generation: host_sync.h)
-    std::vector<u32> lab_min;                 // MIN-combined labels (host)
-    std::vector<std::vector<u32>> lab_dev((size_t)nd);
-    std::vector<u32> bnd_sum;                 // per-source counter bounds summed over postings slices (host)
-    std::vector<std::vector<u32>> bnd_dev((size_t)nd);
-    std::vector<u64> all_sizes((size_t)nd * 4, 0);
-    u64 total = 0;
-    std::vector<u64> edge_off((size_t)nd + 1, 0);
-    Buf merged;                               // all edges on the first device (nd > 1)
-
-    auto body = [&](int i) {
-        Dev& D = dev[(size_t)i];
-        const int device = devices[i];
-        auto fail = [&](int rc) { D.rc = rc; D.err = g_error; bar.fail(); };
-        auto sync_point = [&]() { return bar.sync(); };
-        int rc = ksp_engine_create(device, &D.e);
-        if (rc) fail(rc);
-        for (int j = 0; j < nd && !rc; ++j)   // direct xGMI copies between the devices of this job (already enabled: fine)
-            if (devices[j] != device) { (void)hipDeviceEnablePeerAccess(devices[j], 0); (void)hipGetLastError(); }
-        // ---- stage 1 --------------------------------------------------------------------------------------------
-        int owner = i;   // the first worker on my device uploads the input; the others use its copy
-        for (int j = 0; j < i; ++j)
-            if (devices[j] == device) { owner = j; break; }
-        if (job.postings && sliced) owner = i;   // (every worker uploads its own slice of the index)
-        std::vector<u64> my_off;                 // key offsets of my slice, from 0
-        u32 my_keys = 0;
-        if (!bar.failed_hint() && job.postings && sliced) {
-            const u32 k0 = pk_cut[(size_t)i], k1 = pk_cut[(size_t)i + 1];
-            my_keys = k1 - k0;
-            my_off.resize((size_t)my_keys + 1);
-            const u64 e0 = job.key_off[k0];
-            for (u32 k = 0; k <= my_keys; ++k) my_off[k] = job.key_off[k0 + k] - e0;
-            const u64 ne = my_off[my_keys];
-            if ((rc = ksp_device_malloc(device, ne * 4, &D.d_a)) || (rc = ksp_memcpy_h2d(D.d_a, job.sources + e0, ne * 4))) fail(rc);
-            if (!rc && job.key_weights &&   // (allocated even for an empty slice: a non-NULL weight array is what makes a build weighted)
-                ((rc = ksp_device_malloc(device, (u64)my_keys * 4, &D.d_b)) || (rc = ksp_memcpy_h2d(D.d_b, job.key_weights + k0, (u64)my_keys * 4))))
-                fail(rc);
-        } else if (!bar.failed_hint() && n && owner == i) {
-            if (job.postings) {
-                if ((rc = ksp_device_malloc(device, n * 4, &D.d_a)) || (rc = ksp_memcpy_h2d(D.d_a, job.sources, n * 4))) fail(rc);
-                if (!rc && job.key_weights &&
-                    ((rc = ksp_device_malloc(device, (u64)job.n_keys * 4, &D.d_b)) || (rc = ksp_memcpy_h2d(D.d_b, job.key_weights, (u64)job.n_keys * 4))))
-                    fail(rc);
-            } else {
-                if ((rc = ksp_device_malloc(device, n * 8, &D.d_a)) || (rc = ksp_memcpy_h2d(D.d_a, job.keys, n * 8))) fail(rc);
-                if (!rc && job.weights && ((rc = ksp_device_malloc(device, n * 4, &D.d_b)) || (rc = ksp_memcpy_h2d(D.d_b, job.weights, n * 4))))
-                    fail(rc);
-            }
-        }
-        if (nd > 1 && sync_point()) return;   // (the uploads are complete: ksp_memcpy_h2d is synchronous)
-        if (owner != i) { D.d_a = dev[(size_t)owner].d_a; D.d_b = dev[(size_t)owner].d_b; D.borrowed = true; }
-        if (!bar.failed_hint()) {
-            if (job.postings && sliced)
-                rc = ksp_engine_build_postings_slice(D.e, my_off.data(), (const u32*)D.d_a, (const u32*)D.d_b, my_keys, N, nullptr);
-            else if (job.postings)
-                rc = ksp_engine_build_postings(D.e, job.key_off, (const u32*)D.d_a, (const u32*)D.d_b, job.n_keys, N, nullptr);
-            else if (nd == 1)
-                rc = ksp_engine_build_blocks(D.e, (const u64*)D.d_a, (const u32*)D.d_b, job.offsets, N, 0, nullptr);
-            else
-                rc = ksp_engine_build_slice(D.e, (const u64*)D.d_a, (const u32*)D.d_b, job.offsets, N, 0, (u32)i, (u32)nd, nullptr);
-            if (rc) fail(rc);
-        }
-        if (sliced) {   // the slices become the full lists on every device
-            // common source order: element-wise MIN of the devices' labels
-            if (!bar.failed_hint() && N) {
-                lab_dev[(size_t)i].resize(N);
-                if ((rc = D.labels.ensure((size_t)N * 4)) || (rc = ksp_engine_slice_labels(D.e, D.labels.as<u32>(), nullptr)) ||
-                    (rc = ksp_memcpy_d2h(lab_dev[(size_t)i].data(), D.labels.p, (u64)N * 4)))
-                    fail(rc);
-            }
-            // postings slices hold a share of every source's keys: the counters' bounds are the sums over the slices
-            if (!bar.failed_hint() && N && job.postings) {
-                bnd_dev[(size_t)i].resize(N);
-                if ((rc = ksp_engine_slice_bounds(D.e, D.labels.as<u32>(), nullptr)) ||
-                    (rc = ksp_memcpy_d2h(bnd_dev[(size_t)i].data(), D.labels.p, (u64)N * 4)))
-                    fail(rc);
-            }
-            if (sync_point()) return;
-            if (i == 0) {
-                lab_min = lab_dev[0];
-                for (int j = 1; j < nd; ++j)
-                    for (u32 s = 0; s < N; ++s) lab_min[s] = std::min(lab_min[s], lab_dev[(size_t)j][s]);
-                if (job.postings && N) {
-                    bnd_sum.assign(N, 0);
-                    for (int j = 0; j < nd; ++j)
-                        for (u32 s = 0; s < N; ++s)
-                            bnd_sum[s] = (u32)std::min<u64>((u64)bnd_sum[s] + bnd_dev[(size_t)j][s], 0xFFFFFFFFull);
-                }
-            }
-            if (sync_point()) return;
-            if (N && job.postings &&
-                ((rc = ksp_memcpy_h2d(D.labels.p, bnd_sum.data(), (u64)N * 4)) || (rc = ksp_engine_slice_set_bounds(D.e, D.labels.as<u32>(), nullptr))))
-                fail(rc);
-            else if (N && ((rc = ksp_memcpy_h2d(D.labels.p, lab_min.data(), (u64)N * 4)) || (rc = ksp_engine_slice_finish(D.e, D.labels.as<u32>(), nullptr))))
-                fail(rc);
-            else if (!N && (rc = ksp_engine_slice_finish(D.e, nullptr, nullptr)))
-                fail(rc);
-            if (!bar.failed_hint() && (rc = ksp_engine_slice_sizes(D.e, D.sizes))) fail(rc);
-            for (int q = 0; q < 4; ++q) all_sizes[(size_t)i * 4 + q] = D.sizes[q];
-            if (sync_point()) return;
-            // every device receives every slice: [part][stride] buffers, filled by peer copies from the owners
-            u64 lstride = 4, bigstride = 1;
-            for (int j = 0; j < nd; ++j) { lstride = std::max(lstride, all_sizes[(size_t)j * 4]); bigstride = std::max(bigstride, all_sizes[(size_t)j * 4 + 2]); }
-            const u32 nb = D.e->nb;   // (the same on every device: a function of the source count)
-            const bool weighted = job.postings ? job.key_weights != nullptr : job.weights != nullptr;
-            const size_t bytes[6] = {lstride * 4, lstride * 4, weighted ? lstride * 4 : 0, ((size_t)nb + 1) * 4, ((size_t)nb + 1) * 4, bigstride * 16};
-            for (int q = 0; q < 6 && !rc; ++q) {
-                if (!bytes[q]) continue;
-                if ((rc = D.exp[q].ensure(bytes[q])) || (rc = D.gather[q].ensure(bytes[q] * (size_t)nd))) fail(rc);
-                else if (hipMemset(D.exp[q].p, 0, bytes[q]) != hipSuccess || hipMemset(D.gather[q].p, 0, bytes[q] * (size_t)nd) != hipSuccess) { set_error("pairwise: hipMemset"); fail(rc = KSP_E_HIP); }
-            }
-            if (!bar.failed_hint() && n &&
-                (rc = ksp_engine_slice_export(D.e, D.exp[0].as<u32>(), D.exp[1].as<u32>(), weighted ? D.exp[2].as<u32>() : nullptr,
-                                              D.exp[3].as<u32>(), D.exp[4].as<u32>(), D.exp[5].p, nullptr)))
-                fail(rc);
-            if (sync_point()) return;
-            for (int j = 0; j < nd && !bar.failed_hint(); ++j)      // my slice into device j's gather buffers
-                for (int q = 0; q < 6; ++q) {
-                    if (!bytes[q]) continue;
-                    if (hipMemcpyPeer((char*)dev[(size_t)j].gather[q].p + bytes[q] * (size_t)i, devices[j], D.exp[q].p, device, bytes[q]) != hipSuccess) {
-                        set_error("pairwise: peer copy of a block-list slice failed");
-                        fail(KSP_E_HIP);
-                        break;
-                    }
-                }
-            if (sync_point()) return;
-            if ((rc = ksp_engine_assemble(D.e, (u32)nd, all_sizes.data(), D.gather[0].as<u32>(), D.gather[1].as<u32>(),
-                                          weighted ? D.gather[2].as<u32>() : nullptr, lstride, D.gather[3].as<u32>(), D.gather[4].as<u32>(),
-                                          D.gather[5].p, bigstride, nullptr)))
-                fail(rc);
-        }
-        if (sync_point()) return;
-        // ---- stage 2: my share of the tiles ------------------------------------------------------------------
-        D.cuts.assign((size_t)nd + 1, 0);
-        if ((rc = ksp_engine_balanced_cuts(D.e, (u32)nd, D.cuts.data()))) fail(rc);
-        if (sync_point()) return;
-        if (i == 0)
-            for (int j = 1; j < nd; ++j)
-                if (dev[(size_t)j].cuts != dev[0].cuts || dev[(size_t)j].e->st.n_block_keys != dev[0].e->st.n_block_keys) {
-                    set_error("pairwise: the devices built different block lists (cannot shard the tiles)");
-                    fail(KSP_E_HIP);
-                }
-        if (sync_point()) return;
-        if ((rc = join_range_grow(D.e, D.cuts[(size_t)i], D.cuts[(size_t)i + 1], D.edges, D.count, D.ms_join))) fail(rc);
-        D.found = D.count;
-        if (!rc && job.wants(AfterJoin::kCut) && D.count) {   // the cut, on my own edges: what follows (gather, sort, copy) sees the kept records only
-            Buf d_cnt, kept;
-            CutPass pass;
-            u64 n_kept = 0;
-            if ((rc = d_cnt.ensure((size_t)N * 4)) || (rc = ksp_memcpy_h2d(d_cnt.p, after->kmer_counts, (u64)N * 4)) ||
-                (rc = cut_count_on_device(D.edges.as<ksp_edge>(), D.count, d_cnt.as<u32>(), after->col, after->cutoff, pass, &n_kept)))
-                fail(rc);
-            else if (n_kept == D.count) {}   // (every record passes: they stay where they are)
-            else if (n_kept == 0) D.count = 0;
-            else if ((rc = kept.ensure(n_kept * sizeof(ksp_edge))) ||   // (sized by the count pass's total, not by the input)
-                     (rc = cut_scatter_on_device(D.edges.as<ksp_edge>(), D.count, d_cnt.as<u32>(), after->col, pass, kept.as<ksp_edge>())))
-                fail(rc);
-            else {
-                D.edges.release();
-                D.edges = kept;
-                kept = Buf();
-                D.count = n_kept;
-            }
-            pass.release(); d_cnt.release(); kept.release();
-        }
-        if (sync_point()) return;
-        if (i == 0) {
-            for (int j = 0; j < nd; ++j) edge_off[(size_t)j + 1] = edge_off[(size_t)j] + dev[(size_t)j].count;
-            total = edge_off[(size_t)nd];
-            if (job.wants(AfterJoin::kCut))
-                for (int j = 0; j < nd; ++j) after->n_found += dev[(size_t)j].found;
-            if (nd > 1 && total && (rc = merged.ensure(total * sizeof(ksp_edge)))) fail(rc);
-        }
-        if (sync_point()) return;
-        if (nd > 1 && D.count &&      // the gather to the first device: one peer copy per device (xGMI)
-            hipMemcpyPeer((char*)merged.p + edge_off[(size_t)i] * sizeof(ksp_edge), devices[0], D.edges.p, device, D.count * sizeof(ksp_edge)) != hipSuccess) {
-            set_error("pairwise: peer copy of the edges failed");
-            fail(KSP_E_HIP);
-        }
-        if (sync_point()) return;
-        if (i == 0) {
-            ksp_edge* d_all = nd > 1 ? merged.as<ksp_edge>() : D.edges.as<ksp_edge>();
-            if (total && (rc = sort_edges_device(d_all, total, N))) { fail(rc); return; }
-            if (after && after->kind != AfterJoin::kNone && after->kind != AfterJoin::kCut) {
-                // from HBM: the same edge records, which never travel to the host and back as text for this
-                AfterJoin& A = *after;
-                Buf d_cnt;
-                const bool run = N && !(rc = d_cnt.ensure((size_t)N * 4)) && !(rc = ksp_memcpy_h2d(d_cnt.p, A.kmer_counts, (u64)N * 4));
-                u32 n_out = 0;   // kRepr: the sources ranked, kTree: the records of the forest
-                switch (A.kind) {
-                    case AfterJoin::kCluster:
-                        A.labels.assign((size_t)N, 0);
-                        if (run) rc = cc_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.cutoff, A.labels.data(), &A.n_kept, A.ksize);
-                        break;
-                    case AfterJoin::kSweep:   // one classification of the records, components continued from rank to rank
-                        A.labels.assign((size_t)A.n_cutoffs * N, 0);
-                        A.kept.assign(A.n_cutoffs, 0);
-                        if (run) rc = sweep_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.cutoffs, A.n_cutoffs, A.labels.data(), A.kept.data());
-                        break;
-                    case AfterJoin::kTree:
-                        A.index.assign((size_t)std::min<u64>(N ? N - 1 : 0, total) + 1, 0);
-                        if (run) rc = tree_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.index.data(), &n_out);
-                        A.index.resize(n_out);
-                        break;
-                    case AfterJoin::kDerep:   // (the ranks go to A.node; without a source nothing is asked)
-                        A.rep.assign((size_t)N, 0); A.via.assign((size_t)N, 0); A.node.assign((size_t)N, 0); A.degree.assign((size_t)N, 0);
-                        if (run) rc = derep_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.threshold, A.rep.data(), A.via.data(), A.node.data(),
-                                                            A.degree.data(), &n_out, &A.derep);
-                        break;
-                    case AfterJoin::kTopk:   // (index: n_sources x k record indices, count: the hits of every source)
-                        A.index.assign((size_t)N * A.k, 0xFFFFFFFFu); A.count.assign((size_t)N, 0);
-                        if (run) rc = topk_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.k, A.index.data(), A.count.data(), &A.topk);
-                        break;
-                    default:   // kRepr
-                        A.node.assign((size_t)N, 0);
-                        A.count.assign((size_t)N, 0);
-                        if (run) rc = repr_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.threshold, nullptr, A.node.data(), A.count.data(), &n_out);
-                        A.node.resize(n_out);
-                        A.count.resize(n_out);
-                }
-                d_cnt.release();
-                if (rc) { fail(rc); return; }
-            }
-            ksp_edge* out = (ksp_edge*)alloc_result(total * sizeof(ksp_edge));
-            if (!out) { set_error("pairwise_host: out of pinned host memory"); fail(KSP_E_LIMIT); return; }
-            if (total && (rc = ksp_memcpy_d2h(out, d_all, total * sizeof(ksp_edge)))) { ksp_free(out); fail(rc); return; }
-            *out_edges = out;
-            *n_edges = total;
-            if (stats) {
-                ksp_engine_get_stats(D.e, stats);
-                stats->ms_join = 0; stats->last_tiles = 0; stats->last_pairs = 0;
-                for (int j = 0; j < nd; ++j) {
-                    stats->ms_join = std::max(stats->ms_join, dev[(size_t)j].ms_join);
-                    stats->last_tiles += dev[(size_t)j].e->st.last_tiles;
-                    stats->last_pairs += dev[(size_t)j].e->st.last_pairs;
-                }
-                stats->last_edges = total;
-            }
-        }
-    };
-    if (nd == 1) body(0);
-    else {
-        std::vector<std::thread> th;
-        for (int i = 0; i < nd; ++i) th.emplace_back(body, i);
-        for (auto& t : th) t.join();
-    }
-    int rc = KSP_OK;
-    for (int i = 0; i < nd; ++i) {
-        Dev& D = dev[(size_t)i];
-        if (D.rc && !rc) { rc = D.rc; set_error(D.err); }
-        if (D.e) (void)hipSetDevice(D.e->device);
-        if (D.d_a && !D.borrowed) (void)hipFree(D.d_a);
-        if (D.d_b && !D.borrowed) (void)hipFree(D.d_b);
-        D.edges.release(); D.labels.release();
-        for (int q = 0; q < 6; ++q) { D.gather[q].release(); D.exp[q].release(); }
-        ksp_engine_destroy(D.e);
-    }
-    if (nd > 1 || merged.p) { (void)hipSetDevice(devices[0]); merged.release(); }
-    if (rc && *out_edges) { ksp_free(*out_edges); *out_edges = nullptr; *n_edges = 0; }
-    return rc;
-}
-
 #ifdef KSP_FKTIME
 int ksp_debug_fktime(unsigned long long* out16, int reset) {
     KSP_HIP(hipDeviceSynchronize());
@@ -3431,73 +2956,5 @@ int ksp_debug_sttime(unsigned long long* out64, int reset) {
     return KSP_OK;
 }
 #endif
-
-}  // extern "C"
-int ksp::pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
-                                    uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
-                                    ksp_stats* stats, AfterJoin* after) {
-    if (!out_edges || !n_edges || !devices || (n_keys && (!key_off || !sources))) { set_error("pairwise_postings_host: NULL argument"); return KSP_E_ARG; }
-    const u64 n = n_keys ? key_off[n_keys] : 0;
-    for (u64 i = 0; i < n; ++i)
-        if (sources[i] >= n_sources) { set_error("pairwise_postings_host: source index out of range"); return KSP_E_ARG; }
-    MultiJob job;
-    job.postings = true;
-    job.key_off = key_off; job.sources = sources; job.key_weights = key_weights; job.n_keys = n_keys; job.n_sources = n_sources;
-    job.after = after;
-    return run_multi(job, devices, n_devices, out_edges, n_edges, stats);
-}
-extern "C" {
-
-int ksp_pairwise_host_multi(const uint64_t* keys, const uint32_t* weights, const uint64_t* offsets, uint32_t n_sources,
-                            const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges, ksp_stats* stats) {
-    if (!offsets || !out_edges || !n_edges || !devices) { set_error("pairwise_host: NULL argument"); return KSP_E_ARG; }
-    MultiJob job;
-    job.keys = keys; job.weights = weights; job.offsets = offsets; job.n_sources = n_sources;
-    return run_multi(job, devices, n_devices, out_edges, n_edges, stats);
-}
-
-int ksp_pairwise_host_cut(const uint64_t* keys, const uint32_t* weights, const uint64_t* offsets, uint32_t n_sources,
-                          const uint32_t* kmer_counts, int dist_col, double cutoff, const int* devices, int n_devices,
-                          ksp_edge** out_edges, uint64_t* n_edges, uint64_t* n_found, ksp_stats* stats) {
-    if (!offsets || !out_edges || !n_edges || !devices) { set_error("ksp_pairwise_host_cut: NULL argument"); return KSP_E_ARG; }
-    if (dist_col < 3 || dist_col > 5) { set_error("ksp_pairwise_host_cut: dist_col is 3 (min), 4 (avg) or 5 (max containment)"); return KSP_E_ARG; }
-    if (cutoff != cutoff) { set_error("ksp_pairwise_host_cut: the cut-off is NaN"); return KSP_E_ARG; }
-    std::vector<u32> lengths;
-    if (!kmer_counts) {   // the k-mer count of a source is the length of its run
-        lengths.resize(n_sources);
-        for (u32 v = 0; v < n_sources; ++v) {
-            const u64 len = offsets[v + 1] - offsets[v];
-            if (len > 0xFFFFFFFFull) { set_error("ksp_pairwise_host_cut: a run of 2^32 keys or more"); return KSP_E_LIMIT; }
-            lengths[v] = (u32)len;
-        }
-        kmer_counts = lengths.data();
-    }
-    AfterJoin cut;
-    cut.kind = AfterJoin::kCut; cut.kmer_counts = kmer_counts; cut.col = dist_col; cut.cutoff = cutoff;
-    MultiJob job;
-    job.keys = keys; job.weights = weights; job.offsets = offsets; job.n_sources = n_sources;
-    job.after = &cut;
-    if (n_found) *n_found = 0;
-    const int rc = run_multi(job, devices, n_devices, out_edges, n_edges, stats);
-    if (!rc && n_found) *n_found = cut.n_found;
-    return rc;
-}
-
-int ksp_pairwise_postings_host_multi(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights,
-                                     uint32_t n_keys, uint32_t n_sources, const int* devices, int n_devices,
-                                     ksp_edge** out_edges, uint64_t* n_edges, ksp_stats* stats) {
-    return ksp::pairwise_postings_multi_cc(key_off, sources, key_weights, n_keys, n_sources, devices, n_devices, out_edges, n_edges, stats, nullptr);
-}
-
-int ksp_pairwise_host(const uint64_t* keys, const uint32_t* weights, const uint64_t* offsets, uint32_t n_sources,
-                      int device, ksp_edge** out_edges, uint64_t* n_edges, ksp_stats* stats) {
-    return ksp_pairwise_host_multi(keys, weights, offsets, n_sources, &device, 1, out_edges, n_edges, stats);
-}
-
-int ksp_pairwise_postings_host(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights,
-                               uint32_t n_keys, uint32_t n_sources, int device, ksp_edge** out_edges,
-                               uint64_t* n_edges, ksp_stats* stats) {
-    return ksp_pairwise_postings_host_multi(key_off, sources, key_weights, n_keys, n_sources, &device, 1, out_edges, n_edges, stats);
-}
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// Internal declarations shared by the engine (engine.hip) and the host-side
-// reference surface (pairwise_host.cpp).  Not part of the C ABI.
+// Internal declarations shared by the engine (engine.hip), the multi-device job (multi.hip), the consumers of the
+// join's edges and the host-side reference surface (pairwise_host.cpp).  Not part of the C ABI.
 #ifndef KSPIDER_ENGINE_INTERNAL_H
 #define KSPIDER_ENGINE_INTERNAL_H
 #include <cstdint>

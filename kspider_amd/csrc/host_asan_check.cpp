@@ -3,6 +3,9 @@
 //                   | cut PREFIX DIST CUTOFF | edges_cut X | host_cut X   (the last two: the entry point with nothing to do)
 //                   | partial DIR   (partial_file.h itself in DIR, which holds only the directory d.tsv with a file in it: one
 //                                    "ok" / "FAIL" line per case)
+//                   | plan sketch N DEVICES | plan postings DEVICES COUNT...   (slice_plan.h with $KSP_SLICES: the slices of N key
+//                                    entries, or of an index whose keys have COUNT members each, on the devices "0,1,...": the
+//                                    lines "slices S", "devices d0 d1 ...", "cuts c0 c1 ..." and "sliced 0|1", then the rc line)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -10,9 +13,11 @@
 #include <sstream>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/kspider_amd.h"
 #include "partial_file.h"
+#include "slice_plan.h"
 
 namespace {
 bool exists(const std::string& path) { return (bool)std::ifstream(path); }
@@ -82,13 +87,34 @@ int check_partial_files(const std::string& dir) {
     }
     return 0;
 }
+
+int print_plan(const int argc, char** argv) {
+    const bool postings = !std::strcmp(argv[2], "postings");
+    std::vector<int> devices;
+    for (const char* p = argv[postings ? 3 : 4]; *p; p += std::strcspn(p, ","), p += *p == ',') devices.push_back(std::atoi(p));
+    std::vector<uint64_t> key_off(1, 0);
+    for (int a = 4; postings && a < argc; ++a) key_off.push_back(key_off.back() + std::strtoull(argv[a], nullptr, 10));
+    const uint64_t n = postings ? key_off.back() : std::strtoull(argv[3], nullptr, 10);
+    ksp::SlicePlan plan;
+    const uint32_t n_keys = (uint32_t)key_off.size() - 1;   // (no COUNT: an index without keys, whose key_off may be NULL)
+    const int rc = ksp::plan_slices(postings, n, n_keys, postings && n_keys ? key_off.data() : nullptr, devices.data(), (int)devices.size(),
+                                    std::getenv("KSP_SLICES"), plan);
+    if (rc) return rc;
+    std::printf("slices %zu\ndevices", plan.devices.size());
+    for (const int d : plan.devices) std::printf(" %d", d);
+    std::printf("\ncuts");
+    for (const uint32_t c : plan.pk_cut) std::printf(" %u", c);
+    std::printf("\nsliced %d\n", (int)plan.sliced);
+    return rc;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc < 3) return 64;
     int rc = -1;
     if (!std::strcmp(argv[1], "partial")) return check_partial_files(argv[2]);
-    if (!std::strcmp(argv[1], "index")) rc = kspider_pairwise(argv[2], 2);
+    if (!std::strcmp(argv[1], "plan") && argc >= (std::strcmp(argv[2], "postings") ? 5 : 4)) rc = print_plan(argc, argv);
+    else if (!std::strcmp(argv[1], "index")) rc = kspider_pairwise(argv[2], 2);
     else if (!std::strcmp(argv[1], "info")) { uint64_t out[6]; rc = ksp_index_info(argv[2], out); if (!rc) std::printf("info %llu %llu %llu %llu %llu %llu\n", (unsigned long long)out[0], (unsigned long long)out[1], (unsigned long long)out[2], (unsigned long long)out[3], (unsigned long long)out[4], (unsigned long long)out[5]); }
     else if (!std::strcmp(argv[1], "sigs") && argc >= 5) rc = kspider_pairwise_sigs(argv[2], std::atoi(argv[3]), argv[4], 2);
     else if (!std::strcmp(argv[1], "bins") && argc >= 4) rc = kspider_pairwise_bins(argv[2], argv[3], 2);

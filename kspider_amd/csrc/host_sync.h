@@ -1,4 +1,4 @@
-// Synchronisation of the per-device host threads of a multi-GPU call (run_multi in engine.hip; one thread + one
+// Synchronisation of the per-device host threads of a multi-GPU call (run_multi in multi.hip; one thread + one
 // engine per device where the reference has one OpenMP team, src/pairwise.cpp:199-203).  Host-only C++17: also
 // compiled by the sanitizer build, whose check program injects a failure at every stage (tests/test_host_hardening_cpu.py).
 #ifndef KSPIDER_HOST_SYNC_H
@@ -8,6 +8,10 @@
 #include <mutex>
 
 namespace ksp {
+
+// the steps of a worker of run_multi, each with a sync point behind it (multi.hip asserts that its step list has this length;
+// host_sync_check.cpp runs its skeleton of the loop with as many stages)
+constexpr int kMultiSteps = 14;
 
 // A barrier that also carries the "somebody failed" decision.  The decision is taken ONCE per barrier generation, by
 // the thread that arrives last, under the mutex; every thread of that generation returns that same value.  (Reading a

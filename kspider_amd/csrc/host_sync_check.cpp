@@ -1,8 +1,9 @@
-// Check program of host_sync.h (make asan): the thread / barrier skeleton of run_multi (engine.hip) — every worker
-// runs the same sequence of stages with a sync point behind each — with a failure injected into one worker at one
-// stage, the others delayed at random so that fast threads run ahead of slow ones.  Every run must end with all
-// workers returned (no thread left waiting at a barrier) and with the failure reported; a watchdog turns a hang into
-// a non-zero exit.  tests/test_host_hardening_cpu.py runs it.
+// Check program of host_sync.h (make asan): the thread / barrier skeleton of run_multi (Worker::run in multi.hip) — every
+// worker runs the same list of steps, each skipped once a failure is known, with a sync point behind each — with as many
+// stages as that list has (ksp::kMultiSteps) and a failure injected into one worker at one stage, the others delayed at
+// random so that fast threads run ahead of slow ones.  Every run must end with all workers returned (no thread left
+// waiting at a barrier) and with the failure reported; a watchdog turns a hang into a non-zero exit.
+// tests/test_host_hardening_cpu.py runs it.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -49,7 +50,7 @@ int main(int argc, char** argv) {
         if (!done.load()) { std::printf("HANG: a worker is still waiting at a barrier\n"); std::fflush(stdout); std::_Exit(3); }
     });
     int bad = 0, runs = 0;
-    const int stages = 12;   // (run_multi has up to 12 sync points on the sketch path)
+    const int stages = ksp::kMultiSteps;   // (a job that is not sliced skips some, every worker the same ones)
     for (int r = 0; r < rounds && !bad; ++r)
         for (int nd : {1, 2, 3, 5, 8}) {
             if (run_once(nd, stages, -1, -1, (unsigned)r) != 0) { bad = 1; break; }   // no failure: all stages run

@@ -1,4 +1,4 @@
-"""The sliced stage 1 driven call by call on one GPU, as run_multi (engine.hip) and kspider_amd/dist.py drive it between
+"""The sliced stage 1 driven call by call on one GPU, as run_multi (multi.hip) and kspider_amd/dist.py drive it between
 devices: build every slice up to its labels, MIN-combine the labels (for slices of an inverted index also SUM-combine
 the counter bounds), finish every slice in that source order, export, stack the slices as the exchange would, assemble,
 join."""

@@ -3,7 +3,7 @@
 Sketch input (engine.hip, build_impl in slice mode): the keys of [0, span) are shared out in key order, span being the
 largest key + 1, or 2^key_bits when the caller fixed key_bits.  The contract restated here is a partition: part p holds
 the keys span * p // nparts <= k < span * (p + 1) // nparts (an empty range when span < nparts leaves nothing for it).
-Postings input (engine.hip, run_multi): whole keys, cut where the memberships reach s / nd of all of them.
+Postings input (slice_plan.h, the plan of run_multi in multi.hip): whole keys, cut where the memberships reach s / nd of all of them.
 """
 import numpy as np
 

@@ -200,10 +200,11 @@ def test_partial_files_commit_or_leave_nothing(exe, tmp_path):
 
 
 def test_multi_device_barrier_returns_on_an_injected_failure_at_every_stage(exe):
-    """run_multi's host threads (one per device; kspider_amd/csrc/engine.hip) meet at ksp::FailBarrier sync points.  A
-    failure injected into any worker at any of the 12 stages must make EVERY worker return at the sync point behind
-    that stage — none left waiting at a later barrier (the round-2 race: a flag read after leaving a plain barrier).
-    ThreadSanitizer build; a watchdog inside the program turns a hang into exit code 3."""
+    """run_multi's host threads (one per device; kspider_amd/csrc/multi.hip) meet at ksp::FailBarrier sync points.  A
+    failure injected into any worker at any of the stages (ksp::kMultiSteps, the length of run_multi's step list) must
+    make EVERY worker return at the sync point behind that stage — none left waiting at a later barrier (the round-2
+    race: a flag read after leaving a plain barrier).  ThreadSanitizer build; a watchdog inside the program turns a
+    hang into exit code 3."""
     check = os.path.join(os.path.dirname(exe), "host_sync_check")
     # (address randomisation off for this one process: g++'s TSan runtime dies at start-up with "unexpected memory
     #  mapping" when the kernel randomises mmap with more than 28 bits, vm.mmap_rnd_bits)

@@ -82,6 +82,37 @@ def test_dropin_tsv_bytes_equal_under_kspider_devices(oracle_lib, tmp_path):
     assert p.returncode != 0 and not os.path.exists(prefix + "_kSpider_pairwise.tsv")
 
 
+def test_a_failing_worker_ends_the_call_and_leaves_the_next_one_whole():
+    """The failure path inside one process (the child process above cannot show a thread left at a barrier, or state that
+    leaks into the next call): the middle worker of three cannot create its engine (device 99 does not exist: an error return
+    of the runtime, no fault), every worker leaves at the sync point behind that step and the call raises with that worker's
+    text; the next call, on three workers that exist, returns the single-device edges."""
+    sk = synth.generate("C2", n_sources=300, mean_size=200, cluster_cap=20, seed=815)
+    one, _ = engine.pairwise_host(sk.keys, sk.offsets)
+    with pytest.raises(engine.KspError) as err:
+        engine.pairwise_host(sk.keys, sk.offsets, devices=[0, 99, 0])
+    assert "no such device" in str(err.value), err.value
+    again, st = engine.pairwise_host(sk.keys, sk.offsets, devices=[0, 0, 0])
+    assert len(one) == len(again) > 0 and (one == again).all()
+    assert st["last_edges"] == len(again)
+
+
+def test_an_index_without_keys_on_several_devices(monkeypatch):
+    """0 keys with a NULL key_off, which the entry point admits: one whole (empty) build per device, on two devices and
+    under KSP_SLICES, and no edges."""
+    import ctypes
+    for devices, slices in (([0, 0], None), ([0], "3"), ([0, 0, 0], "5")):
+        if slices:
+            monkeypatch.setenv("KSP_SLICES", slices)
+        else:
+            monkeypatch.delenv("KSP_SLICES", raising=False)
+        out, n = ctypes.c_void_p(), ctypes.c_uint64(7)
+        devs = (ctypes.c_int * len(devices))(*devices)
+        rc = engine.lib().ksp_pairwise_postings_host_multi(None, None, None, 0, 4, devs, len(devs), ctypes.byref(out), ctypes.byref(n), None)
+        engine.lib().ksp_free(out)
+        assert rc == 0 and n.value == 0, (devices, slices, rc)
+
+
 def test_forced_slices_on_one_device(oracle_lib, monkeypatch):
     """$KSP_SLICES: the sequential-slice path that lifts the 2^30-entry limit of one build, on a small set."""
     sk = synth.generate("C2", n_sources=700, mean_size=600, cluster_cap=40, seed=812)

@@ -475,8 +475,8 @@ def _postings_input(counts, n_sources, seed=0, same_block=None):
 
 
 def _check_postings(monkeypatch, key_off, sources, who, n_sources, nd, what, env=None):
-    """run_multi's own pk_cut is covered through the edge sets of the KSP_SLICES / devices runs only (the host entry
-    reports no per-slice figure); the driver is handed the restatement's cuts, so its slice_sizes()[1] == keys per
+    """run_multi's own pk_cut is covered here through the edge sets of the KSP_SLICES / devices runs (the host entry reports
+    no per-slice figure) and as numbers on the CPU (tests/test_slice_plan_cpu.py); the driver is handed the restatement's cuts, so its slice_sizes()[1] == keys per
     slice shows what that slot means for postings slices and that slices cut there assemble to the right result."""
     env = env or {}
     n_keys = key_off.size - 1
