@@ -632,6 +632,29 @@ int ksp_topk_ranked(int device, uint32_t n_nodes, const uint32_t* h_a, const uin
 int kspider_topk(const char* index_prefix, const char* dist_type, uint32_t k, const char* out_path);
 int kspider_pairwise_and_topk(const char* index_prefix, int user_threads, const char* dist_type, uint32_t k, const char* out_path);
 
+/* ---- the rows of the pairwise TSV as text, made on the device (csrc/tsv.hip) ----
+ * ksp_edges_tsv: the text of `n_edges` ksp_edge records in DEVICE memory (never written), in their order, rows only, no header:
+ *       id1 \t id2 \t shared \t min \t avg \t max \n
+ *   byte for byte what the pairwise writer prints for the record: id = d_ids[source] (device, n_nodes entries), or the source
+ *   index itself when d_ids is NULL; shared in decimal; the three containments in the writer's single-precision maths from
+ *   d_kmer_counts (device, n_nodes entries), each as `std::ostream << float` prints it (ksp_format_float, "%.6g"): the digits come
+ *   from integer arithmetic on the float's exact binary value, rounded to nearest, ties to even (csrc/tsv_text.h).
+ *   *n_bytes = the bytes of the text.  h_text NULL: the size query, nothing is written.  capacity < *n_bytes: KSP_E_OVERFLOW,
+ *   *n_bytes is set and nothing is written.  Otherwise h_text (host) receives exactly *n_bytes bytes, no terminator.  A row is
+ *   KSP_TSV_ROW_MIN = 12 to KSP_TSV_ROW_MAX = 79 bytes (two ids of 10 digits, a count of 20, three floats of 11, six
+ *   separators), so 79 * n_edges always suffices; byte counts and offsets are 64-bit throughout.  n_edges = 0: 0 bytes, no
+ *   kernel runs.  KSP_E_ARG, with nothing written, for a NULL d_kmer_counts or n_bytes, a NULL d_edges with n_edges > 0, and
+ *   — found on the device — a record naming a source >= n_nodes, a row with a NaN column (shared = 0 beside a count of 0: its
+ *   text is the host libc's business) and a column outside the formatter's domain: 0, +inf and the positive floats in
+ *   [2^-40, 2^40) (no record with counts and sums below 2^32 leaves it).  Rows are taken in chunks of KSP_TSV_CHUNK_ROWS;
+ *   the text leaves the device through a window in HBM and from there in pieces of $KSP_TSV_PIECE bytes (default 8 MiB;
+ *   tests: any size >= 1, pieces end inside rows) through two pinned staging buffers, as ksp_engine_join_to_host moves edges.
+ *   $KSP_TSV_MAX_WORKGROUPS caps the grids (tests).  $KSPIDER_TSV=device makes the drop-in calls (kspider_pairwise and its
+ *   _cut / _and_* siblings over an index) write PREFIX_kSpider_pairwise.tsv from this text: the same bytes, see DESIGN.md 7k. */
+#define KSP_TSV_CHUNK_ROWS 256u
+int ksp_edges_tsv(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
+                  const uint32_t* d_ids, char* h_text, uint64_t capacity, uint64_t* n_bytes);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

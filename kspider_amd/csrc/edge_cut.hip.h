@@ -20,6 +20,16 @@ __device__ inline float edge_col_value(const ksp_edge& x, const uint32_t* __rest
     return v;
 }
 
+// Columns 3, 4 and 5 of edge x at once, from one pair of divisions: the same operations in the same order as edge_col_value
+// (and as the writer), so each value is bit for bit the one edge_col_value returns for its column.
+__device__ inline void edge_col_values(const ksp_edge& x, const uint32_t* __restrict__ cnt, float* mn, float* av, float* mx) {
+    const float n1 = (float)cnt[x.source_1], n2 = (float)cnt[x.source_2];
+    const float c12 = (float)x.shared / n2, c21 = (float)x.shared / n1;
+    *mn = c21 < c12 ? c21 : c12;                   // std::min(c12, c21)
+    *av = (float)((double)(c12 + c21) / 2.0);
+    *mx = c12 < c21 ? c21 : c12;                   // std::max(c12, c21)
+}
+
 // An edge counts for the clustering when its containment column is not below the cut.  `vcrit` is the smallest float the
 // reference's test (text of the float with 6 significant digits -> Python float -> x 100 -> not below cutoff x 100,
 // ks_clustering.py:101-105) lets through: that test is monotone in the float, so one compare against the critical value

@@ -3,6 +3,7 @@
 #ifndef KSPIDER_ENGINE_INTERNAL_H
 #define KSPIDER_ENGINE_INTERNAL_H
 #include <cstdint>
+#include <functional>
 #include <string>
 
 #include "../../include/kspider_amd.h"
@@ -106,6 +107,15 @@ int topk_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_e
 // the names; count[v]: the hits of name v, neighbour / text: the other end and the value text of every hit, flat in that order
 void write_topk_file(const std::string& out_path, const std::string& dist, const std::vector<std::string>& name_of, const std::vector<uint32_t>& count,
                      const std::vector<uint32_t>& neighbour, const std::vector<std::string>& text);
+// ---- the rows of the pairwise TSV as text, made on the device from the join's edges (tsv.hip) ----
+// takes the next piece of the text (it lives until the call returns); a code other than KSP_OK, with its text in
+// ksp_last_error(), ends the pass
+typedef std::function<int(const char*, uint64_t)> TsvSink;
+// ksp_edges_tsv on the CURRENT device: *n_bytes = the bytes of the text; sink NULL: nothing else (the size query), otherwise the
+// text goes to *sink in order, in pieces of at most $KSP_TSV_PIECE bytes, unless capacity < *n_bytes (KSP_E_OVERFLOW, nothing
+// is handed out).  d_ids NULL: a source's id is its index.  ms_kernels (may be NULL): the device time of the passes.
+int tsv_edges_on_device(const char* who, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, const uint32_t* d_ids,
+                        uint64_t capacity, const TsvSink* sink, uint64_t* n_bytes, float* ms_kernels = nullptr);
 // ---- what a job wants from its edges besides the edges themselves: one kind per job ----
 // kCut: only the edges that pass a containment cut are wanted, so every device cuts its own directly after its join and only the
 // kept ones are gathered, sorted and copied.  The other kinds are taken from the sorted edges on the first device, while they
@@ -134,6 +144,15 @@ struct AfterJoin {
     DerepTrace derep;                        //   the ranks are in `node` (rank[v]); what the selection did
     TopkTrace topk;                          // kTopk: per source index its hits in `index` (n_sources x k records of the returned edges) and
                                              //   their number in `count`; what the selection did
+    // The rows' text, wanted besides whatever `kind` asks for (KSPIDER_TSV=device): the text pass runs on the first device over
+    // the gathered, sorted edges, after the consumer.  ids: the id of every source index (n_sources entries).  text_sink takes
+    // the pieces in file order.  With kNone and kCut nobody reads the records afterwards, so they are not copied to the host:
+    // the job returns no edges (an empty array) with their number.
+    bool want_text = false;
+    const uint32_t* ids = nullptr;
+    TsvSink text_sink;
+    uint64_t text_bytes = 0;                 // out: the bytes handed to text_sink
+    bool edges_skipped = false;              // out: the records stayed on the device
 };
 int pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
@@ -169,5 +188,19 @@ int ksp_debug_topk_classes(uint64_t out[4]);
  * 1 = rocprim::segmented_radix_sort_keys and a gather (KSP_TOPK_SELECT=library). */
 int ksp_debug_topk_times(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col,
                          uint32_t k, int which, int reps, float* ms, uint32_t* h_index, uint32_t* h_count);
+/* (tests) the device's "%.6g" (tsv_text.h) on n host floats: h_text[16 * i ...] holds the h_len[i] bytes of value i's text.  KSP_E_ARG,
+ * with nothing written, when a value is outside the domain: 0, +inf and the positive floats in [2^-40, 2^40). */
+int ksp_debug_format_floats(int device, const float* h_values, uint64_t n, char* h_text /* n x 16 */, uint32_t* h_len);
+/* (tests) the yardstick in the same layout: ksp_format_float (the host's snprintf) on every value; KSP_E_ARG for a text above 16 bytes. */
+int ksp_debug_format_floats_host(const float* h_values, uint64_t n, char* h_text /* n x 16 */, uint32_t* h_len);
+/* (tools/tsv_times.py) valid seeded inputs of the timing, made on the device: ids index + 1, counts of 10^3 .. 10^6, n_edges records with
+ * source_1 ascending and below source_2 and a shared count of 1 .. the smaller count.  All three arrays are device memory. */
+int ksp_debug_tsv_records(int device, uint32_t n_nodes, uint64_t n_edges, uint64_t seed, ksp_edge* d_edges, uint32_t* d_kmer_counts, uint32_t* d_ids);
+/* (tools/tsv_times.py) `reps` runs of one way from the records in device memory to the rows' text in host memory, without a file:
+ * which 0 = the device's text kernels and the copy of the text to pinned host memory, 1 = the copy of the records to pinned host
+ * memory and the host writer's formatting (index_io.cpp format_rows) with `threads` host threads.  ms holds 2 x reps values:
+ * ms[2r] the wall time of run r, ms[2r + 1] which 0: the kernels' own time by HIP events, which 1: the time of the copy. */
+int ksp_debug_tsv_times(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, const uint32_t* d_ids,
+                        int which, int reps, int threads, float* ms);
 }
 #endif

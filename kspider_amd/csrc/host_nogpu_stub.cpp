@@ -79,6 +79,22 @@ int ksp_pairwise_host_cut(const uint64_t*, const uint32_t*, const uint64_t*, uin
     ksp::set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }
+int ksp_edges_tsv(int, uint32_t, const ksp_edge*, uint64_t, const uint32_t*, const uint32_t*, char*, uint64_t, uint64_t*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_debug_format_floats(int, const float*, uint64_t, char*, uint32_t*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_debug_tsv_records(int, uint32_t, uint64_t, uint64_t, ksp_edge*, uint32_t*, uint32_t*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_debug_tsv_times(int, uint32_t, const ksp_edge*, uint64_t, const uint32_t*, const uint32_t*, int, int, int, float*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
 void ksp_free(void* p) { std::free(p); }
 int ksp_engine_lists_path(const ksp_engine*, int*) {
     ksp::set_error("host-only sanitizer build: no HIP engine");

@@ -299,7 +299,6 @@ int format_float(char* buf, float v) {
     return std::snprintf(buf, 32, "%.6g", (double)v);
 }
 
-namespace {
 void format_rows(const std::vector<EdgeRow>& rows, size_t lo, size_t hi,
                  const std::unordered_map<uint32_t, uint32_t>& kmer_count, std::string& out) {
     out.reserve((hi - lo) * 56);
@@ -327,7 +326,20 @@ void format_rows(const std::vector<EdgeRow>& rows, size_t lo, size_t hi,
         out.append(buf, (size_t)n);
     }
 }
-}  // namespace
+
+namespace {
+const char kPairwiseHeader[] = "source_1\tsource_2\tshared_kmers\tmin_containment\tavg_containment\tmax_containment\n";
+}
+
+PairwiseTsvPieces::PairwiseTsvPieces(const std::string& prefix) : path_(prefix + "_kSpider_pairwise.tsv") {
+    files_.open(path_, f_);
+    f_ << kPairwiseHeader;
+}
+void PairwiseTsvPieces::append(const char* text, const uint64_t n) {
+    if (n && !f_.write(text, (std::streamsize)n)) throw std::runtime_error("write error on " + path_);
+    bytes_ += n;
+}
+void PairwiseTsvPieces::commit() { files_.commit(); }
 
 void write_pairwise_tsv(const std::string& prefix, const std::vector<EdgeRow>& rows,
                         const std::unordered_map<uint32_t, uint32_t>& kmer_count, int threads) {
@@ -337,7 +349,7 @@ void write_pairwise_tsv(const std::string& prefix, const std::vector<EdgeRow>& r
     std::ofstream f;
     PartialFiles files;   // never a partial TSV under the final name
     files.open(path, f);
-    f << "source_1\tsource_2\tshared_kmers\tmin_containment\tavg_containment\tmax_containment\n";
+    f << kPairwiseHeader;
     // format T chunks at a time in parallel, write them in order
     for (size_t base = 0; base < rows.size(); base += chunk * T) {
         std::vector<std::string> parts(T);

@@ -3,10 +3,13 @@
 #ifndef KSPIDER_INDEX_IO_H
 #define KSPIDER_INDEX_IO_H
 #include <cstdint>
+#include <fstream>
 #include <string>
 #include <unordered_map>
 #include <utility>
 #include <vector>
+
+#include "partial_file.h"
 
 namespace ksp {
 
@@ -55,6 +58,26 @@ struct EdgeRow {
 // order they are to be written.  n1/n2 = k-mer counts of the two sources.
 void write_pairwise_tsv(const std::string& prefix, const std::vector<EdgeRow>& rows,
                         const std::unordered_map<uint32_t, uint32_t>& kmer_count, int threads);
+
+// the text of rows [lo, hi) appended to out, as write_pairwise_tsv writes it
+void format_rows(const std::vector<EdgeRow>& rows, size_t lo, size_t hi, const std::unordered_map<uint32_t, uint32_t>& kmer_count, std::string& out);
+
+// The same file from row text that somebody else made and hands over in pieces, in order (the device: tsv.hip).  The
+// constructor opens PREFIX_kSpider_pairwise.tsv.partial and writes the header; append() takes a piece, which may end anywhere,
+// inside a row too; commit() renames.  Without a commit the destructor removes the partial file: never a partial TSV under
+// the final name.  Throws std::runtime_error as write_pairwise_tsv does.
+class PairwiseTsvPieces {
+    std::string path_;
+    std::ofstream f_;
+    PartialFiles files_;
+    uint64_t bytes_ = 0;
+
+public:
+    explicit PairwiseTsvPieces(const std::string& prefix);
+    void append(const char* text, uint64_t n);
+    void commit();
+    uint64_t bytes() const { return bytes_; }   // of the rows, without the header
+};
 
 // One phmap::flat_hash_set<uint64_t> dump (a sketch ".bin": sigs_to_bins.cpp:113-136,
 // src/bins_indexing.cpp:178-180) -> its hashes in slot order.

@@ -128,7 +128,24 @@ static int after_join_check(const AfterJoin* after) {
         set_error("pairwise: a cut-off ladder has between 1 and 255 cut-offs");
         return KSP_E_ARG;
     }
+    if (after->want_text && (!after->kmer_counts || !after->ids || !after->text_sink)) { set_error("pairwise: the rows' text needs the k-mer counts, the ids and a sink"); return KSP_E_ARG; }
     return KSP_OK;
+}
+// the rows' text (AfterJoin::want_text) from the sorted edges on the current device, piece by piece into the job's sink
+static int after_join_text(AfterJoin& A, const u32 N, const ksp_edge* d_all, const u64 total) {
+    A.text_bytes = 0;
+    if (!N || !total) return KSP_OK;
+    Buf d_cnt, d_ids;
+    u64 n_bytes = 0, handed = 0;
+    const TsvSink sink = [&](const char* p, const uint64_t n) { handed += n; return A.text_sink(p, n); };
+    int rc;
+    if ((rc = d_cnt.ensure((size_t)N * 4)) || (rc = d_ids.ensure((size_t)N * 4)) || (rc = ksp_memcpy_h2d(d_cnt.p, A.kmer_counts, (u64)N * 4)) ||
+        (rc = ksp_memcpy_h2d(d_ids.p, A.ids, (u64)N * 4)) ||
+        (rc = tsv_edges_on_device("pairwise (KSPIDER_TSV=device)", N, d_all, total, d_cnt.as<u32>(), d_ids.as<u32>(), ~0ull, &sink, &n_bytes))) {}
+    else if (handed != n_bytes) { set_error("pairwise (KSPIDER_TSV=device): the pieces do not add up to the text"); rc = KSP_E_HIP; }
+    A.text_bytes = handed;
+    d_cnt.release(); d_ids.release();
+    return rc;
 }
 // the consumers of the sorted edges (every kind but kNone and kCut, which is applied before the gather), on the current device,
 // from HBM: the same edge records, which never travel to the host and back as text for this
@@ -409,9 +426,14 @@ struct Worker {
         int rc;
         if (total && (rc = sort_edges_device(d_all, total, R->N))) return rc;
         if (R->job.after && (rc = after_join_run(*R->job.after, R->N, d_all, total))) return rc;
-        ksp_edge* out = (ksp_edge*)alloc_result(total * sizeof(ksp_edge));
+        bool skip_copy = false;   // the device wrote the rows and no finisher reads the records: they stay where they are
+        if (AfterJoin* const after = R->job.after; after && after->want_text) {
+            if ((rc = after_join_text(*after, R->N, d_all, total))) return rc;
+            skip_copy = after->edges_skipped = after->kind == AfterJoin::kNone || after->kind == AfterJoin::kCut;
+        }
+        ksp_edge* out = (ksp_edge*)alloc_result(skip_copy ? 0 : total * sizeof(ksp_edge));
         if (!out) { set_error("pairwise_host: out of pinned host memory"); return KSP_E_LIMIT; }
-        if (total && (rc = ksp_memcpy_d2h(out, d_all, total * sizeof(ksp_edge)))) { ksp_free(out); return rc; }
+        if (total && !skip_copy && (rc = ksp_memcpy_d2h(out, d_all, total * sizeof(ksp_edge)))) { ksp_free(out); return rc; }
         *R->out_edges = out;
         *R->n_edges = total;
         if (ksp_stats* stats = R->stats) {

@@ -542,6 +542,14 @@ void finish_topk(PairwiseJob& job, const Postings& P, const TopkHits& H, const s
 // Mirrors src/pairwise.cpp:123-276 phase by phase (the head of this file), with what job.after asks for between the join and the files.
 int run_job(PairwiseJob& job) {
     AfterJoin& A = job.after;
+    // $KSPIDER_TSV, read once, before anything is read or written: who makes the rows' text of the pairwise TSV
+    bool device_tsv = false;
+    std::string host_reason;   // why the host writes although the device was asked
+    if (const char* tv = std::getenv("KSPIDER_TSV"); tv && *tv && std::strcmp(tv, "host") != 0) {
+        if (std::strcmp(tv, "device") != 0) { ksp::set_error("pairwise: KSPIDER_TSV is 'host' or 'device', not '" + std::string(tv) + "'"); return KSP_E_ARG; }
+        device_tsv = true;
+    }
+    const bool tsv_asked = device_tsv;
     std::shared_ptr<const std::vector<double>> ani_tab;
     if (job.ani) {   // before anything is read or written: the k-mer size (:44-46) and its table
         A.ksize = ksp::read_extra_ksize(job.prefix);
@@ -564,13 +572,33 @@ int run_job(PairwiseJob& job) {
     const std::vector<int> devices = ksp::devices_from_env();
     ksp_stats st;
     auto t1 = Clock::now();
-    if (A.kind != AfterJoin::kNone) {
+    if (A.kind != AfterJoin::kNone || device_tsv) {
         P.counts.resize(N);
         for (uint32_t i = 0; i < N; ++i) {
             auto it = kmer_count.find(P.ids[i]);
             P.counts[i] = it == kmer_count.end() ? 0u : it->second;   // (a missing group counts 0 k-mers, as operator[] of the reference yields)
         }
         A.kmer_counts = P.counts.data();
+    }
+    // The device writes the rows only where its text is exactly the host's: no shared-0 rows to splice in, no row with a NaN
+    // (no source of 0 k-mers), and no ANI column, which reads the rows on the host.
+    if (device_tsv && job.ani) { device_tsv = false; host_reason = "the ANI column reads the rows on the host"; }
+    if (device_tsv && !P.zero_pairs.empty()) { device_tsv = false; host_reason = "rows of weight-0 colours are spliced in on the host"; }
+    if (device_tsv && std::find(P.counts.begin(), P.counts.end(), 0u) != P.counts.end()) { device_tsv = false; host_reason = "a source has 0 k-mers"; }
+    std::unique_ptr<ksp::PairwiseTsvPieces> pieces;   // (abandoned, and its .partial removed, on every way out before the commit)
+    if (device_tsv) {
+        pieces.reset(new ksp::PairwiseTsvPieces(job.prefix));
+        A.want_text = true;
+        A.ids = P.ids.data();
+        A.text_sink = [&pieces](const char* text, const uint64_t n) {
+            try {
+                pieces->append(text, n);
+            } catch (const std::exception& e) {
+                ksp::set_error(e.what());
+                return (int)KSP_E_IO;
+            }
+            return (int)KSP_OK;
+        };
     }
     ksp_edge* pinned = nullptr;
     uint64_t n_edges = 0;
@@ -583,7 +611,9 @@ int run_job(PairwiseJob& job) {
     if (A.kind == AfterJoin::kTree) forest = device_forest(A, P, edges.get(), n_edges);
     if (A.kind == AfterJoin::kDerep) derep_text = derep_texts(A, P, edges.get(), n_edges);
     std::vector<ksp::EdgeRow> rows;
-    const std::vector<ZeroRow> zero_rows = merge_rows(ix, P, A, edges.get(), n_edges, rows);
+    // (the device wrote the rows: there is no shared-0 row, and nobody reads `rows`)
+    const std::vector<ZeroRow> zero_rows = device_tsv ? std::vector<ZeroRow>() : merge_rows(ix, P, A, edges.get(), n_edges, rows);
+    const uint64_t n_rows = device_tsv ? n_edges : rows.size();
     TopkHits topk_hits;
     if (A.kind == AfterJoin::kTopk) topk_hits = device_topk(A, P, edges.get(), n_edges, zero_rows);
     edges.reset();
@@ -593,20 +623,25 @@ int run_job(PairwiseJob& job) {
         std::cout << "kspider_amd: postings from the colour index " << t_transpose << " s, device round trip " << t_device
                   << " s (stage 1 " << st.ms_build << " ms, join " << st.ms_join << " ms)" << std::endl;
     std::cout << "writing pairwise matrix to " << job.prefix << "_kSpider_pairwise.tsv" << std::endl;
-    ksp::write_pairwise_tsv(job.prefix, rows, kmer_count, job.threads);
+    if (device_tsv) pieces->commit();
+    else ksp::write_pairwise_tsv(job.prefix, rows, kmer_count, job.threads);
+    if (tsv_asked && std::getenv("KSPIDER_VERBOSE")) {
+        if (device_tsv) std::cout << "kspider_amd: pairwise TSV written by the device (" << A.text_bytes << " bytes of rows" << (A.edges_skipped ? ", the records stayed on the device" : "") << ")" << std::endl;
+        else std::cout << "kspider_amd: pairwise TSV written by the host (" << host_reason << ")" << std::endl;
+    }
     if (job.ani) {
         t0 = Clock::now();
         ksp::write_ani_column(job.prefix, rows, kmer_count, ani_tab->data(), job.threads);
         if (std::getenv("KSPIDER_VERBOSE")) std::cout << "kspider_amd: ANI column " << since(t0) << " s" << std::endl;
     }
     if (std::getenv("KSPIDER_VERBOSE"))
-        std::cout << "kspider_amd: sources=" << N << " colour-entries=" << P.post_src.size() << " pairs=" << rows.size() << std::endl;
+        std::cout << "kspider_amd: sources=" << N << " colour-entries=" << P.post_src.size() << " pairs=" << n_rows << std::endl;
     switch (A.kind) {
         case AfterJoin::kNone: break;
         case AfterJoin::kCut:
             if (std::getenv("KSPIDER_VERBOSE"))
                 std::cout << "kspider_amd: cut at " << A.cutoff << " on column " << A.col << ": " << A.n_found << " edges found on the device, " << n_edges
-                          << " kept; " << rows.size() << " rows written" << std::endl;
+                          << " kept; " << n_rows << " rows written" << std::endl;
             break;
         case AfterJoin::kRepr: finish_repr(job, P, zero_rows); break;
         case AfterJoin::kCluster: finish_cluster(job, P, zero_rows, n_edges, ani_tab ? ani_tab->data() : nullptr); break;
@@ -794,6 +829,19 @@ extern "C" int ksp_index_info(const char* index_prefix, uint64_t out[6]) {
 }
 
 extern "C" int ksp_format_float(float value, char* buf) { return buf ? ksp::format_float(buf, value) : 0; }
+
+// (tests) ksp_format_float on n values at once, in the layout of ksp_debug_format_floats: h_text[16 * i ...] = the h_len[i] bytes of value i
+extern "C" int ksp_debug_format_floats_host(const float* h_values, uint64_t n, char* h_text, uint32_t* h_len) {
+    if (n && (!h_values || !h_text || !h_len)) { ksp::set_error("ksp_debug_format_floats_host: NULL argument"); return KSP_E_ARG; }
+    char buf[32];
+    for (uint64_t i = 0; i < n; ++i) {
+        const int len = ksp::format_float(buf, h_values[i]);
+        if (len < 0 || len > 16) { ksp::set_error("ksp_debug_format_floats_host: a text longer than 16 bytes"); return KSP_E_ARG; }
+        std::memcpy(h_text + 16 * i, buf, (size_t)len);
+        h_len[i] = (uint32_t)len;
+    }
+    return KSP_OK;
+}
 
 namespace kSpider {
 void pairwise(std::string index_prefix, int user_threads) {

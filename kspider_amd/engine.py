@@ -40,6 +40,11 @@ TOPK_WAVE_ENTRIES = 64
 TOPK_LDS_ENTRIES = 4096
 TOPK_MAX_K = 1024
 
+#: the device's row text (KSP_TSV_* in the header): rows per chunk of the text passes, the shortest and the longest row in bytes
+TSV_CHUNK_ROWS = 256
+TSV_ROW_MIN = 12
+TSV_ROW_MAX = 79
+
 #: ksp_engine_lists_path / Engine.lists_path
 LISTS_NONE, LISTS_KEYED, LISTS_COMPACTED, LISTS_SORTED, LISTS_FUSED = 0, 1, 2, 3, 4
 
@@ -68,6 +73,7 @@ ABI_SYMBOLS = [
     "ksp_edges_forest", "ksp_forest_ranked", "kspider_tree", "kspider_pairwise_and_tree", "kspider_cluster_from_tree",
     "ksp_edges_dereplicate", "kspider_dereplicate", "kspider_pairwise_and_dereplicate",
     "ksp_edges_topk", "ksp_topk_ranked", "kspider_topk", "kspider_pairwise_and_topk",
+    "ksp_edges_tsv",
 ]
 
 
@@ -234,6 +240,13 @@ def lib():
         L.kspider_topk.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p]
         L.kspider_pairwise_and_topk.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p]
         L.ksp_debug_topk_classes.argtypes = [ctypes.c_void_p]
+        L.ksp_edges_tsv.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+        L.ksp_debug_format_floats.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_debug_format_floats_host.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_debug_tsv_records.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_debug_tsv_times.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
         _lib = L
     return _lib
 
@@ -630,6 +643,73 @@ def pairwise_and_topk(index_prefix: str, user_threads: int = 1, dist_type: str =
     """`pairwise` plus the file of `topk`, the selection taken from the edges while they are in HBM."""
     _check(lib().kspider_pairwise_and_topk(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
                                            _topk_k(k), os.fsencode(out_path) if out_path else None))
+
+
+def edges_tsv(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, d_ids_ptr: int = 0, device: int = 0, capacity: int | None = None,
+              tail: int = 0, fill: int = 0xA5) -> bytes:
+    """The rows of the pairwise TSV for ksp_edge records in DEVICE memory, as text made on the device (ksp_edges_tsv in
+    include/kspider_amd.h): no header, the records' order, ids from the device array d_ids_ptr (0: the source indices themselves).
+    capacity None: the size query first, then a buffer of exactly that size.  tail / fill (tests): that many bytes of `fill` are
+    kept behind the text and checked to be untouched; after a refused call (KspError) the whole buffer is checked."""
+    n = ctypes.c_uint64(0)
+    args = (device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, d_ids_ptr or None)
+    if capacity is None:
+        _check(lib().ksp_edges_tsv(*args, None, 0, ctypes.byref(n)))
+        capacity = n.value
+    buf = np.full(capacity + tail, fill, dtype=np.uint8)
+    rc = lib().ksp_edges_tsv(*args, buf.ctypes.data, capacity, ctypes.byref(n))
+    written = n.value if rc == KSP_OK else 0
+    if (buf[written:] != fill).any():
+        raise AssertionError("ksp_edges_tsv wrote behind its text" if rc == KSP_OK else "ksp_edges_tsv refused the call and wrote all the same")
+    _check(rc)
+    return buf[:written].tobytes()
+
+
+def edges_tsv_size(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, d_ids_ptr: int = 0, device: int = 0) -> int:
+    """The bytes edges_tsv would return (ksp_edges_tsv with h_text = NULL)."""
+    n = ctypes.c_uint64(0)
+    _check(lib().ksp_edges_tsv(device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, d_ids_ptr or None, None, 0, ctypes.byref(n)))
+    return n.value
+
+
+def _float_texts(call, values, raw):
+    v = np.ascontiguousarray(values, dtype=np.float32).ravel()
+    text = np.zeros((v.size, 16), dtype=np.uint8)
+    length = np.zeros(v.size, dtype=np.uint32)
+    _check(call(v.ctypes.data if v.size else None, v.size, text.ctypes.data if v.size else None, length.ctypes.data if v.size else None))
+    if v.size and int(length.max()) > 16:
+        raise AssertionError("a text longer than its 16-byte slot")
+    if raw:
+        return text, length
+    data = text.tobytes()
+    return [data[16 * i:16 * i + int(n)].decode("ascii") for i, n in enumerate(length)]
+
+
+def format_floats_device(values, device: int = 0, raw: bool = False):
+    """(tests) The text of every float32 of `values` as the device prints it (ksp_debug_format_floats, csrc/engine_internal.h): what
+    format_float gives, from integer arithmetic.  A list of str, or with raw (text, length): an (n, 16) uint8 array whose row i
+    holds length[i] bytes of text and zeros behind.  KspError (KSP_E_ARG) when a value is outside 0, +inf and [2^-40, 2^40)."""
+    return _float_texts(lambda v, n, t, l: lib().ksp_debug_format_floats(device, v, n, t, l), values, raw)
+
+
+def format_floats(values, raw: bool = False):
+    """format_float of every float32 of `values` in one call (ksp_debug_format_floats_host): the same host snprintf, the layout of
+    format_floats_device."""
+    return _float_texts(lambda v, n, t, l: lib().ksp_debug_format_floats_host(v, n, t, l), values, raw)
+
+
+def tsv_records(n_nodes: int, n_edges: int, seed: int, d_edges_ptr: int, d_kmer_counts_ptr: int, d_ids_ptr: int, device: int = 0) -> None:
+    """(tools/tsv_times.py) ksp_debug_tsv_records: valid seeded records, k-mer counts and ids written into the caller's device arrays."""
+    _check(lib().ksp_debug_tsv_records(device, n_nodes, n_edges, seed, d_edges_ptr or None, d_kmer_counts_ptr or None, d_ids_ptr or None))
+
+
+def tsv_times(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, d_ids_ptr: int, which: int, reps: int, threads: int = 16,
+              device: int = 0) -> np.ndarray:
+    """(tools/tsv_times.py) ksp_debug_tsv_times: reps rows of (wall ms, which 0: kernel ms by HIP events / which 1: ms of the copy)."""
+    ms = np.zeros((reps, 2), dtype=np.float32)
+    _check(lib().ksp_debug_tsv_times(device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, d_ids_ptr or None, int(which), int(reps),
+                                     int(threads), ms.ctypes.data))
+    return ms
 
 
 def cluster_from_tree(index_prefix: str, dist_type: str = "max_cont", cutoff: float = 0.0) -> None:
