@@ -632,6 +632,87 @@ int ksp_topk_ranked(int device, uint32_t n_nodes, const uint32_t* h_a, const uin
 int kspider_topk(const char* index_prefix, const char* dist_type, uint32_t k, const char* out_path);
 int kspider_pairwise_and_topk(const char* index_prefix, int user_threads, const char* dist_type, uint32_t k, const char* out_path);
 
+/* ---- the cluster report: density, medoid and coverage of every cluster, from the edges in HBM ------------------
+ * kspider_cluster says WHICH sources form a cluster; this says how good the cluster is and which member stands for it.  Single
+ * linkage chains: a component may be a clique or a string of pairs that barely pass the cut-off, and only its edges tell.
+ * Inputs as for ksp_components_edges: `n_edges` ksp_edge records in DEVICE memory, in any order, never written; d_kmer_counts;
+ * dist_col 3 / 4 / 5; cutoff.
+ * VALUE of a record: the float of the column in single precision exactly as the pairwise writer computes it.  A record is KEPT
+ * when ksp_components_edges keeps it (the critical float of the reference's text test; a NaN is kept), both ends are < n_nodes
+ * (a larger end is the caller's error and the record is ignored, as in the siblings) and source_1 != source_2 (a self pair takes
+ * no part in anything).  A pair that repeats counts again; source_1 > source_2 is allowed.
+ * CLUSTERS: the components of the kept records; label[v] = the smallest node of v's component, exactly the labels
+ * ksp_components_edges returns.
+ * DOMAIN: a containment lies in [0, 1].  A kept record whose value is not a NaN and exceeds 1 (+inf included: a count of 0
+ * beside shared > 0) is refused with KSP_E_ARG: found on the device, nothing is written to the caller.
+ * QUANTISED VALUE: q(v) = (uint64_t)((double)v * 4294967296.0), floor(v * 2^32): exact for v >= 2^-8, truncated below.  All sums
+ * are sums of q in uint64_t, so every result is independent of record order, grid size and scheduling; with n_edges < 2^32 - 1
+ * no sum can overflow.  A NaN record has no q.
+ * PER NODE v: degree = the kept records naming v, NaN records included; strength = the sum of q over the others.
+ * PER CLUSTER: size; edges = its kept records; nan_edges; sum_q; min / max over the values that are no NaN (both NaN when there
+ * are none); medoid = the member of the largest strength, ties to the smallest node (a singleton is its own); covered = the
+ * members other than the medoid that share a kept record with it.
+ * via[v]: the lowest index of a kept record between v and the medoid of v's cluster; 0xFFFFFFFF for the medoid itself and for
+ * members not adjacent to it.  covered = the members with a via.  Only via depends on the order of the records.
+ * ksp_edges_cluster_report: h_cluster (host, room for n_nodes rows) receives *n_clusters rows in order of root, ascending; rows
+ *   behind that are not written; h_member (host, n_nodes rows).  KSP_E_ARG for a NULL pointer with n_edges > 0, a NULL
+ *   n_clusters (or h_cluster / h_member with n_nodes > 0), a column other than 3 / 4 / 5, a NaN cut-off and the domain refusal;
+ *   KSP_E_LIMIT for 2^32 - 1 records or more (a record's index is `via`, and 0xFFFFFFFF is "none") and, before anything is
+ *   written to the caller, when
+ *       64 * n_nodes + 64 bytes
+ *   do not fit the device's free memory: per node its label (4), degree (4), strength (8) and via (4), and in the slot of a
+ *   root the cluster's edges, nan_edges and sum_q (8 each), min and max (4 each), the best strength (8) and the medoid (4); the
+ *   flag, the round's scratch and the counters.  (ksp_cluster_report_valued: 12 bytes per edge more, for the uploaded edges.)
+ *   Sizes, covered and the rows in root order are made by the host from those arrays.  Nothing is written to the caller unless
+ *   the whole call succeeded.  n_edges = 0: every node is a singleton cluster, no kernel runs.  $KSP_REPORT_MAX_WORKGROUPS caps
+ *   every grid (tests).  KSP_REPORT_CHUNK_EDGES: records per chunk and 256-thread workgroup of the edge passes, a design choice
+ *   inherited from the cut (KSP_CUT_CHUNK_EDGES), not measured for this consumer.
+ * ksp_cluster_report_valued: the same computation for HOST edges the caller has cut already: every record is kept (a self pair
+ *   is still no part of anything), h_value may be NaN, a value above 1 is refused as above and so is one below 0; an end
+ *   >= n_nodes is KSP_E_ARG.  The same kernels run behind an input adaptor.
+ * kspider_cluster_report: reads what kspider_cluster reads, with the same validation and the same refusals, each before any file
+ *   is written; a kept row's ids must be rows of .namesMap; the host applies kspider_cluster's test to the text as it stands, the
+ *   value is that text read with strtof.  dist_type "min_cont", "avg_cont", "max_cont" (NULL / ""); "ani", a NaN cut-off and a
+ *   cut-off outside [0, 1] are KSP_E_ARG.  Writes, through .partial and a rename (on an error nothing new is left behind),
+ *   with <P> the text in the cluster file's name (cutoff * 100 as Python prints a float):
+ *   PREFIX_kSpider_cluster_report_<dist_type>_<P>%.tsv: "cluster\tsize\tedges\tdensity\tmin\tmean\tmax\tmedoid\tmedoid_strength\tcovered",
+ *     one row per cluster in the order of kspider_cluster's file, `cluster` the 1-based number of that file's line; density =
+ *     edges / (size * (size - 1) / 2), mean = (double)sum_q / (double)(edges - nan_edges) / 2^32, medoid_strength = strength /
+ *     2^32, all three "%.6g" and "-" where the divisor is 0; min / max as ksp_format_float prints them, "-" when NaN; medoid: a name.
+ *   PREFIX_kSpider_cluster_members_<dist_type>_<P>%.tsv: "source\tcluster\tmedoid\t<dist_type>\tneighbours\tstrength", one row per
+ *     source in .namesMap order: its name, its cluster's number, the medoid's name, the value text of the via row exactly as it
+ *     stands in the input ("-" without one), degree, strength / 2^32 as "%.6g".
+ *   Device = $KSPIDER_DEVICE; with $KSPIDER_VERBOSE one line reports the records kept, the clusters and the largest one's size and density.
+ * kspider_pairwise_and_cluster_report: kspider_pairwise's two TSVs, byte for byte, plus the same two files, the report taken from
+ *   the gathered, sorted edges on the first device (the value text of a via row is ksp_format_float of the record's float).
+ *   Works with $KSPIDER_DEVICE / $KSPIDER_DEVICES and with KSPIDER_TSV=device.  Rows that exist only with shared_kmers = 0 never
+ *   reach the device; they are kept when they are NaN or when cutoff * 100 <= 0, and if at least one is kept the report is made
+ *   by ksp_cluster_report_valued over ALL rows in (source_1, source_2) order, floats from the records: no such row is silently
+ *   missing.  This path sums the FLOATS, which are finer than the 6-digit text kspider_cluster_report reads.  Promised against
+ *   kspider_cluster_report over the TSV just written: the same clusters, sizes, edges, densities and min / max texts (six
+ *   digits survive the trip through a float); where every value of the column has at most 6 significant decimal digits all
+ *   four files are byte-equal; otherwise mean, the strengths and a medoid chosen among near-ties may differ (and with it
+ *   covered and the via columns).                                                                                           */
+typedef struct ksp_cluster_row {
+    uint32_t root, size;
+    uint64_t edges, nan_edges, sum_q;
+    float min, max;
+    uint32_t medoid, covered;
+} ksp_cluster_row;   /* 48 bytes */
+typedef struct ksp_member_row {
+    uint32_t label, degree;
+    uint64_t strength;
+    uint32_t via, reserved /* 0 */;
+} ksp_member_row;   /* 24 bytes */
+#define KSP_REPORT_CHUNK_EDGES 2048u
+int ksp_edges_cluster_report(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
+                             int dist_col, double cutoff, ksp_cluster_row* h_cluster /* room for n_nodes */, uint32_t* n_clusters,
+                             ksp_member_row* h_member /* n_nodes */);
+int ksp_cluster_report_valued(int device, uint32_t n_nodes, const uint32_t* h_a, const uint32_t* h_b, const float* h_value,
+                              uint64_t n_edges, ksp_cluster_row* h_cluster, uint32_t* n_clusters, ksp_member_row* h_member);
+int kspider_cluster_report(const char* index_prefix, const char* dist_type, double cutoff);
+int kspider_pairwise_and_cluster_report(const char* index_prefix, int user_threads, const char* dist_type, double cutoff);
+
 /* ---- the rows of the pairwise TSV as text, made on the device (csrc/tsv.hip) ----
  * ksp_edges_tsv: the text of `n_edges` ksp_edge records in DEVICE memory (never written), in their order, rows only, no header:
  *       id1 \t id2 \t shared \t min \t avg \t max \n

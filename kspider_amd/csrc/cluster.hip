@@ -47,11 +47,15 @@ namespace {
 
 // The same pass straight over the join's edge records (ksp_edge, device memory): an edge counts when its containment
 // column is not below the cut (cc_edge_kept, edge_cut.hip.h: one compare against the critical float of ksp::cc_critical).
+// strict_nodes > 0 (the cluster report, report.hip): a record that names a node >= strict_nodes is ignored before anything is read
+// through it, and so is a self pair, whatever its value — it never changes a component, so the labels are the same either way.
 __global__ void k_cc_hook_edges(const ksp_edge* __restrict__ ed, u64 m, const u32* __restrict__ cnt, const int col, const float vcrit,
-                                const int mode, u32* __restrict__ parent, u32* __restrict__ changed, unsigned long long* __restrict__ kept) {
+                                const int mode, const u32 strict_nodes, u32* __restrict__ parent, u32* __restrict__ changed,
+                                unsigned long long* __restrict__ kept) {
     unsigned long long mine = 0;
     for (u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += (u64)gridDim.x * blockDim.x) {
         const ksp_edge x = ed[e];
+        if (strict_nodes && (x.source_1 >= strict_nodes || x.source_2 >= strict_nodes || x.source_1 == x.source_2)) continue;
         if (!cc_edge_kept(x, cnt, col, vcrit, mode)) continue;
         ++mine;
         const u32 pu = parent[x.source_1], pv = parent[x.source_2];
@@ -201,6 +205,42 @@ done:
     return rc;
 }
 
+// The rounds of hooking and pointer jumping over d_parent (n_nodes labels in device memory, initialised by k_cc_init or by the
+// caller), until nothing changes: the labels stay on the device.  d_changed: 4 words of device memory, [0] changed, [2..3]
+// the kept records of the first round (*n_kept, may be NULL; records only).
+int cc_rounds_on_device(const CcRounds& R, const uint32_t n_nodes, const uint64_t n_edges, uint32_t* d_parent, uint32_t* d_changed, uint64_t* n_kept) {
+    int rc = KSP_OK;
+    u32 h_changed = 1;
+    unsigned long long* const d_kept = reinterpret_cast<unsigned long long*>(d_changed + 2);
+    const unsigned gn = (n_nodes + 255) / 256;
+    const unsigned ge = (unsigned)std::min<u64>((n_edges + 255) / 256, 1u << 16);
+    // every round at least halves the depth of every tree and merges what an edge connects: O(log n) rounds; the bound only
+    // guards against a defect
+    for (int round = 0; n_edges && h_changed && round < 10000; ++round) {
+        KSP_TRY_HIP(hipMemsetAsync(d_changed, 0, 16, nullptr));
+        if (R.keep)
+            hipLaunchKernelGGL(k_cc_hook_kept, dim3(ge), dim3(256), 0, nullptr, R.ed, n_edges, R.keep, d_parent, d_changed);
+        else if (R.ed)
+            hipLaunchKernelGGL(k_cc_hook_edges, dim3(ge), dim3(256), 0, nullptr, R.ed, n_edges, R.cnt, R.col, R.vcrit, R.mode, R.strict ? n_nodes : 0u, d_parent,
+                               d_changed, round == 0 ? d_kept : nullptr);
+        else
+            hipLaunchKernelGGL(k_cc_hook, dim3(ge), dim3(256), 0, nullptr, R.a, R.b, n_edges, d_parent, d_changed);
+        hipLaunchKernelGGL(k_cc_jump, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes, d_changed);
+        hipLaunchKernelGGL(k_cc_jump, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes, d_changed);
+        KSP_TRY_HIP(hipMemcpy(&h_changed, d_changed, 4, hipMemcpyDeviceToHost));
+        if (round == 0 && n_kept && R.ed && !R.keep) { unsigned long long k = 0; KSP_TRY_HIP(hipMemcpy(&k, d_kept, 8, hipMemcpyDeviceToHost)); *n_kept = k; }
+    }
+    if (n_edges && h_changed) { set_error("components: did not converge"); rc = KSP_E_HIP; }
+done:
+    return rc;
+}
+// d_parent[v] = v: every node its own component (the start of cc_rounds_on_device)
+int cc_init_on_device(const uint32_t n_nodes, uint32_t* d_parent) {
+    if (n_nodes) hipLaunchKernelGGL(k_cc_init, dim3((n_nodes + 255) / 256), dim3(256), 0, nullptr, d_parent, n_nodes);
+    KSP_HIP(hipGetLastError());
+    return KSP_OK;
+}
+
 // connected components of the kept edges among `d_edges` (device memory, on the current device); see ksp_components_edges
 int cc_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, double cutoff,
                        uint32_t* h_label, uint64_t* n_kept, int ksize) {
@@ -210,7 +250,6 @@ int cc_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edg
     unsigned long long* d_kept = nullptr;
     double* d_table = nullptr;
     unsigned long long* d_keep = nullptr;   // ANI: one bit per edge, the cut evaluated once
-    u32 h_changed = 1;
     float vcrit = 0;
     int mode = 0;
     if (col != 6) cc_critical(cutoff, &vcrit, &mode);
@@ -220,7 +259,6 @@ int cc_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edg
     d_kept = reinterpret_cast<unsigned long long*>(d_changed + 2);
     {
         const unsigned gn = (n_nodes + 255) / 256;
-        const unsigned ge = (unsigned)std::min<u64>((n_edges + 255) / 256, 1u << 16);
         hipLaunchKernelGGL(k_cc_init, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes);
         if (col == 6 && n_edges) {   // the ANI cut of every edge, once: a bit per edge
             if ((rc = upload_ani_table(ksize, A, &d_table))) goto done;
@@ -235,19 +273,11 @@ int cc_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edg
             if (n_kept) { unsigned long long k; std::memcpy(&k, head + 2, 8); *n_kept = k; }
             (void)A.release(d_table);   // (not held through the rounds)
         }
-        for (int round = 0; n_edges && h_changed && round < 10000; ++round) {
-            KSP_TRY_HIP(hipMemsetAsync(d_changed, 0, 16, nullptr));
-            if (col == 6)
-                hipLaunchKernelGGL(k_cc_hook_kept, dim3(ge), dim3(256), 0, nullptr, d_edges, n_edges, d_keep, d_parent, d_changed);
-            else
-                hipLaunchKernelGGL(k_cc_hook_edges, dim3(ge), dim3(256), 0, nullptr, d_edges, n_edges, d_cnt, col, vcrit, mode, d_parent, d_changed,
-                                   round == 0 ? d_kept : nullptr);
-            hipLaunchKernelGGL(k_cc_jump, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes, d_changed);
-            hipLaunchKernelGGL(k_cc_jump, dim3(gn), dim3(256), 0, nullptr, d_parent, n_nodes, d_changed);
-            KSP_TRY_HIP(hipMemcpy(&h_changed, d_changed, 4, hipMemcpyDeviceToHost));
-            if (round == 0 && n_kept && col != 6) { unsigned long long k = 0; KSP_TRY_HIP(hipMemcpy(&k, d_kept, 8, hipMemcpyDeviceToHost)); *n_kept = k; }
+        {
+            CcRounds R;
+            R.ed = d_edges; R.keep = d_keep; R.cnt = d_cnt; R.col = col; R.vcrit = vcrit; R.mode = mode;
+            if ((rc = cc_rounds_on_device(R, n_nodes, n_edges, d_parent, d_changed, col != 6 ? n_kept : nullptr))) goto done;
         }
-        if (n_edges && h_changed) { set_error("components: did not converge"); rc = KSP_E_HIP; goto done; }
         KSP_TRY_HIP(hipMemcpy(h_label, d_parent, (size_t)n_nodes * 4, hipMemcpyDeviceToHost));
     }
 done:

@@ -23,6 +23,21 @@ void cc_critical(double cutoff, float* vcrit, int* mode);
 // ANI of `pairwise --estimate-ani` for k-mer size ksize (ani.h; KSP_E_ARG if an edge has a NaN containment)
 int cc_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, double cutoff,
                        uint32_t* h_label, uint64_t* n_kept, int ksize = 0);
+// The edges of cc_rounds_on_device, one of three forms, all in device memory of the CURRENT device: the join's records cut by
+// cc_edge_kept (ed, cnt, col 3 / 4 / 5, vcrit / mode of cc_critical; strict: a record naming a node >= n_nodes and a self pair
+// are skipped before anything is read through them), the records whose bit in keep[] is set (ed, keep), or pairs (a, b).
+struct CcRounds {
+    const ksp_edge* ed = nullptr;
+    const unsigned long long* keep = nullptr;
+    const uint32_t *a = nullptr, *b = nullptr, *cnt = nullptr;
+    int col = 0, mode = 0;
+    float vcrit = 0;
+    bool strict = false;
+};
+// the rounds of cc_edges_on_device alone: d_parent (n_nodes words, set by cc_init_on_device) ends as the labels and stays on the
+// device; d_changed: 4 words of scratch; *n_kept (may be NULL; the cut records only): the records the cut keeps
+int cc_init_on_device(uint32_t n_nodes, uint32_t* d_parent);
+int cc_rounds_on_device(const CcRounds& edges, uint32_t n_nodes, uint64_t n_edges, uint32_t* d_parent, uint32_t* d_changed, uint64_t* n_kept);
 void read_names_map(const std::string& prefix, std::vector<std::string>& name_of);
 void write_cluster_file(const std::string& prefix, double threshold, const std::vector<uint32_t>& label,
                         const std::vector<std::string>& name_of);
@@ -107,6 +122,20 @@ int topk_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_e
 // the names; count[v]: the hits of name v, neighbour / text: the other end and the value text of every hit, flat in that order
 void write_topk_file(const std::string& out_path, const std::string& dist, const std::vector<std::string>& name_of, const std::vector<uint32_t>& count,
                      const std::vector<uint32_t>& neighbour, const std::vector<std::string>& text);
+// ---- the cluster report: density, medoid and coverage of every cluster from the join's edges (report.hip) ----
+// what the last report on this thread did: the kept records, the chunks whose kept records carried one label (their cluster sums
+// left the workgroup as one set of atomics), the sets of cluster atomics and the sets of source_1-side node atomics issued
+struct ReportTrace {
+    uint64_t kept = 0, single_label_chunks = 0, cluster_sets = 0, node_sets = 0;
+};
+// ksp_edges_cluster_report on the CURRENT device (h_cluster / h_member: n_nodes rows); *trace may be NULL
+int report_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, double cutoff,
+                           ksp_cluster_row* h_cluster, uint32_t* n_clusters, ksp_member_row* h_member, ReportTrace* trace = nullptr);
+// PREFIX_kSpider_cluster_report_<dist>_<P>%.tsv and PREFIX_kSpider_cluster_members_<dist>_<P>%.tsv, P = py_float_repr(threshold),
+// both through .partial and a rename: the clusters in order of their root (the lines of write_cluster_file), the members in the
+// order of the names.  via_text[v]: the value text of member v's `via` record ("" without one).
+void write_report_files(const std::string& prefix, const std::string& dist, double threshold, const std::vector<ksp_cluster_row>& cluster,
+                        const std::vector<ksp_member_row>& member, const std::vector<std::string>& via_text, const std::vector<std::string>& name_of);
 // ---- the rows of the pairwise TSV as text, made on the device from the join's edges (tsv.hip) ----
 // takes the next piece of the text (it lives until the call returns); a code other than KSP_OK, with its text in
 // ksp_last_error(), ends the pass
@@ -121,14 +150,14 @@ int tsv_edges_on_device(const char* who, uint32_t n_nodes, const ksp_edge* d_edg
 // kept ones are gathered, sorted and copied.  The other kinds are taken from the sorted edges on the first device, while they
 // are in HBM: the components (cc_edges_on_device), the ranking (repr_edges_on_device), the components at every cut-off of a
 // ladder (sweep_edges_on_device), the maximum spanning forest (tree_edges_on_device), the dereplicated set (derep_edges_on_device),
-// the k best hits of every source (topk_edges_on_device).
+// the k best hits of every source (topk_edges_on_device), the report of every cluster (report_edges_on_device).
 struct AfterJoin {
-    enum Kind { kNone, kCluster, kRepr, kCut, kSweep, kTree, kDerep, kTopk };
+    enum Kind { kNone, kCluster, kRepr, kCut, kSweep, kTree, kDerep, kTopk, kReport };
     Kind kind = kNone;
     const uint32_t* kmer_counts = nullptr;   // per (dense) source index
     int col = 0;                             // 3 / 4 / 5; kCluster: also 6 = ANI
     int ksize = 0;                           // kCluster: k-mer size of the ANI column (col 6)
-    double cutoff = 0;                       // kCluster, kCut
+    double cutoff = 0;                       // kCluster, kCut, kReport
     double threshold = 0.20;                 // kRepr, kDerep
     const double* cutoffs = nullptr;         // kSweep
     uint32_t n_cutoffs = 0;                  //   1 .. KSP_SWEEP_MAX_CUTOFFS
@@ -144,6 +173,9 @@ struct AfterJoin {
     DerepTrace derep;                        //   the ranks are in `node` (rank[v]); what the selection did
     TopkTrace topk;                          // kTopk: per source index its hits in `index` (n_sources x k records of the returned edges) and
                                              //   their number in `count`; what the selection did
+    std::vector<ksp_cluster_row> cluster_rows;   // kReport: the clusters in order of their root (source indices), and per source index
+    std::vector<ksp_member_row> member_rows;     //   its row; `via` is a record of the returned edges; what the passes did
+    ReportTrace report;
     // The rows' text, wanted besides whatever `kind` asks for (KSPIDER_TSV=device): the text pass runs on the first device over
     // the gathered, sorted edges, after the consumer.  ids: the id of every source index (n_sources entries).  text_sink takes
     // the pieces in file order.  With kNone and kCut nobody reads the records afterwards, so they are not copied to the host:
@@ -184,6 +216,14 @@ int ksp_debug_derep_rounds(uint64_t out[4]);
 /* (tests) what the last ksp_edges_topk / ksp_topk_ranked / kspider_topk of this thread did: out[0] / out[1] / out[2] the nodes selected by
  * the wave, workgroup and stream kernels (0 with KSP_TOPK_SELECT=library), out[3] the refills of the stream kernel over all its nodes. */
 int ksp_debug_topk_classes(uint64_t out[4]);
+/* (tests) what the last ksp_edges_cluster_report / ksp_cluster_report_valued of this thread did: out[0] the kept records, out[1] the
+ * chunks that took the single-label path, out[2] the sets of cluster atomics issued, out[3] the sets of source_1-side node atomics. */
+int ksp_debug_report_counts(uint64_t out[4]);
+/* (tools/report_times.py) HIP-event times of `reps` runs over the same records.  ms holds 5 x reps values: ms[5r] the whole device part
+ * of ksp_edges_cluster_report (allocations and the copies to the host included), ms[5r + 1 .. 5r + 3] its accumulate, medoid and links
+ * passes alone, ms[5r + 4] the whole of ksp_components_edges on the same records, for comparison: the labels are what both pay. */
+int ksp_debug_report_times(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col,
+                           double cutoff, int reps, float* ms, ksp_cluster_row* h_cluster, uint32_t* n_clusters, ksp_member_row* h_member);
 /* (tools/topk_times.py) HIP-event times of `reps` runs of ksp_edges_topk's device part: which 0 = the hand-written select kernels,
  * 1 = rocprim::segmented_radix_sort_keys and a gather (KSP_TOPK_SELECT=library). */
 int ksp_debug_topk_times(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col,

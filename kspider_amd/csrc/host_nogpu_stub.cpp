@@ -30,6 +30,8 @@ void write_repr_file(const std::string&, const std::vector<uint32_t>&, const uin
 void write_derep_file(const std::string&, const std::string&, const std::vector<DerepRow>&, const std::vector<std::string>&) {}
 void write_topk_file(const std::string&, const std::string&, const std::vector<std::string>&, const std::vector<uint32_t>&, const std::vector<uint32_t>&,
                      const std::vector<std::string>&) {}
+void write_report_files(const std::string&, const std::string&, double, const std::vector<ksp_cluster_row>&, const std::vector<ksp_member_row>&,
+                        const std::vector<std::string>&, const std::vector<std::string>&) {}
 }  // namespace ksp
 
 extern "C" {
@@ -67,6 +69,10 @@ int ksp_topk_ranked(int, uint32_t, const uint32_t*, const uint32_t*, const uint3
     return KSP_E_HIP;
 }
 int kspider_topk(const char*, const char*, uint32_t, const char*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_cluster_report_valued(int, uint32_t, const uint32_t*, const uint32_t*, const float*, uint64_t, ksp_cluster_row*, uint32_t*, ksp_member_row*) {
     ksp::set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }

@@ -10,9 +10,12 @@
 // The same progress lines go to stdout.
 #include <algorithm>
 #include <chrono>
+#include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -68,12 +71,13 @@ using ksp::AfterJoin;
 //   kTree     the single-linkage tree: the maximum spanning forest of the edges
 //   kDerep    the dereplicated set: greedy representatives in rank order and the members they stand for
 //   kTopk     the k best hits of every source
+//   kReport   the report of every cluster at one cut-off: density, value range, medoid, coverage, and the members' table
 struct PairwiseJob {
     std::string prefix;
     int threads = 1;
     bool ani = false;       // also write the ANI column of `pairwise --estimate-ani` (ks_pairwise.py:29-84; k from PREFIX.extra)
     AfterJoin after;
-    std::string dist;       // kSweep, kTree: the distance's name in their file names
+    std::string dist;       // kSweep, kTree, kReport: the distance's name in their file names
     std::string repr_out;   // kRepr: "" = PREFIX_kSpider_repr_sketches.txt; kDerep: "" = PREFIX_kSpider_dereplicated_<dist>.tsv;
                             // kTopk: "" = PREFIX_kSpider_topk_<dist>.tsv
     bool newick = false;    // kTree
@@ -145,7 +149,7 @@ void node_labels_of(const std::vector<uint32_t>& ids, const uint32_t* lab, const
 int load_inputs(const PairwiseJob& job, ksp::IndexData& ix, std::vector<std::string>& derep_names) {
     auto t0 = Clock::now();
     ksp::load_index(job.prefix, ix);
-    if (job.after.kind == AfterJoin::kDerep || job.after.kind == AfterJoin::kTopk) {   // every source must be a row of .namesMap: refused before any file is written
+    if (job.after.kind == AfterJoin::kDerep || job.after.kind == AfterJoin::kTopk || job.after.kind == AfterJoin::kReport) {   // every source must be a row of .namesMap: refused before any file is written
         ksp::read_names_map(job.prefix, derep_names);
         for (auto& c : ix.colors)
             for (uint32_t g : c.second) ksp::check_row_nodes(g, g, derep_names.size());
@@ -539,6 +543,96 @@ void finish_topk(PairwiseJob& job, const Postings& P, const TopkHits& H, const s
                   << A.topk.wave << " / " << A.topk.workgroup << " / " << A.topk.stream << std::endl;
 }
 
+// the value of every member's via record, while the device's records are still here (per source index; 0 without one)
+std::vector<float> report_via_values(const AfterJoin& A, const Postings& P, const ksp_edge* edges, const uint64_t n_edges) {
+    std::vector<float> value(A.member_rows.size(), 0.0f);
+    for (size_t i = 0; i < A.member_rows.size(); ++i) {
+        const uint32_t e = A.member_rows[i].via;
+        if (e == 0xFFFFFFFFu) continue;
+        if (e >= n_edges || (edges[e].source_1 != i && edges[e].source_2 != i)) throw std::runtime_error("cluster report: the device named a record that does not name the source");
+        value[i] = column_value(A.col, edges[e].shared, P.counts[edges[e].source_1], P.counts[edges[e].source_2]);
+    }
+    return value;
+}
+
+// The device reported on its own records.  A shared-0 row (value 0, or NaN beside a source of 0 k-mers) is kept when it is a NaN
+// or when cutoff * 100 <= 0 — the same test — and never reached the device: if one is kept, the report is made again by
+// ksp_cluster_report_valued over all kept rows in (source_1, source_2) order, so that none is silently missing.  Then the rows
+// of the sources become rows of .namesMap nodes (index order is id order; a name without a source is a singleton) and the files.
+int finish_report(PairwiseJob& job, const Postings& P, const std::vector<ZeroRow>& zero_rows, const std::vector<ksp::EdgeRow>& rows, std::vector<float>& via_value,
+                  const std::vector<std::string>& name_of, const int device) {
+    AfterJoin& A = job.after;
+    const uint32_t N = (uint32_t)P.ids.size(), none = 0xFFFFFFFFu;
+    const uint64_t NN = name_of.size();
+    float vcrit = 0;
+    int mode = 0;
+    ksp::cc_critical(A.cutoff, &vcrit, &mode);
+    auto kept_zero = [&](const ZeroRow& z) { return passes_cut(column_value(A.col, 0, P.counts[z.a], P.counts[z.b]), vcrit, mode); };
+    uint64_t n_kept = A.report.kept;
+    if (std::any_of(zero_rows.begin(), zero_rows.end(), kept_zero)) {
+        std::vector<uint32_t> ea, eb;
+        std::vector<float> val;
+        for (const ksp::EdgeRow& r : rows) {
+            const uint32_t a = P.dense(r.source_1), b = P.dense(r.source_2);
+            const float v = column_value(A.col, r.shared, P.counts[a], P.counts[b]);
+            if (!passes_cut(v, vcrit, mode)) continue;
+            ea.push_back(a); eb.push_back(b); val.push_back(v);
+        }
+        uint32_t n_clusters = 0;
+        A.cluster_rows.assign((size_t)N + 1, ksp_cluster_row());
+        A.member_rows.assign((size_t)N + 1, ksp_member_row());
+        const int rc = ksp_cluster_report_valued(device, N, ea.data(), eb.data(), val.data(), ea.size(), A.cluster_rows.data(), &n_clusters, A.member_rows.data());
+        if (rc != KSP_OK) return rc;
+        A.cluster_rows.resize(n_clusters);
+        A.member_rows.resize(N);
+        via_value.assign(N, 0.0f);
+        for (uint32_t i = 0; i < N; ++i)
+            if (A.member_rows[i].via != none) via_value[i] = val[A.member_rows[i].via];
+        n_kept = ea.size();
+    }
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    std::vector<ksp_member_row> member((size_t)NN);
+    std::vector<std::string> via_text((size_t)NN);
+    std::vector<int64_t> source_of((size_t)NN, -1);
+    for (uint64_t v = 0; v < NN; ++v) member[v] = ksp_member_row{(uint32_t)v, 0u, 0, none, 0u};
+    for (uint32_t i = 0; i < N; ++i) {
+        const ksp_member_row& m = A.member_rows[i];
+        const uint32_t v = P.ids[i] - 1;   // (every source is a row of .namesMap: checked before the first file)
+        member[v] = ksp_member_row{P.ids[m.label] - 1, m.degree, m.strength, m.via, 0u};
+        source_of[v] = i;
+        if (m.via != none) {
+            char buf[64];
+            buf[ksp::format_float(buf, via_value[i])] = 0;
+            via_text[v] = buf;
+        }
+    }
+    std::vector<ksp_cluster_row> cluster;
+    size_t next = 0;   // (the device's rows ascend by root, and so do their nodes)
+    for (uint64_t v = 0; v < NN; ++v) {
+        if (source_of[v] < 0) { cluster.push_back(ksp_cluster_row{(uint32_t)v, 1u, 0, 0, 0, nan, nan, (uint32_t)v, 0u}); continue; }
+        if (member[v].label != v) continue;
+        if (next >= A.cluster_rows.size() || A.cluster_rows[next].root != (uint32_t)source_of[v]) throw std::runtime_error("cluster report: the device's rows do not match its labels");
+        ksp_cluster_row c = A.cluster_rows[next++];
+        c.root = (uint32_t)v;
+        c.medoid = P.ids[c.medoid] - 1;
+        cluster.push_back(c);
+    }
+    ksp::write_report_files(job.prefix, job.dist, A.cutoff * 100.0, cluster, member, via_text, name_of);
+    if (std::getenv("KSPIDER_VERBOSE")) {
+        const ksp_cluster_row* big = nullptr;
+        for (const ksp_cluster_row& c : cluster)
+            if (!big || c.size > big->size) big = &c;
+        std::cout << "kspider_amd: cluster report: " << n_kept << " records kept, " << cluster.size() << " clusters";
+        if (big) {
+            char buf[64] = "-";
+            if (big->size > 1) std::snprintf(buf, sizeof buf, "%.6g", (double)big->edges / ((double)big->size * (big->size - 1.0) / 2.0));
+            std::cout << ", the largest of " << big->size << " sources, density " << buf;
+        }
+        std::cout << std::endl;
+    }
+    return KSP_OK;
+}
+
 // Mirrors src/pairwise.cpp:123-276 phase by phase (the head of this file), with what job.after asks for between the join and the files.
 int run_job(PairwiseJob& job) {
     AfterJoin& A = job.after;
@@ -616,6 +710,8 @@ int run_job(PairwiseJob& job) {
     const uint64_t n_rows = device_tsv ? n_edges : rows.size();
     TopkHits topk_hits;
     if (A.kind == AfterJoin::kTopk) topk_hits = device_topk(A, P, edges.get(), n_edges, zero_rows);
+    std::vector<float> report_values;
+    if (A.kind == AfterJoin::kReport) report_values = report_via_values(A, P, edges.get(), n_edges);
     edges.reset();
     if (job.ani && (rc = refuse_nan_rows(rows, kmer_count)) != KSP_OK) return rc;   // before anything of it is written
     std::cout << "pairwise hashmap construction: " << t_transpose + since(t0) << " secs" << std::endl;
@@ -649,6 +745,7 @@ int run_job(PairwiseJob& job) {
         case AfterJoin::kTree: finish_tree(job, P, zero_rows, n_edges, forest); break;
         case AfterJoin::kDerep: finish_derep(job, P, derep_text, derep_names); break;
         case AfterJoin::kTopk: finish_topk(job, P, topk_hits, derep_names, n_edges); break;
+        case AfterJoin::kReport: return finish_report(job, P, zero_rows, rows, report_values, derep_names, devices.empty() ? 0 : devices[0]);
     }
     return KSP_OK;
 }
@@ -769,6 +866,21 @@ extern "C" int kspider_pairwise_and_topk(const char* index_prefix, int user_thre
     job.after.k = k;
     if (out_path) job.repr_out = out_path;
     return guarded("kspider_pairwise_and_topk", true, job);
+}
+
+extern "C" int kspider_pairwise_and_cluster_report(const char* index_prefix, int user_threads, const char* dist_type, double cutoff) {
+    if (!index_prefix) { ksp::set_error("kspider_pairwise_and_cluster_report: index_prefix is NULL"); return KSP_E_ARG; }
+    std::string dt;
+    const int col = dist_column(dist_type, "max_cont", &dt);
+    if (!col) {
+        ksp::set_error("kspider_pairwise_and_cluster_report: distance '" + dt + "' is not min_cont, avg_cont or max_cont (a report sums containments in [0, 1])");
+        return KSP_E_ARG;
+    }
+    if (!(cutoff >= 0 && cutoff <= 1)) { ksp::set_error("kspider_pairwise_and_cluster_report: the cut-off is not in [0, 1]"); return KSP_E_ARG; }
+    PairwiseJob job(index_prefix, user_threads, AfterJoin::kReport, col);
+    job.dist = dt;
+    job.after.cutoff = cutoff;
+    return guarded("kspider_pairwise_and_cluster_report", true, job);
 }
 
 extern "C" int kspider_pairwise_cut(const char* index_prefix, int user_threads, const char* dist_type, double cutoff) {

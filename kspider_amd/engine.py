@@ -40,6 +40,14 @@ TOPK_WAVE_ENTRIES = 64
 TOPK_LDS_ENTRIES = 4096
 TOPK_MAX_K = 1024
 
+#: records per chunk of the cluster report's edge passes (KSP_REPORT_CHUNK_EDGES in the header)
+REPORT_CHUNK_EDGES = 2048
+
+#: ksp_cluster_row / ksp_member_row of the header (48 and 24 bytes)
+CLUSTER_ROW_DTYPE = np.dtype([("root", "<u4"), ("size", "<u4"), ("edges", "<u8"), ("nan_edges", "<u8"), ("sum_q", "<u8"), ("min", "<f4"), ("max", "<f4"),
+                              ("medoid", "<u4"), ("covered", "<u4")])
+MEMBER_ROW_DTYPE = np.dtype([("label", "<u4"), ("degree", "<u4"), ("strength", "<u8"), ("via", "<u4"), ("reserved", "<u4")])
+
 #: the device's row text (KSP_TSV_* in the header): rows per chunk of the text passes, the shortest and the longest row in bytes
 TSV_CHUNK_ROWS = 256
 TSV_ROW_MIN = 12
@@ -73,6 +81,7 @@ ABI_SYMBOLS = [
     "ksp_edges_forest", "ksp_forest_ranked", "kspider_tree", "kspider_pairwise_and_tree", "kspider_cluster_from_tree",
     "ksp_edges_dereplicate", "kspider_dereplicate", "kspider_pairwise_and_dereplicate",
     "ksp_edges_topk", "ksp_topk_ranked", "kspider_topk", "kspider_pairwise_and_topk",
+    "ksp_edges_cluster_report", "ksp_cluster_report_valued", "kspider_cluster_report", "kspider_pairwise_and_cluster_report",
     "ksp_edges_tsv",
 ]
 
@@ -240,6 +249,15 @@ def lib():
         L.kspider_topk.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p]
         L.kspider_pairwise_and_topk.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p]
         L.ksp_debug_topk_classes.argtypes = [ctypes.c_void_p]
+        L.ksp_edges_cluster_report.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_cluster_report_valued.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.kspider_cluster_report.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double]
+        L.kspider_pairwise_and_cluster_report.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_double]
+        L.ksp_debug_report_counts.argtypes = [ctypes.c_void_p]
+        L.ksp_debug_report_times.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.ksp_edges_tsv.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
         L.ksp_debug_format_floats.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
@@ -643,6 +661,67 @@ def pairwise_and_topk(index_prefix: str, user_threads: int = 1, dist_type: str =
     """`pairwise` plus the file of `topk`, the selection taken from the edges while they are in HBM."""
     _check(lib().kspider_pairwise_and_topk(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
                                            _topk_k(k), os.fsencode(out_path) if out_path else None))
+
+
+def _report_out(who, n_nodes, tail, fill, call):
+    """Both outputs of a report call with `tail` rows of the byte `fill` behind them (all n_nodes rows of the cluster array start as
+    `fill` too).  After a refused call (KspError) every byte is checked to be untouched; after a good one the rows behind n_clusters
+    and both tails are."""
+    cluster = np.full((n_nodes + tail) * CLUSTER_ROW_DTYPE.itemsize, fill, dtype=np.uint8)
+    member = np.full((n_nodes + tail) * MEMBER_ROW_DTYPE.itemsize, fill, dtype=np.uint8)
+    n_clusters = np.full(1 + tail, fill * 0x01010101, dtype=np.uint32)
+    try:
+        _check(call(cluster.ctypes.data if cluster.size else None, n_clusters.ctypes.data, member.ctypes.data if member.size else None))
+    except KspError:
+        if (cluster != fill).any() or (member != fill).any() or (n_clusters != fill * 0x01010101).any():
+            raise AssertionError(f"{who} wrote to its outputs although it refused the call")
+        raise
+    n = int(n_clusters[0])
+    if n > n_nodes:
+        raise AssertionError(f"{who} reported more clusters than nodes")
+    if (cluster[n * CLUSTER_ROW_DTYPE.itemsize:] != fill).any() or (member[n_nodes * MEMBER_ROW_DTYPE.itemsize:] != fill).any() or (n_clusters[1:] != fill * 0x01010101).any():
+        raise AssertionError(f"{who} wrote behind its rows")
+    return (cluster[:n * CLUSTER_ROW_DTYPE.itemsize].view(CLUSTER_ROW_DTYPE).copy(), member[:n_nodes * MEMBER_ROW_DTYPE.itemsize].view(MEMBER_ROW_DTYPE).copy())
+
+
+def edges_cluster_report(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, dist_col: int = 5, cutoff: float = 0.0, device: int = 0,
+                         tail: int = 0, fill: int = 0) -> tuple:
+    """The report of every cluster of the kept ksp_edge records in DEVICE memory (include/kspider_amd.h): (cluster, member), structured
+    arrays of CLUSTER_ROW_DTYPE (one row per cluster, by root) and MEMBER_ROW_DTYPE (one row per node).  tail / fill (tests): that many
+    rows of the byte `fill` are kept behind both arrays and checked to be untouched, as are the cluster rows behind the last one."""
+    return _report_out("ksp_edges_cluster_report", n_nodes, tail, fill, lambda pc, pn, pm: lib().ksp_edges_cluster_report(
+        device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, int(dist_col), float(cutoff), pc, pn, pm))
+
+
+def cluster_report_valued(n_nodes: int, a: np.ndarray, b: np.ndarray, value: np.ndarray, device: int = 0, tail: int = 0, fill: int = 0) -> tuple:
+    """The same report for host edges the caller has cut already: every record is kept, value[e] in [0, 1] or NaN."""
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    value = np.ascontiguousarray(value, dtype=np.float32)
+    if not (a.size == b.size == value.size):
+        raise ValueError("a, b and value need one entry per edge")
+    return _report_out("ksp_cluster_report_valued", n_nodes, tail, fill, lambda pc, pn, pm: lib().ksp_cluster_report_valued(
+        device, n_nodes, a.ctypes.data, b.ctypes.data, value.ctypes.data, a.size, pc, pn, pm))
+
+
+def report_counts() -> dict:
+    """(tests) What the last report of this thread did (ksp_debug_report_counts, csrc/engine_internal.h): the kept records, the chunks
+    that took the single-label path, the sets of cluster atomics and of source_1-side node atomics issued."""
+    out = np.zeros(4, dtype=np.uint64)
+    _check(lib().ksp_debug_report_counts(out.ctypes.data))
+    return dict(kept=int(out[0]), single_label_chunks=int(out[1]), cluster_sets=int(out[2]), node_sets=int(out[3]))
+
+
+def cluster_report(index_prefix: str, dist_type: str = "max_cont", cutoff: float = 0.0) -> None:
+    """The report of every cluster of the pairwise TSV at one cut-off: PREFIX_kSpider_cluster_report_<DIST>_<CUTOFF*100>%.tsv and
+    PREFIX_kSpider_cluster_members_<DIST>_<CUTOFF*100>%.tsv; the sums run on the GPU."""
+    _check(lib().kspider_cluster_report(os.fsencode(index_prefix), dist_type.encode() if dist_type is not None else None, float(cutoff)))
+
+
+def pairwise_and_cluster_report(index_prefix: str, user_threads: int = 1, dist_type: str = "max_cont", cutoff: float = 0.0) -> None:
+    """`pairwise` plus the two files of `cluster_report`, the report taken from the edges while they are in HBM."""
+    _check(lib().kspider_pairwise_and_cluster_report(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
+                                                     float(cutoff)))
 
 
 def edges_tsv(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, d_ids_ptr: int = 0, device: int = 0, capacity: int | None = None,
