@@ -713,6 +713,86 @@ int ksp_cluster_report_valued(int device, uint32_t n_nodes, const uint32_t* h_a,
 int kspider_cluster_report(const char* index_prefix, const char* dist_type, double cutoff);
 int kspider_pairwise_and_cluster_report(const char* index_prefix, int user_threads, const char* dist_type, double cutoff);
 
+/* ---- the average-linkage tree (UPGMA) of the containment graph, exact, from the edges in HBM (csrc/upgma.hip) -----
+ * Single linkage chains; average linkage is what users of genome clustering reach for instead (dRep's secondary clustering,
+ * scipy's linkage(..., 'average')).  Here it runs on the sparse edge list: no N x N matrix and no node limit.
+ * RECORDS: inputs as for ksp_edges_cluster_report: `n_edges` ksp_edge records in DEVICE memory, any order, never written;
+ * d_kmer_counts; dist_col 3 / 4 / 5.  The VALUE of a record is the float of the column exactly as the pairwise writer computes it.
+ * q(v) = (uint64_t)((double)v * 4294967296.0), as in the report.  A record TAKES PART when both ends are < n_nodes (a larger end
+ * is the caller's error and is ignored, as in the siblings), source_1 != source_2 and q > 0: a NaN, a 0 and a value below 2^-32
+ * take no part, so a row that exists only with shared_kmers = 0 never matters.  A pair that repeats counts again; source_1 >
+ * source_2 is allowed.  DOMAIN: a value that is not a NaN and exceeds 1 (+inf included), in a record whose ends are both nodes
+ * (a self pair too), is refused with KSP_E_ARG: found on the device, nothing is written to the caller.
+ * CLUSTERS: a cluster is named by its smallest member, its root.  S(A, B) = the sum of q over the participating records between a
+ * member of A and a member of B.  {A, B} is a CANDIDATE when S(A, B) > 0; its similarity is the rational S(A, B) / (|A| * |B|),
+ * in containment units that divided by 2^32.  Pairs without a record between them have similarity 0 and are never merged: the
+ * result is a forest, like kspider_tree's.
+ * ORDER of candidate pairs, a strict total order: similarity descending, compared exactly by cross-multiplication in 128 bits
+ * (S < 2^64 because n_edges < 2^32 - 1 and q <= 2^32; |A| * |B| < 2^64; so a cross product is below 2^128); then the smaller
+ * root ascending; then the larger root ascending.
+ * RESULT: start from singletons and repeatedly merge the first candidate pair.  A merge is the row (lo, hi, sum_q = S, size_lo,
+ * size_hi), lo < hi the two roots; the merged cluster's root is lo.  Rows are returned in merge order.  Average linkage is
+ * reducible, so the rows are strictly descending in the order above and a cut at any similarity keeps a prefix of them.
+ * The device computes it in rounds (every cluster picks its first candidate; pairs picked by both ends merge, all at once; the
+ * rest is contracted), which gives exactly these rows: DESIGN.md 7m.  Rounds are at most n_nodes - 1; a path with monotone
+ * weights needs about 0.6 * n_nodes of them.
+ * ksp_edges_upgma: h_rows (host, room for n_nodes - 1 rows) receives *n_rows rows; rows behind that are not written.  KSP_E_ARG for
+ *   a NULL pointer with n_edges > 0, a NULL n_rows, a NULL h_rows with n_nodes > 1, a column other than 3 / 4 / 5 and the domain
+ *   refusal; KSP_E_LIMIT for 2^32 - 1 records or more (checked before any device call) and, before anything is written to the
+ *   caller, when
+ *       32 * n_edges + 16 * (ceil(n_edges / 2048) + 1) + 40 * n_nodes + 64 bytes
+ *       + the larger of rocPRIM's scratch for the sort of n_edges (key, value) pairs of 8 + 8 bytes and for its scan of
+ *         ceil(n_edges / 2048) + 1 counts
+ *   do not fit the device's free memory: two (key, S) buffers of 16 bytes per record, the chunk counts and offsets, per node its
+ *   size (4), map (4) and best (8) and a 24-byte row of the merge log, the counters.  KSP_E_HIP with a message, never a spin,
+ *   should a round merge nothing while pairs are live or the rounds exceed n_nodes.  Nothing is written to the caller unless the
+ *   whole call succeeded.  n_edges = 0 (or n_nodes < 2): *n_rows = 0, no kernel runs.  $KSP_UPGMA_MAX_WORKGROUPS caps every grid
+ *   (tests).  KSP_UPGMA_CHUNK_EDGES: entries per chunk and 256-thread workgroup, inherited from the cut, not measured here.
+ *   KSP_UPGMA_TAIL_PAIRS: at that many live pairs or fewer the pair list goes to the host, which finishes sequentially with the
+ *   same comparison (the top of the tree merges a handful of big clusters one pair per round); $KSP_UPGMA_TAIL_PAIRS overrides
+ *   it, 0 keeps the device rounds to the end; the rows are the same either way.  Measured on an MI355X (the table of DESIGN.md
+ *   7m): on a path the host finish beats the device's rounds up to about 2^15 pairs, but on the bench workload's edges a
+ *   hand-over above 1 024 pairs only costs, so the constant is the smaller figure.
+ * ksp_upgma_valued: the same for HOST edges the caller has valued already; the same kernels run behind an input adaptor.  An end
+ *   >= n_nodes, a value below 0 and a value above 1 are KSP_E_ARG; a NaN takes no part.  (12 bytes per edge more.)
+ * ksp_upgma_before: host only — the comparison of two pairs: *before = 1 when the first comes first in the order, else 0.
+ *   KSP_E_ARG for a NULL pointer and a size of 0.
+ * kspider_upgma: reads what kspider_tree reads, with the same validation and refusals, each before any file is written; the ids of
+ *   a participating row must be rows of .namesMap; the value is the column's text read with strtof.  dist_type "min_cont",
+ *   "avg_cont", "max_cont" (NULL / ""); "ani" and an unknown distance are KSP_E_ARG.  Writes, through .partial and a rename,
+ *   PREFIX_kSpider_upgma_<dist>.tsv: "source_1\tsource_2\t<dist>_average\tsum_q\tsize_1\tsize_2\tmerged_size", one row per merge in
+ *   merge order, the two ids the .namesMap ids of lo and hi, the average (double)sum_q / ((double)size_1 * size_2) / 2^32 as
+ *   "%.9g" (for people: sum_q and the sizes, decimal, are the exact data).  newick != 0: also PREFIX_kSpider_upgma_<dist>.newick by
+ *   the conventions of kspider_tree's: height of a merge 1 - average clamped to [0, 1], branch lengths "%.6g", the child holding
+ *   lo first, clusters that never join under one root at height 1 in order of their smallest node, a single node `name;`.
+ *   Device = $KSPIDER_DEVICE; with $KSPIDER_VERBOSE one line reports the records taking part, the pairs, the device rounds and the
+ *   merges made on the device / by the host finish.
+ * kspider_cluster_from_upgma: host only — reads .namesMap and that merge table and keeps a row when sum_q >= q_cut * size_1 *
+ *   size_2 in 128 bits, q_cut = (uint64_t)(cutoff * 4294967296.0); writes PREFIX_kSpider_clusters_upgma_<dist>_<P>%.tsv, P =
+ *   cutoff * 100 as Python prints a float, in the format and order kspider_cluster uses.  KSP_E_ARG for a cut-off outside [0, 1]
+ *   or NaN and an unknown distance; KSP_E_IO for a missing or malformed table or an id that is not in .namesMap.
+ * kspider_pairwise_and_upgma: kspider_pairwise's two TSVs, byte for byte, plus the files of kspider_upgma, the tree taken from the
+ *   gathered, sorted edges on the first device.  Works with $KSPIDER_DEVICE / $KSPIDER_DEVICES and with KSPIDER_TSV=device.  Rows
+ *   that exist only with shared_kmers = 0 have q = 0 and need no host merge.  Every source of the index must be a row of
+ *   .namesMap.  This path sums the FLOATS, kspider_upgma the 6-digit texts: where every value of the column has at most 6
+ *   significant decimal digits all files are byte-equal; otherwise sums, averages and choices among near-ties may differ.   */
+typedef struct ksp_upgma_row {
+    uint32_t lo, hi;
+    uint64_t sum_q;
+    uint32_t size_lo, size_hi;
+} ksp_upgma_row;   /* 24 bytes */
+#define KSP_UPGMA_CHUNK_EDGES 2048u
+#define KSP_UPGMA_TAIL_PAIRS 1024u   /* measured: DESIGN.md 7m */
+int ksp_edges_upgma(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
+                    int dist_col, ksp_upgma_row* h_rows /* room for n_nodes - 1 */, uint32_t* n_rows);
+int ksp_upgma_valued(int device, uint32_t n_nodes, const uint32_t* h_a, const uint32_t* h_b, const float* h_value, uint64_t n_edges,
+                     ksp_upgma_row* h_rows, uint32_t* n_rows);
+int ksp_upgma_before(uint64_t s1, uint32_t size_lo1, uint32_t size_hi1, uint32_t lo1, uint32_t hi1,
+                     uint64_t s2, uint32_t size_lo2, uint32_t size_hi2, uint32_t lo2, uint32_t hi2, int* before);
+int kspider_upgma(const char* index_prefix, const char* dist_type, int newick);
+int kspider_pairwise_and_upgma(const char* index_prefix, int user_threads, const char* dist_type, int newick);
+int kspider_cluster_from_upgma(const char* index_prefix, const char* dist_type, double cutoff);
+
 /* ---- the rows of the pairwise TSV as text, made on the device (csrc/tsv.hip) ----
  * ksp_edges_tsv: the text of `n_edges` ksp_edge records in DEVICE memory (never written), in their order, rows only, no header:
  *       id1 \t id2 \t shared \t min \t avg \t max \n

@@ -18,6 +18,7 @@ falls back to the CPU.
 """
 from .engine import cluster, estimate_ani, export, pairwise, pairwise_ani, pairwise_bins, pairwise_sigs  # noqa: F401
 from .engine import cluster_sweep, pairwise_and_cluster_sweep  # noqa: F401
+from .engine import UPGMA_CHUNK_EDGES, UPGMA_ROW_DTYPE, UPGMA_TAIL_PAIRS, cluster_from_upgma, edges_upgma, pairwise_and_upgma, upgma, upgma_before, upgma_valued  # noqa: F401
 from .engine import TREE_CHUNK_EDGES, cluster_from_tree, edges_forest, forest_ranked, pairwise_and_tree, tree  # noqa: F401
 from .engine import single_linkage_rows  # noqa: F401
 from .engine import CUT_CHUNK_EDGES, edges_cut, pairwise_cut, pairwise_host_cut  # noqa: F401

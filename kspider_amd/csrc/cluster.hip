@@ -284,10 +284,9 @@ done:
     return rc;
 }
 
-// one line per component — in order of their smallest node, members ascending — into PREFIX_kSpider_clusters_<cutoff*100>%.tsv
-// (ks_clustering.py:121-137, 150-163); label[v] = smallest node of v's component, names by node index
-void write_cluster_file(const std::string& prefix, const double threshold, const std::vector<u32>& label,
-                        const std::vector<std::string>& name_of) {
+// one line per component — in order of their smallest node, members ascending — into `out` (ks_clustering.py:121-137, 150-163);
+// label[v] = smallest node of v's component, names by node index
+void write_cluster_file_as(const std::string& out, const std::vector<u32>& label, const std::vector<std::string>& name_of) {
     const u64 N = label.size();
     std::vector<u32> count((size_t)N + 1, 0), order((size_t)N);
     for (u64 v = 0; v < N; ++v) ++count[label[v] + 1];
@@ -296,7 +295,6 @@ void write_cluster_file(const std::string& prefix, const double threshold, const
         std::vector<u32> cur(count.begin(), count.end() - 1);
         for (u64 v = 0; v < N; ++v) order[cur[label[v]]++] = (u32)v;
     }
-    const std::string out = prefix + "_kSpider_clusters_" + py_float_repr(threshold) + "%.tsv";
     std::ofstream f;
     PartialFiles files;
     files.open(out, f);
@@ -309,6 +307,12 @@ void write_cluster_file(const std::string& prefix, const double threshold, const
         f << '\n';
     }
     files.commit();
+}
+
+// the same into PREFIX_kSpider_clusters_<cutoff*100>%.tsv
+void write_cluster_file(const std::string& prefix, const double threshold, const std::vector<u32>& label,
+                        const std::vector<std::string>& name_of) {
+    write_cluster_file_as(prefix + "_kSpider_clusters_" + py_float_repr(threshold) + "%.tsv", label, name_of);
 }
 
 // PREFIX.namesMap -> name of node index v = id - 1 (ks_clustering.py:56-61); ids must be 1..N

@@ -1,5 +1,5 @@
 // The inputs of `kSpider cluster`, read and validated as ks_clustering.py does (:48-61, :67-105), and the text helpers around
-// them.  Shared by the clustering (cluster.hip) and the single-linkage tree (tree.hip); each includes its own copy.
+// them.  Shared by the clustering (cluster.hip), the trees (tree.hip, upgma.hip) and their siblings; each includes its own copy.
 #ifndef KSPIDER_CLUSTER_INPUTS_H
 #define KSPIDER_CLUSTER_INPUTS_H
 #include <algorithm>

@@ -41,6 +41,8 @@ int cc_rounds_on_device(const CcRounds& edges, uint32_t n_nodes, uint64_t n_edge
 void read_names_map(const std::string& prefix, std::vector<std::string>& name_of);
 void write_cluster_file(const std::string& prefix, double threshold, const std::vector<uint32_t>& label,
                         const std::vector<std::string>& name_of);
+// the same lines to a file of the caller's name (through .partial and a rename)
+void write_cluster_file_as(const std::string& out_path, const std::vector<uint32_t>& label, const std::vector<std::string>& name_of);
 // ---- neighbour counts straight from the join's edges (repr.hip; apps/repr_sketches.cpp) ----
 // the text test of the reference on one float: "%.6g" text -> strtof -> as double -> > threshold
 bool repr_text_passes(float v, double threshold);
@@ -136,6 +138,19 @@ int report_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n
 // order of the names.  via_text[v]: the value text of member v's `via` record ("" without one).
 void write_report_files(const std::string& prefix, const std::string& dist, double threshold, const std::vector<ksp_cluster_row>& cluster,
                         const std::vector<ksp_member_row>& member, const std::vector<std::string>& via_text, const std::vector<std::string>& name_of);
+// ---- the average-linkage tree (UPGMA) of the join's edges, exact, on the sparse edge list (upgma.hip) ----
+// what the last tree on this thread did: the records taking part, the pairs after the first fold, the device rounds, the merges
+// made on the device, the live pairs handed to the host finish, its merges, and the longest run a fold inside a round summed
+struct UpgmaTrace {
+    uint64_t taking_part = 0, first_pairs = 0, rounds = 0, device_merges = 0, handed_over = 0, host_merges = 0, longest_run = 0;
+};
+// ksp_edges_upgma on the CURRENT device (h_rows: room for n_nodes - 1 rows); *trace may be NULL
+int upgma_edges_on_device(uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_cnt, int col, ksp_upgma_row* h_rows,
+                          uint32_t* n_rows, UpgmaTrace* trace = nullptr);
+// PREFIX_kSpider_upgma_<dist>.tsv (and .newick) from the rows in merge order (node indices of name_of), through .partial and a
+// rename; on a failure every file this call created is removed again
+void write_upgma_files(const std::string& prefix, const std::string& dist, const std::vector<ksp_upgma_row>& rows, const std::vector<std::string>& name_of,
+                       bool newick);
 // ---- the rows of the pairwise TSV as text, made on the device from the join's edges (tsv.hip) ----
 // takes the next piece of the text (it lives until the call returns); a code other than KSP_OK, with its text in
 // ksp_last_error(), ends the pass
@@ -150,9 +165,10 @@ int tsv_edges_on_device(const char* who, uint32_t n_nodes, const ksp_edge* d_edg
 // kept ones are gathered, sorted and copied.  The other kinds are taken from the sorted edges on the first device, while they
 // are in HBM: the components (cc_edges_on_device), the ranking (repr_edges_on_device), the components at every cut-off of a
 // ladder (sweep_edges_on_device), the maximum spanning forest (tree_edges_on_device), the dereplicated set (derep_edges_on_device),
-// the k best hits of every source (topk_edges_on_device), the report of every cluster (report_edges_on_device).
+// the k best hits of every source (topk_edges_on_device), the report of every cluster (report_edges_on_device), the average-linkage
+// tree (upgma_edges_on_device).
 struct AfterJoin {
-    enum Kind { kNone, kCluster, kRepr, kCut, kSweep, kTree, kDerep, kTopk, kReport };
+    enum Kind { kNone, kCluster, kRepr, kCut, kSweep, kTree, kDerep, kTopk, kReport, kUpgma };
     Kind kind = kNone;
     const uint32_t* kmer_counts = nullptr;   // per (dense) source index
     int col = 0;                             // 3 / 4 / 5; kCluster: also 6 = ANI
@@ -176,6 +192,8 @@ struct AfterJoin {
     std::vector<ksp_cluster_row> cluster_rows;   // kReport: the clusters in order of their root (source indices), and per source index
     std::vector<ksp_member_row> member_rows;     //   its row; `via` is a record of the returned edges; what the passes did
     ReportTrace report;
+    std::vector<ksp_upgma_row> upgma_rows;   // kUpgma: the merges in merge order (source indices); what the rounds did
+    UpgmaTrace upgma;
     // The rows' text, wanted besides whatever `kind` asks for (KSPIDER_TSV=device): the text pass runs on the first device over
     // the gathered, sorted edges, after the consumer.  ids: the id of every source index (n_sources entries).  text_sink takes
     // the pieces in file order.  With kNone and kCut nobody reads the records afterwards, so they are not copied to the host:
@@ -219,6 +237,14 @@ int ksp_debug_topk_classes(uint64_t out[4]);
 /* (tests) what the last ksp_edges_cluster_report / ksp_cluster_report_valued of this thread did: out[0] the kept records, out[1] the
  * chunks that took the single-label path, out[2] the sets of cluster atomics issued, out[3] the sets of source_1-side node atomics. */
 int ksp_debug_report_counts(uint64_t out[4]);
+/* (tests) what the last ksp_edges_upgma / ksp_upgma_valued / kspider_upgma of this thread did: out[0] the pairs after the first fold, out[1]
+ * the device rounds, out[2] the merges made on the device, out[3] the live pairs at the hand-over, out[4] the merges made by the host
+ * finish, out[5] the longest run a fold inside a round summed (0: no round folded a run above 1). */
+int ksp_debug_upgma_counts(uint64_t out[6]);
+/* (tools/upgma_times.py) HIP-event times of `reps` whole runs of ksp_edges_upgma over the same records (allocations, copies and the
+ * host finish included): ms[reps]; counts: ksp_debug_upgma_counts of the last run. */
+int ksp_debug_upgma_times(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col, int reps,
+                          float* ms, ksp_upgma_row* h_rows, uint32_t* n_rows, uint64_t counts[6]);
 /* (tools/report_times.py) HIP-event times of `reps` runs over the same records.  ms holds 5 x reps values: ms[5r] the whole device part
  * of ksp_edges_cluster_report (allocations and the copies to the host included), ms[5r + 1 .. 5r + 3] its accumulate, medoid and links
  * passes alone, ms[5r + 4] the whole of ksp_components_edges on the same records, for comparison: the labels are what both pay. */

@@ -32,6 +32,7 @@ void write_topk_file(const std::string&, const std::string&, const std::vector<s
                      const std::vector<std::string>&) {}
 void write_report_files(const std::string&, const std::string&, double, const std::vector<ksp_cluster_row>&, const std::vector<ksp_member_row>&,
                         const std::vector<std::string>&, const std::vector<std::string>&) {}
+void write_upgma_files(const std::string&, const std::string&, const std::vector<ksp_upgma_row>&, const std::vector<std::string>&, bool) {}
 }  // namespace ksp
 
 extern "C" {

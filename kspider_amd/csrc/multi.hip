@@ -125,6 +125,7 @@ static int after_join_check(const AfterJoin* after) {
     if (after->kind == AfterJoin::kTree && (after->col < 3 || after->col > 5)) { set_error("pairwise: a tree needs a column 3 / 4 / 5 and room for its result"); return KSP_E_ARG; }
     if (after->kind == AfterJoin::kTopk && (after->col < 3 || after->col > 5 || after->k < 1 || after->k > KSP_TOPK_MAX_K)) { set_error("pairwise: top-k needs a column 3 / 4 / 5 and 1 <= k <= KSP_TOPK_MAX_K"); return KSP_E_ARG; }
     if (after->kind == AfterJoin::kReport && (after->col < 3 || after->col > 5 || after->cutoff != after->cutoff)) { set_error("pairwise: a cluster report needs a column 3 / 4 / 5 and a cut-off that is a number"); return KSP_E_ARG; }
+    if (after->kind == AfterJoin::kUpgma && (after->col < 3 || after->col > 5)) { set_error("pairwise: an average-linkage tree needs a column 3 / 4 / 5"); return KSP_E_ARG; }
     if (after->kind == AfterJoin::kSweep && (!after->cutoffs || after->n_cutoffs < 1 || after->n_cutoffs > KSP_SWEEP_MAX_CUTOFFS)) {
         set_error("pairwise: a cut-off ladder has between 1 and 255 cut-offs");
         return KSP_E_ARG;
@@ -184,6 +185,11 @@ static int after_join_run(AfterJoin& A, const u32 N, const ksp_edge* d_all, cons
             A.cluster_rows.assign((size_t)N + 1, ksp_cluster_row()); A.member_rows.assign((size_t)N + 1, ksp_member_row());
             if (run) rc = report_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.cutoff, A.cluster_rows.data(), &n_out, A.member_rows.data(), &A.report);
             A.cluster_rows.resize(n_out); A.member_rows.resize((size_t)N);
+            break;
+        case AfterJoin::kUpgma:   // (upgma_rows: the merges in merge order)
+            A.upgma_rows.assign((size_t)N + 1, ksp_upgma_row());
+            if (run) rc = upgma_edges_on_device(N, d_all, total, d_cnt.as<u32>(), A.col, A.upgma_rows.data(), &n_out, &A.upgma);
+            A.upgma_rows.resize(n_out);
             break;
         default:   // kRepr
             A.node.assign((size_t)N, 0);

@@ -72,15 +72,16 @@ using ksp::AfterJoin;
 //   kDerep    the dereplicated set: greedy representatives in rank order and the members they stand for
 //   kTopk     the k best hits of every source
 //   kReport   the report of every cluster at one cut-off: density, value range, medoid, coverage, and the members' table
+//   kUpgma    the average-linkage tree: the exact UPGMA merges of the edges
 struct PairwiseJob {
     std::string prefix;
     int threads = 1;
     bool ani = false;       // also write the ANI column of `pairwise --estimate-ani` (ks_pairwise.py:29-84; k from PREFIX.extra)
     AfterJoin after;
-    std::string dist;       // kSweep, kTree, kReport: the distance's name in their file names
+    std::string dist;       // kSweep, kTree, kReport, kUpgma: the distance's name in their file names
     std::string repr_out;   // kRepr: "" = PREFIX_kSpider_repr_sketches.txt; kDerep: "" = PREFIX_kSpider_dereplicated_<dist>.tsv;
                             // kTopk: "" = PREFIX_kSpider_topk_<dist>.tsv
-    bool newick = false;    // kTree
+    bool newick = false;    // kTree, kUpgma
     PairwiseJob(const char* index_prefix, int user_threads, AfterJoin::Kind kind = AfterJoin::kNone, int col = 0)
         : prefix(index_prefix), threads(user_threads < 1 ? 1 : user_threads) { after.kind = kind; after.col = col; }
 };
@@ -149,7 +150,7 @@ void node_labels_of(const std::vector<uint32_t>& ids, const uint32_t* lab, const
 int load_inputs(const PairwiseJob& job, ksp::IndexData& ix, std::vector<std::string>& derep_names) {
     auto t0 = Clock::now();
     ksp::load_index(job.prefix, ix);
-    if (job.after.kind == AfterJoin::kDerep || job.after.kind == AfterJoin::kTopk || job.after.kind == AfterJoin::kReport) {   // every source must be a row of .namesMap: refused before any file is written
+    if (job.after.kind == AfterJoin::kDerep || job.after.kind == AfterJoin::kTopk || job.after.kind == AfterJoin::kReport || job.after.kind == AfterJoin::kUpgma) {   // every source must be a row of .namesMap: refused before any file is written
         ksp::read_names_map(job.prefix, derep_names);
         for (auto& c : ix.colors)
             for (uint32_t g : c.second) ksp::check_row_nodes(g, g, derep_names.size());
@@ -633,6 +634,21 @@ int finish_report(PairwiseJob& job, const Postings& P, const std::vector<ZeroRow
     return KSP_OK;
 }
 
+// The device's merges name source indices: index order is id order, so lo < hi and "the smallest member" survive the step to
+// .namesMap nodes (id - 1).  A shared-0 row has q = 0 and takes no part: nothing to merge in on the host.
+void finish_upgma(PairwiseJob& job, const Postings& P, const std::vector<std::string>& name_of) {
+    AfterJoin& A = job.after;
+    std::vector<ksp_upgma_row> rows = A.upgma_rows;
+    for (ksp_upgma_row& r : rows) {
+        r.lo = P.ids[r.lo] - 1;   // (every source is a row of .namesMap: checked before the first file)
+        r.hi = P.ids[r.hi] - 1;
+    }
+    ksp::write_upgma_files(job.prefix, job.dist, rows, name_of, job.newick);
+    if (std::getenv("KSPIDER_VERBOSE"))
+        std::cout << "kspider_amd: upgma: " << A.upgma.taking_part << " records taking part, " << A.upgma.first_pairs << " pairs, " << A.upgma.rounds
+                  << " device rounds, merges " << A.upgma.device_merges << " on the device / " << A.upgma.host_merges << " by the host finish" << std::endl;
+}
+
 // Mirrors src/pairwise.cpp:123-276 phase by phase (the head of this file), with what job.after asks for between the join and the files.
 int run_job(PairwiseJob& job) {
     AfterJoin& A = job.after;
@@ -745,6 +761,7 @@ int run_job(PairwiseJob& job) {
         case AfterJoin::kTree: finish_tree(job, P, zero_rows, n_edges, forest); break;
         case AfterJoin::kDerep: finish_derep(job, P, derep_text, derep_names); break;
         case AfterJoin::kTopk: finish_topk(job, P, topk_hits, derep_names, n_edges); break;
+        case AfterJoin::kUpgma: finish_upgma(job, P, derep_names); break;
         case AfterJoin::kReport: return finish_report(job, P, zero_rows, rows, report_values, derep_names, devices.empty() ? 0 : devices[0]);
     }
     return KSP_OK;
@@ -824,6 +841,20 @@ extern "C" int kspider_pairwise_and_tree(const char* index_prefix, int user_thre
     job.dist = dt;
     job.newick = newick != 0;
     return guarded("kspider_pairwise_and_tree", true, job);
+}
+
+extern "C" int kspider_pairwise_and_upgma(const char* index_prefix, int user_threads, const char* dist_type, int newick) {
+    if (!index_prefix) { ksp::set_error("kspider_pairwise_and_upgma: index_prefix is NULL"); return KSP_E_ARG; }
+    std::string dt;
+    const int col = dist_column(dist_type, "max_cont", &dt);
+    if (!col) {
+        ksp::set_error("kspider_pairwise_and_upgma: distance '" + dt + "' is not min_cont, avg_cont or max_cont (an average is one of containments in [0, 1])");
+        return KSP_E_ARG;
+    }
+    PairwiseJob job(index_prefix, user_threads, AfterJoin::kUpgma, col);
+    job.dist = dt;
+    job.newick = newick != 0;
+    return guarded("kspider_pairwise_and_upgma", true, job);
 }
 
 extern "C" int kspider_pairwise_and_repr(const char* index_prefix, int user_threads, const char* dist_type, double threshold, const char* out_path) {

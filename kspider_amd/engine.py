@@ -48,6 +48,12 @@ CLUSTER_ROW_DTYPE = np.dtype([("root", "<u4"), ("size", "<u4"), ("edges", "<u8")
                               ("medoid", "<u4"), ("covered", "<u4")])
 MEMBER_ROW_DTYPE = np.dtype([("label", "<u4"), ("degree", "<u4"), ("strength", "<u8"), ("via", "<u4"), ("reserved", "<u4")])
 
+#: the average-linkage tree (KSP_UPGMA_* in the header): entries per chunk of its passes; the live pairs at or below which the host
+#: finishes (measured: DESIGN.md 7m); ksp_upgma_row (24 bytes)
+UPGMA_CHUNK_EDGES = 2048
+UPGMA_TAIL_PAIRS = 1024
+UPGMA_ROW_DTYPE = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("sum_q", "<u8"), ("size_lo", "<u4"), ("size_hi", "<u4")])
+
 #: the device's row text (KSP_TSV_* in the header): rows per chunk of the text passes, the shortest and the longest row in bytes
 TSV_CHUNK_ROWS = 256
 TSV_ROW_MIN = 12
@@ -82,6 +88,7 @@ ABI_SYMBOLS = [
     "ksp_edges_dereplicate", "kspider_dereplicate", "kspider_pairwise_and_dereplicate",
     "ksp_edges_topk", "ksp_topk_ranked", "kspider_topk", "kspider_pairwise_and_topk",
     "ksp_edges_cluster_report", "ksp_cluster_report_valued", "kspider_cluster_report", "kspider_pairwise_and_cluster_report",
+    "ksp_edges_upgma", "ksp_upgma_valued", "ksp_upgma_before", "kspider_upgma", "kspider_pairwise_and_upgma", "kspider_cluster_from_upgma",
     "ksp_edges_tsv",
 ]
 
@@ -258,6 +265,16 @@ def lib():
         L.ksp_debug_report_counts.argtypes = [ctypes.c_void_p]
         L.ksp_debug_report_times.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_edges_upgma.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_upgma_valued.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_upgma_before.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                       ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int)]
+        L.kspider_upgma.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]
+        L.kspider_pairwise_and_upgma.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        L.kspider_cluster_from_upgma.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double]
+        L.ksp_debug_upgma_counts.argtypes = [ctypes.c_void_p]
+        L.ksp_debug_upgma_times.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.ksp_edges_tsv.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
         L.ksp_debug_format_floats.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
@@ -722,6 +739,80 @@ def pairwise_and_cluster_report(index_prefix: str, user_threads: int = 1, dist_t
     """`pairwise` plus the two files of `cluster_report`, the report taken from the edges while they are in HBM."""
     _check(lib().kspider_pairwise_and_cluster_report(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
                                                      float(cutoff)))
+
+
+def _upgma_out(who, n_nodes, tail, fill, call):
+    """The rows of an UPGMA call with `tail` rows of the byte `fill` behind the room for n_nodes - 1 rows (which starts as `fill` too).
+    After a refused call (KspError) every byte is checked to be untouched; after a good one the rows behind n_rows are."""
+    room = max(0, n_nodes - 1)
+    rows = np.full((room + tail) * UPGMA_ROW_DTYPE.itemsize, fill, dtype=np.uint8)
+    n_rows = np.full(1 + tail, fill * 0x01010101, dtype=np.uint32)
+    try:
+        _check(call(rows.ctypes.data if rows.size else None, n_rows.ctypes.data))
+    except KspError:
+        if (rows != fill).any() or (n_rows != fill * 0x01010101).any():
+            raise AssertionError(f"{who} wrote to its outputs although it refused the call")
+        raise
+    n = int(n_rows[0])
+    if n > room:
+        raise AssertionError(f"{who} reported more merges than a forest has")
+    if (rows[n * UPGMA_ROW_DTYPE.itemsize:] != fill).any() or (n_rows[1:] != fill * 0x01010101).any():
+        raise AssertionError(f"{who} wrote behind its rows")
+    return rows[:n * UPGMA_ROW_DTYPE.itemsize].view(UPGMA_ROW_DTYPE).copy()
+
+
+def edges_upgma(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, dist_col: int = 5, device: int = 0, tail: int = 0,
+                fill: int = 0) -> np.ndarray:
+    """The exact average-linkage (UPGMA) merges of ksp_edge records in DEVICE memory (include/kspider_amd.h), in merge order: a structured
+    array of UPGMA_ROW_DTYPE.  tail / fill (tests): that many rows of the byte `fill` are kept behind the room the call may use and
+    checked to be untouched, as are the rows behind the last one."""
+    return _upgma_out("ksp_edges_upgma", n_nodes, tail, fill, lambda pr, pn: lib().ksp_edges_upgma(
+        device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, int(dist_col), pr, pn))
+
+
+def upgma_valued(n_nodes: int, a: np.ndarray, b: np.ndarray, value: np.ndarray, device: int = 0, tail: int = 0, fill: int = 0) -> np.ndarray:
+    """The same merges for host edges the caller has valued already: value[e] in [0, 1] or NaN (takes no part)."""
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    value = np.ascontiguousarray(value, dtype=np.float32)
+    if not (a.size == b.size == value.size):
+        raise ValueError("a, b and value need one entry per edge")
+    return _upgma_out("ksp_upgma_valued", n_nodes, tail, fill, lambda pr, pn: lib().ksp_upgma_valued(
+        device, n_nodes, a.ctypes.data, b.ctypes.data, value.ctypes.data, a.size, pr, pn))
+
+
+def upgma_before(pair1, pair2) -> bool:
+    """Host only: does candidate pair 1 come before pair 2 in the order of the average-linkage tree?  A pair is
+    (sum_q, size_lo, size_hi, lo, hi); the similarities sum_q / (size_lo * size_hi) are compared exactly."""
+    out = ctypes.c_int(-1)
+    _check(lib().ksp_upgma_before(*[int(x) for x in pair1], *[int(x) for x in pair2], ctypes.byref(out)))
+    return bool(out.value)
+
+
+def upgma_counts() -> dict:
+    """(tests) What the last UPGMA call of this thread did (ksp_debug_upgma_counts, csrc/engine_internal.h)."""
+    out = np.zeros(6, dtype=np.uint64)
+    _check(lib().ksp_debug_upgma_counts(out.ctypes.data))
+    return dict(first_pairs=int(out[0]), rounds=int(out[1]), device_merges=int(out[2]), handed_over=int(out[3]), host_merges=int(out[4]),
+                longest_run=int(out[5]))
+
+
+def upgma(index_prefix: str, dist_type: str = "max_cont", newick: bool = False) -> None:
+    """The average-linkage tree (UPGMA) of the pairwise TSV: PREFIX_kSpider_upgma_<DIST>.tsv, one row per merge (and .newick), the
+    merges found on the GPU from the sparse rows; `cluster_from_upgma` then writes the clusters of any cut-off from it."""
+    _check(lib().kspider_upgma(os.fsencode(index_prefix), dist_type.encode() if dist_type is not None else None, int(bool(newick))))
+
+
+def pairwise_and_upgma(index_prefix: str, user_threads: int = 1, dist_type: str = "max_cont", newick: bool = False) -> None:
+    """`pairwise` plus the files of `upgma`, the merges taken from the edges while they are in HBM."""
+    _check(lib().kspider_pairwise_and_upgma(os.fsencode(index_prefix), int(user_threads), dist_type.encode() if dist_type is not None else None,
+                                            int(bool(newick))))
+
+
+def cluster_from_upgma(index_prefix: str, dist_type: str = "max_cont", cutoff: float = 0.0) -> None:
+    """The clusters of the average-linkage tree at one cut-off, from PREFIX_kSpider_upgma_<DIST>.tsv alone (host only):
+    PREFIX_kSpider_clusters_upgma_<DIST>_<CUTOFF*100>%.tsv in the format of `cluster`."""
+    _check(lib().kspider_cluster_from_upgma(os.fsencode(index_prefix), dist_type.encode() if dist_type is not None else None, float(cutoff)))
 
 
 def edges_tsv(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: int, d_ids_ptr: int = 0, device: int = 0, capacity: int | None = None,
