@@ -816,6 +816,74 @@ int kspider_cluster_from_upgma(const char* index_prefix, const char* dist_type, 
 int ksp_edges_tsv(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts,
                   const uint32_t* d_ids, char* h_text, uint64_t capacity, uint64_t* n_bytes);
 
+/* ---- query mode: new sketches against a database, without the N x N join (csrc/query.hip, csrc/sketch_pack.cpp) ----
+ * Numbering: database sources are 0 .. n_db - 1, queries n_db .. n_db + n_q - 1.  An edge is a ksp_edge with source_1 < source_2 in
+ * that numbering and shared > 0.  mode KSP_QUERY_CROSS: only database x query pairs (source_1 < n_db <= source_2);
+ * KSP_QUERY_CROSS_AND_SELF: also every query x query pair once (source_2 >= n_db) — the old database x database table plus this
+ * result is the full table of the union (the append case).  Runs are duplicate-free within a source, as everywhere in this ABI;
+ * the table build sorts and deduplicates the query side itself, and the probe does not depend on the order of a database run.
+ * ksp_query_device: the caller keeps the database in HBM and calls per batch of queries.  d_db_keys / d_q_keys: DEVICE memory, the
+ *   runs back to back; h_db_offsets / h_q_offsets: HOST memory, n + 1 element offsets.  The edges go to d_edges (device, room for
+ *   `capacity` records) in unspecified order; *n_edges = the edges found.  More than `capacity`: KSP_E_OVERFLOW, *n_edges is the
+ *   required size and nothing was written past `capacity`; d_edges NULL with capacity 0 is the size query.  KSP_E_ARG, before
+ *   anything is allocated: a NULL pointer (stats may be NULL), n_db = 0 or n_q = 0, offsets that do not start at 0 or decrease, an
+ *   unknown mode.  KSP_E_LIMIT: n_db + n_q > 2^32 - 2, a query tile of 2^31 entries or more, memory that does not fit the device's
+ *   free memory (the message says what was asked).  The queries are taken in tiles of at most KSP_QUERY_TILE_MAX: n_q above it
+ *   means one pass over the database per tile.  Read on every call: $KSP_QUERY_TILE (queries per tile, 1 .. KSP_QUERY_TILE_MAX),
+ *   $KSP_QUERY_LONG_RUN (a probe source of that many entries or more gets a workgroup instead of a wave; default
+ *   KSP_QUERY_LONG_RUN), $KSP_QUERY_LIST (touched-list capacity, 1 .. KSP_QUERY_LIST_MAX), $KSP_QUERY_MAX_WORKGROUPS (caps the grids;
+ *   tests).  The result is the same under each.
+ * ksp_query_host: the same for HOST arrays: uploads, calls, retries once at the exact size, sorts the edges by (source_1, source_2)
+ *   on the device and returns them in *edges (ksp_free).  A device that is not there: KSP_E_HIP, "ksp_query_host: no such device".
+ * ksp_query_directory: host only — the first level of a tile's table: for a table of n_keys distinct keys, the largest max_key,
+ *   dir[b] is the first index whose key >> *shift is >= b, b = 0 .. 2^*bits.  *bits + *shift = the significant bits of max_key;
+ *   about four keys per bucket of a uniform table, 1 <= *bits <= KSP_QUERY_DIR_BITS_MAX (0 and shift 0 for max_key = 0).
+ * kspider_pack: one pack file (csrc/sketch_set.h: little-endian, fixed width) from a directory of .sig / .gz files (kSize > 0) or
+ *   .bin files (kSize = 0); group ids, names, k-mer counts and the skipping of a signature without that ksize are exactly those of
+ *   kspider_pairwise_sigs / kspider_pairwise_bins.  Written through OUT.partial and a rename: a failed write leaves no file.
+ * ksp_pack_info / ksp_pack_load: host only — read a pack file whole and checked, or refuse with KSP_E_IO and nothing written to the
+ *   caller: a wrong magic or version, a length that is not exactly what the header implies, offsets that do not start at 0 or
+ *   decrease, a run that is not strictly ascending, a presence or name count that disagrees with the header.  out[0] kSize, out[1]
+ *   groups G, out[2] groups with a sketch S, out[3] keys K, out[4] bytes of all names B.  load: kmers[G], present[G], offsets[S + 1],
+ *   keys[K], name_offsets[G + 1], names[B] (no terminators).
+ * kspider_query: db and queries are each a pack file or a directory (.sig / .gz for kSize > 0, .bin for kSize = 0); a pack whose
+ *   kSize differs from a non-zero kSize is KSP_E_ARG; out_prefix is required.  Writes OUT.namesMap (database names with ids 1 .. N,
+ *   then the queries N + 1 .. N + Q), OUT_kSpider_seqToKmersNo.tsv and OUT_kSpider_pairwise.tsv with only the rows of the mode,
+ *   sorted by (source_1, source_2), maths and text those of the pairwise writer — ordinary pairwise files for kspider_topk,
+ *   kspider_cluster, kspider_export and the others.  A refused or failed call writes no file.  Device = $KSPIDER_DEVICE (default
+ *   0); $KSPIDER_DEVICES and $KSPIDER_TSV are not read.                                                                          */
+#define KSP_QUERY_CROSS 0
+#define KSP_QUERY_CROSS_AND_SELF 1
+#define KSP_QUERY_TILE_MAX 2048u      /* 8 KiB of u32 counters per probe source in LDS */
+#define KSP_QUERY_LIST_MAX 512u
+#define KSP_QUERY_LONG_RUN 2048u
+#define KSP_QUERY_DIR_BITS_MAX 24
+typedef struct ksp_query_stats {
+    uint64_t n_db, n_q;
+    uint64_t db_entries, q_entries;
+    uint64_t table_keys;       /* distinct keys, summed over the tiles                                  */
+    uint64_t table_holders;    /* (key, query) memberships, summed over the tiles                      */
+    uint64_t passes;           /* query tiles probed: passes over the database                         */
+    uint64_t short_sources;    /* probe sources of a pass that get a wave                              */
+    uint64_t long_sources;     /* ... that get a workgroup                                             */
+    uint64_t list_overflows;   /* (source, tile) emissions that scanned all counters                   */
+    uint64_t edges;
+    uint64_t long_run;         /* the switches as the call read them                                   */
+    float ms_table, ms_probe;  /* HIP-event times, summed over the tiles                               */
+    float ms_sort;             /* ksp_query_host: the sort of the edges                                */
+    uint32_t tile, list_capacity, reserved;
+} ksp_query_stats;   /* 120 bytes */
+int ksp_query_device(int device, const uint64_t* d_db_keys, const uint64_t* h_db_offsets, uint32_t n_db, const uint64_t* d_q_keys,
+                     const uint64_t* h_q_offsets, uint32_t n_q, int mode, ksp_edge* d_edges, uint64_t capacity, uint64_t* n_edges,
+                     ksp_query_stats* stats);
+int ksp_query_host(const uint64_t* db_keys, const uint64_t* db_offsets, uint32_t n_db, const uint64_t* q_keys, const uint64_t* q_offsets,
+                   uint32_t n_q, int mode, int device, ksp_edge** edges, uint64_t* n_edges, ksp_query_stats* stats);
+int ksp_query_directory(uint64_t max_key, uint64_t n_keys, int* bits, int* shift);
+int kspider_pack(const char* dir, int kSize, const char* out_path, int user_threads);
+int ksp_pack_info(const char* path, uint64_t out[5]);
+int ksp_pack_load(const char* path, uint32_t* kmers, uint8_t* present, uint64_t* offsets, uint64_t* keys, uint64_t* name_offsets, char* names);
+int kspider_query(const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, int mode);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

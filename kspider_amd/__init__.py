@@ -10,6 +10,8 @@ Host-side mirror of the reference interface for this one path:
   kspider_amd.cluster_sweep(index_prefix, dist_type, cutoffs)  `kSpider cluster` at a list of cut-offs in one device pass
   kspider_amd.tree(index_prefix, dist_type, newick)  the single-linkage tree of the pairwise TSV (maximum spanning forest on the GPU)
   kspider_amd.cluster_from_tree(index_prefix, dist_type, cutoff)  `kSpider cluster` at any cut-off from the tree file alone
+  kspider_amd.query(db, queries, kSize, out_prefix, threads, mode)  new sketches against a database, without the N x N join
+  kspider_amd.pack(sketch_dir, kSize, out_path, threads)  a directory of sketches as one database file
   kspider_amd.engine                                   ctypes binding of include/kspider_amd.h
   kspider_amd.dist                                     tile sharding + edge gather for one-process-per-GPU runs
   kspider_amd.synth                                    synthetic sketch sets shaped like BASELINE.json's configs
@@ -22,8 +24,10 @@ from .engine import UPGMA_CHUNK_EDGES, UPGMA_ROW_DTYPE, UPGMA_TAIL_PAIRS, cluste
 from .engine import TREE_CHUNK_EDGES, cluster_from_tree, edges_forest, forest_ranked, pairwise_and_tree, tree  # noqa: F401
 from .engine import single_linkage_rows  # noqa: F401
 from .engine import CUT_CHUNK_EDGES, edges_cut, pairwise_cut, pairwise_host_cut  # noqa: F401
+from .engine import QUERY_CROSS, QUERY_CROSS_AND_SELF, pack, query  # noqa: F401
 
 __all__ = ["pairwise", "pairwise_sigs", "pairwise_bins", "cluster", "estimate_ani", "pairwise_ani", "export",
+           "query", "pack", "QUERY_CROSS", "QUERY_CROSS_AND_SELF",
            "single_linkage_rows", "pairwise_cut", "pairwise_host_cut", "edges_cut", "CUT_CHUNK_EDGES",
            "cluster_sweep", "pairwise_and_cluster_sweep",
            "tree", "pairwise_and_tree", "cluster_from_tree", "edges_forest", "forest_ranked", "TREE_CHUNK_EDGES"]

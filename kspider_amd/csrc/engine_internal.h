@@ -254,6 +254,9 @@ int ksp_debug_report_times(int device, uint32_t n_nodes, const ksp_edge* d_edges
  * 1 = rocprim::segmented_radix_sort_keys and a gather (KSP_TOPK_SELECT=library). */
 int ksp_debug_topk_times(int device, uint32_t n_nodes, const ksp_edge* d_edges, uint64_t n_edges, const uint32_t* d_kmer_counts, int dist_col,
                          uint32_t k, int which, int reps, float* ms, uint32_t* h_index, uint32_t* h_count);
+/* (tools/query_times.py) HIP-event times of `reps` device-to-device copies of `bytes` bytes: the copy rate of the session, the
+ * yardstick of the query probe's floor (8 bytes per database hash). */
+int ksp_debug_copy_times(int device, uint64_t bytes, int reps, float* ms);
 /* (tests) the device's "%.6g" (tsv_text.h) on n host floats: h_text[16 * i ...] holds the h_len[i] bytes of value i's text.  KSP_E_ARG,
  * with nothing written, when a value is outside the domain: 0, +inf and the positive floats in [2^-40, 2^40). */
 int ksp_debug_format_floats(int device, const float* h_values, uint64_t n, char* h_text /* n x 16 */, uint32_t* h_len);

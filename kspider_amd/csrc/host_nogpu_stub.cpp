@@ -102,6 +102,10 @@ int ksp_debug_tsv_times(int, uint32_t, const ksp_edge*, uint64_t, const uint32_t
     ksp::set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }
+int ksp_query_host(const uint64_t*, const uint64_t*, uint32_t, const uint64_t*, const uint64_t*, uint32_t, int, int, ksp_edge**, uint64_t*, ksp_query_stats*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
 void ksp_free(void* p) { std::free(p); }
 int ksp_engine_lists_path(const ksp_engine*, int*) {
     ksp::set_error("host-only sanitizer build: no HIP engine");

@@ -41,6 +41,7 @@
 #include "../../include/kspider_amd.h"
 #include "engine_internal.h"
 #include "index_io.h"
+#include "sketch_set.h"
 
 namespace {
 
@@ -219,11 +220,7 @@ bool parse_sig(const std::string& path, const std::string& text, int k, std::vec
     return found;
 }
 
-struct Source {
-    uint32_t id;
-    uint32_t kmers;               // what the reference stores in groupID_to_kmerCount
-    std::vector<uint64_t> run;    // sorted unique hashes
-};
+typedef ksp::SketchSource Source;
 
 int run_sources(const std::string& prefix, const std::vector<std::pair<uint32_t, std::string>>& names,
                 std::vector<Source>& src, int threads) {
@@ -285,50 +282,80 @@ int guarded(Fn fn) {
 
 }  // namespace
 
+void ksp::load_sig_dir(const std::string& sigs_dir, int kSize, int user_threads, SketchNames& names, std::vector<SketchSource>& src) {
+    const std::string dir = strip_slashes(sigs_dir);
+    std::unordered_map<std::string, uint32_t> id_of;
+    std::vector<std::string> sig_files;
+    uint32_t next_id = 1;
+    for (auto& f : glob_dir(dir)) {
+        const std::string ext = extension_of(f);
+        if (ext != "sig" && ext != "gz") continue;
+        const std::string name = stem_of(f);
+        if (!id_of.count(name)) {
+            id_of[name] = next_id;
+            names.emplace_back(next_id, name);
+            ++next_id;
+        }
+        if (ext == "sig") sig_files.push_back(f);   // pass 2 of the reference reads ".sig" only
+    }
+    if (names.empty()) throw std::runtime_error("kspider_amd: no .sig/.gz files in " + dir);
+    // files are read, parsed and sorted by `user_threads` host threads; the reference's sequential
+    // semantics (a later file of the same group replaces the earlier one) are applied in file order
+    std::vector<Source> parsed(sig_files.size());
+    std::vector<char> has(sig_files.size(), 0);
+    parallel_for(sig_files.size(), user_threads, [&](size_t i) {
+        const std::string& f = sig_files[i];
+        std::vector<uint64_t> mins;
+        if (!parse_sig(f, read_maybe_gz(f), kSize, mins)) return;   // no signature with that ksize
+        Source& s = parsed[i];
+        s.id = id_of.at(stem_of(f));
+        s.kmers = (uint32_t)mins.size();
+        std::sort(mins.begin(), mins.end());
+        mins.erase(std::unique(mins.begin(), mins.end()), mins.end());
+        s.run.swap(mins);
+        has[i] = 1;
+    });
+    std::unordered_map<uint32_t, Source> by_id;
+    for (size_t i = 0; i < sig_files.size(); ++i)
+        if (has[i]) by_id[parsed[i].id] = std::move(parsed[i]);
+    if (by_id.empty()) throw std::runtime_error("kspider_amd: no signature with ksize " + std::to_string(kSize));
+    for (auto& kv : by_id) src.push_back(std::move(kv.second));
+    std::sort(src.begin(), src.end(), [](const Source& a, const Source& b) { return a.id < b.id; });
+}
+
+void ksp::load_bin_dir(const std::string& bins_dir, int user_threads, SketchNames& names, std::vector<SketchSource>& src) {
+    const std::string dir = strip_slashes(bins_dir);
+    std::vector<std::string> files;
+    std::unordered_map<std::string, uint32_t> seen;
+    uint32_t next_id = 1;
+    for (auto& f : glob_dir(dir)) {
+        if (extension_of(f) != "bin") continue;
+        const std::string name = stem_of(f);
+        if (seen.count(name)) continue;
+        seen[name] = next_id;
+        names.emplace_back(next_id, name);
+        Source s;
+        s.id = next_id++;
+        src.push_back(std::move(s));
+        files.push_back(f);
+    }
+    parallel_for(files.size(), user_threads, [&](size_t i) {
+        Source& s = src[i];
+        ksp::load_u64_set(files[i], s.run);
+        s.kmers = (uint32_t)s.run.size();
+        std::sort(s.run.begin(), s.run.end());
+        s.run.erase(std::unique(s.run.begin(), s.run.end()), s.run.end());
+    });
+    if (src.empty()) throw std::runtime_error("kspider_amd: no .bin files in " + dir);
+}
+
 extern "C" int kspider_pairwise_sigs(const char* sigs_dir, int kSize, const char* out_prefix, int user_threads) {
     if (!sigs_dir) { ksp::set_error("kspider_pairwise_sigs: sigs_dir is NULL"); return KSP_E_ARG; }
     return guarded([&]() {
-        const std::string dir = strip_slashes(sigs_dir);
-        const std::string prefix = (out_prefix && *out_prefix) ? out_prefix : default_prefix(dir);
-        std::vector<std::pair<uint32_t, std::string>> names;
-        std::unordered_map<std::string, uint32_t> id_of;
-        std::vector<std::string> sig_files;
-        uint32_t next_id = 1;
-        for (auto& f : glob_dir(dir)) {
-            const std::string ext = extension_of(f);
-            if (ext != "sig" && ext != "gz") continue;
-            const std::string name = stem_of(f);
-            if (!id_of.count(name)) {
-                id_of[name] = next_id;
-                names.emplace_back(next_id, name);
-                ++next_id;
-            }
-            if (ext == "sig") sig_files.push_back(f);   // pass 2 of the reference reads ".sig" only
-        }
-        if (names.empty()) throw std::runtime_error("kspider_amd: no .sig/.gz files in " + dir);
-        // files are read, parsed and sorted by `user_threads` host threads; the reference's sequential
-        // semantics (a later file of the same group replaces the earlier one) are applied in file order
-        std::vector<Source> parsed(sig_files.size());
-        std::vector<char> has(sig_files.size(), 0);
-        parallel_for(sig_files.size(), user_threads, [&](size_t i) {
-            const std::string& f = sig_files[i];
-            std::vector<uint64_t> mins;
-            if (!parse_sig(f, read_maybe_gz(f), kSize, mins)) return;   // no signature with that ksize
-            Source& s = parsed[i];
-            s.id = id_of.at(stem_of(f));
-            s.kmers = (uint32_t)mins.size();
-            std::sort(mins.begin(), mins.end());
-            mins.erase(std::unique(mins.begin(), mins.end()), mins.end());
-            s.run.swap(mins);
-            has[i] = 1;
-        });
-        std::unordered_map<uint32_t, Source> by_id;
-        for (size_t i = 0; i < sig_files.size(); ++i)
-            if (has[i]) by_id[parsed[i].id] = std::move(parsed[i]);
-        if (by_id.empty()) throw std::runtime_error("kspider_amd: no signature with ksize " + std::to_string(kSize));
+        const std::string prefix = (out_prefix && *out_prefix) ? out_prefix : default_prefix(sigs_dir);
+        ksp::SketchNames names;
         std::vector<Source> src;
-        for (auto& kv : by_id) src.push_back(std::move(kv.second));
-        std::sort(src.begin(), src.end(), [](const Source& a, const Source& b) { return a.id < b.id; });
+        ksp::load_sig_dir(sigs_dir, kSize, user_threads, names, src);
         return run_sources(prefix, names, src, user_threads < 1 ? 1 : user_threads);
     });
 }
@@ -336,32 +363,10 @@ extern "C" int kspider_pairwise_sigs(const char* sigs_dir, int kSize, const char
 extern "C" int kspider_pairwise_bins(const char* bins_dir, const char* out_prefix, int user_threads) {
     if (!bins_dir) { ksp::set_error("kspider_pairwise_bins: bins_dir is NULL"); return KSP_E_ARG; }
     return guarded([&]() {
-        const std::string dir = strip_slashes(bins_dir);
-        const std::string prefix = (out_prefix && *out_prefix) ? out_prefix : default_prefix(dir);
-        std::vector<std::pair<uint32_t, std::string>> names;
+        const std::string prefix = (out_prefix && *out_prefix) ? out_prefix : default_prefix(bins_dir);
+        ksp::SketchNames names;
         std::vector<Source> src;
-        std::vector<std::string> files;
-        std::unordered_map<std::string, uint32_t> seen;
-        uint32_t next_id = 1;
-        for (auto& f : glob_dir(dir)) {
-            if (extension_of(f) != "bin") continue;
-            const std::string name = stem_of(f);
-            if (seen.count(name)) continue;
-            seen[name] = next_id;
-            names.emplace_back(next_id, name);
-            Source s;
-            s.id = next_id++;
-            src.push_back(std::move(s));
-            files.push_back(f);
-        }
-        parallel_for(files.size(), user_threads, [&](size_t i) {
-            Source& s = src[i];
-            ksp::load_u64_set(files[i], s.run);
-            s.kmers = (uint32_t)s.run.size();
-            std::sort(s.run.begin(), s.run.end());
-            s.run.erase(std::unique(s.run.begin(), s.run.end()), s.run.end());
-        });
-        if (src.empty()) throw std::runtime_error("kspider_amd: no .bin files in " + dir);
+        ksp::load_bin_dir(bins_dir, user_threads, names, src);
         return run_sources(prefix, names, src, user_threads < 1 ? 1 : user_threads);
     });
 }

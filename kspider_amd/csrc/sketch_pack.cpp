@@ -1,0 +1,306 @@
+// A database of sketches in one file, and the file entry point of query mode.  Host only.
+//   kspider_pack    a directory of .sig / .gz files (kSize > 0) or .bin files (kSize = 0) -> one pack file.  The loaders, and so
+//                   the group ids, the names, the k-mer counts and the skipping of a signature without that ksize, are those of
+//                   kspider_pairwise_sigs / kspider_pairwise_bins (sketch_loaders.cpp).  The format: sketch_set.h.
+//   kspider_query   database and queries, each a pack file or a directory -> the three files of a pairwise run over
+//                   database + queries, the TSV holding only the rows of the mode.  The device part is ksp_query_host (query.hip).
+#include <sys/stat.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <stdexcept>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/kspider_amd.h"
+#include "engine_internal.h"
+#include "index_io.h"
+#include "partial_file.h"
+#include "sketch_set.h"
+
+namespace {
+
+const char kMagic[8] = {'K', 'S', 'P', 'P', 'A', 'C', 'K', '1'};
+constexpr uint32_t kVersion = 1;
+constexpr uint64_t kHeaderBytes = 8 + 4 + 4 + 4 * 8;
+
+uint64_t pad8(const uint64_t n) { return (n + 7) & ~7ull; }
+
+template <class T>
+void put(std::ofstream& f, const T* p, const uint64_t n, const uint64_t padded_bytes) {
+    static const char zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (n) f.write((const char*)p, (std::streamsize)(n * sizeof(T)));
+    f.write(zeros, (std::streamsize)(padded_bytes - n * sizeof(T)));
+}
+
+bool is_directory(const std::string& path) {
+    struct stat st;
+    return stat(path.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
+}
+
+// what a guarded entry throws for a bad argument (KSP_E_ARG instead of KSP_E_IO)
+struct ArgError : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+
+template <class Fn>
+int guarded(const char* who, Fn fn) {
+    try {
+        return fn();
+    } catch (const std::bad_alloc&) {
+        ksp::set_error(std::string(who) + ": out of host memory");
+        return KSP_E_LIMIT;
+    } catch (const ArgError& e) {
+        ksp::set_error(std::string(who) + ": " + e.what());
+        return KSP_E_ARG;
+    } catch (const std::exception& e) {
+        ksp::set_error(std::string(who) + ": " + e.what());
+        return KSP_E_IO;
+    }
+}
+
+// one side of a query: a directory (its kind by kSize) or a pack file, whose kSize must be the caller's when that is not 0
+void load_side(const std::string& path, const int kSize, const int threads, ksp::SketchSet& set) {
+    if (is_directory(path)) { ksp::sketch_set_from_dir(path, kSize, threads, set); return; }
+    ksp::read_sketch_pack(path, set);
+    if (kSize != 0 && set.ksize != kSize)
+        throw ArgError(path + " was packed with kSize " + std::to_string(set.ksize) + ", not " + std::to_string(kSize));
+}
+
+}  // namespace
+
+void ksp::sketch_set_from_dir(const std::string& dir, const int kSize, const int threads, SketchSet& out) {
+    SketchNames names;
+    std::vector<SketchSource> src;
+    if (kSize > 0) load_sig_dir(dir, kSize, threads, names, src);
+    else load_bin_dir(dir, threads, names, src);
+    SketchSet set;
+    set.ksize = kSize;
+    const size_t G = names.size();
+    set.present.assign(G, 0);
+    set.kmers.assign(G, 0);
+    for (auto& n : names) set.names.push_back(n.second);   // (ids are 1, 2, ... in this order)
+    set.offsets.push_back(0);
+    for (const SketchSource& s : src) {   // ascending by id
+        set.present[s.id - 1] = 1;
+        set.kmers[s.id - 1] = s.kmers;
+        set.keys.insert(set.keys.end(), s.run.begin(), s.run.end());
+        set.offsets.push_back(set.keys.size());
+    }
+    out = std::move(set);
+}
+
+void ksp::write_sketch_pack(const std::string& out_path, const SketchSet& set) {
+    const uint64_t G = set.names.size(), S = set.offsets.size() - 1, K = set.keys.size();
+    std::vector<uint64_t> name_off(G + 1, 0);
+    std::string text;
+    for (uint64_t g = 0; g < G; ++g) {
+        text += set.names[g];
+        name_off[g + 1] = text.size();
+    }
+    const uint64_t B = text.size();
+    const uint32_t version = kVersion;
+    const int32_t ksize = set.ksize;
+    std::ofstream f;
+    PartialFiles files;
+    files.open(out_path, f);
+    f.write(kMagic, 8);
+    f.write((const char*)&version, 4);
+    f.write((const char*)&ksize, 4);
+    for (const uint64_t v : {G, S, K, B}) f.write((const char*)&v, 8);
+    put(f, set.kmers.data(), G, pad8(4 * G));
+    put(f, set.present.data(), G, pad8(G));
+    put(f, set.offsets.data(), S + 1, 8 * (S + 1));
+    f.write((const char*)&G, 8);
+    put(f, name_off.data(), G + 1, 8 * (G + 1));
+    put(f, text.data(), B, pad8(B));
+    put(f, set.keys.data(), K, 8 * K);
+    files.commit();
+}
+
+void ksp::read_sketch_pack(const std::string& path, SketchSet& out) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("cannot open " + path);
+    f.seekg(0, std::ios::end);
+    const uint64_t size = (uint64_t)f.tellg();
+    f.seekg(0);
+    const auto bad = [&](const std::string& what) { return std::runtime_error(path + ": " + what); };
+    char head[kHeaderBytes];
+    if (size < kHeaderBytes || !f.read(head, kHeaderBytes)) throw bad("shorter than a pack file's header");
+    if (std::memcmp(head, kMagic, 8) != 0) throw bad("not a pack file (wrong magic)");
+    uint32_t version;
+    int32_t ksize;
+    uint64_t G, S, K, B;
+    std::memcpy(&version, head + 8, 4);
+    std::memcpy(&ksize, head + 12, 4);
+    std::memcpy(&G, head + 16, 8);
+    std::memcpy(&S, head + 24, 8);
+    std::memcpy(&K, head + 32, 8);
+    std::memcpy(&B, head + 40, 8);
+    if (version != kVersion) throw bad("pack version " + std::to_string(version) + ", this reader knows " + std::to_string(kVersion));
+    // every count is below the file's size before anything is multiplied or allocated
+    if (G > size || S > size || K > size || B > size || S > G) throw bad("counts in the header exceed the file");
+    const uint64_t want = kHeaderBytes + pad8(4 * G) + pad8(G) + 8 * (S + 1) + 8 + 8 * (G + 1) + pad8(B) + 8 * K;
+    if (size != want) throw bad("is " + std::to_string(size) + " bytes, its header implies " + std::to_string(want));
+    SketchSet set;
+    set.ksize = ksize;
+    std::vector<char> skip(8);
+    const auto get = [&](void* p, const uint64_t bytes, const uint64_t padded) {
+        if (bytes) f.read((char*)p, (std::streamsize)bytes);
+        if (padded > bytes) f.read(skip.data(), (std::streamsize)(padded - bytes));
+        if (!f) throw bad("read error");
+    };
+    set.kmers.resize(G);
+    set.present.resize(G);
+    set.offsets.resize(S + 1);
+    get(set.kmers.data(), 4 * G, pad8(4 * G));
+    get(set.present.data(), G, pad8(G));
+    get(set.offsets.data(), 8 * (S + 1), 8 * (S + 1));
+    uint64_t n_present = 0;
+    for (const uint8_t p : set.present) {
+        if (p > 1) throw bad("a presence byte is not 0 or 1");
+        n_present += p;
+    }
+    if (n_present != S) throw bad(std::to_string(n_present) + " groups are marked as having a sketch, the header says " + std::to_string(S));
+    if (set.offsets[0] != 0) throw bad("the offsets do not start at 0");
+    for (uint64_t s = 0; s < S; ++s)
+        if (set.offsets[s + 1] < set.offsets[s]) throw bad("the offsets decrease at source " + std::to_string(s));
+    if (set.offsets[S] != K) throw bad("the offsets end at " + std::to_string(set.offsets[S]) + ", the header has " + std::to_string(K) + " keys");
+    uint64_t name_count = 0;
+    get(&name_count, 8, 8);
+    if (name_count != G) throw bad("the name count " + std::to_string(name_count) + " disagrees with the header's " + std::to_string(G));
+    std::vector<uint64_t> name_off(G + 1);
+    std::string text(B, '\0');
+    get(name_off.data(), 8 * (G + 1), 8 * (G + 1));
+    get(&text[0], B, pad8(B));
+    if (name_off[0] != 0) throw bad("the name offsets do not start at 0");
+    for (uint64_t g = 0; g < G; ++g)
+        if (name_off[g + 1] < name_off[g] || name_off[g + 1] > B) throw bad("the name offsets decrease or leave the text at name " + std::to_string(g));
+    if (name_off[G] != B) throw bad("the name offsets do not end at the text's end");
+    for (uint64_t g = 0; g < G; ++g) set.names.emplace_back(text, name_off[g], name_off[g + 1] - name_off[g]);
+    set.keys.resize(K);
+    get(set.keys.data(), 8 * K, 8 * K);
+    for (uint64_t s = 0; s < S; ++s)
+        for (uint64_t i = set.offsets[s] + 1; i < set.offsets[s + 1]; ++i)
+            if (set.keys[i] <= set.keys[i - 1]) throw bad("the run of source " + std::to_string(s) + " is not strictly ascending");
+    out = std::move(set);
+}
+
+extern "C" int kspider_pack(const char* dir, int kSize, const char* out_path, int user_threads) {
+    const char* who = "kspider_pack";
+    if (!dir || !out_path || !*out_path) { ksp::set_error(std::string(who) + ": dir or out_path is NULL or empty"); return KSP_E_ARG; }
+    if (kSize < 0) { ksp::set_error(std::string(who) + ": kSize is the signatures' ksize, or 0 for .bin sketches"); return KSP_E_ARG; }
+    return guarded(who, [&]() {
+        ksp::SketchSet set;
+        ksp::sketch_set_from_dir(dir, kSize, user_threads, set);
+        ksp::write_sketch_pack(out_path, set);
+        return (int)KSP_OK;
+    });
+}
+
+extern "C" int ksp_pack_info(const char* path, uint64_t out[5]) {
+    const char* who = "ksp_pack_info";
+    if (!path || !out) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+    return guarded(who, [&]() {
+        ksp::SketchSet set;
+        ksp::read_sketch_pack(path, set);
+        uint64_t text = 0;
+        for (const std::string& n : set.names) text += n.size();
+        out[0] = (uint64_t)(int64_t)set.ksize;
+        out[1] = set.names.size();
+        out[2] = set.offsets.size() - 1;
+        out[3] = set.keys.size();
+        out[4] = text;
+        return (int)KSP_OK;
+    });
+}
+
+extern "C" int ksp_pack_load(const char* path, uint32_t* kmers, uint8_t* present, uint64_t* offsets, uint64_t* keys, uint64_t* name_offsets, char* names) {
+    const char* who = "ksp_pack_load";
+    if (!path || !kmers || !present || !offsets || !keys || !name_offsets || !names) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+    return guarded(who, [&]() {
+        ksp::SketchSet set;
+        ksp::read_sketch_pack(path, set);
+        const size_t G = set.names.size();
+        if (G) std::memcpy(kmers, set.kmers.data(), 4 * G);
+        if (G) std::memcpy(present, set.present.data(), G);
+        std::memcpy(offsets, set.offsets.data(), 8 * set.offsets.size());
+        if (!set.keys.empty()) std::memcpy(keys, set.keys.data(), 8 * set.keys.size());
+        uint64_t at = 0;
+        for (size_t g = 0; g < G; ++g) {
+            name_offsets[g] = at;
+            std::memcpy(names + at, set.names[g].data(), set.names[g].size());
+            at += set.names[g].size();
+        }
+        name_offsets[G] = at;
+        return (int)KSP_OK;
+    });
+}
+
+extern "C" int kspider_query(const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, int mode) {
+    const char* who = "kspider_query";
+    if (!db || !queries || !out_prefix || !*out_prefix) { ksp::set_error(std::string(who) + ": db, queries and out_prefix are required"); return KSP_E_ARG; }
+    if (kSize < 0) { ksp::set_error(std::string(who) + ": kSize is the signatures' ksize, or 0 for .bin sketches"); return KSP_E_ARG; }
+    if (mode != KSP_QUERY_CROSS && mode != KSP_QUERY_CROSS_AND_SELF) {
+        ksp::set_error(std::string(who) + ": mode is KSP_QUERY_CROSS (0) or KSP_QUERY_CROSS_AND_SELF (1)");
+        return KSP_E_ARG;
+    }
+    return guarded(who, [&]() {
+        const int threads = user_threads < 1 ? 1 : user_threads;
+        const std::string prefix = out_prefix;
+        ksp::SketchSet side[2];
+        load_side(db, kSize, threads, side[0]);
+        load_side(queries, kSize, threads, side[1]);
+        const uint64_t G0 = side[0].names.size(), G = G0 + side[1].names.size();
+        if (G > 0xFFFFFFFEull) throw std::runtime_error("more than 2^32 - 2 groups");
+        // the sources of both sides by their ids in the union: database 1 .. N, queries N + 1 .. N + Q
+        std::vector<uint32_t> id_of[2];
+        ksp::IndexData ix;
+        std::unordered_map<uint32_t, uint32_t> kmer_count;
+        for (int s = 0; s < 2; ++s)
+            for (uint64_t g = 0; g < side[s].names.size(); ++g) {
+                if (!side[s].present[g]) continue;
+                const uint32_t id = (uint32_t)((s ? G0 : 0) + g + 1);
+                id_of[s].push_back(id);
+                ix.kmer_slots.emplace_back(id, side[s].kmers[g]);
+                kmer_count[id] = side[s].kmers[g];
+            }
+        if (id_of[0].empty() || id_of[1].empty()) throw ArgError(id_of[0].empty() ? "the database has no sketch" : "there is no query sketch");
+        ksp_edge* edges = nullptr;
+        uint64_t n_edges = 0;
+        ksp_query_stats st;
+        const char* dv = std::getenv("KSPIDER_DEVICE");
+        const int rc = ksp_query_host(side[0].keys.data(), side[0].offsets.data(), (uint32_t)id_of[0].size(), side[1].keys.data(), side[1].offsets.data(),
+                                      (uint32_t)id_of[1].size(), mode, dv ? std::atoi(dv) : 0, &edges, &n_edges, &st);
+        if (rc != KSP_OK) return rc;
+        std::vector<ksp::EdgeRow> rows;
+        rows.reserve(n_edges);
+        const uint32_t n_db = (uint32_t)id_of[0].size();
+        for (uint64_t i = 0; i < n_edges; ++i) {   // ids ascend with the source numbers, so the rows stay sorted
+            const ksp_edge& e = edges[i];
+            rows.push_back(ksp::EdgeRow{e.source_1 < n_db ? id_of[0][e.source_1] : id_of[1][e.source_1 - n_db], id_of[1][e.source_2 - n_db], e.shared});
+        }
+        ksp_free(edges);
+        // the files only now: a refused or failed query leaves none
+        {
+            std::ofstream f;
+            ksp::PartialFiles files;
+            files.open(prefix + ".namesMap", f);
+            f << G << "\n";
+            for (int s = 0; s < 2; ++s)
+                for (uint64_t g = 0; g < side[s].names.size(); ++g) f << (s ? G0 : 0) + g + 1 << " " << side[s].names[g] << "\n";
+            files.commit();
+        }
+        ksp::write_seq_to_kmers(prefix, ix);
+        ksp::write_pairwise_tsv(prefix, rows, kmer_count, threads);
+        if (std::getenv("KSPIDER_VERBOSE"))
+            std::cout << "kspider_amd: query: " << st.n_q << " queries against " << st.n_db << " database sources, " << st.passes << " passes, " << n_edges
+                      << " rows; table " << st.ms_table << " ms, probe " << st.ms_probe << " ms" << std::endl;
+        return (int)KSP_OK;
+    });
+}

@@ -59,6 +59,13 @@ TSV_CHUNK_ROWS = 256
 TSV_ROW_MIN = 12
 TSV_ROW_MAX = 79
 
+#: query mode (include/kspider_amd.h KSP_QUERY_*): the modes, the largest tile and touched list, the default short/long switch
+QUERY_CROSS, QUERY_CROSS_AND_SELF = 0, 1
+QUERY_TILE_MAX = 2048
+QUERY_LIST_MAX = 512
+QUERY_LONG_RUN = 2048
+QUERY_DIR_BITS_MAX = 24
+
 #: ksp_engine_lists_path / Engine.lists_path
 LISTS_NONE, LISTS_KEYED, LISTS_COMPACTED, LISTS_SORTED, LISTS_FUSED = 0, 1, 2, 3, 4
 
@@ -90,6 +97,7 @@ ABI_SYMBOLS = [
     "ksp_edges_cluster_report", "ksp_cluster_report_valued", "kspider_cluster_report", "kspider_pairwise_and_cluster_report",
     "ksp_edges_upgma", "ksp_upgma_valued", "ksp_upgma_before", "kspider_upgma", "kspider_pairwise_and_upgma", "kspider_cluster_from_upgma",
     "ksp_edges_tsv",
+    "ksp_query_device", "ksp_query_host", "ksp_query_directory", "kspider_pack", "ksp_pack_info", "ksp_pack_load", "kspider_query",
 ]
 
 
@@ -109,6 +117,21 @@ class Stats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class QueryStats(ctypes.Structure):
+    """ksp_query_stats (include/kspider_amd.h)."""
+    _fields_ = [
+        ("n_db", ctypes.c_uint64), ("n_q", ctypes.c_uint64), ("db_entries", ctypes.c_uint64), ("q_entries", ctypes.c_uint64),
+        ("table_keys", ctypes.c_uint64), ("table_holders", ctypes.c_uint64), ("passes", ctypes.c_uint64),
+        ("short_sources", ctypes.c_uint64), ("long_sources", ctypes.c_uint64), ("list_overflows", ctypes.c_uint64),
+        ("edges", ctypes.c_uint64), ("long_run", ctypes.c_uint64),
+        ("ms_table", ctypes.c_float), ("ms_probe", ctypes.c_float), ("ms_sort", ctypes.c_float),
+        ("tile", ctypes.c_uint32), ("list_capacity", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 class KspError(RuntimeError):
@@ -282,6 +305,15 @@ def lib():
         L.ksp_debug_tsv_records.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.ksp_debug_tsv_times.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        L.ksp_query_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                       ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_query_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_query_directory.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+        L.kspider_pack.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        L.ksp_pack_info.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
+        L.ksp_pack_load.argtypes = [ctypes.c_char_p] + [ctypes.c_void_p] * 6
+        L.kspider_query.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]
         _lib = L
     return _lib
 
@@ -880,6 +912,79 @@ def tsv_times(n_nodes: int, d_edges_ptr: int, n_edges: int, d_kmer_counts_ptr: i
     _check(lib().ksp_debug_tsv_times(device, n_nodes, d_edges_ptr or None, n_edges, d_kmer_counts_ptr or None, d_ids_ptr or None, int(which), int(reps),
                                      int(threads), ms.ctypes.data))
     return ms
+
+
+def _ptr(a):
+    """Address of a numpy array, or None for None (the C side's NULL)."""
+    return None if a is None else a.ctypes.data
+
+
+def query_host(db_keys, db_offsets, q_keys, q_offsets, mode: int = QUERY_CROSS, device: int = 0):
+    """Host sketches of a database and of queries -> (edges sorted by (source_1, source_2), stats).  Database sources are numbered
+    0 .. n_db - 1, queries n_db .. n_db + n_q - 1; mode QUERY_CROSS: database x query pairs, QUERY_CROSS_AND_SELF: also query x
+    query.  None stands for a NULL pointer (refused by the C side)."""
+    def arr(a):
+        return None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
+    dk, do, qk, qo = arr(db_keys), arr(db_offsets), arr(q_keys), arr(q_offsets)
+    out = ctypes.c_void_p()
+    ne = ctypes.c_uint64(0)
+    st = QueryStats()
+    _check(lib().ksp_query_host(_ptr(dk), _ptr(do), 0 if do is None else max(do.size - 1, 0), _ptr(qk), _ptr(qo), 0 if qo is None else max(qo.size - 1, 0),
+                                int(mode), int(device), ctypes.byref(out), ctypes.byref(ne), ctypes.byref(st)))
+    try:
+        buf = (ctypes.c_char * (ne.value * EDGE_DTYPE.itemsize)).from_address(out.value) if ne.value else b""
+        edges = np.frombuffer(buf, dtype=EDGE_DTYPE).copy()
+    finally:
+        lib().ksp_free(out)
+    return edges, st.as_dict()
+
+
+def query_device(d_db_keys_ptr: int, db_offsets, d_q_keys_ptr: int, q_offsets, d_edges_ptr: int, capacity: int, mode: int = QUERY_CROSS, device: int = 0) -> tuple:
+    """ksp_query_device: keys in DEVICE memory, offsets on the host, edges into d_edges (room for `capacity`; 0 / 0: the size query).
+    -> (rc, n_edges, stats): rc is KSP_OK or KSP_E_OVERFLOW (n_edges is then the required size); anything else raises."""
+    do = None if db_offsets is None else np.ascontiguousarray(db_offsets, dtype=np.uint64)
+    qo = None if q_offsets is None else np.ascontiguousarray(q_offsets, dtype=np.uint64)
+    ne = ctypes.c_uint64(0)
+    st = QueryStats()
+    rc = lib().ksp_query_device(int(device), d_db_keys_ptr or None, _ptr(do), 0 if do is None else max(do.size - 1, 0), d_q_keys_ptr or None, _ptr(qo),
+                                0 if qo is None else max(qo.size - 1, 0), int(mode), d_edges_ptr or None, int(capacity), ctypes.byref(ne), ctypes.byref(st))
+    if rc not in (KSP_OK, KSP_E_OVERFLOW):
+        _check(rc)
+    return rc, ne.value, st.as_dict()
+
+
+def query_directory(max_key: int, n_keys: int) -> tuple:
+    """(bits, shift) of the first level of a query table of n_keys distinct keys, the largest max_key (host only)."""
+    bits, shift = ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib().ksp_query_directory(int(max_key), int(n_keys), ctypes.byref(bits), ctypes.byref(shift)))
+    return bits.value, shift.value
+
+
+def pack(sketch_dir: str, kSize: int, out_path: str, user_threads: int = 1) -> None:
+    """A directory of .sig / .gz files (kSize > 0) or .bin files (kSize = 0) -> one pack file (kspider_pack)."""
+    _check(lib().kspider_pack(os.fsencode(sketch_dir), int(kSize), os.fsencode(out_path), int(user_threads)))
+
+
+def pack_read(path: str) -> dict:
+    """A pack file, read whole and checked (ksp_pack_info + ksp_pack_load; host only): ksize, names (one per group), present and
+    kmers per group, offsets and keys of the groups that have a sketch."""
+    info = np.zeros(5, dtype=np.uint64)
+    _check(lib().ksp_pack_info(os.fsencode(path), info.ctypes.data))
+    ksize, G, S, K, B = int(np.int64(info[0])), int(info[1]), int(info[2]), int(info[3]), int(info[4])
+    kmers, present = np.zeros(G + 1, dtype=np.uint32), np.zeros(G + 1, dtype=np.uint8)
+    offsets, keys, name_off = np.zeros(S + 1, dtype=np.uint64), np.zeros(K + 1, dtype=np.uint64), np.zeros(G + 1, dtype=np.uint64)
+    text = np.zeros(B + 1, dtype=np.uint8)
+    _check(lib().ksp_pack_load(os.fsencode(path), kmers.ctypes.data, present.ctypes.data, offsets.ctypes.data, keys.ctypes.data, name_off.ctypes.data,
+                               text.ctypes.data))
+    blob = text[:B].tobytes()
+    names = [os.fsdecode(blob[int(name_off[g]):int(name_off[g + 1])]) for g in range(G)]
+    return {"ksize": ksize, "names": names, "present": present[:G].copy(), "kmers": kmers[:G].copy(), "offsets": offsets, "keys": keys[:K].copy()}
+
+
+def query(db: str, queries: str, kSize: int, out_prefix: str, user_threads: int = 1, mode: int = QUERY_CROSS) -> None:
+    """New sketches against a database (kspider_query): db and queries are each a pack file or a directory; writes OUT.namesMap,
+    OUT_kSpider_seqToKmersNo.tsv and OUT_kSpider_pairwise.tsv with only the rows of the mode."""
+    _check(lib().kspider_query(os.fsencode(db), os.fsencode(queries), int(kSize), os.fsencode(out_prefix) if out_prefix else None, int(user_threads), int(mode)))
 
 
 def cluster_from_tree(index_prefix: str, dist_type: str = "max_cont", cutoff: float = 0.0) -> None:
