@@ -884,6 +884,73 @@ int ksp_pack_info(const char* path, uint64_t out[5]);
 int ksp_pack_load(const char* path, uint32_t* kmers, uint8_t* present, uint64_t* offsets, uint64_t* keys, uint64_t* name_offsets, char* names);
 int kspider_query(const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, int mode);
 
+/* ---- gather: what is each query made of?  The greedy minimum-set-cover by database sources (csrc/gather.hip) ----
+ * Database sources are 0 .. n_db - 1, queries 0 .. n_q - 1, each a strictly ascending run of 64-bit hashes as in ksp_query_*.
+ * Every query q with hash set Q is treated on its own:  R = Q, rank = 0;  loop: u(s) = |S_s ∩ R| for every source s; s* = the
+ * source with the largest u, among equals the smallest s; stop when u(s*) < min_hashes, or when max_matches is not 0 and rank has
+ * reached it; otherwise rank += 1, R = R \ S_s*, and the row is (q, rank, s*, overlap = |S_s* ∩ Q|, unique = u(s*),
+ * remaining = |R|).  Rows are ordered by (query, rank); everything is an integer and the tie rule is total, so the table is the
+ * same under every switch and schedule.
+ * ksp_gather_device: the caller keeps the database in HBM across calls.  d_db_keys / d_q_keys: DEVICE memory, the runs back to
+ *   back; h_db_offsets / h_q_offsets: HOST memory, n + 1 element offsets.  The rows go to d_rows (device, room for `capacity`);
+ *   *n_rows = the rows found.  More than `capacity`: KSP_E_OVERFLOW, *n_rows is the required size, the first `capacity` rows were
+ *   written and nothing past them; d_rows NULL with capacity 0 is the size query.  KSP_E_ARG, before a device is chosen and before
+ *   anything is allocated: a NULL pointer (stats may be NULL), d_rows NULL with a capacity, n_db = 0 or n_q = 0, min_hashes = 0,
+ *   offsets that do not start at 0 or decrease, a switch of the environment that is not a number in its range.  KSP_E_LIMIT:
+ *   n_db + n_q > 2^32 - 2, a query tile of 2^31 entries or more, 2^32 - 1 or more candidates or matched hashes of candidates in
+ *   one query tile, memory that does not fit the device's free memory (the message says what was asked: beside query mode's table,
+ *   40 bytes per candidate — a (source, query) pair with overlap >= min_hashes —, 4 per matched hash of a candidate, a bit per
+ *   query hash, 48 per possible row).  The queries are taken in tiles as in query mode: one pass over the database per tile, and a
+ *   second over the sources that have a candidate.  Read on every call: $KSP_QUERY_TILE, $KSP_QUERY_LONG_RUN, $KSP_QUERY_LIST as in
+ *   query mode; $KSP_GATHER_LONG_SEG (a candidate of that many matched hashes or more is counted by a workgroup instead of a wave;
+ *   1 .. 2^32 - 1, default KSP_GATHER_LONG_SEG); $KSP_GATHER_TAIL (0: rounds in batches to the end; 1, the default: one workgroup
+ *   runs the remaining rounds once at most $KSP_GATHER_TAIL_CANDS candidates are live, 0 .. KSP_GATHER_TAIL_CANDS_MAX, default
+ *   KSP_GATHER_TAIL_CANDS); $KSP_GATHER_MAX_WORKGROUPS (caps the grids; tests).  The rows are the same under each.  Rounds are
+ *   launched KSP_GATHER_BATCH at a time; the host reads the device's count of live queries once per batch.
+ * ksp_gather_host: the same for HOST arrays; the rows come back in *rows (ksp_free).  A device that is not there: KSP_E_HIP,
+ *   "ksp_gather_host: no such device".
+ * kspider_gather: db and queries are each a pack file or a directory, exactly as kspider_query loads them; out_prefix is required.
+ *   Writes OUT_kSpider_gather.tsv: a header line, then per row the query's name, rank, the match's name, overlap, unique,
+ *   f_orig_query = overlap / |Q|, f_unique_to_query = unique / |Q|, f_match = overlap / |S| (single precision, printed as
+ *   ksp_format_float prints) and remaining.  The file is written through OUT.partial only after the call has succeeded: a refused
+ *   or failed call writes none.  KSP_E_ARG: a NULL or empty argument, kSize < 0, min_hashes = 0, a pack of another kSize, a side
+ *   without a sketch.  Device = $KSPIDER_DEVICE (default 0).                                                                      */
+#define KSP_GATHER_BATCH 16u
+#define KSP_GATHER_LONG_SEG 1024u
+#define KSP_GATHER_TAIL_CANDS 256u
+#define KSP_GATHER_TAIL_CANDS_MAX 1048576u
+typedef struct ksp_gather_row {
+    uint32_t query, rank, source;
+    uint32_t overlap, unique, remaining;
+} ksp_gather_row;   /* 24 bytes */
+typedef struct ksp_gather_stats {
+    uint64_t n_db, n_q;
+    uint64_t db_entries, q_entries;
+    uint64_t table_keys, table_holders;   /* as in ksp_query_stats, summed over the tiles                    */
+    uint64_t passes;           /* query tiles swept: passes over the database                                */
+    uint64_t candidates;       /* (source, query) pairs with overlap >= min_hashes                            */
+    uint64_t dropped;          /* pairs with 0 < overlap < min_hashes: dropped before the rounds             */
+    uint64_t fell_below;       /* candidates counted below min_hashes in a round: dead from then on          */
+    uint64_t slots;            /* matched hashes of the candidates: u32 words of segments                    */
+    uint64_t rounds;           /* rounds with a live query, summed over the tiles                            */
+    uint64_t batches;          /* batches of KSP_GATHER_BATCH rounds launched = reads of the live count      */
+    uint64_t tail_rounds;      /* of `rounds`, those the one-workgroup tail ran                              */
+    uint64_t live_at_tail;     /* live candidates handed to the tail                                         */
+    uint64_t rows;
+    uint64_t long_seg;         /* the switches as the call read them                                         */
+    uint64_t tail_cands;       /* (0 also when $KSP_GATHER_TAIL is 0)                                        */
+    float ms_table, ms_candidates, ms_fill, ms_rounds;   /* HIP-event times, summed over the tiles           */
+    uint32_t tile, min_hashes, max_matches, reserved;
+} ksp_gather_stats;   /* 176 bytes */
+int ksp_gather_device(int device, const uint64_t* d_db_keys, const uint64_t* h_db_offsets, uint32_t n_db, const uint64_t* d_q_keys,
+                      const uint64_t* h_q_offsets, uint32_t n_q, uint32_t min_hashes, uint32_t max_matches, ksp_gather_row* d_rows,
+                      uint64_t capacity, uint64_t* n_rows, ksp_gather_stats* stats);
+int ksp_gather_host(const uint64_t* db_keys, const uint64_t* db_offsets, uint32_t n_db, const uint64_t* q_keys, const uint64_t* q_offsets,
+                    uint32_t n_q, uint32_t min_hashes, uint32_t max_matches, int device, ksp_gather_row** rows, uint64_t* n_rows,
+                    ksp_gather_stats* stats);
+int kspider_gather(const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, uint32_t min_hashes,
+                   uint32_t max_matches);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

@@ -1,0 +1,757 @@
+// Gather: the greedy minimum-set-cover of every query by database sources — take the source that covers most of
+// what is left of the query, remove its hashes, ask again — on the database that stays in HBM.  Exact integers, a total tie
+// rule (the smaller source), so one well-defined table whatever the scheduling.
+//
+// Per tile of queries (the tiling and the table are query mode's: query_table.hip.h):
+//   candidates  one sweep of the database against the tile's table counts, per source, the hashes it shares with every query
+//               (u32 counters in LDS, a wave per short source, a workgroup per long one).  A (source, query) pair whose overlap
+//               reaches min_hashes is a candidate: (query << 32 | source, overlap) appended through one returning add per
+//               wave; the others can never win and are only counted.  Sorted by that word, a candidate's index orders the
+//               sources within its query; an exclusive scan of the overlaps gives every candidate a segment.
+//   segments    a second sweep, over the sources that have a candidate only, counts again and then turns the counter of a
+//               touched query into the cursor of its segment (the candidate is found by binary search in the sorted words; a
+//               pair below min_hashes gets kNone).  A second walk over the source's hashes writes, for every hit, the holder
+//               slot h (the index into the table's tq[], unique per (key, query) membership) at the cursor's returning add.
+//               No second LDS array: the counters ARE the segment bases, and the LDS budget stays query mode's.
+//   alive       one bit per holder slot, all set.  Slots of different queries share words: clearing is an atomic AND.
+//   a round     for all queries of the tile at once.  count: a wave per live candidate with a short segment, a workgroup per
+//               long one, counts the alive slots u of its segment by ballots; u < min_hashes: dead for good (counts only fall);
+//               otherwise it offers (u << 32) | ~index to a 64-bit atomicMax per query.  take: a wave per query; the winner's
+//               slots are cleared, the row appended, remaining lowered, the offer reset; a query without an offer, or at
+//               max_matches, is finished.
+//   batches     KSP_GATHER_BATCH rounds are launched back to back; the kernels return at once when the device's counter of live
+//               queries is 0; the host reads that counter once per batch, after the live lists were compacted.
+//   tail        at KSP_GATHER_TAIL_CANDS live candidates or fewer ONE workgroup of 1 024 threads runs the remaining rounds with
+//               __syncthreads() between count and take (k_derep_tail's pattern); KSP_GATHER_TAIL=0: batches to the end.
+// Every loop is bounded by a size the host computed; no workgroup waits on another; stores are plain vector stores.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/kspider_amd.h"
+#include "device_call.h"
+#include "engine_internal.h"
+#include "query_table.hip.h"
+
+namespace {
+
+constexpr u32 kTileMax = KSP_QUERY_TILE_MAX;
+constexpr u32 kListMax = KSP_QUERY_LIST_MAX;
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kTailThreads = 1024;
+constexpr u32 kNone = 0xFFFFFFFFu;
+// the sweeps hold what query mode's probe holds: 4 x (8 + 2) KiB and a few words per workgroup
+static_assert(2 * (kWaves * (kTileMax + kListMax) * 4 + 64) <= 160 * 1024, "two workgroups per CU");
+static_assert(kWaves * (kTileMax + kListMax) * 4 + 64 <= 64 * 1024, "static LDS of one workgroup");
+
+// the device's words of a tile (unsigned long long each)
+enum : int { kLiveQ = 0, kRounds, kRows, kGo, kFell, kKept0, kKept1, kCands, kDropped, kFill0, kFill1, kCtrlWords };
+
+__device__ inline u32 load_u32(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ inline unsigned long long load_u64(const unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// ---------------------------------------------------------------------------------------------------------------- the sweeps
+struct GSweep {
+    const u64 *db_keys, *db_off;
+    const u32* list;   // the sources of this kernel
+    u32 n_list;
+    u32 list_cap;      // touched-list capacity, 1 .. kListMax
+    u32 min_hashes;
+    unsigned long long* ctrl;
+    // the counting sweep: candidates out
+    u64* cand_key;     // (query inside the tile << 32) | source
+    u32* cand_ovl;
+    u64 cand_cap;
+    u32* fill_list;    // the sources of this kernel that have a candidate; its counter: ctrl[fill_word]
+    int fill_word;
+    // the filling sweep: the sorted candidates in, holder slots out
+    const u64* ckey;
+    const u64* cbase;  // n_cand + 1
+    u32 n_cand;
+    u32* seg;
+    u32 n_slots;
+};
+
+// cnt[t] += the keys of the run [o0, o1) that query t of the tile holds; a query whose counter left 0 goes to the touched list
+template <bool kWave>
+__device__ inline void gather_count_run(const QTable& T, const u64* __restrict__ keys, const u64 o0, const u64 o1, u32* cnt, u32* list, u32* n, const u32 list_cap,
+                                        const u32 t) {
+    constexpr u32 kLanes = kWave ? 64 : kThreads;
+    for (u64 e = o0 + t; e < o1; e += (u64)kLanes * kProbeKeys) {
+        u64 k[kProbeKeys];
+        bool live[kProbeKeys];
+        u32 at[kProbeKeys];
+#pragma unroll
+        for (int x = 0; x < kProbeKeys; ++x) {
+            const u64 ex = e + (u64)x * kLanes;
+            live[x] = ex < o1;
+            k[x] = live[x] ? keys[ex] : 0;
+        }
+        query_lookup(T, k, live, at);
+#pragma unroll
+        for (int x = 0; x < kProbeKeys; ++x) {
+            if (!live[x]) continue;
+            const u32 h1 = T.toff[at[x] + 1];
+            for (u32 h = T.toff[at[x]]; h < h1; ++h) {
+                const u32 tag = T.tq[h];
+                if (tag >= T.nq) continue;   // (a tag is below nq by construction)
+                if (atomicAdd(&cnt[tag], 1u) == 0) {
+                    const u32 pos = atomicAdd(n, 1u);
+                    if (pos < list_cap) list[pos] = tag;
+                }
+            }
+        }
+    }
+}
+
+// the index of `word` in the ascending ckey[0 .. n), or kNone
+__device__ inline u32 gather_find(const u64* __restrict__ ckey, const u32 n, const u64 word) {
+    u32 lo = 0, hi = n;
+    while (lo < hi) {
+        const u32 mid = lo + (hi - lo) / 2;
+        if (ckey[mid] < word) lo = mid + 1; else hi = mid;
+    }
+    return lo < n && ckey[lo] == word ? lo : kNone;
+}
+
+// One group per source: a wave (kWave, four groups per workgroup) or the whole workgroup.  kFill false: the candidates of the
+// source; kFill true: the holder slots of its candidates into their segments.
+template <bool kWave, bool kFill>
+__global__ __launch_bounds__(kThreads) void k_gather_sweep(const QTable T, const GSweep P) {
+    constexpr u32 kGroups = kWave ? kWaves : 1;
+    constexpr u32 kLanes = kWave ? 64 : kThreads;
+    __shared__ u32 s_cnt[kGroups][kTileMax];
+    __shared__ u32 s_list[kGroups][kListMax];
+    __shared__ u32 s_n[kGroups];
+    __shared__ u32 s_any[kGroups];
+    const u32 g = kWave ? threadIdx.x >> 6 : 0, t = kWave ? threadIdx.x & 63 : threadIdx.x, lane = threadIdx.x & 63;
+    u32* const cnt = s_cnt[g];
+    u32* const list = s_list[g];
+    u32* const n = &s_n[g];
+    for (u32 j = t; j < T.nq; j += kLanes) cnt[j] = 0;
+    if (t == 0) { *n = 0; s_any[g] = 0; }
+    query_group_sync<kWave>();
+    const u64 first = kWave ? (u64)blockIdx.x * kWaves + g : blockIdx.x, stride = kWave ? (u64)gridDim.x * kWaves : gridDim.x;
+    for (u64 i = first; i < P.n_list; i += stride) {
+        const u32 p = P.list[i];
+        const u64 o0 = P.db_off[p], o1 = P.db_off[p + 1];
+        gather_count_run<kWave>(T, P.db_keys, o0, o1, cnt, list, n, P.list_cap, t);
+        query_group_sync<kWave>();
+        const u32 touched = *n;
+        query_group_sync<kWave>();
+        if (t == 0) *n = 0;
+        const bool over = touched > P.list_cap;   // the list lost entries: one scan over all counters replaces it
+        const u32 count = over ? T.nq : touched;
+        if (!kFill) {
+            for (u32 base = 0; base < count; base += kLanes) {   // (the same trips for every lane of the group)
+                const u32 j = base + t;
+                u32 tag = 0, c = 0;
+                if (j < count) {
+                    tag = over ? j : list[j];
+                    c = cnt[tag];
+                    if (c) cnt[tag] = 0;
+                }
+                const bool cand = c >= P.min_hashes;   // (min_hashes >= 1: never for c = 0)
+                const unsigned long long have = __ballot(cand), low = __ballot(c != 0 && !cand);
+                if (low && lane == (u32)__ffsll((long long)low) - 1) atomicAdd(&P.ctrl[kDropped], (unsigned long long)__popcll(low));
+                if (!have) continue;   // (the whole wave)
+                unsigned long long at = 0;
+                const int src = __ffsll((long long)have) - 1;
+                if (lane == (u32)src) { at = atomicAdd(&P.ctrl[kCands], (unsigned long long)__popcll(have)); s_any[g] = 1; }
+                const u32 at_lo = (u32)__shfl((int)(u32)at, src), at_hi = (u32)__shfl((int)(u32)(at >> 32), src);
+                const u64 slot = (((u64)at_hi << 32) | at_lo) + (u64)__popcll(have & ((1ull << lane) - 1));
+                if (cand && slot < P.cand_cap) {
+                    P.cand_key[slot] = ((u64)tag << 32) | p;
+                    P.cand_ovl[slot] = c;
+                }
+            }
+            query_group_sync<kWave>();
+            if (t == 0 && s_any[g]) {   // (at most once per source: the list has room for every source of the kernel)
+                s_any[g] = 0;
+                const unsigned long long pos = atomicAdd(&P.ctrl[P.fill_word], 1ull);
+                if (pos < P.n_list) P.fill_list[pos] = p;
+            }
+            query_group_sync<kWave>();
+        } else {
+            // the counter of a touched query becomes the cursor of its candidate's segment
+            for (u32 j = t; j < count; j += kLanes) {
+                const u32 tag = over ? j : list[j];
+                const u32 c = cnt[tag];
+                if (!c) continue;
+                u32 cursor = kNone;
+                if (c >= P.min_hashes) {
+                    const u32 idx = gather_find(P.ckey, P.n_cand, ((u64)tag << 32) | p);
+                    if (idx != kNone) cursor = (u32)P.cbase[idx];
+                }
+                cnt[tag] = cursor;
+            }
+            query_group_sync<kWave>();
+            for (u64 e = o0 + t; e < o1; e += (u64)kLanes * kProbeKeys) {
+                u64 k[kProbeKeys];
+                bool live[kProbeKeys];
+                u32 at[kProbeKeys];
+#pragma unroll
+                for (int x = 0; x < kProbeKeys; ++x) {
+                    const u64 ex = e + (u64)x * kLanes;
+                    live[x] = ex < o1;
+                    k[x] = live[x] ? P.db_keys[ex] : 0;
+                }
+                query_lookup(T, k, live, at);
+#pragma unroll
+                for (int x = 0; x < kProbeKeys; ++x) {
+                    if (!live[x]) continue;
+                    const u32 h1 = T.toff[at[x] + 1];
+                    for (u32 h = T.toff[at[x]]; h < h1; ++h) {
+                        const u32 tag = T.tq[h];
+                        if (tag >= T.nq) continue;
+                        if (__hip_atomic_load(&cnt[tag], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == kNone) continue;   // (kNone is never a cursor: n_slots < 2^32 - 1)
+                        const u32 pos = atomicAdd(&cnt[tag], 1u);
+                        if (pos < P.n_slots) P.seg[pos] = h;
+                    }
+                }
+            }
+            query_group_sync<kWave>();
+            for (u32 j = t; j < count; j += kLanes) cnt[over ? j : list[j]] = 0;
+            query_group_sync<kWave>();
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the rounds
+struct GRound {
+    const u64* ckey;    // n_cand sorted candidates: (query inside the tile << 32) | source
+    const u32* covl;    // their overlaps = segment lengths
+    const u64* cbase;   // their segments' first slots in seg[]
+    const u32* seg;     // holder slots
+    u32* alive;         // one bit per holder slot
+    u32* cdead;         // per candidate: taken, or fallen below min_hashes
+    unsigned long long* best;   // per query of the tile: the best offer of the round, 0: none
+    u32 *qrank, *qrem, *qdone;  // per query: rows so far, |R|, finished
+    u32 n_cand, nq, q0, min_hashes, max_matches;
+    ksp_gather_row* rows;       // the tile's rows in the order they were found
+    u32 rows_cap;
+    unsigned long long* ctrl;
+};
+
+// the alive slots of candidate c's segment among the entries first + lane, first + lane + stride, ...: the same for the whole wave
+__device__ inline u32 gather_alive(const GRound& R, const u32 c, const u32 first, const u32 stride, const u32 lane) {
+    const u64 base = R.cbase[c];
+    const u32 len = R.covl[c];
+    u32 u = 0;
+    for (u32 i0 = first; i0 < len; i0 += stride) {   // (the same trips for every lane of the wave)
+        const u32 i = i0 + lane;
+        bool bit = false;
+        if (i < len) {
+            const u32 h = R.seg[base + i];
+            bit = (load_u32(&R.alive[h >> 5]) >> (h & 31)) & 1u;
+        }
+        u += (u32)__popcll(__ballot(bit));
+    }
+    return u;
+}
+
+// is candidate c still in the running?  (the same answer for every lane that asks in one round)
+__device__ inline bool gather_is_live(const GRound& R, const u32 c) {
+    return c < R.n_cand && !load_u32(&R.cdead[c]) && !load_u32(&R.qdone[(u32)(R.ckey[c] >> 32)]);
+}
+
+// what ONE lane does with the count u of candidate c
+__device__ inline void gather_offer(const GRound& R, const u32 c, const u32 u) {
+    if (u < R.min_hashes) {
+        R.cdead[c] = 1;
+        atomicAdd(&R.ctrl[kFell], 1ull);
+    } else {
+        atomicMax(&R.best[(u32)(R.ckey[c] >> 32)], ((unsigned long long)u << 32) | (u32)~c);
+    }
+}
+
+// what ONE wave does with query `tag` of the tile behind the counts of a round
+__device__ inline void gather_take(const GRound& R, const u32 tag, const u32 lane) {
+    if (load_u32(&R.qdone[tag])) return;
+    const unsigned long long w = load_u64(&R.best[tag]);
+    if (w == 0) {   // nobody offered: nothing covers min_hashes of what is left
+        if (lane == 0) { R.qdone[tag] = 1; atomicAdd(&R.ctrl[kLiveQ], ~0ull); }
+        return;
+    }
+    const u32 u = (u32)(w >> 32), c = ~(u32)w;
+    if (c >= R.n_cand) return;   // (never: an offer names its candidate)
+    const u64 base = R.cbase[c];
+    const u32 len = R.covl[c];
+    for (u32 i = lane; i < len; i += 64) {
+        const u32 h = R.seg[base + i];
+        const u32 bit = 1u << (h & 31);
+        if (load_u32(&R.alive[h >> 5]) & bit) atomicAnd(&R.alive[h >> 5], ~bit);
+    }
+    if (lane == 0) {
+        const u32 rank = R.qrank[tag] + 1, rem = R.qrem[tag] - u;
+        const unsigned long long at = atomicAdd(&R.ctrl[kRows], 1ull);
+        if (at < R.rows_cap) R.rows[at] = ksp_gather_row{R.q0 + tag, rank, (u32)R.ckey[c], len, u, rem};
+        R.qrank[tag] = rank;
+        R.qrem[tag] = rem;
+        R.best[tag] = 0;
+        R.cdead[c] = 1;
+        if (R.max_matches && rank >= R.max_matches) { R.qdone[tag] = 1; atomicAdd(&R.ctrl[kLiveQ], ~0ull); }
+    }
+}
+
+// The counts of a round: workgroups [0, short_groups) take the short list, a wave per candidate; the others the long list, a
+// workgroup per candidate.  Returns at once when no query is live.
+__global__ __launch_bounds__(kThreads) void k_gather_count(const GRound R, const u32* __restrict__ list0, const u32 n0, const u32 short_groups,
+                                                           const u32* __restrict__ list1, const u32 n1) {
+    __shared__ u32 s_u;
+    const bool go = load_u64(&R.ctrl[kLiveQ]) != 0;   // (no kernel of a round's counts changes it)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        R.ctrl[kGo] = go;
+        if (go) R.ctrl[kRounds] += 1;
+    }
+    if (!go) return;
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (blockIdx.x < short_groups) {
+        for (u64 i = (u64)blockIdx.x * kWaves + wave; i < n0; i += (u64)short_groups * kWaves) {
+            const u32 c = list0[i];
+            if (!gather_is_live(R, c)) continue;   // (the whole wave)
+            const u32 u = gather_alive(R, c, 0, 64, lane);
+            if (lane == 0) gather_offer(R, c, u);
+        }
+    } else {
+        const u32 long_groups = gridDim.x - short_groups;
+        for (u64 i = blockIdx.x - short_groups; i < n1; i += long_groups) {
+            const u32 c = list1[i];
+            if (!gather_is_live(R, c)) continue;   // (the whole workgroup)
+            if (threadIdx.x == 0) s_u = 0;
+            __syncthreads();
+            const u32 u = gather_alive(R, c, wave * 64, kThreads, lane);
+            if (lane == 0 && u) atomicAdd(&s_u, u);
+            __syncthreads();
+            if (threadIdx.x == 0) gather_offer(R, c, s_u);
+            __syncthreads();
+        }
+    }
+}
+
+// The takes of a round: a wave per query of the tile.
+__global__ __launch_bounds__(kThreads) void k_gather_take(const GRound R) {
+    if (load_u64(&R.ctrl[kGo]) == 0) return;
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (u64 tag = (u64)blockIdx.x * kWaves + wave; tag < R.nq; tag += (u64)gridDim.x * kWaves) gather_take(R, (u32)tag, lane);
+}
+
+// The remaining rounds by ONE workgroup: the same counts and takes, separated by __syncthreads() and not by dispatches.  A round
+// with a live query takes a candidate or finishes every query, so `bound` = the live candidates + 1 rounds suffice.  Hand-over:
+// the queries it finds unfinished must be the device's count of them (out[2] = 1 otherwise, and nothing runs).  out[0] = the
+// rounds that ran, out[1] = the queries still live (0 unless the bound was hit, which the host reports).
+__global__ __launch_bounds__(kTailThreads) void k_gather_tail(const GRound R, const u32* __restrict__ list0, const u32 n0, const u32* __restrict__ list1, const u32 n1,
+                                                              const u32 bound, u32* __restrict__ out) {
+    __shared__ u32 s_live;
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr u32 kTailWaves = kTailThreads / 64;
+    if (threadIdx.x == 0) s_live = 0;
+    __syncthreads();
+    u32 mine = 0;
+    for (u32 j = threadIdx.x; j < R.nq; j += kTailThreads) mine += !load_u32(&R.qdone[j]);
+    if (mine) atomicAdd(&s_live, mine);
+    __syncthreads();
+    u32 live = s_live, rounds = 0;
+    const bool handed = live == (u32)load_u64(&R.ctrl[kLiveQ]);
+    __syncthreads();
+    for (u32 it = 0; handed && it < bound && live; ++it) {
+        for (u32 i = wave; i < n0 + n1; i += kTailWaves) {
+            const u32 c = i < n0 ? list0[i] : list1[i - n0];
+            if (!gather_is_live(R, c)) continue;   // (the whole wave)
+            const u32 u = gather_alive(R, c, 0, 64, lane);
+            if (lane == 0) gather_offer(R, c, u);
+        }
+        __threadfence();
+        __syncthreads();   // every offer of this round is made
+        for (u32 tag = wave; tag < R.nq; tag += kTailWaves) gather_take(R, tag, lane);
+        __threadfence();
+        __syncthreads();   // every take of this round is made
+        if (threadIdx.x == 0) s_live = (u32)load_u64(&R.ctrl[kLiveQ]);
+        __syncthreads();
+        live = s_live;
+        ++rounds;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        R.ctrl[kRounds] += rounds;
+        out[0] = rounds;
+        out[1] = live;
+        out[2] = handed ? 0 : 1;
+    }
+}
+
+// per query of the tile: nothing found yet, everything left; every query is live (the device's words were zeroed before)
+__global__ void k_gather_init(const u64* __restrict__ q_off, const GRound R) {
+    const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= R.nq) return;
+    if (j == 0) R.ctrl[kLiveQ] = R.nq;
+    R.best[j] = 0;
+    R.qrank[j] = 0;
+    R.qdone[j] = 0;
+    R.qrem[j] = (u32)(q_off[R.q0 + j + 1] - q_off[R.q0 + j]);   // (a tile has fewer than 2^31 entries)
+}
+
+// The live candidates of `in` (in == NULL: of all candidates), split by segment length when `out1` is given: one append per wave.
+__global__ __launch_bounds__(kThreads) void k_gather_live(const GRound R, const u32* __restrict__ in, const u32 n, const u64 long_seg, const bool split, u32* __restrict__ out0,
+                                                          u32* __restrict__ out1, const int word0) {
+    const u32 lane = threadIdx.x & 63;
+    const u64 span = (u64)gridDim.x * blockDim.x;
+    for (u64 base = (u64)blockIdx.x * blockDim.x; base < n; base += span) {   // (the same trips for every lane of the wave)
+        const u64 i = base + threadIdx.x;
+        const u32 c = i < n ? (in ? in[i] : (u32)i) : kNone;
+        const bool keep = i < n && gather_is_live(R, c);
+        const bool is_long = keep && split && (u64)R.covl[c] >= long_seg;
+#pragma unroll
+        for (int cls = 0; cls < 2; ++cls) {
+            const unsigned long long b = __ballot(keep && is_long == (cls == 1));
+            if (!b) continue;
+            unsigned long long at = 0;
+            const int src = __ffsll((long long)b) - 1;
+            if (lane == (u32)src) at = atomicAdd(&R.ctrl[word0 + cls], (unsigned long long)__popcll(b));
+            const u32 pos = (u32)__shfl((int)(u32)at, src) + (u32)__popcll(b & ((1ull << lane) - 1));
+            if (keep && is_long == (cls == 1) && pos < R.n_cand) (cls ? out1 : out0)[pos] = c;
+        }
+    }
+}
+
+// the tile's rows into (query, rank) order: qoff[] = the exclusive scan of the queries' row counts
+__global__ void k_gather_rows(const GRound R, const u32 n_rows, const u32* __restrict__ qoff, ksp_gather_row* __restrict__ sorted) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n_rows; i += (u64)gridDim.x * blockDim.x) {
+        const ksp_gather_row r = R.rows[i];
+        const u32 tag = r.query - R.q0;
+        if (tag >= R.nq || r.rank == 0) continue;
+        const u64 at = (u64)qoff[tag] + r.rank - 1;
+        if (at < n_rows) sorted[at] = r;
+    }
+}
+
+struct AsU64 {
+    __host__ __device__ u64 operator()(const u32 v) const { return v; }
+};
+
+// what all entry points refuse before anything is allocated
+int check_gather_args(const char* who, const void* db_keys, const u64* db_off, const u32 n_db, const void* q_keys, const u64* q_off, const u32 n_q, const u32 min_hashes,
+                      const void* n_rows) {
+    if (!db_keys || !db_off || !q_keys || !q_off || !n_rows) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+    if (n_db == 0 || n_q == 0) { ksp::set_error(std::string(who) + ": no database source or no query"); return KSP_E_ARG; }
+    if (min_hashes == 0) { ksp::set_error(std::string(who) + ": min_hashes is 1 or more"); return KSP_E_ARG; }
+    if ((u64)n_db + n_q > 0xFFFFFFFEull) { ksp::set_error(std::string(who) + ": more than 2^32 - 2 sources"); return KSP_E_LIMIT; }   // (from the counts alone)
+    if (const int rc = check_offsets(who, "database", db_off, n_db)) return rc;
+    return check_offsets(who, "query", q_off, n_q);
+}
+
+struct GatherSwitches {
+    u64 tile = 0, long_run = 0, list_cap = 0, long_seg = 0, tail = 0, tail_cands = 0;
+};
+
+// the environment's switches, refused before a device is chosen
+int read_switches(const char* who, GatherSwitches& W) {
+    int rc = KSP_OK;
+    if ((rc = env_number(who, "KSP_QUERY_TILE", kTileMax, 1, kTileMax, &W.tile)) || (rc = env_number(who, "KSP_QUERY_LONG_RUN", KSP_QUERY_LONG_RUN, 1, ~0ull, &W.long_run)) ||
+        (rc = env_number(who, "KSP_QUERY_LIST", kListMax, 1, kListMax, &W.list_cap)) || (rc = env_number(who, "KSP_GATHER_LONG_SEG", KSP_GATHER_LONG_SEG, 1, 0xFFFFFFFFull, &W.long_seg)) ||
+        (rc = env_number(who, "KSP_GATHER_TAIL", 1, 0, 1, &W.tail)) || (rc = env_number(who, "KSP_GATHER_TAIL_CANDS", KSP_GATHER_TAIL_CANDS, 0, KSP_GATHER_TAIL_CANDS_MAX, &W.tail_cands)))
+        return rc;
+    return KSP_OK;
+}
+
+// The gather on the CURRENT device; the arguments have passed check_gather_args and read_switches.  The rows go to d_rows (room
+// for `capacity`) or, when h_rows is given, to the host vector.
+int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_keys, const u64* h_db_off, const u32 n_db, const u64* d_q_keys, const u64* h_q_off, const u32 n_q,
+                     const u32 min_hashes, const u32 max_matches, ksp_gather_row* d_rows, const u64 capacity, std::vector<ksp_gather_row>* h_rows, u64* n_rows,
+                     ksp_gather_stats* stats) {
+    int rc = KSP_OK;
+    ksp_gather_stats S;
+    std::memset(&S, 0, sizeof S);
+    ksp::WorkgroupCap G;
+    u32 n_tiles = 0;
+    u64 e_max = 0, rows_done = 0;
+    if ((rc = query_tiles(who, h_q_off, n_q, W.tile, &n_tiles, &e_max))) return rc;
+    if ((rc = ksp::workgroup_cap("KSP_GATHER_MAX_WORKGROUPS", who, G))) return rc;
+    std::vector<u32> probes[2];   // [0] short, [1] long; a source without entries shares nothing
+    for (u32 p = 0; p < n_db; ++p)
+        if (const u64 len = h_db_off[p + 1] - h_db_off[p]) probes[len >= W.long_run].push_back(p);
+    S.n_db = n_db; S.n_q = n_q; S.db_entries = h_db_off[n_db]; S.q_entries = h_q_off[n_q];
+    S.tile = (u32)W.tile; S.long_seg = W.long_seg; S.tail_cands = W.tail ? W.tail_cands : 0; S.min_hashes = min_hashes; S.max_matches = max_matches;
+
+    ksp::DeviceArena A;
+    u64 *d_db_off = nullptr, *d_q_off = nullptr;
+    u32 *d_list[2] = {nullptr, nullptr}, *d_fill[2] = {nullptr, nullptr};
+    u32 *qrank = nullptr, *qrem = nullptr, *qdone = nullptr, *qoff = nullptr, *d_out = nullptr;
+    unsigned long long *ctrl = nullptr, *best = nullptr;
+    u64* cand_key = nullptr;   // the candidates as the sweep found them; they grow when a tile finds more
+    u32* cand_ovl = nullptr;
+    u64 cand_cap = 0;
+    QTableBufs B;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    unsigned long long h_ctrl[kCtrlWords];
+    size_t tb_rows = 0;
+    B.e_max = e_max;
+    if ((rc = query_table_scratch(e_max, &B.tb))) return rc;
+    KSP_TRY_HIP(rocprim::exclusive_scan(nullptr, tb_rows, (u32*)nullptr, (u32*)nullptr, 0u, (size_t)kTileMax, rocprim::plus<u32>(), (hipStream_t) nullptr));
+    B.tb = std::max<size_t>(std::max(B.tb, tb_rows), 8);
+    cand_cap = std::max<u64>(4096, 4ull * n_db);
+    // ---- what the call holds whatever the tiles find, sized and checked first: 8 per source (offsets), 8 per source with entries
+    // (its list and the list of those with a candidate), 24 per query of a tile, the table, the first candidate buffer, the scratch
+    if ((rc = ksp::device_fits(who, 8ull * ((u64)n_db + n_q + 2) + 8ull * (probes[0].size() + probes[1].size()) + 24ull * kTileMax + B.bytes() + 12 * cand_cap + B.tb + 256,
+                               "8 per source, 8 per source with entries, 40 per entry of the largest query tile, its directory, the candidates, the sort's scratch")))
+        return rc;
+    if ((rc = A.alloc(&d_db_off, (size_t)n_db + 1)) || (rc = A.alloc(&d_q_off, (size_t)n_q + 1)) || (rc = A.alloc(&ctrl, (size_t)kCtrlWords)) || (rc = A.alloc(&d_out, 4))) return rc;
+    for (int c = 0; c < 2; ++c)
+        if (!probes[c].empty() && ((rc = A.alloc(&d_list[c], probes[c].size())) || (rc = A.alloc(&d_fill[c], probes[c].size())))) return rc;
+    if ((rc = A.alloc(&best, (size_t)kTileMax)) || (rc = A.alloc(&qrank, (size_t)kTileMax)) || (rc = A.alloc(&qrem, (size_t)kTileMax)) || (rc = A.alloc(&qdone, (size_t)kTileMax)) ||
+        (rc = A.alloc(&qoff, (size_t)kTileMax)))
+        return rc;
+    if ((rc = A.alloc(&cand_key, (size_t)cand_cap)) || (rc = A.alloc(&cand_ovl, (size_t)cand_cap))) return rc;
+    if (e_max && ((rc = query_table_alloc(A, B)) || (rc = A.alloc_bytes(&B.tmp, B.tb)))) return rc;
+    KSP_TRY_HIP(hipMemcpy(d_db_off, h_db_off, ((size_t)n_db + 1) * 8, hipMemcpyHostToDevice));
+    KSP_TRY_HIP(hipMemcpy(d_q_off, h_q_off, ((size_t)n_q + 1) * 8, hipMemcpyHostToDevice));
+    for (int c = 0; c < 2; ++c)
+        if (!probes[c].empty()) KSP_TRY_HIP(hipMemcpy(d_list[c], probes[c].data(), probes[c].size() * 4, hipMemcpyHostToDevice));
+    for (hipEvent_t& e : ev) KSP_TRY_HIP(hipEventCreate(&e));
+
+    for (u32 t = 0; t < n_tiles; ++t) {
+        const u32 q0 = (u32)((u64)t * W.tile), nq = (u32)(std::min<u64>((u64)q0 + W.tile, n_q) - q0);
+        const u64 e0 = h_q_off[q0];
+        const u32 E = (u32)(h_q_off[q0 + nq] - e0);
+        if (E == 0) continue;   // a tile of empty queries matches nothing
+        // ---- the table
+        KSP_TRY_HIP(hipEventRecord(ev[0], nullptr));
+        QTable T;
+        u32 U = 0, H = 0;
+        if ((rc = query_table_build(who, G, B, d_q_keys, d_q_off, q0, nq, e0, E, &T, &U, &H))) goto done;
+        KSP_TRY_HIP(hipEventRecord(ev[1], nullptr));
+        // ---- the candidates: every source against this tile; once more with a larger buffer when it found more than fit
+        GSweep P;
+        std::memset(&P, 0, sizeof P);
+        P.db_keys = d_db_keys; P.db_off = d_db_off; P.list_cap = (u32)W.list_cap; P.min_hashes = min_hashes; P.ctrl = ctrl;
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            KSP_TRY_HIP(hipMemsetAsync(ctrl, 0, sizeof h_ctrl, nullptr));
+            P.cand_key = cand_key; P.cand_ovl = cand_ovl; P.cand_cap = cand_cap;
+            if (!probes[0].empty()) {
+                P.list = d_list[0]; P.n_list = (u32)probes[0].size(); P.fill_list = d_fill[0]; P.fill_word = kFill0;
+                hipLaunchKernelGGL((k_gather_sweep<true, false>), dim3(G.grid_of(((u64)P.n_list + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, T, P);
+            }
+            if (!probes[1].empty()) {
+                P.list = d_list[1]; P.n_list = (u32)probes[1].size(); P.fill_list = d_fill[1]; P.fill_word = kFill1;
+                hipLaunchKernelGGL((k_gather_sweep<false, false>), dim3(G.grid_of(P.n_list)), dim3(kThreads), 0, nullptr, T, P);
+            }
+            KSP_TRY_HIP(hipGetLastError());
+            KSP_TRY_HIP(hipMemcpy(h_ctrl, ctrl, sizeof h_ctrl, hipMemcpyDeviceToHost));
+            if (h_ctrl[kCands] <= cand_cap) break;
+            if (attempt == 1) { ksp::set_error(std::string(who) + ": the second sweep found more candidates than the first"); rc = KSP_E_HIP; goto done; }
+            if (h_ctrl[kCands] >= 0xFFFFFFFFull) { ksp::set_error(std::string(who) + ": 2^32 - 1 candidates or more in a query tile (lower KSP_QUERY_TILE)"); rc = KSP_E_LIMIT; goto done; }
+            KSP_TRY_HIP(A.release(cand_key));
+            KSP_TRY_HIP(A.release(cand_ovl));
+            cand_key = nullptr; cand_ovl = nullptr;
+            cand_cap = h_ctrl[kCands];
+            if ((rc = ksp::device_fits(who, 12 * cand_cap, "the candidates of a query tile"))) goto done;
+            if ((rc = A.alloc(&cand_key, (size_t)cand_cap)) || (rc = A.alloc(&cand_ovl, (size_t)cand_cap))) goto done;
+        }
+        const u32 n_cand = (u32)h_ctrl[kCands];
+        const u64 n_fill[2] = {h_ctrl[kFill0], h_ctrl[kFill1]};
+        if (n_fill[0] > probes[0].size() || n_fill[1] > probes[1].size()) { ksp::set_error(std::string(who) + ": more sources with a candidate than sources"); rc = KSP_E_HIP; goto done; }
+        S.candidates += n_cand; S.dropped += h_ctrl[kDropped]; S.table_keys += U; S.table_holders += H; ++S.passes;
+        float ms = 0;
+        if (n_cand == 0) {   // nothing reaches min_hashes: no row for any query of the tile
+            KSP_TRY_HIP(hipEventRecord(ev[2], nullptr));
+            KSP_TRY_HIP(hipEventSynchronize(ev[2]));
+            KSP_TRY_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); S.ms_table += ms;
+            KSP_TRY_HIP(hipEventElapsedTime(&ms, ev[1], ev[2])); S.ms_candidates += ms;
+            continue;
+        }
+        // ---- the tile's own arrays: the sorted candidates (key 8, overlap 4, base 8, dead 4, two live lists 2 x 2 x 4), the sort's
+        // scratch; then, when the slots are known, 4 per slot and a bit per holder; then the rows
+        u64 *ckey = nullptr, *cbase = nullptr, n_slots = 0;
+        u32 *covl = nullptr, *cdead = nullptr, *live[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *seg = nullptr, *alive = nullptr;
+        ksp_gather_row *rows = nullptr, *sorted = nullptr;
+        void* tmp2 = nullptr;
+        size_t tb_sort = 0, tb_scan = 0, tb2 = 0;
+        const auto ovl64 = [](const u32* p) { return rocprim::make_transform_iterator(p, AsU64()); };
+        KSP_TRY_HIP(rocprim::radix_sort_pairs(nullptr, tb_sort, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, (size_t)n_cand, 0, 44, (hipStream_t) nullptr));
+        KSP_TRY_HIP(rocprim::exclusive_scan(nullptr, tb_scan, ovl64(nullptr), (u64*)nullptr, (u64)0, (size_t)n_cand + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
+        tb2 = std::max<size_t>(std::max(tb_sort, tb_scan), 8);
+        if ((rc = ksp::device_fits(who, 40ull * ((u64)n_cand + 1) + tb2, "40 per candidate of a query tile, the sort's scratch"))) goto done;
+        if ((rc = A.alloc(&ckey, (size_t)n_cand)) || (rc = A.alloc(&covl, (size_t)n_cand + 1)) || (rc = A.alloc(&cbase, (size_t)n_cand + 1)) || (rc = A.alloc(&cdead, (size_t)n_cand)) ||
+            (rc = A.alloc_bytes(&tmp2, tb2)))
+            goto done;
+        for (int b = 0; b < 2; ++b)
+            for (int c = 0; c < 2; ++c)
+                if ((rc = A.alloc(&live[b][c], (size_t)n_cand))) goto done;
+        {
+            size_t b = tb2;
+            KSP_TRY_HIP(rocprim::radix_sort_pairs(tmp2, b, (const u64*)cand_key, ckey, (const u32*)cand_ovl, covl, (size_t)n_cand, 0, 44, (hipStream_t) nullptr));
+            KSP_TRY_HIP(hipMemsetAsync(covl + n_cand, 0, 4, nullptr));
+            KSP_TRY_HIP(hipMemsetAsync(cdead, 0, (size_t)n_cand * 4, nullptr));
+            b = tb2;
+            KSP_TRY_HIP(rocprim::exclusive_scan(tmp2, b, ovl64(covl), cbase, (u64)0, (size_t)n_cand + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
+        }
+        KSP_TRY_HIP(hipMemcpy(&n_slots, cbase + n_cand, 8, hipMemcpyDeviceToHost));
+        if (n_slots >= 0xFFFFFFFFull) { ksp::set_error(std::string(who) + ": match segments of 2^32 - 1 slots or more in a query tile (lower KSP_QUERY_TILE)"); rc = KSP_E_LIMIT; goto done; }
+        if (n_slots < (u64)n_cand * min_hashes) { ksp::set_error(std::string(who) + ": the segments are shorter than their candidates' overlaps"); rc = KSP_E_HIP; goto done; }
+        S.slots += n_slots;
+        KSP_TRY_HIP(hipEventRecord(ev[2], nullptr));
+        // ---- the segments: the sources that have a candidate once more
+        const u64 alive_words = ((u64)H + 31) / 32;
+        // a row removes min_hashes or more of its query, and a candidate is taken once
+        const u64 rows_cap = std::min<u64>(std::min<u64>(n_cand, (u64)E / min_hashes), max_matches ? (u64)nq * max_matches : ~0ull);
+        if ((rc = ksp::device_fits(who, 4 * n_slots + 4 * alive_words + 48 * rows_cap + 64, "4 per matched hash of a candidate, a bit per query hash, 48 per possible row"))) goto done;
+        if ((rc = A.alloc(&seg, (size_t)n_slots)) || (rc = A.alloc(&alive, (size_t)alive_words)) || (rc = A.alloc(&rows, (size_t)rows_cap + 1)) || (rc = A.alloc(&sorted, (size_t)rows_cap + 1)))
+            goto done;
+        KSP_TRY_HIP(hipMemsetAsync(alive, 0xFF, (size_t)alive_words * 4, nullptr));
+        P.ckey = ckey; P.cbase = cbase; P.n_cand = n_cand; P.seg = seg; P.n_slots = (u32)n_slots;
+        if (n_fill[0]) {
+            P.list = d_fill[0]; P.n_list = (u32)n_fill[0];
+            hipLaunchKernelGGL((k_gather_sweep<true, true>), dim3(G.grid_of(((u64)P.n_list + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, T, P);
+        }
+        if (n_fill[1]) {
+            P.list = d_fill[1]; P.n_list = (u32)n_fill[1];
+            hipLaunchKernelGGL((k_gather_sweep<false, true>), dim3(G.grid_of(P.n_list)), dim3(kThreads), 0, nullptr, T, P);
+        }
+        KSP_TRY_HIP(hipGetLastError());
+        KSP_TRY_HIP(hipEventRecord(ev[3], nullptr));
+        // ---- the rounds
+        {
+            const GRound R{ckey, covl, cbase, seg, alive, cdead, best, qrank, qrem, qdone, n_cand, nq, q0, min_hashes, max_matches, rows, (u32)rows_cap, ctrl};
+            const unsigned gq = (unsigned)(((u64)nq + 255) / 256), gc = G.grid_of(((u64)n_cand + kThreads - 1) / kThreads);
+            u64 n_live[2] = {0, 0};
+            int cur = 0;
+            bool in_tail = false;
+            KSP_TRY_HIP(hipMemsetAsync(ctrl, 0, sizeof h_ctrl, nullptr));
+            hipLaunchKernelGGL(k_gather_init, dim3(gq), dim3(256), 0, nullptr, (const u64*)d_q_off, R);
+            hipLaunchKernelGGL(k_gather_live, dim3(gc), dim3(kThreads), 0, nullptr, R, (const u32*)nullptr, n_cand, W.long_seg, true, live[cur][0], live[cur][1], (int)kKept0);
+            KSP_TRY_HIP(hipGetLastError());
+            KSP_TRY_HIP(hipMemcpy(h_ctrl, ctrl, sizeof h_ctrl, hipMemcpyDeviceToHost));
+            n_live[0] = h_ctrl[kKept0]; n_live[1] = h_ctrl[kKept1];
+            if (n_live[0] + n_live[1] != n_cand) { ksp::set_error(std::string(who) + ": the first live lists do not hold every candidate"); rc = KSP_E_HIP; goto done; }
+            const u64 max_batches = (u64)n_cand / KSP_GATHER_BATCH + 2;   // a round with a live query takes a candidate or finishes every query
+            u64 batches = 0;
+            while (h_ctrl[kLiveQ]) {
+                const u64 n_both = n_live[0] + n_live[1];
+                if (W.tail && n_both <= W.tail_cands) {
+                    u32 h_out[4] = {0, 0, 0, 0};
+                    hipLaunchKernelGGL(k_gather_tail, dim3(1), dim3(kTailThreads), 0, nullptr, R, (const u32*)live[cur][0], (u32)n_live[0], (const u32*)live[cur][1], (u32)n_live[1],
+                                       (u32)n_both + 1, d_out);
+                    KSP_TRY_HIP(hipGetLastError());
+                    KSP_TRY_HIP(hipMemcpy(h_out, d_out, 12, hipMemcpyDeviceToHost));
+                    if (h_out[2]) { ksp::set_error(std::string(who) + ": the tail's count of live queries does not match the batches'"); rc = KSP_E_HIP; goto done; }
+                    if (h_out[1]) { ksp::set_error(std::string(who) + ": the tail left " + std::to_string(h_out[1]) + " queries live after " + std::to_string(h_out[0]) + " rounds"); rc = KSP_E_HIP; goto done; }
+                    S.tail_rounds += h_out[0];
+                    S.live_at_tail += n_both;
+                    in_tail = true;
+                    break;
+                }
+                if (++batches > max_batches) { ksp::set_error(std::string(who) + ": more than " + std::to_string(max_batches) + " batches of rounds"); rc = KSP_E_HIP; goto done; }
+                const unsigned g0 = G.grid_of((n_live[0] + kWaves - 1) / kWaves), g1 = G.grid_of(n_live[1]);
+                for (u32 r = 0; r < KSP_GATHER_BATCH; ++r) {
+                    hipLaunchKernelGGL(k_gather_count, dim3(g0 + g1), dim3(kThreads), 0, nullptr, R, (const u32*)live[cur][0], (u32)n_live[0], (u32)g0, (const u32*)live[cur][1], (u32)n_live[1]);
+                    hipLaunchKernelGGL(k_gather_take, dim3(G.grid_of(((u64)nq + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, R);
+                }
+                // the dead leave the lists
+                KSP_TRY_HIP(hipMemsetAsync(&ctrl[kKept0], 0, 16, nullptr));
+                for (int c = 0; c < 2; ++c)
+                    if (n_live[c])
+                        hipLaunchKernelGGL(k_gather_live, dim3(G.grid_of((n_live[c] + kThreads - 1) / kThreads)), dim3(kThreads), 0, nullptr, R, (const u32*)live[cur][c], (u32)n_live[c], W.long_seg,
+                                           false, live[cur ^ 1][c], (u32*)nullptr, (int)kKept0 + c);
+                KSP_TRY_HIP(hipGetLastError());
+                KSP_TRY_HIP(hipMemcpy(h_ctrl, ctrl, sizeof h_ctrl, hipMemcpyDeviceToHost));
+                if (h_ctrl[kKept0] > n_live[0] || h_ctrl[kKept1] > n_live[1]) { ksp::set_error(std::string(who) + ": a compaction kept more candidates than its list holds"); rc = KSP_E_HIP; goto done; }
+                n_live[0] = h_ctrl[kKept0]; n_live[1] = h_ctrl[kKept1];
+                cur ^= 1;
+                ++S.batches;
+            }
+            if (in_tail) KSP_TRY_HIP(hipMemcpy(h_ctrl, ctrl, sizeof h_ctrl, hipMemcpyDeviceToHost));
+            S.rounds += h_ctrl[kRounds]; S.fell_below += h_ctrl[kFell];
+            // ---- the tile's rows, by (query, rank)
+            const u64 found = h_ctrl[kRows];
+            if (found > rows_cap) { ksp::set_error(std::string(who) + ": more rows than a tile can have"); rc = KSP_E_HIP; goto done; }
+            if (found) {
+                size_t b = B.tb;
+                KSP_TRY_HIP(rocprim::exclusive_scan(B.tmp, b, (const u32*)qrank, qoff, 0u, (size_t)nq, rocprim::plus<u32>(), (hipStream_t) nullptr));
+                hipLaunchKernelGGL(k_gather_rows, dim3(G.grid_of((found + 255) / 256)), dim3(256), 0, nullptr, R, (u32)found, (const u32*)qoff, sorted);
+                KSP_TRY_HIP(hipGetLastError());
+                if (h_rows) {
+                    const size_t at = h_rows->size();
+                    h_rows->resize(at + (size_t)found);
+                    KSP_TRY_HIP(hipMemcpy(h_rows->data() + at, sorted, (size_t)found * sizeof(ksp_gather_row), hipMemcpyDeviceToHost));
+                } else if (rows_done < capacity) {
+                    KSP_TRY_HIP(hipMemcpyAsync(d_rows + rows_done, sorted, (size_t)std::min<u64>(found, capacity - rows_done) * sizeof(ksp_gather_row), hipMemcpyDeviceToDevice, nullptr));
+                }
+                rows_done += found;
+            }
+        }
+        KSP_TRY_HIP(hipEventRecord(ev[4], nullptr));
+        KSP_TRY_HIP(hipEventSynchronize(ev[4]));
+        KSP_TRY_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); S.ms_table += ms;
+        KSP_TRY_HIP(hipEventElapsedTime(&ms, ev[1], ev[2])); S.ms_candidates += ms;
+        KSP_TRY_HIP(hipEventElapsedTime(&ms, ev[2], ev[3])); S.ms_fill += ms;
+        KSP_TRY_HIP(hipEventElapsedTime(&ms, ev[3], ev[4])); S.ms_rounds += ms;
+        for (void* p : {(void*)ckey, (void*)covl, (void*)cbase, (void*)cdead, (void*)live[0][0], (void*)live[0][1], (void*)live[1][0], (void*)live[1][1], (void*)seg, (void*)alive, (void*)rows,
+                        (void*)sorted, tmp2})
+            KSP_TRY_HIP(A.release(p));
+    }
+    S.rows = rows_done;
+    *n_rows = rows_done;
+    if (stats) *stats = S;
+    if (!h_rows && rows_done > capacity) {
+        ksp::set_error(std::string(who) + ": " + std::to_string(rows_done) + " rows, room for " + std::to_string(capacity));
+        rc = KSP_E_OVERFLOW;
+    }
+done:
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int ksp_gather_device(int device, const uint64_t* d_db_keys, const uint64_t* h_db_offsets, uint32_t n_db, const uint64_t* d_q_keys, const uint64_t* h_q_offsets,
+                                 uint32_t n_q, uint32_t min_hashes, uint32_t max_matches, ksp_gather_row* d_rows, uint64_t capacity, uint64_t* n_rows, ksp_gather_stats* stats) {
+    const char* who = "ksp_gather_device";
+    GatherSwitches W;
+    if (const int rc = check_gather_args(who, d_db_keys, h_db_offsets, n_db, d_q_keys, h_q_offsets, n_q, min_hashes, n_rows)) return rc;
+    if (!d_rows && capacity) { ksp::set_error(std::string(who) + ": d_rows is NULL but capacity is not 0"); return KSP_E_ARG; }
+    if (const int rc = read_switches(who, W)) return rc;
+    if (const int rc = ksp::set_device(who, device)) return rc;
+    return gather_on_device(who, W, d_db_keys, h_db_offsets, n_db, d_q_keys, h_q_offsets, n_q, min_hashes, max_matches, d_rows, capacity, nullptr, n_rows, stats);
+}
+
+extern "C" int ksp_gather_host(const uint64_t* db_keys, const uint64_t* db_offsets, uint32_t n_db, const uint64_t* q_keys, const uint64_t* q_offsets, uint32_t n_q,
+                               uint32_t min_hashes, uint32_t max_matches, int device, ksp_gather_row** rows, uint64_t* n_rows, ksp_gather_stats* stats) {
+    const char* who = "ksp_gather_host";
+    GatherSwitches W;
+    if (!rows) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+    if (const int rc = check_gather_args(who, db_keys, db_offsets, n_db, q_keys, q_offsets, n_q, min_hashes, n_rows)) return rc;
+    if (const int rc = read_switches(who, W)) return rc;
+    if (const int rc = ksp::set_device(who, device)) return rc;
+    int rc = KSP_OK;
+    ksp::DeviceArena A;
+    const u64 n_dbk = db_offsets[n_db], n_qk = q_offsets[n_q];
+    u64 *d_db = nullptr, *d_q = nullptr, found = 0;
+    std::vector<ksp_gather_row> got;
+    ksp_gather_row* out = nullptr;
+    if ((rc = ksp::device_fits(who, 8ull * (n_dbk + n_qk + 2), "the keys of both sides"))) return rc;
+    if ((rc = A.alloc(&d_db, (size_t)n_dbk + 1)) || (rc = A.alloc(&d_q, (size_t)n_qk + 1))) return rc;
+    KSP_TRY_HIP(hipMemcpy(d_db, db_keys, (size_t)n_dbk * 8, hipMemcpyHostToDevice));
+    KSP_TRY_HIP(hipMemcpy(d_q, q_keys, (size_t)n_qk * 8, hipMemcpyHostToDevice));
+    try {
+        rc = gather_on_device(who, W, d_db, db_offsets, n_db, d_q, q_offsets, n_q, min_hashes, max_matches, nullptr, 0, &got, &found, stats);
+    } catch (const std::bad_alloc&) {
+        ksp::set_error(std::string(who) + ": out of host memory");
+        rc = KSP_E_LIMIT;
+    }
+    if (rc != KSP_OK) goto done;
+    out = (ksp_gather_row*)std::malloc(std::max<size_t>(got.size(), 1) * sizeof(ksp_gather_row));
+    if (!out) { ksp::set_error(std::string(who) + ": out of host memory"); rc = KSP_E_LIMIT; goto done; }
+    if (!got.empty()) std::memcpy(out, got.data(), got.size() * sizeof(ksp_gather_row));
+    *rows = out;
+    *n_rows = found;
+done:
+    return rc;
+}

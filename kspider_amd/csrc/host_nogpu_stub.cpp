@@ -106,6 +106,16 @@ int ksp_query_host(const uint64_t*, const uint64_t*, uint32_t, const uint64_t*, 
     ksp::set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }
+int ksp_gather_host(const uint64_t*, const uint64_t*, uint32_t, const uint64_t*, const uint64_t*, uint32_t, uint32_t, uint32_t, int, ksp_gather_row**, uint64_t*,
+                    ksp_gather_stats*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_gather_device(int, const uint64_t*, const uint64_t*, uint32_t, const uint64_t*, const uint64_t*, uint32_t, uint32_t, uint32_t, ksp_gather_row*, uint64_t, uint64_t*,
+                      ksp_gather_stats*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
 void ksp_free(void* p) { std::free(p); }
 int ksp_engine_lists_path(const ksp_engine*, int*) {
     ksp::set_error("host-only sanitizer build: no HIP engine");

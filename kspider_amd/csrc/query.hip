@@ -6,12 +6,8 @@
 //   source_1 < source_2 in that numbering and shared > 0: KSP_QUERY_CROSS gives the database x query pairs,
 //   KSP_QUERY_CROSS_AND_SELF also every query x query pair once.
 //
-//   table    per tile of at most KSP_QUERY_TILE consecutive queries: every query entry tagged with its query index inside the
-//            tile (k_query_tag), (key, tag) sorted by key with rocPRIM's radix sort (stable: the tags of a key ascend), adjacent
-//            duplicates dropped by one scan of packed (head, kept) flags and k_query_compact.  Result: the distinct keys tk[U],
-//            the holder ranges toff[U + 1] and the holders tq[].  First level: dir[b] = the first index whose key >> shift is
-//            >= b (k_query_dir; bits and shift: ksp_query_directory), then a binary search inside the bucket.  A probe key above
-//            tk[U - 1] misses without a memory access.  No hash function, no compare-and-swap build, no collisions.
+//   table    per tile of at most KSP_QUERY_TILE consecutive queries: the collision-free sorted table with its directory
+//            (query_table.hip.h, shared with gather.hip).
 //   probe    the probe sources are the database sources, followed in mode 1 by the queries.  A source's pair counters are u32
 //            in LDS, one per query of the tile.  k_query_probe<true>: one wave per source with wave-private counters, for runs
 //            below KSP_QUERY_LONG_RUN entries; k_query_probe<false>: one 256-thread workgroup per source for the others.  A lane
@@ -31,17 +27,11 @@
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_merge_sort.hpp>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
 
 #include "../../include/kspider_amd.h"
 #include "device_call.h"
 #include "engine_internal.h"
-
-typedef uint32_t u32;
-typedef uint64_t u64;
+#include "query_table.hip.h"
 
 namespace {
 
@@ -52,17 +42,6 @@ constexpr int kWaves = kThreads / 64;
 // the wave kernel holds four groups: 4 x (8 + 2) KiB + 16 bytes; four of its workgroups fit the 160 KiB of a CU
 static_assert(2 * (kWaves * (kTileMax + kListMax) * 4 + 64) <= 160 * 1024, "two workgroups per CU");
 static_assert(kWaves * (kTileMax + kListMax) * 4 + 64 <= 64 * 1024, "static LDS of one workgroup");
-
-// one tile's table (device pointers), by value into the probe kernels
-struct QTable {
-    const u64* tk;     // U distinct keys, ascending
-    const u32* toff;   // U + 1: the holders of key u are tq[toff[u] .. toff[u + 1])
-    const u32* tq;     // holders: query indices inside the tile, ascending within a key
-    const u32* dir;    // n_buckets + 1: dir[b] = the first index whose key >> shift is >= b
-    u64 max_key;       // tk[U - 1]
-    int shift;
-    u32 q0, nq;        // the tile's queries: q0 .. q0 + nq - 1 (indices among the queries)
-};
 
 // what a probe kernel reads and writes besides the table
 struct QProbe {
@@ -76,112 +55,6 @@ struct QProbe {
     unsigned long long* cursor;      // edges appended so far, the ones that found no room included
     unsigned long long* overflows;   // sources whose touched list overflowed
 };
-
-// tag[i] = the query (inside the tile) that holds entry e0 + i: the last offset that is <= the entry
-__global__ void k_query_tag(const u64* __restrict__ q_off, const u32 q0, const u32 nq, const u64 e0, const u32 E, u32* __restrict__ tag) {
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < E; i += (u64)gridDim.x * blockDim.x) {
-        const u64 e = e0 + i;
-        u32 lo = 0, hi = nq;   // the answer is in [lo, hi): q_off[q0 + lo] <= e < q_off[q0 + hi]
-        while (hi - lo > 1) {
-            const u32 mid = lo + (hi - lo) / 2;
-            if (q_off[q0 + mid] <= e) lo = mid; else hi = mid;
-        }
-        tag[i] = lo;
-    }
-}
-
-// (head << 32) | kept of sorted entry i: head = the first entry of its key, kept = head or another holder than the entry before
-struct QFlags {
-    const u64* key;
-    const u32* tag;
-    u32 E;
-    __host__ __device__ u64 operator()(const u32 i) const {
-        if (i >= E) return 0;
-        const bool head = i == 0 || key[i] != key[i - 1];
-        const bool kept = head || tag[i] != tag[i - 1];
-        return ((u64)head << 32) | (u64)kept;
-    }
-};
-
-// scan[i] = (heads << 32) | kept before entry i (E + 1 values: the last is the totals U and H)
-__global__ void k_query_compact(const u64* __restrict__ key, const u32* __restrict__ tag, const u64* __restrict__ scan, const u32 E, u64* __restrict__ tk,
-                                u32* __restrict__ toff, u32* __restrict__ tq) {
-    const QFlags flags{key, tag, E};
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < E; i += (u64)gridDim.x * blockDim.x) {
-        const u64 f = flags((u32)i), s = scan[i];
-        const u32 h = (u32)s, u = (u32)(s >> 32);
-        if (f & 1) tq[h] = tag[i];
-        if (f >> 32) { tk[u] = key[i]; toff[u] = h; }
-        if (i == 0) toff[(u32)(scan[E] >> 32)] = (u32)scan[E];
-    }
-}
-
-// dir[b] = the first index whose key is >= b << shift, b = 0 .. n_buckets (the last: U)
-__global__ void k_query_dir(const u64* __restrict__ tk, const u32 U, const int shift, const u32 n_buckets, u32* __restrict__ dir) {
-    for (u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x; b <= n_buckets; b += (u64)gridDim.x * blockDim.x) {
-        u32 lo = 0, hi = U;
-        if (b == n_buckets) lo = U;
-        const u64 first = b << shift;
-        while (lo < hi) {
-            const u32 mid = lo + (hi - lo) / 2;
-            if (tk[mid] < first) lo = mid + 1; else hi = mid;
-        }
-        dir[b] = lo;
-    }
-}
-
-// A lane looks kProbeKeys keys up at a time, step by step for all of them, so that the loads of a step — the keys, the bucket
-// bounds, a halving of every search, the final compare — are in flight together: a look-up is a chain of dependent loads from
-// L2 / Infinity Cache, and one chain at a time leaves the lane waiting on each (measured: DESIGN.md 7n).
-constexpr int kProbeKeys = 4;
-
-// at[x] = the index of k[x] in the table for every x whose live[x] stays set (a key above the largest misses without a load)
-__device__ inline void query_lookup(const QTable& T, const u64 (&k)[kProbeKeys], bool (&live)[kProbeKeys], u32 (&at)[kProbeKeys]) {
-    u32 lo[kProbeKeys], hi[kProbeKeys], end[kProbeKeys];
-#pragma unroll
-    for (int x = 0; x < kProbeKeys; ++x) {
-        live[x] = live[x] && k[x] <= T.max_key;
-        const u32 b = live[x] ? (u32)(k[x] >> T.shift) : 0;
-        lo[x] = live[x] ? T.dir[b] : 0;
-        end[x] = hi[x] = live[x] ? T.dir[b + 1] : 0;
-    }
-    bool more = true;
-    while (more) {   // (a bucket of a uniform table holds about four keys: two or three rounds)
-        u32 mid[kProbeKeys];
-        u64 v[kProbeKeys];
-#pragma unroll
-        for (int x = 0; x < kProbeKeys; ++x) {
-            mid[x] = lo[x] + (hi[x] - lo[x]) / 2;
-            v[x] = lo[x] < hi[x] ? T.tk[mid[x]] : 0;
-        }
-        more = false;
-#pragma unroll
-        for (int x = 0; x < kProbeKeys; ++x) {
-            if (lo[x] >= hi[x]) continue;
-            if (v[x] < k[x]) lo[x] = mid[x] + 1; else hi[x] = mid[x];
-            more |= lo[x] < hi[x];
-        }
-    }
-    u64 found[kProbeKeys];
-#pragma unroll
-    for (int x = 0; x < kProbeKeys; ++x) found[x] = lo[x] < end[x] ? T.tk[lo[x]] : 0;
-#pragma unroll
-    for (int x = 0; x < kProbeKeys; ++x) {
-        live[x] = lo[x] < end[x] && found[x] == k[x];   // (end is 0 for a key that was not live)
-        at[x] = lo[x];
-    }
-}
-
-// everything the group's lanes wrote to its LDS is visible to all of them behind this
-template <bool kWave>
-__device__ inline void query_group_sync() {
-    if (kWave) {
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-    } else {
-        __syncthreads();
-    }
-}
 
 // One group per probe source: a wave (kWave, four groups per workgroup) or the whole workgroup.  cnt[t]: the keys the source
 // shares with query t of the tile; list[0 .. min(*n, cap)): the queries whose counter left 0.
@@ -267,28 +140,6 @@ struct EdgeBefore {
     }
 };
 
-// $name as a number in [lo, hi], or `fallback` when it is unset or empty
-int env_number(const char* who, const char* name, const u64 fallback, const u64 lo, const u64 hi, u64* out) {
-    const char* s = std::getenv(name);
-    *out = fallback;
-    if (!s || !*s) return KSP_OK;
-    char* end = nullptr;
-    const unsigned long long v = std::strtoull(s, &end, 10);
-    if (end == s || *end || *s == '-' || v < lo || v > hi) {
-        ksp::set_error(std::string(who) + ": " + name + " is a number from " + std::to_string(lo) + " to " + std::to_string(hi));
-        return KSP_E_ARG;
-    }
-    *out = v;
-    return KSP_OK;
-}
-
-int check_offsets(const char* who, const char* what, const u64* off, const u32 n) {
-    if (off[0] != 0) { ksp::set_error(std::string(who) + ": the " + what + " offsets do not start at 0"); return KSP_E_ARG; }
-    for (u32 s = 0; s < n; ++s)
-        if (off[s + 1] < off[s]) { ksp::set_error(std::string(who) + ": the " + what + " offsets decrease at source " + std::to_string(s)); return KSP_E_ARG; }
-    return KSP_OK;
-}
-
 // what both entry points refuse before anything is allocated
 int check_query_args(const char* who, const void* db_keys, const u64* db_off, const u32 n_db, const void* q_keys, const u64* q_off, const u32 n_q, const int mode,
                      const void* n_edges) {
@@ -315,13 +166,9 @@ int query_on_device(const char* who, const u64* d_db_keys, const u64* h_db_off, 
         (rc = env_number(who, "KSP_QUERY_LIST", kListMax, 1, kListMax, &list_cap)))
         return rc;
     // the tiles and the largest of them
-    const u32 n_tiles = (u32)(((u64)n_q + tile - 1) / tile);
+    u32 n_tiles = 0;
     u64 e_max = 0;
-    for (u32 t = 0; t < n_tiles; ++t) {
-        const u64 q0 = (u64)t * tile, q1 = std::min<u64>(q0 + tile, n_q), E = h_q_off[q1] - h_q_off[q0];
-        if (E >= (1ull << 31)) { ksp::set_error(std::string(who) + ": a query tile of 2^31 entries or more (lower KSP_QUERY_TILE)"); return KSP_E_LIMIT; }
-        e_max = std::max(e_max, E);
-    }
+    if ((rc = query_tiles(who, h_q_off, n_q, tile, &n_tiles, &e_max))) return rc;
     if ((rc = ksp::workgroup_cap("KSP_QUERY_MAX_WORKGROUPS", who, G))) return rc;
     // the probe sources by run length; a source without entries shares nothing
     std::vector<u32> probes[2];   // [0] short, [1] long
@@ -335,36 +182,24 @@ int query_on_device(const char* who, const u64* d_db_keys, const u64* h_db_off, 
     S.tile = (u32)tile; S.long_run = long_run; S.list_capacity = (u32)list_cap;
 
     ksp::DeviceArena A;
-    u64 *d_db_off = nullptr, *d_q_off = nullptr, *skey = nullptr, *scan = nullptr, *tk = nullptr;
-    u32 *d_list[2] = {nullptr, nullptr}, *tag = nullptr, *stag = nullptr, *toff = nullptr, *tq = nullptr, *dir = nullptr;
+    u64 *d_db_off = nullptr, *d_q_off = nullptr;
+    u32* d_list[2] = {nullptr, nullptr};
     unsigned long long* d_count = nullptr;   // [0] the cursor, [1] the list overflows
-    void* tmp = nullptr;
-    size_t tb_sort = 0, tb_scan = 0, tb = 0;
+    QTableBufs B;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     unsigned long long h_count[2] = {0, 0};
-    const u64 dir_max = (1ull << KSP_QUERY_DIR_BITS_MAX) + 1;
-    const auto flags_of = [](const u64* k, const u32* t, const u32 E) {
-        return rocprim::make_transform_iterator(rocprim::counting_iterator<u32>(0), QFlags{k, t, E});
-    };
-    if (e_max) {
-        KSP_TRY_HIP(rocprim::radix_sort_pairs(nullptr, tb_sort, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, (size_t)e_max, 0, 64, (hipStream_t) nullptr));
-        KSP_TRY_HIP(rocprim::exclusive_scan(nullptr, tb_scan, flags_of(nullptr, nullptr, 0), (u64*)nullptr, (u64)0, (size_t)e_max + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
-    }
-    tb = std::max<size_t>(std::max(tb_sort, tb_scan), 8);
+    B.e_max = e_max;
+    if ((rc = query_table_scratch(e_max, &B.tb))) return rc;
+    B.tb = std::max<size_t>(B.tb, 8);
     // ---- everything the call holds, sized and checked first: 8 per source (offsets), 4 per probe source, and per entry of the
     // largest tile 40 (tag 4, sorted key 8 and tag 4, scan 8, table key 8, holder range 4, holder 4), the directory, the scratch
-    if ((rc = ksp::device_fits(who, 8ull * ((u64)n_db + n_q + 2) + 4ull * (probes[0].size() + probes[1].size()) + 40ull * (e_max + 1) + 4 * std::min<u64>(dir_max, e_max + 2) + tb + 64,
+    if ((rc = ksp::device_fits(who, 8ull * ((u64)n_db + n_q + 2) + 4ull * (probes[0].size() + probes[1].size()) + B.bytes() + B.tb + 64,
                                "8 per source, 4 per probe source, 40 per entry of the largest query tile, its directory, the sort's scratch")))
         return rc;
     if ((rc = A.alloc(&d_db_off, (size_t)n_db + 1)) || (rc = A.alloc(&d_q_off, (size_t)n_q + 1)) || (rc = A.alloc(&d_count, 2))) return rc;
     for (int c = 0; c < 2; ++c)
         if (!probes[c].empty() && (rc = A.alloc(&d_list[c], probes[c].size()))) return rc;
-    if (e_max) {
-        if ((rc = A.alloc(&tag, (size_t)e_max)) || (rc = A.alloc(&skey, (size_t)e_max)) || (rc = A.alloc(&stag, (size_t)e_max)) || (rc = A.alloc(&scan, (size_t)e_max + 1)) ||
-            (rc = A.alloc(&tk, (size_t)e_max)) || (rc = A.alloc(&toff, (size_t)e_max + 1)) || (rc = A.alloc(&tq, (size_t)e_max)) ||
-            (rc = A.alloc(&dir, (size_t)std::min<u64>(dir_max, e_max + 2))) || (rc = A.alloc_bytes(&tmp, tb)))
-            return rc;
-    }
+    if (e_max && ((rc = query_table_alloc(A, B)) || (rc = A.alloc_bytes(&B.tmp, B.tb)))) return rc;
     KSP_TRY_HIP(hipMemcpy(d_db_off, h_db_off, ((size_t)n_db + 1) * 8, hipMemcpyHostToDevice));
     KSP_TRY_HIP(hipMemcpy(d_q_off, h_q_off, ((size_t)n_q + 1) * 8, hipMemcpyHostToDevice));
     for (int c = 0; c < 2; ++c)
@@ -379,36 +214,12 @@ int query_on_device(const char* who, const u64* d_db_keys, const u64* h_db_off, 
         if (E == 0) continue;   // a tile of empty queries shares nothing
         // ---- the table
         KSP_TRY_HIP(hipEventRecord(ev[0], nullptr));
-        const unsigned ge = G.grid_of(((u64)E + 255) / 256);
-        hipLaunchKernelGGL(k_query_tag, dim3(ge), dim3(256), 0, nullptr, (const u64*)d_q_off, q0, nq, e0, E, tag);
-        KSP_TRY_HIP(hipGetLastError());
-        {
-            size_t b = 0, b2 = 0;   // (the scratch was sized for the largest tile: a smaller one must not ask for more)
-            KSP_TRY_HIP(rocprim::radix_sort_pairs(nullptr, b, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, (size_t)E, 0, 64, (hipStream_t) nullptr));
-            KSP_TRY_HIP(rocprim::exclusive_scan(nullptr, b2, flags_of(nullptr, nullptr, 0), (u64*)nullptr, (u64)0, (size_t)E + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
-            if (std::max(b, b2) > tb) { ksp::set_error(std::string(who) + ": a smaller tile asks for more scratch than the largest"); rc = KSP_E_HIP; goto done; }
-            b = tb;
-            KSP_TRY_HIP(rocprim::radix_sort_pairs(tmp, b, d_q_keys + e0, skey, (const u32*)tag, stag, (size_t)E, 0, 64, (hipStream_t) nullptr));
-            b = tb;
-            KSP_TRY_HIP(rocprim::exclusive_scan(tmp, b, flags_of(skey, stag, E), scan, (u64)0, (size_t)E + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
-        }
-        u64 totals = 0, max_key = 0;
-        KSP_TRY_HIP(hipMemcpy(&totals, scan + E, 8, hipMemcpyDeviceToHost));
-        const u32 U = (u32)(totals >> 32), H = (u32)totals;
-        if (U == 0 || U > E || H < U || H > E) { ksp::set_error(std::string(who) + ": the query table lost its keys"); rc = KSP_E_HIP; goto done; }
-        hipLaunchKernelGGL(k_query_compact, dim3(ge), dim3(256), 0, nullptr, (const u64*)skey, (const u32*)stag, (const u64*)scan, E, tk, toff, tq);
-        KSP_TRY_HIP(hipGetLastError());
-        KSP_TRY_HIP(hipMemcpy(&max_key, tk + (U - 1), 8, hipMemcpyDeviceToHost));
-        int bits = 0, shift = 0;
-        (void)ksp_query_directory(max_key, U, &bits, &shift);
-        const u32 n_buckets = 1u << bits;
-        if ((u64)n_buckets + 1 > std::min<u64>(dir_max, (u64)e_max + 2)) { ksp::set_error(std::string(who) + ": the directory outgrew its buffer"); rc = KSP_E_HIP; goto done; }
-        hipLaunchKernelGGL(k_query_dir, dim3(G.grid_of(((u64)n_buckets + 256) / 256)), dim3(256), 0, nullptr, (const u64*)tk, U, shift, n_buckets, dir);
-        KSP_TRY_HIP(hipGetLastError());
+        QTable T;
+        u32 U = 0, H = 0;
+        if ((rc = query_table_build(who, G, B, d_q_keys, d_q_off, q0, nq, e0, E, &T, &U, &H))) goto done;
         KSP_TRY_HIP(hipEventRecord(ev[1], nullptr));
         // ---- the probe: every probe source against this tile
         {
-            const QTable T{tk, toff, tq, dir, max_key, shift, q0, nq};
             QProbe P{d_db_keys, d_db_off, d_q_keys, d_q_off, n_db, nullptr, 0, (u32)list_cap, d_edges, d_edges ? capacity : 0, &d_count[0], &d_count[1]};
             if (!probes[0].empty()) {
                 P.list = d_list[0]; P.n_list = (u32)probes[0].size();

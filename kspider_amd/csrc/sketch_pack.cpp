@@ -4,6 +4,7 @@
 //                   kspider_pairwise_sigs / kspider_pairwise_bins (sketch_loaders.cpp).  The format: sketch_set.h.
 //   kspider_query   database and queries, each a pack file or a directory -> the three files of a pairwise run over
 //                   database + queries, the TSV holding only the rows of the mode.  The device part is ksp_query_host (query.hip).
+//   kspider_gather  database and queries as above -> OUT_kSpider_gather.tsv, the rows of ksp_gather_host (gather.hip).
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -301,6 +302,60 @@ extern "C" int kspider_query(const char* db, const char* queries, int kSize, con
         if (std::getenv("KSPIDER_VERBOSE"))
             std::cout << "kspider_amd: query: " << st.n_q << " queries against " << st.n_db << " database sources, " << st.passes << " passes, " << n_edges
                       << " rows; table " << st.ms_table << " ms, probe " << st.ms_probe << " ms" << std::endl;
+        return (int)KSP_OK;
+    });
+}
+
+extern "C" int kspider_gather(const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, uint32_t min_hashes, uint32_t max_matches) {
+    const char* who = "kspider_gather";
+    if (!db || !queries || !out_prefix || !*out_prefix) { ksp::set_error(std::string(who) + ": db, queries and out_prefix are required"); return KSP_E_ARG; }
+    if (kSize < 0) { ksp::set_error(std::string(who) + ": kSize is the signatures' ksize, or 0 for .bin sketches"); return KSP_E_ARG; }
+    if (min_hashes == 0) { ksp::set_error(std::string(who) + ": min_hashes is 1 or more"); return KSP_E_ARG; }
+    return guarded(who, [&]() {
+        const int threads = user_threads < 1 ? 1 : user_threads;
+        ksp::SketchSet side[2];
+        load_side(db, kSize, threads, side[0]);
+        load_side(queries, kSize, threads, side[1]);
+        // source s of a side is its s-th group that has a sketch
+        std::vector<uint64_t> group_of[2];
+        for (int s = 0; s < 2; ++s)
+            for (uint64_t g = 0; g < side[s].names.size(); ++g)
+                if (side[s].present[g]) group_of[s].push_back(g);
+        if (group_of[0].empty() || group_of[1].empty()) throw ArgError(group_of[0].empty() ? "the database has no sketch" : "there is no query sketch");
+        if (group_of[0].size() + group_of[1].size() > 0xFFFFFFFEull) throw std::runtime_error("more than 2^32 - 2 groups");
+        ksp_gather_row* rows = nullptr;
+        uint64_t n_rows = 0;
+        ksp_gather_stats st;
+        const char* dv = std::getenv("KSPIDER_DEVICE");
+        const int rc = ksp_gather_host(side[0].keys.data(), side[0].offsets.data(), (uint32_t)group_of[0].size(), side[1].keys.data(), side[1].offsets.data(),
+                                       (uint32_t)group_of[1].size(), min_hashes, max_matches, dv ? std::atoi(dv) : 0, &rows, &n_rows, &st);
+        if (rc != KSP_OK) return rc;
+        // the file only now: a refused or failed call leaves none
+        std::string text = "query\trank\tmatch\toverlap\tunique\tf_orig_query\tf_unique_to_query\tf_match\tremaining\n";
+        char buf[32];
+        for (uint64_t i = 0; i < n_rows; ++i) {
+            const ksp_gather_row& r = rows[i];
+            const float q_size = (float)(side[1].offsets[r.query + 1] - side[1].offsets[r.query]), s_size = (float)(side[0].offsets[r.source + 1] - side[0].offsets[r.source]);
+            text += side[1].names[group_of[1][r.query]] + "\t" + std::to_string(r.rank) + "\t" + side[0].names[group_of[0][r.source]] + "\t" + std::to_string(r.overlap) + "\t" +
+                    std::to_string(r.unique);
+            for (const float v : {(float)r.overlap / q_size, (float)r.unique / q_size, (float)r.overlap / s_size}) {
+                text += "\t";
+                text.append(buf, (size_t)ksp::format_float(buf, v));
+            }
+            text += "\t" + std::to_string(r.remaining) + "\n";
+        }
+        ksp_free(rows);
+        {
+            std::ofstream f;
+            ksp::PartialFiles files;
+            files.open(std::string(out_prefix) + "_kSpider_gather.tsv", f);
+            f.write(text.data(), (std::streamsize)text.size());
+            files.commit();
+        }
+        if (std::getenv("KSPIDER_VERBOSE"))
+            std::cout << "kspider_amd: gather: " << st.n_q << " queries against " << st.n_db << " database sources, " << st.passes << " passes, " << st.candidates
+                      << " candidates, " << st.rounds << " rounds (" << st.tail_rounds << " in the tail), " << n_rows << " rows; table " << st.ms_table << " ms, candidates "
+                      << st.ms_candidates << " ms, fill " << st.ms_fill << " ms, rounds " << st.ms_rounds << " ms" << std::endl;
         return (int)KSP_OK;
     });
 }

@@ -66,6 +66,14 @@ QUERY_LIST_MAX = 512
 QUERY_LONG_RUN = 2048
 QUERY_DIR_BITS_MAX = 24
 
+#: gather (include/kspider_amd.h KSP_GATHER_*): rounds per batch, the default switches, the row record
+GATHER_BATCH = 16
+GATHER_LONG_SEG = 1024
+GATHER_TAIL_CANDS = 256
+GATHER_TAIL_CANDS_MAX = 1 << 20
+GATHER_ROW_DTYPE = np.dtype([("query", np.uint32), ("rank", np.uint32), ("source", np.uint32), ("overlap", np.uint32), ("unique", np.uint32),
+                             ("remaining", np.uint32)])
+
 #: ksp_engine_lists_path / Engine.lists_path
 LISTS_NONE, LISTS_KEYED, LISTS_COMPACTED, LISTS_SORTED, LISTS_FUSED = 0, 1, 2, 3, 4
 
@@ -98,6 +106,7 @@ ABI_SYMBOLS = [
     "ksp_edges_upgma", "ksp_upgma_valued", "ksp_upgma_before", "kspider_upgma", "kspider_pairwise_and_upgma", "kspider_cluster_from_upgma",
     "ksp_edges_tsv",
     "ksp_query_device", "ksp_query_host", "ksp_query_directory", "kspider_pack", "ksp_pack_info", "ksp_pack_load", "kspider_query",
+    "ksp_gather_device", "ksp_gather_host", "kspider_gather",
 ]
 
 
@@ -128,6 +137,22 @@ class QueryStats(ctypes.Structure):
         ("edges", ctypes.c_uint64), ("long_run", ctypes.c_uint64),
         ("ms_table", ctypes.c_float), ("ms_probe", ctypes.c_float), ("ms_sort", ctypes.c_float),
         ("tile", ctypes.c_uint32), ("list_capacity", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class GatherStats(ctypes.Structure):
+    """ksp_gather_stats (include/kspider_amd.h)."""
+    _fields_ = [
+        ("n_db", ctypes.c_uint64), ("n_q", ctypes.c_uint64), ("db_entries", ctypes.c_uint64), ("q_entries", ctypes.c_uint64),
+        ("table_keys", ctypes.c_uint64), ("table_holders", ctypes.c_uint64), ("passes", ctypes.c_uint64),
+        ("candidates", ctypes.c_uint64), ("dropped", ctypes.c_uint64), ("fell_below", ctypes.c_uint64), ("slots", ctypes.c_uint64),
+        ("rounds", ctypes.c_uint64), ("batches", ctypes.c_uint64), ("tail_rounds", ctypes.c_uint64), ("live_at_tail", ctypes.c_uint64),
+        ("rows", ctypes.c_uint64), ("long_seg", ctypes.c_uint64), ("tail_cands", ctypes.c_uint64),
+        ("ms_table", ctypes.c_float), ("ms_candidates", ctypes.c_float), ("ms_fill", ctypes.c_float), ("ms_rounds", ctypes.c_float),
+        ("tile", ctypes.c_uint32), ("min_hashes", ctypes.c_uint32), ("max_matches", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
     ]
 
     def as_dict(self):
@@ -314,6 +339,11 @@ def lib():
         L.ksp_pack_info.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
         L.ksp_pack_load.argtypes = [ctypes.c_char_p] + [ctypes.c_void_p] * 6
         L.kspider_query.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]
+        L.ksp_gather_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                        ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_gather_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                      ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.kspider_gather.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]
         _lib = L
     return _lib
 
@@ -985,6 +1015,50 @@ def query(db: str, queries: str, kSize: int, out_prefix: str, user_threads: int 
     """New sketches against a database (kspider_query): db and queries are each a pack file or a directory; writes OUT.namesMap,
     OUT_kSpider_seqToKmersNo.tsv and OUT_kSpider_pairwise.tsv with only the rows of the mode."""
     _check(lib().kspider_query(os.fsencode(db), os.fsencode(queries), int(kSize), os.fsencode(out_prefix) if out_prefix else None, int(user_threads), int(mode)))
+
+
+def gather_host(db_keys, db_offsets, q_keys, q_offsets, min_hashes: int = 1, max_matches: int = 0, device: int = 0):
+    """What every query is made of (ksp_gather_host): host sketches of a database and of queries -> (rows ordered by (query, rank),
+    stats).  A row (GATHER_ROW_DTYPE) names the database source that covers most of what is left of the query, its overlap with the
+    whole query, the hashes it was the first to cover (unique) and what remains after it; a source is reported while unique is at
+    least min_hashes; max_matches caps the rows per query (0: no cap).  None stands for a NULL pointer (refused by the C side)."""
+    def arr(a):
+        return None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
+    dk, do, qk, qo = arr(db_keys), arr(db_offsets), arr(q_keys), arr(q_offsets)
+    out = ctypes.c_void_p()
+    nr = ctypes.c_uint64(0)
+    st = GatherStats()
+    _check(lib().ksp_gather_host(_ptr(dk), _ptr(do), 0 if do is None else max(do.size - 1, 0), _ptr(qk), _ptr(qo), 0 if qo is None else max(qo.size - 1, 0),
+                                 int(min_hashes), int(max_matches), int(device), ctypes.byref(out), ctypes.byref(nr), ctypes.byref(st)))
+    try:
+        buf = (ctypes.c_char * (nr.value * GATHER_ROW_DTYPE.itemsize)).from_address(out.value) if nr.value else b""
+        rows = np.frombuffer(buf, dtype=GATHER_ROW_DTYPE).copy()
+    finally:
+        lib().ksp_free(out)
+    return rows, st.as_dict()
+
+
+def gather_device(d_db_keys_ptr: int, db_offsets, d_q_keys_ptr: int, q_offsets, d_rows_ptr: int, capacity: int, min_hashes: int = 1, max_matches: int = 0,
+                  device: int = 0) -> tuple:
+    """ksp_gather_device: keys in DEVICE memory, offsets on the host, rows into d_rows (room for `capacity`; 0 / 0: the size query).
+    -> (rc, n_rows, stats): rc is KSP_OK or KSP_E_OVERFLOW (n_rows is then the required size); anything else raises."""
+    do = None if db_offsets is None else np.ascontiguousarray(db_offsets, dtype=np.uint64)
+    qo = None if q_offsets is None else np.ascontiguousarray(q_offsets, dtype=np.uint64)
+    nr = ctypes.c_uint64(0)
+    st = GatherStats()
+    rc = lib().ksp_gather_device(int(device), d_db_keys_ptr or None, _ptr(do), 0 if do is None else max(do.size - 1, 0), d_q_keys_ptr or None, _ptr(qo),
+                                 0 if qo is None else max(qo.size - 1, 0), int(min_hashes), int(max_matches), d_rows_ptr or None, int(capacity), ctypes.byref(nr),
+                                 ctypes.byref(st))
+    if rc not in (KSP_OK, KSP_E_OVERFLOW):
+        _check(rc)
+    return rc, nr.value, st.as_dict()
+
+
+def gather(db: str, queries: str, kSize: int, out_prefix: str, user_threads: int = 1, min_hashes: int = 1, max_matches: int = 0) -> None:
+    """What every query sketch is made of (kspider_gather): db and queries are each a pack file or a directory; writes
+    OUT_kSpider_gather.tsv."""
+    _check(lib().kspider_gather(os.fsencode(db), os.fsencode(queries), int(kSize), os.fsencode(out_prefix) if out_prefix else None, int(user_threads),
+                                int(min_hashes), int(max_matches)))
 
 
 def cluster_from_tree(index_prefix: str, dist_type: str = "max_cont", cutoff: float = 0.0) -> None:

@@ -254,3 +254,15 @@ def from_runs(runs, name: str = "custom") -> SketchSet:
         offsets[1:] = np.cumsum([r.size for r in rs], dtype=np.uint64)
     keys = np.concatenate(rs).astype(np.uint64) if rs else np.zeros(0, dtype=np.uint64)
     return SketchSet(keys, offsets, np.zeros(len(rs), dtype=np.int32), name)
+
+
+def gather_sample(sk: SketchSet, n_pick: int, n_noise: int, seed: int = 1) -> np.ndarray:
+    """A synthetic metagenome for gather: the union of a random half of each of ``n_pick`` random sources of ``sk`` plus ``n_noise``
+    hashes that (almost surely) no source holds; strictly ascending."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for s in rng.choice(sk.n_sources, size=min(n_pick, sk.n_sources), replace=False):
+        run = sk.run(int(s))
+        parts.append(rng.choice(run, size=run.size // 2, replace=False))
+    parts.append(rng.integers(0, 2**63, size=n_noise, dtype=np.uint64) | np.uint64(1 << 63))
+    return np.unique(np.concatenate(parts).astype(np.uint64))
