@@ -951,6 +951,82 @@ int ksp_gather_host(const uint64_t* db_keys, const uint64_t* db_offsets, uint32_
 int kspider_gather(const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, uint32_t min_hashes,
                    uint32_t max_matches);
 
+/* ---- sketching: FASTA / FASTQ in, sourmash-compatible DNA FracMinHash sketches out (csrc/sketch_hash.h, csrc/sketcher.hip,
+ *      csrc/sketch_cpu.cpp, csrc/fastx_reader.cpp, csrc/sketch_files.cpp) ----
+ * The definition.  Bytes ACGTacgt are bases, lower case counts as upper case; every other byte value breaks k-mers.  A k-mer is
+ * ksize (1 .. 64) consecutive bases inside one source; its canonical form is the smaller, as text, of its upper-case letters and
+ * their reverse complement; its hash is the first word of MurmurHash3_x64_128 over the ksize letters of the canonical form with
+ * `seed` (sourmash: 42); it is kept iff hash <= max_hash.  A source's sketch is the ascending list of its distinct kept hashes.
+ * The input of the compute calls is a byte stream and src_offsets[n_sources + 1] (ascending from 0 to n_bytes): source s is the
+ * bytes [src_offsets[s], src_offsets[s + 1]).  Records inside a source are separated by any non-base byte.
+ * ksp_sketch_max_hash: host only — sourmash's threshold of `scaled`: 2^64 - 1 for 1, (uint64_t)(2^64 / (double)scaled) above;
+ *   KSP_E_ARG for 0.
+ * ksp_murmur64: host only — both words of MurmurHash3_x64_128 over any bytes (data may be NULL with len 0).
+ * ksp_sketch_kmer_hash: host only — the hash of the k-mer spelled by `ksize` bytes of text; *valid = 0 (and *hash = 0) when a
+ *   byte is not a base.
+ * ksp_sketch_cpu: host only — the plain single-thread loop: out_keys (room for `capacity`) receives the sketches back to back,
+ *   out_offsets[n_sources + 1] their bounds, *needed = the keys of all sketches.  More than `capacity`: KSP_E_OVERFLOW with
+ *   *needed and the offsets set and nothing written to out_keys; out_keys NULL with capacity 0 is the size query.
+ * ksp_sketch_device: d_seq (16-byte aligned) and d_out_keys (room for `capacity`) are DEVICE memory, the offsets are on the
+ *   host.  `capacity` must hold the survivors — the kept k-mers before duplicates are dropped —, whose number comes back in
+ *   stats->needed: more than `capacity` is KSP_E_OVERFLOW, with stats->needed exact and nothing written to d_out_keys or
+ *   h_out_offsets; d_out_keys NULL with capacity 0 is the size query.  One hash pass over the bytes (workgroups of 256 loop over
+ *   tiles of KSP_SKETCH_TILE_BASES positions; $KSPIDER_SKETCH_MAX_WGS caps the grid), then the select pass: survivors sorted by
+ *   (source, hash), adjacent duplicates dropped, per-source offsets.  The result does not depend on scheduling.  Takes max_hash,
+ *   not scaled, so that the threshold can be tested at an exact value.  KSP_E_ARG, before a device is chosen: a NULL pointer,
+ *   ksize outside 1 .. 64, n_sources = 0, offsets that do not start at 0, decrease or do not end at n_bytes, a d_seq that is not
+ *   16-byte aligned.  KSP_E_LIMIT when the memory asked for (40 bytes per survivor of `capacity`, the sort's scratch, 16 per
+ *   source) does not fit the device's free memory; nothing has run then.
+ * ksp_sketch_host: the same for HOST arrays: uploads, calls, retries once at the exact size on overflow, and returns the keys in
+ *   *out_keys (ksp_free).  $KSPIDER_SKETCH_FIRST_CAPACITY: the first call's capacity (tests: forces the retry).  A device that is
+ *   not there: KSP_E_HIP, "ksp_sketch_host: no such device".
+ * ksp_fastx_info / ksp_fastx_load: host only, two calls — the FASTA / FASTQ reader (plain or gzip; wrapped lines, CRLF, empty
+ *   records, a missing final newline; FASTQ by its 4-line structure).  info: out[0] records, out[1] bytes of seq, out[2] bytes of
+ *   the names, out[3] 0 FASTA / 1 FASTQ.  load: seq = every record's bases as they stand in the file followed by one '\n',
+ *   rec_offsets[records + 1] their bounds, names = every header's first word back to back, name_offsets[records + 1].  KSP_E_IO,
+ *   naming the file and the line, for a file that is neither, a FASTQ record cut short or with a quality line of another length,
+ *   and a truncated or corrupt gzip.
+ * kspider_sketch: the file driver.  input: a directory (its files ending in .fa .fasta .fna .fq .fastq, each optionally .gz, in
+ *   the glob order of the sig loader, each one source named by the file without those endings), or one file, whose records are
+ *   each a source named by the header's first word with KSP_SKETCH_PER_RECORD in flags and one source otherwise.  Writes
+ *   out_dir/<name>.sig per source (out_dir is created): the fields of a sourmash signature file with one signature {num 0, ksize,
+ *   seed, max_hash, molecule "DNA", md5sum, mins}; md5sum is the MD5 of the decimal text of ksize followed by the decimal text of
+ *   every min, without separators.  seed: flags >> 32 when KSP_SKETCH_SEED is set, else 42.  Files are read by user_threads
+ *   threads and sent in batches of at most $KSPIDER_SKETCH_BATCH_MB (256; $KSPIDER_SKETCH_BATCH_BYTES: the same in bytes, at
+ *   least 1024) through pinned staging, the next batch being read while the device hashes; a source may span batches, a record
+ *   longer than a batch is cut with ksize - 1 bytes of overlap, and the result does not depend on the batch size.
+ *   KSPIDER_SKETCH=host runs the same driver over ksp_sketch_cpu: the same bytes, no GPU.  Works with $KSPIDER_DEVICE.
+ *   KSP_E_ARG: NULL or empty input / out_dir, ksize outside 1 .. 64, scaled = 0, two sources of one name; KSP_E_IO: no input
+ *   file, a reader error, a file that cannot be written.                                                                    */
+#define KSP_SKETCH_TILE_BASES 4096u
+#define KSP_SKETCH_PER_RECORD 1ull
+#define KSP_SKETCH_SEED 2ull
+typedef struct ksp_sketch_stats {
+    uint64_t bases;            /* base bytes of the stream                                                        */
+    uint64_t valid_kmers;      /* windows of ksize bases without a break byte (one over a source boundary that no
+                                  break byte marks is counted here and dropped when it is attributed)              */
+    uint64_t kept;             /* survivors: windows with hash <= max_hash that lie inside a source                */
+    uint64_t distinct_out;     /* keys of all sketches                                                            */
+    uint64_t needed;           /* the capacity the call needs: = kept                                             */
+    uint64_t workgroups;       /* the hash pass's grid                                                            */
+    uint64_t retries;          /* ksp_sketch_host: 1 when the first capacity overflowed                           */
+    float ms_upload, ms_hash, ms_select;   /* HIP-event times (upload: ksp_sketch_host only)                       */
+    uint32_t reserved;
+} ksp_sketch_stats;   /* 72 bytes */
+int ksp_sketch_max_hash(uint64_t scaled, uint64_t* out);
+int ksp_murmur64(const void* data, uint64_t len, uint32_t seed, uint64_t out[2]);
+int ksp_sketch_kmer_hash(const char* text, int ksize, uint32_t seed, uint64_t* hash, int* valid);
+int ksp_sketch_cpu(const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize, uint64_t max_hash,
+                   uint32_t seed, uint64_t* out_keys, uint64_t capacity, uint64_t* out_offsets, uint64_t* needed);
+int ksp_sketch_device(int device, const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* h_src_offsets, uint32_t n_sources, int ksize,
+                      uint64_t max_hash, uint32_t seed, uint64_t* d_out_keys, uint64_t capacity, uint64_t* h_out_offsets,
+                      ksp_sketch_stats* stats);
+int ksp_sketch_host(int device, const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize,
+                    uint64_t max_hash, uint32_t seed, uint64_t** out_keys, uint64_t* out_offsets, ksp_sketch_stats* stats);
+int ksp_fastx_info(const char* path, uint64_t out[4]);
+int ksp_fastx_load(const char* path, uint8_t* seq, uint64_t* rec_offsets, uint64_t* name_offsets, char* names);
+int kspider_sketch(const char* input, int kSize, uint64_t scaled, const char* out_dir, int user_threads, uint64_t flags);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

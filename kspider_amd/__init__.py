@@ -13,6 +13,7 @@ Host-side mirror of the reference interface for this one path:
   kspider_amd.query(db, queries, kSize, out_prefix, threads, mode)  new sketches against a database, without the N x N join
   kspider_amd.gather(db, queries, kSize, out_prefix, threads, min_hashes, max_matches)  what each query is made of: greedy set cover
   kspider_amd.pack(sketch_dir, kSize, out_path, threads)  a directory of sketches as one database file
+  kspider_amd.sketch_files(input, kSize, scaled, out_dir, threads)  FASTA / FASTQ in, sourmash-compatible .sig files out, hashed on the GPU
   kspider_amd.engine                                   ctypes binding of include/kspider_amd.h
   kspider_amd.dist                                     tile sharding + edge gather for one-process-per-GPU runs
   kspider_amd.synth                                    synthetic sketch sets shaped like BASELINE.json's configs
@@ -27,10 +28,12 @@ from .engine import single_linkage_rows  # noqa: F401
 from .engine import CUT_CHUNK_EDGES, edges_cut, pairwise_cut, pairwise_host_cut  # noqa: F401
 from .engine import QUERY_CROSS, QUERY_CROSS_AND_SELF, pack, query  # noqa: F401
 from .engine import GATHER_ROW_DTYPE, GatherStats, gather, gather_device, gather_host  # noqa: F401
+from .engine import SketchStats, sketch_cpu, sketch_device, sketch_files, sketch_host, sketch_max_hash  # noqa: F401
 
 __all__ = ["pairwise", "pairwise_sigs", "pairwise_bins", "cluster", "estimate_ani", "pairwise_ani", "export",
            "query", "pack", "QUERY_CROSS", "QUERY_CROSS_AND_SELF",
            "gather", "gather_host", "gather_device", "GatherStats", "GATHER_ROW_DTYPE",
+           "sketch_files", "sketch_host", "sketch_device", "sketch_cpu", "sketch_max_hash", "SketchStats",
            "single_linkage_rows", "pairwise_cut", "pairwise_host_cut", "edges_cut", "CUT_CHUNK_EDGES",
            "cluster_sweep", "pairwise_and_cluster_sweep",
            "tree", "pairwise_and_tree", "cluster_from_tree", "edges_forest", "forest_ranked", "TREE_CHUNK_EDGES"]

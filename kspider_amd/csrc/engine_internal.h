@@ -207,6 +207,24 @@ struct AfterJoin {
 int pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources, const uint32_t* key_weights, uint32_t n_keys,
                                uint32_t n_sources, const int* devices, int n_devices, ksp_edge** out_edges, uint64_t* n_edges,
                                ksp_stats* stats, AfterJoin* after);
+// ---- sketching (sketch_cpu.cpp, sketcher.hip, fastx_reader.cpp, sketch_files.cpp) ----
+// what ksp_sketch_cpu / _device / _host refuse with KSP_E_ARG: a NULL pointer, ksize outside 1 .. 64, no source, offsets that do
+// not start at 0, decrease or do not end at n_bytes
+int check_sketch_args(const char* who, const void* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize);
+// page-locked host memory for the batches of the file driver (sketcher.hip; NULL when it cannot be had)
+void* pinned_alloc(size_t bytes);
+void pinned_free(void* p);
+// a file, gzip or plain, whole (sketch_loaders.cpp; throws std::runtime_error naming the file)
+std::string read_maybe_gz(const std::string& path);
+// One FASTA / FASTQ file (fastx_reader.cpp; throws std::runtime_error naming the file and the line): seq = every record's bases
+// as they stand in the file followed by one '\n', rec_off[records + 1] their bounds, names = every header's first word.
+struct FastxFile {
+    std::string seq;
+    std::vector<uint64_t> rec_off;
+    std::vector<std::string> names;
+    bool fastq = false;
+};
+void read_fastx(const std::string& path, FastxFile& out);
 }
 
 extern "C" {

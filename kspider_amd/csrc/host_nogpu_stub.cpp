@@ -33,6 +33,8 @@ void write_topk_file(const std::string&, const std::string&, const std::vector<s
 void write_report_files(const std::string&, const std::string&, double, const std::vector<ksp_cluster_row>&, const std::vector<ksp_member_row>&,
                         const std::vector<std::string>&, const std::vector<std::string>&) {}
 void write_upgma_files(const std::string&, const std::string&, const std::vector<ksp_upgma_row>&, const std::vector<std::string>&, bool) {}
+void* pinned_alloc(size_t bytes) { return std::malloc(bytes ? bytes : 1); }
+void pinned_free(void* p) { std::free(p); }
 }  // namespace ksp
 
 extern "C" {
@@ -113,6 +115,10 @@ int ksp_gather_host(const uint64_t*, const uint64_t*, uint32_t, const uint64_t*,
 }
 int ksp_gather_device(int, const uint64_t*, const uint64_t*, uint32_t, const uint64_t*, const uint64_t*, uint32_t, uint32_t, uint32_t, ksp_gather_row*, uint64_t, uint64_t*,
                       ksp_gather_stats*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_sketch_host(int, const uint8_t*, uint64_t, const uint64_t*, uint32_t, int, uint64_t, uint32_t, uint64_t**, uint64_t*, ksp_sketch_stats*) {
     ksp::set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }

@@ -1,0 +1,425 @@
+// The file driver of the sketcher: FASTA / FASTQ files in, one sourmash-compatible .sig file per source out.
+// Host only; the device part is ksp_sketch_host (sketcher.hip), the host mode's ksp_sketch_cpu (sketch_cpu.cpp).
+//   feed     the input files in order, read `threads` at a time (fastx_reader.cpp); what is read and not yet sent waits as pieces
+//   batch    at most `batch_bytes` bytes of pieces back to back, each a segment of one source.  A piece that does not fit is cut:
+//            the batch takes what it has room for, and the rest starts ksize - 1 bytes before the cut, so every window of ksize
+//            bytes lies whole in one of the two.  A source's sketch is the union of its segments' sketches.
+//   pipeline two batch buffers (page-locked in device mode): the next one is filled by a thread while this one is hashed
+//   write    the signatures at the end, each through .partial and a rename
+#include <glob.h>
+#include <sys/stat.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cerrno>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <exception>
+#include <iostream>
+#include <memory>
+#include <mutex>
+#include <set>
+#include <stdexcept>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/kspider_amd.h"
+#include "engine_internal.h"
+#include "partial_file.h"
+
+namespace {
+
+// ---- MD5 (RFC 1321) of a text handed over in pieces ----
+class Md5 {
+    uint32_t a_ = 0x67452301u, b_ = 0xefcdab89u, c_ = 0x98badcfeu, d_ = 0x10325476u;
+    uint64_t bytes_ = 0;
+    unsigned char buf_[64];
+
+    static uint32_t rotl(const uint32_t x, const int s) { return (x << s) | (x >> (32 - s)); }
+    void block(const unsigned char* p) {
+        static const uint32_t K[64] = {
+            0xd76aa478, 0xe8c7b756, 0x242070db, 0xc1bdceee, 0xf57c0faf, 0x4787c62a, 0xa8304613, 0xfd469501, 0x698098d8, 0x8b44f7af, 0xffff5bb1,
+            0x895cd7be, 0x6b901122, 0xfd987193, 0xa679438e, 0x49b40821, 0xf61e2562, 0xc040b340, 0x265e5a51, 0xe9b6c7aa, 0xd62f105d, 0x02441453,
+            0xd8a1e681, 0xe7d3fbc8, 0x21e1cde6, 0xc33707d6, 0xf4d50d87, 0x455a14ed, 0xa9e3e905, 0xfcefa3f8, 0x676f02d9, 0x8d2a4c8a, 0xfffa3942,
+            0x8771f681, 0x6d9d6122, 0xfde5380c, 0xa4beea44, 0x4bdecfa9, 0xf6bb4b60, 0xbebfbc70, 0x289b7ec6, 0xeaa127fa, 0xd4ef3085, 0x04881d05,
+            0xd9d4d039, 0xe6db99e5, 0x1fa27cf8, 0xc4ac5665, 0xf4292244, 0x432aff97, 0xab9423a7, 0xfc93a039, 0x655b59c3, 0x8f0ccc92, 0xffeff47d,
+            0x85845dd1, 0x6fa87e4f, 0xfe2ce6e0, 0xa3014314, 0x4e0811a1, 0xf7537e82, 0xbd3af235, 0x2ad7d2bb, 0xeb86d391};
+        static const int S[64] = {7, 12, 17, 22, 7, 12, 17, 22, 7, 12, 17, 22, 7, 12, 17, 22, 5, 9, 14, 20, 5, 9, 14, 20, 5, 9, 14, 20, 5, 9, 14, 20,
+                                  4, 11, 16, 23, 4, 11, 16, 23, 4, 11, 16, 23, 4, 11, 16, 23, 6, 10, 15, 21, 6, 10, 15, 21, 6, 10, 15, 21, 6, 10, 15, 21};
+        uint32_t m[16];
+        for (int i = 0; i < 16; ++i) m[i] = (uint32_t)p[4 * i] | (uint32_t)p[4 * i + 1] << 8 | (uint32_t)p[4 * i + 2] << 16 | (uint32_t)p[4 * i + 3] << 24;
+        uint32_t a = a_, b = b_, c = c_, d = d_;
+        for (int i = 0; i < 64; ++i) {
+            uint32_t f;
+            int g;
+            if (i < 16) { f = (b & c) | (~b & d); g = i; }
+            else if (i < 32) { f = (d & b) | (~d & c); g = (5 * i + 1) & 15; }
+            else if (i < 48) { f = b ^ c ^ d; g = (3 * i + 5) & 15; }
+            else { f = c ^ (b | ~d); g = (7 * i) & 15; }
+            const uint32_t t = d;
+            d = c;
+            c = b;
+            b = b + rotl(a + f + K[i] + m[g], S[i]);
+            a = t;
+        }
+        a_ += a; b_ += b; c_ += c; d_ += d;
+    }
+
+public:
+    void add(const char* p, size_t n) {
+        while (n) {
+            const size_t fill = (size_t)(bytes_ & 63), take = std::min<size_t>(n, 64 - fill);
+            std::memcpy(buf_ + fill, p, take);
+            bytes_ += take; p += take; n -= take;
+            if (((bytes_) & 63) == 0) block(buf_);
+        }
+    }
+    std::string hex() {
+        const uint64_t bits = bytes_ * 8;
+        const char one = (char)0x80, zero = 0;
+        add(&one, 1);
+        while ((bytes_ & 63) != 56) add(&zero, 1);
+        unsigned char len[8];
+        for (int i = 0; i < 8; ++i) len[i] = (unsigned char)(bits >> (8 * i));
+        add((const char*)len, 8);
+        static const char* digits = "0123456789abcdef";
+        std::string out;
+        for (const uint32_t w : {a_, b_, c_, d_})
+            for (int i = 0; i < 4; ++i) {
+                const unsigned byte = (w >> (8 * i)) & 0xFF;
+                out += digits[byte >> 4];
+                out += digits[byte & 15];
+            }
+        return out;
+    }
+};
+
+// what a guarded entry throws for a bad argument (KSP_E_ARG instead of KSP_E_IO)
+struct ArgError : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+// a compute call failed: its code, the text is already in ksp_last_error()
+struct CallError {
+    int rc;
+};
+
+bool is_directory(const std::string& path) {
+    struct stat st;
+    return stat(path.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
+}
+std::string base_name(const std::string& path) { return path.substr(path.find_last_of("/\\") + 1); }
+bool ends_with(const std::string& s, const std::string& e) { return s.size() >= e.size() && s.compare(s.size() - e.size(), e.size(), e) == 0; }
+
+// the file name without .gz and without its FASTA / FASTQ ending; "" when it has none of the endings
+std::string source_name_of(const std::string& path) {
+    std::string n = base_name(path);
+    if (ends_with(n, ".gz")) n.resize(n.size() - 3);
+    for (const char* e : {".fa", ".fasta", ".fna", ".fq", ".fastq"})
+        if (ends_with(n, e) && n.size() > std::strlen(e)) return n.substr(0, n.size() - std::strlen(e));
+    return "";
+}
+
+std::string json_text(const std::string& s) {
+    std::string out = "\"";
+    char buf[8];
+    for (const unsigned char c : s) {
+        if (c == '"' || c == '\\') { out += '\\'; out += (char)c; }
+        else if (c < 0x20) { std::snprintf(buf, sizeof buf, "\\u%04x", c); out += buf; }
+        else out += (char)c;
+    }
+    return out + "\"";
+}
+
+// the signature file of one source: the fields of the files sourmash writes, in a fixed order
+std::string sig_text(const std::string& filename, const int ksize, const uint32_t seed, const uint64_t max_hash, const std::vector<uint64_t>& mins) {
+    std::string list;
+    Md5 md5;
+    char num[24];
+    int n = std::snprintf(num, sizeof num, "%d", ksize);
+    md5.add(num, (size_t)n);
+    for (size_t i = 0; i < mins.size(); ++i) {
+        n = std::snprintf(num, sizeof num, "%llu", (unsigned long long)mins[i]);
+        md5.add(num, (size_t)n);
+        if (i) list += ',';
+        list.append(num, (size_t)n);
+    }
+    return "[{\"class\":\"sourmash_signature\",\"email\":\"\",\"hash_function\":\"0.murmur64\",\"filename\":" + json_text(filename) +
+           ",\"license\":\"CC0\",\"version\":0.4,\"signatures\":[{\"num\":0,\"ksize\":" + std::to_string(ksize) + ",\"seed\":" + std::to_string(seed) +
+           ",\"max_hash\":" + std::to_string(max_hash) + ",\"molecule\":\"DNA\",\"md5sum\":\"" + md5.hex() + "\",\"mins\":[" + list + "]}]}]\n";
+}
+
+// fn(i) for i in [0, n) on up to `threads` host threads; the first exception is rethrown on the caller
+template <class Fn>
+void parallel_for(const size_t n, const int threads, Fn fn) {
+    const size_t nt = std::max<size_t>(1, std::min<size_t>({(size_t)std::max(1, threads), n, 64}));
+    if (nt <= 1) { for (size_t i = 0; i < n; ++i) fn(i); return; }
+    std::atomic<size_t> next{0};
+    std::exception_ptr err;
+    std::mutex mu;
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < nt; ++t)
+        th.emplace_back([&]() {
+            try {
+                for (size_t i = next.fetch_add(1); i < n; i = next.fetch_add(1)) fn(i);
+            } catch (...) {
+                std::lock_guard<std::mutex> g(mu);
+                if (!err) err = std::current_exception();
+            }
+        });
+    for (auto& t : th) t.join();
+    if (err) std::rethrow_exception(err);
+}
+
+// bytes of one source that are read and not yet in a batch
+struct Piece {
+    uint32_t source;
+    std::shared_ptr<const std::string> text;
+    size_t at, end;
+};
+
+// one batch: segments of sources back to back
+struct Batch {
+    uint8_t* buf = nullptr;
+    size_t n_bytes = 0;
+    std::vector<uint64_t> off{0};    // the segments' bounds
+    std::vector<uint32_t> source;    // the source of every segment
+    void clear() { n_bytes = 0; off.assign(1, 0); source.clear(); }
+};
+
+// The input in order.  Only one thread at a time calls fill().
+class Feed {
+    std::vector<std::string> files_;
+    size_t next_file_ = 0;
+    bool per_record_;
+    int threads_;
+    size_t batch_bytes_, overlap_;
+    std::deque<Piece> pieces_;
+
+    void read_more() {
+        const size_t n = std::min<size_t>((size_t)std::max(1, threads_), files_.size() - next_file_);
+        std::vector<ksp::FastxFile> read(n);
+        parallel_for(n, threads_, [&](const size_t i) { ksp::read_fastx(files_[next_file_ + i], read[i]); });
+        for (size_t i = 0; i < n; ++i) {
+            const std::string& path = files_[next_file_ + i];
+            ksp::FastxFile& f = read[i];
+            const size_t n_rec = f.names.size();
+            const auto text = std::make_shared<const std::string>(std::move(f.seq));
+            if (per_record_) {
+                for (size_t r = 0; r < n_rec; ++r) {
+                    std::string name = f.names[r];
+                    std::replace(name.begin(), name.end(), '/', '_');
+                    names.push_back(name);
+                    filenames.push_back(base_name(path));
+                    pieces_.push_back(Piece{(uint32_t)(names.size() - 1), text, (size_t)f.rec_off[r], (size_t)f.rec_off[r + 1]});
+                }
+            } else {
+                const std::string by_ending = source_name_of(path);
+                names.push_back(by_ending.empty() ? base_name(path) : by_ending);
+                filenames.push_back(base_name(path));
+                pieces_.push_back(Piece{(uint32_t)(names.size() - 1), text, 0, text->size()});
+            }
+            if (names.size() > 0xFFFFFFFEull) throw std::runtime_error("more than 2^32 - 2 sources");
+        }
+        next_file_ += n;
+    }
+
+public:
+    std::vector<std::string> names, filenames;   // of every source met so far (read by the caller only after the last fill())
+
+    Feed(std::vector<std::string> files, const bool per_record, const int threads, const size_t batch_bytes, const int ksize)
+        : files_(std::move(files)), per_record_(per_record), threads_(threads), batch_bytes_(batch_bytes), overlap_((size_t)ksize - 1) {}
+
+    // the next batch; false when the input is used up and the batch is empty
+    bool fill(Batch& b) {
+        b.clear();
+        for (;;) {
+            if (pieces_.empty()) {
+                if (next_file_ >= files_.size()) break;
+                read_more();
+                continue;
+            }
+            Piece& p = pieces_.front();
+            const size_t left = p.end - p.at, room = batch_bytes_ - b.n_bytes;
+            if (left == 0) { pieces_.pop_front(); continue; }
+            if (left > room && room <= 2 * overlap_ + 16) break;   // too little room to cut into: the batch is full
+            const size_t take = std::min(left, room);
+            std::memcpy(b.buf + b.n_bytes, p.text->data() + p.at, take);
+            b.n_bytes += take;
+            b.off.push_back(b.n_bytes);
+            b.source.push_back(p.source);
+            if (take == left) { pieces_.pop_front(); continue; }
+            p.at += take - overlap_;   // the rest starts ksize - 1 bytes before the cut
+            break;
+        }
+        return b.n_bytes > 0 || !pieces_.empty() || next_file_ < files_.size();
+    }
+};
+
+std::vector<std::string> input_files(const std::string& input) {
+    if (!is_directory(input)) return {input};
+    std::string dir = input;
+    while (dir.size() > 1 && dir.back() == '/') dir.pop_back();
+    glob_t g;
+    std::memset(&g, 0, sizeof g);
+    const std::string pat = dir + "/*";
+    const int rv = glob(pat.c_str(), GLOB_TILDE, nullptr, &g);   // the order of the sig loader
+    std::vector<std::string> out;
+    if (rv == 0)
+        for (size_t i = 0; i < g.gl_pathc; ++i)
+            if (!source_name_of(g.gl_pathv[i]).empty() && !is_directory(g.gl_pathv[i])) out.emplace_back(g.gl_pathv[i]);
+    globfree(&g);
+    if (rv != 0 && rv != GLOB_NOMATCH) throw std::runtime_error("glob() failed on " + pat);
+    if (out.empty()) throw std::runtime_error("no .fa / .fasta / .fna / .fq / .fastq file (plain or .gz) in " + dir);
+    return out;
+}
+
+// $name as a number of at least `lo`, `fallback` when unset or empty
+uint64_t env_bytes(const char* name, const uint64_t fallback, const uint64_t lo) {
+    const char* s = std::getenv(name);
+    if (!s || !*s) return fallback;
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(s, &end, 10);
+    if (end == s || *end || *s == '-' || v < lo) throw ArgError(std::string(name) + " is a number of at least " + std::to_string(lo));
+    return v;
+}
+
+// the sketches of one batch, appended to the keys of their sources
+void run_batch(const Batch& b, const bool on_host, const int device, const int ksize, const uint64_t max_hash, const uint32_t seed,
+               std::vector<std::vector<uint64_t>>& keys, std::vector<uint32_t>& segments, ksp_sketch_stats& total) {
+    const uint32_t n_seg = (uint32_t)b.source.size();
+    if (n_seg == 0) return;
+    std::vector<uint64_t> out_off((size_t)n_seg + 1, 0), host_keys;
+    uint64_t* got = nullptr;
+    if (on_host) {
+        uint64_t needed = 0;
+        const double share = ((double)max_hash + 1.0) / 18446744073709551616.0;
+        host_keys.resize((size_t)std::min<uint64_t>(b.n_bytes, (uint64_t)((double)b.n_bytes * share * 1.25) + 4096));
+        int rc = ksp_sketch_cpu(b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, host_keys.data(), host_keys.size(), out_off.data(), &needed);
+        if (rc == KSP_E_OVERFLOW) {
+            host_keys.resize((size_t)needed);
+            rc = ksp_sketch_cpu(b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, host_keys.data(), host_keys.size(), out_off.data(), &needed);
+        }
+        if (rc != KSP_OK) throw CallError{rc};
+        got = host_keys.data();
+    } else {
+        ksp_sketch_stats st;
+        const int rc = ksp_sketch_host(device, b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, &got, out_off.data(), &st);
+        if (rc != KSP_OK) throw CallError{rc};
+        total.bases += st.bases; total.valid_kmers += st.valid_kmers; total.kept += st.kept; total.distinct_out += st.distinct_out;
+        total.retries += st.retries; total.ms_upload += st.ms_upload; total.ms_hash += st.ms_hash; total.ms_select += st.ms_select;
+    }
+    for (uint32_t s = 0; s < n_seg; ++s) {
+        const uint32_t src = b.source[s];
+        if (src >= keys.size()) { keys.resize((size_t)src + 1); segments.resize((size_t)src + 1, 0); }
+        keys[src].insert(keys[src].end(), got + out_off[s], got + out_off[s + 1]);
+        ++segments[src];
+    }
+    if (!on_host) ksp_free(got);
+}
+
+}  // namespace
+
+extern "C" int kspider_sketch(const char* input, int kSize, uint64_t scaled, const char* out_dir, int user_threads, uint64_t flags) {
+    const char* who = "kspider_sketch";
+    if (!input || !*input || !out_dir || !*out_dir) { ksp::set_error(std::string(who) + ": input and out_dir are required"); return KSP_E_ARG; }
+    if (kSize < 1 || kSize > 64) { ksp::set_error(std::string(who) + ": kSize is 1 .. 64"); return KSP_E_ARG; }
+    uint64_t max_hash = 0;
+    if (const int rc = ksp_sketch_max_hash(scaled, &max_hash)) return rc;
+    uint8_t* bufs[2] = {nullptr, nullptr};
+    bool on_host = false;
+    int rc = KSP_OK;
+    try {
+        const char* how = std::getenv("KSPIDER_SKETCH");
+        if (how && *how && std::strcmp(how, "host") != 0 && std::strcmp(how, "device") != 0) throw ArgError("KSPIDER_SKETCH is \"host\" or \"device\"");
+        on_host = how && std::strcmp(how, "host") == 0;
+        const int threads = user_threads < 1 ? 1 : user_threads;
+        const uint32_t seed = (flags & KSP_SKETCH_SEED) ? (uint32_t)(flags >> 32) : 42u;
+        const bool per_record = (flags & KSP_SKETCH_PER_RECORD) != 0;
+        if (per_record && is_directory(input)) throw ArgError("KSP_SKETCH_PER_RECORD takes one file, not a directory");
+        const size_t batch_bytes = (size_t)env_bytes("KSPIDER_SKETCH_BATCH_BYTES", env_bytes("KSPIDER_SKETCH_BATCH_MB", 256, 1) << 20, 1024);
+        const char* dv = std::getenv("KSPIDER_DEVICE");
+        const int device = dv ? std::atoi(dv) : 0;
+        Feed feed(input_files(input), per_record, threads, batch_bytes, kSize);
+        for (uint8_t*& p : bufs) {
+            p = (uint8_t*)(on_host ? std::malloc(batch_bytes) : ksp::pinned_alloc(batch_bytes));
+            if (!p) throw std::bad_alloc();
+        }
+        Batch batch[2];
+        batch[0].buf = bufs[0];
+        batch[1].buf = bufs[1];
+        std::vector<std::vector<uint64_t>> keys;
+        std::vector<uint32_t> segments;
+        ksp_sketch_stats total;
+        std::memset(&total, 0, sizeof total);
+        uint64_t n_batches = 0;
+        // ---- the pipeline: batch `cur` is hashed while a thread fills the other
+        int cur = 0;
+        bool more = feed.fill(batch[cur]);
+        while (more) {
+            bool more_next = false;
+            std::exception_ptr fill_err;
+            std::thread filler([&]() {
+                try {
+                    more_next = feed.fill(batch[cur ^ 1]);
+                } catch (...) {
+                    fill_err = std::current_exception();
+                }
+            });
+            std::exception_ptr run_err;
+            try {
+                run_batch(batch[cur], on_host, device, kSize, max_hash, seed, keys, segments, total);
+                ++n_batches;
+            } catch (...) {
+                run_err = std::current_exception();
+            }
+            filler.join();
+            if (run_err) std::rethrow_exception(run_err);
+            if (fill_err) std::rethrow_exception(fill_err);
+            more = more_next;
+            cur ^= 1;
+        }
+        // ---- the sources: names, unions, files
+        const size_t n_src = feed.names.size();
+        keys.resize(n_src);
+        segments.resize(n_src, 0);
+        {
+            std::set<std::string> seen;
+            for (const std::string& n : feed.names) {
+                if (n.empty()) throw ArgError("a source without a name");
+                if (!seen.insert(n).second) throw ArgError("two sources are named " + n);
+            }
+        }
+        if (mkdir(out_dir, 0777) != 0 && errno != EEXIST) throw std::runtime_error(std::string("cannot create ") + out_dir);
+        parallel_for(n_src, threads, [&](const size_t s) {
+            std::vector<uint64_t>& k = keys[s];
+            if (segments[s] > 1) {
+                std::sort(k.begin(), k.end());
+                k.erase(std::unique(k.begin(), k.end()), k.end());
+            }
+            ksp::write_file_atomically(std::string(out_dir) + "/" + feed.names[s] + ".sig", sig_text(feed.filenames[s], kSize, seed, max_hash, k));
+        });
+        if (std::getenv("KSPIDER_VERBOSE"))
+            std::cout << "kspider_amd: sketch: " << n_src << " sources in " << n_batches << " batches" << (on_host ? " on the host" : "") << "; " << total.bases
+                      << " bases, " << total.kept << " kept; upload " << total.ms_upload << " ms, hash " << total.ms_hash << " ms, select " << total.ms_select << " ms"
+                      << std::endl;
+    } catch (const CallError& e) {
+        rc = e.rc;
+    } catch (const std::bad_alloc&) {
+        ksp::set_error(std::string(who) + ": out of host memory");
+        rc = KSP_E_LIMIT;
+    } catch (const ArgError& e) {
+        ksp::set_error(std::string(who) + ": " + e.what());
+        rc = KSP_E_ARG;
+    } catch (const std::exception& e) {
+        ksp::set_error(std::string(who) + ": " + e.what());
+        rc = KSP_E_IO;
+    }
+    for (uint8_t* p : bufs) {
+        if (on_host) std::free(p);
+        else ksp::pinned_free(p);
+    }
+    return rc;
+}

@@ -94,7 +94,9 @@ std::string strip_slashes(std::string d) {
     return d;
 }
 
-std::string read_maybe_gz(const std::string& path) {
+}  // namespace
+
+std::string ksp::read_maybe_gz(const std::string& path) {
     gzFile f = gzopen(path.c_str(), "rb");   // transparent for plain files
     if (!f) throw std::runtime_error("kspider_amd: cannot open " + path);
     std::string out;
@@ -106,6 +108,10 @@ std::string read_maybe_gz(const std::string& path) {
     if (bad || rc != Z_OK) throw std::runtime_error("kspider_amd: read error on " + path + " (truncated or corrupt gzip?)");
     return out;
 }
+
+namespace {
+
+using ksp::read_maybe_gz;
 
 // ---- minimal JSON walker: enough to reach [0]["signatures"][i]{"ksize","mins"} ---------------
 struct Json {

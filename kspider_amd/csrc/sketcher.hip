@@ -1,0 +1,368 @@
+// The device part of the sketcher: bytes of FASTA / FASTQ records in HBM -> sourmash-compatible DNA FracMinHash
+// sketches.  The arithmetic — codes, reverse complement, the k-mer's text, Murmur — is sketch_hash.h, shared with the host loop.
+//
+//   hash     one pass over the bytes.  A workgroup of 256 loops over tiles of kTile positions.  Per tile every thread loads
+//            16 bytes (the first four another 16: the halo of ksize - 1 <= 63 bytes) and turns them into 32 bits of 2-bit codes
+//            and 16 break bits in LDS (1.6 KiB); bytes behind the stream's end are breaks.  Then a thread takes the positions
+//            tid, tid + 256, ...: "no break bit in [p, p + k)" from two mask words; the forward k-mer, left-aligned, as a funnel
+//            shift of two (k > 32: three) code words — no lane rolls over the bases before it; canonical form, text, Murmur,
+//            hash <= max_hash.  A survivor (about 1 in `scaled`) finds its source by binary search of the offsets, is dropped
+//            when its k-mer would cross the source's end, and is appended as (hash, source): one ballot and one returning add
+//            per wave; the counter keeps counting past the capacity, nothing is written past it.
+//   select   rocPRIM's merge sort by (source, hash), one scan of head flags (an entry that differs from the one before),
+//            k_sketch_compact writes the heads' hashes, k_sketch_offsets the per-source bounds by binary search.
+// Every loop is bounded by a size the host computed; no workgroup waits on another; the result does not depend on scheduling.
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <algorithm>
+#include <string>
+
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_merge_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include "../../include/kspider_amd.h"
+#include "device_call.h"
+#include "engine_internal.h"
+#include "sketch_hash.h"
+
+namespace {
+
+namespace sk = ksp_sketch;
+typedef uint32_t u32;
+typedef uint64_t u64;
+
+constexpr int kThreads = 256;
+constexpr u32 kTile = KSP_SKETCH_TILE_BASES;
+constexpr u32 kChunks = kTile / 16 + 4;   // 16-byte pieces of a tile and its halo of 64 bytes
+constexpr u32 kCodeWords = kChunks / 2;   // 32 bases per word
+constexpr u32 kMaskWords = kChunks / 4;   // 64 positions per word
+static_assert(kTile == 16 * kThreads, "a thread loads one 16-byte piece of the tile");
+static_assert(kTile % 64 == 0 && kChunks % 4 == 0, "whole mask words");
+
+// a survivor: its hash and its source
+struct Rec {
+    u64 hash, src;
+};
+
+struct HashArgs {
+    const uint8_t* seq;
+    u64 n_bytes, n_tiles;
+    const u64* src_off;   // n_sources + 1, device
+    u32 n_sources, k, seed;
+    u64 max_hash;
+    Rec* recs;
+    u64 capacity;
+    unsigned long long* counters;   // [0] survivors, the ones without room included, [1] bases, [2] windows without a break
+};
+
+// the sum of v over the wave, in lane 0
+__device__ inline u32 wave_sum(u32 v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += (u32)__shfl_down((int)v, d);
+    return v;
+}
+
+// kWide: ksize > 32, the k-mer takes two words
+template <bool kWide>
+__global__ __launch_bounds__(kThreads) void k_sketch_hash(const HashArgs A) {
+    __shared__ u64 s_code[kCodeWords];   // big-endian: base 32j of the tile on top of word j
+    __shared__ u64 s_mask[kMaskWords];   // little-endian: bit i of word m = position 64m + i is a break
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    u32 n_bases = 0, n_valid = 0;
+    const u64 win_mask = A.k == 64 ? ~0ull : (1ull << A.k) - 1;
+    for (u64 tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {
+        const u64 t0 = tile * kTile;
+        // ---- the tile and its halo as codes and break bits
+        for (u32 c = tid; c < kChunks; c += kThreads) {   // (two trips for the first four threads, one for the others)
+            const u64 at = t0 + 16ull * c;
+            u32 w[4] = {0, 0, 0, 0};   // (a zero byte is a break)
+            if (at + 16 <= A.n_bytes) {
+                const uint4 v = *reinterpret_cast<const uint4*>(A.seq + at);
+                w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+            } else if (at < A.n_bytes) {
+                const u32 n = (u32)(A.n_bytes - at);   // 1 .. 15 bytes are left
+#pragma unroll
+                for (u32 j = 0; j < 16; ++j)
+                    if (j < n) w[j >> 2] |= (u32)A.seq[at + j] << (8 * (j & 3));
+            }
+            u32 code = 0, breaks = 0;
+#pragma unroll
+            for (u32 j = 0; j < 16; ++j) {
+                const u32 b = (w[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+                code |= sk::base_code(b) << (30 - 2 * j);
+                breaks |= (sk::is_base(b) ? 0u : 1u) << j;
+            }
+            reinterpret_cast<u32*>(s_code)[c ^ 1u] = code;   // (the even piece is the upper half of its word)
+            reinterpret_cast<uint16_t*>(s_mask)[c] = (uint16_t)breaks;
+            if (c < kTile / 16) n_bases += 16u - (u32)__popc(breaks);
+        }
+        __syncthreads();
+        // ---- the positions of the tile
+        for (u32 p = tid; p < kTile; p += kThreads) {   // (the same trips for every thread)
+            const u32 m = p >> 6, s = p & 63;
+            const u64 window = s ? (s_mask[m] >> s) | (s_mask[m + 1] << (64 - s)) : s_mask[m];   // (m + 1 <= 64: the halo's word)
+            const bool valid = (window & win_mask) == 0;
+            bool keep = false;
+            u64 h = 0, src = 0;
+            if (valid) {
+                ++n_valid;
+                const u32 j = p >> 5, s2 = 2 * (p & 31);
+                sk::Kmer fw;
+                fw.hi = s2 ? (s_code[j] << s2) | (s_code[j + 1] >> (64 - s2)) : s_code[j];
+                fw.lo = 0;
+                if (kWide) fw.lo = s2 ? (s_code[j + 1] << s2) | (s_code[j + 2] >> (64 - s2)) : s_code[j + 1];   // (j + 2 <= 129)
+                fw = sk::keep_top(fw, A.k);
+                h = sk::kmer_hash(sk::canonical(fw, A.k), A.k, A.seed);
+                if (h <= A.max_hash) {
+                    const u64 gp = t0 + p;   // (below n_bytes: the window is valid)
+                    u32 lo = 0, hi = A.n_sources;   // the source of gp: the last s with src_off[s] <= gp
+                    while (hi - lo > 1) {
+                        const u32 mid = lo + (hi - lo) / 2;
+                        if (A.src_off[mid] <= gp) lo = mid; else hi = mid;
+                    }
+                    src = lo;
+                    keep = gp + A.k <= A.src_off[lo + 1];   // a k-mer over the end of its source is none
+                }
+            }
+            const unsigned long long have = __ballot(keep);
+            if (!have) continue;   // (the whole wave)
+            const int first = __ffsll((long long)have) - 1;
+            unsigned long long at = 0;
+            if ((int)lane == first) at = atomicAdd(&A.counters[0], (unsigned long long)__popcll(have));
+            const u32 at_lo = (u32)__shfl((int)(u32)at, first), at_hi = (u32)__shfl((int)(u32)(at >> 32), first);
+            const u64 slot = (((u64)at_hi << 32) | at_lo) + (u64)__popcll(have & ((1ull << lane) - 1));
+            if (keep && slot < A.capacity) A.recs[slot] = Rec{h, src};
+        }
+        __syncthreads();   // (the next tile's pieces overwrite the words)
+    }
+    n_bases = wave_sum(n_bases);
+    n_valid = wave_sum(n_valid);
+    if (lane == 0) {
+        if (n_bases) atomicAdd(&A.counters[1], (unsigned long long)n_bases);
+        if (n_valid) atomicAdd(&A.counters[2], (unsigned long long)n_valid);
+    }
+}
+
+struct RecBefore {
+    __host__ __device__ bool operator()(const Rec& a, const Rec& b) const { return a.src != b.src ? a.src < b.src : a.hash < b.hash; }
+};
+
+// 1 for a sorted entry that differs from the one before it, 0 behind the end
+struct HeadFlag {
+    const Rec* rec;
+    u64 n;
+    __host__ __device__ u64 operator()(const u64 i) const {
+        if (i >= n) return 0;
+        return i == 0 || rec[i].src != rec[i - 1].src || rec[i].hash != rec[i - 1].hash;
+    }
+};
+
+inline auto head_flags_of(const Rec* rec, const u64 n) { return rocprim::make_transform_iterator(rocprim::counting_iterator<u64>(0), HeadFlag{rec, n}); }
+
+// scan[i] = heads before entry i (n + 1 values: the last is their number)
+__global__ void k_sketch_compact(const Rec* __restrict__ rec, const u64* __restrict__ scan, const u64 n, u64* __restrict__ out_keys) {
+    const HeadFlag head{rec, n};
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
+        if (head(i)) out_keys[scan[i]] = rec[i].hash;
+}
+
+// off[s] = the heads of the sources before s, s = 0 .. n_sources
+__global__ void k_sketch_offsets(const Rec* __restrict__ rec, const u64* __restrict__ scan, const u64 n, const u32 n_sources, u64* __restrict__ off) {
+    for (u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x; s <= n_sources; s += (u64)gridDim.x * blockDim.x) {
+        u64 lo = 0, hi = n;   // the first entry whose source is >= s
+        while (lo < hi) {
+            const u64 mid = lo + (hi - lo) / 2;
+            if (rec[mid].src < s) lo = mid + 1; else hi = mid;
+        }
+        off[s] = scan[lo];
+    }
+}
+
+// the scratch the sort and the scan of n survivors ask for
+int select_scratch(const u64 n, size_t* tb) {
+    int rc = KSP_OK;
+    size_t tb_sort = 0, tb_scan = 0;
+    if (n) {
+        KSP_TRY_HIP(rocprim::merge_sort(nullptr, tb_sort, (const Rec*)nullptr, (Rec*)nullptr, (size_t)n, RecBefore(), (hipStream_t) nullptr));
+        KSP_TRY_HIP(rocprim::exclusive_scan(nullptr, tb_scan, head_flags_of(nullptr, 0), (u64*)nullptr, (u64)0, (size_t)n + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
+    }
+    *tb = std::max<size_t>(std::max(tb_sort, tb_scan), 8);
+done:
+    return rc;
+}
+
+// The sketches on the CURRENT device; the arguments have passed ksp::check_sketch_args.
+int sketch_on_device(const char* who, const uint8_t* d_seq, const u64 n_bytes, const u64* h_src_off, const u32 n_sources, const int ksize, const u64 max_hash,
+                     const u32 seed, u64* d_out_keys, const u64 capacity, u64* h_out_off, ksp_sketch_stats* stats) {
+    int rc = KSP_OK;
+    ksp_sketch_stats S;
+    std::memset(&S, 0, sizeof S);
+    ksp::WorkgroupCap G;
+    if ((rc = ksp::workgroup_cap("KSPIDER_SKETCH_MAX_WGS", who, G))) return rc;
+    const u64 n_tiles = (n_bytes + kTile - 1) / kTile;
+    ksp::DeviceArena A;
+    u64 *d_src_off = nullptr, *d_out_off = nullptr, *d_scan = nullptr;
+    Rec *d_recs = nullptr, *d_sorted = nullptr;
+    unsigned long long* d_count = nullptr;
+    void* d_tmp = nullptr;
+    size_t tb = 0;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    unsigned long long h_count[3] = {0, 0, 0};
+    u64 n = 0, distinct = 0;
+    // ---- everything the call holds, sized for `capacity` survivors and checked first
+    if ((rc = select_scratch(capacity, &tb))) return rc;
+    if ((rc = ksp::device_fits(who, 40ull * (capacity + 1) + tb + 16ull * ((u64)n_sources + 1) + 64,
+                               "per survivor of the capacity 16 unsorted, 16 sorted and 8 of the scan, the sort's scratch, 16 per source")))
+        return rc;
+    if ((rc = A.alloc(&d_src_off, (size_t)n_sources + 1)) || (rc = A.alloc(&d_out_off, (size_t)n_sources + 1)) || (rc = A.alloc(&d_count, 3))) return rc;
+    if (capacity && ((rc = A.alloc(&d_recs, (size_t)capacity)) || (rc = A.alloc(&d_sorted, (size_t)capacity)) || (rc = A.alloc(&d_scan, (size_t)capacity + 1)) ||
+                     (rc = A.alloc_bytes(&d_tmp, tb))))
+        return rc;
+    KSP_TRY_HIP(hipMemcpy(d_src_off, h_src_off, ((size_t)n_sources + 1) * 8, hipMemcpyHostToDevice));
+    KSP_TRY_HIP(hipMemset(d_count, 0, sizeof h_count));
+    for (hipEvent_t& e : ev) KSP_TRY_HIP(hipEventCreate(&e));
+    // ---- the hash pass
+    KSP_TRY_HIP(hipEventRecord(ev[0], nullptr));
+    if (n_tiles) {
+        const HashArgs H{d_seq, n_bytes, n_tiles, d_src_off, n_sources, (u32)ksize, seed, max_hash, d_recs, d_recs ? capacity : 0, d_count};
+        S.workgroups = G.grid_of(n_tiles);
+        if (ksize > 32) hipLaunchKernelGGL(k_sketch_hash<true>, dim3((unsigned)S.workgroups), dim3(kThreads), 0, nullptr, H);
+        else hipLaunchKernelGGL(k_sketch_hash<false>, dim3((unsigned)S.workgroups), dim3(kThreads), 0, nullptr, H);
+        KSP_TRY_HIP(hipGetLastError());
+    }
+    KSP_TRY_HIP(hipEventRecord(ev[1], nullptr));
+    KSP_TRY_HIP(hipMemcpy(h_count, d_count, sizeof h_count, hipMemcpyDeviceToHost));
+    n = h_count[0];
+    S.kept = S.needed = n; S.bases = h_count[1]; S.valid_kmers = h_count[2];
+    KSP_TRY_HIP(hipEventElapsedTime(&S.ms_hash, ev[0], ev[1]));
+    if (n > capacity) {
+        if (stats) *stats = S;
+        ksp::set_error(std::string(who) + ": " + std::to_string(n) + " survivors, room for " + std::to_string(capacity));
+        rc = KSP_E_OVERFLOW;
+        goto done;
+    }
+    // ---- the select pass
+    if (n) {
+        const unsigned ge = G.grid_of((n + 255) / 256);
+        size_t b = tb;   // (sized for the capacity: fewer survivors must not ask for more)
+        size_t need = 0;
+        if ((rc = select_scratch(n, &need))) goto done;
+        if (need > tb) { ksp::set_error(std::string(who) + ": fewer survivors ask for more scratch than the capacity"); rc = KSP_E_HIP; goto done; }
+        KSP_TRY_HIP(rocprim::merge_sort(d_tmp, b, (const Rec*)d_recs, d_sorted, (size_t)n, RecBefore(), (hipStream_t) nullptr));
+        b = tb;
+        KSP_TRY_HIP(rocprim::exclusive_scan(d_tmp, b, head_flags_of(d_sorted, n), d_scan, (u64)0, (size_t)n + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
+        hipLaunchKernelGGL(k_sketch_compact, dim3(ge), dim3(256), 0, nullptr, (const Rec*)d_sorted, (const u64*)d_scan, n, d_out_keys);
+        hipLaunchKernelGGL(k_sketch_offsets, dim3(G.grid_of(((u64)n_sources + 256) / 256)), dim3(256), 0, nullptr, (const Rec*)d_sorted, (const u64*)d_scan, n, n_sources,
+                           d_out_off);
+        KSP_TRY_HIP(hipGetLastError());
+        KSP_TRY_HIP(hipEventRecord(ev[2], nullptr));
+        KSP_TRY_HIP(hipMemcpy(h_out_off, d_out_off, ((size_t)n_sources + 1) * 8, hipMemcpyDeviceToHost));
+        KSP_TRY_HIP(hipEventElapsedTime(&S.ms_select, ev[1], ev[2]));
+        distinct = h_out_off[n_sources];
+        if (h_out_off[0] != 0 || distinct == 0 || distinct > n) { ksp::set_error(std::string(who) + ": the select pass lost its keys"); rc = KSP_E_HIP; goto done; }
+    } else {
+        std::fill(h_out_off, h_out_off + (size_t)n_sources + 1, 0);
+    }
+    S.distinct_out = distinct;
+    if (stats) *stats = S;
+done:
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
+// the first capacity of ksp_sketch_host: $KSPIDER_SKETCH_FIRST_CAPACITY when it is set (tests: forces the retry), else `guess`
+int env_first_capacity(const char* who, const u64 guess, u64* out) {
+    const char* s = std::getenv("KSPIDER_SKETCH_FIRST_CAPACITY");
+    *out = guess;
+    if (!s || !*s) return KSP_OK;
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(s, &end, 10);
+    if (end == s || *end || *s == '-') { ksp::set_error(std::string(who) + ": KSPIDER_SKETCH_FIRST_CAPACITY is a number"); return KSP_E_ARG; }
+    *out = v;
+    return KSP_OK;
+}
+
+int check_device_args(const char* who, const void* seq, const u64 n_bytes, const u64* src_off, const u32 n_sources, const int ksize, const void* out_off) {
+    if (!out_off) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+    return ksp::check_sketch_args(who, seq, n_bytes, src_off, n_sources, ksize);
+}
+
+}  // namespace
+
+void* ksp::pinned_alloc(const size_t bytes) {
+    void* p = nullptr;
+    return hipHostMalloc(&p, std::max<size_t>(bytes, 1), hipHostMallocDefault) == hipSuccess ? p : nullptr;
+}
+void ksp::pinned_free(void* p) {
+    if (p) (void)hipHostFree(p);
+}
+
+extern "C" int ksp_sketch_device(int device, const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* h_src_offsets, uint32_t n_sources, int ksize,
+                                 uint64_t max_hash, uint32_t seed, uint64_t* d_out_keys, uint64_t capacity, uint64_t* h_out_offsets,
+                                 ksp_sketch_stats* stats) {
+    const char* who = "ksp_sketch_device";
+    if (const int rc = check_device_args(who, d_seq, n_bytes, h_src_offsets, n_sources, ksize, h_out_offsets)) return rc;
+    if (!d_out_keys && capacity) { ksp::set_error(std::string(who) + ": d_out_keys is NULL but capacity is not 0"); return KSP_E_ARG; }
+    if ((uintptr_t)d_seq & 15) { ksp::set_error(std::string(who) + ": d_seq is not 16-byte aligned"); return KSP_E_ARG; }
+    if (const int rc = ksp::set_device(who, device)) return rc;
+    return sketch_on_device(who, d_seq, n_bytes, h_src_offsets, n_sources, ksize, max_hash, seed, d_out_keys, capacity, h_out_offsets, stats);
+}
+
+extern "C" int ksp_sketch_host(int device, const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize,
+                               uint64_t max_hash, uint32_t seed, uint64_t** out_keys, uint64_t* out_offsets, ksp_sketch_stats* stats) {
+    const char* who = "ksp_sketch_host";
+    if (!out_keys) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+    if (const int rc = check_device_args(who, seq, n_bytes, src_offsets, n_sources, ksize, out_offsets)) return rc;
+    u64 first = 0;
+    {   // the share of all hashes that max_hash keeps, a quarter more, and room for a small input whatever its luck
+        const double share = ((double)max_hash + 1.0) / 18446744073709551616.0;
+        const u64 guess = std::min<u64>(n_bytes, (u64)((double)n_bytes * share * 1.25) + 4096);
+        if (const int rc = env_first_capacity(who, guess, &first)) return rc;
+    }
+    if (const int rc = ksp::set_device(who, device)) return rc;
+    int rc = KSP_OK;
+    ksp::DeviceArena A;
+    uint8_t* d_seq = nullptr;
+    u64 *d_keys = nullptr, *h_keys = nullptr, capacity = first;
+    ksp_sketch_stats S;
+    float ms_upload = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::memset(&S, 0, sizeof S);
+    if ((rc = ksp::device_fits(who, n_bytes + 16 + 8ull * capacity, "the bytes and the first key buffer"))) return rc;
+    if ((rc = A.alloc(&d_seq, (size_t)n_bytes + 16)) || (rc = A.alloc(&d_keys, (size_t)capacity))) return rc;
+    KSP_TRY_HIP(hipEventCreate(&ev0));
+    KSP_TRY_HIP(hipEventCreate(&ev1));
+    KSP_TRY_HIP(hipEventRecord(ev0, nullptr));
+    if (n_bytes) KSP_TRY_HIP(hipMemcpyAsync(d_seq, seq, (size_t)n_bytes, hipMemcpyHostToDevice, nullptr));
+    KSP_TRY_HIP(hipEventRecord(ev1, nullptr));
+    KSP_TRY_HIP(hipEventSynchronize(ev1));
+    KSP_TRY_HIP(hipEventElapsedTime(&ms_upload, ev0, ev1));
+    rc = sketch_on_device(who, d_seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, d_keys, capacity, out_offsets, &S);
+    if (rc == KSP_E_OVERFLOW) {   // once more, at the exact size
+        KSP_TRY_HIP(A.release(d_keys));
+        d_keys = nullptr;
+        capacity = S.needed;
+        if ((rc = ksp::device_fits(who, 8ull * capacity, "the keys"))) goto done;
+        if ((rc = A.alloc(&d_keys, (size_t)capacity))) goto done;
+        rc = sketch_on_device(who, d_seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, d_keys, capacity, out_offsets, &S);
+        S.retries = 1;
+    }
+    if (rc != KSP_OK) goto done;
+    h_keys = (u64*)std::malloc((size_t)std::max<u64>(S.distinct_out, 1) * 8);
+    if (!h_keys) { ksp::set_error(std::string(who) + ": out of host memory"); rc = KSP_E_LIMIT; goto done; }
+    if (S.distinct_out) KSP_TRY_HIP(hipMemcpy(h_keys, d_keys, (size_t)S.distinct_out * 8, hipMemcpyDeviceToHost));
+    *out_keys = h_keys;
+    h_keys = nullptr;
+    S.ms_upload = ms_upload;
+    if (stats) *stats = S;
+done:
+    if (h_keys) std::free(h_keys);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    return rc;
+}

@@ -74,6 +74,10 @@ GATHER_TAIL_CANDS_MAX = 1 << 20
 GATHER_ROW_DTYPE = np.dtype([("query", np.uint32), ("rank", np.uint32), ("source", np.uint32), ("overlap", np.uint32), ("unique", np.uint32),
                              ("remaining", np.uint32)])
 
+#: the sketcher (csrc/sketcher.hip): positions per tile of the hash pass; the flags of kspider_sketch
+SKETCH_TILE_BASES = 4096
+SKETCH_PER_RECORD, SKETCH_SEED = 1, 2
+
 #: ksp_engine_lists_path / Engine.lists_path
 LISTS_NONE, LISTS_KEYED, LISTS_COMPACTED, LISTS_SORTED, LISTS_FUSED = 0, 1, 2, 3, 4
 
@@ -107,6 +111,8 @@ ABI_SYMBOLS = [
     "ksp_edges_tsv",
     "ksp_query_device", "ksp_query_host", "ksp_query_directory", "kspider_pack", "ksp_pack_info", "ksp_pack_load", "kspider_query",
     "ksp_gather_device", "ksp_gather_host", "kspider_gather",
+    "ksp_sketch_max_hash", "ksp_murmur64", "ksp_sketch_kmer_hash", "ksp_sketch_cpu", "ksp_sketch_device", "ksp_sketch_host",
+    "ksp_fastx_info", "ksp_fastx_load", "kspider_sketch",
 ]
 
 
@@ -153,6 +159,18 @@ class GatherStats(ctypes.Structure):
         ("rows", ctypes.c_uint64), ("long_seg", ctypes.c_uint64), ("tail_cands", ctypes.c_uint64),
         ("ms_table", ctypes.c_float), ("ms_candidates", ctypes.c_float), ("ms_fill", ctypes.c_float), ("ms_rounds", ctypes.c_float),
         ("tile", ctypes.c_uint32), ("min_hashes", ctypes.c_uint32), ("max_matches", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class SketchStats(ctypes.Structure):
+    """ksp_sketch_stats (include/kspider_amd.h)."""
+    _fields_ = [
+        ("bases", ctypes.c_uint64), ("valid_kmers", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("distinct_out", ctypes.c_uint64),
+        ("needed", ctypes.c_uint64), ("workgroups", ctypes.c_uint64), ("retries", ctypes.c_uint64),
+        ("ms_upload", ctypes.c_float), ("ms_hash", ctypes.c_float), ("ms_select", ctypes.c_float), ("reserved", ctypes.c_uint32),
     ]
 
     def as_dict(self):
@@ -344,6 +362,18 @@ def lib():
         L.ksp_gather_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                       ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.kspider_gather.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]
+        L.ksp_sketch_max_hash.argtypes = [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+        L.ksp_murmur64.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p]
+        L.ksp_sketch_kmer_hash.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]
+        L.ksp_sketch_cpu.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
+                                     ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+        L.ksp_sketch_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64,
+                                        ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(SketchStats)]
+        L.ksp_sketch_host.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64,
+                                      ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.POINTER(SketchStats)]
+        L.ksp_fastx_info.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
+        L.ksp_fastx_load.argtypes = [ctypes.c_char_p] + [ctypes.c_void_p] * 4
+        L.kspider_sketch.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint64]
         _lib = L
     return _lib
 
@@ -1059,6 +1089,105 @@ def gather(db: str, queries: str, kSize: int, out_prefix: str, user_threads: int
     OUT_kSpider_gather.tsv."""
     _check(lib().kspider_gather(os.fsencode(db), os.fsencode(queries), int(kSize), os.fsencode(out_prefix) if out_prefix else None, int(user_threads),
                                 int(min_hashes), int(max_matches)))
+
+
+def sketch_max_hash(scaled: int) -> int:
+    """sourmash's threshold of `scaled` (host only): 2^64 - 1 for 1, int(2^64 / float(scaled)) above; 0 is refused."""
+    out = ctypes.c_uint64(0)
+    _check(lib().ksp_sketch_max_hash(int(scaled), ctypes.byref(out)))
+    return out.value
+
+
+def murmur64(data: bytes, seed: int = 42) -> tuple:
+    """Both words of MurmurHash3_x64_128 over the bytes (host only)."""
+    data = bytes(data)
+    out = np.zeros(2, dtype=np.uint64)
+    _check(lib().ksp_murmur64(data, len(data), int(seed), out.ctypes.data))
+    return int(out[0]), int(out[1])
+
+
+def sketch_kmer_hash(text, seed: int = 42) -> tuple:
+    """(hash, valid) of the k-mer the bytes spell (host only); valid is False, and hash 0, when a byte is not one of ACGTacgt."""
+    text = text.encode() if isinstance(text, str) else bytes(text)
+    h, v = ctypes.c_uint64(0), ctypes.c_int(0)
+    _check(lib().ksp_sketch_kmer_hash(text, len(text), int(seed), ctypes.byref(h), ctypes.byref(v)))
+    return h.value, bool(v.value)
+
+
+def _sketch_input(seq, src_offsets, max_hash, scaled):
+    if (max_hash is None) == (scaled is None):
+        raise ValueError("give max_hash or scaled")
+    buf = np.frombuffer(bytes(seq), dtype=np.uint8) if isinstance(seq, (bytes, bytearray)) else np.ascontiguousarray(seq, dtype=np.uint8)
+    off = np.ascontiguousarray(src_offsets, dtype=np.uint64)
+    return buf, off, (sketch_max_hash(scaled) if max_hash is None else int(max_hash))
+
+
+def sketch_cpu(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled: int | None = None, seed: int = 42) -> tuple:
+    """ksp_sketch_cpu, the plain host loop: bytes and source offsets -> (keys, offsets) of the sources' sketches.  No GPU."""
+    buf, off, mh = _sketch_input(seq, src_offsets, max_hash, scaled)
+    n_src = max(off.size - 1, 0)
+    out_off = np.zeros(n_src + 1, dtype=np.uint64)
+    needed = ctypes.c_uint64(0)
+    rc = lib().ksp_sketch_cpu(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), None, 0, out_off.ctypes.data, ctypes.byref(needed))
+    if rc not in (KSP_OK, KSP_E_OVERFLOW):
+        _check(rc)
+    keys = np.zeros(max(needed.value, 1), dtype=np.uint64)
+    _check(lib().ksp_sketch_cpu(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), keys.ctypes.data, needed.value, out_off.ctypes.data,
+                                ctypes.byref(needed)))
+    return keys[:needed.value].copy(), out_off
+
+
+def sketch_host(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled: int | None = None, seed: int = 42, device: int = 0) -> tuple:
+    """ksp_sketch_host: host bytes and source offsets -> (keys, offsets, stats) of the sources' sketches, made on the device."""
+    buf, off, mh = _sketch_input(seq, src_offsets, max_hash, scaled)
+    n_src = max(off.size - 1, 0)
+    out_off = np.zeros(n_src + 1, dtype=np.uint64)
+    out = ctypes.c_void_p()
+    st = SketchStats()
+    _check(lib().ksp_sketch_host(int(device), _ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), ctypes.byref(out), out_off.ctypes.data,
+                                 ctypes.byref(st)))
+    try:
+        n = int(out_off[-1])
+        keys = np.frombuffer((ctypes.c_char * (8 * n)).from_address(out.value), dtype=np.uint64).copy() if n else np.zeros(0, dtype=np.uint64)
+    finally:
+        lib().ksp_free(out)
+    return keys, out_off, st.as_dict()
+
+
+def sketch_device(d_seq_ptr: int, n_bytes: int, src_offsets, ksize: int, max_hash: int, d_out_keys_ptr: int, capacity: int, seed: int = 42,
+                  device: int = 0) -> tuple:
+    """ksp_sketch_device: bytes and keys in DEVICE memory, offsets on the host (d_out_keys 0 / capacity 0: the size query).
+    -> (rc, offsets, stats): rc is KSP_OK or KSP_E_OVERFLOW (stats["needed"] is then the required capacity); anything else raises."""
+    off = np.ascontiguousarray(src_offsets, dtype=np.uint64)
+    n_src = max(off.size - 1, 0)
+    out_off = np.zeros(n_src + 1, dtype=np.uint64)
+    st = SketchStats()
+    rc = lib().ksp_sketch_device(int(device), d_seq_ptr or None, int(n_bytes), _ptr(off), n_src, int(ksize), int(max_hash), int(seed), d_out_keys_ptr or None,
+                                 int(capacity), out_off.ctypes.data, ctypes.byref(st))
+    if rc not in (KSP_OK, KSP_E_OVERFLOW):
+        _check(rc)
+    return rc, out_off, st.as_dict()
+
+
+def fastx_read(path: str) -> dict:
+    """A FASTA / FASTQ file, plain or gzip (ksp_fastx_info + ksp_fastx_load; host only): seq (every record's bases followed by one
+    newline), rec_offsets, names (every header's first word), fastq."""
+    info = np.zeros(4, dtype=np.uint64)
+    _check(lib().ksp_fastx_info(os.fsencode(path), info.ctypes.data))
+    R, B, T = int(info[0]), int(info[1]), int(info[2])
+    seq, text = np.zeros(B + 1, dtype=np.uint8), np.zeros(T + 1, dtype=np.uint8)
+    rec_off, name_off = np.zeros(R + 1, dtype=np.uint64), np.zeros(R + 1, dtype=np.uint64)
+    _check(lib().ksp_fastx_load(os.fsencode(path), seq.ctypes.data, rec_off.ctypes.data, name_off.ctypes.data, text.ctypes.data))
+    blob = text[:T].tobytes()
+    return {"seq": seq[:B].tobytes(), "rec_offsets": rec_off, "names": [os.fsdecode(blob[int(name_off[r]):int(name_off[r + 1])]) for r in range(R)],
+            "fastq": bool(info[3])}
+
+
+def sketch_files(input_path: str, kSize: int, scaled: int, out_dir: str, user_threads: int = 1, per_record: bool = False, seed: int | None = None) -> None:
+    """FASTA / FASTQ files -> one sourmash-compatible .sig file per source in out_dir (kspider_sketch).  input_path: a directory
+    (each file a source) or one file (per_record: each record a source).  KSPIDER_SKETCH=host in the environment: no GPU."""
+    flags = (SKETCH_PER_RECORD if per_record else 0) | (0 if seed is None else SKETCH_SEED | (int(seed) << 32))
+    _check(lib().kspider_sketch(os.fsencode(input_path), int(kSize), int(scaled), os.fsencode(out_dir), int(user_threads), flags))
 
 
 def cluster_from_tree(index_prefix: str, dist_type: str = "max_cont", cutoff: float = 0.0) -> None:
