@@ -919,6 +919,7 @@ int kspider_query(const char* db, const char* queries, int kSize, const char* ou
 #define KSP_GATHER_LONG_SEG 1024u
 #define KSP_GATHER_TAIL_CANDS 256u
 #define KSP_GATHER_TAIL_CANDS_MAX 1048576u
+#define KSP_GATHER_FIRST_CANDS 4096u   /* candidates the first buffer of a call holds (or 4 per source); a tile with more is swept twice */
 typedef struct ksp_gather_row {
     uint32_t query, rank, source;
     uint32_t overlap, unique, remaining;

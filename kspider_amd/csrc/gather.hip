@@ -496,7 +496,7 @@ int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_k
     if ((rc = query_table_scratch(e_max, &B.tb))) return rc;
     KSP_TRY_HIP(rocprim::exclusive_scan(nullptr, tb_rows, (u32*)nullptr, (u32*)nullptr, 0u, (size_t)kTileMax, rocprim::plus<u32>(), (hipStream_t) nullptr));
     B.tb = std::max<size_t>(std::max(B.tb, tb_rows), 8);
-    cand_cap = std::max<u64>(4096, 4ull * n_db);
+    cand_cap = std::max<u64>(KSP_GATHER_FIRST_CANDS, 4ull * n_db);
     // ---- what the call holds whatever the tiles find, sized and checked first: 8 per source (offsets), 8 per source with entries
     // (its list and the list of those with a candidate), 24 per query of a tile, the table, the first candidate buffer, the scratch
     if ((rc = ksp::device_fits(who, 8ull * ((u64)n_db + n_q + 2) + 8ull * (probes[0].size() + probes[1].size()) + 24ull * kTileMax + B.bytes() + 12 * cand_cap + B.tb + 256,

@@ -66,11 +66,12 @@ QUERY_LIST_MAX = 512
 QUERY_LONG_RUN = 2048
 QUERY_DIR_BITS_MAX = 24
 
-#: gather (include/kspider_amd.h KSP_GATHER_*): rounds per batch, the default switches, the row record
+#: gather (include/kspider_amd.h KSP_GATHER_*): rounds per batch, the default switches, the first candidate buffer, the row record
 GATHER_BATCH = 16
 GATHER_LONG_SEG = 1024
 GATHER_TAIL_CANDS = 256
 GATHER_TAIL_CANDS_MAX = 1 << 20
+GATHER_FIRST_CANDS = 4096
 GATHER_ROW_DTYPE = np.dtype([("query", np.uint32), ("rank", np.uint32), ("source", np.uint32), ("overlap", np.uint32), ("unique", np.uint32),
                              ("remaining", np.uint32)])
 

@@ -97,6 +97,84 @@ def sample_case(n_db=100, mean_size=5000, n_pick=10, n_noise=2000, seed=9):
     return [sk.run(s) for s in range(sk.n_sources)], [synth.gather_sample(sk, n_pick, n_noise, seed)], 5, 0
 
 
+def wide_case(n_q=1100, n_db=5):
+    """One tile wider than the touched list, the tail's 1 024 threads and (in candidates) the first candidate buffer: n_db sources
+    of 1 .. n_db keys of their own plus one key of the next source; every query holds all 15 keys but one (every 7th: but up to
+    three) and a key of its own, so every source shares keys with every query and the sources hide each other."""
+    core = [[1000 * (s + 1) + i for i in range(s + 1)] for s in range(n_db)]
+    allcore = [k for c in core for k in c]
+    db = [core[s] + core[(s + 1) % n_db][:1] for s in range(n_db)]
+    q = []
+    for j in range(n_q):
+        drop = {allcore[j % len(allcore)]}
+        if j % 7 == 0:
+            drop |= {allcore[(j // 7) % len(allcore)], allcore[(j // 7 + 4) % len(allcore)]}
+        q.append([k for k in allcore if k not in drop] + [10**6 + j])
+    return db, q, 2, 0
+
+
+def list_edge_case(n_share):
+    """n_share queries {77, 78, own key} at min_hashes 2: source 0 is a candidate of every query (both sweeps see it touch n_share
+    queries), source 1 touches every query but is only dropped (the counting sweep alone), source 2 touches none."""
+    return [[77, 78, 5], [78, 6], [6, 5]], [[77, 78, 10**6 + j] for j in range(n_share)], 2, 0
+
+
+def seam_case():
+    """Under a tile of 2: a tile of empty queries, a tile whose queries share no key with the database, a tile with rows (queries
+    4 and 5: tiles_case(5)'s first two), a last tile of one empty query."""
+    db, q, m, _ = tiles_case(5)
+    return db, [[], [], [1000, 1001, 1002], [2000, 2001], q[0], q[1], []], m, 0
+
+
+def block_case():
+    """query_inputs.block_case(): database runs of 255 / 256 / 257 / 1 023 / 1 024 / 1 025 and 3 entries at min_hashes 2"""
+    db, q = query_inputs.block_case()
+    return db, q, 2, 0
+
+
+SWITCH_CHOICES = (("KSP_QUERY_TILE", ("1", "2", "3", None)), ("KSP_QUERY_LIST", ("1", "2", "3", None)), ("KSP_QUERY_LONG_RUN", ("1", "8", None)),
+                  ("KSP_GATHER_LONG_SEG", ("1", "4", None)), ("KSP_GATHER_TAIL", ("0", "1")), ("KSP_GATHER_TAIL_CANDS", ("0", "3", None)),
+                  ("KSP_GATHER_MAX_WORKGROUPS", ("1", "2", None)))
+
+
+def switch_cases(n=48, seed=20261020):
+    """n small random cases, each with an independent draw of every switch: [(case, {switch: value or None = unset})].  1 .. 12
+    sources and 1 .. 9 queries of 0 .. 30 keys from 12, 40 or 90 values, min_hashes of 1 / 2 / 3 / 5, max_matches of 0 / 0 / 1 / 2."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(n):
+        n_db, n_q, universe = int(rng.integers(1, 13)), int(rng.integers(1, 10)), int(rng.choice([12, 40, 90]))
+        draw = lambda k: [np.sort(rng.choice(universe, size=min(int(rng.integers(0, 31)), universe), replace=False)) for _ in range(k)]   # noqa: E731
+        case = (draw(n_db), draw(n_q), int(rng.choice([1, 2, 3, 5])), int(rng.choice([0, 0, 1, 2])))
+        out.append((case, {name: values[int(rng.integers(len(values)))] for name, values in SWITCH_CHOICES}))
+    return out
+
+
+def slots(db_runs, q_runs, min_hashes):
+    """Σ overlap over the candidates: the (source, query) pairs that share min_hashes keys or more"""
+    sets = [set(int(k) for k in run) for run in db_runs]
+    shared = [len(S & set(int(k) for k in run)) for run in q_runs for S in sets]
+    return sum(n for n in shared if n >= min_hashes)
+
+
+def by_tile(case, tile, restate):
+    """What a case gives when its queries are taken `tile` at a time (queries are independent; a tile's first query is added to
+    the query index): (rows, {candidates, dropped, fell_below, slots: sums over the tiles; passes: the tiles that have an entry;
+    rounds: Σ max(iterations) over the tiles that have a candidate — a tile without one runs no round}).  `restate` is
+    gather_restate.gather."""
+    db, q, m, k = case
+    rows, total = [], {"candidates": 0, "dropped": 0, "fell_below": 0, "slots": 0, "passes": 0, "rounds": 0}
+    for q0 in range(0, len(q), tile):
+        part, counts = q[q0:q0 + tile], {}
+        rows += [(r[0] + q0,) + r[1:] for r in restate(db, part, m, k, counts)]
+        for name in ("candidates", "dropped", "fell_below"):
+            total[name] += counts[name]
+        total["slots"] += slots(db, part, m)
+        total["passes"] += any(len(run) for run in part)
+        total["rounds"] += max(counts["iterations"]) if counts["candidates"] else 0
+    return rows, total
+
+
 def arrays(db_runs, q_runs):
     """(db_keys, db_offsets, q_keys, q_offsets) as the ABI takes them"""
     sk = query_inputs.concat(db_runs, q_runs)

@@ -87,6 +87,18 @@ def long_run_case(seed=5):
     return [rng.choice(3000, size=n, replace=False) for n in LONG_RUN_LENGTHS], _universe_runs(rng, 12, 200, 3000)
 
 
+BLOCK_RUN_LENGTHS = (255, 256, 257, 1023, 1024, 1025, 3)
+BLOCK_QUERY_LENGTH = 600
+
+
+def block_case(seed=4):
+    """Database runs one short of, exactly and one past what a wave (64 lanes x 4 keys = 256 entries) and a workgroup (1 024) look
+    up in one step, and a run of 3, from 4 000 values; 6 queries of 600 from the same values.  (The seed: the run of 3 shares two
+    keys with a query, so that gather at min_hashes 2 has it as a candidate.)"""
+    rng = np.random.default_rng(seed)
+    return [rng.choice(4000, size=n, replace=False) for n in BLOCK_RUN_LENGTHS], _universe_runs(rng, 6, BLOCK_QUERY_LENGTH, 4000)
+
+
 def list_case(n_share):
     """Database source 0 shares the key 77 with n_share queries of two hashes each; source 1 shares it with none."""
     return [[77, 5], [6, 5]], [[77, 10**6 + i] for i in range(n_share)]

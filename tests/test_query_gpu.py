@@ -82,6 +82,22 @@ def test_short_and_long_kernels(monkeypatch, mode):
 
 
 @pytest.mark.parametrize("mode", MODES)
+def test_run_lengths_at_the_probe_block(monkeypatch, mode):
+    """A wave looks 64 x 4 = 256 entries up per step, a workgroup 1 024: runs of 255 / 256 / 257 and 1 023 / 1 024 / 1 025 through
+    the workgroup kernel (1), the three longest through it (1 000), all through the wave kernel (100 000)."""
+    db, q = Q.block_case()
+    sk = Q.concat(db, q)
+    want = Q.expected(sk, len(db), mode)
+    probes = Q.BLOCK_RUN_LENGTHS + ((Q.BLOCK_QUERY_LENGTH,) * (len(q) - 1) if mode == Q.CROSS_AND_SELF else ())
+    for long_run in (1, 1000, 100000):
+        monkeypatch.setenv("KSP_QUERY_LONG_RUN", str(long_run))
+        got, st = engine.query_host(*Q.split(sk, len(db)), mode=mode)
+        _same(got, want)
+        assert st["long_run"] == long_run and st["long_sources"] == sum(n >= long_run for n in probes) and st["short_sources"] == sum(n < long_run for n in probes)
+    assert sum(n >= 1000 for n in Q.BLOCK_RUN_LENGTHS) == 3 and len(want) >= len(db)
+
+
+@pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("long_run", ["1", "100000"])
 @pytest.mark.parametrize("n_share", [31, 32, 33, 200])
 def test_touched_list(monkeypatch, n_share, long_run, mode):

@@ -98,6 +98,18 @@ def test_long_run_case_lengths():
     assert {255, 256, 257, 1000} <= set(Q.LONG_RUN_LENGTHS) and min(Q.LONG_RUN_LENGTHS) < 255
 
 
+def test_block_case_lengths_sit_on_both_sides_of_the_probe_blocks():
+    db, q = Q.block_case()
+    assert tuple(len(np.unique(r)) for r in db) == Q.BLOCK_RUN_LENGTHS
+    for block in (256, 1024):                                                  # 64 lanes and 256 threads x 4 keys per step
+        assert {block - 1, block, block + 1} <= set(Q.BLOCK_RUN_LENGTHS)
+    assert min(Q.BLOCK_RUN_LENGTHS) < 64 and len(q) == 6 and all(len(np.unique(r)) == Q.BLOCK_QUERY_LENGTH for r in q)
+    sk = Q.concat(db, q)
+    cross, both = Q.expected(sk, len(db), Q.CROSS), Q.expected(sk, len(db), Q.CROSS_AND_SELF)
+    assert set(cross["source_1"].tolist()) == set(range(len(db)))              # every run has a row
+    assert len(both) == len(cross) + len(q) * (len(q) - 1) // 2                # and every pair of queries shares a key
+
+
 @pytest.mark.parametrize("n_share", [31, 32, 33, 200])
 def test_list_case_overflows_exactly_above_the_capacity(n_share):
     db, q = Q.list_case(n_share)
