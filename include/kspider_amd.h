@@ -952,6 +952,44 @@ int ksp_gather_host(const uint64_t* db_keys, const uint64_t* db_offsets, uint32_
 int kspider_gather(const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, uint32_t min_hashes,
                    uint32_t max_matches);
 
+/* ---- weighted gather: the same decomposition of queries that carry an abundance per hash (csrc/gather.hip) ----
+ * Query q has hash set Q and abundances a(h), uint32_t, parallel to its keys: q_abund[i] belongs to q_keys[i].  0 is legal and
+ * counts as 0.  W = Σ_{h∈Q} a(h).  The greedy is exactly the one above — selection by the unweighted u(s), ties to the smaller
+ * source, the same stops —, so the first six fields of every row are ksp_gather_*'s.  For the row of rank r let T = S_s* ∩ R
+ * BEFORE the removal, n = |T| = unique.  The row additionally carries
+ *   w_unique = Σ_{h∈T} a(h);   w_found = Σ of w_unique over ranks 1 .. r of this query;   sq_lo, sq_hi = the 128-bit Σ_{h∈T} a(h)²;
+ *   median2 = a_(⌈n/2⌉) + a_(⌊n/2⌋+1) of T's abundances in ascending order (1-based): twice the median.
+ * The statistics are over the hashes TAKEN IN THAT ROUND, with the original query's abundances — not over the whole overlap.
+ * Everything is an integer, so the table is the same under every switch and schedule.  A database has no abundances here.
+ * (A query that lists a hash more than once holds it once, as above, with the largest of the abundances listed for it.)
+ * ksp_gather_abund_device / ksp_gather_abund_host: ksp_gather_device / ksp_gather_host with d_q_abund (DEVICE) / q_abund (HOST)
+ *   beside the query keys and rows of ksp_gather_wrow.  The same argument, limit and overflow rules (q_abund NULL: KSP_E_ARG), the
+ *   same switches, the same ksp_gather_stats.  Memory beside the unweighted call's: 4 bytes per holder of a tile's query table
+ *   (the abundance at its holder slot), 8 per query of a tile, and 128 instead of 48 per possible row; the message names them.
+ *   On the device: after a tile's table is built one pass puts a(h) at its holder slot; the take sums a and a² over the winner's
+ *   alive slots before it clears them, compacts their abundances into the winner's own segment (dead after the take) and selects
+ *   the median there: by ranking in registers up to 64 values, above by a radix select over 8-bit digits (a 256-bin histogram per
+ *   wave in LDS, four passes).  One wave per take, as in the unweighted call; no library sort.
+ * kspider_gather_abund: kspider_gather for queries that carry abundances.  `queries` must be a directory of signatures that all
+ *   have "abundances": a pack file, or a signature without them, is KSP_E_ARG naming it.  Abundances of the database are
+ *   ignored.  Writes OUT_kSpider_gather.tsv: kspider_gather's nine columns, byte for byte, then f_unique_weighted = w_unique / W,
+ *   average_abund = w_unique / unique, median_abund = median2 / 2, std_abund = sqrt(n·sq − w_unique²) / n (the numerator exact
+ *   in 128 bits, rounded once to double) — each cast to float and printed as ksp_format_float prints —, then the integers
+ *   n_unique_weighted_found = w_unique, sum_weighted_found = w_found and total_weighted_hashes = W.  A refused or failed call
+ *   writes no file.                                                                                                            */
+typedef struct ksp_gather_wrow {
+    uint32_t query, rank, source, overlap, unique, remaining;
+    uint64_t w_unique, w_found, sq_lo, sq_hi, median2;
+} ksp_gather_wrow;   /* 64 bytes */
+int ksp_gather_abund_device(int device, const uint64_t* d_db_keys, const uint64_t* h_db_offsets, uint32_t n_db, const uint64_t* d_q_keys,
+                            const uint32_t* d_q_abund, const uint64_t* h_q_offsets, uint32_t n_q, uint32_t min_hashes, uint32_t max_matches,
+                            ksp_gather_wrow* d_rows, uint64_t capacity, uint64_t* n_rows, ksp_gather_stats* stats);
+int ksp_gather_abund_host(const uint64_t* db_keys, const uint64_t* db_offsets, uint32_t n_db, const uint64_t* q_keys, const uint32_t* q_abund,
+                          const uint64_t* q_offsets, uint32_t n_q, uint32_t min_hashes, uint32_t max_matches, int device,
+                          ksp_gather_wrow** rows, uint64_t* n_rows, ksp_gather_stats* stats);
+int kspider_gather_abund(const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, uint32_t min_hashes,
+                         uint32_t max_matches);
+
 /* ---- sketching: FASTA / FASTQ in, sourmash-compatible DNA FracMinHash sketches out (csrc/sketch_hash.h, csrc/sketcher.hip,
  *      csrc/sketch_cpu.cpp, csrc/fastx_reader.cpp, csrc/sketch_files.cpp) ----
  * The definition.  Bytes ACGTacgt are bases, lower case counts as upper case; every other byte value breaks k-mers.  A k-mer is
@@ -998,10 +1036,28 @@ int kspider_gather(const char* db, const char* queries, int kSize, const char* o
  *   longer than a batch is cut with ksize - 1 bytes of overlap, and the result does not depend on the batch size.
  *   KSPIDER_SKETCH=host runs the same driver over ksp_sketch_cpu: the same bytes, no GPU.  Works with $KSPIDER_DEVICE.
  *   KSP_E_ARG: NULL or empty input / out_dir, ksize outside 1 .. 64, scaled = 0, two sources of one name; KSP_E_IO: no input
- *   file, a reader error, a file that cannot be written.                                                                    */
+ *   file, a reader error, a file that cannot be written.
+ * Counted sketches.  With the definition above unchanged, the abundance of a kept hash in a source is the number of valid windows
+ *   inside that source whose canonical k-mer has that hash: forward and reverse-complement occurrences count together.  It is
+ *   clamped at 2^32 - 1 and is a uint32_t array parallel to the keys: abund[i] belongs to keys[i].
+ * ksp_sketch_cpu_abund / ksp_sketch_device_abund / ksp_sketch_host_abund: the calls above with out_abund / d_out_abund / *out_abund
+ *   (room for `capacity`; ksp_free for the host call's) beside the keys; the keys and offsets are those of the calls above, and
+ *   the overflow, size-query, argument and limit rules are the same (out_abund NULL with a capacity: KSP_E_ARG; the device call
+ *   asks for the same memory).  On the device the select pass's head of a run of equal (source, hash) entries writes
+ *   min(the next head's index - its own, 2^32 - 1) beside its hash.
+ * kspider_sketch with KSP_SKETCH_ABUND in flags: every signature has "abundances":[...] directly after "mins", parallel to it;
+ *   md5sum is unchanged (sourmash's ignores abundances).  A source's sketch is the union of its segments' sketches WITH THE
+ *   COUNTS ADDED (every window lies in exactly one piece of a cut record), clamped after adding; KSPIDER_SKETCH=host writes the
+ *   same bytes.  Without the flag the files are what they were.
+ * ksp_sig_read: host only — one .sig / .sig.gz file as the loaders read it: the first signature of that kSize; mins sorted,
+ *   a hash listed twice once, with its abundances added and clamped; *has_abund = 1 when the signature has "abundances" (else
+ *   abunds is untouched and may be NULL).  *n = the distinct mins.  More than `capacity`: KSP_E_OVERFLOW with *n set; mins NULL
+ *   with capacity 0 is the size query.  KSP_E_IO naming the file: unreadable, malformed, no signature of that kSize, or
+ *   "abundances" of another length than "mins".                                                                              */
 #define KSP_SKETCH_TILE_BASES 4096u
 #define KSP_SKETCH_PER_RECORD 1ull
 #define KSP_SKETCH_SEED 2ull
+#define KSP_SKETCH_ABUND 4ull
 typedef struct ksp_sketch_stats {
     uint64_t bases;            /* base bytes of the stream                                                        */
     uint64_t valid_kmers;      /* windows of ksize bases without a break byte (one over a source boundary that no
@@ -1027,6 +1083,15 @@ int ksp_sketch_host(int device, const uint8_t* seq, uint64_t n_bytes, const uint
 int ksp_fastx_info(const char* path, uint64_t out[4]);
 int ksp_fastx_load(const char* path, uint8_t* seq, uint64_t* rec_offsets, uint64_t* name_offsets, char* names);
 int kspider_sketch(const char* input, int kSize, uint64_t scaled, const char* out_dir, int user_threads, uint64_t flags);
+int ksp_sketch_cpu_abund(const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize, uint64_t max_hash,
+                         uint32_t seed, uint64_t* out_keys, uint32_t* out_abund, uint64_t capacity, uint64_t* out_offsets, uint64_t* needed);
+int ksp_sketch_device_abund(int device, const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* h_src_offsets, uint32_t n_sources, int ksize,
+                            uint64_t max_hash, uint32_t seed, uint64_t* d_out_keys, uint32_t* d_out_abund, uint64_t capacity,
+                            uint64_t* h_out_offsets, ksp_sketch_stats* stats);
+int ksp_sketch_host_abund(int device, const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize,
+                          uint64_t max_hash, uint32_t seed, uint64_t** out_keys, uint32_t** out_abund, uint64_t* out_offsets,
+                          ksp_sketch_stats* stats);
+int ksp_sig_read(const char* path, int kSize, uint64_t* mins, uint32_t* abunds, uint64_t capacity, uint64_t* n, int* has_abund);
 
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:

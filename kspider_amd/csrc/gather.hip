@@ -23,6 +23,10 @@
 //               queries is 0; the host reads that counter once per batch, after the live lists were compacted.
 //   tail        at KSP_GATHER_TAIL_CANDS live candidates or fewer ONE workgroup of 1 024 threads runs the remaining rounds with
 //               __syncthreads() between count and take (k_derep_tail's pattern); KSP_GATHER_TAIL=0: batches to the end.
+//   weighted    (ksp_gather_abund_*) the queries carry an abundance per hash.  k_gather_habund puts it at the holder slot
+//               of its (hash, query); the take (gather_take<true>: k_gather_take_w, k_gather_tail_w) sums a and a^2 over the slots
+//               it clears, compacts their abundances into the winner's own segment and selects the median there.  The greedy, the
+//               counts and every kernel of the unweighted call are what they were.
 // Every loop is bounded by a size the host computed; no workgroup waits on another; stores are plain vector stores.
 #include <cstdint>
 #include <cstdio>
@@ -30,6 +34,7 @@
 #include <cstring>
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -46,6 +51,7 @@ constexpr u32 kListMax = KSP_QUERY_LIST_MAX;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kTailThreads = 1024;
+constexpr u32 kTailWaves = kTailThreads / 64;
 constexpr u32 kNone = 0xFFFFFFFFu;
 // the sweeps hold what query mode's probe holds: 4 x (8 + 2) KiB and a few words per workgroup
 static_assert(2 * (kWaves * (kTileMax + kListMax) * 4 + 64) <= 160 * 1024, "two workgroups per CU");
@@ -272,8 +278,124 @@ __device__ inline void gather_offer(const GRound& R, const u32 c, const u32 u) {
     }
 }
 
-// what ONE wave does with query `tag` of the tile behind the counts of a round
-__device__ inline void gather_take(const GRound& R, const u32 tag, const u32 lane) {
+// ---- the weighted take: what a round's row says about the abundances of the hashes it takes
+struct GAbund {
+    const u32* habund;            // per holder slot: the abundance of its hash in its query
+    u32* vals;                    // = seg: the words of a taken segment are dead and hold the abundances it took
+    unsigned long long* qwfound;  // per query of the tile: w_found so far
+    ksp_gather_wrow* rows;        // the tile's rows in the order they were found
+};
+
+__device__ inline u64 shfl_down_u64(const u64 v, const int d) {
+    return ((u64)(u32)__shfl_down((int)(u32)(v >> 32), d) << 32) | (u32)__shfl_down((int)(u32)v, d);
+}
+
+// habund[h] = the abundance of entry e0 + i of the tile, h = the holder slot of (its key, its query).  tag[] is k_query_tag's.
+__global__ __launch_bounds__(kThreads) void k_gather_habund(const QTable T, const u64* __restrict__ q_keys, const u32* __restrict__ q_abund, const u32* __restrict__ tag,
+                                                            const u64 e0, const u32 E, const u32 H, u32* __restrict__ habund) {
+    const u64 span = (u64)gridDim.x * kThreads;
+    for (u64 i0 = (u64)blockIdx.x * kThreads + threadIdx.x; i0 < E; i0 += span * kProbeKeys) {
+        u64 k[kProbeKeys];
+        bool live[kProbeKeys];
+        u32 at[kProbeKeys];
+#pragma unroll
+        for (int x = 0; x < kProbeKeys; ++x) {
+            const u64 i = i0 + (u64)x * span;
+            live[x] = i < E;
+            k[x] = live[x] ? q_keys[e0 + i] : 0;
+        }
+        query_lookup(T, k, live, at);
+#pragma unroll
+        for (int x = 0; x < kProbeKeys; ++x) {
+            if (!live[x]) continue;   // (never for an entry of the tile: the table holds its key)
+            const u64 i = i0 + (u64)x * span;
+            const u32 mine = tag[i];
+            u32 lo = T.toff[at[x]], hi = T.toff[at[x] + 1];   // the holders of a key ascend
+            while (lo < hi) {
+                const u32 mid = lo + (hi - lo) / 2;
+                if (T.tq[mid] < mine) lo = mid + 1; else hi = mid;
+            }
+            if (lo < H && lo < T.toff[at[x] + 1] && T.tq[lo] == mine) atomicMax(&habund[lo], q_abund[e0 + i]);   // (max: an entry listed twice)
+        }
+    }
+}
+
+// chunks of 64 values a lane has in flight in a pass of the select: a pass is a chain of dependent loads from L2, as a look-up is
+constexpr u32 kSelectChunks = 4;
+
+// Twice the median of vals[0 .. n) (n >= 1), for the whole wave: v(k1) + v(k2), k1 = (n - 1) / 2 and k2 = n / 2 counted from 0 in
+// ascending order.  Up to 64 values are ranked in registers; more are selected by four passes over 8-bit digits from the top
+// with the wave's 256-bin histogram `hist` in LDS, and the upper value, when it is another one, is the smallest above the lower.
+__device__ inline u64 gather_median2(const u32* vals, const u32 n, u32* hist, const u32 lane) {
+    const u32 k1 = (n - 1) / 2, k2 = n / 2;
+    if (n <= 64) {
+        const bool has = lane < n;
+        const u32 a = has ? load_u32(&vals[lane]) : 0;
+        u32 rank = 0;
+        for (u32 j = 0; j < n; ++j) {   // (the same trips for every lane)
+            const u32 aj = (u32)__shfl((int)a, (int)j);
+            rank += (aj < a || (aj == a && j < lane)) ? 1u : 0u;
+        }
+        const unsigned long long b1 = __ballot(has && rank == k1), b2 = __ballot(has && rank == k2);
+        const u32 v1 = (u32)__shfl((int)a, __ffsll((long long)b1) - 1), v2 = (u32)__shfl((int)a, __ffsll((long long)b2) - 1);
+        return (u64)v1 + v2;
+    }
+    u32 prefix = 0, r = k1, eq = n;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        const u32 above = pass ? 0xFFFFFFFFu << (shift + 8) : 0u;   // the digits already chosen
+#pragma unroll
+        for (int b = 0; b < 4; ++b) hist[4 * lane + b] = 0;
+        query_group_sync<true>();
+        for (u32 i0 = 0; i0 < n; i0 += 64 * kSelectChunks) {   // (the same trips for every lane)
+            u32 v[kSelectChunks];
+#pragma unroll
+            for (u32 x = 0; x < kSelectChunks; ++x) v[x] = i0 + 64 * x + lane < n ? load_u32(&vals[i0 + 64 * x + lane]) : 0;
+#pragma unroll
+            for (u32 x = 0; x < kSelectChunks; ++x)
+                if (i0 + 64 * x + lane < n && (v[x] & above) == prefix) atomicAdd(&hist[(v[x] >> shift) & 255u], 1u);
+        }
+        query_group_sync<true>();
+        u32 c[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) c[b] = hist[4 * lane + b];
+        const u32 mine = c[0] + c[1] + c[2] + c[3];
+        u32 incl = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const u32 o = (u32)__shfl_up((int)incl, d);
+            if (lane >= (u32)d) incl += o;
+        }
+        const unsigned long long past = __ballot(incl > r);   // (not empty: the bins hold more than r values)
+        const int L = past ? __ffsll((long long)past) - 1 : 63;
+        u32 rr = r - (incl - mine), digit = 4 * lane, cnt = c[0];
+        if (rr >= c[0]) { rr -= c[0]; ++digit; cnt = c[1];
+            if (rr >= c[1]) { rr -= c[1]; ++digit; cnt = c[2];
+                if (rr >= c[2]) { rr -= c[2]; ++digit; cnt = c[3]; } } }
+        prefix |= (u32)__shfl((int)digit, L) << shift;
+        r = (u32)__shfl((int)rr, L);
+        eq = (u32)__shfl((int)cnt, L);
+        query_group_sync<true>();   // (the bins are read before the next pass clears them)
+    }
+    const u32 v1 = prefix;   // r = how many of the eq values equal to v1 lie before rank k1
+    if (k2 == k1 || r + 1 < eq) return 2ull * v1;
+    u32 next = 0xFFFFFFFFu;   // rank k2 is the smallest value above v1 (there is one: k2 < n)
+    for (u32 i0 = 0; i0 < n; i0 += 64 * kSelectChunks) {
+        u32 v[kSelectChunks];
+#pragma unroll
+        for (u32 x = 0; x < kSelectChunks; ++x) v[x] = i0 + 64 * x + lane < n ? load_u32(&vals[i0 + 64 * x + lane]) : 0;   // (0 is never above v1)
+#pragma unroll
+        for (u32 x = 0; x < kSelectChunks; ++x)
+            if (v[x] > v1 && v[x] < next) next = v[x];
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) next = min(next, (u32)__shfl_xor((int)next, d));
+    return (u64)v1 + next;
+}
+
+// what ONE wave does with query `tag` of the tile behind the counts of a round; kW: the weighted row (A and the wave's hist are set)
+template <bool kW>
+__device__ inline void gather_take(const GRound& R, const GAbund* A, u32* hist, const u32 tag, const u32 lane) {
     if (load_u32(&R.qdone[tag])) return;
     const unsigned long long w = load_u64(&R.best[tag]);
     if (w == 0) {   // nobody offered: nothing covers min_hashes of what is left
@@ -284,15 +406,62 @@ __device__ inline void gather_take(const GRound& R, const u32 tag, const u32 lan
     if (c >= R.n_cand) return;   // (never: an offer names its candidate)
     const u64 base = R.cbase[c];
     const u32 len = R.covl[c];
-    for (u32 i = lane; i < len; i += 64) {
-        const u32 h = R.seg[base + i];
-        const u32 bit = 1u << (h & 31);
-        if (load_u32(&R.alive[h >> 5]) & bit) atomicAnd(&R.alive[h >> 5], ~bit);
+    u64 sum = 0, sq_lo = 0, sq_hi = 0, median2 = 0;
+    if (kW) {
+        // the alive slots before they are cleared: their abundances summed, and compacted to the front of the segment, which
+        // nobody reads after this take — an abundance goes to an entry at or before its own slot's, which the wave has read by then
+        // (every trip loads its kSelectChunks chunks before it stores)
+        u32 n = 0;
+        for (u32 i0 = 0; i0 < len; i0 += 64 * kSelectChunks) {   // (the same trips for every lane; the loads of a step together)
+            u32 h[kSelectChunks], a[kSelectChunks];
+            bool on[kSelectChunks];
+#pragma unroll
+            for (u32 x = 0; x < kSelectChunks; ++x) h[x] = i0 + 64 * x + lane < len ? R.seg[base + i0 + 64 * x + lane] : 0;
+#pragma unroll
+            for (u32 x = 0; x < kSelectChunks; ++x) on[x] = i0 + 64 * x + lane < len && ((load_u32(&R.alive[h[x] >> 5]) >> (h[x] & 31)) & 1u);
+#pragma unroll
+            for (u32 x = 0; x < kSelectChunks; ++x) a[x] = on[x] ? A->habund[h[x]] : 0;
+#pragma unroll
+            for (u32 x = 0; x < kSelectChunks; ++x) {   // (a slot's bit is cleared by its own lane alone: the words read above hold for it)
+                const unsigned long long b = __ballot(on[x]);
+                if (on[x]) {
+                    const u64 aa = (u64)a[x] * a[x];
+                    atomicAnd(&R.alive[h[x] >> 5], ~(1u << (h[x] & 31)));
+                    sum += a[x];
+                    sq_lo += aa;
+                    sq_hi += sq_lo < aa;
+                    A->vals[base + n + (u32)__popcll(b & ((1ull << lane) - 1))] = a[x];
+                }
+                n += (u32)__popcll(b);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");   // the abundances are in memory before the wave reads them back
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const u64 lo = shfl_down_u64(sq_lo, d), hi = shfl_down_u64(sq_hi, d);
+            sum += shfl_down_u64(sum, d);
+            sq_lo += lo;
+            sq_hi += hi + (sq_lo < lo);
+        }
+        if (n) median2 = gather_median2(A->vals + base, n, hist, lane);   // (n = u >= min_hashes >= 1)
+    } else {
+        for (u32 i = lane; i < len; i += 64) {
+            const u32 h = R.seg[base + i];
+            const u32 bit = 1u << (h & 31);
+            if (load_u32(&R.alive[h >> 5]) & bit) atomicAnd(&R.alive[h >> 5], ~bit);
+        }
     }
     if (lane == 0) {
         const u32 rank = R.qrank[tag] + 1, rem = R.qrem[tag] - u;
         const unsigned long long at = atomicAdd(&R.ctrl[kRows], 1ull);
-        if (at < R.rows_cap) R.rows[at] = ksp_gather_row{R.q0 + tag, rank, (u32)R.ckey[c], len, u, rem};
+        if (kW) {
+            const unsigned long long found = A->qwfound[tag] + sum;
+            A->qwfound[tag] = found;
+            if (at < R.rows_cap) A->rows[at] = ksp_gather_wrow{R.q0 + tag, rank, (u32)R.ckey[c], len, u, rem, sum, found, sq_lo, sq_hi, median2};
+        } else if (at < R.rows_cap) {
+            R.rows[at] = ksp_gather_row{R.q0 + tag, rank, (u32)R.ckey[c], len, u, rem};
+        }
         R.qrank[tag] = rank;
         R.qrem[tag] = rem;
         R.best[tag] = 0;
@@ -340,18 +509,26 @@ __global__ __launch_bounds__(kThreads) void k_gather_count(const GRound R, const
 __global__ __launch_bounds__(kThreads) void k_gather_take(const GRound R) {
     if (load_u64(&R.ctrl[kGo]) == 0) return;
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (u64 tag = (u64)blockIdx.x * kWaves + wave; tag < R.nq; tag += (u64)gridDim.x * kWaves) gather_take(R, (u32)tag, lane);
+    for (u64 tag = (u64)blockIdx.x * kWaves + wave; tag < R.nq; tag += (u64)gridDim.x * kWaves) gather_take<false>(R, nullptr, nullptr, (u32)tag, lane);
+}
+
+// the same with the weighted rows
+__global__ __launch_bounds__(kThreads) void k_gather_take_w(const GRound R, const GAbund A) {
+    __shared__ u32 s_hist[kWaves][256];
+    if (load_u64(&R.ctrl[kGo]) == 0) return;
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (u64 tag = (u64)blockIdx.x * kWaves + wave; tag < R.nq; tag += (u64)gridDim.x * kWaves) gather_take<true>(R, &A, s_hist[wave], (u32)tag, lane);
 }
 
 // The remaining rounds by ONE workgroup: the same counts and takes, separated by __syncthreads() and not by dispatches.  A round
 // with a live query takes a candidate or finishes every query, so `bound` = the live candidates + 1 rounds suffice.  Hand-over:
 // the queries it finds unfinished must be the device's count of them (out[2] = 1 otherwise, and nothing runs).  out[0] = the
 // rounds that ran, out[1] = the queries still live (0 unless the bound was hit, which the host reports).
-__global__ __launch_bounds__(kTailThreads) void k_gather_tail(const GRound R, const u32* __restrict__ list0, const u32 n0, const u32* __restrict__ list1, const u32 n1,
-                                                              const u32 bound, u32* __restrict__ out) {
+template <bool kW>
+__device__ inline void gather_tail(const GRound& R, const GAbund* A, u32* hist, const u32* __restrict__ list0, const u32 n0, const u32* __restrict__ list1, const u32 n1,
+                                   const u32 bound, u32* __restrict__ out) {
     __shared__ u32 s_live;
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr u32 kTailWaves = kTailThreads / 64;
     if (threadIdx.x == 0) s_live = 0;
     __syncthreads();
     u32 mine = 0;
@@ -370,7 +547,7 @@ __global__ __launch_bounds__(kTailThreads) void k_gather_tail(const GRound R, co
         }
         __threadfence();
         __syncthreads();   // every offer of this round is made
-        for (u32 tag = wave; tag < R.nq; tag += kTailWaves) gather_take(R, tag, lane);
+        for (u32 tag = wave; tag < R.nq; tag += kTailWaves) gather_take<kW>(R, A, hist, tag, lane);
         __threadfence();
         __syncthreads();   // every take of this round is made
         if (threadIdx.x == 0) s_live = (u32)load_u64(&R.ctrl[kLiveQ]);
@@ -385,6 +562,17 @@ __global__ __launch_bounds__(kTailThreads) void k_gather_tail(const GRound R, co
         out[1] = live;
         out[2] = handed ? 0 : 1;
     }
+}
+
+__global__ __launch_bounds__(kTailThreads) void k_gather_tail(const GRound R, const u32* __restrict__ list0, const u32 n0, const u32* __restrict__ list1, const u32 n1,
+                                                              const u32 bound, u32* __restrict__ out) {
+    gather_tail<false>(R, nullptr, nullptr, list0, n0, list1, n1, bound, out);
+}
+
+__global__ __launch_bounds__(kTailThreads) void k_gather_tail_w(const GRound R, const GAbund A, const u32* __restrict__ list0, const u32 n0, const u32* __restrict__ list1,
+                                                                const u32 n1, const u32 bound, u32* __restrict__ out) {
+    __shared__ u32 s_hist[kTailWaves][256];
+    gather_tail<true>(R, &A, s_hist[threadIdx.x >> 6], list0, n0, list1, n1, bound, out);
 }
 
 // per query of the tile: nothing found yet, everything left; every query is live (the device's words were zeroed before)
@@ -432,6 +620,17 @@ __global__ void k_gather_rows(const GRound R, const u32 n_rows, const u32* __res
     }
 }
 
+// the same for the weighted rows `in`
+__global__ void k_gather_wrows(const GRound R, const ksp_gather_wrow* __restrict__ in, const u32 n_rows, const u32* __restrict__ qoff, ksp_gather_wrow* __restrict__ sorted) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n_rows; i += (u64)gridDim.x * blockDim.x) {
+        const ksp_gather_wrow r = in[i];
+        const u32 tag = r.query - R.q0;
+        if (tag >= R.nq || r.rank == 0) continue;
+        const u64 at = (u64)qoff[tag] + r.rank - 1;
+        if (at < n_rows) sorted[at] = r;
+    }
+}
+
 struct AsU64 {
     __host__ __device__ u64 operator()(const u32 v) const { return v; }
 };
@@ -462,10 +661,13 @@ int read_switches(const char* who, GatherSwitches& W) {
 }
 
 // The gather on the CURRENT device; the arguments have passed check_gather_args and read_switches.  The rows go to d_rows (room
-// for `capacity`) or, when h_rows is given, to the host vector.
-int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_keys, const u64* h_db_off, const u32 n_db, const u64* d_q_keys, const u64* h_q_off, const u32 n_q,
-                     const u32 min_hashes, const u32 max_matches, ksp_gather_row* d_rows, const u64 capacity, std::vector<ksp_gather_row>* h_rows, u64* n_rows,
+// for `capacity`) or, when h_rows is given, to the host vector.  Row = ksp_gather_wrow: the weighted call, d_q_abund beside the
+// query keys; Row = ksp_gather_row: d_q_abund is not read.
+template <class Row>
+int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_keys, const u64* h_db_off, const u32 n_db, const u64* d_q_keys, const u32* d_q_abund,
+                     const u64* h_q_off, const u32 n_q, const u32 min_hashes, const u32 max_matches, Row* d_rows, const u64 capacity, std::vector<Row>* h_rows, u64* n_rows,
                      ksp_gather_stats* stats) {
+    constexpr bool kW = std::is_same<Row, ksp_gather_wrow>::value;
     int rc = KSP_OK;
     ksp_gather_stats S;
     std::memset(&S, 0, sizeof S);
@@ -484,7 +686,7 @@ int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_k
     u64 *d_db_off = nullptr, *d_q_off = nullptr;
     u32 *d_list[2] = {nullptr, nullptr}, *d_fill[2] = {nullptr, nullptr};
     u32 *qrank = nullptr, *qrem = nullptr, *qdone = nullptr, *qoff = nullptr, *d_out = nullptr;
-    unsigned long long *ctrl = nullptr, *best = nullptr;
+    unsigned long long *ctrl = nullptr, *best = nullptr, *qwfound = nullptr;
     u64* cand_key = nullptr;   // the candidates as the sweep found them; they grow when a tile finds more
     u32* cand_ovl = nullptr;
     u64 cand_cap = 0;
@@ -499,8 +701,9 @@ int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_k
     cand_cap = std::max<u64>(KSP_GATHER_FIRST_CANDS, 4ull * n_db);
     // ---- what the call holds whatever the tiles find, sized and checked first: 8 per source (offsets), 8 per source with entries
     // (its list and the list of those with a candidate), 24 per query of a tile, the table, the first candidate buffer, the scratch
-    if ((rc = ksp::device_fits(who, 8ull * ((u64)n_db + n_q + 2) + 8ull * (probes[0].size() + probes[1].size()) + 24ull * kTileMax + B.bytes() + 12 * cand_cap + B.tb + 256,
-                               "8 per source, 8 per source with entries, 40 per entry of the largest query tile, its directory, the candidates, the sort's scratch")))
+    if ((rc = ksp::device_fits(who, 8ull * ((u64)n_db + n_q + 2) + 8ull * (probes[0].size() + probes[1].size()) + (kW ? 32ull : 24ull) * kTileMax + B.bytes() + 12 * cand_cap + B.tb + 256,
+                               kW ? "8 per source, 8 per source with entries, 40 per entry of the largest query tile, its directory, the candidates, the sort's scratch, 8 per query of a tile"
+                                  : "8 per source, 8 per source with entries, 40 per entry of the largest query tile, its directory, the candidates, the sort's scratch")))
         return rc;
     if ((rc = A.alloc(&d_db_off, (size_t)n_db + 1)) || (rc = A.alloc(&d_q_off, (size_t)n_q + 1)) || (rc = A.alloc(&ctrl, (size_t)kCtrlWords)) || (rc = A.alloc(&d_out, 4))) return rc;
     for (int c = 0; c < 2; ++c)
@@ -508,6 +711,7 @@ int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_k
     if ((rc = A.alloc(&best, (size_t)kTileMax)) || (rc = A.alloc(&qrank, (size_t)kTileMax)) || (rc = A.alloc(&qrem, (size_t)kTileMax)) || (rc = A.alloc(&qdone, (size_t)kTileMax)) ||
         (rc = A.alloc(&qoff, (size_t)kTileMax)))
         return rc;
+    if (kW && (rc = A.alloc(&qwfound, (size_t)kTileMax))) return rc;
     if ((rc = A.alloc(&cand_key, (size_t)cand_cap)) || (rc = A.alloc(&cand_ovl, (size_t)cand_cap))) return rc;
     if (e_max && ((rc = query_table_alloc(A, B)) || (rc = A.alloc_bytes(&B.tmp, B.tb)))) return rc;
     KSP_TRY_HIP(hipMemcpy(d_db_off, h_db_off, ((size_t)n_db + 1) * 8, hipMemcpyHostToDevice));
@@ -569,8 +773,8 @@ int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_k
         // ---- the tile's own arrays: the sorted candidates (key 8, overlap 4, base 8, dead 4, two live lists 2 x 2 x 4), the sort's
         // scratch; then, when the slots are known, 4 per slot and a bit per holder; then the rows
         u64 *ckey = nullptr, *cbase = nullptr, n_slots = 0;
-        u32 *covl = nullptr, *cdead = nullptr, *live[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *seg = nullptr, *alive = nullptr;
-        ksp_gather_row *rows = nullptr, *sorted = nullptr;
+        u32 *covl = nullptr, *cdead = nullptr, *live[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *seg = nullptr, *alive = nullptr, *habund = nullptr;
+        Row *rows = nullptr, *sorted = nullptr;
         void* tmp2 = nullptr;
         size_t tb_sort = 0, tb_scan = 0, tb2 = 0;
         const auto ovl64 = [](const u32* p) { return rocprim::make_transform_iterator(p, AsU64()); };
@@ -601,10 +805,21 @@ int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_k
         const u64 alive_words = ((u64)H + 31) / 32;
         // a row removes min_hashes or more of its query, and a candidate is taken once
         const u64 rows_cap = std::min<u64>(std::min<u64>(n_cand, (u64)E / min_hashes), max_matches ? (u64)nq * max_matches : ~0ull);
-        if ((rc = ksp::device_fits(who, 4 * n_slots + 4 * alive_words + 48 * rows_cap + 64, "4 per matched hash of a candidate, a bit per query hash, 48 per possible row"))) goto done;
+        if ((rc = ksp::device_fits(who, 4 * n_slots + 4 * alive_words + 2 * sizeof(Row) * rows_cap + (kW ? 4ull * H : 0) + 64,
+                                   kW ? "4 per matched hash of a candidate, a bit per query hash, 4 per holder of the query table, 128 per possible row"
+                                      : "4 per matched hash of a candidate, a bit per query hash, 48 per possible row")))
+            goto done;
         if ((rc = A.alloc(&seg, (size_t)n_slots)) || (rc = A.alloc(&alive, (size_t)alive_words)) || (rc = A.alloc(&rows, (size_t)rows_cap + 1)) || (rc = A.alloc(&sorted, (size_t)rows_cap + 1)))
             goto done;
         KSP_TRY_HIP(hipMemsetAsync(alive, 0xFF, (size_t)alive_words * 4, nullptr));
+        if (kW) {   // the abundance of every (hash, query) of the tile at its holder slot
+            if ((rc = A.alloc(&habund, (size_t)H))) goto done;
+            KSP_TRY_HIP(hipMemsetAsync(habund, 0, (size_t)H * 4, nullptr));
+            KSP_TRY_HIP(hipMemsetAsync(qwfound, 0, (size_t)kTileMax * 8, nullptr));
+            hipLaunchKernelGGL(k_gather_habund, dim3(G.grid_of(((u64)E + (u64)kThreads * kProbeKeys - 1) / ((u64)kThreads * kProbeKeys))), dim3(kThreads), 0, nullptr, T, d_q_keys, d_q_abund,
+                               (const u32*)B.tag, e0, E, H, habund);
+            KSP_TRY_HIP(hipGetLastError());
+        }
         P.ckey = ckey; P.cbase = cbase; P.n_cand = n_cand; P.seg = seg; P.n_slots = (u32)n_slots;
         if (n_fill[0]) {
             P.list = d_fill[0]; P.n_list = (u32)n_fill[0];
@@ -618,7 +833,8 @@ int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_k
         KSP_TRY_HIP(hipEventRecord(ev[3], nullptr));
         // ---- the rounds
         {
-            const GRound R{ckey, covl, cbase, seg, alive, cdead, best, qrank, qrem, qdone, n_cand, nq, q0, min_hashes, max_matches, rows, (u32)rows_cap, ctrl};
+            const GRound R{ckey, covl, cbase, seg, alive, cdead, best, qrank, qrem, qdone, n_cand, nq, q0, min_hashes, max_matches, kW ? nullptr : (ksp_gather_row*)(void*)rows, (u32)rows_cap, ctrl};
+            const GAbund AB{habund, seg, qwfound, kW ? (ksp_gather_wrow*)(void*)rows : nullptr};
             const unsigned gq = (unsigned)(((u64)nq + 255) / 256), gc = G.grid_of(((u64)n_cand + kThreads - 1) / kThreads);
             u64 n_live[2] = {0, 0};
             int cur = 0;
@@ -636,8 +852,12 @@ int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_k
                 const u64 n_both = n_live[0] + n_live[1];
                 if (W.tail && n_both <= W.tail_cands) {
                     u32 h_out[4] = {0, 0, 0, 0};
-                    hipLaunchKernelGGL(k_gather_tail, dim3(1), dim3(kTailThreads), 0, nullptr, R, (const u32*)live[cur][0], (u32)n_live[0], (const u32*)live[cur][1], (u32)n_live[1],
-                                       (u32)n_both + 1, d_out);
+                    if (kW)
+                        hipLaunchKernelGGL(k_gather_tail_w, dim3(1), dim3(kTailThreads), 0, nullptr, R, AB, (const u32*)live[cur][0], (u32)n_live[0], (const u32*)live[cur][1], (u32)n_live[1],
+                                           (u32)n_both + 1, d_out);
+                    else
+                        hipLaunchKernelGGL(k_gather_tail, dim3(1), dim3(kTailThreads), 0, nullptr, R, (const u32*)live[cur][0], (u32)n_live[0], (const u32*)live[cur][1], (u32)n_live[1],
+                                           (u32)n_both + 1, d_out);
                     KSP_TRY_HIP(hipGetLastError());
                     KSP_TRY_HIP(hipMemcpy(h_out, d_out, 12, hipMemcpyDeviceToHost));
                     if (h_out[2]) { ksp::set_error(std::string(who) + ": the tail's count of live queries does not match the batches'"); rc = KSP_E_HIP; goto done; }
@@ -651,7 +871,8 @@ int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_k
                 const unsigned g0 = G.grid_of((n_live[0] + kWaves - 1) / kWaves), g1 = G.grid_of(n_live[1]);
                 for (u32 r = 0; r < KSP_GATHER_BATCH; ++r) {
                     hipLaunchKernelGGL(k_gather_count, dim3(g0 + g1), dim3(kThreads), 0, nullptr, R, (const u32*)live[cur][0], (u32)n_live[0], (u32)g0, (const u32*)live[cur][1], (u32)n_live[1]);
-                    hipLaunchKernelGGL(k_gather_take, dim3(G.grid_of(((u64)nq + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, R);
+                    if (kW) hipLaunchKernelGGL(k_gather_take_w, dim3(G.grid_of(((u64)nq + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, R, AB);
+                    else hipLaunchKernelGGL(k_gather_take, dim3(G.grid_of(((u64)nq + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, R);
                 }
                 // the dead leave the lists
                 KSP_TRY_HIP(hipMemsetAsync(&ctrl[kKept0], 0, 16, nullptr));
@@ -674,14 +895,15 @@ int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_k
             if (found) {
                 size_t b = B.tb;
                 KSP_TRY_HIP(rocprim::exclusive_scan(B.tmp, b, (const u32*)qrank, qoff, 0u, (size_t)nq, rocprim::plus<u32>(), (hipStream_t) nullptr));
-                hipLaunchKernelGGL(k_gather_rows, dim3(G.grid_of((found + 255) / 256)), dim3(256), 0, nullptr, R, (u32)found, (const u32*)qoff, sorted);
+                if constexpr (kW) hipLaunchKernelGGL(k_gather_wrows, dim3(G.grid_of((found + 255) / 256)), dim3(256), 0, nullptr, R, (const ksp_gather_wrow*)rows, (u32)found, (const u32*)qoff, sorted);
+                else hipLaunchKernelGGL(k_gather_rows, dim3(G.grid_of((found + 255) / 256)), dim3(256), 0, nullptr, R, (u32)found, (const u32*)qoff, sorted);
                 KSP_TRY_HIP(hipGetLastError());
                 if (h_rows) {
                     const size_t at = h_rows->size();
                     h_rows->resize(at + (size_t)found);
-                    KSP_TRY_HIP(hipMemcpy(h_rows->data() + at, sorted, (size_t)found * sizeof(ksp_gather_row), hipMemcpyDeviceToHost));
+                    KSP_TRY_HIP(hipMemcpy(h_rows->data() + at, sorted, (size_t)found * sizeof(Row), hipMemcpyDeviceToHost));
                 } else if (rows_done < capacity) {
-                    KSP_TRY_HIP(hipMemcpyAsync(d_rows + rows_done, sorted, (size_t)std::min<u64>(found, capacity - rows_done) * sizeof(ksp_gather_row), hipMemcpyDeviceToDevice, nullptr));
+                    KSP_TRY_HIP(hipMemcpyAsync(d_rows + rows_done, sorted, (size_t)std::min<u64>(found, capacity - rows_done) * sizeof(Row), hipMemcpyDeviceToDevice, nullptr));
                 }
                 rows_done += found;
             }
@@ -695,6 +917,7 @@ int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_k
         for (void* p : {(void*)ckey, (void*)covl, (void*)cbase, (void*)cdead, (void*)live[0][0], (void*)live[0][1], (void*)live[1][0], (void*)live[1][1], (void*)seg, (void*)alive, (void*)rows,
                         (void*)sorted, tmp2})
             KSP_TRY_HIP(A.release(p));
+        if (habund) KSP_TRY_HIP(A.release(habund));
     }
     S.rows = rows_done;
     *n_rows = rows_done;
@@ -719,7 +942,7 @@ extern "C" int ksp_gather_device(int device, const uint64_t* d_db_keys, const ui
     if (!d_rows && capacity) { ksp::set_error(std::string(who) + ": d_rows is NULL but capacity is not 0"); return KSP_E_ARG; }
     if (const int rc = read_switches(who, W)) return rc;
     if (const int rc = ksp::set_device(who, device)) return rc;
-    return gather_on_device(who, W, d_db_keys, h_db_offsets, n_db, d_q_keys, h_q_offsets, n_q, min_hashes, max_matches, d_rows, capacity, nullptr, n_rows, stats);
+    return gather_on_device<ksp_gather_row>(who, W, d_db_keys, h_db_offsets, n_db, d_q_keys, nullptr, h_q_offsets, n_q, min_hashes, max_matches, d_rows, capacity, nullptr, n_rows, stats);
 }
 
 extern "C" int ksp_gather_host(const uint64_t* db_keys, const uint64_t* db_offsets, uint32_t n_db, const uint64_t* q_keys, const uint64_t* q_offsets, uint32_t n_q,
@@ -741,7 +964,7 @@ extern "C" int ksp_gather_host(const uint64_t* db_keys, const uint64_t* db_offse
     KSP_TRY_HIP(hipMemcpy(d_db, db_keys, (size_t)n_dbk * 8, hipMemcpyHostToDevice));
     KSP_TRY_HIP(hipMemcpy(d_q, q_keys, (size_t)n_qk * 8, hipMemcpyHostToDevice));
     try {
-        rc = gather_on_device(who, W, d_db, db_offsets, n_db, d_q, q_offsets, n_q, min_hashes, max_matches, nullptr, 0, &got, &found, stats);
+        rc = gather_on_device<ksp_gather_row>(who, W, d_db, db_offsets, n_db, d_q, nullptr, q_offsets, n_q, min_hashes, max_matches, nullptr, 0, &got, &found, stats);
     } catch (const std::bad_alloc&) {
         ksp::set_error(std::string(who) + ": out of host memory");
         rc = KSP_E_LIMIT;
@@ -750,6 +973,56 @@ extern "C" int ksp_gather_host(const uint64_t* db_keys, const uint64_t* db_offse
     out = (ksp_gather_row*)std::malloc(std::max<size_t>(got.size(), 1) * sizeof(ksp_gather_row));
     if (!out) { ksp::set_error(std::string(who) + ": out of host memory"); rc = KSP_E_LIMIT; goto done; }
     if (!got.empty()) std::memcpy(out, got.data(), got.size() * sizeof(ksp_gather_row));
+    *rows = out;
+    *n_rows = found;
+done:
+    return rc;
+}
+
+extern "C" int ksp_gather_abund_device(int device, const uint64_t* d_db_keys, const uint64_t* h_db_offsets, uint32_t n_db, const uint64_t* d_q_keys, const uint32_t* d_q_abund,
+                                       const uint64_t* h_q_offsets, uint32_t n_q, uint32_t min_hashes, uint32_t max_matches, ksp_gather_wrow* d_rows, uint64_t capacity,
+                                       uint64_t* n_rows, ksp_gather_stats* stats) {
+    const char* who = "ksp_gather_abund_device";
+    GatherSwitches W;
+    if (!d_q_abund) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+    if (const int rc = check_gather_args(who, d_db_keys, h_db_offsets, n_db, d_q_keys, h_q_offsets, n_q, min_hashes, n_rows)) return rc;
+    if (!d_rows && capacity) { ksp::set_error(std::string(who) + ": d_rows is NULL but capacity is not 0"); return KSP_E_ARG; }
+    if (const int rc = read_switches(who, W)) return rc;
+    if (const int rc = ksp::set_device(who, device)) return rc;
+    return gather_on_device<ksp_gather_wrow>(who, W, d_db_keys, h_db_offsets, n_db, d_q_keys, d_q_abund, h_q_offsets, n_q, min_hashes, max_matches, d_rows, capacity, nullptr, n_rows,
+                                             stats);
+}
+
+extern "C" int ksp_gather_abund_host(const uint64_t* db_keys, const uint64_t* db_offsets, uint32_t n_db, const uint64_t* q_keys, const uint32_t* q_abund, const uint64_t* q_offsets,
+                                     uint32_t n_q, uint32_t min_hashes, uint32_t max_matches, int device, ksp_gather_wrow** rows, uint64_t* n_rows, ksp_gather_stats* stats) {
+    const char* who = "ksp_gather_abund_host";
+    GatherSwitches W;
+    if (!rows || !q_abund) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+    if (const int rc = check_gather_args(who, db_keys, db_offsets, n_db, q_keys, q_offsets, n_q, min_hashes, n_rows)) return rc;
+    if (const int rc = read_switches(who, W)) return rc;
+    if (const int rc = ksp::set_device(who, device)) return rc;
+    int rc = KSP_OK;
+    ksp::DeviceArena A;
+    const u64 n_dbk = db_offsets[n_db], n_qk = q_offsets[n_q];
+    u64 *d_db = nullptr, *d_q = nullptr, found = 0;
+    u32* d_a = nullptr;
+    std::vector<ksp_gather_wrow> got;
+    ksp_gather_wrow* out = nullptr;
+    if ((rc = ksp::device_fits(who, 8ull * (n_dbk + n_qk + 2) + 4ull * (n_qk + 1), "the keys of both sides and the queries' abundances"))) return rc;
+    if ((rc = A.alloc(&d_db, (size_t)n_dbk + 1)) || (rc = A.alloc(&d_q, (size_t)n_qk + 1)) || (rc = A.alloc(&d_a, (size_t)n_qk + 1))) return rc;
+    KSP_TRY_HIP(hipMemcpy(d_db, db_keys, (size_t)n_dbk * 8, hipMemcpyHostToDevice));
+    KSP_TRY_HIP(hipMemcpy(d_q, q_keys, (size_t)n_qk * 8, hipMemcpyHostToDevice));
+    KSP_TRY_HIP(hipMemcpy(d_a, q_abund, (size_t)n_qk * 4, hipMemcpyHostToDevice));
+    try {
+        rc = gather_on_device<ksp_gather_wrow>(who, W, d_db, db_offsets, n_db, d_q, d_a, q_offsets, n_q, min_hashes, max_matches, nullptr, 0, &got, &found, stats);
+    } catch (const std::bad_alloc&) {
+        ksp::set_error(std::string(who) + ": out of host memory");
+        rc = KSP_E_LIMIT;
+    }
+    if (rc != KSP_OK) goto done;
+    out = (ksp_gather_wrow*)std::malloc(std::max<size_t>(got.size(), 1) * sizeof(ksp_gather_wrow));
+    if (!out) { ksp::set_error(std::string(who) + ": out of host memory"); rc = KSP_E_LIMIT; goto done; }
+    if (!got.empty()) std::memcpy(out, got.data(), got.size() * sizeof(ksp_gather_wrow));
     *rows = out;
     *n_rows = found;
 done:

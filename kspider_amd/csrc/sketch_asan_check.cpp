@@ -5,6 +5,14 @@
 //   sketch_asan_check sketch INPUT K SCALED OUT [--per-record]
 //                                                kspider_sketch in host mode with 2 threads (set KSPIDER_SKETCH_BATCH_BYTES for
 //                                                small batches), then the rc line
+//   sketch_asan_check abund INPUT K SCALED OUT [--per-record]
+//                                                the same with KSP_SKETCH_ABUND; then every file of OUT back through ksp_sig_read
+//                                                into buffers of exactly the reported sizes: "sig <rc> <mins> <sum of the
+//                                                abundances> <file>" per file, in the order of the names, then the rc line
+//   sketch_asan_check sigs K FILE...             every file through ksp_sig_read alone, the same lines
+#include <dirent.h>
+
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,6 +20,21 @@
 #include <vector>
 
 #include "../../include/kspider_amd.h"
+
+// one signature file through the size query and, when that accepts it, the read into buffers of exactly that size
+static void read_sig(const std::string& path, const int k) {
+    uint64_t n = 0, sum = 0;
+    int has = 0;
+    int rc = ksp_sig_read(path.c_str(), k, nullptr, nullptr, 0, &n, &has);
+    if (rc == KSP_OK || rc == KSP_E_OVERFLOW) {
+        std::vector<uint64_t> mins((size_t)(n ? n : 1));
+        std::vector<uint32_t> abunds((size_t)(n ? n : 1));
+        rc = ksp_sig_read(path.c_str(), k, mins.data(), abunds.data(), n, &n, &has);
+        if (rc == KSP_OK && has)
+            for (uint64_t i = 0; i < n; ++i) sum += abunds[(size_t)i];
+    }
+    std::printf("sig %d %llu %llu %s\n", rc, (unsigned long long)n, (unsigned long long)sum, path.c_str());
+}
 
 int main(int argc, char** argv) {
     const std::string cmd = argc > 1 ? argv[1] : "";
@@ -38,6 +61,24 @@ int main(int argc, char** argv) {
         std::printf("rc %d %s\n", rc, rc ? ksp_last_error() : "");
         return 0;
     }
-    std::fprintf(stderr, "usage: %s read FILE... | sketch INPUT K SCALED OUT [--per-record]\n", argv[0]);
+    if (cmd == "abund" && (argc == 6 || (argc == 7 && std::strcmp(argv[6], "--per-record") == 0))) {
+        setenv("KSPIDER_SKETCH", "host", 1);
+        const int rc = kspider_sketch(argv[2], std::atoi(argv[3]), std::strtoull(argv[4], nullptr, 10), argv[5], 2, KSP_SKETCH_ABUND | (argc == 7 ? KSP_SKETCH_PER_RECORD : 0));
+        std::vector<std::string> names;
+        if (DIR* d = opendir(argv[5])) {
+            while (const dirent* e = readdir(d))
+                if (e->d_name[0] != '.') names.push_back(e->d_name);
+            closedir(d);
+        }
+        std::sort(names.begin(), names.end());
+        for (const std::string& n : names) read_sig(std::string(argv[5]) + "/" + n, std::atoi(argv[3]));
+        std::printf("rc %d %s\n", rc, rc ? ksp_last_error() : "");
+        return 0;
+    }
+    if (cmd == "sigs" && argc > 3) {
+        for (int i = 3; i < argc; ++i) read_sig(argv[i], std::atoi(argv[2]));
+        return 0;
+    }
+    std::fprintf(stderr, "usage: %s read FILE... | sketch INPUT K SCALED OUT [--per-record] | abund INPUT K SCALED OUT [--per-record] | sigs K FILE...\n", argv[0]);
     return 2;
 }

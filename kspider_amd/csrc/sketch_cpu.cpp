@@ -24,6 +24,55 @@ uint64_t word_at(const uint8_t* p, const uint64_t len, const uint64_t i) {
     return w;
 }
 
+// ksp_sketch_cpu and, with counts (out_abund may then be NULL only with capacity 0), ksp_sketch_cpu_abund
+int sketch_cpu(const char* who, const bool counted, const uint8_t* seq, const uint64_t n_bytes, const uint64_t* src_offsets, const uint32_t n_sources, const int ksize,
+               const uint64_t max_hash, const uint32_t seed, uint64_t* out_keys, uint32_t* out_abund, const uint64_t capacity, uint64_t* out_offsets, uint64_t* needed) {
+    if (!out_offsets || !needed || (!out_keys && capacity) || (counted && !out_abund && capacity)) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+    if (const int rc = ksp::check_sketch_args(who, seq, n_bytes, src_offsets, n_sources, ksize)) return rc;
+    try {
+        const unsigned k = (unsigned)ksize;
+        std::vector<uint64_t> all, run;
+        std::vector<uint32_t> counts;
+        out_offsets[0] = 0;
+        for (uint32_t s = 0; s < n_sources; ++s) {
+            run.clear();
+            sk::Kmer fw{0, 0};   // the last min(have, k) bases, right-aligned
+            unsigned have = 0;   // bases since the last break, capped at k
+            for (uint64_t p = src_offsets[s]; p < src_offsets[s + 1]; ++p) {
+                const unsigned c = seq[p];
+                if (!sk::is_base(c)) { have = 0; fw = sk::Kmer{0, 0}; continue; }
+                fw = sk::shift_left(fw, 2);
+                fw.lo |= sk::base_code(c);
+                if (have < k) ++have;
+                if (have < k) continue;
+                const sk::Kmer left = sk::shift_left(fw, 128 - 2 * k);   // (drops the bases older than k)
+                const uint64_t h = sk::kmer_hash(sk::canonical(left, k), k, seed);
+                if (h <= max_hash) run.push_back(h);
+            }
+            std::sort(run.begin(), run.end());
+            if (counted)
+                for (size_t i = 0, j = 0; i < run.size(); i = j) {   // the length of every run of equal hashes
+                    while (j < run.size() && run[j] == run[i]) ++j;
+                    counts.push_back((uint32_t)std::min<uint64_t>(j - i, 0xFFFFFFFFull));
+                }
+            run.erase(std::unique(run.begin(), run.end()), run.end());
+            all.insert(all.end(), run.begin(), run.end());
+            out_offsets[s + 1] = all.size();
+        }
+        *needed = all.size();
+        if (all.size() > capacity) {
+            ksp::set_error(std::string(who) + ": " + std::to_string(all.size()) + " keys, room for " + std::to_string(capacity));
+            return KSP_E_OVERFLOW;
+        }
+        if (!all.empty()) std::memcpy(out_keys, all.data(), 8 * all.size());
+        if (counted && !counts.empty()) std::memcpy(out_abund, counts.data(), 4 * counts.size());
+        return KSP_OK;
+    } catch (const std::bad_alloc&) {
+        ksp::set_error(std::string(who) + ": out of host memory");
+        return KSP_E_LIMIT;
+    }
+}
+
 }  // namespace
 
 int ksp::check_sketch_args(const char* who, const void* seq, const uint64_t n_bytes, const uint64_t* off, const uint32_t n_sources, const int ksize) {
@@ -77,42 +126,10 @@ extern "C" int ksp_sketch_kmer_hash(const char* text, int ksize, uint32_t seed, 
 
 extern "C" int ksp_sketch_cpu(const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize, uint64_t max_hash,
                               uint32_t seed, uint64_t* out_keys, uint64_t capacity, uint64_t* out_offsets, uint64_t* needed) {
-    const char* who = "ksp_sketch_cpu";
-    if (!out_offsets || !needed || (!out_keys && capacity)) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
-    if (const int rc = ksp::check_sketch_args(who, seq, n_bytes, src_offsets, n_sources, ksize)) return rc;
-    try {
-        const unsigned k = (unsigned)ksize;
-        std::vector<uint64_t> all, run;
-        out_offsets[0] = 0;
-        for (uint32_t s = 0; s < n_sources; ++s) {
-            run.clear();
-            sk::Kmer fw{0, 0};   // the last min(have, k) bases, right-aligned
-            unsigned have = 0;   // bases since the last break, capped at k
-            for (uint64_t p = src_offsets[s]; p < src_offsets[s + 1]; ++p) {
-                const unsigned c = seq[p];
-                if (!sk::is_base(c)) { have = 0; fw = sk::Kmer{0, 0}; continue; }
-                fw = sk::shift_left(fw, 2);
-                fw.lo |= sk::base_code(c);
-                if (have < k) ++have;
-                if (have < k) continue;
-                const sk::Kmer left = sk::shift_left(fw, 128 - 2 * k);   // (drops the bases older than k)
-                const uint64_t h = sk::kmer_hash(sk::canonical(left, k), k, seed);
-                if (h <= max_hash) run.push_back(h);
-            }
-            std::sort(run.begin(), run.end());
-            run.erase(std::unique(run.begin(), run.end()), run.end());
-            all.insert(all.end(), run.begin(), run.end());
-            out_offsets[s + 1] = all.size();
-        }
-        *needed = all.size();
-        if (all.size() > capacity) {
-            ksp::set_error(std::string(who) + ": " + std::to_string(all.size()) + " keys, room for " + std::to_string(capacity));
-            return KSP_E_OVERFLOW;
-        }
-        if (!all.empty()) std::memcpy(out_keys, all.data(), 8 * all.size());
-        return KSP_OK;
-    } catch (const std::bad_alloc&) {
-        ksp::set_error(std::string(who) + ": out of host memory");
-        return KSP_E_LIMIT;
-    }
+    return sketch_cpu("ksp_sketch_cpu", false, seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, out_keys, nullptr, capacity, out_offsets, needed);
+}
+
+extern "C" int ksp_sketch_cpu_abund(const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize, uint64_t max_hash,
+                                    uint32_t seed, uint64_t* out_keys, uint32_t* out_abund, uint64_t capacity, uint64_t* out_offsets, uint64_t* needed) {
+    return sketch_cpu("ksp_sketch_cpu_abund", true, seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, out_keys, out_abund, capacity, out_offsets, needed);
 }

@@ -3,7 +3,8 @@
 //   feed     the input files in order, read `threads` at a time (fastx_reader.cpp); what is read and not yet sent waits as pieces
 //   batch    at most `batch_bytes` bytes of pieces back to back, each a segment of one source.  A piece that does not fit is cut:
 //            the batch takes what it has room for, and the rest starts ksize - 1 bytes before the cut, so every window of ksize
-//            bytes lies whole in one of the two.  A source's sketch is the union of its segments' sketches.
+//            bytes lies whole in one of the two.  A source's sketch is the union of its segments' sketches; with KSP_SKETCH_ABUND
+//            the counts of a hash in its segments are added (every window lies in exactly one segment) and clamped after adding.
 //   pipeline two batch buffers (page-locked in device mode): the next one is filled by a thread while this one is hashed
 //   write    the signatures at the end, each through .partial and a rename
 #include <glob.h>
@@ -24,6 +25,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/kspider_amd.h"
@@ -133,8 +135,9 @@ std::string json_text(const std::string& s) {
     return out + "\"";
 }
 
-// the signature file of one source: the fields of the files sourmash writes, in a fixed order
-std::string sig_text(const std::string& filename, const int ksize, const uint32_t seed, const uint64_t max_hash, const std::vector<uint64_t>& mins) {
+// the signature file of one source: the fields of the files sourmash writes, in a fixed order; abund: "abundances" behind "mins"
+std::string sig_text(const std::string& filename, const int ksize, const uint32_t seed, const uint64_t max_hash, const std::vector<uint64_t>& mins,
+                     const std::vector<uint32_t>* abund) {
     std::string list;
     Md5 md5;
     char num[24];
@@ -145,6 +148,13 @@ std::string sig_text(const std::string& filename, const int ksize, const uint32_
         md5.add(num, (size_t)n);
         if (i) list += ',';
         list.append(num, (size_t)n);
+    }
+    if (abund) {   // (the MD5 is over ksize and the mins alone, as sourmash's)
+        list += "],\"abundances\":[";
+        for (size_t i = 0; i < abund->size(); ++i) {
+            if (i) list += ',';
+            list += std::to_string((*abund)[i]);
+        }
     }
     return "[{\"class\":\"sourmash_signature\",\"email\":\"\",\"hash_function\":\"0.murmur64\",\"filename\":" + json_text(filename) +
            ",\"license\":\"CC0\",\"version\":0.4,\"signatures\":[{\"num\":0,\"ksize\":" + std::to_string(ksize) + ",\"seed\":" + std::to_string(seed) +
@@ -286,27 +296,36 @@ uint64_t env_bytes(const char* name, const uint64_t fallback, const uint64_t lo)
     return v;
 }
 
-// the sketches of one batch, appended to the keys of their sources
+// the sketches of one batch, appended to the keys of their sources (counts: and their counts to `counts`)
 void run_batch(const Batch& b, const bool on_host, const int device, const int ksize, const uint64_t max_hash, const uint32_t seed,
-               std::vector<std::vector<uint64_t>>& keys, std::vector<uint32_t>& segments, ksp_sketch_stats& total) {
+               std::vector<std::vector<uint64_t>>& keys, std::vector<std::vector<uint32_t>>* counts, std::vector<uint32_t>& segments, ksp_sketch_stats& total) {
     const uint32_t n_seg = (uint32_t)b.source.size();
     if (n_seg == 0) return;
     std::vector<uint64_t> out_off((size_t)n_seg + 1, 0), host_keys;
+    std::vector<uint32_t> host_abund;
     uint64_t* got = nullptr;
+    uint32_t* got_abund = nullptr;
     if (on_host) {
         uint64_t needed = 0;
         const double share = ((double)max_hash + 1.0) / 18446744073709551616.0;
         host_keys.resize((size_t)std::min<uint64_t>(b.n_bytes, (uint64_t)((double)b.n_bytes * share * 1.25) + 4096));
-        int rc = ksp_sketch_cpu(b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, host_keys.data(), host_keys.size(), out_off.data(), &needed);
+        const auto call = [&]() {
+            if (!counts) return ksp_sketch_cpu(b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, host_keys.data(), host_keys.size(), out_off.data(), &needed);
+            host_abund.resize(host_keys.size());
+            return ksp_sketch_cpu_abund(b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, host_keys.data(), host_abund.data(), host_keys.size(), out_off.data(), &needed);
+        };
+        int rc = call();
         if (rc == KSP_E_OVERFLOW) {
             host_keys.resize((size_t)needed);
-            rc = ksp_sketch_cpu(b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, host_keys.data(), host_keys.size(), out_off.data(), &needed);
+            rc = call();
         }
         if (rc != KSP_OK) throw CallError{rc};
         got = host_keys.data();
+        got_abund = host_abund.data();
     } else {
         ksp_sketch_stats st;
-        const int rc = ksp_sketch_host(device, b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, &got, out_off.data(), &st);
+        const int rc = counts ? ksp_sketch_host_abund(device, b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, &got, &got_abund, out_off.data(), &st)
+                              : ksp_sketch_host(device, b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, &got, out_off.data(), &st);
         if (rc != KSP_OK) throw CallError{rc};
         total.bases += st.bases; total.valid_kmers += st.valid_kmers; total.kept += st.kept; total.distinct_out += st.distinct_out;
         total.retries += st.retries; total.ms_upload += st.ms_upload; total.ms_hash += st.ms_hash; total.ms_select += st.ms_select;
@@ -315,9 +334,13 @@ void run_batch(const Batch& b, const bool on_host, const int device, const int k
         const uint32_t src = b.source[s];
         if (src >= keys.size()) { keys.resize((size_t)src + 1); segments.resize((size_t)src + 1, 0); }
         keys[src].insert(keys[src].end(), got + out_off[s], got + out_off[s + 1]);
+        if (counts) {
+            if (src >= counts->size()) counts->resize((size_t)src + 1);
+            (*counts)[src].insert((*counts)[src].end(), got_abund + out_off[s], got_abund + out_off[s + 1]);
+        }
         ++segments[src];
     }
-    if (!on_host) ksp_free(got);
+    if (!on_host) { ksp_free(got); ksp_free(got_abund); }
 }
 
 }  // namespace
@@ -337,7 +360,7 @@ extern "C" int kspider_sketch(const char* input, int kSize, uint64_t scaled, con
         on_host = how && std::strcmp(how, "host") == 0;
         const int threads = user_threads < 1 ? 1 : user_threads;
         const uint32_t seed = (flags & KSP_SKETCH_SEED) ? (uint32_t)(flags >> 32) : 42u;
-        const bool per_record = (flags & KSP_SKETCH_PER_RECORD) != 0;
+        const bool per_record = (flags & KSP_SKETCH_PER_RECORD) != 0, counted = (flags & KSP_SKETCH_ABUND) != 0;
         if (per_record && is_directory(input)) throw ArgError("KSP_SKETCH_PER_RECORD takes one file, not a directory");
         const size_t batch_bytes = (size_t)env_bytes("KSPIDER_SKETCH_BATCH_BYTES", env_bytes("KSPIDER_SKETCH_BATCH_MB", 256, 1) << 20, 1024);
         const char* dv = std::getenv("KSPIDER_DEVICE");
@@ -351,6 +374,7 @@ extern "C" int kspider_sketch(const char* input, int kSize, uint64_t scaled, con
         batch[0].buf = bufs[0];
         batch[1].buf = bufs[1];
         std::vector<std::vector<uint64_t>> keys;
+        std::vector<std::vector<uint32_t>> counts;
         std::vector<uint32_t> segments;
         ksp_sketch_stats total;
         std::memset(&total, 0, sizeof total);
@@ -370,7 +394,7 @@ extern "C" int kspider_sketch(const char* input, int kSize, uint64_t scaled, con
             });
             std::exception_ptr run_err;
             try {
-                run_batch(batch[cur], on_host, device, kSize, max_hash, seed, keys, segments, total);
+                run_batch(batch[cur], on_host, device, kSize, max_hash, seed, keys, counted ? &counts : nullptr, segments, total);
                 ++n_batches;
             } catch (...) {
                 run_err = std::current_exception();
@@ -384,6 +408,7 @@ extern "C" int kspider_sketch(const char* input, int kSize, uint64_t scaled, con
         // ---- the sources: names, unions, files
         const size_t n_src = feed.names.size();
         keys.resize(n_src);
+        counts.resize(n_src);
         segments.resize(n_src, 0);
         {
             std::set<std::string> seen;
@@ -395,11 +420,24 @@ extern "C" int kspider_sketch(const char* input, int kSize, uint64_t scaled, con
         if (mkdir(out_dir, 0777) != 0 && errno != EEXIST) throw std::runtime_error(std::string("cannot create ") + out_dir);
         parallel_for(n_src, threads, [&](const size_t s) {
             std::vector<uint64_t>& k = keys[s];
-            if (segments[s] > 1) {
+            std::vector<uint32_t>& c = counts[s];
+            if (segments[s] > 1 && counted) {   // the union with the counts added: a plain union would lose them
+                std::vector<std::pair<uint64_t, uint32_t>> both(k.size());
+                for (size_t i = 0; i < k.size(); ++i) both[i] = {k[i], c[i]};
+                std::sort(both.begin(), both.end());
+                k.clear();
+                c.clear();
+                for (size_t i = 0, j = 0; i < both.size(); i = j) {
+                    uint64_t sum = 0;
+                    for (; j < both.size() && both[j].first == both[i].first; ++j) sum = std::min<uint64_t>(sum + both[j].second, 0xFFFFFFFFull);
+                    k.push_back(both[i].first);
+                    c.push_back((uint32_t)sum);
+                }
+            } else if (segments[s] > 1) {
                 std::sort(k.begin(), k.end());
                 k.erase(std::unique(k.begin(), k.end()), k.end());
             }
-            ksp::write_file_atomically(std::string(out_dir) + "/" + feed.names[s] + ".sig", sig_text(feed.filenames[s], kSize, seed, max_hash, k));
+            ksp::write_file_atomically(std::string(out_dir) + "/" + feed.names[s] + ".sig", sig_text(feed.filenames[s], kSize, seed, max_hash, k, counted ? &c : nullptr));
         });
         if (std::getenv("KSPIDER_VERBOSE"))
             std::cout << "kspider_amd: sketch: " << n_src << " sources in " << n_batches << " batches" << (on_host ? " on the host" : "") << "; " << total.bases

@@ -171,8 +171,10 @@ struct Json {
     }
 };
 
-// first signature of the first top-level element whose ksize == k; false when there is none
-bool parse_sig(const std::string& path, const std::string& text, int k, std::vector<uint64_t>& mins) {
+// first signature of the first top-level element whose ksize == k; false when there is none.  abunds / has_abund: its
+// "abundances" when it has them (values above 2^32 - 1 are clamped); another length than "mins" fails with the file's name.
+bool parse_sig(const std::string& path, const std::string& text, int k, std::vector<uint64_t>& mins, std::vector<uint32_t>& abunds, bool& has_abund) {
+    has_abund = false;
     Json j{text.data(), text.data() + text.size(), path};
     j.need('[');
     j.need('{');
@@ -188,7 +190,8 @@ bool parse_sig(const std::string& path, const std::string& text, int k, std::vec
                 j.need('{');
                 long long ks = -1;
                 std::vector<uint64_t> m;
-                bool have_mins = false;
+                std::vector<uint32_t> a;
+                bool have_mins = false, have_abund = false;
                 if (!j.eat('}')) {
                     do {
                         std::string f = j.str();
@@ -207,6 +210,19 @@ bool parse_sig(const std::string& path, const std::string& text, int k, std::vec
                                 } while (j.eat(','));
                                 j.need(']');
                             }
+                        } else if (f == "abundances" && !found) {
+                            have_abund = true;
+                            j.need('[');
+                            if (!j.eat(']')) {
+                                do {
+                                    std::string t = j.num();
+                                    errno = 0;
+                                    const unsigned long long v = std::strtoull(t.c_str(), nullptr, 10);
+                                    if (errno || t[0] == '-') j.fail("abundance out of range");
+                                    a.push_back((uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull));
+                                } while (j.eat(','));
+                                j.need(']');
+                            }
                         } else {
                             j.skip();
                         }
@@ -215,6 +231,10 @@ bool parse_sig(const std::string& path, const std::string& text, int k, std::vec
                 }
                 if (!found && ks == k) {
                     if (!have_mins) j.fail("signature without mins");
+                    if (have_abund && a.size() != m.size())
+                        throw std::runtime_error("kspider_amd: " + path + ": " + std::to_string(a.size()) + " abundances for " + std::to_string(m.size()) + " mins");
+                    has_abund = have_abund;
+                    abunds.swap(a);
                     mins.swap(m);
                     found = true;
                 }
@@ -288,6 +308,46 @@ int guarded(Fn fn) {
 
 }  // namespace
 
+void ksp::sort_sig_mins(std::vector<uint64_t>& mins, std::vector<uint32_t>* abunds) {
+    if (!abunds) {
+        std::sort(mins.begin(), mins.end());
+        mins.erase(std::unique(mins.begin(), mins.end()), mins.end());
+        return;
+    }
+    std::vector<std::pair<uint64_t, uint32_t>> both(mins.size());
+    for (size_t i = 0; i < mins.size(); ++i) both[i] = {mins[i], (*abunds)[i]};
+    std::sort(both.begin(), both.end());
+    mins.clear();
+    abunds->clear();
+    for (size_t i = 0, j = 0; i < both.size(); i = j) {
+        uint64_t sum = 0;
+        for (; j < both.size() && both[j].first == both[i].first; ++j) sum = std::min<uint64_t>(sum + both[j].second, 0xFFFFFFFFull);
+        mins.push_back(both[i].first);
+        abunds->push_back((uint32_t)sum);
+    }
+}
+
+extern "C" int ksp_sig_read(const char* path, int kSize, uint64_t* mins, uint32_t* abunds, uint64_t capacity, uint64_t* n, int* has_abund) {
+    if (!path || !n || !has_abund || (!mins && capacity)) { ksp::set_error("ksp_sig_read: NULL argument"); return KSP_E_ARG; }
+    return guarded([&]() {
+        std::vector<uint64_t> m;
+        std::vector<uint32_t> a;
+        bool counted = false;
+        if (!parse_sig(path, read_maybe_gz(path), kSize, m, a, counted)) throw std::runtime_error(std::string("kspider_amd: ") + path + ": no signature with ksize " + std::to_string(kSize));
+        ksp::sort_sig_mins(m, counted ? &a : nullptr);
+        *n = m.size();
+        *has_abund = counted ? 1 : 0;
+        if (counted && !abunds && capacity) { ksp::set_error(std::string("ksp_sig_read: ") + path + " has abundances but abunds is NULL"); return (int)KSP_E_ARG; }
+        if (m.size() > capacity) {
+            ksp::set_error("ksp_sig_read: " + std::to_string(m.size()) + " mins, room for " + std::to_string(capacity));
+            return (int)KSP_E_OVERFLOW;
+        }
+        if (!m.empty()) std::memcpy(mins, m.data(), 8 * m.size());
+        if (counted && !a.empty()) std::memcpy(abunds, a.data(), 4 * a.size());
+        return (int)KSP_OK;
+    });
+}
+
 void ksp::load_sig_dir(const std::string& sigs_dir, int kSize, int user_threads, SketchNames& names, std::vector<SketchSource>& src) {
     const std::string dir = strip_slashes(sigs_dir);
     std::unordered_map<std::string, uint32_t> id_of;
@@ -312,13 +372,16 @@ void ksp::load_sig_dir(const std::string& sigs_dir, int kSize, int user_threads,
     parallel_for(sig_files.size(), user_threads, [&](size_t i) {
         const std::string& f = sig_files[i];
         std::vector<uint64_t> mins;
-        if (!parse_sig(f, read_maybe_gz(f), kSize, mins)) return;   // no signature with that ksize
+        std::vector<uint32_t> abunds;
+        bool has_abund = false;
+        if (!parse_sig(f, read_maybe_gz(f), kSize, mins, abunds, has_abund)) return;   // no signature with that ksize
         Source& s = parsed[i];
         s.id = id_of.at(stem_of(f));
         s.kmers = (uint32_t)mins.size();
-        std::sort(mins.begin(), mins.end());
-        mins.erase(std::unique(mins.begin(), mins.end()), mins.end());
+        ksp::sort_sig_mins(mins, has_abund ? &abunds : nullptr);
         s.run.swap(mins);
+        s.abund.swap(abunds);
+        s.has_abund = has_abund;
         has[i] = 1;
     });
     std::unordered_map<uint32_t, Source> by_id;

@@ -1,6 +1,7 @@
-// `sketch INPUT K SCALED OUT_DIR THREADS [--per-record] [--seed S]` — sourmash-compatible DNA FracMinHash sketches of FASTA /
+// `sketch INPUT K SCALED OUT_DIR THREADS [--per-record] [--seed S] [--abund]` — sourmash-compatible DNA FracMinHash sketches of FASTA /
 // FASTQ files (kspider_sketch): INPUT is a directory, each of its .fa .fasta .fna .fq .fastq files (plain or .gz) one source, or
-// one file; --per-record makes every record of that file a source.  Writes OUT_DIR/<name>.sig.  KSPIDER_SKETCH=host: no GPU.
+// one file; --per-record makes every record of that file a source; --abund writes every hash's abundance ("abundances").  Writes
+// OUT_DIR/<name>.sig.  KSPIDER_SKETCH=host: no GPU.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,11 +22,12 @@ int main(int argc, char** argv) {
     bool ok = argc >= 6;
     for (int i = 6; ok && i < argc; ++i) {
         if (std::strcmp(argv[i], "--per-record") == 0) flags |= KSP_SKETCH_PER_RECORD;
+        else if (std::strcmp(argv[i], "--abund") == 0) flags |= KSP_SKETCH_ABUND;
         else if (std::strcmp(argv[i], "--seed") == 0 && i + 1 < argc && number(argv[i + 1], 0xFFFFFFFFull, &seed)) { flags |= KSP_SKETCH_SEED; ++i; }
         else ok = false;
     }
     if (!ok) {
-        std::fprintf(stderr, "usage: %s INPUT K SCALED OUT_DIR THREADS [--per-record] [--seed S]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s INPUT K SCALED OUT_DIR THREADS [--per-record] [--seed S] [--abund]\n", argv[0]);
         return 2;
     }
     if (!number(argv[2], 64, &k) || !number(argv[3], ~0ull, &scaled) || !number(argv[5], 1000000, &threads)) {

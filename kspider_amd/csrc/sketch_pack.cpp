@@ -5,9 +5,12 @@
 //   kspider_query   database and queries, each a pack file or a directory -> the three files of a pairwise run over
 //                   database + queries, the TSV holding only the rows of the mode.  The device part is ksp_query_host (query.hip).
 //   kspider_gather  database and queries as above -> OUT_kSpider_gather.tsv, the rows of ksp_gather_host (gather.hip).
+//   kspider_gather_abund  the same for a directory of query signatures with abundances: the rows of ksp_gather_abund_host, the
+//                   weighted columns behind the nine.
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -85,6 +88,9 @@ void ksp::sketch_set_from_dir(const std::string& dir, const int kSize, const int
     const size_t G = names.size();
     set.present.assign(G, 0);
     set.kmers.assign(G, 0);
+    set.counted.assign(G, 0);
+    bool any_abund = false;
+    for (const SketchSource& s : src) any_abund |= s.has_abund;
     for (auto& n : names) set.names.push_back(n.second);   // (ids are 1, 2, ... in this order)
     set.offsets.push_back(0);
     for (const SketchSource& s : src) {   // ascending by id
@@ -92,6 +98,11 @@ void ksp::sketch_set_from_dir(const std::string& dir, const int kSize, const int
         set.kmers[s.id - 1] = s.kmers;
         set.keys.insert(set.keys.end(), s.run.begin(), s.run.end());
         set.offsets.push_back(set.keys.size());
+        set.counted[s.id - 1] = s.has_abund;
+        if (any_abund) {
+            if (s.has_abund) set.abund.insert(set.abund.end(), s.abund.begin(), s.abund.end());
+            else set.abund.resize(set.keys.size(), 0);
+        }
     }
     out = std::move(set);
 }
@@ -306,16 +317,23 @@ extern "C" int kspider_query(const char* db, const char* queries, int kSize, con
     });
 }
 
-extern "C" int kspider_gather(const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, uint32_t min_hashes, uint32_t max_matches) {
-    const char* who = "kspider_gather";
+namespace {
+
+// kspider_gather and, weighted, kspider_gather_abund
+int gather_files(const char* who, const bool weighted, const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, uint32_t min_hashes,
+                 uint32_t max_matches) {
     if (!db || !queries || !out_prefix || !*out_prefix) { ksp::set_error(std::string(who) + ": db, queries and out_prefix are required"); return KSP_E_ARG; }
     if (kSize < 0) { ksp::set_error(std::string(who) + ": kSize is the signatures' ksize, or 0 for .bin sketches"); return KSP_E_ARG; }
     if (min_hashes == 0) { ksp::set_error(std::string(who) + ": min_hashes is 1 or more"); return KSP_E_ARG; }
     return guarded(who, [&]() {
         const int threads = user_threads < 1 ? 1 : user_threads;
         ksp::SketchSet side[2];
+        if (weighted && (kSize == 0 || !is_directory(queries))) throw ArgError(std::string(queries) + " is not a directory of signatures (abundances are read from .sig files only)");
         load_side(db, kSize, threads, side[0]);
         load_side(queries, kSize, threads, side[1]);
+        if (weighted)
+            for (uint64_t g = 0; g < side[1].names.size(); ++g)
+                if (side[1].present[g] && !side[1].counted[g]) throw ArgError("the signature of " + side[1].names[g] + " in " + queries + " has no abundances");
         // source s of a side is its s-th group that has a sketch
         std::vector<uint64_t> group_of[2];
         for (int s = 0; s < 2; ++s)
@@ -324,17 +342,32 @@ extern "C" int kspider_gather(const char* db, const char* queries, int kSize, co
         if (group_of[0].empty() || group_of[1].empty()) throw ArgError(group_of[0].empty() ? "the database has no sketch" : "there is no query sketch");
         if (group_of[0].size() + group_of[1].size() > 0xFFFFFFFEull) throw std::runtime_error("more than 2^32 - 2 groups");
         ksp_gather_row* rows = nullptr;
+        ksp_gather_wrow* wrows = nullptr;
         uint64_t n_rows = 0;
         ksp_gather_stats st;
         const char* dv = std::getenv("KSPIDER_DEVICE");
-        const int rc = ksp_gather_host(side[0].keys.data(), side[0].offsets.data(), (uint32_t)group_of[0].size(), side[1].keys.data(), side[1].offsets.data(),
-                                       (uint32_t)group_of[1].size(), min_hashes, max_matches, dv ? std::atoi(dv) : 0, &rows, &n_rows, &st);
+        if (weighted && side[1].abund.size() != side[1].keys.size()) throw std::runtime_error("the queries' abundances are not parallel to their hashes");
+        const int rc = weighted ? ksp_gather_abund_host(side[0].keys.data(), side[0].offsets.data(), (uint32_t)group_of[0].size(), side[1].keys.data(), side[1].abund.data(),
+                                                        side[1].offsets.data(), (uint32_t)group_of[1].size(), min_hashes, max_matches, dv ? std::atoi(dv) : 0, &wrows, &n_rows, &st)
+                                : ksp_gather_host(side[0].keys.data(), side[0].offsets.data(), (uint32_t)group_of[0].size(), side[1].keys.data(), side[1].offsets.data(),
+                                                  (uint32_t)group_of[1].size(), min_hashes, max_matches, dv ? std::atoi(dv) : 0, &rows, &n_rows, &st);
         if (rc != KSP_OK) return rc;
+        // W of every query
+        std::vector<uint64_t> total_w;
+        if (weighted)
+            for (size_t q = 0; q + 1 < side[1].offsets.size(); ++q) {
+                uint64_t w = 0;
+                for (uint64_t e = side[1].offsets[q]; e < side[1].offsets[q + 1]; ++e) w += side[1].abund[e];
+                total_w.push_back(w);
+            }
         // the file only now: a refused or failed call leaves none
-        std::string text = "query\trank\tmatch\toverlap\tunique\tf_orig_query\tf_unique_to_query\tf_match\tremaining\n";
+        std::string text = "query\trank\tmatch\toverlap\tunique\tf_orig_query\tf_unique_to_query\tf_match\tremaining";
+        if (weighted) text += "\tf_unique_weighted\taverage_abund\tmedian_abund\tstd_abund\tn_unique_weighted_found\tsum_weighted_found\ttotal_weighted_hashes";
+        text += "\n";
         char buf[32];
         for (uint64_t i = 0; i < n_rows; ++i) {
-            const ksp_gather_row& r = rows[i];
+            const ksp_gather_wrow* w = weighted ? &wrows[i] : nullptr;
+            const ksp_gather_row r = w ? ksp_gather_row{w->query, w->rank, w->source, w->overlap, w->unique, w->remaining} : rows[i];
             const float q_size = (float)(side[1].offsets[r.query + 1] - side[1].offsets[r.query]), s_size = (float)(side[0].offsets[r.source + 1] - side[0].offsets[r.source]);
             text += side[1].names[group_of[1][r.query]] + "\t" + std::to_string(r.rank) + "\t" + side[0].names[group_of[0][r.source]] + "\t" + std::to_string(r.overlap) + "\t" +
                     std::to_string(r.unique);
@@ -342,9 +375,23 @@ extern "C" int kspider_gather(const char* db, const char* queries, int kSize, co
                 text += "\t";
                 text.append(buf, (size_t)ksp::format_float(buf, v));
             }
-            text += "\t" + std::to_string(r.remaining) + "\n";
+            text += "\t" + std::to_string(r.remaining);
+            if (w) {
+                typedef unsigned __int128 u128;
+                const uint64_t W = total_w[r.query];
+                const u128 sq = ((u128)w->sq_hi << 64) | w->sq_lo, mean2 = (u128)w->w_unique * w->w_unique;
+                const u128 spread = (u128)r.unique * sq - mean2;   // n Σa² - (Σa)² >= 0: exact, rounded once below
+                for (const float v : {W ? (float)((double)w->w_unique / (double)W) : 0.0f /* a query of abundances 0 */,(float)((double)w->w_unique / (double)r.unique), (float)((double)w->median2 / 2.0),
+                                      (float)(std::sqrt((double)spread) / (double)r.unique)}) {
+                    text += "\t";
+                    text.append(buf, (size_t)ksp::format_float(buf, v));
+                }
+                text += "\t" + std::to_string(w->w_unique) + "\t" + std::to_string(w->w_found) + "\t" + std::to_string(W);
+            }
+            text += "\n";
         }
         ksp_free(rows);
+        ksp_free(wrows);
         {
             std::ofstream f;
             ksp::PartialFiles files;
@@ -358,4 +405,14 @@ extern "C" int kspider_gather(const char* db, const char* queries, int kSize, co
                       << st.ms_candidates << " ms, fill " << st.ms_fill << " ms, rounds " << st.ms_rounds << " ms" << std::endl;
         return (int)KSP_OK;
     });
+}
+
+}  // namespace
+
+extern "C" int kspider_gather(const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, uint32_t min_hashes, uint32_t max_matches) {
+    return gather_files("kspider_gather", false, db, queries, kSize, out_prefix, user_threads, min_hashes, max_matches);
+}
+
+extern "C" int kspider_gather_abund(const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, uint32_t min_hashes, uint32_t max_matches) {
+    return gather_files("kspider_gather_abund", true, db, queries, kSize, out_prefix, user_threads, min_hashes, max_matches);
 }

@@ -10,9 +10,11 @@
 namespace ksp {
 
 struct SketchSource {
-    uint32_t id;
-    uint32_t kmers;               // what the reference stores in groupID_to_kmerCount
+    uint32_t id = 0;
+    uint32_t kmers = 0;           // what the reference stores in groupID_to_kmerCount
     std::vector<uint64_t> run;    // sorted unique hashes
+    std::vector<uint32_t> abund;  // parallel to run when the signature has "abundances" (has_abund), else empty
+    bool has_abund = false;
 };
 typedef std::vector<std::pair<uint32_t, std::string>> SketchNames;   // (group id, group name), ids 1, 2, ... in glob order
 
@@ -31,7 +33,13 @@ struct SketchSet {
     std::vector<uint32_t> kmers;      // per group; 0 without a sketch
     std::vector<uint64_t> offsets;    // present groups + 1
     std::vector<uint64_t> keys;
+    // optional: filled from a directory of signatures only, and not kept by the pack file
+    std::vector<uint8_t> counted;     // per group: its signature has abundances
+    std::vector<uint32_t> abund;      // per key, parallel to keys (0 for a sketch without abundances); empty when no sketch has any
 };
+// mins and, when abunds is given, the abundance beside each, sorted by hash; a hash listed twice once, its abundances added and
+// clamped at 2^32 - 1
+void sort_sig_mins(std::vector<uint64_t>& mins, std::vector<uint32_t>* abunds);
 // the directory's sketches (kSize > 0: load_sig_dir, kSize = 0: load_bin_dir) as a set
 void sketch_set_from_dir(const std::string& dir, int kSize, int threads, SketchSet& out);
 // The pack file format (little-endian, fixed width; every section padded to 8 bytes):

@@ -10,7 +10,8 @@
 //            when its k-mer would cross the source's end, and is appended as (hash, source): one ballot and one returning add
 //            per wave; the counter keeps counting past the capacity, nothing is written past it.
 //   select   rocPRIM's merge sort by (source, hash), one scan of head flags (an entry that differs from the one before),
-//            k_sketch_compact writes the heads' hashes, k_sketch_offsets the per-source bounds by binary search.
+//            k_sketch_compact writes the heads' hashes, k_sketch_offsets the per-source bounds by binary search.  The counted
+//            calls launch k_sketch_compact_abund instead: a head also writes the length of its run, its abundance.
 // Every loop is bounded by a size the host computed; no workgroup waits on another; the result does not depend on scheduling.
 #include <cstdint>
 #include <cstdlib>
@@ -170,6 +171,25 @@ __global__ void k_sketch_compact(const Rec* __restrict__ rec, const u64* __restr
         if (head(i)) out_keys[scan[i]] = rec[i].hash;
 }
 
+// the same, and beside its hash a head writes the length of its run: the next head's index - its own, clamped at 2^32 - 1.  The next
+// head is one before the first x > i whose scan[x] reaches scan[i] + 2 (n when there is none): doubling steps, then halving.
+__global__ void k_sketch_compact_abund(const Rec* __restrict__ rec, const u64* __restrict__ scan, const u64 n, u64* __restrict__ out_keys, u32* __restrict__ out_abund) {
+    const HeadFlag head{rec, n};
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        if (!head(i)) continue;
+        const u64 at = scan[i], target = at + 2;
+        u64 lo = i + 1, step = 1;   // scan[lo] = at + 1 < target
+        while (lo + step <= n && scan[lo + step] < target) { lo += step; step <<= 1; }   // (at most 64 trips: step doubles)
+        u64 hi = std::min(lo + step, n + 1);   // scan[hi] >= target, or hi = n + 1
+        while (hi - lo > 1) {
+            const u64 mid = lo + (hi - lo) / 2;
+            if (scan[mid] < target) lo = mid; else hi = mid;
+        }
+        out_keys[at] = rec[i].hash;
+        out_abund[at] = (u32)std::min<u64>(hi - 1 - i, 0xFFFFFFFFull);
+    }
+}
+
 // off[s] = the heads of the sources before s, s = 0 .. n_sources
 __global__ void k_sketch_offsets(const Rec* __restrict__ rec, const u64* __restrict__ scan, const u64 n, const u32 n_sources, u64* __restrict__ off) {
     for (u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x; s <= n_sources; s += (u64)gridDim.x * blockDim.x) {
@@ -195,9 +215,9 @@ done:
     return rc;
 }
 
-// The sketches on the CURRENT device; the arguments have passed ksp::check_sketch_args.
+// The sketches on the CURRENT device; the arguments have passed ksp::check_sketch_args.  d_out_abund: the counts beside the keys, or NULL.
 int sketch_on_device(const char* who, const uint8_t* d_seq, const u64 n_bytes, const u64* h_src_off, const u32 n_sources, const int ksize, const u64 max_hash,
-                     const u32 seed, u64* d_out_keys, const u64 capacity, u64* h_out_off, ksp_sketch_stats* stats) {
+                     const u32 seed, u64* d_out_keys, u32* d_out_abund, const u64 capacity, u64* h_out_off, ksp_sketch_stats* stats) {
     int rc = KSP_OK;
     ksp_sketch_stats S;
     std::memset(&S, 0, sizeof S);
@@ -255,7 +275,8 @@ int sketch_on_device(const char* who, const uint8_t* d_seq, const u64 n_bytes, c
         KSP_TRY_HIP(rocprim::merge_sort(d_tmp, b, (const Rec*)d_recs, d_sorted, (size_t)n, RecBefore(), (hipStream_t) nullptr));
         b = tb;
         KSP_TRY_HIP(rocprim::exclusive_scan(d_tmp, b, head_flags_of(d_sorted, n), d_scan, (u64)0, (size_t)n + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
-        hipLaunchKernelGGL(k_sketch_compact, dim3(ge), dim3(256), 0, nullptr, (const Rec*)d_sorted, (const u64*)d_scan, n, d_out_keys);
+        if (d_out_abund) hipLaunchKernelGGL(k_sketch_compact_abund, dim3(ge), dim3(256), 0, nullptr, (const Rec*)d_sorted, (const u64*)d_scan, n, d_out_keys, d_out_abund);
+        else hipLaunchKernelGGL(k_sketch_compact, dim3(ge), dim3(256), 0, nullptr, (const Rec*)d_sorted, (const u64*)d_scan, n, d_out_keys);
         hipLaunchKernelGGL(k_sketch_offsets, dim3(G.grid_of(((u64)n_sources + 256) / 256)), dim3(256), 0, nullptr, (const Rec*)d_sorted, (const u64*)d_scan, n, n_sources,
                            d_out_off);
         KSP_TRY_HIP(hipGetLastError());
@@ -302,21 +323,20 @@ void ksp::pinned_free(void* p) {
     if (p) (void)hipHostFree(p);
 }
 
-extern "C" int ksp_sketch_device(int device, const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* h_src_offsets, uint32_t n_sources, int ksize,
-                                 uint64_t max_hash, uint32_t seed, uint64_t* d_out_keys, uint64_t capacity, uint64_t* h_out_offsets,
-                                 ksp_sketch_stats* stats) {
-    const char* who = "ksp_sketch_device";
+// ksp_sketch_device and, with counts, ksp_sketch_device_abund
+static int sketch_device(const char* who, const bool counted, int device, const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* h_src_offsets, uint32_t n_sources, int ksize,
+                  uint64_t max_hash, uint32_t seed, uint64_t* d_out_keys, uint32_t* d_out_abund, uint64_t capacity, uint64_t* h_out_offsets, ksp_sketch_stats* stats) {
     if (const int rc = check_device_args(who, d_seq, n_bytes, h_src_offsets, n_sources, ksize, h_out_offsets)) return rc;
     if (!d_out_keys && capacity) { ksp::set_error(std::string(who) + ": d_out_keys is NULL but capacity is not 0"); return KSP_E_ARG; }
+    if (counted && !d_out_abund && capacity) { ksp::set_error(std::string(who) + ": d_out_abund is NULL but capacity is not 0"); return KSP_E_ARG; }
     if ((uintptr_t)d_seq & 15) { ksp::set_error(std::string(who) + ": d_seq is not 16-byte aligned"); return KSP_E_ARG; }
     if (const int rc = ksp::set_device(who, device)) return rc;
-    return sketch_on_device(who, d_seq, n_bytes, h_src_offsets, n_sources, ksize, max_hash, seed, d_out_keys, capacity, h_out_offsets, stats);
+    return sketch_on_device(who, d_seq, n_bytes, h_src_offsets, n_sources, ksize, max_hash, seed, d_out_keys, counted ? d_out_abund : nullptr, capacity, h_out_offsets, stats);
 }
 
-extern "C" int ksp_sketch_host(int device, const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize,
-                               uint64_t max_hash, uint32_t seed, uint64_t** out_keys, uint64_t* out_offsets, ksp_sketch_stats* stats) {
-    const char* who = "ksp_sketch_host";
-    if (!out_keys) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+// ksp_sketch_host and, with counts in *out_abund, ksp_sketch_host_abund
+static int sketch_host(const char* who, int device, const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize, uint64_t max_hash, uint32_t seed,
+                uint64_t** out_keys, uint32_t** out_abund, uint64_t* out_offsets, ksp_sketch_stats* stats) {
     if (const int rc = check_device_args(who, seq, n_bytes, src_offsets, n_sources, ksize, out_offsets)) return rc;
     u64 first = 0;
     {   // the share of all hashes that max_hash keeps, a quarter more, and room for a small input whatever its luck
@@ -329,12 +349,15 @@ extern "C" int ksp_sketch_host(int device, const uint8_t* seq, uint64_t n_bytes,
     ksp::DeviceArena A;
     uint8_t* d_seq = nullptr;
     u64 *d_keys = nullptr, *h_keys = nullptr, capacity = first;
+    u32 *d_abund = nullptr, *h_abund = nullptr;
+    const u64 per_key = out_abund ? 12 : 8;
     ksp_sketch_stats S;
     float ms_upload = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::memset(&S, 0, sizeof S);
-    if ((rc = ksp::device_fits(who, n_bytes + 16 + 8ull * capacity, "the bytes and the first key buffer"))) return rc;
+    if ((rc = ksp::device_fits(who, n_bytes + 16 + per_key * capacity, out_abund ? "the bytes and the first key and count buffers" : "the bytes and the first key buffer"))) return rc;
     if ((rc = A.alloc(&d_seq, (size_t)n_bytes + 16)) || (rc = A.alloc(&d_keys, (size_t)capacity))) return rc;
+    if (out_abund && (rc = A.alloc(&d_abund, (size_t)capacity + 1))) return rc;
     KSP_TRY_HIP(hipEventCreate(&ev0));
     KSP_TRY_HIP(hipEventCreate(&ev1));
     KSP_TRY_HIP(hipEventRecord(ev0, nullptr));
@@ -342,27 +365,61 @@ extern "C" int ksp_sketch_host(int device, const uint8_t* seq, uint64_t n_bytes,
     KSP_TRY_HIP(hipEventRecord(ev1, nullptr));
     KSP_TRY_HIP(hipEventSynchronize(ev1));
     KSP_TRY_HIP(hipEventElapsedTime(&ms_upload, ev0, ev1));
-    rc = sketch_on_device(who, d_seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, d_keys, capacity, out_offsets, &S);
+    rc = sketch_on_device(who, d_seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, d_keys, d_abund, capacity, out_offsets, &S);
     if (rc == KSP_E_OVERFLOW) {   // once more, at the exact size
         KSP_TRY_HIP(A.release(d_keys));
         d_keys = nullptr;
+        if (d_abund) KSP_TRY_HIP(A.release(d_abund));
+        d_abund = nullptr;
         capacity = S.needed;
-        if ((rc = ksp::device_fits(who, 8ull * capacity, "the keys"))) goto done;
+        if ((rc = ksp::device_fits(who, per_key * capacity, out_abund ? "the keys and the counts" : "the keys"))) goto done;
         if ((rc = A.alloc(&d_keys, (size_t)capacity))) goto done;
-        rc = sketch_on_device(who, d_seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, d_keys, capacity, out_offsets, &S);
+        if (out_abund && (rc = A.alloc(&d_abund, (size_t)capacity + 1))) goto done;
+        rc = sketch_on_device(who, d_seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, d_keys, d_abund, capacity, out_offsets, &S);
         S.retries = 1;
     }
     if (rc != KSP_OK) goto done;
     h_keys = (u64*)std::malloc((size_t)std::max<u64>(S.distinct_out, 1) * 8);
-    if (!h_keys) { ksp::set_error(std::string(who) + ": out of host memory"); rc = KSP_E_LIMIT; goto done; }
+    if (out_abund) h_abund = (u32*)std::malloc((size_t)std::max<u64>(S.distinct_out, 1) * 4);
+    if (!h_keys || (out_abund && !h_abund)) { ksp::set_error(std::string(who) + ": out of host memory"); rc = KSP_E_LIMIT; goto done; }
     if (S.distinct_out) KSP_TRY_HIP(hipMemcpy(h_keys, d_keys, (size_t)S.distinct_out * 8, hipMemcpyDeviceToHost));
+    if (S.distinct_out && out_abund) KSP_TRY_HIP(hipMemcpy(h_abund, d_abund, (size_t)S.distinct_out * 4, hipMemcpyDeviceToHost));
     *out_keys = h_keys;
     h_keys = nullptr;
+    if (out_abund) { *out_abund = h_abund; h_abund = nullptr; }
     S.ms_upload = ms_upload;
     if (stats) *stats = S;
 done:
     if (h_keys) std::free(h_keys);
+    if (h_abund) std::free(h_abund);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     return rc;
+}
+
+extern "C" int ksp_sketch_device(int device, const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* h_src_offsets, uint32_t n_sources, int ksize,
+                                 uint64_t max_hash, uint32_t seed, uint64_t* d_out_keys, uint64_t capacity, uint64_t* h_out_offsets,
+                                 ksp_sketch_stats* stats) {
+    return sketch_device("ksp_sketch_device", false, device, d_seq, n_bytes, h_src_offsets, n_sources, ksize, max_hash, seed, d_out_keys, nullptr, capacity, h_out_offsets, stats);
+}
+
+extern "C" int ksp_sketch_device_abund(int device, const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* h_src_offsets, uint32_t n_sources, int ksize,
+                                       uint64_t max_hash, uint32_t seed, uint64_t* d_out_keys, uint32_t* d_out_abund, uint64_t capacity, uint64_t* h_out_offsets,
+                                       ksp_sketch_stats* stats) {
+    return sketch_device("ksp_sketch_device_abund", true, device, d_seq, n_bytes, h_src_offsets, n_sources, ksize, max_hash, seed, d_out_keys, d_out_abund, capacity, h_out_offsets,
+                         stats);
+}
+
+extern "C" int ksp_sketch_host(int device, const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize,
+                               uint64_t max_hash, uint32_t seed, uint64_t** out_keys, uint64_t* out_offsets, ksp_sketch_stats* stats) {
+    const char* who = "ksp_sketch_host";
+    if (!out_keys) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+    return sketch_host(who, device, seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, out_keys, nullptr, out_offsets, stats);
+}
+
+extern "C" int ksp_sketch_host_abund(int device, const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize,
+                                     uint64_t max_hash, uint32_t seed, uint64_t** out_keys, uint32_t** out_abund, uint64_t* out_offsets, ksp_sketch_stats* stats) {
+    const char* who = "ksp_sketch_host_abund";
+    if (!out_keys || !out_abund) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+    return sketch_host(who, device, seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, out_keys, out_abund, out_offsets, stats);
 }

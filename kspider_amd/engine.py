@@ -74,10 +74,14 @@ GATHER_TAIL_CANDS_MAX = 1 << 20
 GATHER_FIRST_CANDS = 4096
 GATHER_ROW_DTYPE = np.dtype([("query", np.uint32), ("rank", np.uint32), ("source", np.uint32), ("overlap", np.uint32), ("unique", np.uint32),
                              ("remaining", np.uint32)])
+#: ksp_gather_wrow: the weighted row, 64 bytes (the 128-bit sum of squares as two words)
+GATHER_WROW_DTYPE = np.dtype([("query", np.uint32), ("rank", np.uint32), ("source", np.uint32), ("overlap", np.uint32), ("unique", np.uint32),
+                              ("remaining", np.uint32), ("w_unique", np.uint64), ("w_found", np.uint64), ("sq_lo", np.uint64), ("sq_hi", np.uint64),
+                              ("median2", np.uint64)])
 
 #: the sketcher (csrc/sketcher.hip): positions per tile of the hash pass; the flags of kspider_sketch
 SKETCH_TILE_BASES = 4096
-SKETCH_PER_RECORD, SKETCH_SEED = 1, 2
+SKETCH_PER_RECORD, SKETCH_SEED, SKETCH_ABUND = 1, 2, 4
 
 #: ksp_engine_lists_path / Engine.lists_path
 LISTS_NONE, LISTS_KEYED, LISTS_COMPACTED, LISTS_SORTED, LISTS_FUSED = 0, 1, 2, 3, 4
@@ -112,6 +116,8 @@ ABI_SYMBOLS = [
     "ksp_edges_tsv",
     "ksp_query_device", "ksp_query_host", "ksp_query_directory", "kspider_pack", "ksp_pack_info", "ksp_pack_load", "kspider_query",
     "ksp_gather_device", "ksp_gather_host", "kspider_gather",
+    "ksp_gather_abund_device", "ksp_gather_abund_host", "kspider_gather_abund",
+    "ksp_sketch_cpu_abund", "ksp_sketch_device_abund", "ksp_sketch_host_abund", "ksp_sig_read",
     "ksp_sketch_max_hash", "ksp_murmur64", "ksp_sketch_kmer_hash", "ksp_sketch_cpu", "ksp_sketch_device", "ksp_sketch_host",
     "ksp_fastx_info", "ksp_fastx_load", "kspider_sketch",
 ]
@@ -164,6 +170,13 @@ class GatherStats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class GatherWRow(ctypes.Structure):
+    """ksp_gather_wrow (include/kspider_amd.h): 64 bytes."""
+    _fields_ = [("query", ctypes.c_uint32), ("rank", ctypes.c_uint32), ("source", ctypes.c_uint32), ("overlap", ctypes.c_uint32), ("unique", ctypes.c_uint32),
+                ("remaining", ctypes.c_uint32), ("w_unique", ctypes.c_uint64), ("w_found", ctypes.c_uint64), ("sq_lo", ctypes.c_uint64), ("sq_hi", ctypes.c_uint64),
+                ("median2", ctypes.c_uint64)]
 
 
 class SketchStats(ctypes.Structure):
@@ -363,6 +376,19 @@ def lib():
         L.ksp_gather_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                       ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.kspider_gather.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]
+        L.ksp_gather_abund_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                              ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_gather_abund_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                            ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.kspider_gather_abund.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]
+        L.ksp_sketch_cpu_abund.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+        L.ksp_sketch_device_abund.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64,
+                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(SketchStats)]
+        L.ksp_sketch_host_abund.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64,
+                                            ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.POINTER(SketchStats)]
+        L.ksp_sig_read.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                   ctypes.POINTER(ctypes.c_int)]
         L.ksp_sketch_max_hash.argtypes = [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
         L.ksp_murmur64.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p]
         L.ksp_sketch_kmer_hash.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]
@@ -1092,6 +1118,63 @@ def gather(db: str, queries: str, kSize: int, out_prefix: str, user_threads: int
                                 int(min_hashes), int(max_matches)))
 
 
+def gather_abund_host(db_keys, db_offsets, q_keys, q_abund, q_offsets, min_hashes: int = 1, max_matches: int = 0, device: int = 0):
+    """gather_host for queries that carry an abundance per hash (ksp_gather_abund_host): q_abund is parallel to q_keys -> (rows of
+    GATHER_WROW_DTYPE, stats).  The first six fields are gather_host's; w_unique, w_found, the 128-bit sum of squares and twice the
+    median are over the hashes a row takes, with the query's abundances."""
+    def arr(a):
+        return None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
+    dk, do, qk, qo = arr(db_keys), arr(db_offsets), arr(q_keys), arr(q_offsets)
+    qa = None if q_abund is None else np.ascontiguousarray(q_abund, dtype=np.uint32)
+    out = ctypes.c_void_p()
+    nr = ctypes.c_uint64(0)
+    st = GatherStats()
+    _check(lib().ksp_gather_abund_host(_ptr(dk), _ptr(do), 0 if do is None else max(do.size - 1, 0), _ptr(qk), _ptr(qa), _ptr(qo), 0 if qo is None else max(qo.size - 1, 0),
+                                       int(min_hashes), int(max_matches), int(device), ctypes.byref(out), ctypes.byref(nr), ctypes.byref(st)))
+    try:
+        buf = (ctypes.c_char * (nr.value * GATHER_WROW_DTYPE.itemsize)).from_address(out.value) if nr.value else b""
+        rows = np.frombuffer(buf, dtype=GATHER_WROW_DTYPE).copy()
+    finally:
+        lib().ksp_free(out)
+    return rows, st.as_dict()
+
+
+def gather_abund_device(d_db_keys_ptr: int, db_offsets, d_q_keys_ptr: int, d_q_abund_ptr: int, q_offsets, d_rows_ptr: int, capacity: int, min_hashes: int = 1,
+                        max_matches: int = 0, device: int = 0) -> tuple:
+    """ksp_gather_abund_device: keys and abundances in DEVICE memory, offsets on the host, rows of 64 bytes into d_rows (room for
+    `capacity`; 0 / 0: the size query).  -> (rc, n_rows, stats) as gather_device."""
+    do = None if db_offsets is None else np.ascontiguousarray(db_offsets, dtype=np.uint64)
+    qo = None if q_offsets is None else np.ascontiguousarray(q_offsets, dtype=np.uint64)
+    nr = ctypes.c_uint64(0)
+    st = GatherStats()
+    rc = lib().ksp_gather_abund_device(int(device), d_db_keys_ptr or None, _ptr(do), 0 if do is None else max(do.size - 1, 0), d_q_keys_ptr or None, d_q_abund_ptr or None,
+                                       _ptr(qo), 0 if qo is None else max(qo.size - 1, 0), int(min_hashes), int(max_matches), d_rows_ptr or None, int(capacity),
+                                       ctypes.byref(nr), ctypes.byref(st))
+    if rc not in (KSP_OK, KSP_E_OVERFLOW):
+        _check(rc)
+    return rc, nr.value, st.as_dict()
+
+
+def gather_abund(db: str, queries: str, kSize: int, out_prefix: str, user_threads: int = 1, min_hashes: int = 1, max_matches: int = 0) -> None:
+    """kspider_gather_abund: gather for a directory of query signatures with abundances; OUT_kSpider_gather.tsv has gather's nine
+    columns, then f_unique_weighted, average_abund, median_abund, std_abund, n_unique_weighted_found, sum_weighted_found and
+    total_weighted_hashes."""
+    _check(lib().kspider_gather_abund(os.fsencode(db), os.fsencode(queries), int(kSize), os.fsencode(out_prefix) if out_prefix else None, int(user_threads),
+                                      int(min_hashes), int(max_matches)))
+
+
+def sig_read(path: str, kSize: int) -> tuple:
+    """One .sig / .sig.gz file as the loaders read it (ksp_sig_read; host only) -> (mins sorted and distinct, abundances parallel to
+    them or None when the signature has none)."""
+    n, has = ctypes.c_uint64(0), ctypes.c_int(0)
+    rc = lib().ksp_sig_read(os.fsencode(path), int(kSize), None, None, 0, ctypes.byref(n), ctypes.byref(has))
+    if rc not in (KSP_OK, KSP_E_OVERFLOW):
+        _check(rc)
+    mins, abunds = np.zeros(max(n.value, 1), dtype=np.uint64), np.zeros(max(n.value, 1), dtype=np.uint32)
+    _check(lib().ksp_sig_read(os.fsencode(path), int(kSize), mins.ctypes.data, abunds.ctypes.data, n.value, ctypes.byref(n), ctypes.byref(has)))
+    return mins[:n.value].copy(), (abunds[:n.value].copy() if has.value else None)
+
+
 def sketch_max_hash(scaled: int) -> int:
     """sourmash's threshold of `scaled` (host only): 2^64 - 1 for 1, int(2^64 / float(scaled)) above; 0 is refused."""
     out = ctypes.c_uint64(0)
@@ -1136,6 +1219,54 @@ def sketch_cpu(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled
     _check(lib().ksp_sketch_cpu(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), keys.ctypes.data, needed.value, out_off.ctypes.data,
                                 ctypes.byref(needed)))
     return keys[:needed.value].copy(), out_off
+
+
+def sketch_cpu_abund(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled: int | None = None, seed: int = 42) -> tuple:
+    """ksp_sketch_cpu_abund: sketch_cpu with every key's abundance -> (keys, abund, offsets).  No GPU."""
+    buf, off, mh = _sketch_input(seq, src_offsets, max_hash, scaled)
+    n_src = max(off.size - 1, 0)
+    out_off = np.zeros(n_src + 1, dtype=np.uint64)
+    needed = ctypes.c_uint64(0)
+    rc = lib().ksp_sketch_cpu_abund(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), None, None, 0, out_off.ctypes.data, ctypes.byref(needed))
+    if rc not in (KSP_OK, KSP_E_OVERFLOW):
+        _check(rc)
+    keys, abund = np.zeros(max(needed.value, 1), dtype=np.uint64), np.zeros(max(needed.value, 1), dtype=np.uint32)
+    _check(lib().ksp_sketch_cpu_abund(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), keys.ctypes.data, abund.ctypes.data, needed.value,
+                                      out_off.ctypes.data, ctypes.byref(needed)))
+    return keys[:needed.value].copy(), abund[:needed.value].copy(), out_off
+
+
+def sketch_host_abund(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled: int | None = None, seed: int = 42, device: int = 0) -> tuple:
+    """ksp_sketch_host_abund: sketch_host with every key's abundance, counted on the device -> (keys, abund, offsets, stats)."""
+    buf, off, mh = _sketch_input(seq, src_offsets, max_hash, scaled)
+    n_src = max(off.size - 1, 0)
+    out_off = np.zeros(n_src + 1, dtype=np.uint64)
+    out, out_a = ctypes.c_void_p(), ctypes.c_void_p()
+    st = SketchStats()
+    _check(lib().ksp_sketch_host_abund(int(device), _ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), ctypes.byref(out), ctypes.byref(out_a),
+                                       out_off.ctypes.data, ctypes.byref(st)))
+    try:
+        n = int(out_off[-1])
+        keys = np.frombuffer((ctypes.c_char * (8 * n)).from_address(out.value), dtype=np.uint64).copy() if n else np.zeros(0, dtype=np.uint64)
+        abund = np.frombuffer((ctypes.c_char * (4 * n)).from_address(out_a.value), dtype=np.uint32).copy() if n else np.zeros(0, dtype=np.uint32)
+    finally:
+        lib().ksp_free(out)
+        lib().ksp_free(out_a)
+    return keys, abund, out_off, st.as_dict()
+
+
+def sketch_device_abund(d_seq_ptr: int, n_bytes: int, src_offsets, ksize: int, max_hash: int, d_out_keys_ptr: int, d_out_abund_ptr: int, capacity: int, seed: int = 42,
+                        device: int = 0) -> tuple:
+    """ksp_sketch_device_abund: sketch_device with d_out_abund (DEVICE, room for `capacity`) beside the keys -> (rc, offsets, stats)."""
+    off = np.ascontiguousarray(src_offsets, dtype=np.uint64)
+    n_src = max(off.size - 1, 0)
+    out_off = np.zeros(n_src + 1, dtype=np.uint64)
+    st = SketchStats()
+    rc = lib().ksp_sketch_device_abund(int(device), d_seq_ptr or None, int(n_bytes), _ptr(off), n_src, int(ksize), int(max_hash), int(seed), d_out_keys_ptr or None,
+                                       d_out_abund_ptr or None, int(capacity), out_off.ctypes.data, ctypes.byref(st))
+    if rc not in (KSP_OK, KSP_E_OVERFLOW):
+        _check(rc)
+    return rc, out_off, st.as_dict()
 
 
 def sketch_host(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled: int | None = None, seed: int = 42, device: int = 0) -> tuple:
@@ -1184,10 +1315,12 @@ def fastx_read(path: str) -> dict:
             "fastq": bool(info[3])}
 
 
-def sketch_files(input_path: str, kSize: int, scaled: int, out_dir: str, user_threads: int = 1, per_record: bool = False, seed: int | None = None) -> None:
+def sketch_files(input_path: str, kSize: int, scaled: int, out_dir: str, user_threads: int = 1, per_record: bool = False, seed: int | None = None,
+                 abund: bool = False) -> None:
     """FASTA / FASTQ files -> one sourmash-compatible .sig file per source in out_dir (kspider_sketch).  input_path: a directory
-    (each file a source) or one file (per_record: each record a source).  KSPIDER_SKETCH=host in the environment: no GPU."""
-    flags = (SKETCH_PER_RECORD if per_record else 0) | (0 if seed is None else SKETCH_SEED | (int(seed) << 32))
+    (each file a source) or one file (per_record: each record a source); abund: every hash's abundance beside it ("abundances").
+    KSPIDER_SKETCH=host in the environment: no GPU."""
+    flags = (SKETCH_PER_RECORD if per_record else 0) | (0 if seed is None else SKETCH_SEED | (int(seed) << 32)) | (SKETCH_ABUND if abund else 0)
     _check(lib().kspider_sketch(os.fsencode(input_path), int(kSize), int(scaled), os.fsencode(out_dir), int(user_threads), flags))
 
 
