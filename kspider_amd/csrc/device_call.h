@@ -1,7 +1,8 @@
 // What every consumer of the join's edges does on the host before its first kernel launch (cluster.hip, export.hip, repr.hip,
 // cut.hip, sweep.hip, tree.hip, derep.hip): check a HIP call, choose the device, size a grid of chunk-loop workgroups, ask
 // whether an allocation fits, and own device memory until the call returns.  Also the growing device buffer and the HIP check
-// of the engine and of the multi-device job (engine.hip, multi.hip).  Host code only: no kernel, nothing __device__.
+// of the engine and of the multi-device job (engine.hip, multi.hip), and the owner of the HIP events that time the phases of a
+// call (Events: query.hip, gather.hip), so that those calls leave by `return`.  Host code only: no kernel, nothing __device__.
 #ifndef KSPIDER_DEVICE_CALL_H
 #define KSPIDER_DEVICE_CALL_H
 #include <algorithm>
@@ -138,14 +139,31 @@ public:
     }
 };
 
+// N HIP events of one call: create() makes them, the destructor destroys the ones that were made
+template <int N>
+struct Events {
+    hipEvent_t ev[N] = {};
+    Events() = default;
+    Events(const Events&) = delete;
+    Events& operator=(const Events&) = delete;
+    ~Events() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int create() {
+        for (hipEvent_t& e : ev) KSP_HIP(hipEventCreate(&e));
+        return KSP_OK;
+    }
+    hipEvent_t operator[](const int i) const { return ev[i]; }
+};
+
 // two host arrays of n node indices as *d_a, *d_b in the arena (the (a, b) form of an edge list)
 inline int upload_pairs(DeviceArena& arena, const uint32_t* h_a, const uint32_t* h_b, const uint64_t n, uint32_t** d_a, uint32_t** d_b) {
     int rc = KSP_OK;
     if ((rc = arena.alloc(d_a, (size_t)n)) || (rc = arena.alloc(d_b, (size_t)n))) return rc;
-    KSP_TRY_HIP(hipMemcpy(*d_a, h_a, (size_t)n * 4, hipMemcpyHostToDevice));
-    KSP_TRY_HIP(hipMemcpy(*d_b, h_b, (size_t)n * 4, hipMemcpyHostToDevice));
-done:
-    return rc;
+    KSP_HIP(hipMemcpy(*d_a, h_a, (size_t)n * 4, hipMemcpyHostToDevice));
+    KSP_HIP(hipMemcpy(*d_b, h_b, (size_t)n * 4, hipMemcpyHostToDevice));
+    return KSP_OK;
 }
 
 }  // namespace ksp

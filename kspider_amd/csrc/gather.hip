@@ -609,21 +609,11 @@ __global__ __launch_bounds__(kThreads) void k_gather_live(const GRound R, const 
     }
 }
 
-// the tile's rows into (query, rank) order: qoff[] = the exclusive scan of the queries' row counts
-__global__ void k_gather_rows(const GRound R, const u32 n_rows, const u32* __restrict__ qoff, ksp_gather_row* __restrict__ sorted) {
+// the tile's rows `in`, of either kind, into (query, rank) order: qoff[] = the exclusive scan of the queries' row counts
+template <class Row>
+__global__ void k_gather_rows(const GRound R, const Row* __restrict__ in, const u32 n_rows, const u32* __restrict__ qoff, Row* __restrict__ sorted) {
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n_rows; i += (u64)gridDim.x * blockDim.x) {
-        const ksp_gather_row r = R.rows[i];
-        const u32 tag = r.query - R.q0;
-        if (tag >= R.nq || r.rank == 0) continue;
-        const u64 at = (u64)qoff[tag] + r.rank - 1;
-        if (at < n_rows) sorted[at] = r;
-    }
-}
-
-// the same for the weighted rows `in`
-__global__ void k_gather_wrows(const GRound R, const ksp_gather_wrow* __restrict__ in, const u32 n_rows, const u32* __restrict__ qoff, ksp_gather_wrow* __restrict__ sorted) {
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n_rows; i += (u64)gridDim.x * blockDim.x) {
-        const ksp_gather_wrow r = in[i];
+        const Row r = in[i];
         const u32 tag = r.query - R.q0;
         if (tag >= R.nq || r.rank == 0) continue;
         const u64 at = (u64)qoff[tag] + r.rank - 1;
@@ -660,371 +650,423 @@ int read_switches(const char* who, GatherSwitches& W) {
     return KSP_OK;
 }
 
-// The gather on the CURRENT device; the arguments have passed check_gather_args and read_switches.  The rows go to d_rows (room
-// for `capacity`) or, when h_rows is given, to the host vector.  Row = ksp_gather_wrow: the weighted call, d_q_abund beside the
+// One tile of queries: its table, what the steps found, and its own arrays, which go back to the device when the tile is done
+template <class Row>
+struct GatherTile {
+    u32 q0 = 0, nq = 0, E = 0, U = 0, H = 0, n_cand = 0;
+    u64 e0 = 0, n_fill[2] = {0, 0}, n_slots = 0, rows_cap = 0, found = 0;
+    QTable T;
+    GSweep P;
+    GRound R;
+    GAbund AB;
+    ksp::DeviceArena mem;   // of the arrays below
+    // the sorted candidates (key 8, overlap 4, base 8, dead 4, two live lists 2 x 2 x 4) and the sort's scratch
+    u64 *ckey = nullptr, *cbase = nullptr;
+    u32 *covl = nullptr, *cdead = nullptr, *live[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    void* tmp2 = nullptr;
+    size_t tb2 = 0;
+    // when the slots are known: 4 per slot, a bit per holder, weighted 4 per holder; the rows as found and by (query, rank)
+    u32 *seg = nullptr, *alive = nullptr, *habund = nullptr;
+    Row *rows = nullptr, *sorted = nullptr;
+};
+
+// One gather call on the CURRENT device (weighted: 7q): what it is given, what it holds whatever the tiles find,
+// and its phases as steps.  The arguments have passed check_gather_args and read_switches.  The rows go to d_rows (room for
+// `capacity`) or, when h_rows is given, to the host vector.  Row = ksp_gather_wrow: the weighted call, d_q_abund beside the
 // query keys; Row = ksp_gather_row: d_q_abund is not read.
 template <class Row>
-int gather_on_device(const char* who, const GatherSwitches& W, const u64* d_db_keys, const u64* h_db_off, const u32 n_db, const u64* d_q_keys, const u32* d_q_abund,
-                     const u64* h_q_off, const u32 n_q, const u32 min_hashes, const u32 max_matches, Row* d_rows, const u64 capacity, std::vector<Row>* h_rows, u64* n_rows,
-                     ksp_gather_stats* stats) {
-    constexpr bool kW = std::is_same<Row, ksp_gather_wrow>::value;
-    int rc = KSP_OK;
-    ksp_gather_stats S;
-    std::memset(&S, 0, sizeof S);
-    ksp::WorkgroupCap G;
-    u32 n_tiles = 0;
-    u64 e_max = 0, rows_done = 0;
-    if ((rc = query_tiles(who, h_q_off, n_q, W.tile, &n_tiles, &e_max))) return rc;
-    if ((rc = ksp::workgroup_cap("KSP_GATHER_MAX_WORKGROUPS", who, G))) return rc;
-    std::vector<u32> probes[2];   // [0] short, [1] long; a source without entries shares nothing
-    for (u32 p = 0; p < n_db; ++p)
-        if (const u64 len = h_db_off[p + 1] - h_db_off[p]) probes[len >= W.long_run].push_back(p);
-    S.n_db = n_db; S.n_q = n_q; S.db_entries = h_db_off[n_db]; S.q_entries = h_q_off[n_q];
-    S.tile = (u32)W.tile; S.long_seg = W.long_seg; S.tail_cands = W.tail ? W.tail_cands : 0; S.min_hashes = min_hashes; S.max_matches = max_matches;
+struct GatherCall {
+    static constexpr bool kW = std::is_same<Row, ksp_gather_wrow>::value;
+    typedef GatherTile<Row> Tile;
 
+    const char* who;
+    GatherSwitches W;
+    const u64 *d_db_keys, *h_db_off;
+    u32 n_db;
+    const u64* d_q_keys;
+    const u32* d_q_abund;
+    const u64* h_q_off;
+    u32 n_q, min_hashes, max_matches;
+    Row* d_rows;
+    u64 capacity;
+    std::vector<Row>* h_rows;
+    // (an aggregate: the members above are the call's arguments, in this order)
+    ksp::WorkgroupCap G;
     ksp::DeviceArena A;
+    ksp::Events<5> ev;   // of a tile: table | candidates | fill | rounds
+    u32 n_tiles = 0;
+    std::vector<u32> probes[2];   // [0] short, [1] long
     u64 *d_db_off = nullptr, *d_q_off = nullptr;
-    u32 *d_list[2] = {nullptr, nullptr}, *d_fill[2] = {nullptr, nullptr};
-    u32 *qrank = nullptr, *qrem = nullptr, *qdone = nullptr, *qoff = nullptr, *d_out = nullptr;
-    unsigned long long *ctrl = nullptr, *best = nullptr, *qwfound = nullptr;
+    u32 *d_list[2] = {nullptr, nullptr}, *d_fill[2] = {nullptr, nullptr};   // the sources of a sweep; those of them that have a candidate
+    u32 *qrank = nullptr, *qrem = nullptr, *qdone = nullptr, *qoff = nullptr, *d_out = nullptr;   // per query of a tile; the tail's report
+    unsigned long long *ctrl = nullptr, *best = nullptr, *qwfound = nullptr;   // (qwfound: weighted only)
+    unsigned long long h_ctrl[kCtrlWords] = {};
     u64* cand_key = nullptr;   // the candidates as the sweep found them; they grow when a tile finds more
     u32* cand_ovl = nullptr;
     u64 cand_cap = 0;
     QTableBufs B;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    unsigned long long h_ctrl[kCtrlWords];
-    size_t tb_rows = 0;
-    B.e_max = e_max;
-    if ((rc = query_table_scratch(e_max, &B.tb))) return rc;
-    KSP_TRY_HIP(rocprim::exclusive_scan(nullptr, tb_rows, (u32*)nullptr, (u32*)nullptr, 0u, (size_t)kTileMax, rocprim::plus<u32>(), (hipStream_t) nullptr));
-    B.tb = std::max<size_t>(std::max(B.tb, tb_rows), 8);
-    cand_cap = std::max<u64>(KSP_GATHER_FIRST_CANDS, 4ull * n_db);
+    ksp_gather_stats S = {};
+    u64 rows_done = 0;
+
     // ---- what the call holds whatever the tiles find, sized and checked first: 8 per source (offsets), 8 per source with entries
     // (its list and the list of those with a candidate), 24 per query of a tile, the table, the first candidate buffer, the scratch
-    if ((rc = ksp::device_fits(who, 8ull * ((u64)n_db + n_q + 2) + 8ull * (probes[0].size() + probes[1].size()) + (kW ? 32ull : 24ull) * kTileMax + B.bytes() + 12 * cand_cap + B.tb + 256,
-                               kW ? "8 per source, 8 per source with entries, 40 per entry of the largest query tile, its directory, the candidates, the sort's scratch, 8 per query of a tile"
-                                  : "8 per source, 8 per source with entries, 40 per entry of the largest query tile, its directory, the candidates, the sort's scratch")))
-        return rc;
-    if ((rc = A.alloc(&d_db_off, (size_t)n_db + 1)) || (rc = A.alloc(&d_q_off, (size_t)n_q + 1)) || (rc = A.alloc(&ctrl, (size_t)kCtrlWords)) || (rc = A.alloc(&d_out, 4))) return rc;
-    for (int c = 0; c < 2; ++c)
-        if (!probes[c].empty() && ((rc = A.alloc(&d_list[c], probes[c].size())) || (rc = A.alloc(&d_fill[c], probes[c].size())))) return rc;
-    if ((rc = A.alloc(&best, (size_t)kTileMax)) || (rc = A.alloc(&qrank, (size_t)kTileMax)) || (rc = A.alloc(&qrem, (size_t)kTileMax)) || (rc = A.alloc(&qdone, (size_t)kTileMax)) ||
-        (rc = A.alloc(&qoff, (size_t)kTileMax)))
-        return rc;
-    if (kW && (rc = A.alloc(&qwfound, (size_t)kTileMax))) return rc;
-    if ((rc = A.alloc(&cand_key, (size_t)cand_cap)) || (rc = A.alloc(&cand_ovl, (size_t)cand_cap))) return rc;
-    if (e_max && ((rc = query_table_alloc(A, B)) || (rc = A.alloc_bytes(&B.tmp, B.tb)))) return rc;
-    KSP_TRY_HIP(hipMemcpy(d_db_off, h_db_off, ((size_t)n_db + 1) * 8, hipMemcpyHostToDevice));
-    KSP_TRY_HIP(hipMemcpy(d_q_off, h_q_off, ((size_t)n_q + 1) * 8, hipMemcpyHostToDevice));
-    for (int c = 0; c < 2; ++c)
-        if (!probes[c].empty()) KSP_TRY_HIP(hipMemcpy(d_list[c], probes[c].data(), probes[c].size() * 4, hipMemcpyHostToDevice));
-    for (hipEvent_t& e : ev) KSP_TRY_HIP(hipEventCreate(&e));
+    int setup() {
+        int rc = KSP_OK;
+        u64 e_max = 0;
+        if ((rc = query_tiles(who, h_q_off, n_q, W.tile, &n_tiles, &e_max))) return rc;
+        if ((rc = ksp::workgroup_cap("KSP_GATHER_MAX_WORKGROUPS", who, G))) return rc;
+        query_split_sources(h_db_off, n_db, W.long_run, 0, probes);
+        S.n_db = n_db; S.n_q = n_q; S.db_entries = h_db_off[n_db]; S.q_entries = h_q_off[n_q];
+        S.tile = (u32)W.tile; S.long_seg = W.long_seg; S.tail_cands = W.tail ? W.tail_cands : 0; S.min_hashes = min_hashes; S.max_matches = max_matches;
+        size_t tb_rows = 0;
+        B.e_max = e_max;
+        if ((rc = query_table_scratch(e_max, &B.tb))) return rc;
+        KSP_HIP(rocprim::exclusive_scan(nullptr, tb_rows, (u32*)nullptr, (u32*)nullptr, 0u, (size_t)kTileMax, rocprim::plus<u32>(), (hipStream_t) nullptr));
+        B.tb = std::max<size_t>(std::max(B.tb, tb_rows), 8);
+        cand_cap = std::max<u64>(KSP_GATHER_FIRST_CANDS, 4ull * n_db);
+        if ((rc = ksp::device_fits(who, 8ull * ((u64)n_db + n_q + 2) + 8ull * (probes[0].size() + probes[1].size()) + (kW ? 32ull : 24ull) * kTileMax + B.bytes() + 12 * cand_cap + B.tb + 256,
+                                   kW ? "8 per source, 8 per source with entries, 40 per entry of the largest query tile, its directory, the candidates, the sort's scratch, 8 per query of a tile"
+                                      : "8 per source, 8 per source with entries, 40 per entry of the largest query tile, its directory, the candidates, the sort's scratch")))
+            return rc;
+        if ((rc = query_upload_front(A, h_db_off, n_db, h_q_off, n_q, probes, &d_db_off, &d_q_off, d_list)) || (rc = A.alloc(&ctrl, (size_t)kCtrlWords)) || (rc = A.alloc(&d_out, 4)))
+            return rc;
+        for (int c = 0; c < 2; ++c)
+            if (!probes[c].empty() && (rc = A.alloc(&d_fill[c], probes[c].size()))) return rc;
+        if ((rc = A.alloc(&best, (size_t)kTileMax)) || (rc = A.alloc(&qrank, (size_t)kTileMax)) || (rc = A.alloc(&qrem, (size_t)kTileMax)) || (rc = A.alloc(&qdone, (size_t)kTileMax)) ||
+            (rc = A.alloc(&qoff, (size_t)kTileMax)))
+            return rc;
+        if constexpr (kW)
+            if ((rc = A.alloc(&qwfound, (size_t)kTileMax))) return rc;
+        if ((rc = A.alloc(&cand_key, (size_t)cand_cap)) || (rc = A.alloc(&cand_ovl, (size_t)cand_cap))) return rc;
+        if (e_max && ((rc = query_table_alloc(A, B)) || (rc = A.alloc_bytes(&B.tmp, B.tb)))) return rc;
+        return ev.create();
+    }
 
-    for (u32 t = 0; t < n_tiles; ++t) {
-        const u32 q0 = (u32)((u64)t * W.tile), nq = (u32)(std::min<u64>((u64)q0 + W.tile, n_q) - q0);
-        const u64 e0 = h_q_off[q0];
-        const u32 E = (u32)(h_q_off[q0 + nq] - e0);
-        if (E == 0) continue;   // a tile of empty queries matches nothing
-        // ---- the table
-        KSP_TRY_HIP(hipEventRecord(ev[0], nullptr));
-        QTable T;
-        u32 U = 0, H = 0;
-        if ((rc = query_table_build(who, G, B, d_q_keys, d_q_off, q0, nq, e0, E, &T, &U, &H))) goto done;
-        KSP_TRY_HIP(hipEventRecord(ev[1], nullptr));
-        // ---- the candidates: every source against this tile; once more with a larger buffer when it found more than fit
-        GSweep P;
+    // ---- the candidates: every source against this tile; once more with a larger buffer when it found more than fit
+    int candidates(Tile& t) {
+        int rc = KSP_OK;
+        GSweep& P = t.P;
         std::memset(&P, 0, sizeof P);
         P.db_keys = d_db_keys; P.db_off = d_db_off; P.list_cap = (u32)W.list_cap; P.min_hashes = min_hashes; P.ctrl = ctrl;
         for (int attempt = 0; attempt < 2; ++attempt) {
-            KSP_TRY_HIP(hipMemsetAsync(ctrl, 0, sizeof h_ctrl, nullptr));
+            KSP_HIP(hipMemsetAsync(ctrl, 0, sizeof h_ctrl, nullptr));
             P.cand_key = cand_key; P.cand_ovl = cand_ovl; P.cand_cap = cand_cap;
             if (!probes[0].empty()) {
                 P.list = d_list[0]; P.n_list = (u32)probes[0].size(); P.fill_list = d_fill[0]; P.fill_word = kFill0;
-                hipLaunchKernelGGL((k_gather_sweep<true, false>), dim3(G.grid_of(((u64)P.n_list + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, T, P);
+                hipLaunchKernelGGL((k_gather_sweep<true, false>), dim3(G.grid_of(((u64)P.n_list + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, t.T, P);
             }
             if (!probes[1].empty()) {
                 P.list = d_list[1]; P.n_list = (u32)probes[1].size(); P.fill_list = d_fill[1]; P.fill_word = kFill1;
-                hipLaunchKernelGGL((k_gather_sweep<false, false>), dim3(G.grid_of(P.n_list)), dim3(kThreads), 0, nullptr, T, P);
+                hipLaunchKernelGGL((k_gather_sweep<false, false>), dim3(G.grid_of(P.n_list)), dim3(kThreads), 0, nullptr, t.T, P);
             }
-            KSP_TRY_HIP(hipGetLastError());
-            KSP_TRY_HIP(hipMemcpy(h_ctrl, ctrl, sizeof h_ctrl, hipMemcpyDeviceToHost));
+            KSP_HIP(hipGetLastError());
+            KSP_HIP(hipMemcpy(h_ctrl, ctrl, sizeof h_ctrl, hipMemcpyDeviceToHost));
             if (h_ctrl[kCands] <= cand_cap) break;
-            if (attempt == 1) { ksp::set_error(std::string(who) + ": the second sweep found more candidates than the first"); rc = KSP_E_HIP; goto done; }
-            if (h_ctrl[kCands] >= 0xFFFFFFFFull) { ksp::set_error(std::string(who) + ": 2^32 - 1 candidates or more in a query tile (lower KSP_QUERY_TILE)"); rc = KSP_E_LIMIT; goto done; }
-            KSP_TRY_HIP(A.release(cand_key));
-            KSP_TRY_HIP(A.release(cand_ovl));
+            if (attempt == 1) { ksp::set_error(std::string(who) + ": the second sweep found more candidates than the first"); return KSP_E_HIP; }
+            if (h_ctrl[kCands] >= 0xFFFFFFFFull) { ksp::set_error(std::string(who) + ": 2^32 - 1 candidates or more in a query tile (lower KSP_QUERY_TILE)"); return KSP_E_LIMIT; }
+            KSP_HIP(A.release(cand_key));
+            KSP_HIP(A.release(cand_ovl));
             cand_key = nullptr; cand_ovl = nullptr;
             cand_cap = h_ctrl[kCands];
-            if ((rc = ksp::device_fits(who, 12 * cand_cap, "the candidates of a query tile"))) goto done;
-            if ((rc = A.alloc(&cand_key, (size_t)cand_cap)) || (rc = A.alloc(&cand_ovl, (size_t)cand_cap))) goto done;
+            if ((rc = ksp::device_fits(who, 12 * cand_cap, "the candidates of a query tile"))) return rc;
+            if ((rc = A.alloc(&cand_key, (size_t)cand_cap)) || (rc = A.alloc(&cand_ovl, (size_t)cand_cap))) return rc;
         }
-        const u32 n_cand = (u32)h_ctrl[kCands];
-        const u64 n_fill[2] = {h_ctrl[kFill0], h_ctrl[kFill1]};
-        if (n_fill[0] > probes[0].size() || n_fill[1] > probes[1].size()) { ksp::set_error(std::string(who) + ": more sources with a candidate than sources"); rc = KSP_E_HIP; goto done; }
-        S.candidates += n_cand; S.dropped += h_ctrl[kDropped]; S.table_keys += U; S.table_holders += H; ++S.passes;
-        float ms = 0;
-        if (n_cand == 0) {   // nothing reaches min_hashes: no row for any query of the tile
-            KSP_TRY_HIP(hipEventRecord(ev[2], nullptr));
-            KSP_TRY_HIP(hipEventSynchronize(ev[2]));
-            KSP_TRY_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); S.ms_table += ms;
-            KSP_TRY_HIP(hipEventElapsedTime(&ms, ev[1], ev[2])); S.ms_candidates += ms;
-            continue;
-        }
-        // ---- the tile's own arrays: the sorted candidates (key 8, overlap 4, base 8, dead 4, two live lists 2 x 2 x 4), the sort's
-        // scratch; then, when the slots are known, 4 per slot and a bit per holder; then the rows
-        u64 *ckey = nullptr, *cbase = nullptr, n_slots = 0;
-        u32 *covl = nullptr, *cdead = nullptr, *live[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *seg = nullptr, *alive = nullptr, *habund = nullptr;
-        Row *rows = nullptr, *sorted = nullptr;
-        void* tmp2 = nullptr;
-        size_t tb_sort = 0, tb_scan = 0, tb2 = 0;
+        t.n_cand = (u32)h_ctrl[kCands];
+        t.n_fill[0] = h_ctrl[kFill0]; t.n_fill[1] = h_ctrl[kFill1];
+        if (t.n_fill[0] > probes[0].size() || t.n_fill[1] > probes[1].size()) { ksp::set_error(std::string(who) + ": more sources with a candidate than sources"); return KSP_E_HIP; }
+        S.candidates += t.n_cand; S.dropped += h_ctrl[kDropped]; S.table_keys += t.U; S.table_holders += t.H; ++S.passes;
+        return KSP_OK;
+    }
+
+    // ---- the candidates sorted by (query, source), a segment for each by the scan of the overlaps, the slots of all of them
+    int sort_candidates(Tile& t) {
+        int rc = KSP_OK;
+        const u32 n_cand = t.n_cand;
+        size_t tb_sort = 0, tb_scan = 0;
         const auto ovl64 = [](const u32* p) { return rocprim::make_transform_iterator(p, AsU64()); };
-        KSP_TRY_HIP(rocprim::radix_sort_pairs(nullptr, tb_sort, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, (size_t)n_cand, 0, 44, (hipStream_t) nullptr));
-        KSP_TRY_HIP(rocprim::exclusive_scan(nullptr, tb_scan, ovl64(nullptr), (u64*)nullptr, (u64)0, (size_t)n_cand + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
-        tb2 = std::max<size_t>(std::max(tb_sort, tb_scan), 8);
-        if ((rc = ksp::device_fits(who, 40ull * ((u64)n_cand + 1) + tb2, "40 per candidate of a query tile, the sort's scratch"))) goto done;
-        if ((rc = A.alloc(&ckey, (size_t)n_cand)) || (rc = A.alloc(&covl, (size_t)n_cand + 1)) || (rc = A.alloc(&cbase, (size_t)n_cand + 1)) || (rc = A.alloc(&cdead, (size_t)n_cand)) ||
-            (rc = A.alloc_bytes(&tmp2, tb2)))
-            goto done;
+        KSP_HIP(rocprim::radix_sort_pairs(nullptr, tb_sort, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, (size_t)n_cand, 0, 44, (hipStream_t) nullptr));
+        KSP_HIP(rocprim::exclusive_scan(nullptr, tb_scan, ovl64(nullptr), (u64*)nullptr, (u64)0, (size_t)n_cand + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
+        t.tb2 = std::max<size_t>(std::max(tb_sort, tb_scan), 8);
+        if ((rc = ksp::device_fits(who, 40ull * ((u64)n_cand + 1) + t.tb2, "40 per candidate of a query tile, the sort's scratch"))) return rc;
+        if ((rc = t.mem.alloc(&t.ckey, (size_t)n_cand)) || (rc = t.mem.alloc(&t.covl, (size_t)n_cand + 1)) || (rc = t.mem.alloc(&t.cbase, (size_t)n_cand + 1)) ||
+            (rc = t.mem.alloc(&t.cdead, (size_t)n_cand)) || (rc = t.mem.alloc_bytes(&t.tmp2, t.tb2)))
+            return rc;
         for (int b = 0; b < 2; ++b)
             for (int c = 0; c < 2; ++c)
-                if ((rc = A.alloc(&live[b][c], (size_t)n_cand))) goto done;
-        {
-            size_t b = tb2;
-            KSP_TRY_HIP(rocprim::radix_sort_pairs(tmp2, b, (const u64*)cand_key, ckey, (const u32*)cand_ovl, covl, (size_t)n_cand, 0, 44, (hipStream_t) nullptr));
-            KSP_TRY_HIP(hipMemsetAsync(covl + n_cand, 0, 4, nullptr));
-            KSP_TRY_HIP(hipMemsetAsync(cdead, 0, (size_t)n_cand * 4, nullptr));
-            b = tb2;
-            KSP_TRY_HIP(rocprim::exclusive_scan(tmp2, b, ovl64(covl), cbase, (u64)0, (size_t)n_cand + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
-        }
-        KSP_TRY_HIP(hipMemcpy(&n_slots, cbase + n_cand, 8, hipMemcpyDeviceToHost));
-        if (n_slots >= 0xFFFFFFFFull) { ksp::set_error(std::string(who) + ": match segments of 2^32 - 1 slots or more in a query tile (lower KSP_QUERY_TILE)"); rc = KSP_E_LIMIT; goto done; }
-        if (n_slots < (u64)n_cand * min_hashes) { ksp::set_error(std::string(who) + ": the segments are shorter than their candidates' overlaps"); rc = KSP_E_HIP; goto done; }
-        S.slots += n_slots;
-        KSP_TRY_HIP(hipEventRecord(ev[2], nullptr));
-        // ---- the segments: the sources that have a candidate once more
-        const u64 alive_words = ((u64)H + 31) / 32;
+                if ((rc = t.mem.alloc(&t.live[b][c], (size_t)n_cand))) return rc;
+        size_t b = t.tb2;
+        KSP_HIP(rocprim::radix_sort_pairs(t.tmp2, b, (const u64*)cand_key, t.ckey, (const u32*)cand_ovl, t.covl, (size_t)n_cand, 0, 44, (hipStream_t) nullptr));
+        KSP_HIP(hipMemsetAsync(t.covl + n_cand, 0, 4, nullptr));
+        KSP_HIP(hipMemsetAsync(t.cdead, 0, (size_t)n_cand * 4, nullptr));
+        b = t.tb2;
+        KSP_HIP(rocprim::exclusive_scan(t.tmp2, b, ovl64(t.covl), t.cbase, (u64)0, (size_t)n_cand + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
+        KSP_HIP(hipMemcpy(&t.n_slots, t.cbase + n_cand, 8, hipMemcpyDeviceToHost));
+        if (t.n_slots >= 0xFFFFFFFFull) { ksp::set_error(std::string(who) + ": match segments of 2^32 - 1 slots or more in a query tile (lower KSP_QUERY_TILE)"); return KSP_E_LIMIT; }
+        if (t.n_slots < (u64)n_cand * min_hashes) { ksp::set_error(std::string(who) + ": the segments are shorter than their candidates' overlaps"); return KSP_E_HIP; }
+        S.slots += t.n_slots;
+        return KSP_OK;
+    }
+
+    // ---- the segments: the sources that have a candidate once more
+    int segments(Tile& t) {
+        int rc = KSP_OK;
+        const u64 alive_words = ((u64)t.H + 31) / 32;
         // a row removes min_hashes or more of its query, and a candidate is taken once
-        const u64 rows_cap = std::min<u64>(std::min<u64>(n_cand, (u64)E / min_hashes), max_matches ? (u64)nq * max_matches : ~0ull);
-        if ((rc = ksp::device_fits(who, 4 * n_slots + 4 * alive_words + 2 * sizeof(Row) * rows_cap + (kW ? 4ull * H : 0) + 64,
+        t.rows_cap = std::min<u64>(std::min<u64>(t.n_cand, (u64)t.E / min_hashes), max_matches ? (u64)t.nq * max_matches : ~0ull);
+        if ((rc = ksp::device_fits(who, 4 * t.n_slots + 4 * alive_words + 2 * sizeof(Row) * t.rows_cap + (kW ? 4ull * t.H : 0) + 64,
                                    kW ? "4 per matched hash of a candidate, a bit per query hash, 4 per holder of the query table, 128 per possible row"
                                       : "4 per matched hash of a candidate, a bit per query hash, 48 per possible row")))
-            goto done;
-        if ((rc = A.alloc(&seg, (size_t)n_slots)) || (rc = A.alloc(&alive, (size_t)alive_words)) || (rc = A.alloc(&rows, (size_t)rows_cap + 1)) || (rc = A.alloc(&sorted, (size_t)rows_cap + 1)))
-            goto done;
-        KSP_TRY_HIP(hipMemsetAsync(alive, 0xFF, (size_t)alive_words * 4, nullptr));
-        if (kW) {   // the abundance of every (hash, query) of the tile at its holder slot
-            if ((rc = A.alloc(&habund, (size_t)H))) goto done;
-            KSP_TRY_HIP(hipMemsetAsync(habund, 0, (size_t)H * 4, nullptr));
-            KSP_TRY_HIP(hipMemsetAsync(qwfound, 0, (size_t)kTileMax * 8, nullptr));
-            hipLaunchKernelGGL(k_gather_habund, dim3(G.grid_of(((u64)E + (u64)kThreads * kProbeKeys - 1) / ((u64)kThreads * kProbeKeys))), dim3(kThreads), 0, nullptr, T, d_q_keys, d_q_abund,
-                               (const u32*)B.tag, e0, E, H, habund);
-            KSP_TRY_HIP(hipGetLastError());
+            return rc;
+        if ((rc = t.mem.alloc(&t.seg, (size_t)t.n_slots)) || (rc = t.mem.alloc(&t.alive, (size_t)alive_words)) || (rc = t.mem.alloc(&t.rows, (size_t)t.rows_cap + 1)) ||
+            (rc = t.mem.alloc(&t.sorted, (size_t)t.rows_cap + 1)))
+            return rc;
+        KSP_HIP(hipMemsetAsync(t.alive, 0xFF, (size_t)alive_words * 4, nullptr));
+        if constexpr (kW) {   // the abundance of every (hash, query) of the tile at its holder slot
+            if ((rc = t.mem.alloc(&t.habund, (size_t)t.H))) return rc;
+            KSP_HIP(hipMemsetAsync(t.habund, 0, (size_t)t.H * 4, nullptr));
+            KSP_HIP(hipMemsetAsync(qwfound, 0, (size_t)kTileMax * 8, nullptr));
+            hipLaunchKernelGGL(k_gather_habund, dim3(G.grid_of(((u64)t.E + (u64)kThreads * kProbeKeys - 1) / ((u64)kThreads * kProbeKeys))), dim3(kThreads), 0, nullptr, t.T, d_q_keys,
+                               d_q_abund, (const u32*)B.tag, t.e0, t.E, t.H, t.habund);
+            KSP_HIP(hipGetLastError());
         }
-        P.ckey = ckey; P.cbase = cbase; P.n_cand = n_cand; P.seg = seg; P.n_slots = (u32)n_slots;
-        if (n_fill[0]) {
-            P.list = d_fill[0]; P.n_list = (u32)n_fill[0];
-            hipLaunchKernelGGL((k_gather_sweep<true, true>), dim3(G.grid_of(((u64)P.n_list + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, T, P);
+        GSweep& P = t.P;
+        P.ckey = t.ckey; P.cbase = t.cbase; P.n_cand = t.n_cand; P.seg = t.seg; P.n_slots = (u32)t.n_slots;
+        if (t.n_fill[0]) {
+            P.list = d_fill[0]; P.n_list = (u32)t.n_fill[0];
+            hipLaunchKernelGGL((k_gather_sweep<true, true>), dim3(G.grid_of(((u64)P.n_list + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, t.T, P);
         }
-        if (n_fill[1]) {
-            P.list = d_fill[1]; P.n_list = (u32)n_fill[1];
-            hipLaunchKernelGGL((k_gather_sweep<false, true>), dim3(G.grid_of(P.n_list)), dim3(kThreads), 0, nullptr, T, P);
+        if (t.n_fill[1]) {
+            P.list = d_fill[1]; P.n_list = (u32)t.n_fill[1];
+            hipLaunchKernelGGL((k_gather_sweep<false, true>), dim3(G.grid_of(P.n_list)), dim3(kThreads), 0, nullptr, t.T, P);
         }
-        KSP_TRY_HIP(hipGetLastError());
-        KSP_TRY_HIP(hipEventRecord(ev[3], nullptr));
-        // ---- the rounds
-        {
-            const GRound R{ckey, covl, cbase, seg, alive, cdead, best, qrank, qrem, qdone, n_cand, nq, q0, min_hashes, max_matches, kW ? nullptr : (ksp_gather_row*)(void*)rows, (u32)rows_cap, ctrl};
-            const GAbund AB{habund, seg, qwfound, kW ? (ksp_gather_wrow*)(void*)rows : nullptr};
-            const unsigned gq = (unsigned)(((u64)nq + 255) / 256), gc = G.grid_of(((u64)n_cand + kThreads - 1) / kThreads);
-            u64 n_live[2] = {0, 0};
-            int cur = 0;
-            bool in_tail = false;
-            KSP_TRY_HIP(hipMemsetAsync(ctrl, 0, sizeof h_ctrl, nullptr));
-            hipLaunchKernelGGL(k_gather_init, dim3(gq), dim3(256), 0, nullptr, (const u64*)d_q_off, R);
-            hipLaunchKernelGGL(k_gather_live, dim3(gc), dim3(kThreads), 0, nullptr, R, (const u32*)nullptr, n_cand, W.long_seg, true, live[cur][0], live[cur][1], (int)kKept0);
-            KSP_TRY_HIP(hipGetLastError());
-            KSP_TRY_HIP(hipMemcpy(h_ctrl, ctrl, sizeof h_ctrl, hipMemcpyDeviceToHost));
+        KSP_HIP(hipGetLastError());
+        return KSP_OK;
+    }
+
+    // the takes of a round, by the kernel of the row type: a wave per query of the tile
+    void launch_take(const Tile& t) {
+        const dim3 grid(G.grid_of(((u64)t.nq + kWaves - 1) / kWaves));
+        if constexpr (kW) hipLaunchKernelGGL(k_gather_take_w, grid, dim3(kThreads), 0, nullptr, t.R, t.AB);
+        else hipLaunchKernelGGL(k_gather_take, grid, dim3(kThreads), 0, nullptr, t.R);
+    }
+
+    // the remaining rounds over the live lists `cur`, by the tail kernel of the row type: one workgroup
+    void launch_tail(const Tile& t, const int cur, const u64 (&n_live)[2]) {
+        const u32* const list[2] = {t.live[cur][0], t.live[cur][1]};
+        const u32 bound = (u32)(n_live[0] + n_live[1]) + 1;
+        if constexpr (kW)
+            hipLaunchKernelGGL(k_gather_tail_w, dim3(1), dim3(kTailThreads), 0, nullptr, t.R, t.AB, list[0], (u32)n_live[0], list[1], (u32)n_live[1], bound, d_out);
+        else
+            hipLaunchKernelGGL(k_gather_tail, dim3(1), dim3(kTailThreads), 0, nullptr, t.R, list[0], (u32)n_live[0], list[1], (u32)n_live[1], bound, d_out);
+    }
+
+    // ---- the rounds: every query live, every candidate in the live lists; batches of rounds until no query is live, or the tail
+    int rounds(Tile& t) {
+        t.R = GRound{t.ckey, t.covl, t.cbase, t.seg, t.alive, t.cdead, best, qrank, qrem, qdone, t.n_cand, t.nq, t.q0, min_hashes, max_matches, nullptr, (u32)t.rows_cap, ctrl};
+        t.AB = GAbund{t.habund, t.seg, qwfound, nullptr};
+        if constexpr (kW) t.AB.rows = t.rows;
+        else t.R.rows = t.rows;
+        const GRound& R = t.R;
+        const unsigned gq = (unsigned)(((u64)t.nq + 255) / 256), gc = G.grid_of(((u64)t.n_cand + kThreads - 1) / kThreads);
+        u64 n_live[2] = {0, 0};
+        int cur = 0;
+        bool in_tail = false;
+        KSP_HIP(hipMemsetAsync(ctrl, 0, sizeof h_ctrl, nullptr));
+        hipLaunchKernelGGL(k_gather_init, dim3(gq), dim3(256), 0, nullptr, (const u64*)d_q_off, R);
+        hipLaunchKernelGGL(k_gather_live, dim3(gc), dim3(kThreads), 0, nullptr, R, (const u32*)nullptr, t.n_cand, W.long_seg, true, t.live[cur][0], t.live[cur][1], (int)kKept0);
+        KSP_HIP(hipGetLastError());
+        KSP_HIP(hipMemcpy(h_ctrl, ctrl, sizeof h_ctrl, hipMemcpyDeviceToHost));
+        n_live[0] = h_ctrl[kKept0]; n_live[1] = h_ctrl[kKept1];
+        if (n_live[0] + n_live[1] != t.n_cand) { ksp::set_error(std::string(who) + ": the first live lists do not hold every candidate"); return KSP_E_HIP; }
+        const u64 max_batches = (u64)t.n_cand / KSP_GATHER_BATCH + 2;   // a round with a live query takes a candidate or finishes every query
+        u64 batches = 0;
+        while (h_ctrl[kLiveQ]) {
+            const u64 n_both = n_live[0] + n_live[1];
+            if (W.tail && n_both <= W.tail_cands) {
+                u32 h_out[4] = {0, 0, 0, 0};
+                launch_tail(t, cur, n_live);
+                KSP_HIP(hipGetLastError());
+                KSP_HIP(hipMemcpy(h_out, d_out, 12, hipMemcpyDeviceToHost));
+                if (h_out[2]) { ksp::set_error(std::string(who) + ": the tail's count of live queries does not match the batches'"); return KSP_E_HIP; }
+                if (h_out[1]) { ksp::set_error(std::string(who) + ": the tail left " + std::to_string(h_out[1]) + " queries live after " + std::to_string(h_out[0]) + " rounds"); return KSP_E_HIP; }
+                S.tail_rounds += h_out[0];
+                S.live_at_tail += n_both;
+                in_tail = true;
+                break;
+            }
+            if (++batches > max_batches) { ksp::set_error(std::string(who) + ": more than " + std::to_string(max_batches) + " batches of rounds"); return KSP_E_HIP; }
+            const unsigned g0 = G.grid_of((n_live[0] + kWaves - 1) / kWaves), g1 = G.grid_of(n_live[1]);
+            for (u32 r = 0; r < KSP_GATHER_BATCH; ++r) {
+                hipLaunchKernelGGL(k_gather_count, dim3(g0 + g1), dim3(kThreads), 0, nullptr, R, (const u32*)t.live[cur][0], (u32)n_live[0], (u32)g0, (const u32*)t.live[cur][1], (u32)n_live[1]);
+                launch_take(t);
+            }
+            // the dead leave the lists
+            KSP_HIP(hipMemsetAsync(&ctrl[kKept0], 0, 16, nullptr));
+            for (int c = 0; c < 2; ++c)
+                if (n_live[c])
+                    hipLaunchKernelGGL(k_gather_live, dim3(G.grid_of((n_live[c] + kThreads - 1) / kThreads)), dim3(kThreads), 0, nullptr, R, (const u32*)t.live[cur][c], (u32)n_live[c],
+                                       W.long_seg, false, t.live[cur ^ 1][c], (u32*)nullptr, (int)kKept0 + c);
+            KSP_HIP(hipGetLastError());
+            KSP_HIP(hipMemcpy(h_ctrl, ctrl, sizeof h_ctrl, hipMemcpyDeviceToHost));
+            if (h_ctrl[kKept0] > n_live[0] || h_ctrl[kKept1] > n_live[1]) { ksp::set_error(std::string(who) + ": a compaction kept more candidates than its list holds"); return KSP_E_HIP; }
             n_live[0] = h_ctrl[kKept0]; n_live[1] = h_ctrl[kKept1];
-            if (n_live[0] + n_live[1] != n_cand) { ksp::set_error(std::string(who) + ": the first live lists do not hold every candidate"); rc = KSP_E_HIP; goto done; }
-            const u64 max_batches = (u64)n_cand / KSP_GATHER_BATCH + 2;   // a round with a live query takes a candidate or finishes every query
-            u64 batches = 0;
-            while (h_ctrl[kLiveQ]) {
-                const u64 n_both = n_live[0] + n_live[1];
-                if (W.tail && n_both <= W.tail_cands) {
-                    u32 h_out[4] = {0, 0, 0, 0};
-                    if (kW)
-                        hipLaunchKernelGGL(k_gather_tail_w, dim3(1), dim3(kTailThreads), 0, nullptr, R, AB, (const u32*)live[cur][0], (u32)n_live[0], (const u32*)live[cur][1], (u32)n_live[1],
-                                           (u32)n_both + 1, d_out);
-                    else
-                        hipLaunchKernelGGL(k_gather_tail, dim3(1), dim3(kTailThreads), 0, nullptr, R, (const u32*)live[cur][0], (u32)n_live[0], (const u32*)live[cur][1], (u32)n_live[1],
-                                           (u32)n_both + 1, d_out);
-                    KSP_TRY_HIP(hipGetLastError());
-                    KSP_TRY_HIP(hipMemcpy(h_out, d_out, 12, hipMemcpyDeviceToHost));
-                    if (h_out[2]) { ksp::set_error(std::string(who) + ": the tail's count of live queries does not match the batches'"); rc = KSP_E_HIP; goto done; }
-                    if (h_out[1]) { ksp::set_error(std::string(who) + ": the tail left " + std::to_string(h_out[1]) + " queries live after " + std::to_string(h_out[0]) + " rounds"); rc = KSP_E_HIP; goto done; }
-                    S.tail_rounds += h_out[0];
-                    S.live_at_tail += n_both;
-                    in_tail = true;
-                    break;
-                }
-                if (++batches > max_batches) { ksp::set_error(std::string(who) + ": more than " + std::to_string(max_batches) + " batches of rounds"); rc = KSP_E_HIP; goto done; }
-                const unsigned g0 = G.grid_of((n_live[0] + kWaves - 1) / kWaves), g1 = G.grid_of(n_live[1]);
-                for (u32 r = 0; r < KSP_GATHER_BATCH; ++r) {
-                    hipLaunchKernelGGL(k_gather_count, dim3(g0 + g1), dim3(kThreads), 0, nullptr, R, (const u32*)live[cur][0], (u32)n_live[0], (u32)g0, (const u32*)live[cur][1], (u32)n_live[1]);
-                    if (kW) hipLaunchKernelGGL(k_gather_take_w, dim3(G.grid_of(((u64)nq + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, R, AB);
-                    else hipLaunchKernelGGL(k_gather_take, dim3(G.grid_of(((u64)nq + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, R);
-                }
-                // the dead leave the lists
-                KSP_TRY_HIP(hipMemsetAsync(&ctrl[kKept0], 0, 16, nullptr));
-                for (int c = 0; c < 2; ++c)
-                    if (n_live[c])
-                        hipLaunchKernelGGL(k_gather_live, dim3(G.grid_of((n_live[c] + kThreads - 1) / kThreads)), dim3(kThreads), 0, nullptr, R, (const u32*)live[cur][c], (u32)n_live[c], W.long_seg,
-                                           false, live[cur ^ 1][c], (u32*)nullptr, (int)kKept0 + c);
-                KSP_TRY_HIP(hipGetLastError());
-                KSP_TRY_HIP(hipMemcpy(h_ctrl, ctrl, sizeof h_ctrl, hipMemcpyDeviceToHost));
-                if (h_ctrl[kKept0] > n_live[0] || h_ctrl[kKept1] > n_live[1]) { ksp::set_error(std::string(who) + ": a compaction kept more candidates than its list holds"); rc = KSP_E_HIP; goto done; }
-                n_live[0] = h_ctrl[kKept0]; n_live[1] = h_ctrl[kKept1];
-                cur ^= 1;
-                ++S.batches;
-            }
-            if (in_tail) KSP_TRY_HIP(hipMemcpy(h_ctrl, ctrl, sizeof h_ctrl, hipMemcpyDeviceToHost));
-            S.rounds += h_ctrl[kRounds]; S.fell_below += h_ctrl[kFell];
-            // ---- the tile's rows, by (query, rank)
-            const u64 found = h_ctrl[kRows];
-            if (found > rows_cap) { ksp::set_error(std::string(who) + ": more rows than a tile can have"); rc = KSP_E_HIP; goto done; }
-            if (found) {
-                size_t b = B.tb;
-                KSP_TRY_HIP(rocprim::exclusive_scan(B.tmp, b, (const u32*)qrank, qoff, 0u, (size_t)nq, rocprim::plus<u32>(), (hipStream_t) nullptr));
-                if constexpr (kW) hipLaunchKernelGGL(k_gather_wrows, dim3(G.grid_of((found + 255) / 256)), dim3(256), 0, nullptr, R, (const ksp_gather_wrow*)rows, (u32)found, (const u32*)qoff, sorted);
-                else hipLaunchKernelGGL(k_gather_rows, dim3(G.grid_of((found + 255) / 256)), dim3(256), 0, nullptr, R, (u32)found, (const u32*)qoff, sorted);
-                KSP_TRY_HIP(hipGetLastError());
-                if (h_rows) {
-                    const size_t at = h_rows->size();
-                    h_rows->resize(at + (size_t)found);
-                    KSP_TRY_HIP(hipMemcpy(h_rows->data() + at, sorted, (size_t)found * sizeof(Row), hipMemcpyDeviceToHost));
-                } else if (rows_done < capacity) {
-                    KSP_TRY_HIP(hipMemcpyAsync(d_rows + rows_done, sorted, (size_t)std::min<u64>(found, capacity - rows_done) * sizeof(Row), hipMemcpyDeviceToDevice, nullptr));
-                }
-                rows_done += found;
-            }
+            cur ^= 1;
+            ++S.batches;
         }
-        KSP_TRY_HIP(hipEventRecord(ev[4], nullptr));
-        KSP_TRY_HIP(hipEventSynchronize(ev[4]));
-        KSP_TRY_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); S.ms_table += ms;
-        KSP_TRY_HIP(hipEventElapsedTime(&ms, ev[1], ev[2])); S.ms_candidates += ms;
-        KSP_TRY_HIP(hipEventElapsedTime(&ms, ev[2], ev[3])); S.ms_fill += ms;
-        KSP_TRY_HIP(hipEventElapsedTime(&ms, ev[3], ev[4])); S.ms_rounds += ms;
-        for (void* p : {(void*)ckey, (void*)covl, (void*)cbase, (void*)cdead, (void*)live[0][0], (void*)live[0][1], (void*)live[1][0], (void*)live[1][1], (void*)seg, (void*)alive, (void*)rows,
-                        (void*)sorted, tmp2})
-            KSP_TRY_HIP(A.release(p));
-        if (habund) KSP_TRY_HIP(A.release(habund));
+        if (in_tail) KSP_HIP(hipMemcpy(h_ctrl, ctrl, sizeof h_ctrl, hipMemcpyDeviceToHost));
+        S.rounds += h_ctrl[kRounds]; S.fell_below += h_ctrl[kFell];
+        t.found = h_ctrl[kRows];
+        if (t.found > t.rows_cap) { ksp::set_error(std::string(who) + ": more rows than a tile can have"); return KSP_E_HIP; }
+        return KSP_OK;
     }
-    S.rows = rows_done;
-    *n_rows = rows_done;
-    if (stats) *stats = S;
-    if (!h_rows && rows_done > capacity) {
-        ksp::set_error(std::string(who) + ": " + std::to_string(rows_done) + " rows, room for " + std::to_string(capacity));
-        rc = KSP_E_OVERFLOW;
+
+    // ---- the tile's rows, by (query, rank), behind the rows of the tiles before it
+    int emit_rows(Tile& t) {
+        if (!t.found) return KSP_OK;
+        size_t b = B.tb;
+        KSP_HIP(rocprim::exclusive_scan(B.tmp, b, (const u32*)qrank, qoff, 0u, (size_t)t.nq, rocprim::plus<u32>(), (hipStream_t) nullptr));
+        hipLaunchKernelGGL(k_gather_rows<Row>, dim3(G.grid_of((t.found + 255) / 256)), dim3(256), 0, nullptr, t.R, (const Row*)t.rows, (u32)t.found, (const u32*)qoff, t.sorted);
+        KSP_HIP(hipGetLastError());
+        if (h_rows) {
+            const size_t at = h_rows->size();
+            h_rows->resize(at + (size_t)t.found);
+            KSP_HIP(hipMemcpy(h_rows->data() + at, t.sorted, (size_t)t.found * sizeof(Row), hipMemcpyDeviceToHost));
+        } else if (rows_done < capacity) {
+            KSP_HIP(hipMemcpyAsync(d_rows + rows_done, t.sorted, (size_t)std::min<u64>(t.found, capacity - rows_done) * sizeof(Row), hipMemcpyDeviceToDevice, nullptr));
+        }
+        rows_done += t.found;
+        return KSP_OK;
     }
-done:
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    return rc;
+
+    // the tile has reached event `last`: the times between its events go to the phases' sums
+    int add_times(const int last) {
+        float* const phase[4] = {&S.ms_table, &S.ms_candidates, &S.ms_fill, &S.ms_rounds};
+        KSP_HIP(hipEventSynchronize(ev[last]));
+        for (int i = 0; i < last; ++i) {
+            float ms = 0;
+            KSP_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+            *phase[i] += ms;
+        }
+        return KSP_OK;
+    }
+
+    // tile `index`: the steps between the event records that bound ms_table, ms_candidates, ms_fill and ms_rounds
+    int run_tile(const u32 index) {
+        int rc = KSP_OK;
+        Tile t;
+        t.q0 = (u32)((u64)index * W.tile);
+        t.nq = (u32)(std::min<u64>((u64)t.q0 + W.tile, n_q) - t.q0);
+        t.e0 = h_q_off[t.q0];
+        t.E = (u32)(h_q_off[t.q0 + t.nq] - t.e0);
+        if (t.E == 0) return KSP_OK;   // a tile of empty queries matches nothing
+        KSP_HIP(hipEventRecord(ev[0], nullptr));
+        if ((rc = query_table_build(who, G, B, d_q_keys, d_q_off, t.q0, t.nq, t.e0, t.E, &t.T, &t.U, &t.H))) return rc;
+        KSP_HIP(hipEventRecord(ev[1], nullptr));
+        if ((rc = candidates(t))) return rc;
+        if (t.n_cand == 0) {   // nothing reaches min_hashes: no row for any query of the tile
+            KSP_HIP(hipEventRecord(ev[2], nullptr));
+            return add_times(2);
+        }
+        if ((rc = sort_candidates(t))) return rc;
+        KSP_HIP(hipEventRecord(ev[2], nullptr));
+        if ((rc = segments(t))) return rc;
+        KSP_HIP(hipEventRecord(ev[3], nullptr));
+        if ((rc = rounds(t)) || (rc = emit_rows(t))) return rc;
+        KSP_HIP(hipEventRecord(ev[4], nullptr));
+        return add_times(4);
+    }
+
+    int run(u64* n_rows, ksp_gather_stats* stats) {
+        int rc = KSP_OK;
+        if ((rc = setup())) return rc;
+        for (u32 index = 0; index < n_tiles; ++index)
+            if ((rc = run_tile(index))) return rc;
+        S.rows = rows_done;
+        *n_rows = rows_done;
+        if (stats) *stats = S;
+        if (!h_rows && rows_done > capacity) {
+            ksp::set_error(std::string(who) + ": " + std::to_string(rows_done) + " rows, room for " + std::to_string(capacity));
+            return KSP_E_OVERFLOW;
+        }
+        return KSP_OK;
+    }
+};
+
+// what the two device entries do behind their own first refusals
+template <class Row>
+int gather_device_entry(const char* who, const int device, const u64* d_db_keys, const u64* h_db_off, const u32 n_db, const u64* d_q_keys, const u32* d_q_abund, const u64* h_q_off,
+                        const u32 n_q, const u32 min_hashes, const u32 max_matches, Row* d_rows, const u64 capacity, u64* n_rows, ksp_gather_stats* stats) {
+    GatherSwitches W;
+    if (const int rc = check_gather_args(who, d_db_keys, h_db_off, n_db, d_q_keys, h_q_off, n_q, min_hashes, n_rows)) return rc;
+    if (!d_rows && capacity) { ksp::set_error(std::string(who) + ": d_rows is NULL but capacity is not 0"); return KSP_E_ARG; }
+    if (const int rc = read_switches(who, W)) return rc;
+    if (const int rc = ksp::set_device(who, device)) return rc;
+    return GatherCall<Row>{who, W, d_db_keys, h_db_off, n_db, d_q_keys, d_q_abund, h_q_off, n_q, min_hashes, max_matches, d_rows, capacity, nullptr}.run(n_rows, stats);
+}
+
+// what the two host entries do behind their own first refusals; q_abund: the weighted call's, NULL for the other
+template <class Row>
+int gather_host_entry(const char* who, const u64* db_keys, const u64* db_off, const u32 n_db, const u64* q_keys, const u32* q_abund, const u64* q_off, const u32 n_q,
+                      const u32 min_hashes, const u32 max_matches, const int device, Row** rows, u64* n_rows, ksp_gather_stats* stats) {
+    GatherSwitches W;
+    if (const int rc = check_gather_args(who, db_keys, db_off, n_db, q_keys, q_off, n_q, min_hashes, n_rows)) return rc;
+    if (const int rc = read_switches(who, W)) return rc;
+    if (const int rc = ksp::set_device(who, device)) return rc;
+    int rc = KSP_OK;
+    ksp::DeviceArena A;
+    const u64 n_dbk = db_off[n_db], n_qk = q_off[n_q];
+    u64 *d_db = nullptr, *d_q = nullptr, found = 0;
+    u32* d_a = nullptr;
+    std::vector<Row> got;
+    if ((rc = q_abund ? ksp::device_fits(who, 8ull * (n_dbk + n_qk + 2) + 4ull * (n_qk + 1), "the keys of both sides and the queries' abundances")
+                      : ksp::device_fits(who, 8ull * (n_dbk + n_qk + 2), "the keys of both sides")))
+        return rc;
+    if ((rc = query_upload_keys(A, db_keys, n_dbk, q_keys, n_qk, &d_db, &d_q))) return rc;
+    if (q_abund) {
+        if ((rc = A.alloc(&d_a, (size_t)n_qk + 1))) return rc;
+        KSP_HIP(hipMemcpy(d_a, q_abund, (size_t)n_qk * 4, hipMemcpyHostToDevice));
+    }
+    try {
+        rc = GatherCall<Row>{who, W, d_db, db_off, n_db, d_q, d_a, q_off, n_q, min_hashes, max_matches, nullptr, 0, &got}.run(&found, stats);
+    } catch (const std::bad_alloc&) {
+        ksp::set_error(std::string(who) + ": out of host memory");
+        rc = KSP_E_LIMIT;
+    }
+    if (rc != KSP_OK) return rc;
+    Row* const out = (Row*)std::malloc(std::max<size_t>(got.size(), 1) * sizeof(Row));
+    if (!out) { ksp::set_error(std::string(who) + ": out of host memory"); return KSP_E_LIMIT; }
+    if (!got.empty()) std::memcpy(out, got.data(), got.size() * sizeof(Row));
+    *rows = out;
+    *n_rows = found;
+    return KSP_OK;
 }
 
 }  // namespace
 
 extern "C" int ksp_gather_device(int device, const uint64_t* d_db_keys, const uint64_t* h_db_offsets, uint32_t n_db, const uint64_t* d_q_keys, const uint64_t* h_q_offsets,
                                  uint32_t n_q, uint32_t min_hashes, uint32_t max_matches, ksp_gather_row* d_rows, uint64_t capacity, uint64_t* n_rows, ksp_gather_stats* stats) {
-    const char* who = "ksp_gather_device";
-    GatherSwitches W;
-    if (const int rc = check_gather_args(who, d_db_keys, h_db_offsets, n_db, d_q_keys, h_q_offsets, n_q, min_hashes, n_rows)) return rc;
-    if (!d_rows && capacity) { ksp::set_error(std::string(who) + ": d_rows is NULL but capacity is not 0"); return KSP_E_ARG; }
-    if (const int rc = read_switches(who, W)) return rc;
-    if (const int rc = ksp::set_device(who, device)) return rc;
-    return gather_on_device<ksp_gather_row>(who, W, d_db_keys, h_db_offsets, n_db, d_q_keys, nullptr, h_q_offsets, n_q, min_hashes, max_matches, d_rows, capacity, nullptr, n_rows, stats);
+    return gather_device_entry<ksp_gather_row>("ksp_gather_device", device, d_db_keys, h_db_offsets, n_db, d_q_keys, nullptr, h_q_offsets, n_q, min_hashes, max_matches, d_rows, capacity,
+                                               n_rows, stats);
 }
 
 extern "C" int ksp_gather_host(const uint64_t* db_keys, const uint64_t* db_offsets, uint32_t n_db, const uint64_t* q_keys, const uint64_t* q_offsets, uint32_t n_q,
                                uint32_t min_hashes, uint32_t max_matches, int device, ksp_gather_row** rows, uint64_t* n_rows, ksp_gather_stats* stats) {
     const char* who = "ksp_gather_host";
-    GatherSwitches W;
     if (!rows) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
-    if (const int rc = check_gather_args(who, db_keys, db_offsets, n_db, q_keys, q_offsets, n_q, min_hashes, n_rows)) return rc;
-    if (const int rc = read_switches(who, W)) return rc;
-    if (const int rc = ksp::set_device(who, device)) return rc;
-    int rc = KSP_OK;
-    ksp::DeviceArena A;
-    const u64 n_dbk = db_offsets[n_db], n_qk = q_offsets[n_q];
-    u64 *d_db = nullptr, *d_q = nullptr, found = 0;
-    std::vector<ksp_gather_row> got;
-    ksp_gather_row* out = nullptr;
-    if ((rc = ksp::device_fits(who, 8ull * (n_dbk + n_qk + 2), "the keys of both sides"))) return rc;
-    if ((rc = A.alloc(&d_db, (size_t)n_dbk + 1)) || (rc = A.alloc(&d_q, (size_t)n_qk + 1))) return rc;
-    KSP_TRY_HIP(hipMemcpy(d_db, db_keys, (size_t)n_dbk * 8, hipMemcpyHostToDevice));
-    KSP_TRY_HIP(hipMemcpy(d_q, q_keys, (size_t)n_qk * 8, hipMemcpyHostToDevice));
-    try {
-        rc = gather_on_device<ksp_gather_row>(who, W, d_db, db_offsets, n_db, d_q, nullptr, q_offsets, n_q, min_hashes, max_matches, nullptr, 0, &got, &found, stats);
-    } catch (const std::bad_alloc&) {
-        ksp::set_error(std::string(who) + ": out of host memory");
-        rc = KSP_E_LIMIT;
-    }
-    if (rc != KSP_OK) goto done;
-    out = (ksp_gather_row*)std::malloc(std::max<size_t>(got.size(), 1) * sizeof(ksp_gather_row));
-    if (!out) { ksp::set_error(std::string(who) + ": out of host memory"); rc = KSP_E_LIMIT; goto done; }
-    if (!got.empty()) std::memcpy(out, got.data(), got.size() * sizeof(ksp_gather_row));
-    *rows = out;
-    *n_rows = found;
-done:
-    return rc;
+    return gather_host_entry<ksp_gather_row>(who, db_keys, db_offsets, n_db, q_keys, nullptr, q_offsets, n_q, min_hashes, max_matches, device, rows, n_rows, stats);
 }
 
 extern "C" int ksp_gather_abund_device(int device, const uint64_t* d_db_keys, const uint64_t* h_db_offsets, uint32_t n_db, const uint64_t* d_q_keys, const uint32_t* d_q_abund,
                                        const uint64_t* h_q_offsets, uint32_t n_q, uint32_t min_hashes, uint32_t max_matches, ksp_gather_wrow* d_rows, uint64_t capacity,
                                        uint64_t* n_rows, ksp_gather_stats* stats) {
     const char* who = "ksp_gather_abund_device";
-    GatherSwitches W;
     if (!d_q_abund) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
-    if (const int rc = check_gather_args(who, d_db_keys, h_db_offsets, n_db, d_q_keys, h_q_offsets, n_q, min_hashes, n_rows)) return rc;
-    if (!d_rows && capacity) { ksp::set_error(std::string(who) + ": d_rows is NULL but capacity is not 0"); return KSP_E_ARG; }
-    if (const int rc = read_switches(who, W)) return rc;
-    if (const int rc = ksp::set_device(who, device)) return rc;
-    return gather_on_device<ksp_gather_wrow>(who, W, d_db_keys, h_db_offsets, n_db, d_q_keys, d_q_abund, h_q_offsets, n_q, min_hashes, max_matches, d_rows, capacity, nullptr, n_rows,
-                                             stats);
+    return gather_device_entry<ksp_gather_wrow>(who, device, d_db_keys, h_db_offsets, n_db, d_q_keys, d_q_abund, h_q_offsets, n_q, min_hashes, max_matches, d_rows, capacity, n_rows, stats);
 }
 
 extern "C" int ksp_gather_abund_host(const uint64_t* db_keys, const uint64_t* db_offsets, uint32_t n_db, const uint64_t* q_keys, const uint32_t* q_abund, const uint64_t* q_offsets,
                                      uint32_t n_q, uint32_t min_hashes, uint32_t max_matches, int device, ksp_gather_wrow** rows, uint64_t* n_rows, ksp_gather_stats* stats) {
     const char* who = "ksp_gather_abund_host";
-    GatherSwitches W;
     if (!rows || !q_abund) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
-    if (const int rc = check_gather_args(who, db_keys, db_offsets, n_db, q_keys, q_offsets, n_q, min_hashes, n_rows)) return rc;
-    if (const int rc = read_switches(who, W)) return rc;
-    if (const int rc = ksp::set_device(who, device)) return rc;
-    int rc = KSP_OK;
-    ksp::DeviceArena A;
-    const u64 n_dbk = db_offsets[n_db], n_qk = q_offsets[n_q];
-    u64 *d_db = nullptr, *d_q = nullptr, found = 0;
-    u32* d_a = nullptr;
-    std::vector<ksp_gather_wrow> got;
-    ksp_gather_wrow* out = nullptr;
-    if ((rc = ksp::device_fits(who, 8ull * (n_dbk + n_qk + 2) + 4ull * (n_qk + 1), "the keys of both sides and the queries' abundances"))) return rc;
-    if ((rc = A.alloc(&d_db, (size_t)n_dbk + 1)) || (rc = A.alloc(&d_q, (size_t)n_qk + 1)) || (rc = A.alloc(&d_a, (size_t)n_qk + 1))) return rc;
-    KSP_TRY_HIP(hipMemcpy(d_db, db_keys, (size_t)n_dbk * 8, hipMemcpyHostToDevice));
-    KSP_TRY_HIP(hipMemcpy(d_q, q_keys, (size_t)n_qk * 8, hipMemcpyHostToDevice));
-    KSP_TRY_HIP(hipMemcpy(d_a, q_abund, (size_t)n_qk * 4, hipMemcpyHostToDevice));
-    try {
-        rc = gather_on_device<ksp_gather_wrow>(who, W, d_db, db_offsets, n_db, d_q, d_a, q_offsets, n_q, min_hashes, max_matches, nullptr, 0, &got, &found, stats);
-    } catch (const std::bad_alloc&) {
-        ksp::set_error(std::string(who) + ": out of host memory");
-        rc = KSP_E_LIMIT;
-    }
-    if (rc != KSP_OK) goto done;
-    out = (ksp_gather_wrow*)std::malloc(std::max<size_t>(got.size(), 1) * sizeof(ksp_gather_wrow));
-    if (!out) { ksp::set_error(std::string(who) + ": out of host memory"); rc = KSP_E_LIMIT; goto done; }
-    if (!got.empty()) std::memcpy(out, got.data(), got.size() * sizeof(ksp_gather_wrow));
-    *rows = out;
-    *n_rows = found;
-done:
-    return rc;
+    return gather_host_entry<ksp_gather_wrow>(who, db_keys, db_offsets, n_db, q_keys, q_abund, q_offsets, n_q, min_hashes, max_matches, device, rows, n_rows, stats);
 }

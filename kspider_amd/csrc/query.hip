@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -170,24 +171,17 @@ int query_on_device(const char* who, const u64* d_db_keys, const u64* h_db_off, 
     u64 e_max = 0;
     if ((rc = query_tiles(who, h_q_off, n_q, tile, &n_tiles, &e_max))) return rc;
     if ((rc = ksp::workgroup_cap("KSP_QUERY_MAX_WORKGROUPS", who, G))) return rc;
-    // the probe sources by run length; a source without entries shares nothing
+    // the probe sources by run length: the database's, then in mode 1 the queries (the last query has no query above it)
     std::vector<u32> probes[2];   // [0] short, [1] long
-    for (u32 p = 0; p < n_db; ++p)
-        if (const u64 len = h_db_off[p + 1] - h_db_off[p]) probes[len >= long_run].push_back(p);
-    if (mode == KSP_QUERY_CROSS_AND_SELF)
-        for (u32 i = 0; i + 1 < n_q; ++i)   // (the last query has no query above it)
-            if (const u64 len = h_q_off[i + 1] - h_q_off[i]) probes[len >= long_run].push_back(n_db + i);
+    query_split_sources(h_db_off, n_db, long_run, 0, probes);
+    if (mode == KSP_QUERY_CROSS_AND_SELF) query_split_sources(h_q_off, n_q - 1, long_run, n_db, probes);
     S.n_db = n_db; S.n_q = n_q; S.db_entries = h_db_off[n_db]; S.q_entries = h_q_off[n_q];
     S.short_sources = probes[0].size(); S.long_sources = probes[1].size();
     S.tile = (u32)tile; S.long_run = long_run; S.list_capacity = (u32)list_cap;
 
     ksp::DeviceArena A;
-    u64 *d_db_off = nullptr, *d_q_off = nullptr;
-    u32* d_list[2] = {nullptr, nullptr};
-    unsigned long long* d_count = nullptr;   // [0] the cursor, [1] the list overflows
+    ksp::Events<3> ev;
     QTableBufs B;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    unsigned long long h_count[2] = {0, 0};
     B.e_max = e_max;
     if ((rc = query_table_scratch(e_max, &B.tb))) return rc;
     B.tb = std::max<size_t>(B.tb, 8);
@@ -196,16 +190,13 @@ int query_on_device(const char* who, const u64* d_db_keys, const u64* h_db_off, 
     if ((rc = ksp::device_fits(who, 8ull * ((u64)n_db + n_q + 2) + 4ull * (probes[0].size() + probes[1].size()) + B.bytes() + B.tb + 64,
                                "8 per source, 4 per probe source, 40 per entry of the largest query tile, its directory, the sort's scratch")))
         return rc;
-    if ((rc = A.alloc(&d_db_off, (size_t)n_db + 1)) || (rc = A.alloc(&d_q_off, (size_t)n_q + 1)) || (rc = A.alloc(&d_count, 2))) return rc;
-    for (int c = 0; c < 2; ++c)
-        if (!probes[c].empty() && (rc = A.alloc(&d_list[c], probes[c].size()))) return rc;
+    u64 *d_db_off = nullptr, *d_q_off = nullptr;
+    u32* d_list[2] = {nullptr, nullptr};
+    unsigned long long* d_count = nullptr;   // [0] the cursor, [1] the list overflows
+    if ((rc = query_upload_front(A, h_db_off, n_db, h_q_off, n_q, probes, &d_db_off, &d_q_off, d_list)) || (rc = A.alloc(&d_count, 2))) return rc;
     if (e_max && ((rc = query_table_alloc(A, B)) || (rc = A.alloc_bytes(&B.tmp, B.tb)))) return rc;
-    KSP_TRY_HIP(hipMemcpy(d_db_off, h_db_off, ((size_t)n_db + 1) * 8, hipMemcpyHostToDevice));
-    KSP_TRY_HIP(hipMemcpy(d_q_off, h_q_off, ((size_t)n_q + 1) * 8, hipMemcpyHostToDevice));
-    for (int c = 0; c < 2; ++c)
-        if (!probes[c].empty()) KSP_TRY_HIP(hipMemcpy(d_list[c], probes[c].data(), probes[c].size() * 4, hipMemcpyHostToDevice));
-    KSP_TRY_HIP(hipMemset(d_count, 0, 16));
-    for (hipEvent_t& e : ev) KSP_TRY_HIP(hipEventCreate(&e));
+    KSP_HIP(hipMemset(d_count, 0, 16));
+    if ((rc = ev.create())) return rc;
 
     for (u32 t = 0; t < n_tiles; ++t) {
         const u32 q0 = (u32)((u64)t * tile), nq = (u32)(std::min<u64>((u64)q0 + tile, n_q) - q0);
@@ -213,44 +204,40 @@ int query_on_device(const char* who, const u64* d_db_keys, const u64* h_db_off, 
         const u32 E = (u32)(h_q_off[q0 + nq] - e0);
         if (E == 0) continue;   // a tile of empty queries shares nothing
         // ---- the table
-        KSP_TRY_HIP(hipEventRecord(ev[0], nullptr));
+        KSP_HIP(hipEventRecord(ev[0], nullptr));
         QTable T;
         u32 U = 0, H = 0;
-        if ((rc = query_table_build(who, G, B, d_q_keys, d_q_off, q0, nq, e0, E, &T, &U, &H))) goto done;
-        KSP_TRY_HIP(hipEventRecord(ev[1], nullptr));
+        if ((rc = query_table_build(who, G, B, d_q_keys, d_q_off, q0, nq, e0, E, &T, &U, &H))) return rc;
+        KSP_HIP(hipEventRecord(ev[1], nullptr));
         // ---- the probe: every probe source against this tile
-        {
-            QProbe P{d_db_keys, d_db_off, d_q_keys, d_q_off, n_db, nullptr, 0, (u32)list_cap, d_edges, d_edges ? capacity : 0, &d_count[0], &d_count[1]};
-            if (!probes[0].empty()) {
-                P.list = d_list[0]; P.n_list = (u32)probes[0].size();
-                hipLaunchKernelGGL(k_query_probe<true>, dim3(G.grid_of(((u64)P.n_list + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, T, P);
-            }
-            if (!probes[1].empty()) {
-                P.list = d_list[1]; P.n_list = (u32)probes[1].size();
-                hipLaunchKernelGGL(k_query_probe<false>, dim3(G.grid_of(P.n_list)), dim3(kThreads), 0, nullptr, T, P);
-            }
-            KSP_TRY_HIP(hipGetLastError());
+        QProbe P{d_db_keys, d_db_off, d_q_keys, d_q_off, n_db, nullptr, 0, (u32)list_cap, d_edges, d_edges ? capacity : 0, &d_count[0], &d_count[1]};
+        if (!probes[0].empty()) {
+            P.list = d_list[0]; P.n_list = (u32)probes[0].size();
+            hipLaunchKernelGGL(k_query_probe<true>, dim3(G.grid_of(((u64)P.n_list + kWaves - 1) / kWaves)), dim3(kThreads), 0, nullptr, T, P);
         }
-        KSP_TRY_HIP(hipEventRecord(ev[2], nullptr));
-        KSP_TRY_HIP(hipEventSynchronize(ev[2]));
+        if (!probes[1].empty()) {
+            P.list = d_list[1]; P.n_list = (u32)probes[1].size();
+            hipLaunchKernelGGL(k_query_probe<false>, dim3(G.grid_of(P.n_list)), dim3(kThreads), 0, nullptr, T, P);
+        }
+        KSP_HIP(hipGetLastError());
+        KSP_HIP(hipEventRecord(ev[2], nullptr));
+        KSP_HIP(hipEventSynchronize(ev[2]));
         float ms_t = 0, ms_p = 0;
-        KSP_TRY_HIP(hipEventElapsedTime(&ms_t, ev[0], ev[1]));
-        KSP_TRY_HIP(hipEventElapsedTime(&ms_p, ev[1], ev[2]));
+        KSP_HIP(hipEventElapsedTime(&ms_t, ev[0], ev[1]));
+        KSP_HIP(hipEventElapsedTime(&ms_p, ev[1], ev[2]));
         S.ms_table += ms_t; S.ms_probe += ms_p;
         S.table_keys += U; S.table_holders += H; ++S.passes;
     }
-    KSP_TRY_HIP(hipMemcpy(h_count, d_count, 16, hipMemcpyDeviceToHost));
+    unsigned long long h_count[2] = {0, 0};
+    KSP_HIP(hipMemcpy(h_count, d_count, 16, hipMemcpyDeviceToHost));
     S.edges = h_count[0]; S.list_overflows = h_count[1];
     *n_edges = h_count[0];
     if (stats) *stats = S;
     if (h_count[0] > capacity) {
         ksp::set_error(std::string(who) + ": " + std::to_string(h_count[0]) + " edges, room for " + std::to_string(capacity));
-        rc = KSP_E_OVERFLOW;
+        return KSP_E_OVERFLOW;
     }
-done:
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    return rc;
+    return KSP_OK;
 }
 
 }  // namespace
@@ -273,23 +260,19 @@ extern "C" int ksp_debug_copy_times(int device, uint64_t bytes, int reps, float*
     if (const int rc = ksp::set_device(who, device)) return rc;
     int rc = KSP_OK;
     ksp::DeviceArena A;
+    ksp::Events<2> ev;
     void *src = nullptr, *dst = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if ((rc = ksp::device_fits(who, 2 * bytes, "two buffers")) || (rc = A.alloc_bytes(&src, (size_t)bytes)) || (rc = A.alloc_bytes(&dst, (size_t)bytes))) return rc;
-    KSP_TRY_HIP(hipMemset(src, 1, (size_t)bytes));
-    KSP_TRY_HIP(hipEventCreate(&ev0));
-    KSP_TRY_HIP(hipEventCreate(&ev1));
+    KSP_HIP(hipMemset(src, 1, (size_t)bytes));
+    if ((rc = ev.create())) return rc;
     for (int r = 0; r < reps; ++r) {
-        KSP_TRY_HIP(hipEventRecord(ev0, nullptr));
-        KSP_TRY_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, nullptr));
-        KSP_TRY_HIP(hipEventRecord(ev1, nullptr));
-        KSP_TRY_HIP(hipEventSynchronize(ev1));
-        KSP_TRY_HIP(hipEventElapsedTime(&ms[r], ev0, ev1));
+        KSP_HIP(hipEventRecord(ev[0], nullptr));
+        KSP_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, nullptr));
+        KSP_HIP(hipEventRecord(ev[1], nullptr));
+        KSP_HIP(hipEventSynchronize(ev[1]));
+        KSP_HIP(hipEventElapsedTime(&ms[r], ev[0], ev[1]));
     }
-done:
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    return rc;
+    return KSP_OK;
 }
 
 extern "C" int ksp_query_device(int device, const uint64_t* d_db_keys, const uint64_t* h_db_offsets, uint32_t n_db, const uint64_t* d_q_keys,
@@ -309,51 +292,44 @@ extern "C" int ksp_query_host(const uint64_t* db_keys, const uint64_t* db_offset
     if (const int rc = ksp::set_device(who, device)) return rc;
     int rc = KSP_OK;
     ksp::DeviceArena A;
+    ksp::Events<2> ev;
     const u64 n_dbk = db_offsets[n_db], n_qk = q_offsets[n_q];
     u64 *d_db = nullptr, *d_q = nullptr, found = 0;
-    ksp_edge *d_edges = nullptr, *d_sorted = nullptr, *h_edges = nullptr;
-    void* tmp = nullptr;
-    size_t tb = 0;
+    ksp_edge* d_edges = nullptr;
     ksp_query_stats S;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // a first guess that a few hits per query satisfy; the call reports the exact size when it does not
     u64 capacity = std::max<u64>(4096, 8ull * ((u64)n_db + n_q));
     if ((rc = ksp::device_fits(who, 8ull * (n_dbk + n_qk + 2) + 16ull * capacity, "the keys of both sides and the first edge buffer"))) return rc;
-    if ((rc = A.alloc(&d_db, (size_t)n_dbk + 1)) || (rc = A.alloc(&d_q, (size_t)n_qk + 1)) || (rc = A.alloc(&d_edges, (size_t)capacity))) return rc;
-    KSP_TRY_HIP(hipMemcpy(d_db, db_keys, (size_t)n_dbk * 8, hipMemcpyHostToDevice));
-    KSP_TRY_HIP(hipMemcpy(d_q, q_keys, (size_t)n_qk * 8, hipMemcpyHostToDevice));
+    if ((rc = query_upload_keys(A, db_keys, n_dbk, q_keys, n_qk, &d_db, &d_q)) || (rc = A.alloc(&d_edges, (size_t)capacity))) return rc;
     rc = query_on_device(who, d_db, db_offsets, n_db, d_q, q_offsets, n_q, mode, d_edges, capacity, &found, &S);
     if (rc == KSP_E_OVERFLOW) {   // once more, at the exact size
-        KSP_TRY_HIP(A.release(d_edges));
+        KSP_HIP(A.release(d_edges));
         d_edges = nullptr;
         capacity = found;
         if ((rc = ksp::device_fits(who, 16ull * capacity, "the edges"))) return rc;
         if ((rc = A.alloc(&d_edges, (size_t)capacity))) return rc;
         rc = query_on_device(who, d_db, db_offsets, n_db, d_q, q_offsets, n_q, mode, d_edges, capacity, &found, &S);
     }
-    if (rc != KSP_OK) goto done;
-    KSP_TRY_HIP(hipEventCreate(&ev0));
-    KSP_TRY_HIP(hipEventCreate(&ev1));
-    h_edges = (ksp_edge*)std::malloc((size_t)std::max<u64>(found, 1) * sizeof(ksp_edge));
-    if (!h_edges) { ksp::set_error(std::string(who) + ": out of host memory"); rc = KSP_E_LIMIT; goto done; }
+    if (rc != KSP_OK) return rc;
+    if ((rc = ev.create())) return rc;
+    std::unique_ptr<ksp_edge, decltype(&std::free)> h_edges((ksp_edge*)std::malloc((size_t)std::max<u64>(found, 1) * sizeof(ksp_edge)), &std::free);
+    if (!h_edges) { ksp::set_error(std::string(who) + ": out of host memory"); return KSP_E_LIMIT; }
     if (found) {
-        KSP_TRY_HIP(rocprim::merge_sort(nullptr, tb, (const ksp_edge*)d_edges, d_sorted, (size_t)found, EdgeBefore(), (hipStream_t) nullptr));
+        ksp_edge* d_sorted = nullptr;
+        void* tmp = nullptr;
+        size_t tb = 0;
+        KSP_HIP(rocprim::merge_sort(nullptr, tb, (const ksp_edge*)d_edges, d_sorted, (size_t)found, EdgeBefore(), (hipStream_t) nullptr));
         tb = std::max<size_t>(tb, 8);
-        if ((rc = ksp::device_fits(who, 16ull * found + tb, "the sorted edges and the sort's scratch"))) goto done;
-        if ((rc = A.alloc(&d_sorted, (size_t)found)) || (rc = A.alloc_bytes(&tmp, tb))) goto done;
-        KSP_TRY_HIP(hipEventRecord(ev0, nullptr));
-        KSP_TRY_HIP(rocprim::merge_sort(tmp, tb, (const ksp_edge*)d_edges, d_sorted, (size_t)found, EdgeBefore(), (hipStream_t) nullptr));
-        KSP_TRY_HIP(hipEventRecord(ev1, nullptr));
-        KSP_TRY_HIP(hipMemcpy(h_edges, d_sorted, (size_t)found * sizeof(ksp_edge), hipMemcpyDeviceToHost));
-        KSP_TRY_HIP(hipEventElapsedTime(&S.ms_sort, ev0, ev1));
+        if ((rc = ksp::device_fits(who, 16ull * found + tb, "the sorted edges and the sort's scratch"))) return rc;
+        if ((rc = A.alloc(&d_sorted, (size_t)found)) || (rc = A.alloc_bytes(&tmp, tb))) return rc;
+        KSP_HIP(hipEventRecord(ev[0], nullptr));
+        KSP_HIP(rocprim::merge_sort(tmp, tb, (const ksp_edge*)d_edges, d_sorted, (size_t)found, EdgeBefore(), (hipStream_t) nullptr));
+        KSP_HIP(hipEventRecord(ev[1], nullptr));
+        KSP_HIP(hipMemcpy(h_edges.get(), d_sorted, (size_t)found * sizeof(ksp_edge), hipMemcpyDeviceToHost));
+        KSP_HIP(hipEventElapsedTime(&S.ms_sort, ev[0], ev[1]));
     }
-    *edges = h_edges;
-    h_edges = nullptr;
+    *edges = h_edges.release();
     *n_edges = found;
     if (stats) *stats = S;
-done:
-    if (h_edges) std::free(h_edges);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    return rc;
+    return KSP_OK;
 }

@@ -1,5 +1,6 @@
 // The table side of query mode, shared by query.hip and gather.hip: one tile's collision-free sorted table of the
-// query hashes with its directory, the look-up a probing lane does in it, and the host sequence that builds it.
+// query hashes with its directory, the look-up a probing lane does in it, the host sequence that builds it, and the front of a
+// call that both share: the probe sources split by run length, the offsets and the lists uploaded, the host keys uploaded.
 //
 //   table    per tile of at most KSP_QUERY_TILE consecutive queries: every query entry tagged with its query index inside the
 //            tile (k_query_tag), (key, tag) sorted by key with rocPRIM's radix sort (stable: the tags of a key ascend), adjacent
@@ -14,6 +15,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <string>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -181,6 +183,36 @@ int query_tiles(const char* who, const u64* h_q_off, const u32 n_q, const u64 ti
     return KSP_OK;
 }
 
+// The sources 0 .. n - 1 that have entries (one without shares nothing), numbered from `first`, appended to probes[0] when the run
+// is shorter than long_run entries and to probes[1] otherwise.
+void query_split_sources(const u64* h_off, const u32 n, const u64 long_run, const u32 first, std::vector<u32> (&probes)[2]) {
+    for (u32 p = 0; p < n; ++p)
+        if (const u64 len = h_off[p + 1] - h_off[p]) probes[len >= long_run].push_back(first + p);
+}
+
+// both offset arrays as *d_db_off, *d_q_off and every non-empty list as d_list[c] in the arena (an empty list stays NULL)
+int query_upload_front(ksp::DeviceArena& A, const u64* h_db_off, const u32 n_db, const u64* h_q_off, const u32 n_q, const std::vector<u32> (&probes)[2], u64** d_db_off,
+                       u64** d_q_off, u32* (&d_list)[2]) {
+    int rc = KSP_OK;
+    if ((rc = A.alloc(d_db_off, (size_t)n_db + 1)) || (rc = A.alloc(d_q_off, (size_t)n_q + 1))) return rc;
+    for (int c = 0; c < 2; ++c)
+        if (!probes[c].empty() && (rc = A.alloc(&d_list[c], probes[c].size()))) return rc;
+    KSP_HIP(hipMemcpy(*d_db_off, h_db_off, ((size_t)n_db + 1) * 8, hipMemcpyHostToDevice));
+    KSP_HIP(hipMemcpy(*d_q_off, h_q_off, ((size_t)n_q + 1) * 8, hipMemcpyHostToDevice));
+    for (int c = 0; c < 2; ++c)
+        if (!probes[c].empty()) KSP_HIP(hipMemcpy(d_list[c], probes[c].data(), probes[c].size() * 4, hipMemcpyHostToDevice));
+    return KSP_OK;
+}
+
+// the host keys of both sides as *d_db, *d_q in the arena (an entry more than the keys: never an allocation of 0 bytes)
+int query_upload_keys(ksp::DeviceArena& A, const u64* db_keys, const u64 n_dbk, const u64* q_keys, const u64 n_qk, u64** d_db, u64** d_q) {
+    int rc = KSP_OK;
+    if ((rc = A.alloc(d_db, (size_t)n_dbk + 1)) || (rc = A.alloc(d_q, (size_t)n_qk + 1))) return rc;
+    KSP_HIP(hipMemcpy(*d_db, db_keys, (size_t)n_dbk * 8, hipMemcpyHostToDevice));
+    KSP_HIP(hipMemcpy(*d_q, q_keys, (size_t)n_qk * 8, hipMemcpyHostToDevice));
+    return KSP_OK;
+}
+
 // What the table of the largest tile (e_max entries) holds on the device: per entry 40 bytes (tag 4, sorted key 8 and tag 4,
 // scan 8, table key 8, holder range 4, holder 4), the directory, and the library's scratch, which the caller owns (it may be
 // larger than the table's need and serve the caller's own sorts).
@@ -201,15 +233,13 @@ inline auto query_flags_of(const u64* k, const u32* t, const u32 E) {
 
 // *tb = the scratch the sort and the scan of a table of E entries ask for
 int query_table_scratch(const u64 E, size_t* tb) {
-    int rc = KSP_OK;
     size_t tb_sort = 0, tb_scan = 0;
     if (E) {
-        KSP_TRY_HIP(rocprim::radix_sort_pairs(nullptr, tb_sort, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, (size_t)E, 0, 64, (hipStream_t) nullptr));
-        KSP_TRY_HIP(rocprim::exclusive_scan(nullptr, tb_scan, query_flags_of(nullptr, nullptr, 0), (u64*)nullptr, (u64)0, (size_t)E + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
+        KSP_HIP(rocprim::radix_sort_pairs(nullptr, tb_sort, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, (size_t)E, 0, 64, (hipStream_t) nullptr));
+        KSP_HIP(rocprim::exclusive_scan(nullptr, tb_scan, query_flags_of(nullptr, nullptr, 0), (u64*)nullptr, (u64)0, (size_t)E + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
     }
     *tb = std::max(tb_sort, tb_scan);
-done:
-    return rc;
+    return KSP_OK;
 }
 
 // the table's arrays in the arena (B.e_max > 0 is set; the scratch is the caller's)
@@ -226,39 +256,37 @@ int query_table_alloc(ksp::DeviceArena& A, QTableBufs& B) {
 // the device twice (the totals of the scan, the largest key).
 int query_table_build(const char* who, const ksp::WorkgroupCap& G, const QTableBufs& B, const u64* d_q_keys, const u64* d_q_off, const u32 q0, const u32 nq, const u64 e0,
                       const u32 E, QTable* T, u32* U_out, u32* H_out) {
-    int rc = KSP_OK;
     const unsigned ge = G.grid_of(((u64)E + 255) / 256);
     u64 totals = 0, max_key = 0;
     u32 U = 0, H = 0, n_buckets = 0;
     int bits = 0, shift = 0;
     hipLaunchKernelGGL(k_query_tag, dim3(ge), dim3(256), 0, nullptr, d_q_off, q0, nq, e0, E, B.tag);
-    KSP_TRY_HIP(hipGetLastError());
+    KSP_HIP(hipGetLastError());
     {
         size_t b = 0;   // (the scratch was sized for the largest tile: a smaller one must not ask for more)
-        if ((rc = query_table_scratch(E, &b))) return rc;
+        if (const int rc = query_table_scratch(E, &b)) return rc;
         if (b > B.tb) { ksp::set_error(std::string(who) + ": a smaller tile asks for more scratch than the largest"); return KSP_E_HIP; }
         b = B.tb;
-        KSP_TRY_HIP(rocprim::radix_sort_pairs(B.tmp, b, d_q_keys + e0, B.skey, (const u32*)B.tag, B.stag, (size_t)E, 0, 64, (hipStream_t) nullptr));
+        KSP_HIP(rocprim::radix_sort_pairs(B.tmp, b, d_q_keys + e0, B.skey, (const u32*)B.tag, B.stag, (size_t)E, 0, 64, (hipStream_t) nullptr));
         b = B.tb;
-        KSP_TRY_HIP(rocprim::exclusive_scan(B.tmp, b, query_flags_of(B.skey, B.stag, E), B.scan, (u64)0, (size_t)E + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
+        KSP_HIP(rocprim::exclusive_scan(B.tmp, b, query_flags_of(B.skey, B.stag, E), B.scan, (u64)0, (size_t)E + 1, rocprim::plus<u64>(), (hipStream_t) nullptr));
     }
-    KSP_TRY_HIP(hipMemcpy(&totals, B.scan + E, 8, hipMemcpyDeviceToHost));
+    KSP_HIP(hipMemcpy(&totals, B.scan + E, 8, hipMemcpyDeviceToHost));
     U = (u32)(totals >> 32);
     H = (u32)totals;
     if (U == 0 || U > E || H < U || H > E) { ksp::set_error(std::string(who) + ": the query table lost its keys"); return KSP_E_HIP; }
     hipLaunchKernelGGL(k_query_compact, dim3(ge), dim3(256), 0, nullptr, (const u64*)B.skey, (const u32*)B.stag, (const u64*)B.scan, E, B.tk, B.toff, B.tq);
-    KSP_TRY_HIP(hipGetLastError());
-    KSP_TRY_HIP(hipMemcpy(&max_key, B.tk + (U - 1), 8, hipMemcpyDeviceToHost));
+    KSP_HIP(hipGetLastError());
+    KSP_HIP(hipMemcpy(&max_key, B.tk + (U - 1), 8, hipMemcpyDeviceToHost));
     (void)ksp_query_directory(max_key, U, &bits, &shift);
     n_buckets = 1u << bits;
     if ((u64)n_buckets + 1 > B.dir_entries()) { ksp::set_error(std::string(who) + ": the directory outgrew its buffer"); return KSP_E_HIP; }
     hipLaunchKernelGGL(k_query_dir, dim3(G.grid_of(((u64)n_buckets + 256) / 256)), dim3(256), 0, nullptr, (const u64*)B.tk, U, shift, n_buckets, B.dir);
-    KSP_TRY_HIP(hipGetLastError());
+    KSP_HIP(hipGetLastError());
     *T = QTable{B.tk, B.toff, B.tq, B.dir, max_key, shift, q0, nq};
     *U_out = U;
     *H_out = H;
-done:
-    return rc;
+    return KSP_OK;
 }
 
 }  // namespace

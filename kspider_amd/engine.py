@@ -430,11 +430,7 @@ def pairwise_host(keys: np.ndarray, offsets: np.ndarray, weights: np.ndarray | N
     devs = (ctypes.c_int * len(devices))(*devices) if devices else (ctypes.c_int * 1)(device)
     _check(lib().ksp_pairwise_host_multi(keys.ctypes.data, w.ctypes.data if w is not None else None, offsets.ctypes.data,
                                          n, devs, len(devs), ctypes.byref(out), ctypes.byref(ne), ctypes.byref(st)))
-    try:
-        buf = (ctypes.c_char * (ne.value * EDGE_DTYPE.itemsize)).from_address(out.value) if ne.value else b""
-        edges = np.frombuffer(buf, dtype=EDGE_DTYPE).copy()
-    finally:
-        lib().ksp_free(out)
+    edges = _take(out, ne.value, EDGE_DTYPE)
     return edges, st.as_dict()
 
 
@@ -469,11 +465,7 @@ def pairwise_postings_host(key_off: np.ndarray, sources: np.ndarray, key_weights
     _check(lib().ksp_pairwise_postings_host_multi(key_off.ctypes.data, sources.ctypes.data,
                                                   kw.ctypes.data if kw is not None else None, key_off.size - 1, n_sources,
                                                   devs, len(devs), ctypes.byref(out), ctypes.byref(n), ctypes.byref(st)))
-    try:
-        buf = (ctypes.c_char * (n.value * EDGE_DTYPE.itemsize)).from_address(out.value) if n.value else b""
-        edges = np.frombuffer(buf, dtype=EDGE_DTYPE).copy()
-    finally:
-        lib().ksp_free(out)
+    edges = _take(out, n.value, EDGE_DTYPE)
     return edges, st.as_dict()
 
 
@@ -576,11 +568,7 @@ def pairwise_host_cut(keys: np.ndarray, offsets: np.ndarray, weights: np.ndarray
     _check(lib().ksp_pairwise_host_cut(keys.ctypes.data, w.ctypes.data if w is not None else None, offsets.ctypes.data, offsets.size - 1,
                                        kc.ctypes.data if kc is not None else None, int(dist_col), float(cutoff), devs, len(devs),
                                        ctypes.byref(out), ctypes.byref(ne), ctypes.byref(nf), ctypes.byref(st)))
-    try:
-        buf = (ctypes.c_char * (ne.value * EDGE_DTYPE.itemsize)).from_address(out.value) if ne.value else b""
-        edges = np.frombuffer(buf, dtype=EDGE_DTYPE).copy()
-    finally:
-        lib().ksp_free(out)
+    edges = _take(out, ne.value, EDGE_DTYPE)
     return edges, int(nf.value), st.as_dict()
 
 
@@ -1006,35 +994,47 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
+def _u64(a):
+    """A contiguous uint64 array, or None for None."""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def _n_sketches(offsets):
+    """The sketches an offsets array describes: one fewer than its entries, 0 for None or an empty one."""
+    return 0 if offsets is None else max(offsets.size - 1, 0)
+
+
+def _take(out, count, dtype):
+    """`count` items of `dtype` at the C buffer `out` (a c_void_p) as a numpy copy; the buffer is freed whether the copy succeeds or not."""
+    try:
+        buf = (ctypes.c_char * (count * np.dtype(dtype).itemsize)).from_address(out.value) if count else b""
+        return np.frombuffer(buf, dtype=dtype).copy()
+    finally:
+        lib().ksp_free(out)
+
+
 def query_host(db_keys, db_offsets, q_keys, q_offsets, mode: int = QUERY_CROSS, device: int = 0):
     """Host sketches of a database and of queries -> (edges sorted by (source_1, source_2), stats).  Database sources are numbered
     0 .. n_db - 1, queries n_db .. n_db + n_q - 1; mode QUERY_CROSS: database x query pairs, QUERY_CROSS_AND_SELF: also query x
     query.  None stands for a NULL pointer (refused by the C side)."""
-    def arr(a):
-        return None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
-    dk, do, qk, qo = arr(db_keys), arr(db_offsets), arr(q_keys), arr(q_offsets)
+    dk, do, qk, qo = _u64(db_keys), _u64(db_offsets), _u64(q_keys), _u64(q_offsets)
     out = ctypes.c_void_p()
     ne = ctypes.c_uint64(0)
     st = QueryStats()
-    _check(lib().ksp_query_host(_ptr(dk), _ptr(do), 0 if do is None else max(do.size - 1, 0), _ptr(qk), _ptr(qo), 0 if qo is None else max(qo.size - 1, 0),
+    _check(lib().ksp_query_host(_ptr(dk), _ptr(do), _n_sketches(do), _ptr(qk), _ptr(qo), _n_sketches(qo),
                                 int(mode), int(device), ctypes.byref(out), ctypes.byref(ne), ctypes.byref(st)))
-    try:
-        buf = (ctypes.c_char * (ne.value * EDGE_DTYPE.itemsize)).from_address(out.value) if ne.value else b""
-        edges = np.frombuffer(buf, dtype=EDGE_DTYPE).copy()
-    finally:
-        lib().ksp_free(out)
+    edges = _take(out, ne.value, EDGE_DTYPE)
     return edges, st.as_dict()
 
 
 def query_device(d_db_keys_ptr: int, db_offsets, d_q_keys_ptr: int, q_offsets, d_edges_ptr: int, capacity: int, mode: int = QUERY_CROSS, device: int = 0) -> tuple:
     """ksp_query_device: keys in DEVICE memory, offsets on the host, edges into d_edges (room for `capacity`; 0 / 0: the size query).
     -> (rc, n_edges, stats): rc is KSP_OK or KSP_E_OVERFLOW (n_edges is then the required size); anything else raises."""
-    do = None if db_offsets is None else np.ascontiguousarray(db_offsets, dtype=np.uint64)
-    qo = None if q_offsets is None else np.ascontiguousarray(q_offsets, dtype=np.uint64)
+    do, qo = _u64(db_offsets), _u64(q_offsets)
     ne = ctypes.c_uint64(0)
     st = QueryStats()
-    rc = lib().ksp_query_device(int(device), d_db_keys_ptr or None, _ptr(do), 0 if do is None else max(do.size - 1, 0), d_q_keys_ptr or None, _ptr(qo),
-                                0 if qo is None else max(qo.size - 1, 0), int(mode), d_edges_ptr or None, int(capacity), ctypes.byref(ne), ctypes.byref(st))
+    rc = lib().ksp_query_device(int(device), d_db_keys_ptr or None, _ptr(do), _n_sketches(do), d_q_keys_ptr or None, _ptr(qo),
+                                _n_sketches(qo), int(mode), d_edges_ptr or None, int(capacity), ctypes.byref(ne), ctypes.byref(st))
     if rc not in (KSP_OK, KSP_E_OVERFLOW):
         _check(rc)
     return rc, ne.value, st.as_dict()
@@ -1079,19 +1079,13 @@ def gather_host(db_keys, db_offsets, q_keys, q_offsets, min_hashes: int = 1, max
     stats).  A row (GATHER_ROW_DTYPE) names the database source that covers most of what is left of the query, its overlap with the
     whole query, the hashes it was the first to cover (unique) and what remains after it; a source is reported while unique is at
     least min_hashes; max_matches caps the rows per query (0: no cap).  None stands for a NULL pointer (refused by the C side)."""
-    def arr(a):
-        return None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
-    dk, do, qk, qo = arr(db_keys), arr(db_offsets), arr(q_keys), arr(q_offsets)
+    dk, do, qk, qo = _u64(db_keys), _u64(db_offsets), _u64(q_keys), _u64(q_offsets)
     out = ctypes.c_void_p()
     nr = ctypes.c_uint64(0)
     st = GatherStats()
-    _check(lib().ksp_gather_host(_ptr(dk), _ptr(do), 0 if do is None else max(do.size - 1, 0), _ptr(qk), _ptr(qo), 0 if qo is None else max(qo.size - 1, 0),
+    _check(lib().ksp_gather_host(_ptr(dk), _ptr(do), _n_sketches(do), _ptr(qk), _ptr(qo), _n_sketches(qo),
                                  int(min_hashes), int(max_matches), int(device), ctypes.byref(out), ctypes.byref(nr), ctypes.byref(st)))
-    try:
-        buf = (ctypes.c_char * (nr.value * GATHER_ROW_DTYPE.itemsize)).from_address(out.value) if nr.value else b""
-        rows = np.frombuffer(buf, dtype=GATHER_ROW_DTYPE).copy()
-    finally:
-        lib().ksp_free(out)
+    rows = _take(out, nr.value, GATHER_ROW_DTYPE)
     return rows, st.as_dict()
 
 
@@ -1099,12 +1093,11 @@ def gather_device(d_db_keys_ptr: int, db_offsets, d_q_keys_ptr: int, q_offsets, 
                   device: int = 0) -> tuple:
     """ksp_gather_device: keys in DEVICE memory, offsets on the host, rows into d_rows (room for `capacity`; 0 / 0: the size query).
     -> (rc, n_rows, stats): rc is KSP_OK or KSP_E_OVERFLOW (n_rows is then the required size); anything else raises."""
-    do = None if db_offsets is None else np.ascontiguousarray(db_offsets, dtype=np.uint64)
-    qo = None if q_offsets is None else np.ascontiguousarray(q_offsets, dtype=np.uint64)
+    do, qo = _u64(db_offsets), _u64(q_offsets)
     nr = ctypes.c_uint64(0)
     st = GatherStats()
-    rc = lib().ksp_gather_device(int(device), d_db_keys_ptr or None, _ptr(do), 0 if do is None else max(do.size - 1, 0), d_q_keys_ptr or None, _ptr(qo),
-                                 0 if qo is None else max(qo.size - 1, 0), int(min_hashes), int(max_matches), d_rows_ptr or None, int(capacity), ctypes.byref(nr),
+    rc = lib().ksp_gather_device(int(device), d_db_keys_ptr or None, _ptr(do), _n_sketches(do), d_q_keys_ptr or None, _ptr(qo),
+                                 _n_sketches(qo), int(min_hashes), int(max_matches), d_rows_ptr or None, int(capacity), ctypes.byref(nr),
                                  ctypes.byref(st))
     if rc not in (KSP_OK, KSP_E_OVERFLOW):
         _check(rc)
@@ -1122,20 +1115,14 @@ def gather_abund_host(db_keys, db_offsets, q_keys, q_abund, q_offsets, min_hashe
     """gather_host for queries that carry an abundance per hash (ksp_gather_abund_host): q_abund is parallel to q_keys -> (rows of
     GATHER_WROW_DTYPE, stats).  The first six fields are gather_host's; w_unique, w_found, the 128-bit sum of squares and twice the
     median are over the hashes a row takes, with the query's abundances."""
-    def arr(a):
-        return None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
-    dk, do, qk, qo = arr(db_keys), arr(db_offsets), arr(q_keys), arr(q_offsets)
+    dk, do, qk, qo = _u64(db_keys), _u64(db_offsets), _u64(q_keys), _u64(q_offsets)
     qa = None if q_abund is None else np.ascontiguousarray(q_abund, dtype=np.uint32)
     out = ctypes.c_void_p()
     nr = ctypes.c_uint64(0)
     st = GatherStats()
-    _check(lib().ksp_gather_abund_host(_ptr(dk), _ptr(do), 0 if do is None else max(do.size - 1, 0), _ptr(qk), _ptr(qa), _ptr(qo), 0 if qo is None else max(qo.size - 1, 0),
+    _check(lib().ksp_gather_abund_host(_ptr(dk), _ptr(do), _n_sketches(do), _ptr(qk), _ptr(qa), _ptr(qo), _n_sketches(qo),
                                        int(min_hashes), int(max_matches), int(device), ctypes.byref(out), ctypes.byref(nr), ctypes.byref(st)))
-    try:
-        buf = (ctypes.c_char * (nr.value * GATHER_WROW_DTYPE.itemsize)).from_address(out.value) if nr.value else b""
-        rows = np.frombuffer(buf, dtype=GATHER_WROW_DTYPE).copy()
-    finally:
-        lib().ksp_free(out)
+    rows = _take(out, nr.value, GATHER_WROW_DTYPE)
     return rows, st.as_dict()
 
 
@@ -1143,12 +1130,11 @@ def gather_abund_device(d_db_keys_ptr: int, db_offsets, d_q_keys_ptr: int, d_q_a
                         max_matches: int = 0, device: int = 0) -> tuple:
     """ksp_gather_abund_device: keys and abundances in DEVICE memory, offsets on the host, rows of 64 bytes into d_rows (room for
     `capacity`; 0 / 0: the size query).  -> (rc, n_rows, stats) as gather_device."""
-    do = None if db_offsets is None else np.ascontiguousarray(db_offsets, dtype=np.uint64)
-    qo = None if q_offsets is None else np.ascontiguousarray(q_offsets, dtype=np.uint64)
+    do, qo = _u64(db_offsets), _u64(q_offsets)
     nr = ctypes.c_uint64(0)
     st = GatherStats()
-    rc = lib().ksp_gather_abund_device(int(device), d_db_keys_ptr or None, _ptr(do), 0 if do is None else max(do.size - 1, 0), d_q_keys_ptr or None, d_q_abund_ptr or None,
-                                       _ptr(qo), 0 if qo is None else max(qo.size - 1, 0), int(min_hashes), int(max_matches), d_rows_ptr or None, int(capacity),
+    rc = lib().ksp_gather_abund_device(int(device), d_db_keys_ptr or None, _ptr(do), _n_sketches(do), d_q_keys_ptr or None, d_q_abund_ptr or None,
+                                       _ptr(qo), _n_sketches(qo), int(min_hashes), int(max_matches), d_rows_ptr or None, int(capacity),
                                        ctypes.byref(nr), ctypes.byref(st))
     if rc not in (KSP_OK, KSP_E_OVERFLOW):
         _check(rc)
@@ -1246,12 +1232,9 @@ def sketch_host_abund(seq, src_offsets, ksize: int, max_hash: int | None = None,
     _check(lib().ksp_sketch_host_abund(int(device), _ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), ctypes.byref(out), ctypes.byref(out_a),
                                        out_off.ctypes.data, ctypes.byref(st)))
     try:
-        n = int(out_off[-1])
-        keys = np.frombuffer((ctypes.c_char * (8 * n)).from_address(out.value), dtype=np.uint64).copy() if n else np.zeros(0, dtype=np.uint64)
-        abund = np.frombuffer((ctypes.c_char * (4 * n)).from_address(out_a.value), dtype=np.uint32).copy() if n else np.zeros(0, dtype=np.uint32)
-    finally:
-        lib().ksp_free(out)
-        lib().ksp_free(out_a)
+        keys = _take(out, int(out_off[-1]), np.uint64)
+    finally:   # (the second buffer is freed also when the first copy failed)
+        abund = _take(out_a, int(out_off[-1]), np.uint32)
     return keys, abund, out_off, st.as_dict()
 
 
@@ -1278,12 +1261,7 @@ def sketch_host(seq, src_offsets, ksize: int, max_hash: int | None = None, scale
     st = SketchStats()
     _check(lib().ksp_sketch_host(int(device), _ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), ctypes.byref(out), out_off.ctypes.data,
                                  ctypes.byref(st)))
-    try:
-        n = int(out_off[-1])
-        keys = np.frombuffer((ctypes.c_char * (8 * n)).from_address(out.value), dtype=np.uint64).copy() if n else np.zeros(0, dtype=np.uint64)
-    finally:
-        lib().ksp_free(out)
-    return keys, out_off, st.as_dict()
+    return _take(out, int(out_off[-1]), np.uint64), out_off, st.as_dict()
 
 
 def sketch_device(d_seq_ptr: int, n_bytes: int, src_offsets, ksize: int, max_hash: int, d_out_keys_ptr: int, capacity: int, seed: int = 42,
