@@ -1093,6 +1093,61 @@ int ksp_sketch_host_abund(int device, const uint8_t* seq, uint64_t n_bytes, cons
                           ksp_sketch_stats* stats);
 int ksp_sig_read(const char* path, int kSize, uint64_t* mins, uint32_t* abunds, uint64_t capacity, uint64_t* n, int* has_abund);
 
+/* ---- protein, dayhoff and hp sketches; six-frame translation (csrc/sketch_mol.h, csrc/sketch_mol_kernels.hip.h) ----
+ * Molecule types: KSP_MOL_DNA 0 is the section above, untouched; KSP_MOL_PROTEIN 1, KSP_MOL_DAYHOFF 2, KSP_MOL_HP 3.
+ * Residues.  A residue byte is an ASCII letter (either case, taken as upper case) or '*'; every other byte value breaks k-mers,
+ *   the newline the reader puts behind each record included.  The letter that is hashed for a residue r:
+ *     protein  r itself, upper case
+ *     dayhoff  C -> a;  A G P S T -> b;  D E N Q -> c;  H K R -> d;  I L M V -> e;  F W Y -> f;  * -> *;  every other letter -> X
+ *     hp       A F G I L M P V W Y -> h;  N C S T D E R H K Q -> p;  * -> *;  every other letter -> X
+ * Protein input.  A k-mer is ksize (1 .. 64) consecutive residue bytes inside one source; its hash is the first word of
+ *   MurmurHash3_x64_128 over its ksize encoded letters with `seed` (42); there is no canonical form; kept iff hash <= max_hash.
+ * Translated input (KSP_SKETCH_TRANSLATE in flags).  The bytes are DNA with the rules above (ACGTacgt are bases, everything else
+ *   breaks).  A window is 3 ksize consecutive bases inside one source, at EVERY position (all three frames); it yields two k-mers:
+ *   the translation of its codons at offsets 0, 3, .. 3 ksize - 3, and the translation of the codons of its reverse complement.
+ *   The standard genetic code, indexed by 16 b1 + 4 b2 + b3 with T, C, A, G = 0 .. 3:
+ *     FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG
+ *   Each translated k-mer is encoded and hashed as above, those with '*' like any other.  ksize is 1 .. 21 here (3 ksize <= 63
+ *   bases fit the packed k-mer and the 64-byte halo); more is KSP_E_ARG naming the limit.  hp at sourmash's customary ksize 42
+ *   therefore works on protein input only.
+ * Sketch and counts.  A source's sketch is the ascending list of its distinct kept hashes.  The abundance of a hash is the number
+ *   of (window, strand) pairs of the source that hash to it — for protein input the number of windows —, clamped at 2^32 - 1; a
+ *   window whose two strands translate to the same k-mer counts twice.
+ * ksp_sketch_text_hash: host only — the hash of the one k-mer that the `len` (1 .. 64) bytes of text spell for moltype 1 .. 3;
+ *   *valid = 0 (and *hash = 0) when a byte is no residue.
+ * ksp_sketch_cpu_mol / ksp_sketch_device_mol / ksp_sketch_host_mol: ksp_sketch_cpu / _device / _host with `moltype` and `flags`
+ *   (KSP_SKETCH_TRANSLATE or 0) behind ksize, and the abundance output of the _abund calls, which may be NULL: one entry serves
+ *   counted and plain.  moltype 0 without translate gives the DNA calls' results.  KSP_E_ARG: an unknown moltype, moltype 0 with
+ *   translate, any other flag, ksize outside the limits above; otherwise the rules of the DNA calls.  stats->valid_kmers counts
+ *   windows, stats->kept survivors (up to two per window when translating); ksp_sketch_host_mol's first capacity doubles when
+ *   translating.  ksp_sketch_cpu_mol is the plain single-thread loop: the timing baseline and KSPIDER_SKETCH=host.
+ * kspider_sketch with KSP_SKETCH_PROTEIN, _DAYHOFF or _HP in flags (more than one: KSP_E_ARG), and KSP_SKETCH_TRANSLATE beside one
+ *   of them (alone: KSP_E_ARG): kSize is the RESIDUE k.  Without translate the input is protein, and a directory is searched for
+ *   .faa .fa .fasta (each optionally .gz); with it the input is DNA in the files of the section above.  A record longer than a
+ *   batch is cut with (window - 1) bytes of overlap, 3 kSize - 1 when translating; unions and added counts stay exact.  Every
+ *   refusal happens before a device is chosen or a file is written.
+ * The signature files: "molecule" is "protein", "dayhoff" or "hp"; "ksize" is 3 * kSize, and md5sum is taken over that decimal
+ *   text followed by the mins — sourmash's stored form as far as it is known here (DESIGN.md 7r says what could not be checked).
+ *   Downstream calls that take a kSize (kspider_pack, kspider_query, kspider_gather, kspider_pairwise_sigs, ksp_sig_read) therefore
+ *   take 3 * kSize for these files.  The loaders select by "ksize" alone: do not mix DNA and protein signatures in a directory. */
+#define KSP_MOL_DNA 0
+#define KSP_MOL_PROTEIN 1
+#define KSP_MOL_DAYHOFF 2
+#define KSP_MOL_HP 3
+#define KSP_SKETCH_PROTEIN 8ull
+#define KSP_SKETCH_DAYHOFF 16ull
+#define KSP_SKETCH_HP 32ull
+#define KSP_SKETCH_TRANSLATE 64ull
+int ksp_sketch_text_hash(const char* text, int len, int moltype, uint32_t seed, uint64_t* hash, int* valid);
+int ksp_sketch_cpu_mol(const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize, int moltype, uint64_t flags,
+                       uint64_t max_hash, uint32_t seed, uint64_t* out_keys, uint32_t* out_abund, uint64_t capacity, uint64_t* out_offsets, uint64_t* needed);
+int ksp_sketch_device_mol(int device, const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* h_src_offsets, uint32_t n_sources, int ksize, int moltype,
+                          uint64_t flags, uint64_t max_hash, uint32_t seed, uint64_t* d_out_keys, uint32_t* d_out_abund, uint64_t capacity,
+                          uint64_t* h_out_offsets, ksp_sketch_stats* stats);
+int ksp_sketch_host_mol(int device, const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize, int moltype,
+                        uint64_t flags, uint64_t max_hash, uint32_t seed, uint64_t** out_keys, uint32_t** out_abund, uint64_t* out_offsets,
+                        ksp_sketch_stats* stats);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

@@ -15,6 +15,7 @@ Host-side mirror of the reference interface for this one path:
   kspider_amd.gather_abund(db, queries, kSize, out_prefix, threads, min_hashes, max_matches)  the same for signatures with abundances: weighted columns
   kspider_amd.pack(sketch_dir, kSize, out_path, threads)  a directory of sketches as one database file
   kspider_amd.sketch_files(input, kSize, scaled, out_dir, threads)  FASTA / FASTQ in, sourmash-compatible .sig files out, hashed on the GPU
+      (moltype="protein" | "dayhoff" | "hp", translate=True: protein sketches of proteomes, or of genomes read in six frames)
   kspider_amd.engine                                   ctypes binding of include/kspider_amd.h
   kspider_amd.dist                                     tile sharding + edge gather for one-process-per-GPU runs
   kspider_amd.synth                                    synthetic sketch sets shaped like BASELINE.json's configs
@@ -32,12 +33,14 @@ from .engine import GATHER_ROW_DTYPE, GatherStats, gather, gather_device, gather
 from .engine import GATHER_WROW_DTYPE, GatherWRow, gather_abund, gather_abund_device, gather_abund_host, sig_read  # noqa: F401
 from .engine import SketchStats, sketch_cpu, sketch_device, sketch_files, sketch_host, sketch_max_hash  # noqa: F401
 from .engine import sketch_cpu_abund, sketch_device_abund, sketch_host_abund  # noqa: F401
+from .engine import sketch_cpu_mol, sketch_device_mol, sketch_host_mol, sketch_text_hash  # noqa: F401
 
 __all__ = ["pairwise", "pairwise_sigs", "pairwise_bins", "cluster", "estimate_ani", "pairwise_ani", "export",
            "query", "pack", "QUERY_CROSS", "QUERY_CROSS_AND_SELF",
            "gather", "gather_host", "gather_device", "GatherStats", "GATHER_ROW_DTYPE",
            "gather_abund", "gather_abund_host", "gather_abund_device", "GatherWRow", "GATHER_WROW_DTYPE", "sig_read",
            "sketch_cpu_abund", "sketch_host_abund", "sketch_device_abund",
+           "sketch_cpu_mol", "sketch_host_mol", "sketch_device_mol", "sketch_text_hash",
            "sketch_files", "sketch_host", "sketch_device", "sketch_cpu", "sketch_max_hash", "SketchStats",
            "single_linkage_rows", "pairwise_cut", "pairwise_host_cut", "edges_cut", "CUT_CHUNK_EDGES",
            "cluster_sweep", "pairwise_and_cluster_sweep",

@@ -211,6 +211,9 @@ int pairwise_postings_multi_cc(const uint64_t* key_off, const uint32_t* sources,
 // what ksp_sketch_cpu / _device / _host refuse with KSP_E_ARG: a NULL pointer, ksize outside 1 .. 64, no source, offsets that do
 // not start at 0, decrease or do not end at n_bytes
 int check_sketch_args(const char* who, const void* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize);
+// what the _mol calls refuse with KSP_E_ARG before that: an unknown moltype, a flag other than KSP_SKETCH_TRANSLATE,
+// translate with KSP_MOL_DNA, ksize outside 1 .. 21 with translate (the message names the limit) and outside 1 .. 64 without
+int check_sketch_mol(const char* who, int ksize, int moltype, uint64_t flags);
 // page-locked host memory for the batches of the file driver (sketcher.hip; NULL when it cannot be had)
 void* pinned_alloc(size_t bytes);
 void pinned_free(void* p);

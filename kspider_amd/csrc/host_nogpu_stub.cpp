@@ -126,6 +126,10 @@ int ksp_sketch_host_abund(int, const uint8_t*, uint64_t, const uint64_t*, uint32
     ksp::set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }
+int ksp_sketch_host_mol(int, const uint8_t*, uint64_t, const uint64_t*, uint32_t, int, int, uint64_t, uint64_t, uint32_t, uint64_t**, uint32_t**, uint64_t*, ksp_sketch_stats*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
 int ksp_gather_abund_host(const uint64_t*, const uint64_t*, uint32_t, const uint64_t*, const uint32_t*, const uint64_t*, uint32_t, uint32_t, uint32_t, int, ksp_gather_wrow**,
                           uint64_t*, ksp_gather_stats*) {
     ksp::set_error("host-only sanitizer build: no HIP engine");

@@ -9,6 +9,10 @@
 //                                                the same with KSP_SKETCH_ABUND; then every file of OUT back through ksp_sig_read
 //                                                into buffers of exactly the reported sizes: "sig <rc> <mins> <sum of the
 //                                                abundances> <file>" per file, in the order of the names, then the rc line
+//   sketch_asan_check mol FLAGS INPUT K SCALED OUT
+//                                                kspider_sketch in host mode with FLAGS, the decimal value of any of its flags
+//                                                (KSP_SKETCH_PROTEIN 8, _DAYHOFF 16, _HP 32, _TRANSLATE 64, _ABUND 4, _PER_RECORD 1);
+//                                                then the files of OUT back through ksp_sig_read at 3 K, and the rc line
 //   sketch_asan_check sigs K FILE...             every file through ksp_sig_read alone, the same lines
 #include <dirent.h>
 
@@ -34,6 +38,18 @@ static void read_sig(const std::string& path, const int k) {
             for (uint64_t i = 0; i < n; ++i) sum += abunds[(size_t)i];
     }
     std::printf("sig %d %llu %llu %s\n", rc, (unsigned long long)n, (unsigned long long)sum, path.c_str());
+}
+
+// the files of a directory through read_sig, in the order of their names
+static void read_sigs_of(const char* dir, const int k) {
+    std::vector<std::string> names;
+    if (DIR* d = opendir(dir)) {
+        while (const dirent* e = readdir(d))
+            if (e->d_name[0] != '.') names.push_back(e->d_name);
+        closedir(d);
+    }
+    std::sort(names.begin(), names.end());
+    for (const std::string& n : names) read_sig(std::string(dir) + "/" + n, k);
 }
 
 int main(int argc, char** argv) {
@@ -64,14 +80,14 @@ int main(int argc, char** argv) {
     if (cmd == "abund" && (argc == 6 || (argc == 7 && std::strcmp(argv[6], "--per-record") == 0))) {
         setenv("KSPIDER_SKETCH", "host", 1);
         const int rc = kspider_sketch(argv[2], std::atoi(argv[3]), std::strtoull(argv[4], nullptr, 10), argv[5], 2, KSP_SKETCH_ABUND | (argc == 7 ? KSP_SKETCH_PER_RECORD : 0));
-        std::vector<std::string> names;
-        if (DIR* d = opendir(argv[5])) {
-            while (const dirent* e = readdir(d))
-                if (e->d_name[0] != '.') names.push_back(e->d_name);
-            closedir(d);
-        }
-        std::sort(names.begin(), names.end());
-        for (const std::string& n : names) read_sig(std::string(argv[5]) + "/" + n, std::atoi(argv[3]));
+        read_sigs_of(argv[5], std::atoi(argv[3]));
+        std::printf("rc %d %s\n", rc, rc ? ksp_last_error() : "");
+        return 0;
+    }
+    if (cmd == "mol" && argc == 7) {
+        setenv("KSPIDER_SKETCH", "host", 1);
+        const int rc = kspider_sketch(argv[3], std::atoi(argv[4]), std::strtoull(argv[5], nullptr, 10), argv[6], 2, std::strtoull(argv[2], nullptr, 10));
+        read_sigs_of(argv[6], 3 * std::atoi(argv[4]));
         std::printf("rc %d %s\n", rc, rc ? ksp_last_error() : "");
         return 0;
     }
@@ -79,6 +95,6 @@ int main(int argc, char** argv) {
         for (int i = 3; i < argc; ++i) read_sig(argv[i], std::atoi(argv[2]));
         return 0;
     }
-    std::fprintf(stderr, "usage: %s read FILE... | sketch INPUT K SCALED OUT [--per-record] | abund INPUT K SCALED OUT [--per-record] | sigs K FILE...\n", argv[0]);
+    std::fprintf(stderr, "usage: %s read FILE... | sketch INPUT K SCALED OUT [--per-record] | abund INPUT K SCALED OUT [--per-record] | mol FLAGS INPUT K SCALED OUT | sigs K FILE...\n", argv[0]);
     return 2;
 }

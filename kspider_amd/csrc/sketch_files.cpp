@@ -1,9 +1,10 @@
 // The file driver of the sketcher: FASTA / FASTQ files in, one sourmash-compatible .sig file per source out.
-// Host only; the device part is ksp_sketch_host (sketcher.hip), the host mode's ksp_sketch_cpu (sketch_cpu.cpp).
+// Host only; the device part is ksp_sketch_host (sketcher.hip), the host mode's ksp_sketch_cpu (sketch_cpu.cpp); with a molecule
+// flag their _mol forms over protein files or DNA to translate, and a window of ksize residues or 3 ksize bases.
 //   feed     the input files in order, read `threads` at a time (fastx_reader.cpp); what is read and not yet sent waits as pieces
 //   batch    at most `batch_bytes` bytes of pieces back to back, each a segment of one source.  A piece that does not fit is cut:
-//            the batch takes what it has room for, and the rest starts ksize - 1 bytes before the cut, so every window of ksize
-//            bytes lies whole in one of the two.  A source's sketch is the union of its segments' sketches; with KSP_SKETCH_ABUND
+//            the batch takes what it has room for, and the rest starts window - 1 bytes before the cut, so every window (ksize
+//            bytes; 3 ksize of translated input) lies whole in one of the two.  A source's sketch is the union of its segments' sketches; with KSP_SKETCH_ABUND
 //            the counts of a hash in its segments are added (every window lies in exactly one segment) and clamped after adding.
 //   pipeline two batch buffers (page-locked in device mode): the next one is filled by a thread while this one is hashed
 //   write    the signatures at the end, each through .partial and a rename
@@ -115,14 +116,27 @@ bool is_directory(const std::string& path) {
 std::string base_name(const std::string& path) { return path.substr(path.find_last_of("/\\") + 1); }
 bool ends_with(const std::string& s, const std::string& e) { return s.size() >= e.size() && s.compare(s.size() - e.size(), e.size(), e) == 0; }
 
-// the file name without .gz and without its FASTA / FASTQ ending; "" when it has none of the endings
-std::string source_name_of(const std::string& path) {
+// the endings of the input files: nucleotide (DNA, and translated input), and protein
+const std::vector<std::string> kDnaEndings{".fa", ".fasta", ".fna", ".fq", ".fastq"}, kProteinEndings{".faa", ".fa", ".fasta"};
+
+// the file name without .gz and without its ending; "" when it has none of the endings
+std::string source_name_of(const std::string& path, const std::vector<std::string>& endings) {
     std::string n = base_name(path);
     if (ends_with(n, ".gz")) n.resize(n.size() - 3);
-    for (const char* e : {".fa", ".fasta", ".fna", ".fq", ".fastq"})
-        if (ends_with(n, e) && n.size() > std::strlen(e)) return n.substr(0, n.size() - std::strlen(e));
+    for (const std::string& e : endings)
+        if (ends_with(n, e) && n.size() > e.size()) return n.substr(0, n.size() - e.size());
     return "";
 }
+
+// what kspider_sketch hashes: the molecule type, whether the bytes are DNA to translate, the bytes of a window, and what the
+// signature says (sourmash stores ksize * 3 for the protein types)
+struct Molecule {
+    int type = KSP_MOL_DNA;
+    bool translate = false;
+    int window = 0, stored_ksize = 0;
+    const char* name = "DNA";
+    const std::vector<std::string>* endings = &kDnaEndings;
+};
 
 std::string json_text(const std::string& s) {
     std::string out = "\"";
@@ -136,7 +150,7 @@ std::string json_text(const std::string& s) {
 }
 
 // the signature file of one source: the fields of the files sourmash writes, in a fixed order; abund: "abundances" behind "mins"
-std::string sig_text(const std::string& filename, const int ksize, const uint32_t seed, const uint64_t max_hash, const std::vector<uint64_t>& mins,
+std::string sig_text(const std::string& filename, const int ksize, const char* molecule, const uint32_t seed, const uint64_t max_hash, const std::vector<uint64_t>& mins,
                      const std::vector<uint32_t>* abund) {
     std::string list;
     Md5 md5;
@@ -158,7 +172,7 @@ std::string sig_text(const std::string& filename, const int ksize, const uint32_
     }
     return "[{\"class\":\"sourmash_signature\",\"email\":\"\",\"hash_function\":\"0.murmur64\",\"filename\":" + json_text(filename) +
            ",\"license\":\"CC0\",\"version\":0.4,\"signatures\":[{\"num\":0,\"ksize\":" + std::to_string(ksize) + ",\"seed\":" + std::to_string(seed) +
-           ",\"max_hash\":" + std::to_string(max_hash) + ",\"molecule\":\"DNA\",\"md5sum\":\"" + md5.hex() + "\",\"mins\":[" + list + "]}]}]\n";
+           ",\"max_hash\":" + std::to_string(max_hash) + ",\"molecule\":\"" + molecule + "\",\"md5sum\":\"" + md5.hex() + "\",\"mins\":[" + list + "]}]}]\n";
 }
 
 // fn(i) for i in [0, n) on up to `threads` host threads; the first exception is rethrown on the caller
@@ -206,6 +220,7 @@ class Feed {
     bool per_record_;
     int threads_;
     size_t batch_bytes_, overlap_;
+    const std::vector<std::string>& endings_;
     std::deque<Piece> pieces_;
 
     void read_more() {
@@ -226,7 +241,7 @@ class Feed {
                     pieces_.push_back(Piece{(uint32_t)(names.size() - 1), text, (size_t)f.rec_off[r], (size_t)f.rec_off[r + 1]});
                 }
             } else {
-                const std::string by_ending = source_name_of(path);
+                const std::string by_ending = source_name_of(path, endings_);
                 names.push_back(by_ending.empty() ? base_name(path) : by_ending);
                 filenames.push_back(base_name(path));
                 pieces_.push_back(Piece{(uint32_t)(names.size() - 1), text, 0, text->size()});
@@ -239,8 +254,9 @@ class Feed {
 public:
     std::vector<std::string> names, filenames;   // of every source met so far (read by the caller only after the last fill())
 
-    Feed(std::vector<std::string> files, const bool per_record, const int threads, const size_t batch_bytes, const int ksize)
-        : files_(std::move(files)), per_record_(per_record), threads_(threads), batch_bytes_(batch_bytes), overlap_((size_t)ksize - 1) {}
+    // window: the bytes of one window (ksize; 3 * ksize of translated input)
+    Feed(std::vector<std::string> files, const bool per_record, const int threads, const size_t batch_bytes, const int window, const std::vector<std::string>& endings)
+        : files_(std::move(files)), per_record_(per_record), threads_(threads), batch_bytes_(batch_bytes), overlap_((size_t)window - 1), endings_(endings) {}
 
     // the next batch; false when the input is used up and the batch is empty
     bool fill(Batch& b) {
@@ -261,14 +277,14 @@ public:
             b.off.push_back(b.n_bytes);
             b.source.push_back(p.source);
             if (take == left) { pieces_.pop_front(); continue; }
-            p.at += take - overlap_;   // the rest starts ksize - 1 bytes before the cut
+            p.at += take - overlap_;   // the rest starts window - 1 bytes before the cut
             break;
         }
         return b.n_bytes > 0 || !pieces_.empty() || next_file_ < files_.size();
     }
 };
 
-std::vector<std::string> input_files(const std::string& input) {
+std::vector<std::string> input_files(const std::string& input, const std::vector<std::string>& endings) {
     if (!is_directory(input)) return {input};
     std::string dir = input;
     while (dir.size() > 1 && dir.back() == '/') dir.pop_back();
@@ -279,10 +295,14 @@ std::vector<std::string> input_files(const std::string& input) {
     std::vector<std::string> out;
     if (rv == 0)
         for (size_t i = 0; i < g.gl_pathc; ++i)
-            if (!source_name_of(g.gl_pathv[i]).empty() && !is_directory(g.gl_pathv[i])) out.emplace_back(g.gl_pathv[i]);
+            if (!source_name_of(g.gl_pathv[i], endings).empty() && !is_directory(g.gl_pathv[i])) out.emplace_back(g.gl_pathv[i]);
     globfree(&g);
     if (rv != 0 && rv != GLOB_NOMATCH) throw std::runtime_error("glob() failed on " + pat);
-    if (out.empty()) throw std::runtime_error("no .fa / .fasta / .fna / .fq / .fastq file (plain or .gz) in " + dir);
+    if (out.empty()) {
+        std::string list;
+        for (const std::string& e : endings) list += (list.empty() ? "" : " / ") + e;
+        throw std::runtime_error("no " + list + " file (plain or .gz) in " + dir);
+    }
     return out;
 }
 
@@ -297,7 +317,7 @@ uint64_t env_bytes(const char* name, const uint64_t fallback, const uint64_t lo)
 }
 
 // the sketches of one batch, appended to the keys of their sources (counts: and their counts to `counts`)
-void run_batch(const Batch& b, const bool on_host, const int device, const int ksize, const uint64_t max_hash, const uint32_t seed,
+void run_batch(const Batch& b, const bool on_host, const int device, const int ksize, const Molecule& mol, const uint64_t max_hash, const uint32_t seed,
                std::vector<std::vector<uint64_t>>& keys, std::vector<std::vector<uint32_t>>* counts, std::vector<uint32_t>& segments, ksp_sketch_stats& total) {
     const uint32_t n_seg = (uint32_t)b.source.size();
     if (n_seg == 0) return;
@@ -305,11 +325,17 @@ void run_batch(const Batch& b, const bool on_host, const int device, const int k
     std::vector<uint32_t> host_abund;
     uint64_t* got = nullptr;
     uint32_t* got_abund = nullptr;
+    const uint64_t mol_flags = mol.translate ? KSP_SKETCH_TRANSLATE : 0;
     if (on_host) {
         uint64_t needed = 0;
         const double share = ((double)max_hash + 1.0) / 18446744073709551616.0;
         host_keys.resize((size_t)std::min<uint64_t>(b.n_bytes, (uint64_t)((double)b.n_bytes * share * 1.25) + 4096));
         const auto call = [&]() {
+            if (mol.type != KSP_MOL_DNA) {
+                if (counts) host_abund.resize(host_keys.size() + 1);   // (+ 1: not NULL with room for nothing, which would ask for the plain sketch)
+                return ksp_sketch_cpu_mol(b.buf, b.n_bytes, b.off.data(), n_seg, ksize, mol.type, mol_flags, max_hash, seed, host_keys.data(), counts ? host_abund.data() : nullptr,
+                                          host_keys.size(), out_off.data(), &needed);
+            }
             if (!counts) return ksp_sketch_cpu(b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, host_keys.data(), host_keys.size(), out_off.data(), &needed);
             host_abund.resize(host_keys.size());
             return ksp_sketch_cpu_abund(b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, host_keys.data(), host_abund.data(), host_keys.size(), out_off.data(), &needed);
@@ -324,7 +350,9 @@ void run_batch(const Batch& b, const bool on_host, const int device, const int k
         got_abund = host_abund.data();
     } else {
         ksp_sketch_stats st;
-        const int rc = counts ? ksp_sketch_host_abund(device, b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, &got, &got_abund, out_off.data(), &st)
+        const int rc = mol.type != KSP_MOL_DNA
+                           ? ksp_sketch_host_mol(device, b.buf, b.n_bytes, b.off.data(), n_seg, ksize, mol.type, mol_flags, max_hash, seed, &got, counts ? &got_abund : nullptr, out_off.data(), &st)
+                       : counts ? ksp_sketch_host_abund(device, b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, &got, &got_abund, out_off.data(), &st)
                               : ksp_sketch_host(device, b.buf, b.n_bytes, b.off.data(), n_seg, ksize, max_hash, seed, &got, out_off.data(), &st);
         if (rc != KSP_OK) throw CallError{rc};
         total.bases += st.bases; total.valid_kmers += st.valid_kmers; total.kept += st.kept; total.distinct_out += st.distinct_out;
@@ -349,6 +377,21 @@ extern "C" int kspider_sketch(const char* input, int kSize, uint64_t scaled, con
     const char* who = "kspider_sketch";
     if (!input || !*input || !out_dir || !*out_dir) { ksp::set_error(std::string(who) + ": input and out_dir are required"); return KSP_E_ARG; }
     if (kSize < 1 || kSize > 64) { ksp::set_error(std::string(who) + ": kSize is 1 .. 64"); return KSP_E_ARG; }
+    Molecule mol;
+    {
+        const uint64_t types = flags & (KSP_SKETCH_PROTEIN | KSP_SKETCH_DAYHOFF | KSP_SKETCH_HP);
+        if (types & (types - 1)) { ksp::set_error(std::string(who) + ": KSP_SKETCH_PROTEIN, _DAYHOFF and _HP exclude each other"); return KSP_E_ARG; }
+        mol.translate = (flags & KSP_SKETCH_TRANSLATE) != 0;
+        if (mol.translate && !types) { ksp::set_error(std::string(who) + ": KSP_SKETCH_TRANSLATE needs KSP_SKETCH_PROTEIN, _DAYHOFF or _HP"); return KSP_E_ARG; }
+        if (mol.translate && kSize > 21) { ksp::set_error(std::string(who) + ": kSize is 1 .. 21 with KSP_SKETCH_TRANSLATE (3 * kSize <= 63 bases)"); return KSP_E_ARG; }
+        if (types) {
+            mol.type = types == KSP_SKETCH_PROTEIN ? KSP_MOL_PROTEIN : types == KSP_SKETCH_DAYHOFF ? KSP_MOL_DAYHOFF : KSP_MOL_HP;
+            mol.name = types == KSP_SKETCH_PROTEIN ? "protein" : types == KSP_SKETCH_DAYHOFF ? "dayhoff" : "hp";
+            if (!mol.translate) mol.endings = &kProteinEndings;
+        }
+        mol.window = mol.translate ? 3 * kSize : kSize;
+        mol.stored_ksize = types ? 3 * kSize : kSize;
+    }
     uint64_t max_hash = 0;
     if (const int rc = ksp_sketch_max_hash(scaled, &max_hash)) return rc;
     uint8_t* bufs[2] = {nullptr, nullptr};
@@ -365,7 +408,7 @@ extern "C" int kspider_sketch(const char* input, int kSize, uint64_t scaled, con
         const size_t batch_bytes = (size_t)env_bytes("KSPIDER_SKETCH_BATCH_BYTES", env_bytes("KSPIDER_SKETCH_BATCH_MB", 256, 1) << 20, 1024);
         const char* dv = std::getenv("KSPIDER_DEVICE");
         const int device = dv ? std::atoi(dv) : 0;
-        Feed feed(input_files(input), per_record, threads, batch_bytes, kSize);
+        Feed feed(input_files(input, *mol.endings), per_record, threads, batch_bytes, mol.window, *mol.endings);
         for (uint8_t*& p : bufs) {
             p = (uint8_t*)(on_host ? std::malloc(batch_bytes) : ksp::pinned_alloc(batch_bytes));
             if (!p) throw std::bad_alloc();
@@ -394,7 +437,7 @@ extern "C" int kspider_sketch(const char* input, int kSize, uint64_t scaled, con
             });
             std::exception_ptr run_err;
             try {
-                run_batch(batch[cur], on_host, device, kSize, max_hash, seed, keys, counted ? &counts : nullptr, segments, total);
+                run_batch(batch[cur], on_host, device, kSize, mol, max_hash, seed, keys, counted ? &counts : nullptr, segments, total);
                 ++n_batches;
             } catch (...) {
                 run_err = std::current_exception();
@@ -437,7 +480,7 @@ extern "C" int kspider_sketch(const char* input, int kSize, uint64_t scaled, con
                 std::sort(k.begin(), k.end());
                 k.erase(std::unique(k.begin(), k.end()), k.end());
             }
-            ksp::write_file_atomically(std::string(out_dir) + "/" + feed.names[s] + ".sig", sig_text(feed.filenames[s], kSize, seed, max_hash, k, counted ? &c : nullptr));
+            ksp::write_file_atomically(std::string(out_dir) + "/" + feed.names[s] + ".sig", sig_text(feed.filenames[s], mol.stored_ksize, mol.name, seed, max_hash, k, counted ? &c : nullptr));
         });
         if (std::getenv("KSPIDER_VERBOSE"))
             std::cout << "kspider_amd: sketch: " << n_src << " sources in " << n_batches << " batches" << (on_host ? " on the host" : "") << "; " << total.bases

@@ -1,6 +1,8 @@
-// `sketch INPUT K SCALED OUT_DIR THREADS [--per-record] [--seed S] [--abund]` — sourmash-compatible DNA FracMinHash sketches of FASTA /
-// FASTQ files (kspider_sketch): INPUT is a directory, each of its .fa .fasta .fna .fq .fastq files (plain or .gz) one source, or
-// one file; --per-record makes every record of that file a source; --abund writes every hash's abundance ("abundances").  Writes
+// `sketch INPUT K SCALED OUT_DIR THREADS [--per-record] [--seed S] [--abund] [--protein | --dayhoff | --hp] [--translate]` —
+// sourmash-compatible FracMinHash sketches of FASTA / FASTQ files (kspider_sketch): INPUT is a directory, each of its .fa .fasta
+// .fna .fq .fastq files (plain or .gz) one source, or one file; --per-record makes every record of that file a source; --abund
+// writes every hash's abundance ("abundances").  --protein, --dayhoff, --hp: K is the residue k and INPUT is protein (a directory's
+// .faa .fa .fasta files), or with --translate DNA read in six frames (K <= 21); the signatures say "ksize": 3 K.  Writes
 // OUT_DIR/<name>.sig.  KSPIDER_SKETCH=host: no GPU.
 #include <cstdio>
 #include <cstdlib>
@@ -23,11 +25,15 @@ int main(int argc, char** argv) {
     for (int i = 6; ok && i < argc; ++i) {
         if (std::strcmp(argv[i], "--per-record") == 0) flags |= KSP_SKETCH_PER_RECORD;
         else if (std::strcmp(argv[i], "--abund") == 0) flags |= KSP_SKETCH_ABUND;
+        else if (std::strcmp(argv[i], "--protein") == 0) flags |= KSP_SKETCH_PROTEIN;
+        else if (std::strcmp(argv[i], "--dayhoff") == 0) flags |= KSP_SKETCH_DAYHOFF;
+        else if (std::strcmp(argv[i], "--hp") == 0) flags |= KSP_SKETCH_HP;
+        else if (std::strcmp(argv[i], "--translate") == 0) flags |= KSP_SKETCH_TRANSLATE;
         else if (std::strcmp(argv[i], "--seed") == 0 && i + 1 < argc && number(argv[i + 1], 0xFFFFFFFFull, &seed)) { flags |= KSP_SKETCH_SEED; ++i; }
         else ok = false;
     }
     if (!ok) {
-        std::fprintf(stderr, "usage: %s INPUT K SCALED OUT_DIR THREADS [--per-record] [--seed S] [--abund]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s INPUT K SCALED OUT_DIR THREADS [--per-record] [--seed S] [--abund] [--protein | --dayhoff | --hp] [--translate]\n", argv[0]);
         return 2;
     }
     if (!number(argv[2], 64, &k) || !number(argv[3], ~0ull, &scaled) || !number(argv[5], 1000000, &threads)) {

@@ -12,6 +12,8 @@
 //   select   rocPRIM's merge sort by (source, hash), one scan of head flags (an entry that differs from the one before),
 //            k_sketch_compact writes the heads' hashes, k_sketch_offsets the per-source bounds by binary search.  The counted
 //            calls launch k_sketch_compact_abund instead: a head also writes the length of its run, its abundance.
+// The protein, dayhoff and hp molecule types have hash passes of their own, k_sketch_hash_protein and
+// k_sketch_hash_translated in sketch_mol_kernels.hip.h, and share everything from the survivor records on.
 // Every loop is bounded by a size the host computed; no workgroup waits on another; the result does not depend on scheduling.
 #include <cstdint>
 #include <cstdlib>
@@ -29,6 +31,7 @@
 #include "device_call.h"
 #include "engine_internal.h"
 #include "sketch_hash.h"
+#include "sketch_mol.h"
 
 namespace {
 
@@ -148,6 +151,8 @@ __global__ __launch_bounds__(kThreads) void k_sketch_hash(const HashArgs A) {
     }
 }
 
+#include "sketch_mol_kernels.hip.h"
+
 struct RecBefore {
     __host__ __device__ bool operator()(const Rec& a, const Rec& b) const { return a.src != b.src ? a.src < b.src : a.hash < b.hash; }
 };
@@ -216,8 +221,10 @@ done:
 }
 
 // The sketches on the CURRENT device; the arguments have passed ksp::check_sketch_args.  d_out_abund: the counts beside the keys, or NULL.
+// mol 0: DNA; else the molecule type, the bytes being residues or, with `translate`, DNA read in six frames.
 int sketch_on_device(const char* who, const uint8_t* d_seq, const u64 n_bytes, const u64* h_src_off, const u32 n_sources, const int ksize, const u64 max_hash,
-                     const u32 seed, u64* d_out_keys, u32* d_out_abund, const u64 capacity, u64* h_out_off, ksp_sketch_stats* stats) {
+                     const u32 seed, u64* d_out_keys, u32* d_out_abund, const u64 capacity, u64* h_out_off, ksp_sketch_stats* stats, const int mol = KSP_MOL_DNA,
+                     const bool translate = false) {
     int rc = KSP_OK;
     ksp_sketch_stats S;
     std::memset(&S, 0, sizeof S);
@@ -250,7 +257,9 @@ int sketch_on_device(const char* who, const uint8_t* d_seq, const u64 n_bytes, c
     if (n_tiles) {
         const HashArgs H{d_seq, n_bytes, n_tiles, d_src_off, n_sources, (u32)ksize, seed, max_hash, d_recs, d_recs ? capacity : 0, d_count};
         S.workgroups = G.grid_of(n_tiles);
-        if (ksize > 32) hipLaunchKernelGGL(k_sketch_hash<true>, dim3((unsigned)S.workgroups), dim3(kThreads), 0, nullptr, H);
+        if (mol != KSP_MOL_DNA && translate) hipLaunchKernelGGL(k_sketch_hash_translated, dim3((unsigned)S.workgroups), dim3(kThreads), 0, nullptr, MolArgs{H, mol});
+        else if (mol != KSP_MOL_DNA) hipLaunchKernelGGL(k_sketch_hash_protein, dim3((unsigned)S.workgroups), dim3(kThreads), 0, nullptr, MolArgs{H, mol});
+        else if (ksize > 32) hipLaunchKernelGGL(k_sketch_hash<true>, dim3((unsigned)S.workgroups), dim3(kThreads), 0, nullptr, H);
         else hipLaunchKernelGGL(k_sketch_hash<false>, dim3((unsigned)S.workgroups), dim3(kThreads), 0, nullptr, H);
         KSP_TRY_HIP(hipGetLastError());
     }
@@ -323,25 +332,32 @@ void ksp::pinned_free(void* p) {
     if (p) (void)hipHostFree(p);
 }
 
-// ksp_sketch_device and, with counts, ksp_sketch_device_abund
+// ksp_sketch_device, with counts ksp_sketch_device_abund, and with a molecule type and flags ksp_sketch_device_mol
 static int sketch_device(const char* who, const bool counted, int device, const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* h_src_offsets, uint32_t n_sources, int ksize,
-                  uint64_t max_hash, uint32_t seed, uint64_t* d_out_keys, uint32_t* d_out_abund, uint64_t capacity, uint64_t* h_out_offsets, ksp_sketch_stats* stats) {
+                  uint64_t max_hash, uint32_t seed, uint64_t* d_out_keys, uint32_t* d_out_abund, uint64_t capacity, uint64_t* h_out_offsets, ksp_sketch_stats* stats,
+                  const int mol = KSP_MOL_DNA, const uint64_t flags = 0) {
+    if (const int rc = ksp::check_sketch_mol(who, ksize, mol, flags)) return rc;
     if (const int rc = check_device_args(who, d_seq, n_bytes, h_src_offsets, n_sources, ksize, h_out_offsets)) return rc;
     if (!d_out_keys && capacity) { ksp::set_error(std::string(who) + ": d_out_keys is NULL but capacity is not 0"); return KSP_E_ARG; }
     if (counted && !d_out_abund && capacity) { ksp::set_error(std::string(who) + ": d_out_abund is NULL but capacity is not 0"); return KSP_E_ARG; }
     if ((uintptr_t)d_seq & 15) { ksp::set_error(std::string(who) + ": d_seq is not 16-byte aligned"); return KSP_E_ARG; }
     if (const int rc = ksp::set_device(who, device)) return rc;
-    return sketch_on_device(who, d_seq, n_bytes, h_src_offsets, n_sources, ksize, max_hash, seed, d_out_keys, counted ? d_out_abund : nullptr, capacity, h_out_offsets, stats);
+    return sketch_on_device(who, d_seq, n_bytes, h_src_offsets, n_sources, ksize, max_hash, seed, d_out_keys, counted ? d_out_abund : nullptr, capacity, h_out_offsets, stats, mol,
+                            (flags & KSP_SKETCH_TRANSLATE) != 0);
 }
 
-// ksp_sketch_host and, with counts in *out_abund, ksp_sketch_host_abund
+// ksp_sketch_host, with counts in *out_abund ksp_sketch_host_abund, and with a molecule type and flags ksp_sketch_host_mol
 static int sketch_host(const char* who, int device, const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize, uint64_t max_hash, uint32_t seed,
-                uint64_t** out_keys, uint32_t** out_abund, uint64_t* out_offsets, ksp_sketch_stats* stats) {
+                uint64_t** out_keys, uint32_t** out_abund, uint64_t* out_offsets, ksp_sketch_stats* stats, const int mol = KSP_MOL_DNA, const uint64_t flags = 0) {
+    if (const int rc = ksp::check_sketch_mol(who, ksize, mol, flags)) return rc;
     if (const int rc = check_device_args(who, seq, n_bytes, src_offsets, n_sources, ksize, out_offsets)) return rc;
+    const bool translate = (flags & KSP_SKETCH_TRANSLATE) != 0;
     u64 first = 0;
-    {   // the share of all hashes that max_hash keeps, a quarter more, and room for a small input whatever its luck
+    {   // the share of all hashes that max_hash keeps, a quarter more, and room for a small input whatever its luck; a translated
+        // position has two hashes
         const double share = ((double)max_hash + 1.0) / 18446744073709551616.0;
-        const u64 guess = std::min<u64>(n_bytes, (u64)((double)n_bytes * share * 1.25) + 4096);
+        const u64 per = translate ? 2 : 1;
+        const u64 guess = std::min<u64>(per * n_bytes, per * ((u64)((double)n_bytes * share * 1.25) + 4096));
         if (const int rc = env_first_capacity(who, guess, &first)) return rc;
     }
     if (const int rc = ksp::set_device(who, device)) return rc;
@@ -365,7 +381,7 @@ static int sketch_host(const char* who, int device, const uint8_t* seq, uint64_t
     KSP_TRY_HIP(hipEventRecord(ev1, nullptr));
     KSP_TRY_HIP(hipEventSynchronize(ev1));
     KSP_TRY_HIP(hipEventElapsedTime(&ms_upload, ev0, ev1));
-    rc = sketch_on_device(who, d_seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, d_keys, d_abund, capacity, out_offsets, &S);
+    rc = sketch_on_device(who, d_seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, d_keys, d_abund, capacity, out_offsets, &S, mol, translate);
     if (rc == KSP_E_OVERFLOW) {   // once more, at the exact size
         KSP_TRY_HIP(A.release(d_keys));
         d_keys = nullptr;
@@ -375,7 +391,7 @@ static int sketch_host(const char* who, int device, const uint8_t* seq, uint64_t
         if ((rc = ksp::device_fits(who, per_key * capacity, out_abund ? "the keys and the counts" : "the keys"))) goto done;
         if ((rc = A.alloc(&d_keys, (size_t)capacity))) goto done;
         if (out_abund && (rc = A.alloc(&d_abund, (size_t)capacity + 1))) goto done;
-        rc = sketch_on_device(who, d_seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, d_keys, d_abund, capacity, out_offsets, &S);
+        rc = sketch_on_device(who, d_seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, d_keys, d_abund, capacity, out_offsets, &S, mol, translate);
         S.retries = 1;
     }
     if (rc != KSP_OK) goto done;
@@ -422,4 +438,18 @@ extern "C" int ksp_sketch_host_abund(int device, const uint8_t* seq, uint64_t n_
     const char* who = "ksp_sketch_host_abund";
     if (!out_keys || !out_abund) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
     return sketch_host(who, device, seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, out_keys, out_abund, out_offsets, stats);
+}
+
+extern "C" int ksp_sketch_device_mol(int device, const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* h_src_offsets, uint32_t n_sources, int ksize, int moltype, uint64_t flags,
+                                     uint64_t max_hash, uint32_t seed, uint64_t* d_out_keys, uint32_t* d_out_abund, uint64_t capacity, uint64_t* h_out_offsets,
+                                     ksp_sketch_stats* stats) {
+    return sketch_device("ksp_sketch_device_mol", d_out_abund != nullptr, device, d_seq, n_bytes, h_src_offsets, n_sources, ksize, max_hash, seed, d_out_keys, d_out_abund, capacity,
+                         h_out_offsets, stats, moltype, flags);
+}
+
+extern "C" int ksp_sketch_host_mol(int device, const uint8_t* seq, uint64_t n_bytes, const uint64_t* src_offsets, uint32_t n_sources, int ksize, int moltype, uint64_t flags,
+                                   uint64_t max_hash, uint32_t seed, uint64_t** out_keys, uint32_t** out_abund, uint64_t* out_offsets, ksp_sketch_stats* stats) {
+    const char* who = "ksp_sketch_host_mol";
+    if (!out_keys) { ksp::set_error(std::string(who) + ": NULL argument"); return KSP_E_ARG; }
+    return sketch_host(who, device, seq, n_bytes, src_offsets, n_sources, ksize, max_hash, seed, out_keys, out_abund, out_offsets, stats, moltype, flags);
 }

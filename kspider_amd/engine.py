@@ -82,6 +82,10 @@ GATHER_WROW_DTYPE = np.dtype([("query", np.uint32), ("rank", np.uint32), ("sourc
 #: the sketcher (csrc/sketcher.hip): positions per tile of the hash pass; the flags of kspider_sketch
 SKETCH_TILE_BASES = 4096
 SKETCH_PER_RECORD, SKETCH_SEED, SKETCH_ABUND = 1, 2, 4
+#: protein sketches: the molecule types of the _mol calls, their flags of kspider_sketch, six-frame translation
+MOL_DNA, MOL_PROTEIN, MOL_DAYHOFF, MOL_HP = 0, 1, 2, 3
+SKETCH_PROTEIN, SKETCH_DAYHOFF, SKETCH_HP, SKETCH_TRANSLATE = 8, 16, 32, 64
+_MOLTYPES = {"dna": MOL_DNA, "protein": MOL_PROTEIN, "dayhoff": MOL_DAYHOFF, "hp": MOL_HP}
 
 #: ksp_engine_lists_path / Engine.lists_path
 LISTS_NONE, LISTS_KEYED, LISTS_COMPACTED, LISTS_SORTED, LISTS_FUSED = 0, 1, 2, 3, 4
@@ -120,6 +124,7 @@ ABI_SYMBOLS = [
     "ksp_sketch_cpu_abund", "ksp_sketch_device_abund", "ksp_sketch_host_abund", "ksp_sig_read",
     "ksp_sketch_max_hash", "ksp_murmur64", "ksp_sketch_kmer_hash", "ksp_sketch_cpu", "ksp_sketch_device", "ksp_sketch_host",
     "ksp_fastx_info", "ksp_fastx_load", "kspider_sketch",
+    "ksp_sketch_text_hash", "ksp_sketch_cpu_mol", "ksp_sketch_device_mol", "ksp_sketch_host_mol",
 ]
 
 
@@ -401,6 +406,13 @@ def lib():
         L.ksp_fastx_info.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
         L.ksp_fastx_load.argtypes = [ctypes.c_char_p] + [ctypes.c_void_p] * 4
         L.kspider_sketch.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint64]
+        L.ksp_sketch_text_hash.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]
+        L.ksp_sketch_cpu_mol.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
+                                         ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+        L.ksp_sketch_device_mol.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                            ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(SketchStats)]
+        L.ksp_sketch_host_mol.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                          ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SketchStats)]
         _lib = L
     return _lib
 
@@ -1293,12 +1305,86 @@ def fastx_read(path: str) -> dict:
             "fastq": bool(info[3])}
 
 
+def _moltype(moltype) -> int:
+    """A molecule type by number or by name ("dna", "protein", "dayhoff", "hp"); an unknown number is passed on and refused by the library."""
+    if isinstance(moltype, str):
+        if moltype.lower() not in _MOLTYPES:
+            raise ValueError("moltype is dna, protein, dayhoff or hp")
+        return _MOLTYPES[moltype.lower()]
+    return int(moltype)
+
+
+def sketch_text_hash(text, moltype, seed: int = 42) -> tuple:
+    """(hash, valid) of the one k-mer the residue bytes spell for a protein, dayhoff or hp moltype (host only); valid is False, and
+    hash 0, when a byte is neither a letter nor '*'."""
+    text = text.encode() if isinstance(text, str) else bytes(text)
+    h, v = ctypes.c_uint64(0), ctypes.c_int(0)
+    _check(lib().ksp_sketch_text_hash(text, len(text), _moltype(moltype), int(seed), ctypes.byref(h), ctypes.byref(v)))
+    return h.value, bool(v.value)
+
+
+def sketch_cpu_mol(seq, src_offsets, ksize: int, moltype, translate: bool = False, max_hash: int | None = None, scaled: int | None = None, seed: int = 42,
+                   abund: bool = False) -> tuple:
+    """ksp_sketch_cpu_mol, the plain host loop for a molecule type: residue bytes, or with translate DNA read in six frames ->
+    (keys, offsets), with abund (keys, abund, offsets).  No GPU."""
+    buf, off, mh = _sketch_input(seq, src_offsets, max_hash, scaled)
+    n_src = max(off.size - 1, 0)
+    out_off = np.zeros(n_src + 1, dtype=np.uint64)
+    needed = ctypes.c_uint64(0)
+    mol, flags = _moltype(moltype), SKETCH_TRANSLATE if translate else 0
+    rc = lib().ksp_sketch_cpu_mol(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mol, flags, mh, int(seed), None, None, 0, out_off.ctypes.data, ctypes.byref(needed))
+    if rc not in (KSP_OK, KSP_E_OVERFLOW):
+        _check(rc)
+    keys, counts = np.zeros(max(needed.value, 1), dtype=np.uint64), np.zeros(max(needed.value, 1), dtype=np.uint32)
+    _check(lib().ksp_sketch_cpu_mol(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mol, flags, mh, int(seed), keys.ctypes.data, counts.ctypes.data if abund else None,
+                                    needed.value, out_off.ctypes.data, ctypes.byref(needed)))
+    if abund:
+        return keys[:needed.value].copy(), counts[:needed.value].copy(), out_off
+    return keys[:needed.value].copy(), out_off
+
+
+def sketch_host_mol(seq, src_offsets, ksize: int, moltype, translate: bool = False, max_hash: int | None = None, scaled: int | None = None, seed: int = 42,
+                    abund: bool = False, device: int = 0) -> tuple:
+    """ksp_sketch_host_mol: sketch_cpu_mol's result made on the device -> (keys, offsets, stats), with abund (keys, abund, offsets, stats)."""
+    buf, off, mh = _sketch_input(seq, src_offsets, max_hash, scaled)
+    n_src = max(off.size - 1, 0)
+    out_off = np.zeros(n_src + 1, dtype=np.uint64)
+    out, out_a = ctypes.c_void_p(), ctypes.c_void_p()
+    st = SketchStats()
+    _check(lib().ksp_sketch_host_mol(int(device), _ptr(buf), buf.size, _ptr(off), n_src, int(ksize), _moltype(moltype), SKETCH_TRANSLATE if translate else 0, mh, int(seed),
+                                     ctypes.byref(out), ctypes.byref(out_a) if abund else None, out_off.ctypes.data, ctypes.byref(st)))
+    try:
+        keys = _take(out, int(out_off[-1]), np.uint64)
+    finally:   # (the second buffer is freed also when the first copy failed)
+        counts = _take(out_a, int(out_off[-1]), np.uint32) if abund else None
+    if abund:
+        return keys, counts, out_off, st.as_dict()
+    return keys, out_off, st.as_dict()
+
+
+def sketch_device_mol(d_seq_ptr: int, n_bytes: int, src_offsets, ksize: int, moltype, translate: bool, max_hash: int, d_out_keys_ptr: int, d_out_abund_ptr: int,
+                      capacity: int, seed: int = 42, device: int = 0) -> tuple:
+    """ksp_sketch_device_mol: bytes, keys and (d_out_abund_ptr 0: no) counts in DEVICE memory, offsets on the host -> (rc, offsets,
+    stats): rc is KSP_OK or KSP_E_OVERFLOW (stats["needed"] is then the required capacity); anything else raises."""
+    off = np.ascontiguousarray(src_offsets, dtype=np.uint64)
+    n_src = max(off.size - 1, 0)
+    out_off = np.zeros(n_src + 1, dtype=np.uint64)
+    st = SketchStats()
+    rc = lib().ksp_sketch_device_mol(int(device), d_seq_ptr or None, int(n_bytes), _ptr(off), n_src, int(ksize), _moltype(moltype), SKETCH_TRANSLATE if translate else 0,
+                                     int(max_hash), int(seed), d_out_keys_ptr or None, d_out_abund_ptr or None, int(capacity), out_off.ctypes.data, ctypes.byref(st))
+    if rc not in (KSP_OK, KSP_E_OVERFLOW):
+        _check(rc)
+    return rc, out_off, st.as_dict()
+
+
 def sketch_files(input_path: str, kSize: int, scaled: int, out_dir: str, user_threads: int = 1, per_record: bool = False, seed: int | None = None,
-                 abund: bool = False) -> None:
+                 abund: bool = False, moltype=MOL_DNA, translate: bool = False) -> None:
     """FASTA / FASTQ files -> one sourmash-compatible .sig file per source in out_dir (kspider_sketch).  input_path: a directory
     (each file a source) or one file (per_record: each record a source); abund: every hash's abundance beside it ("abundances").
-    KSPIDER_SKETCH=host in the environment: no GPU."""
+    moltype protein, dayhoff or hp: kSize is the residue k, the input protein (.faa .fa .fasta) or, with translate, DNA read in six
+    frames; the files say "ksize": 3 * kSize.  KSPIDER_SKETCH=host in the environment: no GPU."""
     flags = (SKETCH_PER_RECORD if per_record else 0) | (0 if seed is None else SKETCH_SEED | (int(seed) << 32)) | (SKETCH_ABUND if abund else 0)
+    flags |= {MOL_DNA: 0, MOL_PROTEIN: SKETCH_PROTEIN, MOL_DAYHOFF: SKETCH_DAYHOFF, MOL_HP: SKETCH_HP}[_moltype(moltype)] | (SKETCH_TRANSLATE if translate else 0)
     _check(lib().kspider_sketch(os.fsencode(input_path), int(kSize), int(scaled), os.fsencode(out_dir), int(user_threads), flags))
 
 
