@@ -59,7 +59,13 @@ def _expected(genomes, samples):
     db = [[h for h, _ in A.sketch(genomes[n], [0, len(genomes[n])], K, mh)[0]] for n in db_names]
     q_runs = [A.sketch(samples[n], [0, len(samples[n])], K, mh)[0] for n in q_names]
     q, a = [[h for h, _ in run] for run in q_runs], [[c for _, c in run] for run in q_runs]
-    text, rows = HEADER, WR.gather(db, q, a, MIN_HASHES, 0)
+    text, rows = _tsv(db, q, a, db_names, q_names)
+    return text, rows, db_names
+
+
+def _tsv(db, q, a, db_names, q_names, min_hashes=MIN_HASHES):
+    """(the file of the weighted gather over the runs db, the runs q and their abundances a; the restatement's rows)"""
+    text, rows = HEADER, WR.gather(db, q, a, min_hashes, 0)
     for row in rows:
         query, rank, source, overlap, unique, remaining, w_unique, w_found = row[:8]
         W = sum(a[query])
@@ -67,7 +73,7 @@ def _expected(genomes, samples):
         weighted = [np.float32(v) for v in WR.columns(row, W)]
         text += "\t".join([q_names[query], str(rank), db_names[source], str(overlap), str(unique)] + [engine.format_float(float(v)) for v in floats] + [str(remaining)]
                           + [engine.format_float(float(v)) for v in weighted] + [str(w_unique), str(w_found), str(W)]) + "\n"
-    return text.encode(), rows, db_names
+    return text.encode(), rows
 
 
 def test_sketch_abund_then_gather_abund(planted):

@@ -141,3 +141,89 @@ def test_poly_a():
     assert c.seq == b"A" * (T + 2000)
     kmers = P.source_kmers(c.seq[:100], 10, P.PROTEIN, True)
     assert set(kmers[0::2]) == {"K" * 10} and set(kmers[1::2]) == {"F" * 10}
+
+
+# ---- the builders of the edge tests (tests/test_sketch_protein_edges_gpu.py)
+
+MANY_WINDOWS = [(1, False), (7, False), (16, False), (33, False), (64, False), (3, True), (21, True), (63, True)]   # the windows the edge tests run
+
+
+@pytest.mark.parametrize("window,dna", MANY_WINDOWS)
+def test_many_sources(window, dna):
+    c = I.many_sources(window, dna)
+    off, n = c.offsets, len(c.seq)
+    assert n == 3 * T + 7 and n % 16 and off[0] == 0 and off[-1] == n and off == sorted(off)
+    assert all(chr(x) in (P.BASES if dna else P.RESIDUES) for x in c.seq)            # no break byte: the sources abut
+    assert 0.05 < sum(chr(x).islower() for x in c.seq) / n < 0.15
+    assert {T - 1, T, T + 1, 2 * T} <= set(off)                                        # the forced ends
+    assert {x % 16 for x in off[1:]} == set(range(16))                                 # ends at every offset of a 16-byte piece
+    assert len(off) - 1 >= 100
+    lengths = [b - a for a, b in zip(off, off[1:])]
+    assert lengths[:3] == [0, 0, 0] and lengths[-3:] == [0, 0, 0]                      # empty sources at the start and at the end
+    at = off.index(2 * T)
+    assert off[at:at + 4] == [2 * T] * 4                                               # and three on a tile edge
+    assert sum(x == 0 for x in lengths) >= 9 and (window == 1 or sum(0 < x < window for x in lengths) >= 20)
+    assert sum(x >= window for x in lengths) >= 20
+    # sources lie on both sides of, and over, each tile edge
+    for edge in (T, 2 * T, 3 * T):
+        assert any(a < edge < b for a, b in zip(off, off[1:])) or edge in off
+
+
+def test_strand_thresholds():
+    c = I.dna_mixed()
+    fw, rv = I.strand_hashes(c, 10, P.PROTEIN)
+    m1, m2 = I.strand_thresholds(c, 10, P.PROTEIN)
+    assert m1 in fw and m1 not in rv and m2 in rv and m2 not in fw                     # both kinds exist
+    everything = sorted(fw | rv)
+    for m in (m1, m2):                                                                 # neither empty nor full
+        assert len(everything) // 10 < sum(h <= m for h in everything) < len(everything) - len(everything) // 10
+    m = I.median_hash(I.protein_mixed(), 17, P.PROTEIN, False)
+    hashes = {h for run in P.counted_sketch(*I.protein_mixed()[1:], 17, P.PROTEIN, False, 2**64 - 1) for h in run}
+    assert m in hashes and 100 < sum(h <= m for h in hashes) < len(hashes) - 100
+
+
+def test_clean_records_and_six_frames():
+    c = I.dna_mixed()
+    records = I.clean_records(c)
+    assert len(records) > 5 and all(set(r) <= P.BASES for r in records) and sum(map(len, records)) == sum(chr(x) in P.BASES for x in c.seq)
+    assert any(len(r) >= 63 for r in records)
+    assert I.six_frames(["ATGGCCTAAGTC"]) == b"MA*V\nWPK\nGLS\nDLGH\nT*A\nLRP"   # by hand: the reverse complement is GACTTAGGCCAT
+
+
+@pytest.mark.parametrize("translated", [False, True])
+def test_low_complexity_beats_the_first_capacity(translated):
+    """If a change to the guess in sketch_host stops the retry of test_natural_retry, this says why."""
+    c = I.low_complexity(translated)
+    max_hash = P.max_hash_of(1000)
+    guess = I.first_capacity_guess(len(c.seq), max_hash, translated)
+    (run,) = P.counted_sketch(c.seq, c.offsets, 8, P.PROTEIN, translated, max_hash)
+    (h,) = P.text_hashes(["T" * 8])
+    assert h == 72033104883516 <= max_hash
+    assert run == {h: 9550 if translated else 12281} and guess == (8262 if translated else 4111)
+    assert sum(run.values()) > guess                                                   # survivors > guess
+    assert len(c.seq) == (7 if translated else 3) * T
+
+
+@pytest.mark.parametrize("dna", [False, True])
+def test_long_stream(dna):
+    c = I.long_stream(5, dna)
+    assert len(c.seq) == 5 * T + 9 and c.offsets[0] == 0 and c.offsets[-1] == len(c.seq)
+    newlines = [i for i, x in enumerate(c.seq) if x == 10]
+    assert [x - 1 for x in c.offsets[1:-1]] == newlines[:len(c.offsets) - 2] and len(newlines) - (len(c.offsets) - 2) in (0, 1)
+    gaps = [b - a for a, b in zip([-1] + newlines, newlines)]
+    assert min(gaps) >= 300 and max(gaps) <= 700
+    assert all(chr(x) in (P.BASES if dna else P.RESIDUES) for x in c.seq if x != 10)
+
+
+def test_sweep_cases():
+    cases = [d for seed in I.SWEEP_SEEDS for d in I.sweep_cases(seed)]
+    assert len(cases) == 48 and cases[:12] == I.sweep_cases(I.SWEEP_SEEDS[0])          # seeded
+    assert {d["translated"] for d in cases} == {False, True} and {d["mol"] for d in cases} == {P.PROTEIN, P.DAYHOFF, P.HP}
+    assert {d["cap"] for d in cases} == {None, "1", "2"} and {d["seed"] for d in cases} == {42, 7} and {d["density"] for d in cases} == {0.0, 1 / 400, 1 / 30}
+    assert {0, 2**64 - 1, P.max_hash_of(25)} < {d["max_hash"] for d in cases}          # and hashes that occur
+    for d in cases:
+        c = d["case"]
+        assert 1 <= len(c.seq) <= 2 * T + 64 and 1 <= len(c.offsets) - 1 <= 40 and c.offsets == sorted(c.offsets) and c.offsets[0] == 0 and c.offsets[-1] == len(c.seq)
+        assert d["k"] in (I.TRANSLATED_K if d["translated"] else I.RESIDUE_K)
+    assert any(a == b for d in cases for a, b in zip(d["case"].offsets, d["case"].offsets[1:]))   # empty sources
+    assert any(len(d["case"].seq) > T for d in cases) and any(len(d["case"].seq) < T for d in cases)
