@@ -1093,7 +1093,7 @@ int ksp_sketch_host_abund(int device, const uint8_t* seq, uint64_t n_bytes, cons
                           ksp_sketch_stats* stats);
 int ksp_sig_read(const char* path, int kSize, uint64_t* mins, uint32_t* abunds, uint64_t capacity, uint64_t* n, int* has_abund);
 
-/* ---- protein, dayhoff and hp sketches; six-frame translation (csrc/sketch_mol.h, csrc/sketch_mol_kernels.hip.h) ----
+/* ---- protein, dayhoff and hp sketches; six-frame translation (csrc/sketch_mol.h, csrc/sketch_kernels.hip.h) ----
  * Molecule types: KSP_MOL_DNA 0 is the section above, untouched; KSP_MOL_PROTEIN 1, KSP_MOL_DAYHOFF 2, KSP_MOL_HP 3.
  * Residues.  A residue byte is an ASCII letter (either case, taken as upper case) or '*'; every other byte value breaks k-mers,
  *   the newline the reader puts behind each record included.  The letter that is hashed for a residue r:

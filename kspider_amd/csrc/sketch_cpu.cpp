@@ -1,7 +1,8 @@
 // The host side of the sketch arithmetic: the threshold of `scaled`, MurmurHash3_x64_128 over any bytes, the hash
 // of one k-mer, and ksp_sketch_cpu, the plain single-thread loop over sketch_hash.h.  The loop is the timing baseline of the
 // device's hash pass (tools/sketch_times.py) and what the file driver runs with KSPIDER_SKETCH=host.  ksp_sketch_cpu_mol is the
-// same for the protein, dayhoff and hp molecule types over sketch_mol.h.  Host only.
+// same for the protein, dayhoff and hp molecule types over sketch_mol.h.  sketch_cpu_frame is what every loop
+// shares from the kept hashes on; each_base_window rolls the bases for the DNA loop (k bases) and the translated one (3k).  Host only.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -65,25 +66,32 @@ int sketch_cpu_frame(const char* who, const bool counted, const uint8_t* seq, co
     }
 }
 
-// ksp_sketch_cpu and, with counts, ksp_sketch_cpu_abund
+// The rolling window of the DNA loops: full(left) for every `win` (1 .. 64) consecutive bases among the bytes [first, last), `left`
+// being them left-aligned; a byte that is no base starts the window over.
+template <class Full>
+void each_base_window(const uint8_t* seq, const uint64_t first, const uint64_t last, const unsigned win, Full full) {
+    sk::Kmer fw{0, 0};   // the last min(have, win) bases, right-aligned
+    unsigned have = 0;   // bases since the last break, capped at win
+    for (uint64_t p = first; p < last; ++p) {
+        const unsigned c = seq[p];
+        if (!sk::is_base(c)) { have = 0; fw = sk::Kmer{0, 0}; continue; }
+        fw = sk::shift_left(fw, 2);
+        fw.lo |= sk::base_code(c);
+        if (have < win) ++have;
+        if (have == win) full(sk::shift_left(fw, 128 - 2 * win));   // (drops the bases older than win)
+    }
+}
+
+// ksp_sketch_cpu and, with counts, ksp_sketch_cpu_abund: every window of k bases, canonical form, hashed
 int sketch_cpu(const char* who, const bool counted, const uint8_t* seq, const uint64_t n_bytes, const uint64_t* src_offsets, const uint32_t n_sources, const int ksize,
                const uint64_t max_hash, const uint32_t seed, uint64_t* out_keys, uint32_t* out_abund, const uint64_t capacity, uint64_t* out_offsets, uint64_t* needed) {
     const unsigned k = (unsigned)ksize;
     return sketch_cpu_frame(who, counted, seq, n_bytes, src_offsets, n_sources, ksize, out_keys, out_abund, capacity, out_offsets, needed,
                             [&](const uint64_t first, const uint64_t last, std::vector<uint64_t>& run) {
-                                sk::Kmer fw{0, 0};   // the last min(have, k) bases, right-aligned
-                                unsigned have = 0;   // bases since the last break, capped at k
-                                for (uint64_t p = first; p < last; ++p) {
-                                    const unsigned c = seq[p];
-                                    if (!sk::is_base(c)) { have = 0; fw = sk::Kmer{0, 0}; continue; }
-                                    fw = sk::shift_left(fw, 2);
-                                    fw.lo |= sk::base_code(c);
-                                    if (have < k) ++have;
-                                    if (have < k) continue;
-                                    const sk::Kmer left = sk::shift_left(fw, 128 - 2 * k);   // (drops the bases older than k)
+                                each_base_window(seq, first, last, k, [&](const sk::Kmer& left) {
                                     const uint64_t h = sk::kmer_hash(sk::canonical(left, k), k, seed);
                                     if (h <= max_hash) run.push_back(h);
-                                }
+                                });
                             });
 }
 
@@ -118,25 +126,15 @@ int sketch_cpu_translated(const char* who, const bool counted, const uint8_t* se
     for (unsigned c = 0; c < 64; ++c) codon[c] = (uint8_t)sk::codon_letter(mol, c);
     return sketch_cpu_frame(who, counted, seq, n_bytes, src_offsets, n_sources, ksize, out_keys, out_abund, capacity, out_offsets, needed,
                             [&](const uint64_t first, const uint64_t last, std::vector<uint64_t>& run) {
-                                sk::Kmer fw{0, 0};   // the last min(have, k3) bases, right-aligned
-                                unsigned have = 0;   // bases since the last break, capped at k3
-                                const uint8_t* table = codon;
-                                for (uint64_t p = first; p < last; ++p) {
-                                    const unsigned c = seq[p];
-                                    if (!sk::is_base(c)) { have = 0; fw = sk::Kmer{0, 0}; continue; }
-                                    fw = sk::shift_left(fw, 2);
-                                    fw.lo |= sk::base_code(c);
-                                    if (have < k3) ++have;
-                                    if (have < k3) continue;
-                                    const sk::Kmer left = sk::shift_left(fw, 128 - 2 * k3);   // (drops the bases older than k3)
+                                each_base_window(seq, first, last, k3, [&](const sk::Kmer& left) {
                                     uint64_t w[3];
-                                    sk::translate_words(left, k, table, w);
+                                    sk::translate_words(left, k, codon, w);
                                     const uint64_t h_f = sk::letters_hash<3>(w, k, seed);
-                                    sk::translate_words(sk::reverse_complement(left, k3), k, table, w);
+                                    sk::translate_words(sk::reverse_complement(left, k3), k, codon, w);
                                     const uint64_t h_r = sk::letters_hash<3>(w, k, seed);
                                     if (h_f <= max_hash) run.push_back(h_f);
                                     if (h_r <= max_hash) run.push_back(h_r);
-                                }
+                                });
                             });
 }
 

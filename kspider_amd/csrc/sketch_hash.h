@@ -1,4 +1,4 @@
-// The arithmetic of a DNA FracMinHash sketch, one copy for the device kernel (sketcher.hip) and the host loop
+// The arithmetic of a DNA FracMinHash sketch, one copy for the device kernels (sketch_kernels.hip.h) and the host loop
 // (sketch_cpu.cpp): the 2-bit code of a base, the reverse complement of a packed k-mer, the ASCII text of a packed k-mer, and
 // the first word of MurmurHash3_x64_128 over it.
 //

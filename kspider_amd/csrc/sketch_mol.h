@@ -1,5 +1,5 @@
 // The arithmetic of the protein, dayhoff and hp FracMinHash sketches, one copy for the device kernels
-// (sketch_mol_kernels.hip.h) and the host loop (sketch_cpu.cpp): which bytes are residues, the letter a residue is hashed as,
+// (sketch_kernels.hip.h) and the host loop (sketch_cpu.cpp): which bytes are residues, the letter a residue is hashed as,
 // the codon of a packed k-mer and the letter it translates to, and Murmur over up to 64 letters held as little-endian words.
 // What the DNA path calls is in sketch_hash.h and is not touched.
 #ifndef KSPIDER_SKETCH_MOL_H

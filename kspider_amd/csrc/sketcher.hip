@@ -1,19 +1,14 @@
-// The device part of the sketcher: bytes of FASTA / FASTQ records in HBM -> sourmash-compatible DNA FracMinHash
-// sketches.  The arithmetic — codes, reverse complement, the k-mer's text, Murmur — is sketch_hash.h, shared with the host loop.
+// The device part of the sketcher: bytes of FASTA / FASTQ records in HBM -> sourmash-compatible FracMinHash
+// sketches.  The arithmetic — codes, reverse complement, the k-mer's text, Murmur — is sketch_hash.h, for the protein, dayhoff
+// and hp molecule types sketch_mol.h, both shared with the host loop.
 //
-//   hash     one pass over the bytes.  A workgroup of 256 loops over tiles of kTile positions.  Per tile every thread loads
-//            16 bytes (the first four another 16: the halo of ksize - 1 <= 63 bytes) and turns them into 32 bits of 2-bit codes
-//            and 16 break bits in LDS (1.6 KiB); bytes behind the stream's end are breaks.  Then a thread takes the positions
-//            tid, tid + 256, ...: "no break bit in [p, p + k)" from two mask words; the forward k-mer, left-aligned, as a funnel
-//            shift of two (k > 32: three) code words — no lane rolls over the bases before it; canonical form, text, Murmur,
-//            hash <= max_hash.  A survivor (about 1 in `scaled`) finds its source by binary search of the offsets, is dropped
-//            when its k-mer would cross the source's end, and is appended as (hash, source): one ballot and one returning add
-//            per wave; the counter keeps counting past the capacity, nothing is written past it.
-//   select   rocPRIM's merge sort by (source, hash), one scan of head flags (an entry that differs from the one before),
-//            k_sketch_compact writes the heads' hashes, k_sketch_offsets the per-source bounds by binary search.  The counted
-//            calls launch k_sketch_compact_abund instead: a head also writes the length of its run, its abundance.
-// The protein, dayhoff and hp molecule types have hash passes of their own, k_sketch_hash_protein and
-// k_sketch_hash_translated in sketch_mol_kernels.hip.h, and share everything from the survivor records on.
+//   hash     one pass over the bytes, sketch_kernels.hip.h: one tile frame and what k_sketch_hash (DNA), k_sketch_hash_protein
+//            and k_sketch_hash_translated add to it.  It leaves the survivors, about 1 in `scaled`, as unsorted (hash, source)
+//            records and counts them past the capacity without writing past it.
+//   select   this file: rocPRIM's merge sort by (source, hash), one scan of head flags (an entry that differs from the one
+//            before), k_sketch_compact writes the heads' hashes, k_sketch_offsets the per-source bounds by binary search.  The
+//            counted calls launch k_sketch_compact_abund instead: a head also writes the length of its run, its
+//            abundance.  The same for every molecule type.
 // Every loop is bounded by a size the host computed; no workgroup waits on another; the result does not depend on scheduling.
 #include <cstdint>
 #include <cstdlib>
@@ -39,119 +34,7 @@ namespace sk = ksp_sketch;
 typedef uint32_t u32;
 typedef uint64_t u64;
 
-constexpr int kThreads = 256;
-constexpr u32 kTile = KSP_SKETCH_TILE_BASES;
-constexpr u32 kChunks = kTile / 16 + 4;   // 16-byte pieces of a tile and its halo of 64 bytes
-constexpr u32 kCodeWords = kChunks / 2;   // 32 bases per word
-constexpr u32 kMaskWords = kChunks / 4;   // 64 positions per word
-static_assert(kTile == 16 * kThreads, "a thread loads one 16-byte piece of the tile");
-static_assert(kTile % 64 == 0 && kChunks % 4 == 0, "whole mask words");
-
-// a survivor: its hash and its source
-struct Rec {
-    u64 hash, src;
-};
-
-struct HashArgs {
-    const uint8_t* seq;
-    u64 n_bytes, n_tiles;
-    const u64* src_off;   // n_sources + 1, device
-    u32 n_sources, k, seed;
-    u64 max_hash;
-    Rec* recs;
-    u64 capacity;
-    unsigned long long* counters;   // [0] survivors, the ones without room included, [1] bases, [2] windows without a break
-};
-
-// the sum of v over the wave, in lane 0
-__device__ inline u32 wave_sum(u32 v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (u32)__shfl_down((int)v, d);
-    return v;
-}
-
-// kWide: ksize > 32, the k-mer takes two words
-template <bool kWide>
-__global__ __launch_bounds__(kThreads) void k_sketch_hash(const HashArgs A) {
-    __shared__ u64 s_code[kCodeWords];   // big-endian: base 32j of the tile on top of word j
-    __shared__ u64 s_mask[kMaskWords];   // little-endian: bit i of word m = position 64m + i is a break
-    const u32 tid = threadIdx.x, lane = tid & 63;
-    u32 n_bases = 0, n_valid = 0;
-    const u64 win_mask = A.k == 64 ? ~0ull : (1ull << A.k) - 1;
-    for (u64 tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {
-        const u64 t0 = tile * kTile;
-        // ---- the tile and its halo as codes and break bits
-        for (u32 c = tid; c < kChunks; c += kThreads) {   // (two trips for the first four threads, one for the others)
-            const u64 at = t0 + 16ull * c;
-            u32 w[4] = {0, 0, 0, 0};   // (a zero byte is a break)
-            if (at + 16 <= A.n_bytes) {
-                const uint4 v = *reinterpret_cast<const uint4*>(A.seq + at);
-                w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-            } else if (at < A.n_bytes) {
-                const u32 n = (u32)(A.n_bytes - at);   // 1 .. 15 bytes are left
-#pragma unroll
-                for (u32 j = 0; j < 16; ++j)
-                    if (j < n) w[j >> 2] |= (u32)A.seq[at + j] << (8 * (j & 3));
-            }
-            u32 code = 0, breaks = 0;
-#pragma unroll
-            for (u32 j = 0; j < 16; ++j) {
-                const u32 b = (w[j >> 2] >> (8 * (j & 3))) & 0xFFu;
-                code |= sk::base_code(b) << (30 - 2 * j);
-                breaks |= (sk::is_base(b) ? 0u : 1u) << j;
-            }
-            reinterpret_cast<u32*>(s_code)[c ^ 1u] = code;   // (the even piece is the upper half of its word)
-            reinterpret_cast<uint16_t*>(s_mask)[c] = (uint16_t)breaks;
-            if (c < kTile / 16) n_bases += 16u - (u32)__popc(breaks);
-        }
-        __syncthreads();
-        // ---- the positions of the tile
-        for (u32 p = tid; p < kTile; p += kThreads) {   // (the same trips for every thread)
-            const u32 m = p >> 6, s = p & 63;
-            const u64 window = s ? (s_mask[m] >> s) | (s_mask[m + 1] << (64 - s)) : s_mask[m];   // (m + 1 <= 64: the halo's word)
-            const bool valid = (window & win_mask) == 0;
-            bool keep = false;
-            u64 h = 0, src = 0;
-            if (valid) {
-                ++n_valid;
-                const u32 j = p >> 5, s2 = 2 * (p & 31);
-                sk::Kmer fw;
-                fw.hi = s2 ? (s_code[j] << s2) | (s_code[j + 1] >> (64 - s2)) : s_code[j];
-                fw.lo = 0;
-                if (kWide) fw.lo = s2 ? (s_code[j + 1] << s2) | (s_code[j + 2] >> (64 - s2)) : s_code[j + 1];   // (j + 2 <= 129)
-                fw = sk::keep_top(fw, A.k);
-                h = sk::kmer_hash(sk::canonical(fw, A.k), A.k, A.seed);
-                if (h <= A.max_hash) {
-                    const u64 gp = t0 + p;   // (below n_bytes: the window is valid)
-                    u32 lo = 0, hi = A.n_sources;   // the source of gp: the last s with src_off[s] <= gp
-                    while (hi - lo > 1) {
-                        const u32 mid = lo + (hi - lo) / 2;
-                        if (A.src_off[mid] <= gp) lo = mid; else hi = mid;
-                    }
-                    src = lo;
-                    keep = gp + A.k <= A.src_off[lo + 1];   // a k-mer over the end of its source is none
-                }
-            }
-            const unsigned long long have = __ballot(keep);
-            if (!have) continue;   // (the whole wave)
-            const int first = __ffsll((long long)have) - 1;
-            unsigned long long at = 0;
-            if ((int)lane == first) at = atomicAdd(&A.counters[0], (unsigned long long)__popcll(have));
-            const u32 at_lo = (u32)__shfl((int)(u32)at, first), at_hi = (u32)__shfl((int)(u32)(at >> 32), first);
-            const u64 slot = (((u64)at_hi << 32) | at_lo) + (u64)__popcll(have & ((1ull << lane) - 1));
-            if (keep && slot < A.capacity) A.recs[slot] = Rec{h, src};
-        }
-        __syncthreads();   // (the next tile's pieces overwrite the words)
-    }
-    n_bases = wave_sum(n_bases);
-    n_valid = wave_sum(n_valid);
-    if (lane == 0) {
-        if (n_bases) atomicAdd(&A.counters[1], (unsigned long long)n_bases);
-        if (n_valid) atomicAdd(&A.counters[2], (unsigned long long)n_valid);
-    }
-}
-
-#include "sketch_mol_kernels.hip.h"
+#include "sketch_kernels.hip.h"
 
 struct RecBefore {
     __host__ __device__ bool operator()(const Rec& a, const Rec& b) const { return a.src != b.src ? a.src < b.src : a.hash < b.hash; }

@@ -1204,91 +1204,88 @@ def _sketch_input(seq, src_offsets, max_hash, scaled):
     return buf, off, (sketch_max_hash(scaled) if max_hash is None else int(max_hash))
 
 
-def sketch_cpu(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled: int | None = None, seed: int = 42) -> tuple:
-    """ksp_sketch_cpu, the plain host loop: bytes and source offsets -> (keys, offsets) of the sources' sketches.  No GPU."""
+def _sketch_cpu(entry, lead, abund, seq, src_offsets, ksize, max_hash, scaled, seed):
+    """A host loop: the size query, then the fill -> (keys, [abund,] offsets).  entry: the C function; lead: its arguments between
+    ksize and max_hash; abund: None when it takes no abundance buffer, else whether one is passed and returned."""
     buf, off, mh = _sketch_input(seq, src_offsets, max_hash, scaled)
     n_src = max(off.size - 1, 0)
     out_off = np.zeros(n_src + 1, dtype=np.uint64)
     needed = ctypes.c_uint64(0)
-    rc = lib().ksp_sketch_cpu(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), None, 0, out_off.ctypes.data, ctypes.byref(needed))
+
+    def call(keys, counts, capacity):
+        return entry(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), *lead, mh, int(seed), _ptr(keys), *(() if abund is None else (_ptr(counts),)), capacity,
+                     out_off.ctypes.data, ctypes.byref(needed))
+
+    rc = call(None, None, 0)
     if rc not in (KSP_OK, KSP_E_OVERFLOW):
         _check(rc)
-    keys = np.zeros(max(needed.value, 1), dtype=np.uint64)
-    _check(lib().ksp_sketch_cpu(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), keys.ctypes.data, needed.value, out_off.ctypes.data,
-                                ctypes.byref(needed)))
-    return keys[:needed.value].copy(), out_off
+    keys, counts = np.zeros(max(needed.value, 1), dtype=np.uint64), (np.zeros(max(needed.value, 1), dtype=np.uint32) if abund else None)
+    _check(call(keys, counts, needed.value))
+    return (keys[:needed.value].copy(),) + ((counts[:needed.value].copy(),) if abund else ()) + (out_off,)
 
 
-def sketch_cpu_abund(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled: int | None = None, seed: int = 42) -> tuple:
-    """ksp_sketch_cpu_abund: sketch_cpu with every key's abundance -> (keys, abund, offsets).  No GPU."""
-    buf, off, mh = _sketch_input(seq, src_offsets, max_hash, scaled)
-    n_src = max(off.size - 1, 0)
-    out_off = np.zeros(n_src + 1, dtype=np.uint64)
-    needed = ctypes.c_uint64(0)
-    rc = lib().ksp_sketch_cpu_abund(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), None, None, 0, out_off.ctypes.data, ctypes.byref(needed))
-    if rc not in (KSP_OK, KSP_E_OVERFLOW):
-        _check(rc)
-    keys, abund = np.zeros(max(needed.value, 1), dtype=np.uint64), np.zeros(max(needed.value, 1), dtype=np.uint32)
-    _check(lib().ksp_sketch_cpu_abund(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), keys.ctypes.data, abund.ctypes.data, needed.value,
-                                      out_off.ctypes.data, ctypes.byref(needed)))
-    return keys[:needed.value].copy(), abund[:needed.value].copy(), out_off
-
-
-def sketch_host_abund(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled: int | None = None, seed: int = 42, device: int = 0) -> tuple:
-    """ksp_sketch_host_abund: sketch_host with every key's abundance, counted on the device -> (keys, abund, offsets, stats)."""
+def _sketch_host(entry, lead, abund, seq, src_offsets, ksize, max_hash, scaled, seed, device):
+    """A call that sketches host bytes on the device and returns malloc'ed buffers -> (keys, [abund,] offsets, stats); the
+    arguments as in _sketch_cpu."""
     buf, off, mh = _sketch_input(seq, src_offsets, max_hash, scaled)
     n_src = max(off.size - 1, 0)
     out_off = np.zeros(n_src + 1, dtype=np.uint64)
     out, out_a = ctypes.c_void_p(), ctypes.c_void_p()
     st = SketchStats()
-    _check(lib().ksp_sketch_host_abund(int(device), _ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), ctypes.byref(out), ctypes.byref(out_a),
-                                       out_off.ctypes.data, ctypes.byref(st)))
+    _check(entry(int(device), _ptr(buf), buf.size, _ptr(off), n_src, int(ksize), *lead, mh, int(seed), ctypes.byref(out),
+                 *(() if abund is None else (ctypes.byref(out_a) if abund else None,)), out_off.ctypes.data, ctypes.byref(st)))
     try:
         keys = _take(out, int(out_off[-1]), np.uint64)
     finally:   # (the second buffer is freed also when the first copy failed)
-        abund = _take(out_a, int(out_off[-1]), np.uint32)
-    return keys, abund, out_off, st.as_dict()
+        counts = _take(out_a, int(out_off[-1]), np.uint32) if abund else None
+    return (keys,) + ((counts,) if abund else ()) + (out_off, st.as_dict())
 
 
-def sketch_device_abund(d_seq_ptr: int, n_bytes: int, src_offsets, ksize: int, max_hash: int, d_out_keys_ptr: int, d_out_abund_ptr: int, capacity: int, seed: int = 42,
-                        device: int = 0) -> tuple:
-    """ksp_sketch_device_abund: sketch_device with d_out_abund (DEVICE, room for `capacity`) beside the keys -> (rc, offsets, stats)."""
+def _sketch_device(entry, lead, abund_ptr, d_seq_ptr, n_bytes, src_offsets, ksize, max_hash, d_out_keys_ptr, capacity, seed, device):
+    """A call on bytes and keys in DEVICE memory -> (rc, offsets, stats): rc is KSP_OK or KSP_E_OVERFLOW, anything else raises.
+    abund_ptr: None when the entry takes no abundance buffer, else its device address (0: NULL); entry and lead as in _sketch_cpu."""
     off = np.ascontiguousarray(src_offsets, dtype=np.uint64)
     n_src = max(off.size - 1, 0)
     out_off = np.zeros(n_src + 1, dtype=np.uint64)
     st = SketchStats()
-    rc = lib().ksp_sketch_device_abund(int(device), d_seq_ptr or None, int(n_bytes), _ptr(off), n_src, int(ksize), int(max_hash), int(seed), d_out_keys_ptr or None,
-                                       d_out_abund_ptr or None, int(capacity), out_off.ctypes.data, ctypes.byref(st))
+    rc = entry(int(device), d_seq_ptr or None, int(n_bytes), _ptr(off), n_src, int(ksize), *lead, int(max_hash), int(seed), d_out_keys_ptr or None,
+               *(() if abund_ptr is None else (abund_ptr or None,)), int(capacity), out_off.ctypes.data, ctypes.byref(st))
     if rc not in (KSP_OK, KSP_E_OVERFLOW):
         _check(rc)
     return rc, out_off, st.as_dict()
 
 
+def sketch_cpu(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled: int | None = None, seed: int = 42) -> tuple:
+    """ksp_sketch_cpu, the plain host loop: bytes and source offsets -> (keys, offsets) of the sources' sketches.  No GPU."""
+    return _sketch_cpu(lib().ksp_sketch_cpu, (), None, seq, src_offsets, ksize, max_hash, scaled, seed)
+
+
+def sketch_cpu_abund(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled: int | None = None, seed: int = 42) -> tuple:
+    """ksp_sketch_cpu_abund: sketch_cpu with every key's abundance -> (keys, abund, offsets).  No GPU."""
+    return _sketch_cpu(lib().ksp_sketch_cpu_abund, (), True, seq, src_offsets, ksize, max_hash, scaled, seed)
+
+
+def sketch_host_abund(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled: int | None = None, seed: int = 42, device: int = 0) -> tuple:
+    """ksp_sketch_host_abund: sketch_host with every key's abundance, counted on the device -> (keys, abund, offsets, stats)."""
+    return _sketch_host(lib().ksp_sketch_host_abund, (), True, seq, src_offsets, ksize, max_hash, scaled, seed, device)
+
+
+def sketch_device_abund(d_seq_ptr: int, n_bytes: int, src_offsets, ksize: int, max_hash: int, d_out_keys_ptr: int, d_out_abund_ptr: int, capacity: int, seed: int = 42,
+                        device: int = 0) -> tuple:
+    """ksp_sketch_device_abund: sketch_device with d_out_abund (DEVICE, room for `capacity`) beside the keys -> (rc, offsets, stats)."""
+    return _sketch_device(lib().ksp_sketch_device_abund, (), int(d_out_abund_ptr or 0), d_seq_ptr, n_bytes, src_offsets, ksize, max_hash, d_out_keys_ptr, capacity, seed, device)
+
+
 def sketch_host(seq, src_offsets, ksize: int, max_hash: int | None = None, scaled: int | None = None, seed: int = 42, device: int = 0) -> tuple:
     """ksp_sketch_host: host bytes and source offsets -> (keys, offsets, stats) of the sources' sketches, made on the device."""
-    buf, off, mh = _sketch_input(seq, src_offsets, max_hash, scaled)
-    n_src = max(off.size - 1, 0)
-    out_off = np.zeros(n_src + 1, dtype=np.uint64)
-    out = ctypes.c_void_p()
-    st = SketchStats()
-    _check(lib().ksp_sketch_host(int(device), _ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mh, int(seed), ctypes.byref(out), out_off.ctypes.data,
-                                 ctypes.byref(st)))
-    return _take(out, int(out_off[-1]), np.uint64), out_off, st.as_dict()
+    return _sketch_host(lib().ksp_sketch_host, (), None, seq, src_offsets, ksize, max_hash, scaled, seed, device)
 
 
 def sketch_device(d_seq_ptr: int, n_bytes: int, src_offsets, ksize: int, max_hash: int, d_out_keys_ptr: int, capacity: int, seed: int = 42,
                   device: int = 0) -> tuple:
     """ksp_sketch_device: bytes and keys in DEVICE memory, offsets on the host (d_out_keys 0 / capacity 0: the size query).
     -> (rc, offsets, stats): rc is KSP_OK or KSP_E_OVERFLOW (stats["needed"] is then the required capacity); anything else raises."""
-    off = np.ascontiguousarray(src_offsets, dtype=np.uint64)
-    n_src = max(off.size - 1, 0)
-    out_off = np.zeros(n_src + 1, dtype=np.uint64)
-    st = SketchStats()
-    rc = lib().ksp_sketch_device(int(device), d_seq_ptr or None, int(n_bytes), _ptr(off), n_src, int(ksize), int(max_hash), int(seed), d_out_keys_ptr or None,
-                                 int(capacity), out_off.ctypes.data, ctypes.byref(st))
-    if rc not in (KSP_OK, KSP_E_OVERFLOW):
-        _check(rc)
-    return rc, out_off, st.as_dict()
+    return _sketch_device(lib().ksp_sketch_device, (), None, d_seq_ptr, n_bytes, src_offsets, ksize, max_hash, d_out_keys_ptr, capacity, seed, device)
 
 
 def fastx_read(path: str) -> dict:
@@ -1327,54 +1324,22 @@ def sketch_cpu_mol(seq, src_offsets, ksize: int, moltype, translate: bool = Fals
                    abund: bool = False) -> tuple:
     """ksp_sketch_cpu_mol, the plain host loop for a molecule type: residue bytes, or with translate DNA read in six frames ->
     (keys, offsets), with abund (keys, abund, offsets).  No GPU."""
-    buf, off, mh = _sketch_input(seq, src_offsets, max_hash, scaled)
-    n_src = max(off.size - 1, 0)
-    out_off = np.zeros(n_src + 1, dtype=np.uint64)
-    needed = ctypes.c_uint64(0)
-    mol, flags = _moltype(moltype), SKETCH_TRANSLATE if translate else 0
-    rc = lib().ksp_sketch_cpu_mol(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mol, flags, mh, int(seed), None, None, 0, out_off.ctypes.data, ctypes.byref(needed))
-    if rc not in (KSP_OK, KSP_E_OVERFLOW):
-        _check(rc)
-    keys, counts = np.zeros(max(needed.value, 1), dtype=np.uint64), np.zeros(max(needed.value, 1), dtype=np.uint32)
-    _check(lib().ksp_sketch_cpu_mol(_ptr(buf), buf.size, _ptr(off), n_src, int(ksize), mol, flags, mh, int(seed), keys.ctypes.data, counts.ctypes.data if abund else None,
-                                    needed.value, out_off.ctypes.data, ctypes.byref(needed)))
-    if abund:
-        return keys[:needed.value].copy(), counts[:needed.value].copy(), out_off
-    return keys[:needed.value].copy(), out_off
+    return _sketch_cpu(lib().ksp_sketch_cpu_mol, (_moltype(moltype), SKETCH_TRANSLATE if translate else 0), bool(abund), seq, src_offsets, ksize, max_hash, scaled, seed)
 
 
 def sketch_host_mol(seq, src_offsets, ksize: int, moltype, translate: bool = False, max_hash: int | None = None, scaled: int | None = None, seed: int = 42,
                     abund: bool = False, device: int = 0) -> tuple:
     """ksp_sketch_host_mol: sketch_cpu_mol's result made on the device -> (keys, offsets, stats), with abund (keys, abund, offsets, stats)."""
-    buf, off, mh = _sketch_input(seq, src_offsets, max_hash, scaled)
-    n_src = max(off.size - 1, 0)
-    out_off = np.zeros(n_src + 1, dtype=np.uint64)
-    out, out_a = ctypes.c_void_p(), ctypes.c_void_p()
-    st = SketchStats()
-    _check(lib().ksp_sketch_host_mol(int(device), _ptr(buf), buf.size, _ptr(off), n_src, int(ksize), _moltype(moltype), SKETCH_TRANSLATE if translate else 0, mh, int(seed),
-                                     ctypes.byref(out), ctypes.byref(out_a) if abund else None, out_off.ctypes.data, ctypes.byref(st)))
-    try:
-        keys = _take(out, int(out_off[-1]), np.uint64)
-    finally:   # (the second buffer is freed also when the first copy failed)
-        counts = _take(out_a, int(out_off[-1]), np.uint32) if abund else None
-    if abund:
-        return keys, counts, out_off, st.as_dict()
-    return keys, out_off, st.as_dict()
+    return _sketch_host(lib().ksp_sketch_host_mol, (_moltype(moltype), SKETCH_TRANSLATE if translate else 0), bool(abund), seq, src_offsets, ksize, max_hash, scaled, seed,
+                        device)
 
 
 def sketch_device_mol(d_seq_ptr: int, n_bytes: int, src_offsets, ksize: int, moltype, translate: bool, max_hash: int, d_out_keys_ptr: int, d_out_abund_ptr: int,
                       capacity: int, seed: int = 42, device: int = 0) -> tuple:
     """ksp_sketch_device_mol: bytes, keys and (d_out_abund_ptr 0: no) counts in DEVICE memory, offsets on the host -> (rc, offsets,
     stats): rc is KSP_OK or KSP_E_OVERFLOW (stats["needed"] is then the required capacity); anything else raises."""
-    off = np.ascontiguousarray(src_offsets, dtype=np.uint64)
-    n_src = max(off.size - 1, 0)
-    out_off = np.zeros(n_src + 1, dtype=np.uint64)
-    st = SketchStats()
-    rc = lib().ksp_sketch_device_mol(int(device), d_seq_ptr or None, int(n_bytes), _ptr(off), n_src, int(ksize), _moltype(moltype), SKETCH_TRANSLATE if translate else 0,
-                                     int(max_hash), int(seed), d_out_keys_ptr or None, d_out_abund_ptr or None, int(capacity), out_off.ctypes.data, ctypes.byref(st))
-    if rc not in (KSP_OK, KSP_E_OVERFLOW):
-        _check(rc)
-    return rc, out_off, st.as_dict()
+    return _sketch_device(lib().ksp_sketch_device_mol, (_moltype(moltype), SKETCH_TRANSLATE if translate else 0), int(d_out_abund_ptr or 0), d_seq_ptr, n_bytes, src_offsets,
+                          ksize, max_hash, d_out_keys_ptr, capacity, seed, device)
 
 
 def sketch_files(input_path: str, kSize: int, scaled: int, out_dir: str, user_threads: int = 1, per_record: bool = False, seed: int | None = None,

@@ -1,5 +1,5 @@
 """The device hash passes of the protein, dayhoff and hp sketches (k_sketch_hash_protein and k_sketch_hash_translated,
-csrc/sketch_mol_kernels.hip.h, behind ksp_sketch_host_mol) at the edges that tests/test_sketch_protein_gpu.py leaves out, against
+csrc/sketch_kernels.hip.h, behind ksp_sketch_host_mol) at the edges that tests/test_sketch_protein_gpu.py leaves out, against
 the restatement (tests/sketch_protein_restate.py) itself and not the host loop, which shares sketch_mol.h with the kernels:
 proteome-shaped streams of a thousand abutting sources, hash seeds other than 42, max_hash exactly at one strand's hash, the six
 frames as protein input on the device, a retry that the input and not the environment forces, the default grid with more tiles

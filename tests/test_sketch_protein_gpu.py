@@ -1,4 +1,4 @@
-"""The device hash passes of the protein, dayhoff and hp sketches (csrc/sketch_mol_kernels.hip.h behind ksp_sketch_host_mol /
+"""The device hash passes of the protein, dayhoff and hp sketches (csrc/sketch_kernels.hip.h behind ksp_sketch_host_mol /
 ksp_sketch_device_mol) against the host loop ksp_sketch_cpu_mol — which tests/test_sketch_protein_cpu.py holds to the restatement
 — keys and counts, on the inputs of tests/sketch_protein_inputs.py: the k lists, streams of two to three tiles that end 1 .. 15
 bytes into a 16-byte piece, abutting sources, one hash some thousand times over a tile edge, both strands surviving at every
