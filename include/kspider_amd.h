@@ -1148,6 +1148,87 @@ int ksp_sketch_host_mol(int device, const uint8_t* seq, uint64_t n_bytes, const 
                         uint64_t flags, uint64_t max_hash, uint32_t seed, uint64_t** out_keys, uint32_t** out_abund, uint64_t* out_offsets,
                         ksp_sketch_stats* stats);
 
+/* ---- compare: counted sketches against each other — cosine, angular similarity, weighted containment (csrc/compare.hip,
+ *      csrc/sketch_pack.cpp) ----
+ * Sources are numbered as in query mode: database 0 .. n_db - 1, queries n_db .. n_db + n_q - 1.  Each side is its keys back to
+ * back, host offsets, and an optional uint32_t abundance array parallel to the keys: abund[i] belongs to keys[i].  A NULL
+ * abundance array means every abundance is 1, a flat sketch.  Runs are STRICTLY ASCENDING within a source and every abundance is
+ * >= 1.  For a pair (s1 < s2) of the mode that shares at least one hash the row is a ksp_wedge: shared = the hashes in both,
+ * dot = Σ over them of a_1(h) · a_2(h), mass_1 = Σ over them of a_1(h), mass_2 = Σ over them of a_2(h).  Per source the call also
+ * returns sum[s] = Σ a and sumsq[s] = Σ a².  A source whose exact Σ a² is >= 2^64 is refused with KSP_E_LIMIT before any probe
+ * runs; by Cauchy–Schwarz dot² <= sumsq_1 · sumsq_2, so every dot is then below 2^64, and a mass is at most its source's sum,
+ * which is at most its Σ a²: the 64-bit adds cannot wrap and there is no saturation rule.  Everything on the device is an integer,
+ * so the table is the same under every switch and schedule.
+ * Modes: KSP_QUERY_CROSS and KSP_QUERY_CROSS_AND_SELF as in query mode, except that n_db = 0 is allowed with CROSS_AND_SELF — the
+ *   pure all-pairs comparison of the queries; the database pointers may then be NULL.
+ * ksp_compare_device: keys and abundances in DEVICE memory, offsets on the host.  The rows go to d_rows (device, room for
+ *   `capacity`) in unspecified order; *n_rows = the rows found.  More than `capacity`: KSP_E_OVERFLOW, *n_rows is exact and nothing
+ *   was written past `capacity`; d_rows NULL with capacity 0 is the size query.  h_sum / h_sumsq (host, n_db + n_q values each, may
+ *   be NULL) are written once the totals are known, also by a call that overflows.  KSP_E_ARG, before a device is chosen: a NULL
+ *   pointer (the abundances, h_sum, h_sumsq and stats may be NULL; the database's keys and offsets with n_db = 0), d_rows NULL
+ *   with a capacity, n_q = 0, n_db = 0 with KSP_QUERY_CROSS, an unknown mode, offsets that do not start at 0 or decrease.
+ *   KSP_E_ARG, found on the device before any probe, naming the side and the source: a run that is not strictly ascending, an
+ *   abundance of 0.  KSP_E_LIMIT: n_db + n_q > 2^32 - 2, Σ a² >= 2^64 (naming the side and the source), a query tile of 2^31
+ *   entries or more, memory that does not fit the device's free memory (query mode's list, 4 bytes more per entry of the largest
+ *   tile for the holders' abundances, 24 per source for the totals; the message says what was asked).  On the device: a check
+ *   pass and a totals pass over both sides (Σ a² with a carry word), then per tile of at most KSP_COMPARE_TILE_MAX queries query
+ *   mode's table, one pass that puts every query entry's abundance at its holder slot, and the probe, whose LDS counters are
+ *   per query of the tile a u32 count and the u64 sums dot, mass_1, mass_2.  Read on every call: $KSP_COMPARE_TILE (1 ..
+ *   KSP_COMPARE_TILE_MAX), $KSP_COMPARE_LONG_RUN (default KSP_QUERY_LONG_RUN), $KSP_COMPARE_LIST (1 .. KSP_COMPARE_LIST_MAX),
+ *   $KSP_COMPARE_MAX_WORKGROUPS (caps the grids; tests).  The rows are the same under each.
+ * ksp_compare_host: the same for HOST arrays: uploads, calls, retries once at the exact size, sorts the rows by (source_1,
+ *   source_2) on the device and returns them in *rows (ksp_free).  sum / sumsq as above.  $KSP_COMPARE_FIRST_CAPACITY: the first
+ *   call's capacity (tests: forces the retry).  A device that is not there: KSP_E_HIP, "ksp_compare_host: no such device".
+ * ksp_compare_values: host only — the four derived values of a row, used by every writer.  n_i is the source's key count, kept for
+ *   symmetry with the writers' per-source tables; no output uses it.  out[0] cosine = (double)dot / (sqrt((double)sumsq_1) ·
+ *   sqrt((double)sumsq_2)), clamped to 1, and exactly 1 when dot² == sumsq_1 · sumsq_2 in 128-bit arithmetic (identical samples);
+ *   out[1] angular = 1 − 2·acos(cosine)/π; out[2] weighted containment 1 = mass_1 / sum_1, the share of source 1's k-mer mass
+ *   that lies on hashes source 2 also has; out[3] = mass_2 / sum_2.  KSP_E_ARG for a NULL pointer or a total of 0.
+ * kspider_compare: `samples` is a directory of .sig / .sig.gz files (or whatever kspider_query takes; only signatures carry
+ *   abundances, one without counts as all ones); `against` is NULL — every pair of samples — or a database, a directory or a
+ *   pack file, flat or counted: then only database x sample rows.  Writes OUT.namesMap and OUT_kSpider_seqToKmersNo.tsv as
+ *   kspider_query does (database ids first) and OUT_kSpider_compare.tsv: a header line, then per row source_1, source_2 (ids),
+ *   shared_kmers, dot, mass_1, mass_2 in decimal and cosine, angular_similarity, weighted_containment_1, weighted_containment_2
+ *   from ksp_compare_values printed "%.6g", sorted by (source_1, source_2).  flags KSP_COMPARE_MATRIX, without `against` only
+ *   (else KSP_E_ARG): also OUT_kSpider_compare_matrix.csv — the names in the header line, then N rows of N angular similarities,
+ *   1 on the diagonal, 0 where there is no row, symmetric, the TSV's text; KSP_E_LIMIT above KSP_COMPARE_MATRIX_MAX samples.
+ *   Files go through .partial and a rename; a refused or failed call writes none.  Device = $KSPIDER_DEVICE (default 0).        */
+#define KSP_COMPARE_TILE_MAX 512u     /* 14 KiB of counters per probe source in LDS: 28 bytes per query */
+#define KSP_COMPARE_LIST_MAX 256u
+#define KSP_COMPARE_MATRIX 1ull
+#define KSP_COMPARE_MATRIX_MAX 16384u
+typedef struct ksp_wedge {
+    uint32_t source_1, source_2;
+    uint64_t shared;   /* hashes in both                                   */
+    uint64_t dot;      /* sum over shared hashes of a_1(h) * a_2(h)         */
+    uint64_t mass_1;   /* sum over shared hashes of a_1(h)                  */
+    uint64_t mass_2;   /* sum over shared hashes of a_2(h)                  */
+} ksp_wedge;           /* 40 bytes */
+typedef struct ksp_compare_stats {
+    uint64_t n_db, n_q;
+    uint64_t db_entries, q_entries;
+    uint64_t table_keys, table_holders;   /* as in ksp_query_stats, summed over the tiles                     */
+    uint64_t passes;
+    uint64_t short_sources, long_sources;
+    uint64_t list_overflows;
+    uint64_t edges;            /* the rows found                                                       */
+    uint64_t long_run;
+    float ms_table, ms_probe;  /* HIP-event times, summed over the tiles                               */
+    float ms_sort;             /* ksp_compare_host: the sort of the rows                               */
+    float ms_totals;           /* the check pass and the totals pass                                   */
+    float ms_holders;          /* the abundances to their holder slots, summed over the tiles          */
+    uint32_t tile, list_capacity, reserved;
+} ksp_compare_stats;   /* 128 bytes */
+int ksp_compare_device(int device, const uint64_t* d_db_keys, const uint32_t* d_db_abund, const uint64_t* h_db_offsets, uint32_t n_db,
+                       const uint64_t* d_q_keys, const uint32_t* d_q_abund, const uint64_t* h_q_offsets, uint32_t n_q, int mode,
+                       ksp_wedge* d_rows, uint64_t capacity, uint64_t* n_rows, uint64_t* h_sum, uint64_t* h_sumsq, ksp_compare_stats* stats);
+int ksp_compare_host(const uint64_t* db_keys, const uint32_t* db_abund, const uint64_t* db_offsets, uint32_t n_db, const uint64_t* q_keys,
+                     const uint32_t* q_abund, const uint64_t* q_offsets, uint32_t n_q, int mode, int device, ksp_wedge** rows, uint64_t* n_rows,
+                     uint64_t* sum, uint64_t* sumsq, ksp_compare_stats* stats);
+int ksp_compare_values(const ksp_wedge* row, uint64_t n_1, uint64_t sum_1, uint64_t sumsq_1, uint64_t n_2, uint64_t sum_2, uint64_t sumsq_2,
+                       double out[4]);
+int kspider_compare(const char* samples, const char* against, int kSize, const char* out_prefix, int user_threads, uint64_t flags);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

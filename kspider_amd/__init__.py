@@ -13,6 +13,7 @@ Host-side mirror of the reference interface for this one path:
   kspider_amd.query(db, queries, kSize, out_prefix, threads, mode)  new sketches against a database, without the N x N join
   kspider_amd.gather(db, queries, kSize, out_prefix, threads, min_hashes, max_matches)  what each query is made of: greedy set cover
   kspider_amd.gather_abund(db, queries, kSize, out_prefix, threads, min_hashes, max_matches)  the same for signatures with abundances: weighted columns
+  kspider_amd.compare(samples, kSize, out_prefix, threads, against, matrix)  counted sketches against each other: cosine, angular similarity, weighted containment
   kspider_amd.pack(sketch_dir, kSize, out_path, threads)  a directory of sketches as one database file
   kspider_amd.sketch_files(input, kSize, scaled, out_dir, threads)  FASTA / FASTQ in, sourmash-compatible .sig files out, hashed on the GPU
       (moltype="protein" | "dayhoff" | "hp", translate=True: protein sketches of proteomes, or of genomes read in six frames)
@@ -31,6 +32,7 @@ from .engine import CUT_CHUNK_EDGES, edges_cut, pairwise_cut, pairwise_host_cut 
 from .engine import QUERY_CROSS, QUERY_CROSS_AND_SELF, pack, query  # noqa: F401
 from .engine import GATHER_ROW_DTYPE, GatherStats, gather, gather_device, gather_host  # noqa: F401
 from .engine import GATHER_WROW_DTYPE, GatherWRow, gather_abund, gather_abund_device, gather_abund_host, sig_read  # noqa: F401
+from .engine import WEDGE_DTYPE, CompareStats, Wedge, compare, compare_device, compare_host, compare_values  # noqa: F401
 from .engine import SketchStats, sketch_cpu, sketch_device, sketch_files, sketch_host, sketch_max_hash  # noqa: F401
 from .engine import sketch_cpu_abund, sketch_device_abund, sketch_host_abund  # noqa: F401
 from .engine import sketch_cpu_mol, sketch_device_mol, sketch_host_mol, sketch_text_hash  # noqa: F401
@@ -39,6 +41,7 @@ __all__ = ["pairwise", "pairwise_sigs", "pairwise_bins", "cluster", "estimate_an
            "query", "pack", "QUERY_CROSS", "QUERY_CROSS_AND_SELF",
            "gather", "gather_host", "gather_device", "GatherStats", "GATHER_ROW_DTYPE",
            "gather_abund", "gather_abund_host", "gather_abund_device", "GatherWRow", "GATHER_WROW_DTYPE", "sig_read",
+           "compare", "compare_host", "compare_device", "compare_values", "CompareStats", "Wedge", "WEDGE_DTYPE",
            "sketch_cpu_abund", "sketch_host_abund", "sketch_device_abund",
            "sketch_cpu_mol", "sketch_host_mol", "sketch_device_mol", "sketch_text_hash",
            "sketch_files", "sketch_host", "sketch_device", "sketch_cpu", "sketch_max_hash", "SketchStats",

@@ -140,6 +140,16 @@ int ksp_gather_abund_device(int, const uint64_t*, const uint64_t*, uint32_t, con
     ksp::set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }
+int ksp_compare_host(const uint64_t*, const uint32_t*, const uint64_t*, uint32_t, const uint64_t*, const uint32_t*, const uint64_t*, uint32_t, int, int, ksp_wedge**, uint64_t*,
+                     uint64_t*, uint64_t*, ksp_compare_stats*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_compare_device(int, const uint64_t*, const uint32_t*, const uint64_t*, uint32_t, const uint64_t*, const uint32_t*, const uint64_t*, uint32_t, int, ksp_wedge*, uint64_t,
+                       uint64_t*, uint64_t*, uint64_t*, ksp_compare_stats*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
 void ksp_free(void* p) { std::free(p); }
 int ksp_engine_lists_path(const ksp_engine*, int*) {
     ksp::set_error("host-only sanitizer build: no HIP engine");

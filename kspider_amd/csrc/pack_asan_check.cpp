@@ -4,6 +4,8 @@
 //                                    exactly the reported sizes: one line "<rc> <file>" per file
 //   pack_asan_check pack DIR K OUT   kspider_pack, then the rc line
 //   pack_asan_check query DB Q K OUT kspider_query up to the device call (the stub's ksp_query_host fails), then the rc line
+//   pack_asan_check compare SAMPLES K OUT [DB]   kspider_compare (with the matrix unless DB is given) up to the device call, then
+//                                    the rc line; and ksp_compare_values on a row at the top of its range, one line of four values
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,6 +44,16 @@ int main(int argc, char** argv) {
         std::printf("rc %d %s\n", rc, rc ? ksp_last_error() : "");
         return 0;
     }
-    std::fprintf(stderr, "usage: %s read FILE... | pack DIR K OUT | query DB Q K OUT\n", argv[0]);
+    if (cmd == "compare" && (argc == 5 || argc == 6)) {
+        const int rc = kspider_compare(argv[2], argc == 6 ? argv[5] : nullptr, std::atoi(argv[3]), argv[4], 2, argc == 6 ? 0 : KSP_COMPARE_MATRIX);
+        std::printf("rc %d %s\n", rc, rc ? ksp_last_error() : "");
+        const uint64_t top = ~0ull;
+        const ksp_wedge row = {0, 1, 5, top, 10, 9};
+        double v[4] = {0, 0, 0, 0};
+        const int rv = ksp_compare_values(&row, 5, 10, top, 5, 10, top, v);
+        std::printf("values %d %.17g %.17g %.17g %.17g\n", rv, v[0], v[1], v[2], v[3]);
+        return 0;
+    }
+    std::fprintf(stderr, "usage: %s read FILE... | pack DIR K OUT | query DB Q K OUT | compare SAMPLES K OUT [DB]\n", argv[0]);
     return 2;
 }

@@ -7,6 +7,8 @@
 //   kspider_gather  database and queries as above -> OUT_kSpider_gather.tsv, the rows of ksp_gather_host (gather.hip).
 //   kspider_gather_abund  the same for a directory of query signatures with abundances: the rows of ksp_gather_abund_host, the
 //                   weighted columns behind the nine.
+//   kspider_compare samples among themselves, or against a database -> OUT_kSpider_compare.tsv (and the matrix), the rows of
+//                   ksp_compare_host with the four values of ksp_compare_values, which is here too.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -415,4 +417,139 @@ extern "C" int kspider_gather(const char* db, const char* queries, int kSize, co
 
 extern "C" int kspider_gather_abund(const char* db, const char* queries, int kSize, const char* out_prefix, int user_threads, uint32_t min_hashes, uint32_t max_matches) {
     return gather_files("kspider_gather_abund", true, db, queries, kSize, out_prefix, user_threads, min_hashes, max_matches);
+}
+
+extern "C" int ksp_compare_values(const ksp_wedge* row, uint64_t /*n_1*/, uint64_t sum_1, uint64_t sumsq_1, uint64_t /*n_2*/, uint64_t sum_2, uint64_t sumsq_2, double out[4]) {
+    if (!row || !out) { ksp::set_error("ksp_compare_values: NULL argument"); return KSP_E_ARG; }
+    if (!sum_1 || !sumsq_1 || !sum_2 || !sumsq_2) { ksp::set_error("ksp_compare_values: a source's total is 0"); return KSP_E_ARG; }
+    typedef unsigned __int128 u128;
+    const bool same = (u128)row->dot * row->dot == (u128)sumsq_1 * sumsq_2;   // the vectors are parallel: exactly 1, whatever the roots round to
+    const double cosine = same ? 1.0 : std::min(1.0, (double)row->dot / (std::sqrt((double)sumsq_1) * std::sqrt((double)sumsq_2)));
+    out[0] = cosine;
+    out[1] = 1.0 - 2.0 * std::acos(cosine) / 3.14159265358979323846;
+    out[2] = (double)row->mass_1 / (double)sum_1;
+    out[3] = (double)row->mass_2 / (double)sum_2;
+    return KSP_OK;
+}
+
+namespace {
+
+// The sources of a loaded side as ksp_compare_host takes them: source s is the side's s-th group that has a sketch (group_of[s]),
+// and abund is empty for a side without any counted sketch, else parallel to the keys with 1 for every hash of a flat sketch.
+struct CompareSide {
+    ksp::SketchSet set;
+    std::vector<uint64_t> group_of;
+    std::vector<uint32_t> abund;
+    void load(const std::string& path, const int kSize, const int threads) {
+        load_side(path, kSize, threads, set);
+        for (uint64_t g = 0; g < set.names.size(); ++g)
+            if (set.present[g]) group_of.push_back(g);
+        if (set.abund.empty()) return;
+        if (set.abund.size() != set.keys.size()) throw std::runtime_error("the abundances of " + path + " are not parallel to their hashes");
+        abund = set.abund;
+        for (size_t s = 0; s < group_of.size(); ++s)
+            if (!set.counted[group_of[s]]) std::fill(abund.begin() + (std::ptrdiff_t)set.offsets[s], abund.begin() + (std::ptrdiff_t)set.offsets[s + 1], 1u);
+    }
+    uint32_t n() const { return (uint32_t)group_of.size(); }
+};
+
+}  // namespace
+
+extern "C" int kspider_compare(const char* samples, const char* against, int kSize, const char* out_prefix, int user_threads, uint64_t flags) {
+    const char* who = "kspider_compare";
+    if (!samples || !out_prefix || !*out_prefix) { ksp::set_error(std::string(who) + ": samples and out_prefix are required"); return KSP_E_ARG; }
+    if (kSize < 0) { ksp::set_error(std::string(who) + ": kSize is the signatures' ksize, or 0 for .bin sketches"); return KSP_E_ARG; }
+    if (flags & ~KSP_COMPARE_MATRIX) { ksp::set_error(std::string(who) + ": unknown flags"); return KSP_E_ARG; }
+    const bool matrix = (flags & KSP_COMPARE_MATRIX) != 0;
+    if (matrix && against) { ksp::set_error(std::string(who) + ": the matrix is of the samples among themselves, not of samples against a database"); return KSP_E_ARG; }
+    return guarded(who, [&]() {
+        const int threads = user_threads < 1 ? 1 : user_threads;
+        const std::string prefix = out_prefix;
+        CompareSide side[2];   // [0] the database (empty without `against`), [1] the samples
+        if (against) side[0].load(against, kSize, threads);
+        side[1].load(samples, kSize, threads);
+        const uint64_t G0 = side[0].set.names.size(), G1 = side[1].set.names.size(), G = G0 + G1;
+        if (G > 0xFFFFFFFEull) throw std::runtime_error("more than 2^32 - 2 groups");
+        if (against && side[0].n() == 0) throw ArgError("the database has no sketch");
+        if (side[1].n() == 0) throw ArgError("there is no sample sketch");
+        if (matrix && G1 > KSP_COMPARE_MATRIX_MAX) {
+            ksp::set_error(std::string(who) + ": a matrix of " + std::to_string(G1) + " samples (the limit is " + std::to_string(KSP_COMPARE_MATRIX_MAX) + ")");
+            return (int)KSP_E_LIMIT;
+        }
+        const uint32_t n_db = side[0].n(), n_q = side[1].n();
+        ksp_wedge* rows = nullptr;
+        uint64_t n_rows = 0;
+        ksp_compare_stats st;
+        std::vector<uint64_t> sum((size_t)n_db + n_q), sumsq((size_t)n_db + n_q);
+        const char* dv = std::getenv("KSPIDER_DEVICE");
+        const int rc = ksp_compare_host(n_db ? side[0].set.keys.data() : nullptr, side[0].abund.empty() ? nullptr : side[0].abund.data(), n_db ? side[0].set.offsets.data() : nullptr, n_db,
+                                        side[1].set.keys.data(), side[1].abund.empty() ? nullptr : side[1].abund.data(), side[1].set.offsets.data(), n_q,
+                                        against ? KSP_QUERY_CROSS : KSP_QUERY_CROSS_AND_SELF, dv ? std::atoi(dv) : 0, &rows, &n_rows, sum.data(), sumsq.data(), &st);
+        if (rc != KSP_OK) return rc;
+        // source s of the call -> its side, its index there, its id in the union: database 1 .. N, samples N + 1 .. N + Q
+        const auto id_of = [&](const uint32_t s) { return (uint32_t)(s < n_db ? side[0].group_of[s] + 1 : G0 + side[1].group_of[s - n_db] + 1); };
+        const auto keys_of = [&](const uint32_t s) {
+            const std::vector<uint64_t>& off = s < n_db ? side[0].set.offsets : side[1].set.offsets;
+            const uint32_t i = s < n_db ? s : s - n_db;
+            return off[i + 1] - off[i];
+        };
+        std::string text = "source_1\tsource_2\tshared_kmers\tdot\tmass_1\tmass_2\tcosine\tangular_similarity\tweighted_containment_1\tweighted_containment_2\n";
+        std::vector<float> cells;   // the matrix, by group of the samples
+        if (matrix) {
+            cells.assign((size_t)G1 * G1, 0.0f);
+            for (uint64_t g = 0; g < G1; ++g) cells[(size_t)(g * G1 + g)] = 1.0f;
+        }
+        char buf[256];
+        for (uint64_t i = 0; i < n_rows; ++i) {   // ids ascend with the source numbers, so the rows stay sorted
+            const ksp_wedge& r = rows[i];
+            double v[4];
+            if (ksp_compare_values(&r, keys_of(r.source_1), sum[r.source_1], sumsq[r.source_1], keys_of(r.source_2), sum[r.source_2], sumsq[r.source_2], v) != KSP_OK) {
+                ksp_free(rows);
+                throw std::runtime_error("a row names a source without abundance");
+            }
+            char angular[32];
+            std::snprintf(angular, sizeof angular, "%.6g", v[1]);
+            const int n = std::snprintf(buf, sizeof buf, "%u\t%u\t%llu\t%llu\t%llu\t%llu\t%.6g\t%s\t%.6g\t%.6g\n", id_of(r.source_1), id_of(r.source_2), (unsigned long long)r.shared,
+                                        (unsigned long long)r.dot, (unsigned long long)r.mass_1, (unsigned long long)r.mass_2, v[0], angular, v[2], v[3]);
+            text.append(buf, (size_t)n);
+            if (matrix) {   // six significant digits survive a float, so "%.6g" of the cell is the TSV's text again
+                const uint64_t a = side[1].group_of[r.source_1], b = side[1].group_of[r.source_2];
+                cells[(size_t)(a * G1 + b)] = cells[(size_t)(b * G1 + a)] = std::strtof(angular, nullptr);
+            }
+        }
+        ksp_free(rows);
+        // the files only now: a refused or failed call leaves none
+        ksp::IndexData ix;
+        for (int s = 0; s < 2; ++s)
+            for (const uint64_t g : side[s].group_of) ix.kmer_slots.emplace_back((uint32_t)((s ? G0 : 0) + g + 1), side[s].set.kmers[g]);
+        {
+            std::ofstream f;
+            ksp::PartialFiles files;
+            files.open(prefix + ".namesMap", f);
+            f << G << "\n";
+            for (int s = 0; s < 2; ++s)
+                for (uint64_t g = 0; g < side[s].set.names.size(); ++g) f << (s ? G0 : 0) + g + 1 << " " << side[s].set.names[g] << "\n";
+            files.commit();
+        }
+        ksp::write_seq_to_kmers(prefix, ix);
+        ksp::write_file_atomically(prefix + "_kSpider_compare.tsv", text);
+        if (matrix) {
+            std::string csv;
+            for (uint64_t g = 0; g < G1; ++g) csv += (g ? "," : "") + side[1].set.names[g];
+            csv += "\n";
+            for (uint64_t a = 0; a < G1; ++a) {
+                for (uint64_t b = 0; b < G1; ++b) {
+                    const int n = std::snprintf(buf, sizeof buf, "%s%.6g", b ? "," : "", (double)cells[(size_t)(a * G1 + b)]);
+                    csv.append(buf, (size_t)n);
+                }
+                csv += "\n";
+            }
+            ksp::write_file_atomically(prefix + "_kSpider_compare_matrix.csv", csv);
+        }
+        if (std::getenv("KSPIDER_VERBOSE"))
+            std::cout << "kspider_amd: compare: " << st.n_q << " samples" << (against ? " against " + std::to_string(st.n_db) + " database sources" : std::string()) << ", "
+                      << st.passes << " passes, " << n_rows << " rows; totals " << st.ms_totals << " ms, table " << st.ms_table << " ms, holders " << st.ms_holders
+                      << " ms, probe " << st.ms_probe << " ms" << std::endl;
+        return (int)KSP_OK;
+    });
 }

@@ -79,6 +79,13 @@ GATHER_WROW_DTYPE = np.dtype([("query", np.uint32), ("rank", np.uint32), ("sourc
                               ("remaining", np.uint32), ("w_unique", np.uint64), ("w_found", np.uint64), ("sq_lo", np.uint64), ("sq_hi", np.uint64),
                               ("median2", np.uint64)])
 
+#: compare (include/kspider_amd.h KSP_COMPARE_*): the largest tile and touched list, the matrix flag and its limit, ksp_wedge (40 bytes)
+COMPARE_TILE_MAX = 512
+COMPARE_LIST_MAX = 256
+COMPARE_MATRIX = 1
+COMPARE_MATRIX_MAX = 16384
+WEDGE_DTYPE = np.dtype([("source_1", np.uint32), ("source_2", np.uint32), ("shared", np.uint64), ("dot", np.uint64), ("mass_1", np.uint64), ("mass_2", np.uint64)])
+
 #: the sketcher (csrc/sketcher.hip): positions per tile of the hash pass; the flags of kspider_sketch
 SKETCH_TILE_BASES = 4096
 SKETCH_PER_RECORD, SKETCH_SEED, SKETCH_ABUND = 1, 2, 4
@@ -121,6 +128,7 @@ ABI_SYMBOLS = [
     "ksp_query_device", "ksp_query_host", "ksp_query_directory", "kspider_pack", "ksp_pack_info", "ksp_pack_load", "kspider_query",
     "ksp_gather_device", "ksp_gather_host", "kspider_gather",
     "ksp_gather_abund_device", "ksp_gather_abund_host", "kspider_gather_abund",
+    "ksp_compare_device", "ksp_compare_host", "ksp_compare_values", "kspider_compare",
     "ksp_sketch_cpu_abund", "ksp_sketch_device_abund", "ksp_sketch_host_abund", "ksp_sig_read",
     "ksp_sketch_max_hash", "ksp_murmur64", "ksp_sketch_kmer_hash", "ksp_sketch_cpu", "ksp_sketch_device", "ksp_sketch_host",
     "ksp_fastx_info", "ksp_fastx_load", "kspider_sketch",
@@ -159,6 +167,27 @@ class QueryStats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class CompareStats(ctypes.Structure):
+    """ksp_compare_stats (include/kspider_amd.h): 128 bytes."""
+    _fields_ = [
+        ("n_db", ctypes.c_uint64), ("n_q", ctypes.c_uint64), ("db_entries", ctypes.c_uint64), ("q_entries", ctypes.c_uint64),
+        ("table_keys", ctypes.c_uint64), ("table_holders", ctypes.c_uint64), ("passes", ctypes.c_uint64),
+        ("short_sources", ctypes.c_uint64), ("long_sources", ctypes.c_uint64), ("list_overflows", ctypes.c_uint64),
+        ("edges", ctypes.c_uint64), ("long_run", ctypes.c_uint64),
+        ("ms_table", ctypes.c_float), ("ms_probe", ctypes.c_float), ("ms_sort", ctypes.c_float), ("ms_totals", ctypes.c_float), ("ms_holders", ctypes.c_float),
+        ("tile", ctypes.c_uint32), ("list_capacity", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class Wedge(ctypes.Structure):
+    """ksp_wedge (include/kspider_amd.h): 40 bytes."""
+    _fields_ = [("source_1", ctypes.c_uint32), ("source_2", ctypes.c_uint32), ("shared", ctypes.c_uint64), ("dot", ctypes.c_uint64), ("mass_1", ctypes.c_uint64),
+                ("mass_2", ctypes.c_uint64)]
 
 
 class GatherStats(ctypes.Structure):
@@ -386,6 +415,12 @@ def lib():
         L.ksp_gather_abund_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                             ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.kspider_gather_abund.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]
+        L.ksp_compare_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_compare_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.ksp_compare_values.argtypes = [ctypes.POINTER(Wedge)] + [ctypes.c_uint64] * 6 + [ctypes.POINTER(ctypes.c_double)]
+        L.kspider_compare.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint64]
         L.ksp_sketch_cpu_abund.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
         L.ksp_sketch_device_abund.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64,
@@ -1159,6 +1194,64 @@ def gather_abund(db: str, queries: str, kSize: int, out_prefix: str, user_thread
     total_weighted_hashes."""
     _check(lib().kspider_gather_abund(os.fsencode(db), os.fsencode(queries), int(kSize), os.fsencode(out_prefix) if out_prefix else None, int(user_threads),
                                       int(min_hashes), int(max_matches)))
+
+
+def _u32(a):
+    """A contiguous uint32 array, or None for None."""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def compare_host(db_keys, db_abund, db_offsets, q_keys, q_abund, q_offsets, mode: int = QUERY_CROSS_AND_SELF, device: int = 0):
+    """Counted sketches against each other (ksp_compare_host) -> (rows of WEDGE_DTYPE sorted by (source_1, source_2), sum, sumsq,
+    stats).  Sources are numbered as in query_host; an abundance array is parallel to its keys, None stands for all ones.  With
+    mode QUERY_CROSS_AND_SELF the database may be None, None, None: every pair of the queries.  sum / sumsq: per source, Σ a and
+    Σ a² as uint64 (a source with Σ a² >= 2^64 is refused with KSP_E_LIMIT)."""
+    dk, do, qk, qo = _u64(db_keys), _u64(db_offsets), _u64(q_keys), _u64(q_offsets)
+    da, qa = _u32(db_abund), _u32(q_abund)
+    n = _n_sketches(do) + _n_sketches(qo)
+    total, sq = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    out = ctypes.c_void_p()
+    nr = ctypes.c_uint64(0)
+    st = CompareStats()
+    _check(lib().ksp_compare_host(_ptr(dk), _ptr(da), _ptr(do), _n_sketches(do), _ptr(qk), _ptr(qa), _ptr(qo), _n_sketches(qo), int(mode), int(device),
+                                  ctypes.byref(out), ctypes.byref(nr), total.ctypes.data, sq.ctypes.data, ctypes.byref(st)))
+    rows = _take(out, nr.value, WEDGE_DTYPE)
+    return rows, total[:n].copy(), sq[:n].copy(), st.as_dict()
+
+
+def compare_device(d_db_keys_ptr: int, d_db_abund_ptr: int, db_offsets, d_q_keys_ptr: int, d_q_abund_ptr: int, q_offsets, d_rows_ptr: int, capacity: int,
+                   mode: int = QUERY_CROSS_AND_SELF, device: int = 0) -> tuple:
+    """ksp_compare_device: keys and abundances in DEVICE memory (an abundance pointer of 0 / None: all ones), offsets on the host,
+    rows of 40 bytes into d_rows (room for `capacity`; 0 / 0: the size query).  -> (rc, n_rows, sum, sumsq, stats): rc is KSP_OK or
+    KSP_E_OVERFLOW (n_rows is then the required size); anything else raises."""
+    do, qo = _u64(db_offsets), _u64(q_offsets)
+    n = _n_sketches(do) + _n_sketches(qo)
+    total, sq = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    nr = ctypes.c_uint64(0)
+    st = CompareStats()
+    rc = lib().ksp_compare_device(int(device), d_db_keys_ptr or None, d_db_abund_ptr or None, _ptr(do), _n_sketches(do), d_q_keys_ptr or None, d_q_abund_ptr or None,
+                                  _ptr(qo), _n_sketches(qo), int(mode), d_rows_ptr or None, int(capacity), ctypes.byref(nr), total.ctypes.data, sq.ctypes.data,
+                                  ctypes.byref(st))
+    if rc not in (KSP_OK, KSP_E_OVERFLOW):
+        _check(rc)
+    return rc, nr.value, total[:n].copy(), sq[:n].copy(), st.as_dict()
+
+
+def compare_values(row, n_1: int, sum_1: int, sumsq_1: int, n_2: int, sum_2: int, sumsq_2: int) -> tuple:
+    """(cosine, angular similarity, weighted containment 1, weighted containment 2) of a row (a WEDGE_DTYPE record or a tuple of
+    its six fields) and the totals of its two sources (ksp_compare_values; host only)."""
+    w = Wedge(*(int(x) for x in (row.tolist() if hasattr(row, "tolist") else row)))
+    out = (ctypes.c_double * 4)()
+    _check(lib().ksp_compare_values(ctypes.byref(w), int(n_1), int(sum_1), int(sumsq_1), int(n_2), int(sum_2), int(sumsq_2), out))
+    return tuple(out)
+
+
+def compare(samples: str, kSize: int, out_prefix: str, user_threads: int = 1, against: str | None = None, matrix: bool = False) -> None:
+    """kspider_compare: every pair of the sample signatures in a directory — or, with `against` (a directory or a pack file), every
+    database source against every sample — as OUT_kSpider_compare.tsv beside OUT.namesMap and OUT_kSpider_seqToKmersNo.tsv; matrix
+    (without `against`): also OUT_kSpider_compare_matrix.csv, the N x N angular similarities."""
+    _check(lib().kspider_compare(os.fsencode(samples) if samples else None, os.fsencode(against) if against else None, int(kSize),
+                                 os.fsencode(out_prefix) if out_prefix else None, int(user_threads), COMPARE_MATRIX if matrix else 0))
 
 
 def sig_read(path: str, kSize: int) -> tuple:
