@@ -1168,7 +1168,12 @@ int ksp_sketch_host_mol(int device, const uint8_t* seq, uint64_t n_bytes, const 
  *   pointer (the abundances, h_sum, h_sumsq and stats may be NULL; the database's keys and offsets with n_db = 0), d_rows NULL
  *   with a capacity, n_q = 0, n_db = 0 with KSP_QUERY_CROSS, an unknown mode, offsets that do not start at 0 or decrease.
  *   KSP_E_ARG, found on the device before any probe, naming the side and the source: a run that is not strictly ascending, an
- *   abundance of 0.  KSP_E_LIMIT: n_db + n_q > 2^32 - 2, Σ a² >= 2^64 (naming the side and the source), a query tile of 2^31
+ *   abundance of 0.  Of several such sources the smallest in the common numbering is named, and a run out of order anywhere is
+ *   reported before an abundance of 0 anywhere, also in a smaller source.  A run ascends inside its source only: it may end above
+ *   or at the first key of the next.  A source may be empty: its totals are 0 and 0 and no row names it.  A side whose sources
+ *   are all empty is accepted too (its key pointer is not NULL and is not read): all queries empty gives no row, the totals of every source and
+ *   KSP_OK, and no table is built (stats.passes = 0).
+ *   KSP_E_LIMIT: n_db + n_q > 2^32 - 2, Σ a² >= 2^64 (naming the side and the smallest such source), a query tile of 2^31
  *   entries or more, memory that does not fit the device's free memory (query mode's list, 4 bytes more per entry of the largest
  *   tile for the holders' abundances, 24 per source for the totals; the message says what was asked).  On the device: a check
  *   pass and a totals pass over both sides (Σ a² with a carry word), then per tile of at most KSP_COMPARE_TILE_MAX queries query

@@ -3,7 +3,7 @@
 // mass_2), and per source the call returns Σ a and Σ a² (include/kspider_amd.h has the definition).  Everything is an integer.
 //
 //   check    k_compare_check, a workgroup per source of both sides: a run that is not strictly ascending, an abundance of 0 ->
-//            the smallest such source, KSP_E_ARG.
+//            the smallest such source, KSP_E_ARG; a run out of order anywhere is reported before an abundance of 0 anywhere.
 //   totals   k_compare_totals, a workgroup per source: Σ a (u64) and Σ a² with a carry word.  A carry is Σ a² >= 2^64:
 //            KSP_E_LIMIT before any probe.  Without one every dot and mass is below 2^64 and the probe's adds cannot wrap.
 //   table    per tile of at most KSP_COMPARE_TILE consecutive queries: query_table.hip.h, as query mode builds it.
