@@ -1234,6 +1234,100 @@ int ksp_compare_values(const ksp_wedge* row, uint64_t n_1, uint64_t sum_1, uint6
                        double out[4]);
 int kspider_compare(const char* samples, const char* against, int kSize, const char* out_prefix, int user_threads, uint64_t flags);
 
+/* ---- classify: every read or contig against a sketch database (csrc/classify.hip, csrc/classify_kernels.hip.h,
+ *      csrc/classify_cpu.cpp, csrc/classify_files.cpp) ----
+ * The definition.  Records are DNA with the sketcher's rules unchanged: ACGTacgt are bases, every other byte breaks k-mers, a
+ * k-mer is ksize (1 .. 64) bases inside one record, canonical form, Murmur's first word with `seed`, kept iff hash <= max_hash.
+ * The references are n_refs STRICTLY ASCENDING runs of hashes back to back with host offsets (a counted signature is read as
+ * flat).  For a record r: S(r) = the SET of its kept hashes; kept_windows(r) = the windows whose hash is kept (positions, so >=
+ * |S(r)|); hits(r, q) = |S(r) ∩ ref_q|; matched(r) = |S(r) ∩ ⋃ ref_q|.  A row (r, q, hits) exists iff hits >= min_hits (>= 1);
+ * rows are ordered by (r, q).  Per record, over its rows: n_refs_hit; best_ref = the reference of the largest hits, a tie going
+ * to the smaller index (0xFFFFFFFF: no row); best_hits; second_hits = the largest hits among the record's OTHER rows (0: none).
+ * Everything is an integer and nothing depends on scheduling.  This equals ksp_sketch_cpu per record followed by an intersection
+ * with every reference.
+ * Results of the one-shot calls and of _finish: *rows (ksp_free; never NULL after KSP_OK) with *n_rows, and six caller-owned
+ *   arrays of n_records uint32_t: kept_windows, matched, n_refs_hit, best_ref, best_hits, second_hits.
+ * ksp_classify_cpu: host only, single thread, over csrc/sketch_hash.h — the timing baseline and KSPIDER_CLASSIFY=host.
+ * ksp_classify_host: the same on `device` for HOST arrays: one session, one batch (below).
+ * The session, for a caller with batches: ksp_classify_open builds the table once; ksp_classify_add hashes one batch — n_segments
+ *   segments of the byte stream (seg_offsets[n_segments + 1], ascending from 0 to n_bytes), segment s being a piece of record
+ *   seg_records[s] (any id below 2^32 - 1; ids may repeat within and across batches).  A record cut across batches must have every
+ *   window whole in exactly one piece (cut with ksize - 1 bytes of overlap); the same hash in two pieces counts once.
+ *   ksp_classify_finish(n_records above every id added) returns the results and ends the session's work: after it only
+ *   ksp_classify_close is allowed, which frees everything and may be called at any time (NULL is ignored).
+ * On the device.  Table: query mode's collision-free table (csrc/query_table.hip.h) over ALL references, the tag being the
+ *   reference index; reference hashes above max_hash are dropped first (they can never be hit).  Hash pass (k_classify_hash):
+ *   the sketcher's tile frame — workgroups of 256 over tiles of KSP_SKETCH_TILE_BASES positions, $KSPIDER_SKETCH_MAX_WGS caps the
+ *   grid — whose survivors are compacted by ballot into a list in LDS, drained in rounds by look-ups of four keys per lane; only
+ *   hits leave the workgroup, as 64-bit words (record << 32) | table_index, one reservation per wave; the counter counts past
+ *   the capacity and nothing is written at or past it.  A kept window adds 1 to kept_windows[record].  The hit words of all
+ *   batches stay in one device buffer; a batch that does not fit first has the held words sorted and made unique (a compaction),
+ *   then the buffer grown to the counted need, and its kernel run again (a retry).  $KSPIDER_CLASSIFY_FIRST_CAPACITY: the
+ *   buffer's first capacity in words (tests).  Finish: radix sort and unique of the words (matched = words per record), every word
+ *   expanded into (record << 32) | reference for each holder of its hash, sort, run lengths = hits, the cut at min_hits and the
+ *   summary, all on the device.
+ * KSP_E_ARG, before a device is chosen: a NULL pointer (stats may be NULL; ref_keys with no reference entry; seq with n_bytes 0),
+ *   ksize outside 1 .. 64, n_records / n_segments = 0 (one-shot and _add), offsets that do not start at 0, decrease or do not end
+ *   at n_bytes, reference offsets that do not start at 0 or decrease, a reference run that is not strictly ascending (naming the
+ *   reference), min_hits = 0; _add: a record id of 2^32 - 1; _finish: n_records not above every id added; _add or _finish after
+ *   _finish.  KSP_E_LIMIT: references that hold 2^31 entries or more (after the drop above), memory that does not fit the
+ *   device's free memory (the message says how much was asked; nothing of that step has run, and a refused _add leaves the
+ *   session as it was).  A device that is not there: KSP_E_HIP, "ksp_classify_open: no such device".
+ * kspider_classify: the file driver.  input: one FASTA / FASTQ file or a directory (the sketcher's endings and glob order); EVERY
+ *   record is a unit, its id its 1-based ordinal over the whole input; names may repeat.  db: a directory of .sig / .sig.gz files,
+ *   or a pack file (kspider_pack); a group without a sketch of that kSize is never hit.  max_hash = ksp_sketch_max_hash(scaled),
+ *   seed 42.  Batches of at most $KSPIDER_CLASSIFY_BATCH_MB (256; $KSPIDER_CLASSIFY_BATCH_BYTES: the same in bytes, at least 1024)
+ *   through pinned staging, the next batch being read while the device works; a record longer than a batch is cut with ksize - 1
+ *   bytes of overlap and the result does not depend on the batch size.  KSPIDER_CLASSIFY=host: the same driver over the host
+ *   loop, no GPU.  Device = $KSPIDER_DEVICE (0).  KSPIDER_VERBOSE prints one line of the stats.  Writes, each through .partial and
+ *   a rename, after everything was computed:
+ *     OUT_kSpider_classify.tsv       record_id name length kept_windows matched n_refs best_ref best_hits second_hits — a header
+ *                                    line, then one row per record in input order; best_ref is the reference's name, "-" for none;
+ *                                    length = the bytes of the record's sequence
+ *     OUT_kSpider_classify_hits.tsv  record_id name ref_id ref_name hits — a header line, then the rows by (record_id, ref_id);
+ *                                    ref_id is the group's 1-based position in the database
+ *   KSP_E_ARG: NULL or empty input / db / out_prefix, kSize outside 1 .. 64, scaled = 0, min_hits = 0, KSPIDER_CLASSIFY other than
+ *   "host" / "device"; KSP_E_IO: no input file, a reader error, a database that cannot be read, a file that cannot be written. */
+typedef struct ksp_classify_row {
+    uint32_t record, reference, hits, reserved;
+} ksp_classify_row;   /* 16 bytes */
+typedef struct ksp_classify_stats {
+    uint64_t bases;            /* base bytes of all batches (an overlap of a cut record counts in both pieces)          */
+    uint64_t valid_kmers;      /* windows of ksize bases without a break byte, as in ksp_sketch_stats: the device counts
+                                  one over a record boundary that no break byte marks (and drops it), the host loop does not */
+    uint64_t kept_windows;     /* windows inside a record with hash <= max_hash: the sum of kept_windows[]               */
+    uint64_t hit_words;        /* hit words appended by all batches (a retried batch counts once)                        */
+    uint64_t hit_words_unique; /* distinct (record, table key) pairs: the sum of matched[]                               */
+    uint64_t table_keys;       /* distinct reference hashes <= max_hash                                                  */
+    uint64_t table_holders;    /* (hash, reference) pairs of the table                                                   */
+    uint64_t batches;          /* ksp_classify_add calls that ran                                                        */
+    uint64_t retries;          /* batches whose kernel ran a second time                                                 */
+    uint64_t compactions;      /* sort + unique of the held words because a batch did not fit                            */
+    uint64_t workgroups;       /* the largest grid of a hash pass                                                        */
+    uint64_t rows;             /* rows returned                                                                          */
+    float ms_table, ms_hash, ms_finish;   /* HIP-event times: the table; the hash passes, summed; the finish (0 on the host) */
+    uint32_t reserved;
+} ksp_classify_stats;   /* 112 bytes */
+typedef struct ksp_classify ksp_classify;
+int ksp_classify_cpu(const uint8_t* seq, uint64_t n_bytes, const uint64_t* rec_offsets, uint32_t n_records, int ksize, uint64_t max_hash,
+                     uint32_t seed, const uint64_t* ref_keys, const uint64_t* ref_offsets, uint32_t n_refs, uint32_t min_hits,
+                     ksp_classify_row** rows, uint64_t* n_rows, uint32_t* kept_windows, uint32_t* matched, uint32_t* n_refs_hit,
+                     uint32_t* best_ref, uint32_t* best_hits, uint32_t* second_hits, ksp_classify_stats* stats);
+int ksp_classify_host(int device, const uint8_t* seq, uint64_t n_bytes, const uint64_t* rec_offsets, uint32_t n_records, int ksize,
+                      uint64_t max_hash, uint32_t seed, const uint64_t* ref_keys, const uint64_t* ref_offsets, uint32_t n_refs,
+                      uint32_t min_hits, ksp_classify_row** rows, uint64_t* n_rows, uint32_t* kept_windows, uint32_t* matched,
+                      uint32_t* n_refs_hit, uint32_t* best_ref, uint32_t* best_hits, uint32_t* second_hits, ksp_classify_stats* stats);
+int ksp_classify_open(int device, int ksize, uint64_t max_hash, uint32_t seed, const uint64_t* ref_keys, const uint64_t* ref_offsets,
+                      uint32_t n_refs, ksp_classify** out);
+int ksp_classify_add(ksp_classify* c, const uint8_t* seq, uint64_t n_bytes, const uint64_t* seg_offsets, const uint32_t* seg_records,
+                     uint32_t n_segments);
+int ksp_classify_finish(ksp_classify* c, uint32_t n_records, uint32_t min_hits, ksp_classify_row** rows, uint64_t* n_rows,
+                        uint32_t* kept_windows, uint32_t* matched, uint32_t* n_refs_hit, uint32_t* best_ref, uint32_t* best_hits,
+                        uint32_t* second_hits, ksp_classify_stats* stats);
+void ksp_classify_close(ksp_classify* c);
+int kspider_classify(const char* input, int kSize, uint64_t scaled, const char* db, const char* out_prefix, int user_threads,
+                     uint32_t min_hits);
+
 /* ---- host-only diagnostics (no GPU needed) -------------------------------------------
  * ksp_index_info: parse the three index files and report what the reader detected:
  * out[0] colours, out[1] groups, out[2] colour-count entries, out[3] sum of sources over

@@ -228,6 +228,32 @@ struct FastxFile {
     bool fastq = false;
 };
 void read_fastx(const std::string& path, FastxFile& out);
+// ---- classify (classify_cpu.cpp, classify.hip, classify_files.cpp) ----
+// what the classify calls refuse with KSP_E_ARG about their references: NULL offsets, NULL keys with an entry, ksize outside
+// 1 .. 64, offsets that do not start at 0 or decrease, a run that is not strictly ascending (naming the reference)
+int check_classify_refs(const char* who, int ksize, const uint64_t* ref_keys, const uint64_t* ref_offsets, uint32_t n_refs);
+// ... and about a batch: NULL pointers, no segment, offsets that do not start at 0, decrease or do not end at n_bytes, a record
+// id of 2^32 - 1 (seg_records NULL: segment s is record s)
+int check_classify_batch(const char* who, const void* seq, uint64_t n_bytes, const uint64_t* seg_offsets, const uint32_t* seg_records, uint32_t n_segments);
+// ... and about the results: a NULL pointer, min_hits = 0
+int check_classify_out(const char* who, uint32_t min_hits, const void* rows, const void* n_rows, const void* kept_windows, const void* matched, const void* n_refs_hit,
+                       const void* best_ref, const void* best_hits, const void* second_hits);
+// The host loop's session: the form of ksp_classify_open / _add / _finish on the host, single thread, for ksp_classify_cpu and
+// the file driver's host mode.  Arguments are checked by the caller; the methods return a KSP_* code and never throw.
+class ClassifyCpu {
+    struct State;
+    State* s_ = nullptr;
+
+public:
+    ClassifyCpu() = default;
+    ClassifyCpu(const ClassifyCpu&) = delete;
+    ClassifyCpu& operator=(const ClassifyCpu&) = delete;
+    ~ClassifyCpu();
+    int open(const char* who, int ksize, uint64_t max_hash, uint32_t seed, const uint64_t* ref_keys, const uint64_t* ref_offsets, uint32_t n_refs);
+    int add(const char* who, const uint8_t* seq, const uint64_t* seg_offsets, const uint32_t* seg_records, uint32_t n_segments);
+    int finish(const char* who, uint32_t n_records, uint32_t min_hits, ksp_classify_row** rows, uint64_t* n_rows, uint32_t* kept_windows, uint32_t* matched,
+               uint32_t* n_refs_hit, uint32_t* best_ref, uint32_t* best_hits, uint32_t* second_hits, ksp_classify_stats* stats);
+};
 }
 
 extern "C" {

@@ -150,6 +150,19 @@ int ksp_compare_device(int, const uint64_t*, const uint32_t*, const uint64_t*, u
     ksp::set_error("host-only sanitizer build: no HIP engine");
     return KSP_E_HIP;
 }
+int ksp_classify_open(int, int, uint64_t, uint32_t, const uint64_t*, const uint64_t*, uint32_t, ksp_classify**) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_classify_add(ksp_classify*, const uint8_t*, uint64_t, const uint64_t*, const uint32_t*, uint32_t) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+int ksp_classify_finish(ksp_classify*, uint32_t, uint32_t, ksp_classify_row**, uint64_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, ksp_classify_stats*) {
+    ksp::set_error("host-only sanitizer build: no HIP engine");
+    return KSP_E_HIP;
+}
+void ksp_classify_close(ksp_classify*) {}
 void ksp_free(void* p) { std::free(p); }
 int ksp_engine_lists_path(const ksp_engine*, int*) {
     ksp::set_error("host-only sanitizer build: no HIP engine");

@@ -14,6 +14,7 @@
 #include "engine_internal.h"
 #include "sketch_hash.h"
 #include "sketch_mol.h"
+#include "sketch_windows.h"
 
 namespace sk = ksp_sketch;
 
@@ -66,21 +67,7 @@ int sketch_cpu_frame(const char* who, const bool counted, const uint8_t* seq, co
     }
 }
 
-// The rolling window of the DNA loops: full(left) for every `win` (1 .. 64) consecutive bases among the bytes [first, last), `left`
-// being them left-aligned; a byte that is no base starts the window over.
-template <class Full>
-void each_base_window(const uint8_t* seq, const uint64_t first, const uint64_t last, const unsigned win, Full full) {
-    sk::Kmer fw{0, 0};   // the last min(have, win) bases, right-aligned
-    unsigned have = 0;   // bases since the last break, capped at win
-    for (uint64_t p = first; p < last; ++p) {
-        const unsigned c = seq[p];
-        if (!sk::is_base(c)) { have = 0; fw = sk::Kmer{0, 0}; continue; }
-        fw = sk::shift_left(fw, 2);
-        fw.lo |= sk::base_code(c);
-        if (have < win) ++have;
-        if (have == win) full(sk::shift_left(fw, 128 - 2 * win));   // (drops the bases older than win)
-    }
-}
+using sk::each_base_window;   // (sketch_windows.h: the rolling window of the DNA loops)
 
 // ksp_sketch_cpu and, with counts, ksp_sketch_cpu_abund: every window of k bases, canonical form, hashed
 int sketch_cpu(const char* who, const bool counted, const uint8_t* seq, const uint64_t n_bytes, const uint64_t* src_offsets, const uint32_t n_sources, const int ksize,

@@ -132,6 +132,7 @@ __device__ __forceinline__ void append_survivors(const HashArgs& A, const u32 la
     }
 }
 
+#ifndef KSP_SKETCH_PARTS_ONLY   // (classify.hip takes the parts above and brings its own frame: classify_kernels.hip.h)
 // The frame.  s_mask: kMaskWords of LDS; win: the positions of a window.  stage(c, w) puts the 16 bytes w of piece c into the
 // kernel's LDS and returns their break bits; hashes(p, h) writes the kHashes hashes of the unbroken window at tile position p.
 template <u32 kHashes, class Stage, class Hashes>
@@ -251,3 +252,4 @@ __global__ __launch_bounds__(kThreads) void k_sketch_hash_translated(const MolAr
             h[1] = sk::letters_hash<3>(w, A.k, A.seed);
         });
 }
+#endif

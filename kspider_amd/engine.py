@@ -94,6 +94,10 @@ MOL_DNA, MOL_PROTEIN, MOL_DAYHOFF, MOL_HP = 0, 1, 2, 3
 SKETCH_PROTEIN, SKETCH_DAYHOFF, SKETCH_HP, SKETCH_TRANSLATE = 8, 16, 32, 64
 _MOLTYPES = {"dna": MOL_DNA, "protein": MOL_PROTEIN, "dayhoff": MOL_DAYHOFF, "hp": MOL_HP}
 
+#: classify (csrc/classify.hip): a row of the hits table; "no reference" in best_ref
+CLASSIFY_ROW_DTYPE = np.dtype([("record", np.uint32), ("reference", np.uint32), ("hits", np.uint32), ("reserved", np.uint32)])
+CLASSIFY_NO_REF = 0xFFFFFFFF
+
 #: ksp_engine_lists_path / Engine.lists_path
 LISTS_NONE, LISTS_KEYED, LISTS_COMPACTED, LISTS_SORTED, LISTS_FUSED = 0, 1, 2, 3, 4
 
@@ -133,6 +137,7 @@ ABI_SYMBOLS = [
     "ksp_sketch_max_hash", "ksp_murmur64", "ksp_sketch_kmer_hash", "ksp_sketch_cpu", "ksp_sketch_device", "ksp_sketch_host",
     "ksp_fastx_info", "ksp_fastx_load", "kspider_sketch",
     "ksp_sketch_text_hash", "ksp_sketch_cpu_mol", "ksp_sketch_device_mol", "ksp_sketch_host_mol",
+    "ksp_classify_cpu", "ksp_classify_host", "ksp_classify_open", "ksp_classify_add", "ksp_classify_finish", "ksp_classify_close", "kspider_classify",
 ]
 
 
@@ -219,6 +224,19 @@ class SketchStats(ctypes.Structure):
         ("bases", ctypes.c_uint64), ("valid_kmers", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("distinct_out", ctypes.c_uint64),
         ("needed", ctypes.c_uint64), ("workgroups", ctypes.c_uint64), ("retries", ctypes.c_uint64),
         ("ms_upload", ctypes.c_float), ("ms_hash", ctypes.c_float), ("ms_select", ctypes.c_float), ("reserved", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class ClassifyStats(ctypes.Structure):
+    """ksp_classify_stats (include/kspider_amd.h): 112 bytes."""
+    _fields_ = [
+        ("bases", ctypes.c_uint64), ("valid_kmers", ctypes.c_uint64), ("kept_windows", ctypes.c_uint64), ("hit_words", ctypes.c_uint64),
+        ("hit_words_unique", ctypes.c_uint64), ("table_keys", ctypes.c_uint64), ("table_holders", ctypes.c_uint64), ("batches", ctypes.c_uint64),
+        ("retries", ctypes.c_uint64), ("compactions", ctypes.c_uint64), ("workgroups", ctypes.c_uint64), ("rows", ctypes.c_uint64),
+        ("ms_table", ctypes.c_float), ("ms_hash", ctypes.c_float), ("ms_finish", ctypes.c_float), ("reserved", ctypes.c_uint32),
     ]
 
     def as_dict(self):
@@ -448,6 +466,18 @@ def lib():
                                             ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(SketchStats)]
         L.ksp_sketch_host_mol.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
                                           ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SketchStats)]
+        _classify_out = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)] + [ctypes.c_void_p] * 6 + [ctypes.POINTER(ClassifyStats)]
+        _classify_in = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                        ctypes.c_uint32, ctypes.c_uint32]
+        L.ksp_classify_cpu.argtypes = _classify_in + _classify_out
+        L.ksp_classify_host.argtypes = [ctypes.c_int] + _classify_in + _classify_out
+        L.ksp_classify_open.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                        ctypes.POINTER(ctypes.c_void_p)]
+        L.ksp_classify_add.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
+        L.ksp_classify_finish.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32] + _classify_out
+        L.ksp_classify_close.argtypes = [ctypes.c_void_p]
+        L.ksp_classify_close.restype = None
+        L.kspider_classify.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32]
         _lib = L
     return _lib
 
@@ -1444,6 +1474,82 @@ def sketch_files(input_path: str, kSize: int, scaled: int, out_dir: str, user_th
     flags = (SKETCH_PER_RECORD if per_record else 0) | (0 if seed is None else SKETCH_SEED | (int(seed) << 32)) | (SKETCH_ABUND if abund else 0)
     flags |= {MOL_DNA: 0, MOL_PROTEIN: SKETCH_PROTEIN, MOL_DAYHOFF: SKETCH_DAYHOFF, MOL_HP: SKETCH_HP}[_moltype(moltype)] | (SKETCH_TRANSLATE if translate else 0)
     _check(lib().kspider_sketch(os.fsencode(input_path), int(kSize), int(scaled), os.fsencode(out_dir), int(user_threads), flags))
+
+
+_CLASSIFY_ARRAYS = ("kept_windows", "matched", "n_refs_hit", "best_ref", "best_hits", "second_hits")
+
+
+def _classify_results(n_records, call):
+    """The results of a classify call: call(rows, n_rows, the six arrays' addresses, stats) -> (rows, {array name: uint32[n_records]}, stats)."""
+    arrays = {name: np.zeros(max(int(n_records), 1), dtype=np.uint32) for name in _CLASSIFY_ARRAYS}
+    out = ctypes.c_void_p()
+    nr = ctypes.c_uint64(0)
+    st = ClassifyStats()
+    _check(call(ctypes.byref(out), ctypes.byref(nr), *[arrays[name].ctypes.data for name in _CLASSIFY_ARRAYS], ctypes.byref(st)))
+    rows = _take(out, nr.value, CLASSIFY_ROW_DTYPE)
+    return rows, {name: a[:int(n_records)] for name, a in arrays.items()}, st.as_dict()
+
+
+def _classify_one_shot(entry, lead, seq, rec_offsets, ksize, ref_keys, ref_offsets, min_hits, max_hash, scaled, seed):
+    buf, off, mh = _sketch_input(seq, rec_offsets, max_hash, scaled)
+    rk, ro = _u64(ref_keys), _u64(ref_offsets)
+    n_rec = max(off.size - 1, 0)
+    return _classify_results(n_rec, lambda *res: entry(*lead, _ptr(buf), buf.size, _ptr(off), n_rec, int(ksize), mh, int(seed), _ptr(rk), _ptr(ro), _n_sketches(ro),
+                                                       int(min_hits), *res))
+
+
+def classify_cpu(seq, rec_offsets, ksize: int, ref_keys, ref_offsets, min_hits: int = 1, max_hash: int | None = None, scaled: int | None = None, seed: int = 42) -> tuple:
+    """ksp_classify_cpu, the plain host loop: the records of a byte stream against references (strictly ascending runs of hashes)
+    -> (rows ordered by (record, reference), {kept_windows, matched, n_refs_hit, best_ref, best_hits, second_hits}, stats).  No GPU."""
+    return _classify_one_shot(lib().ksp_classify_cpu, (), seq, rec_offsets, ksize, ref_keys, ref_offsets, min_hits, max_hash, scaled, seed)
+
+
+def classify_host(seq, rec_offsets, ksize: int, ref_keys, ref_offsets, min_hits: int = 1, max_hash: int | None = None, scaled: int | None = None, seed: int = 42,
+                  device: int = 0) -> tuple:
+    """ksp_classify_host: classify_cpu's result made on the device, in one batch."""
+    return _classify_one_shot(lib().ksp_classify_host, (int(device),), seq, rec_offsets, ksize, ref_keys, ref_offsets, min_hits, max_hash, scaled, seed)
+
+
+class ClassifySession:
+    """ksp_classify_open / _add / _finish / _close: the table once, a batch of segments with their record ids per add(), the
+    results once.  close() may be called at any time; the object is also a context manager."""
+
+    def __init__(self, ksize: int, ref_keys, ref_offsets, max_hash: int | None = None, scaled: int | None = None, seed: int = 42, device: int = 0):
+        if (max_hash is None) == (scaled is None):
+            raise ValueError("give max_hash or scaled")
+        rk, ro = _u64(ref_keys), _u64(ref_offsets)
+        self._h = ctypes.c_void_p()
+        _check(lib().ksp_classify_open(int(device), int(ksize), sketch_max_hash(scaled) if max_hash is None else int(max_hash), int(seed), _ptr(rk), _ptr(ro),
+                                       _n_sketches(ro), ctypes.byref(self._h)))
+
+    def add(self, seq, seg_offsets, seg_records) -> None:
+        buf = np.frombuffer(bytes(seq), dtype=np.uint8) if isinstance(seq, (bytes, bytearray)) else np.ascontiguousarray(seq, dtype=np.uint8)
+        off = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
+        rec = None if seg_records is None else np.ascontiguousarray(seg_records, dtype=np.uint32)
+        _check(lib().ksp_classify_add(self._h, _ptr(buf), buf.size, _ptr(off), _ptr(rec), max(off.size - 1, 0)))
+
+    def finish(self, n_records: int, min_hits: int = 1) -> tuple:
+        return _classify_results(n_records, lambda *res: lib().ksp_classify_finish(self._h, int(n_records), int(min_hits), *res))
+
+    def close(self) -> None:
+        if self._h:
+            lib().ksp_classify_close(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def classify_files(input_path: str, kSize: int, scaled: int, db: str, out_prefix: str, user_threads: int = 1, min_hits: int = 1) -> None:
+    """Every read or contig of FASTA / FASTQ input against a sketch database (kspider_classify): input_path is one file or a
+    directory, db a directory of .sig files or a pack file; writes OUT_kSpider_classify.tsv (one row per record) and
+    OUT_kSpider_classify_hits.tsv (one row per record and reference with at least min_hits shared hashes).
+    KSPIDER_CLASSIFY=host in the environment: no GPU."""
+    _check(lib().kspider_classify(os.fsencode(input_path), int(kSize), int(scaled), os.fsencode(db), os.fsencode(out_prefix) if out_prefix else None, int(user_threads),
+                                  int(min_hits)))
 
 
 def cluster_from_tree(index_prefix: str, dist_type: str = "max_cont", cutoff: float = 0.0) -> None:
