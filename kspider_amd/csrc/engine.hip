@@ -118,6 +118,7 @@ struct ksp_engine {
     bool fused_flags = false;     // the tile flags and the diagonal work of this build were written with the block lists (k_fms_place, k_fkeys)
     int fused_used = 0;           // (stats) the last build took the bucket-resident path
     u32 big_buckets = 0;          // (stats) buckets above HB_CAP entries the last build handed to k_bucket_big
+    u32 label_lanes = 0;          // KSP_LABEL_LANES=1|2|..|64 when the engine was created: lanes per sampled key of k_label (0: from the mean holders per kept key)
     bool have_rank_pairs = false; // gp holds (block, rank) of every list word in rank order (key-by-key build)
     bool have_dwork = false;      // ... and dwork the diagonal work / holder sums (k_move_groups)
     ksp::Buf gp, gm, ms_hist;     // group records of the key-by-key build; parked masks; per-chunk block counts of the split (k_ms_*)
@@ -563,8 +564,19 @@ template <class V> void Stage1<V>::label_pass(const u32* firstp, const u32 n_key
     const int ls = N <= spread_max && e->KB.bytes >= (size_t)N * 128 ? 5 : 0;
     u32* lab = ls ? (u32*)e->KB.p : label;
     if (ls) hipLaunchKernelGGL(k_label_spread, dim3(grid_for(N, bs)), dim3(bs), 0, st, lab, ls, N);
-    hipLaunchKernelGGL((k_label<V>), dim3(grid_for(n_keys / (skip + 1) + 1, bs)), dim3(bs), 0, st, VA, firstp, lab, ls,
-                       skip, label_max, n_keys, scal_dev, rider);
+    // a group of lanes per sampled key (k_label): as the engine was told, or the mean holders of a kept key rounded up to
+    // a power of two — from the host's counts where it has them, by the kernel from the device's where it runs ahead of
+    // the read-back (lanes = 0).  A fixed grid strides over the sampled keys.
+    u32 lanes = e->label_lanes;
+    if (!lanes && !scal_dev) {
+        const u64 mean = std::min<u64>(64, n_keys ? (kept + n_keys - 1) / n_keys : 1);
+        lanes = 1;
+        while (lanes < mean) lanes *= 2;
+    }
+    const u64 sampled = (u64)n_keys / (skip + 1) + 1;
+    const u32 grid = (u32)std::min<u64>(2048, grid_for(sampled * (lanes ? lanes : 64), bs));
+    hipLaunchKernelGGL((k_label<V>), dim3(grid), dim3(bs), 0, st, VA, firstp, lab, ls,
+                       skip, label_max, n_keys, scal_dev, rider, lanes);
     if (ls) hipLaunchKernelGGL(k_label_gather, dim3(grid_for(N, bs)), dim3(bs), 0, st, lab, ls, label, N);
 }
 
@@ -1103,7 +1115,7 @@ template <class V> int Stage1<V>::seg_tables(const u32 r1) {
     KSP_HIP(hipMemcpyAsync(e->seg_chk.p, ck.data(), ck.size() * 16, hipMemcpyHostToDevice, st));
     e->seg_groups_nb1 = r1;
     e->seg_groups_ok = true;
-    if ((rc = e->seg_grp.ensure(gs.size() * 4 + 16 + 258 * 8))) return rc;   // (+ the ranges' first keys, k_seg_prep)
+    if ((rc = e->seg_grp.ensure(gs.size() * 4 + 16))) return rc;
     KSP_HIP(hipMemcpyAsync(e->seg_grp.p, gs.data(), gs.size() * 4, hipMemcpyHostToDevice, st));
     return KSP_OK;
 }
@@ -1115,9 +1127,8 @@ template <class V> int Stage1<V>::partition_segment() {
     const u32 ngroups_s = (u32)e->seg_groups.size() - 1;
     phase_mark(e, st, "partition");
     if (e->time_sort) KSP_HIP(hipEventRecord(e->ev[4], st));
-    u64* kmin = (u64*)((char*)e->seg_grp.p + (((e->seg_groups.size() * 4) + 15) & ~(size_t)15));   // (behind the groups)
-    hipLaunchKernelGGL(k_seg_prep, dim3(1), dim3(256), 0, st, scal, nbuckets, pp.seg_pb2, pp.seg_nb1, kmin);   // (the multiplier of this build, the ranges' first keys)
-    hipLaunchKernelGGL(k_seg_bounds, dim3((u32)e->seg_chunks.size()), dim3(64 * SEG_BW), 0, st, d_keys, e->seg_chk.as<uint4>(), scal, kmin,
+    hipLaunchKernelGGL(k_seg_prep, dim3(1), dim3(64), 0, st, scal, nbuckets);   // (the multiplier of this build)
+    hipLaunchKernelGGL(k_seg_bounds, dim3((u32)e->seg_chunks.size()), dim3(64 * SEG_BW), 0, st, d_keys, e->seg_chk.as<uint4>(), scal,
                        pp.seg_pb2, nbuckets - 1, pp.seg_nb1, e->seg_tbl.as<u32>());
     hipLaunchKernelGGL((k_seg_scatter<V>), dim3(ngroups_s * pp.seg_nb1), dim3(P2_THREADS), 0, st, d_keys, d_off, e->seg_tbl.as<u32>(),
                        e->seg_grp.as<u32>(), scal, pp.seg_pb2, nbuckets - 1, pp.seg_nb1, pp.seg_cap, pp.hp_gcnt, KA, VB);
@@ -1145,9 +1156,8 @@ template <class V> int Stage1<V>::partition_paged() {
     phase_mark(e, st, "partition");
     if (e->time_sort) KSP_HIP(hipEventRecord(e->ev[4], st));
     if (pp.seg3) {
-        u64* kmin = (u64*)((char*)e->seg_grp.p + (((e->seg_groups.size() * 4) + 15) & ~(size_t)15));
-        hipLaunchKernelGGL(k_seg_prep, dim3(1), dim3(256), 0, st, scal, nbuckets, pb2 + pbm, pp.hp_nb1, kmin);
-        hipLaunchKernelGGL(k_seg_bounds, dim3((u32)e->seg_chunks.size()), dim3(64 * SEG_BW), 0, st, d_keys, e->seg_chk.as<uint4>(), scal, kmin,
+        hipLaunchKernelGGL(k_seg_prep, dim3(1), dim3(64), 0, st, scal, nbuckets);
+        hipLaunchKernelGGL(k_seg_bounds, dim3((u32)e->seg_chunks.size()), dim3(64 * SEG_BW), 0, st, d_keys, e->seg_chk.as<uint4>(), scal,
                            pb2 + pbm, nbuckets - 1, pp.hp_nb1, e->seg_tbl.as<u32>());
         hipLaunchKernelGGL((k_seg_mid<V>), dim3(((u32)e->seg_groups.size() - 1) * pp.hp_nb1), dim3(P2_THREADS), 0, st, d_keys, d_off,
                            e->seg_tbl.as<u32>(), e->seg_grp.as<u32>(), scal, pb2, pbm, nbuckets - 1, pp.hp_nb1, pp.hp_m, e->PK2.as<u64>(),
@@ -1658,6 +1668,11 @@ int ksp_engine_create(int device, ksp_engine** out) {
     ksp_engine* e = new ksp_engine();
     e->device = device;
     if (const char* mv = std::getenv("KSP_MOVE")) e->move_forced = std::atoi(mv) != 0;   // (once per engine, not per build)
+    if (const char* lv = std::getenv("KSP_LABEL_LANES")) {   // (rounded down to a power of two, 1 .. 64)
+        const int want = std::min(64, std::max(1, std::atoi(lv)));
+        e->label_lanes = 1;
+        while ((int)e->label_lanes * 2 <= want) e->label_lanes *= 2;
+    }
     hipError_t err = hipHostMalloc((void**)&e->h_count, 64);
     if (err == hipSuccess) std::memset(e->h_count, 0, 64);   // ([7]: the sequence number of the early work list's copy-out)
     if (err == hipSuccess) err = hipHostMalloc((void**)&e->h_scal, 128);

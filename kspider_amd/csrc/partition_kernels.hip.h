@@ -551,39 +551,19 @@ constexpr u32 SEG_SMAX = 512;     // sources per group (LDS: start slot and addr
 constexpr u32 SEG_FILL = 3072;    // mean entries of a tile; the tile holds P2_TILE (uniform hashes: +18 sigma)
 constexpr u32 SEG_MIN_LEN = 12;   // mean segment length from which the path is used
 
-// the multiplier of this build and, per range j, the smallest key that belongs to range j or a later one:
-// umulhi(key, mult) >= j << pb2  <=>  key >= ceil((j << pb2) * 2^64 / mult)   (kmin[0] = 0; j << pb2 < nbuckets <= mult)
-__global__ __launch_bounds__(256) void k_seg_prep(u64* __restrict__ scal, const u32 nbuckets, const int pb2, const u32 nb1,
-                                                  u64* __restrict__ kmin) {
+// the multiplier of this build (the boundaries are found with it: k_seg_bounds works out the range of a window's last
+// key, no table of first keys per range)
+__global__ __launch_bounds__(64) void k_seg_prep(u64* __restrict__ scal, const u32 nbuckets) {
     if (threadIdx.x == 0) part_prep(scal, nbuckets);
-    __threadfence_block();
-    __syncthreads();
-    const u64 mult = scal[PC_MULT];
-    const u32 ident = reinterpret_cast<const u32*>(scal + PC_MODE)[0];
-    for (u32 j = threadIdx.x; j <= nb1; j += 256) {
-        const u64 T = (u64)j << pb2;
-        u64 k = T;   // (identity buckets: bucket = min(key, nbuckets - 1))
-        if (j >= nb1) k = ~0ull;   // (sentinel: never read as a boundary)
-        else if (!ident && T) {
-            u64 rem = T, q = 0;   // (T : 0) / mult, T < mult
-            for (int i = 63; i >= 0; --i) {
-                const u64 carry = rem >> 63;
-                rem <<= 1;
-                if (carry || rem >= mult) { rem -= mult; q |= 1ull << i; }
-            }
-            k = q + (rem ? 1ull : 0ull);
-        }
-        kmin[j] = k;
-    }
 }
 
 // one workgroup (four waves) per 2 048 consecutive entries of a source (the chunks come from a host table that is
 // rebuilt when the offsets change).  Window w of the chunk goes to wave w % 4, so every load
 // instruction of the workgroup covers 2 KB of consecutive memory and all eight of a wave are requested together.  The
 // keys of a window ascend, so the window crosses the boundaries between the range of the entry in front of it (the last
-// key of the previous window: exchanged through LDS) and the range of its own last key — uniform 64 x 64 multiplies on
-// the scalar unit instead of one per key — and boundary j sits behind the keys below kmin[j]: one compare + ballot
-// each.  bnd[s][j] = first entry of range j or a later one; bnd[s][0] = 0, bnd[s][nb1] = length.
+// key of the previous window: exchanged through LDS) and the range of its own last key, and boundary j sits in front of
+// the first entry whose range is j or a later one (every lane works out the range of its own key: see below).
+// bnd[s][j] = first entry of range j or a later one; bnd[s][0] = 0, bnd[s][nb1] = length.
 constexpr u32 SEG_BW = 4;          // waves per workgroup
 constexpr u32 SEG_BWIN = 8;        // windows of 64 entries per wave
 constexpr u32 SEG_BPART = 64 * SEG_BWIN * SEG_BW;   // entries per workgroup
@@ -591,7 +571,7 @@ __device__ inline u32 seg_range_of(const u64 key, const u64 mult, const u32 iden
     return part_bucket(key, mult, ident, nbm1) >> pb2;
 }
 __global__ __launch_bounds__(64 * SEG_BW) void k_seg_bounds(const u64* __restrict__ keys, const uint4* __restrict__ chunks,
-                                                            const u64* __restrict__ scal, const u64* __restrict__ kmin, const int pb2,
+                                                            const u64* __restrict__ scal, const int pb2,
                                                             const u32 nbm1, const u32 nb1, u32* __restrict__ bnd) {
     __shared__ u32 s_rl[SEG_BW * SEG_BWIN + 1];   // [1 + w]: range of the last key of window w; [0]: of the entry in front of the chunk
     __shared__ u32 s_bnd[260];                    // the boundaries this chunk crosses: they leave in one piece (single words per
@@ -609,7 +589,6 @@ __global__ __launch_bounds__(64 * SEG_BW) void k_seg_bounds(const u64* __restric
     const u32 ident = reinterpret_cast<const u32*>(scal + PC_MODE)[0];
     u32* const row = bnd + (size_t)s * (nb1 + 1);
     if (a0 == 0 && threadIdx.x == 0) row[0] = 0;
-    (void)kmin;   // (the boundary keys of round 2's scalar formulation; k_seg_scatter does not need them either)
     u64 k[SEG_BWIN];
 #pragma unroll
     for (u32 q = 0; q < SEG_BWIN; ++q) {

@@ -168,25 +168,54 @@ __device__ inline u32 src_of_tag(u32 t) { return (t >> 8) * TB + (t & 0xFFu); }
 template <class V>
 __global__ void k_label(const V* __restrict__ vals, const u32* __restrict__ first, u32* __restrict__ label,
                         const int lshift, const u32 skip, const u32 max_holders, u32 n_keys, const u64* __restrict__ scal,
-                        const Rider rider) {
+                        const Rider rider, u32 lanes) {
     rider_run(rider);
     // scal != NULL: launched before the host has read the grouping's results back — the key count comes from the
     // device (n_keys is an upper bound) and nothing is touched when the grouping gave up (the build is repeated)
     if (scal) {
-        if ((u32)scal[9] | (u32)scal[14]) return;
+        if ((u32)scal[9] | (u32)scal[14]) return;   // (the same for every thread of the grid)
         n_keys = min(n_keys, (u32)scal[2]);
     }
-    const u32 r = (blockIdx.x * blockDim.x + threadIdx.x) * (skip + 1);   // one thread per sampled key (skip = 2^k - 1)
-    if (r >= n_keys) return;
-    const u32 f0 = first[r], f1 = first[r + 1];   // (first[] has a sentinel: first[U] = number of entries)
-    // a key held by very many sources says nothing about who is related to whom — it would only pull
-    // unrelated clusters under one label
-    if (f1 - f0 > max_holders) return;
-    u32 mn = ~0u;   // (the entries of a key are in no particular order after the bucket grouping)
-    for (u32 e = f0; e < f1; ++e) mn = min(mn, src_of_tag(tag_of(vals[e])));
-    for (u32 e = f0; e < f1; ++e) {
-        const u32 s = src_of_tag(tag_of(vals[e]));
-        if (mn < label[(size_t)s << lshift]) atomicMin(&label[(size_t)s << lshift], mn);
+    // A group of `lanes` lanes per sampled key (a power of two up to 64; skip = 2^k - 1): one thread per key walked the
+    // key's holders twice, the second time with two dependent loads per holder — a chain of 3 x holders memory round
+    // trips, and the kernel's time followed the chain, not the work.  lanes = 0: the mean number of holders of a kept
+    // key, from the grouping's own counts, rounded up to a power of two — keys of two or three holders keep small groups.
+    if (lanes == 0) {
+        const u64 keys_kept = scal ? scal[2] : 0, ents = scal ? scal[6] : 0;
+        const u32 mean = keys_kept ? (u32)min((ents + keys_kept - 1) / keys_kept, (u64)64) : 1u;
+        lanes = 1;
+        while (lanes < mean) lanes *= 2;
+    }
+    const int lane = threadIdx.x & 63;
+    const u32 sub = threadIdx.x & (lanes - 1);
+    const u32 n_sampled = n_keys ? (n_keys - 1) / (skip + 1) + 1 : 0;
+    const u32 groups = (gridDim.x * blockDim.x) / lanes;
+    // (every lane stays for its group's exchanges: the trip count is the same for the whole grid, a group without a key
+    //  walks no holders)
+    for (u32 g0 = 0; g0 < n_sampled; g0 += groups) {
+        const u32 g = g0 + (blockIdx.x * blockDim.x + threadIdx.x) / lanes;
+        u32 f0 = 0, f1 = 0;
+        if (g < n_sampled) {
+            const u32 r = g * (skip + 1);
+            f0 = first[r], f1 = first[r + 1];   // (first[] has a sentinel: first[U] = number of entries)
+            // a key held by very many sources says nothing about who is related to whom — it would only pull
+            // unrelated clusters under one label
+            if (f1 - f0 > max_holders) f1 = f0;
+        }
+        u32 mn = ~0u;   // (the entries of a key are in no particular order after the bucket grouping)
+        u32 s0 = 0;     // the lane's first holder: the only one when the key has no more holders than the group lanes
+        if (f0 + sub < f1) mn = s0 = src_of_tag(tag_of(vals[f0 + sub]));
+        for (u32 e = f0 + sub + lanes; e < f1; e += lanes) mn = min(mn, src_of_tag(tag_of(vals[e])));
+        if (lanes > 1) mn = min(mn, xor_lane<1>(mn, lane));
+        if (lanes > 2) mn = min(mn, xor_lane<2>(mn, lane));
+        if (lanes > 4) mn = min(mn, xor_lane<4>(mn, lane));
+        if (lanes > 8) mn = min(mn, xor_lane<8>(mn, lane));
+        if (lanes > 16) mn = min(mn, xor_lane<16>(mn, lane));
+        if (lanes > 32) mn = min(mn, xor_lane<32>(mn, lane));
+        for (u32 e = f0 + sub; e < f1; e += lanes) {
+            const u32 s = e == f0 + sub ? s0 : src_of_tag(tag_of(vals[e]));
+            if (mn < label[(size_t)s << lshift]) atomicMin(&label[(size_t)s << lshift], mn);
+        }
     }
 }
 // While they are being lowered the labels sit on memory lines of their own (label s at index s << lshift):
