@@ -221,19 +221,25 @@ static inline unsigned grid_for(u64 n, unsigned bs) { return (unsigned)((n + bs 
 // the 128-bit masks the posting words of the engine's lists index
 static inline uint4* list_masks(const ksp_engine* e) { return e->masks_in_gm ? e->gm.as<uint4>() : e->mm.as<uint4>(); }
 
+// Wait for a sequence number that a kernel on `stream` stores to pinned memory behind its results (k_readback, k_pack_flags_out):
+// no event in the stream, the host spins on the word.  The three waits of the engine (a read-back, the early work list, the
+// join's count) are this one.
+static hipError_t poll_seq(const volatile unsigned long long* flag, const unsigned long long seq, hipStream_t stream) {
+    for (unsigned long long spins = 1; *flag != seq; ++spins) {
+        if ((spins & 0xFFFFF) == 0) {   // (now and then: is the stream still alive?)
+            const hipError_t q = hipStreamQuery(stream);
+            if (q == hipSuccess) return *flag == seq ? hipSuccess : hipErrorUnknown;   // (idle, and the number never came)
+            if (q != hipErrorNotReady) return q;
+        }
+    }
+    return hipSuccess;
+}
+
 // wait for the read-back behind which e->ev_rb was recorded (later kernels may already be queued on the stream)
 static inline hipError_t wait_readback(ksp_engine* e) {
     if (e->rb_flag) {
         e->rb_flag = false;
-        volatile unsigned long long* f = reinterpret_cast<volatile unsigned long long*>(e->h_scal + 15);
-        for (unsigned long long spins = 1; *f != e->rb_seq; ++spins) {
-            if ((spins & 0xFFFFF) == 0) {   // (now and then: is the stream still alive?)
-                const hipError_t q = hipStreamQuery(e->rb_stream);
-                if (q == hipSuccess) return *f == e->rb_seq ? hipSuccess : hipErrorUnknown;   // (idle, and the number never came)
-                if (q != hipErrorNotReady) return q;
-            }
-        }
-        return hipSuccess;
+        return poll_seq(reinterpret_cast<const volatile unsigned long long*>(e->h_scal + 15), e->rb_seq, e->rb_stream);
     }
     static const int mode = [] { const char* m = std::getenv("KSP_DEBUG_RBWAIT"); return m ? std::atoi(m) : 0; }();
     if (mode == 1) return hipEventSynchronize(e->ev_rb);
@@ -391,6 +397,23 @@ static hipError_t resolve_build_ms(ksp_engine* e) {
     while ((qe = hipEventQuery(e->ev[1])) == hipErrorNotReady) {}
     if (qe != hipSuccess) return qe;
     return hipEventElapsedTime(&e->st.ms_build, e->ev[0], e->ev[1]);
+}
+// A timed section of a build opens: the previous build's time is read before its events are recorded again.  `record`: the
+// step path records no event (ksp_engine::lean).
+static int open_build_section(ksp_engine* e, hipStream_t st, const bool record = true) {
+    KSP_HIP(resolve_build_ms(e));
+    if (record) KSP_HIP(hipEventRecord(e->ev[0], st));
+    return KSP_OK;
+}
+// ... and closes: the stream is idle afterwards.  `add`: the section continues a build (slice finish, assemble) and its time
+// is added to st.ms_build; otherwise it replaces it.
+static int close_build_section(ksp_engine* e, hipStream_t st, const bool add) {
+    KSP_HIP(hipEventRecord(e->ev[1], st));
+    KSP_HIP(hipStreamSynchronize(st));
+    float ms = 0;
+    KSP_HIP(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
+    e->st.ms_build = add ? e->st.ms_build + ms : ms;
+    return KSP_OK;
 }
 
 // what a step of stage 1 answers besides KSP_OK (go on with the next step) and the KSP_E_* codes; build_to_end takes them, its callers never see them
@@ -1896,37 +1919,74 @@ static bool join_still_pending(const ksp_engine* e, const char* what) {
 
 static int finish_build(ksp_engine* e) {
     e->st.key_bits = e->key_bits;
-    if (e->blk_staged) {
-        const size_t bytes = ((size_t)e->nb + 1) * 4;
-        e->h_blk_off.resize((size_t)e->nb + 1);
-        std::memcpy(e->h_blk_max.data(), e->h_blk_stage, bytes);
-        std::memcpy(e->h_blk_off.data(), e->h_blk_stage + 2 * bytes, bytes);
-        if (e->padded) std::memcpy(e->h_blk_src.data(), e->h_blk_stage + bytes, bytes);
-        e->blk_staged = false;
-        u32 big_blocks = 0;
-        for (u32 b = 0; b < e->nb; ++b) big_blocks += e->h_blk_max[b] >= 65536u;
-        e->need32 = big_blocks >= 1;
-        e->st.n_block_keys = e->h_blk_off[e->nb];
-        int rc = build_schedule(e);
-        if (rc) return rc;
-        e->built = true;
-        return KSP_OK;
-    }
-    KSP_HIP(hipMemcpy(e->h_blk_max.data(), e->blk_max.p, ((size_t)e->nb + 1) * 4, hipMemcpyDeviceToHost));
-    if (e->padded)
-        KSP_HIP(hipMemcpy(e->h_blk_src.data(), e->blk_max.as<u32>() + ((size_t)e->nb + 1), ((size_t)e->nb + 1) * 4, hipMemcpyDeviceToHost));
-    {
-        u32 big_blocks = 0;
-        for (u32 b = 0; b < e->nb; ++b) big_blocks += e->h_blk_max[b] >= 65536u;
-        e->need32 = big_blocks >= 1;   // a big block pairs with itself (diagonal tile) at least
-    }
+    // the per-block maxima, the sources before every block (padded builds) and the list offsets: from pinned memory when the
+    // build staged them (stage_block_tables), else from the device
+    const size_t bytes = ((size_t)e->nb + 1) * 4;
     e->h_blk_off.resize((size_t)e->nb + 1);
-    KSP_HIP(hipMemcpy(e->h_blk_off.data(), e->blk_raw.p, ((size_t)e->nb + 1) * 4, hipMemcpyDeviceToHost));
+    if (e->blk_staged) {
+        std::memcpy(e->h_blk_max.data(), e->h_blk_stage, bytes);
+        if (e->padded) std::memcpy(e->h_blk_src.data(), e->h_blk_stage + bytes, bytes);
+        std::memcpy(e->h_blk_off.data(), e->h_blk_stage + 2 * bytes, bytes);
+        e->blk_staged = false;
+    } else {
+        KSP_HIP(hipMemcpy(e->h_blk_max.data(), e->blk_max.p, bytes, hipMemcpyDeviceToHost));
+        if (e->padded) KSP_HIP(hipMemcpy(e->h_blk_src.data(), e->blk_max.as<u32>() + ((size_t)e->nb + 1), bytes, hipMemcpyDeviceToHost));
+        KSP_HIP(hipMemcpy(e->h_blk_off.data(), e->blk_raw.p, bytes, hipMemcpyDeviceToHost));
+    }
+    u32 big_blocks = 0;
+    for (u32 b = 0; b < e->nb; ++b) big_blocks += e->h_blk_max[b] >= 65536u;
+    e->need32 = big_blocks >= 1;   // a big block pairs with itself (diagonal tile) at least
     e->st.n_block_keys = e->h_blk_off[e->nb];
     int rc = build_schedule(e);
     if (rc) return rc;
     e->built = true;
     return KSP_OK;
+}
+
+// What a build from sketches and a build from postings reset in the same way, once their arguments have been accepted:
+// nothing of the previous build's work list survives, the geometry of `n_sources` sources and `n` entries, fresh stats and
+// block tables.  What only one of the two does stays in its front end, under a comment of its own.
+static void reset_for_build(ksp_engine* e, const u32 n_sources, const u64 n, const bool weighted, const int key_bits, const u32 part, const u32 nparts) {
+    e->built = false;
+    e->slice_ready = false;
+    e->post_slice = false;
+    e->sched_on = false; e->collect = false; e->have_bits = false; e->matches_on = false; e->pmask_on = false; e->lists_path = 0;
+    e->act_tid.clear(); e->act_rec.clear();
+    e->part_fail = 0;   // (stats: partition_fallback describes this build)
+    if (const char* ro = std::getenv("KSP_REORDER")) e->reorder = std::atoi(ro) != 0;   // diagnostic / tests
+    e->n_sources = n_sources;
+    e->n_entries = n;
+    e->nb = blocks_for(n_sources, e->reorder);
+    e->padded = e->nb > (n_sources + TB - 1) / TB;
+    e->weighted = weighted;
+    e->key_bits = key_bits;
+    e->have_max_key = false;
+    e->nparts = nparts;
+    e->part_id = part;
+    e->ph_n = 0;
+    e->st = ksp_stats{};
+    e->st.n_sources = n_sources;
+    e->st.n_entries = n;
+    e->sort_entries = 0;
+    e->st.n_blocks = e->nb;
+    e->st.n_tiles = (u64)e->nb * (e->nb + 1) / 2;
+    e->st.weighted = e->weighted;
+    e->n_kept = 0;
+    e->h_blk_off.assign((size_t)e->nb + 1, 0);
+    e->h_blk_max.assign((size_t)e->nb + 1, 0);
+    e->h_blk_src.resize((size_t)e->nb + 1);
+    for (u32 b = 0; b <= e->nb; ++b) e->h_blk_src[b] = (u32)std::min<u64>(n_sources, (u64)b * TB);   // (until a padded build reports its own)
+    std::memset(e->slice_hdr, 0, sizeof e->slice_hdr);
+}
+
+// fine cells: ~32 entries of the largest block (`dmax`) per cell, power of two, index kept below 1 GiB
+static void set_cells(ksp_engine* e, const u64 dmax) {
+    u32 nc = NP;
+    while ((u64)nc * 32 < dmax && nc < (1u << 17)) nc <<= 1;
+    while (nc > NP && (u64)nc * e->nb > (1ull << 28)) nc >>= 1;
+    e->ncell = nc;
+    const char* jm = std::getenv("KSP_JOIN");
+    e->use_cells = !(jm && std::string(jm) == "window");
 }
 
 // common front end of build_blocks / build_slice
@@ -1948,66 +2008,31 @@ static int build_common(ksp_engine* e, const uint64_t* d_keys, const uint32_t* d
     if (n && !d_keys) { set_error("build: d_keys is NULL"); return KSP_E_ARG; }
     if (join_elsewhere(e, st, "build")) return KSP_E_ARG;
     KSP_HIP(hipSetDevice(e->device));
-    e->built = false;
-    e->slice_ready = false;
-    e->post_slice = false;
-    e->sched_on = false; e->collect = false; e->have_bits = false; e->matches_on = false; e->pmask_on = false; e->lists_path = 0;   // (nothing of the previous build's work list survives)
-    e->act_tid.clear(); e->act_rec.clear();
-    e->part_fail = 0;   // (stats: partition_fallback describes this build)
-    if (const char* ro = std::getenv("KSP_REORDER")) e->reorder = std::atoi(ro) != 0;   // diagnostic / tests
-    e->n_sources = n_sources;
-    e->n_entries = n;
-    e->nb = blocks_for(n_sources, e->reorder);
-    e->padded = e->nb > (n_sources + TB - 1) / TB;
-    e->weighted = d_weights != nullptr;
-    e->key_bits = key_bits;
-    e->have_max_key = false;
-    e->nparts = nparts;
-    e->part_id = part;
+    reset_for_build(e, n_sources, n, d_weights != nullptr, key_bits, part, nparts);
+    // of the sketch path alone: slice_phase is left as it is (the callers set it); unchanged offsets keep h_off and their
+    // copy on the device; the switches of the stage-1 paths that only sketches take
     const bool same_offsets = e->d_off_sketch && e->h_off.size() == (size_t)n_sources + 1 &&
                               std::memcmp(e->h_off.data(), h_offsets, ((size_t)n_sources + 1) * 8) == 0;
     if (!same_offsets) { e->h_off.assign(h_offsets, h_offsets + n_sources + 1); e->d_off_sketch = false; e->seg_groups_ok = false; }
     if (std::getenv("KSP_FULL_SORT")) e->full_sort = true;   // diagnostic: sort on all key bits
     if (const char* hg = std::getenv("KSP_HASH_GROUP")) e->hash_off = std::atoi(hg) == 0;   // diagnostic / tests
     if (const char* kg = std::getenv("KSP_KEY_GROUPS")) e->key_groups_off = std::atoi(kg) == 0;
-    if (const char* pp = std::getenv("KSP_PARTITION")) { e->part_off = std::string(pp) == "rocprim"; e->part_fail = 0; }   // diagnostic / tests
+    if (const char* pp = std::getenv("KSP_PARTITION")) e->part_off = std::string(pp) == "rocprim";   // diagnostic / tests
     if (const char* pm = std::getenv("KSP_PART_MIN")) e->part_min = (u32)std::max(1, std::atoi(pm));
-    e->ph_n = 0;
-    e->st = ksp_stats{};
-    e->st.n_sources = n_sources;
-    e->st.n_entries = n;
-    e->sort_entries = 0;
-    e->st.n_blocks = e->nb;
-    e->st.n_tiles = (u64)e->nb * (e->nb + 1) / 2;
-    e->st.weighted = e->weighted;
-    e->n_kept = 0;
-    e->h_blk_off.assign((size_t)e->nb + 1, 0);
-    e->h_blk_max.assign((size_t)e->nb + 1, 0);
-    e->h_blk_src.resize((size_t)e->nb + 1);
-    for (u32 b = 0; b <= e->nb; ++b) e->h_blk_src[b] = (u32)std::min<u64>(n_sources, (u64)b * TB);   // (until a padded build reports its own)
-    std::memset(e->slice_hdr, 0, sizeof e->slice_hdr);
-    if (n == 0 || e->nb == 0) return KSP_OK;   // nothing can intersect
+    if (n == 0 || e->nb == 0) return KSP_OK;   // nothing can intersect (the callers set built / slice_phase)
     int rc;
     if ((rc = e->d_off.ensure(((size_t)n_sources + 1) * 8))) return rc;
-    KSP_HIP(resolve_build_ms(e));   // (the previous build's time, before its events are recorded again)
-    if (!e->lean) KSP_HIP(hipEventRecord(e->ev[0], st));
+    if ((rc = open_build_section(e, st, !e->lean))) return rc;   // (lean: no event at the start either)
     if (!same_offsets) {   // (the engine's own copy is the source: the caller's array may go away before the copy has run)
         KSP_HIP(hipMemcpyAsync(e->d_off.p, e->h_off.data(), ((size_t)n_sources + 1) * 8, hipMemcpyHostToDevice, st));
         e->d_off_sketch = true;
     }
-    {   // fine cells: ~32 entries of the largest block per cell, power of two, index kept below 1 GiB
-        u64 dmax = 0;
-        for (u32 b = 0; (u64)b * TB < n_sources; ++b) {
-            u64 lo = h_offsets[(u64)b * TB], hi = h_offsets[std::min<u64>(n_sources, (u64)(b + 1) * TB)];
-            dmax = std::max(dmax, hi - lo);
-        }
-        u32 nc = NP;
-        while ((u64)nc * 32 < dmax && nc < (1u << 17)) nc <<= 1;
-        while (nc > NP && (u64)nc * e->nb > (1ull << 28)) nc >>= 1;
-        e->ncell = nc;
-        const char* jm = std::getenv("KSP_JOIN");
-        e->use_cells = !(jm && std::string(jm) == "window");
+    u64 dmax = 0;   // entries of the largest block in the caller's order
+    for (u32 b = 0; (u64)b * TB < n_sources; ++b) {
+        u64 lo = h_offsets[(u64)b * TB], hi = h_offsets[std::min<u64>(n_sources, (u64)(b + 1) * TB)];
+        dmax = std::max(dmax, hi - lo);
     }
+    set_cells(e, dmax);
     if ((rc = e->blk_max.ensure((2 * (size_t)e->nb + 4) * 4))) return rc;
     for (int attempt = 0; attempt < 2; ++attempt) {
         const int phase = slice ? 1 : 0;   // a slice stops at the source labels (ksp_engine_slice_finish does the rest)
@@ -2037,22 +2062,13 @@ static int build_common(ksp_engine* e, const uint64_t* d_keys, const uint32_t* d
     if (!(e->lean && flagged)) KSP_HIP(hipEventRecord(e->ev[1], st));   // (lean + signalled: nobody looks at the event)
     // (polling the event instead of a blocking wait: the join cannot be cut into shares before the build's tables have
     //  landed, and waking a blocked host thread is tens of microseconds of device idle time per step)
-    {
-        if (flagged) {   // (the copy-out's last workgroup wrote the number: no event in the stream)
-            volatile unsigned long long* f = reinterpret_cast<volatile unsigned long long*>(e->h_count + 7);
-            for (unsigned long long spins = 1; *f != e->sched_seq; ++spins) {
-                if ((spins & 0xFFFFF) == 0) {   // (now and then: is the stream still alive?)
-                    const hipError_t q = hipStreamQuery(st);
-                    if (q == hipSuccess && *f != e->sched_seq) KSP_HIP(hipErrorUnknown);
-                    if (q != hipErrorNotReady && q != hipSuccess) KSP_HIP(q);
-                }
-            }
-        } else {
+    if (flagged) {   // (the copy-out's last workgroup wrote the number: no event in the stream)
+        KSP_HIP(poll_seq(e->h_count + 7, e->sched_seq, st));
+    } else {
         const hipEvent_t landed = e->sched_early ? e->ev_sched : e->ev[1];   // (early work list: the placement pass is still running)
         hipError_t qe;
         while ((qe = hipEventQuery(landed)) == hipErrorNotReady) {}
         KSP_HIP(qe);
-        }
     }
     if (e->lean) {
         e->st.ms_build = 0;           // (no events were recorded)
@@ -2086,39 +2102,11 @@ static int build_postings_common(ksp_engine* e, const uint64_t* h_key_off, const
     if (n >= (1ull << 30)) { set_error("build_postings: more than 2^30 entries per call"); return KSP_E_LIMIT; }
     if (join_elsewhere(e, st, "build_postings")) return KSP_E_ARG;
     KSP_HIP(hipSetDevice(e->device));
-    e->built = false;
-    e->slice_ready = false;
-    e->sched_on = false; e->collect = false; e->have_bits = false; e->matches_on = false; e->pmask_on = false; e->lists_path = 0;
-    e->act_tid.clear(); e->act_rec.clear();
-    e->ph_n = 0;
+    reset_for_build(e, n_sources, n, d_key_weights != nullptr, /*key_bits*/ 0, /*part*/ 0, /*nparts*/ 1);
+    // of the postings path alone: an unfinished slice is forgotten; there are no sketch offsets to keep (d_off takes the key
+    // offsets below); none of the sketch path's stage-1 switches is read
     e->slice_phase = 0;
-    e->post_slice = false;
-    e->part_fail = 0;
-    if (const char* ro = std::getenv("KSP_REORDER")) e->reorder = std::atoi(ro) != 0;
-    e->n_sources = n_sources;
-    e->n_entries = n;
-    e->nb = blocks_for(n_sources, e->reorder);
-    e->padded = e->nb > (n_sources + TB - 1) / TB;
-    e->weighted = d_key_weights != nullptr;
-    e->key_bits = 0;
-    e->have_max_key = false;
-    e->nparts = 1;
-    e->part_id = 0;
     e->h_off.clear();
-    e->st = ksp_stats{};
-    e->st.n_sources = n_sources;
-    e->st.n_entries = n;
-    e->sort_entries = 0;
-    e->st.n_blocks = e->nb;
-    e->st.n_tiles = (u64)e->nb * (e->nb + 1) / 2;
-    e->st.weighted = e->weighted;
-    e->n_kept = 0;
-    e->h_blk_off.assign((size_t)e->nb + 1, 0);
-    e->h_blk_max.assign((size_t)e->nb + 1, 0);
-    e->h_blk_src.resize((size_t)e->nb + 1);
-    for (u32 b = 0; b <= e->nb; ++b) e->h_blk_src[b] = (u32)std::min<u64>(n_sources, (u64)b * TB);
-    e->have_bits = false;
-    std::memset(e->slice_hdr, 0, sizeof e->slice_hdr);
     if (n == 0 || e->nb == 0) {   // nothing can intersect
         e->st.n_block_keys = 0;
         e->need32 = false;
@@ -2127,17 +2115,8 @@ static int build_postings_common(ksp_engine* e, const uint64_t* h_key_off, const
         return KSP_OK;
     }
     int rc;
-    KSP_HIP(resolve_build_ms(e));   // (the previous build's time, before its events are recorded again)
-    KSP_HIP(hipEventRecord(e->ev[0], st));
-    {   // fine cells as in build_common, from the mean block size (the holders are not grouped by source here)
-        const u64 dmax = 2 * (n / e->nb + 1);
-        u32 nc = NP;
-        while ((u64)nc * 32 < dmax && nc < (1u << 17)) nc <<= 1;
-        while (nc > NP && (u64)nc * e->nb > (1ull << 28)) nc >>= 1;
-        e->ncell = nc;
-        const char* jm = std::getenv("KSP_JOIN");
-        e->use_cells = !(jm && std::string(jm) == "window");
-    }
+    if ((rc = open_build_section(e, st))) return rc;   // (always timed: the step path does not come through here)
+    set_cells(e, 2 * (n / e->nb + 1));   // (twice the mean block size: the holders are not grouped by source here)
     if ((rc = e->blk_max.ensure((2 * (size_t)e->nb + 4) * 4))) return rc;
     // key offsets as 32-bit device array (= first entry of every rank)
     if ((rc = e->d_off.ensure(((size_t)n_keys + 2) * 4))) return rc;
@@ -2158,7 +2137,7 @@ static int build_postings_common(ksp_engine* e, const uint64_t* h_key_off, const
     if (rc) return rc;
     if (slice) {   // (a slice: up to the source labels; ksp_engine_slice_finish builds its lists once all slices' labels are combined)
         KSP_HIP(hipMemcpyAsync(e->h_scal + 4, e->scalars.as<u64>() + 4, 8, hipMemcpyDeviceToHost, st));
-        KSP_HIP(hipEventRecord(e->ev[1], st));
+        KSP_HIP(hipEventRecord(e->ev[1], st));   // (not close_build_section: a refused slice leaves before its time is read)
         KSP_HIP(hipStreamSynchronize(st));
         if ((u32)e->h_scal[4]) { set_error("build_postings: a source index is >= n_sources"); return KSP_E_ARG; }
         e->h_scal[4] = 0;
@@ -2176,9 +2155,7 @@ static int build_postings_common(ksp_engine* e, const uint64_t* h_key_off, const
         e->h_scal_keys = e->h_scal[2];
         if ((rc = launch_sched_kernels(e, st))) return rc;
     }
-    KSP_HIP(hipEventRecord(e->ev[1], st));
-    KSP_HIP(hipStreamSynchronize(st));
-    KSP_HIP(hipEventElapsedTime(&e->st.ms_build, e->ev[0], e->ev[1]));
+    if ((rc = close_build_section(e, st, false))) return rc;
     phase_close(e, e->ev[1]);
     return finish_build(e);
 }
@@ -2239,6 +2216,11 @@ int ksp_engine_slice_labels(ksp_engine* e, uint32_t* d_labels, void* stream) {
 }
 
 static u32* bound_array(ksp_engine* e) { return e->smap.as<u32>() + 5 * smap_stride(e); }   // [5] of the per-source maps
+// the blocks' maxima raised to the bounds in bound_array (the identity order took them at the build)
+static void raise_block_bounds(ksp_engine* e, hipStream_t st) {
+    hipLaunchKernelGGL(k_blk_bound, dim3(grid_for(e->n_sources, 256)), dim3(256), 0, st, bound_array(e),
+                       e->smap.as<u32>() + 4 * smap_stride(e), e->blk_max.as<u32>(), e->n_sources);
+}
 
 // The bound of every source's pair counters as this slice knows it (n_sources uint32: k-mer count / weight sum).  A slice of
 // sketches sees every source's whole run and reports the full bound; a slice of an inverted index sees its own keys only:
@@ -2266,9 +2248,7 @@ int ksp_engine_slice_set_bounds(ksp_engine* e, const uint32_t* d_bounds, void* s
     KSP_HIP(hipSetDevice(e->device));
     if (e->n_entries == 0 || e->nb == 0) return KSP_OK;
     KSP_HIP(hipMemcpyAsync(bound_array(e), d_bounds, (size_t)e->n_sources * 4, hipMemcpyDeviceToDevice, st));
-    if (!e->reorder)   // (the identity order took the blocks' maxima at the build: raise them to the combined bounds)
-        hipLaunchKernelGGL(k_blk_bound, dim3(grid_for(e->n_sources, 256)), dim3(256), 0, st, bound_array(e),
-                           e->smap.as<u32>() + 4 * smap_stride(e), e->blk_max.as<u32>(), e->n_sources);
+    if (!e->reorder) raise_block_bounds(e, st);   // (... to the combined bounds)
     KSP_HIP(hipGetLastError());
     KSP_HIP(hipStreamSynchronize(st));
     e->bounds_set = true;
@@ -2284,16 +2264,13 @@ int ksp_engine_slice_finish(ksp_engine* e, const uint32_t* d_labels, void* strea
     e->slice_phase = 0;
     if (e->n_entries == 0 || e->nb == 0) { e->slice_ready = true; return KSP_OK; }
     int rc;
-    KSP_HIP(resolve_build_ms(e));   // (the previous build's time, before its events are recorded again)
-    KSP_HIP(hipEventRecord(e->ev[0], st));
+    if ((rc = open_build_section(e, st))) return rc;
     if (d_labels) KSP_HIP(hipMemcpyAsync(label_array(e), d_labels, (size_t)e->n_sources * 4, hipMemcpyDeviceToDevice, st));
     if (e->post_slice && !e->bounds_set) {
         // a slice of an index that was never told the bounds over all slices: its own share says nothing about the
         // sums the assembled lists reach, so every source counts as one that needs 32-bit counters
         hipLaunchKernelGGL(k_fill, dim3(grid_for(e->n_sources, 256)), dim3(256), 0, st, bound_array(e), 0xFFFFFFFFu, (u64)e->n_sources);
-        if (!e->reorder)
-            hipLaunchKernelGGL(k_blk_bound, dim3(grid_for(e->n_sources, 256)), dim3(256), 0, st, bound_array(e),
-                               e->smap.as<u32>() + 4 * smap_stride(e), e->blk_max.as<u32>(), e->n_sources);
+        if (!e->reorder) raise_block_bounds(e, st);
         KSP_HIP(hipGetLastError());
     }
     rc = build_dispatch(e, nullptr, nullptr, st, 2);
@@ -2309,11 +2286,7 @@ int ksp_engine_slice_finish(ksp_engine* e, const uint32_t* d_labels, void* strea
         hipLaunchKernelGGL(k_fill, dim3(grid_for(lpad, 256)), dim3(256), 0, st, e->bkeys.as<u32>(), PAD, lpad);
         KSP_HIP(hipMemcpyAsync(e->h_scal + 3, e->scalars.as<u64>() + 3, 8, hipMemcpyDeviceToHost, st));
     }
-    KSP_HIP(hipEventRecord(e->ev[1], st));
-    KSP_HIP(hipStreamSynchronize(st));
-    float ms = 0;
-    KSP_HIP(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
-    e->st.ms_build += ms;
+    if ((rc = close_build_section(e, st, true))) return rc;   // (added to the slice build's time)
     e->slice_hdr[0] = e->h_scal[3];           // padded length
     if (e->n_kept == 0) {
         e->slice_hdr[1] = e->slice_hdr[2] = e->slice_hdr[3] = 0;
@@ -2390,8 +2363,7 @@ int ksp_engine_assemble(ksp_engine* e, uint32_t nparts, const uint64_t* h_sizes 
     if (e->weighted && (rc = e->bw.ensure(lmax * 4))) return rc;
     if ((rc = e->mm.ensure((bigtot + 16) * 16))) return rc;
     if ((rc = e->asm_small.ensure(off.size() * 4))) return rc;
-    KSP_HIP(resolve_build_ms(e));   // (the previous build's time, before its events are recorded again)
-    KSP_HIP(hipEventRecord(e->ev[0], st));
+    if ((rc = open_build_section(e, st))) return rc;
     KSP_HIP(hipMemcpyAsync(e->asm_small.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
     u64* scal = e->scalars.as<u64>();
     hipLaunchKernelGGL(k_asm_counts, dim3(1), dim3(64), 0, st, d_blk_raw_all, nb + 1, nparts, nb, e->blk_raw.as<u32>());
@@ -2426,11 +2398,7 @@ int ksp_engine_assemble(ksp_engine* e, uint32_t nparts, const uint64_t* h_sizes 
     e->masks_in_gm = false;
     e->lists_path = 0;
     if ((rc = launch_sched_kernels(e, st))) return rc;
-    KSP_HIP(hipEventRecord(e->ev[1], st));
-    KSP_HIP(hipStreamSynchronize(st));
-    float ms = 0;
-    KSP_HIP(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
-    e->st.ms_build += ms;   // slice build + assemble
+    if ((rc = close_build_section(e, st, true))) return rc;   // (slice build + assemble)
     return finish_build(e);
 }
 
@@ -2459,18 +2427,22 @@ uint64_t ksp_engine_tile_pairs(const ksp_engine* e, uint64_t t0, uint64_t t1) {
     return pairs;
 }
 
+// work list: the first active tile at or behind tile `t` (index into act_tid / act_rec), and the source pairs of active tile `i`
+static size_t first_active(const ksp_engine* e, const u64 t) {
+    return std::lower_bound(e->act_tid.begin(), e->act_tid.end(), t) - e->act_tid.begin();
+}
+static u64 active_tile_pairs(const ksp_engine* e, const size_t i) {
+    const std::vector<u32>& P = e->h_blk_src;
+    const u32 I = e->act_rec[4 * i], J = e->act_rec[4 * i + 1];
+    const u64 nI = P[I + 1] - P[I], nJ = P[J + 1] - P[J];
+    return (I == J) ? nI * (nI ? nI - 1 : 0) / 2 : nI * nJ;
+}
+
 uint64_t ksp_engine_edge_bound(const ksp_engine* e, uint64_t t0, uint64_t t1) {
     if (!e || !e->nb || !e->built) return 0;
     if (!e->sched_on) return ksp_engine_tile_pairs(e, t0, t1);
-    const size_t a0 = std::lower_bound(e->act_tid.begin(), e->act_tid.end(), t0) - e->act_tid.begin();
-    const size_t a1 = std::lower_bound(e->act_tid.begin(), e->act_tid.end(), t1) - e->act_tid.begin();
-    const std::vector<u32>& P = e->h_blk_src;
     u64 pairs = 0;
-    for (size_t i = a0; i < a1; ++i) {
-        const u32 I = e->act_rec[4 * i], J = e->act_rec[4 * i + 1];
-        const u64 nI = P[I + 1] - P[I], nJ = P[J + 1] - P[J];
-        pairs += (I == J) ? nI * (nI ? nI - 1 : 0) / 2 : nI * nJ;
-    }
+    for (size_t i = first_active(e, t0), a1 = first_active(e, t1); i < a1; ++i) pairs += active_tile_pairs(e, i);
     return pairs;
 }
 
@@ -2496,6 +2468,200 @@ int ksp_engine_balanced_cuts(const ksp_engine* e, uint32_t nparts, uint64_t* cut
     return KSP_OK;
 }
 
+// ---- a join launch in steps: the arguments, one of the two modes, the count, the stream-byte statistic ----
+// HIP caps a launch at 2^32 threads: at most 4 Mi workgroups of 512 threads per launch (a larger grid
+// silently runs only part of its blocks — seen with 30.5 M tiles on MI355X / ROCm 7.2)
+constexpr u64 kMaxTilesPerLaunch = 4ull << 20;
+
+// the one place that names the eight k_join kernels (query_slots asks for the occupancy of one of them)
+static void launch_join(const ksp_engine* e, const bool c16, const dim3 grid, hipStream_t stream, const JoinArgs& args) {
+    const dim3 block(JW * 64);
+    if (e->use_cells) {
+        if (e->weighted) { if (c16) hipLaunchKernelGGL((k_join<true, true, true>), grid, block, 0, stream, args); else hipLaunchKernelGGL((k_join<true, false, true>), grid, block, 0, stream, args); }
+        else { if (c16) hipLaunchKernelGGL((k_join<false, true, true>), grid, block, 0, stream, args); else hipLaunchKernelGGL((k_join<false, false, true>), grid, block, 0, stream, args); }
+    } else {
+        if (e->weighted) { if (c16) hipLaunchKernelGGL((k_join<true, true, false>), grid, block, 0, stream, args); else hipLaunchKernelGGL((k_join<true, false, false>), grid, block, 0, stream, args); }
+        else { if (c16) hipLaunchKernelGGL((k_join<false, true, false>), grid, block, 0, stream, args); else hipLaunchKernelGGL((k_join<false, false, false>), grid, block, 0, stream, args); }
+    }
+}
+
+// the arguments both modes share; what a mode sets itself starts out empty (no work list, no split tiles, no match records)
+static JoinArgs join_args(const ksp_engine* e,const u64 tile_begin, ksp_edge* d_edges, const u64 capacity) {
+    JoinArgs a{};
+    a.brk = e->bkeys.as<u32>();
+    a.info = e->info.as<u32>();
+    a.bw = e->weighted ? e->bw.as<u32>() : nullptr;
+    a.bigmask = list_masks(e);
+    a.pmask = e->pmask_on ? e->pmask.as<uint4>() : nullptr;
+    a.blk_raw = e->blk_raw.as<u32>();
+    a.blk_pos = e->blk_pos.as<u32>();
+    a.cidx = e->part.as<u32>();
+    a.ncell = e->ncell;
+    a.blk_max = e->blk_max.as<u32>();
+    a.inv = e->smap.as<u32>() + 3 * smap_stride(e);
+    a.collect = e->collect ? 1u : 0u;
+    a.nb = e->nb;
+    a.n_sources = e->n_sources;
+    a.tile_begin = tile_begin;
+    a.out = d_edges;
+    a.cap = capacity;
+    a.out_count = e->count.as<unsigned long long>();
+    a.tail_sp = 1;
+    if (const char* dbg = std::getenv("KSP_DEBUG_ABLATE")) a.dbg = (u32)std::atoi(dbg);
+    return a;
+}
+
+// words of the split tiles' buffer: a tile of 32-bit counters per split tile, then its arrival counter, then slack
+static size_t split_buffer_words(const u32 nsplit) { return (size_t)nsplit * TB * TB + nsplit + 16; }
+
+// Work-list mode: the active tiles [act0, act1) of the work list, each in its shares.
+static int join_worklist(ksp_engine* e, JoinArgs a, const size_t act0, const size_t act1, hipStream_t st) {
+    int rc;
+    const u32 wgA = e->act_rec[4 * act0 + 2], wgB = e->act_rec[4 * act1 + 2];
+    const u32 spA = e->act_rec[4 * act0 + 3], spB = e->act_rec[4 * act1 + 3];
+    a.sched = e->sched_in_host ? e->h_sched + e->act_rec.size() : e->d_wg.as<u32>();
+    a.act = e->sched_in_host ? e->h_sched : e->d_act.as<u32>();
+    if (e->matches_on) { a.mrec = e->mr1.as<u64>(); a.mstart = e->mstart.as<u32>(); }
+    a.split0 = spA;
+    ZeroList zj{};
+    zero_add(zj, a.out_count, 8);
+    if (const u32 nsplit = spB - spA) {
+        const size_t words = split_buffer_words(nsplit);
+        if ((rc = e->tailbuf.ensure(words * 4))) return rc;
+        a.tailbuf = e->tailbuf.as<u32>();
+        a.tail_done = a.tailbuf + (size_t)nsplit * TB * TB;
+        if (words < (1ull << 30)) zero_add(zj, a.tailbuf, words * 4);
+        else KSP_HIP(hipMemsetAsync(a.tailbuf, 0, words * 4, st));
+    }
+    hipLaunchKernelGGL(k_zero_regions, dim3(256), dim3(256), 0, st, zj);   // (the edge counter and the split tiles' buffers: one launch)
+#ifdef KSP_WGTIME
+    if (std::getenv("KSP_WGTIME_FILE")) {   // (timing builds only, tools/wg_times.py)
+        e->wgt_n = wgB;
+        if ((rc = e->wgt_buf.ensure(e->wgt_n * 128))) return rc;
+        KSP_HIP(hipMemsetAsync(e->wgt_buf.p, 0, e->wgt_n * 128, st));
+        a.wgt = e->wgt_buf.as<unsigned long long>();
+    }
+#endif
+    // Two passes over the work list when some tile pairs two blocks that both hold a source of >= 2^16 k-mers: the
+    // tiles with packed 16-bit counters, then those with 32-bit counters (64 KB of LDS: two workgroups per CU).  The
+    // second pass runs on a stream of its own BESIDE the first — its few fat workgroups leave most of every CU's
+    // wave slots free (metagenome bins: 9.2 + 4.3 ms one after the other).
+    // (... and not at all when every share of the range stays below 2^16: build_schedule knows every share's bound)
+    bool pass32 = false;
+    for (size_t i = act0; e->need32 && !pass32 && i < act1; ++i) pass32 = e->act32[i] != 0;
+    bool two_streams = pass32 && !std::getenv("KSP_DEBUG_ONE_STREAM");
+    if (two_streams) {   // (the stream and its events are made when first needed; without them: one stream)
+        if (!e->aux_stream && hipStreamCreateWithFlags(&e->aux_stream, hipStreamNonBlocking) != hipSuccess) two_streams = false;
+        for (int i = 0; i < 2 && two_streams; ++i)
+            if (!e->ev_aux[i] && hipEventCreateWithFlags(&e->ev_aux[i], hipEventDisableTiming) != hipSuccess) two_streams = false;
+    }
+    if (two_streams) {
+        KSP_HIP(hipEventRecord(e->ev_aux[0], st));                    // (the zeroing launch above)
+        KSP_HIP(hipStreamWaitEvent(e->aux_stream, e->ev_aux[0], 0));
+    }
+    for (int pass = 0; pass < (pass32 ? 2 : 1); ++pass) {
+        hipStream_t ps = (pass == 1 && two_streams) ? e->aux_stream : st;
+        for (u64 w = wgA; w < wgB; w += kMaxTilesPerLaunch) {
+            a.wg0 = (u32)w;
+            launch_join(e, pass == 0, dim3((u32)std::min<u64>(kMaxTilesPerLaunch, wgB - w)), ps, a);
+        }
+    }
+    if (two_streams) {
+        KSP_HIP(hipEventRecord(e->ev_aux[1], e->aux_stream));
+        KSP_HIP(hipStreamWaitEvent(st, e->ev_aux[1], 0));             // (the count is read behind both passes)
+    }
+    KSP_HIP(hipGetLastError());
+    return KSP_OK;
+}
+
+// Dense mode: every tile of [tile_begin, tile_end), one workgroup each.
+static int join_dense(ksp_engine* e, JoinArgs a, const u64 tile_begin, const u64 tile_end, hipStream_t st) {
+    int rc;
+    ZeroList zj{};
+    zero_add(zj, a.out_count, 8);
+    hipLaunchKernelGGL(k_zero_regions, dim3(1), dim3(64), 0, st, zj);   // (the edge counter)
+    for (u64 chunk_begin = tile_begin; chunk_begin < tile_end; chunk_begin += kMaxTilesPerLaunch) {
+        const u64 chunk_end = std::min(tile_end, chunk_begin + kMaxTilesPerLaunch);
+        a.tile_begin = chunk_begin;
+        const u32 ntiles = (u32)(chunk_end - chunk_begin);
+        // Tile splitting for small launches: when there are fewer tiles than workgroup slots on the chip,
+        // every tile is cut into `sp` rank-range shares (partial counters are summed in a global buffer).
+        u32 n_tail = 0, sp = 1;
+        if ((rc = query_slots(e))) return rc;
+        // (Measured on C2, 3160 tiles on 768 slots: splitting the 88 "remainder" tiles does not pay — tiles
+        //  finish at different times and the dispatcher back-fills — so only under-filled launches split.)
+        if (!std::getenv("KSP_NO_TAIL_SPLIT")) {
+            const u32 r = ntiles < e->slots ? ntiles : 0;
+            if (r > 0 && (u64)r * 4 <= (u64)e->slots * 3) {
+                sp = std::min<u32>(8, e->slots / r);
+                if (sp >= 2) n_tail = r; else sp = 1;
+            }
+        }
+        a.n_normal = ntiles - n_tail;
+        a.tail_sp = sp;
+        a.tailbuf = nullptr;
+        if (n_tail) {
+            if ((rc = e->tailbuf.ensure((size_t)n_tail * TB * TB * 4))) return rc;
+            a.tailbuf = e->tailbuf.as<u32>();
+            KSP_HIP(hipMemsetAsync(a.tailbuf, 0, (size_t)n_tail * TB * TB * 4, st));
+        }
+        // packed 16-bit counters wherever they are exact; 32-bit counters for the other tiles
+        launch_join(e, true, dim3(a.n_normal + n_tail * sp), st, a);
+        if (n_tail) hipLaunchKernelGGL(k_tail_emit, dim3(n_tail), dim3(JW * 64), 0, st, a);
+        if (e->need32) {   // tiles whose two blocks both hold huge sketches: one workgroup per tile, no tail split
+            JoinArgs b = a;
+            b.n_normal = ntiles;
+            b.tail_sp = 1;
+            b.tailbuf = nullptr;
+            launch_join(e, false, dim3(ntiles), st, b);
+        }
+        KSP_HIP(hipGetLastError());
+    }
+    return KSP_OK;
+}
+
+// The edge count follows the join to the host.  Lean: by a kernel of ours with a sequence number behind it (no event in the
+// stream; ksp_engine_join_wait polls the number); otherwise a copy between the events that time the join.
+static int queue_join_count(ksp_engine* e, const unsigned long long* d_count, hipStream_t st) {
+    e->join_flag = false;
+    if (e->lean) {
+        e->join_seq += 1;
+        e->join_flag = true;
+        e->rb_stream = st;
+        hipLaunchKernelGGL(k_readback, dim3(1), dim3(64), 0, st, reinterpret_cast<const u64*>(d_count), reinterpret_cast<u64*>(e->h_count), 1u,
+                           e->h_count + 6, e->join_seq);
+    } else {
+        KSP_HIP(hipEventRecord(e->ev[3], st));
+        KSP_HIP(hipMemcpyAsync(e->h_count, d_count, 8, hipMemcpyDeviceToHost, st));
+        KSP_HIP(hipEventRecord(e->ev_join_done, st));
+    }
+    return KSP_OK;
+}
+
+// (stats) bytes the join streams from the block lists: only the 32-bit ranks (posting words are gathered on matches); a
+// diagonal tile reads its one list, with the weights when there are any
+static u64 join_stream_bytes(const ksp_engine* e, const u64 tile_begin, const u64 tile_end, const size_t act0, const size_t act1) {
+    const u64 per = 4, self = e->weighted ? 8 : 4;
+    const std::vector<u32>& off = e->h_blk_off;
+    u64 bytes = 0;
+    for (size_t i = act0; e->sched_on && i < act1; ++i) {   // work-list mode: the active tiles only
+        const u32 I = e->act_rec[4 * i], J = e->act_rec[4 * i + 1];
+        const u64 kI = off[I + 1] - off[I], kJ = off[J + 1] - off[J];
+        bytes += (J == I) ? kI * self : (kI + kJ) * per;
+    }
+    for (u64 t = tile_begin; !e->sched_on && t < tile_end;) {   // dense mode, row by row in closed form (h_blk_off is a prefix sum)
+        u32 I, J;
+        tile_decode(t, e->nb, I, J);
+        const u64 stop = std::min(tile_row_start((u64)I + 1, e->nb), tile_end);
+        const u64 kI = off[I + 1] - off[I];
+        u64 cnt = stop - t, J0 = J;
+        if (J0 == I) { bytes += kI * self; ++J0; --cnt; }
+        if (cnt) bytes += (cnt * kI + (u64)(off[J0 + cnt] - off[J0])) * per;
+        t = stop;
+    }
+    return bytes;
+}
+
 int ksp_engine_join_launch(ksp_engine* e, uint64_t tile_begin, uint64_t tile_end, ksp_edge* d_edges, uint64_t capacity, void* stream) {
     if (!e) { set_error("join: NULL argument"); return KSP_E_ARG; }
     if (!e->built) { set_error("join: build_blocks has not been run"); return KSP_E_ARG; }
@@ -2511,197 +2677,26 @@ int ksp_engine_join_launch(ksp_engine* e, uint64_t tile_begin, uint64_t tile_end
     if (none) return KSP_OK;
     int rc;
     if ((rc = e->count.ensure(64))) return rc;
-    JoinArgs a;
-    a.brk = e->bkeys.as<u32>();
-    a.info = e->info.as<u32>();
-    a.bw = e->weighted ? e->bw.as<u32>() : nullptr;
-    a.bigmask = list_masks(e);
-    a.pmask = e->pmask_on ? e->pmask.as<uint4>() : nullptr;
-    a.blk_raw = e->blk_raw.as<u32>();
-    a.blk_pos = e->blk_pos.as<u32>();
-    a.cidx = e->part.as<u32>();
-    a.ncell = e->ncell;
-    a.nb = e->nb;
-    a.n_sources = e->n_sources;
-    a.tile_begin = tile_begin;
-    a.out = d_edges;
-    a.cap = capacity;
-    a.out_count = e->count.as<unsigned long long>();
-    a.dbg = 0;
-    if (const char* dbg = std::getenv("KSP_DEBUG_ABLATE")) a.dbg = (u32)std::atoi(dbg);
-    ZeroList zj{};
-    zero_add(zj, a.out_count, 8);
+    const JoinArgs a = join_args(e, tile_begin, d_edges, capacity);
     if (!e->lean) KSP_HIP(hipEventRecord(e->ev[2], st));
-    dim3 block(JW * 64);
-    a.blk_max = e->blk_max.as<u32>();
-    a.inv = e->smap.as<u32>() + 3 * smap_stride(e);
-    a.sched = nullptr; a.act = nullptr; a.wg0 = 0; a.split0 = 0; a.tail_done = nullptr;
-    a.collect = e->collect ? 1u : 0u;
-    a.mrec = nullptr; a.mstart = nullptr;
 #ifdef KSP_WGTIME
-    ksp::Buf& wgt_buf = e->wgt_buf;   // (timing builds only, tools/wg_times.py)
-    a.wgt = nullptr;
-    const char* wgt_file = std::getenv("KSP_WGTIME_FILE");
-    size_t& wgt_n = e->wgt_n;
-    wgt_n = 0;
+    e->wgt_n = 0;
 #endif
-    auto launch = [&](bool c16, dim3 grid, const JoinArgs& args) {
-        if (e->use_cells) {
-            if (e->weighted) { if (c16) hipLaunchKernelGGL((k_join<true, true, true>), grid, block, 0, st, args); else hipLaunchKernelGGL((k_join<true, false, true>), grid, block, 0, st, args); }
-            else { if (c16) hipLaunchKernelGGL((k_join<false, true, true>), grid, block, 0, st, args); else hipLaunchKernelGGL((k_join<false, false, true>), grid, block, 0, st, args); }
-        } else {
-            if (e->weighted) { if (c16) hipLaunchKernelGGL((k_join<true, true, false>), grid, block, 0, st, args); else hipLaunchKernelGGL((k_join<true, false, false>), grid, block, 0, st, args); }
-            else { if (c16) hipLaunchKernelGGL((k_join<false, true, false>), grid, block, 0, st, args); else hipLaunchKernelGGL((k_join<false, false, false>), grid, block, 0, st, args); }
-        }
-    };
-    // HIP caps a launch at 2^32 threads: at most 4 Mi workgroups of 512 threads per launch (a larger grid
-    // silently runs only part of its blocks — seen with 30.5 M tiles on MI355X / ROCm 7.2)
-    const u64 kMaxTilesPerLaunch = 4ull << 20;
     size_t act0 = 0, act1 = 0;
-    if (e->sched_on && st != e->sched_stream) KSP_HIP(hipStreamSynchronize(e->sched_stream));   // (work list uploaded on the build's stream)
     if (e->sched_on) {
-        // work-list mode: the active tiles of [tile_begin, tile_end), each in its shares
-        act0 = std::lower_bound(e->act_tid.begin(), e->act_tid.end(), tile_begin) - e->act_tid.begin();
-        act1 = std::lower_bound(e->act_tid.begin(), e->act_tid.end(), tile_end) - e->act_tid.begin();
-        const u32 wgA = e->act_rec[4 * act0 + 2], wgB = e->act_rec[4 * act1 + 2];
-        const u32 spA = e->act_rec[4 * act0 + 3], spB = e->act_rec[4 * act1 + 3];
-        a.sched = e->sched_in_host ? e->h_sched + e->act_rec.size() : e->d_wg.as<u32>();
-        a.act = e->sched_in_host ? e->h_sched : e->d_act.as<u32>();
-        if (e->matches_on) { a.mrec = e->mr1.as<u64>(); a.mstart = e->mstart.as<u32>(); }
-        a.split0 = spA;
-        a.n_normal = 0; a.tail_sp = 1;
-        a.tailbuf = nullptr;
-        const u32 nsplit = spB - spA;
-        if (nsplit) {
-            if ((rc = e->tailbuf.ensure(((size_t)nsplit * TB * TB + nsplit + 16) * 4))) return rc;
-            a.tailbuf = e->tailbuf.as<u32>();
-            a.tail_done = a.tailbuf + (size_t)nsplit * TB * TB;
-            if (((size_t)nsplit * TB * TB + nsplit + 16) < (1ull << 30)) zero_add(zj, a.tailbuf, ((size_t)nsplit * TB * TB + nsplit + 16) * 4);
-            else KSP_HIP(hipMemsetAsync(a.tailbuf, 0, ((size_t)nsplit * TB * TB + nsplit + 16) * 4, st));
-        }
-        hipLaunchKernelGGL(k_zero_regions, dim3(256), dim3(256), 0, st, zj);   // (the edge counter and the split tiles' buffers: one launch)
-        zj.n = 0;
-#ifdef KSP_WGTIME
-        if (wgt_file) {
-            wgt_n = wgB;
-            if ((rc = wgt_buf.ensure(wgt_n * 128))) return rc;
-            KSP_HIP(hipMemsetAsync(wgt_buf.p, 0, wgt_n * 128, st));
-            a.wgt = wgt_buf.as<unsigned long long>();
-        }
-#endif
-        // Two passes over the work list when some tile pairs two blocks that both hold a source of >= 2^16 k-mers: the
-        // tiles with packed 16-bit counters, then those with 32-bit counters (64 KB of LDS: two workgroups per CU).  The
-        // second pass runs on a stream of its own BESIDE the first — its few fat workgroups leave most of every CU's
-        // wave slots free (metagenome bins: 9.2 + 4.3 ms one after the other).
-        // (... and not at all when every share of the range stays below 2^16: build_schedule knows every share's bound)
-        bool pass32 = false;
-        for (size_t i = act0; e->need32 && !pass32 && i < act1; ++i) pass32 = e->act32[i] != 0;
-        bool two_streams = pass32 && !std::getenv("KSP_DEBUG_ONE_STREAM");
-        if (two_streams) {
-            if (!e->aux_stream && hipStreamCreateWithFlags(&e->aux_stream, hipStreamNonBlocking) != hipSuccess) two_streams = false;
-            for (int i = 0; i < 2 && two_streams; ++i)
-                if (!e->ev_aux[i] && hipEventCreateWithFlags(&e->ev_aux[i], hipEventDisableTiming) != hipSuccess) two_streams = false;
-        }
-        if (two_streams) {
-            KSP_HIP(hipEventRecord(e->ev_aux[0], st));                    // (the zeroing launch above)
-            KSP_HIP(hipStreamWaitEvent(e->aux_stream, e->ev_aux[0], 0));
-        }
-        for (int pass = 0; pass < (pass32 ? 2 : 1); ++pass) {
-            hipStream_t ps = (pass == 1 && two_streams) ? e->aux_stream : st;
-            for (u64 w = wgA; w < wgB; w += kMaxTilesPerLaunch) {
-                a.wg0 = (u32)w;
-                const dim3 grid((u32)std::min<u64>(kMaxTilesPerLaunch, wgB - w));
-                const bool c16 = pass == 0;
-                if (e->use_cells) {
-                    if (e->weighted) { if (c16) hipLaunchKernelGGL((k_join<true, true, true>), grid, block, 0, ps, a); else hipLaunchKernelGGL((k_join<true, false, true>), grid, block, 0, ps, a); }
-                    else { if (c16) hipLaunchKernelGGL((k_join<false, true, true>), grid, block, 0, ps, a); else hipLaunchKernelGGL((k_join<false, false, true>), grid, block, 0, ps, a); }
-                } else {
-                    if (e->weighted) { if (c16) hipLaunchKernelGGL((k_join<true, true, false>), grid, block, 0, ps, a); else hipLaunchKernelGGL((k_join<true, false, false>), grid, block, 0, ps, a); }
-                    else { if (c16) hipLaunchKernelGGL((k_join<false, true, false>), grid, block, 0, ps, a); else hipLaunchKernelGGL((k_join<false, false, false>), grid, block, 0, ps, a); }
-                }
-            }
-        }
-        if (two_streams) {
-            KSP_HIP(hipEventRecord(e->ev_aux[1], e->aux_stream));
-            KSP_HIP(hipStreamWaitEvent(st, e->ev_aux[1], 0));             // (the count is read behind both passes)
-        }
-        KSP_HIP(hipGetLastError());
-    }
-    if (zj.n) { hipLaunchKernelGGL(k_zero_regions, dim3(1), dim3(64), 0, st, zj); zj.n = 0; }   // (dense mode: the edge counter)
-    for (u64 chunk_begin = tile_begin; !e->sched_on && chunk_begin < tile_end; chunk_begin += kMaxTilesPerLaunch) {
-    const u64 chunk_end = std::min(tile_end, chunk_begin + kMaxTilesPerLaunch);
-    a.tile_begin = chunk_begin;
-    const u32 ntiles = (u32)(chunk_end - chunk_begin);
-    // Tile splitting for small launches: when there are fewer tiles than workgroup slots on the chip,
-    // every tile is cut into `sp` rank-range shares (partial counters are summed in a global buffer).
-    u32 n_tail = 0, sp = 1;
-    if ((rc = query_slots(e))) return rc;
-    // (Measured on C2, 3160 tiles on 768 slots: splitting the 88 "remainder" tiles does not pay — tiles
-    //  finish at different times and the dispatcher back-fills — so only under-filled launches split.)
-    if (!std::getenv("KSP_NO_TAIL_SPLIT")) {
-        const u32 r = ntiles < e->slots ? ntiles : 0;
-        if (r > 0 && (u64)r * 4 <= (u64)e->slots * 3) {
-            sp = std::min<u32>(8, e->slots / r);
-            if (sp >= 2) n_tail = r; else sp = 1;
-        }
-    }
-    a.n_normal = ntiles - n_tail;
-    a.tail_sp = sp;
-    a.tailbuf = nullptr;
-    if (n_tail) {
-        if ((rc = e->tailbuf.ensure((size_t)n_tail * TB * TB * 4))) return rc;
-        a.tailbuf = e->tailbuf.as<u32>();
-        KSP_HIP(hipMemsetAsync(a.tailbuf, 0, (size_t)n_tail * TB * TB * 4, st));
-    }
-    dim3 grid(a.n_normal + n_tail * sp);
-    // packed 16-bit counters wherever they are exact; 32-bit counters for the other tiles
-    launch(true, grid, a);
-    if (n_tail) hipLaunchKernelGGL(k_tail_emit, dim3(n_tail), block, 0, st, a);
-    if (e->need32) {   // tiles whose two blocks both hold huge sketches: one workgroup per tile, no tail split
-        JoinArgs b = a;
-        b.n_normal = ntiles;
-        b.tail_sp = 1;
-        b.tailbuf = nullptr;
-        launch(false, dim3(ntiles), b);
-    }
-    KSP_HIP(hipGetLastError());
-    }   // launch chunks
-    e->join_flag = false;
-    if (e->lean) {   // the count and a sequence number behind it, by a kernel of ours: no event in the stream
-        e->join_seq += 1;
-        e->join_flag = true;
-        e->rb_stream = st;
-        hipLaunchKernelGGL(k_readback, dim3(1), dim3(64), 0, st, reinterpret_cast<const u64*>(a.out_count), reinterpret_cast<u64*>(e->h_count), 1u,
-                           e->h_count + 6, e->join_seq);
+        if (st != e->sched_stream) KSP_HIP(hipStreamSynchronize(e->sched_stream));   // (work list uploaded on the build's stream)
+        act0 = first_active(e, tile_begin);
+        act1 = first_active(e, tile_end);
+        rc = join_worklist(e, a, act0, act1, st);
     } else {
-        KSP_HIP(hipEventRecord(e->ev[3], st));
-        KSP_HIP(hipMemcpyAsync(e->h_count, a.out_count, 8, hipMemcpyDeviceToHost, st));
-        KSP_HIP(hipEventRecord(e->ev_join_done, st));
+        rc = join_dense(e, a, tile_begin, tile_end, st);
     }
+    if (rc || (rc = queue_join_count(e, a.out_count, st))) return rc;
     // what ksp_engine_join_wait reports besides the count: known now (a build may start on this engine before the wait)
     e->jst.last_tiles = tile_end - tile_begin;
     e->jst.last_active_tiles = e->sched_on ? (u64)(act1 - act0) : tile_end - tile_begin;
     e->jst.last_pairs = ksp_engine_tile_pairs(e, tile_begin, tile_end);
-    {   // bytes the kernel streams from both block lists; self tiles read info [+ weight] only
-        const u64 per = 4;   // only the 32-bit ranks are streamed; posting words are gathered on matches
-        u64 bytes = 0;
-        for (size_t i = act0; e->sched_on && i < act1; ++i) {   // work-list mode: the active tiles only
-            const u32 I = e->act_rec[4 * i], J = e->act_rec[4 * i + 1];
-            const u64 kI = e->h_blk_off[I + 1] - e->h_blk_off[I], kJ = e->h_blk_off[J + 1] - e->h_blk_off[J];
-            bytes += (J == I) ? kI * (e->weighted ? 8 : 4) : (kI + kJ) * per;
-        }
-        for (u64 t = tile_begin; !e->sched_on && t < tile_end;) {   // dense mode, row by row in closed form (h_blk_off is a prefix sum)
-            u32 I, J;
-            tile_decode(t, e->nb, I, J);
-            u64 stop = std::min(tile_row_start((u64)I + 1, e->nb), tile_end);
-            u64 kI = e->h_blk_off[I + 1] - e->h_blk_off[I];
-            u64 cnt = stop - t, J0 = J;
-            if (J0 == I) { bytes += kI * (e->weighted ? 8 : 4); ++J0; --cnt; }
-            if (cnt) bytes += (cnt * kI + (u64)(e->h_blk_off[J0 + cnt] - e->h_blk_off[J0])) * per;
-            t = stop;
-        }
-        e->jst.last_stream_bytes = bytes;
-    }
+    e->jst.last_stream_bytes = join_stream_bytes(e, tile_begin, tile_end, act0, act1);
     e->join_cap = capacity;
     e->join_st = st;
     e->join_pending = true;
@@ -2716,14 +2711,7 @@ int ksp_engine_join_wait(ksp_engine* e, uint64_t* h_count) {
     KSP_HIP(hipSetDevice(e->device));
     if (e->join_flag) {
         e->join_flag = false;
-        volatile unsigned long long* f = reinterpret_cast<volatile unsigned long long*>(e->h_count + 6);
-        for (unsigned long long spins = 1; *f != e->join_seq; ++spins) {
-            if ((spins & 0xFFFFF) == 0) {   // (now and then: is the stream still alive?)
-                const hipError_t q = hipStreamQuery(e->join_st);
-                if (q == hipSuccess && *f != e->join_seq) KSP_HIP(hipErrorUnknown);
-                if (q != hipErrorNotReady && q != hipSuccess) KSP_HIP(q);
-            }
-        }
+        KSP_HIP(poll_seq(e->h_count + 6, e->join_seq, e->join_st));
         e->st.ms_join = 0;
     } else {
         KSP_HIP(hipEventSynchronize(e->ev_join_done));
@@ -2761,6 +2749,32 @@ int ksp_engine_join(ksp_engine* e, uint64_t tile_begin, uint64_t tile_end, ksp_e
     return ksp_engine_join_wait(e, h_count);
 }
 
+// ksp_engine_join_to_host's next piece [t, t_next): whole tiles while their edge bound fits the limit (one tile at least).  The
+// limit: a staging buffer of `cap` edges over the densest found / bound ratio so far (+ 50 %), halved per overflow (`shrink`).
+// `ai`, `a_end`: the work list's cursor and end (work-list mode); a_next is the cursor behind the piece.
+struct Piece {
+    u64 t_next, bound;
+    size_t a_next;
+};
+static Piece next_piece(const ksp_engine* e, const u64 t, const u64 tile_end, const u64 cap, const double ratio, const u64 shrink,
+                        const size_t ai, const size_t a_end) {
+    u64 limit = ratio > 0 ? (u64)((double)cap / (1.5 * ratio)) : cap;
+    limit = std::max<u64>(limit / shrink, 1);
+    Piece p{tile_end, 0, ai};
+    if (e->sched_on) {
+        for (; p.a_next < a_end; ++p.a_next) {
+            const u64 b = active_tile_pairs(e, p.a_next);
+            if (p.bound && p.bound + b > limit) { p.t_next = e->act_tid[p.a_next]; break; }
+            p.bound += b;
+        }
+    } else {
+        const u64 per = std::max<u64>(1, limit / ((u64)TB * TB));
+        p.t_next = std::min(tile_end, t + per);
+        p.bound = ksp_engine_tile_pairs(e, t, p.t_next);
+    }
+    return p;
+}
+
 // The edges of tiles [tile_begin, tile_end) straight into the caller's (pinned) host buffer: the range is cut into
 // pieces by the edge bound, piece k + 1 is joined while piece k travels over PCIe on a stream of its own.  The
 // reference has no such step (its pair map lives in host memory, src/pairwise.cpp:191); here the result of the
@@ -2788,9 +2802,8 @@ int ksp_engine_join_to_host(ksp_engine* e, uint64_t tile_begin, uint64_t tile_en
     int rc = KSP_OK;
     for (int i = 0; i < 2; ++i)
         if ((rc = e->stage[i].ensure((cap + 16) * sizeof(ksp_edge)))) return rc;
-    const std::vector<u32>& P = e->h_blk_src;
-    size_t ai = e->sched_on ? std::lower_bound(e->act_tid.begin(), e->act_tid.end(), tile_begin) - e->act_tid.begin() : 0;
-    const size_t a_end = e->sched_on ? std::lower_bound(e->act_tid.begin(), e->act_tid.end(), tile_end) - e->act_tid.begin() : 0;
+    size_t ai = e->sched_on ? first_active(e, tile_begin) : 0;
+    const size_t a_end = e->sched_on ? first_active(e, tile_end) : 0;
     u64 total = 0;
     float ms = 0;
     u64 tiles = 0, act = 0, pairs = 0, bytes = 0;
@@ -2801,24 +2814,8 @@ int ksp_engine_join_to_host(ksp_engine* e, uint64_t tile_begin, uint64_t tile_en
     u64 shrink = 1;        // (a piece that overflowed: the limit divided by this until one fits)
     u64 t = tile_begin;
     for (u32 k = 0; t < tile_end;) {
-        u64 limit = ratio > 0 ? (u64)((double)cap / (1.5 * ratio)) : cap;
-        limit = std::max<u64>(limit / shrink, 1);
-        // the piece [t, t_next): whole tiles while their bound fits the limit (one tile at least)
-        u64 t_next = tile_end, bound = 0;
-        size_t aj = ai;
-        if (e->sched_on) {
-            for (; aj < a_end; ++aj) {
-                const u32 I = e->act_rec[4 * aj], J = e->act_rec[4 * aj + 1];
-                const u64 nI = P[I + 1] - P[I], nJ = P[J + 1] - P[J];
-                const u64 b = (I == J) ? nI * (nI ? nI - 1 : 0) / 2 : nI * nJ;
-                if (bound && bound + b > limit) { t_next = e->act_tid[aj]; break; }
-                bound += b;
-            }
-        } else {
-            const u64 per = std::max<u64>(1, limit / ((u64)TB * TB));
-            t_next = std::min(tile_end, t + per);
-            bound = ksp_engine_tile_pairs(e, t, t_next);
-        }
+        const Piece piece = next_piece(e, t, tile_end, cap, ratio, shrink, ai, a_end);
+        const u64 t_next = piece.t_next, bound = piece.bound;
         Buf& sb = e->stage[k & 1];
         if (k >= 2) KSP_HIP(hipStreamWaitEvent(st, e->ev_copy[k & 1], 0));   // (the copy that last read this staging buffer)
         u64 cnt = 0;
@@ -2841,7 +2838,7 @@ int ksp_engine_join_to_host(ksp_engine* e, uint64_t tile_begin, uint64_t tile_en
         KSP_HIP(hipEventRecord(e->ev_copy[k & 1], e->copy_stream));
         total += cnt;
         t = t_next;
-        ai = aj;
+        ai = piece.a_next;
         ++k;
     }
     KSP_HIP(hipStreamSynchronize(e->copy_stream));
