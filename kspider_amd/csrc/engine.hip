@@ -1950,6 +1950,7 @@ static void reset_for_build(ksp_engine* e, const u32 n_sources, const u64 n, con
     e->built = false;
     e->slice_ready = false;
     e->post_slice = false;
+    e->slice_phase = 0;   // an accepted build forgets an unfinished slice (the slice builds set it to 1 once they have succeeded)
     e->sched_on = false; e->collect = false; e->have_bits = false; e->matches_on = false; e->pmask_on = false; e->lists_path = 0;
     e->act_tid.clear(); e->act_rec.clear();
     e->part_fail = 0;   // (stats: partition_fallback describes this build)
@@ -2009,8 +2010,8 @@ static int build_common(ksp_engine* e, const uint64_t* d_keys, const uint32_t* d
     if (join_elsewhere(e, st, "build")) return KSP_E_ARG;
     KSP_HIP(hipSetDevice(e->device));
     reset_for_build(e, n_sources, n, d_weights != nullptr, key_bits, part, nparts);
-    // of the sketch path alone: slice_phase is left as it is (the callers set it); unchanged offsets keep h_off and their
-    // copy on the device; the switches of the stage-1 paths that only sketches take
+    // of the sketch path alone: unchanged offsets keep h_off and their copy on the device; the switches of the stage-1 paths
+    // that only sketches take
     const bool same_offsets = e->d_off_sketch && e->h_off.size() == (size_t)n_sources + 1 &&
                               std::memcmp(e->h_off.data(), h_offsets, ((size_t)n_sources + 1) * 8) == 0;
     if (!same_offsets) { e->h_off.assign(h_offsets, h_offsets + n_sources + 1); e->d_off_sketch = false; e->seg_groups_ok = false; }
@@ -2103,9 +2104,8 @@ static int build_postings_common(ksp_engine* e, const uint64_t* h_key_off, const
     if (join_elsewhere(e, st, "build_postings")) return KSP_E_ARG;
     KSP_HIP(hipSetDevice(e->device));
     reset_for_build(e, n_sources, n, d_key_weights != nullptr, /*key_bits*/ 0, /*part*/ 0, /*nparts*/ 1);
-    // of the postings path alone: an unfinished slice is forgotten; there are no sketch offsets to keep (d_off takes the key
-    // offsets below); none of the sketch path's stage-1 switches is read
-    e->slice_phase = 0;
+    // of the postings path alone: there are no sketch offsets to keep (d_off takes the key offsets below); none of the sketch
+    // path's stage-1 switches is read
     e->h_off.clear();
     if (n == 0 || e->nb == 0) {   // nothing can intersect
         e->st.n_block_keys = 0;
@@ -2306,6 +2306,9 @@ int ksp_engine_slice_sizes(const ksp_engine* e, uint64_t out[4]) {
     return KSP_OK;
 }
 
+// The finished slice's lists, copied out of the engine's buffers.  Defined between ksp_engine_slice_finish and
+// ksp_engine_assemble.  After the assemble the call is still accepted (slice_ready holds), but those buffers hold the assembled
+// lists by then and slice_hdr the last slice's sizes: what it copies is left unspecified, and nothing tests it.
 int ksp_engine_slice_export(ksp_engine* e, uint32_t* d_brk, uint32_t* d_info, uint32_t* d_bw, uint32_t* d_blk_raw,
                             uint32_t* d_blk_pos, void* d_big, void* stream) {
     if (!e || !e->slice_ready) { set_error("slice_export: build_slice has not been run"); return KSP_E_ARG; }

@@ -4,7 +4,11 @@ of their own.
 
 The engine keeps a lot from one call to the next (grown buffers that are never cleared, zeroing and staging flags, the
 offsets of the last build, fall-backs that hold for the rest of its life).  The other suites mostly build once per
-engine; here the pool of inputs is walked big -> small -> big, so stale buffers hold the data of a bigger build."""
+engine; here the pool of inputs is walked big -> small -> big, so stale buffers hold the data of a bigger build.
+
+Sections E to G put the slice protocol (build_slice ... assemble, tests/slice_driver.py) into such sequences: whole builds
+behind a slice left at any phase, refused builds inside a protocol, slice calls out of order, slices as operations of
+the seeded sequences, and seeded walks over the state table of tests/engine_states.py."""
 import ctypes
 import functools
 
@@ -13,7 +17,11 @@ import pytest
 
 from kspider_amd import engine, synth
 
+import engine_states as ES
+from slice_driver import STOPS, Protocol, postings_slice_build, sketch_slice_build
+from slice_driver import _run as slice_run
 from test_fuzz_gpu import MODES
+from test_slices_edges_gpu import SLICE_MODES
 
 pytestmark = pytest.mark.gpu
 
@@ -735,3 +743,480 @@ def test_build_on_another_stream_than_a_pending_join_is_refused(pool, edges_buf,
     assert _same(_full_join(e, b, edges_buf, stream=s2), b.ref)
     pend.free()
     e.close()
+
+
+# ---- E: sliced builds inside call sequences --------------------------------------------------------------------------
+# (what tests/test_slices*_gpu.py leave out: they run the slice protocol in its documented order on a fresh engine)
+
+SLICE_CALLS = ("slice_labels", "slice_bounds", "slice_set_bounds", "slice_finish")
+REFUSED_BUILDS = ("monotone", "first", "limit", "key_bits", "part")
+
+
+def _key_count_cuts(inp, nparts):
+    n_keys = inp.key_off.size - 1
+    return [n_keys * s // nparts for s in range(nparts + 1)]
+
+
+def _slice_build(inp, nparts):
+    """build(e, p) of the slice driver for a pool input: sketches by key range, postings by key count."""
+    if inp.kind == "post":
+        return postings_slice_build(inp.key_off, inp.d_srcbuf.ptr.value, inp.d_weights, inp.n_sources, _key_count_cuts(inp, nparts))
+    return sketch_slice_build(inp.d_keys.ptr.value, inp.offsets, nparts, inp.d_weights)
+
+
+def _protocol(e, inp, nparts, sum_bounds=None, hook=None):
+    sum_bounds = inp.kind == "post" if sum_bounds is None else sum_bounds
+    return Protocol(e, inp.n_sources, nparts, _slice_build(inp, nparts), sum_bounds=sum_bounds, hook=hook)
+
+
+def _sliced(e, inp, nparts, sum_bounds=None, stop=None):
+    """The slice driver on engine e: the edges (None when stopped)."""
+    sum_bounds = inp.kind == "post" if sum_bounds is None else sum_bounds
+    return slice_run(inp.n_sources, nparts, _slice_build(inp, nparts), sum_bounds=sum_bounds, engine_=e, stop=stop)[0]
+
+
+def _refusal(call, stem=None, code=None):
+    """call() raises KspError `code` (KSP_E_ARG) whose message holds `stem`."""
+    with pytest.raises(engine.KspError) as ei:
+        call()
+    assert ei.value.code == (engine.KSP_E_ARG if code is None else code), (ei.value.code, str(ei.value))
+    if stem is not None:
+        assert stem in str(ei.value), str(ei.value)
+
+
+def _no_slice_at_labels(e, scratch):
+    for name in SLICE_CALLS:
+        _refusal(lambda: getattr(e, name)(scratch.ptr.value), "build_slice has not been run")
+
+
+def _no_finished_slice(e, scratch):
+    p = scratch.ptr.value
+    _refusal(e.slice_sizes)
+    _refusal(lambda: e.slice_export(p, p, p, p, p, p))
+    _refusal(lambda: e.assemble(np.zeros(4, dtype=np.uint64), p, p, p, 1, p, p, p, 1))
+
+
+def _not_joinable(e, buf):
+    T = e.num_tiles
+    host = np.zeros(4, dtype=engine.EDGE_DTYPE)
+    _refusal(lambda: e.join(0, T, buf.ptr.value, CAP), "build_blocks has not been run")
+    _refusal(lambda: e.join_launch(0, T, buf.ptr.value, CAP), "build_blocks has not been run")
+    _refusal(lambda: e.join_to_host(0, T, host.ctypes.data, host.size), "build_blocks has not been run")
+    _refusal(lambda: e.balanced_cuts(2), "has not been run")
+    assert e.edge_bound(0, T) == 0 and e.lists_path() == 0
+
+
+def _refused_build(e, kind, dk):
+    """One build that the engine refuses on its arguments (the kinds of Runner.refused that change nothing)."""
+    small = np.array([0, 3, 9], dtype=np.uint64)
+    if kind == "monotone":
+        _refusal(lambda: e.build_blocks(dk, np.array([0, 5, 3, 9], dtype=np.uint64)))
+    elif kind == "first":
+        _refusal(lambda: e.build_blocks(dk, np.array([2, 5, 9], dtype=np.uint64)))
+    elif kind == "limit":
+        _refusal(lambda: e.build_blocks(dk, np.array([0, 1 << 29, 1 << 30], dtype=np.uint64)), code=engine.KSP_E_LIMIT)
+    elif kind == "key_bits":
+        _refusal(lambda: e.build_blocks(dk, small, key_bits=65))
+    else:
+        _refusal(lambda: e.build_slice(dk, small, 2, 2))
+
+
+@pytest.fixture(scope="module")
+def scratch(pool):
+    """4 bytes per source of the largest pool input: what the slice calls copy labels and bounds into."""
+    return engine.DeviceBuffer(4 * max(inp.n_sources for inp in pool.values()) + 64)
+
+
+@pytest.mark.parametrize("whole", ["build_blocks", "step_launch", "build_postings"])
+@pytest.mark.parametrize("abandoned", ["build", "labels", "set_bounds"])
+@pytest.mark.parametrize("start", ["build_slice", "build_postings_slice"])
+def test_whole_build_forgets_an_unfinished_slice(pool, edges_buf, scratch, start, abandoned, whole):
+    """A slice left after its build, after slice_labels or after slice_bounds + slice_set_bounds, then a whole build of a
+    smaller input: the slice is forgotten (no slice call is accepted: slice_finish would run the second half of a slice
+    build over a whole build's state), and the whole build is all the engine knows."""
+    sl = pool["n700" if start == "build_slice" else "post700w"]
+    inp = pool[{"build_blocks": "n129", "step_launch": "n127", "build_postings": "post700"}[whole]]
+    e = engine.Engine(0)
+    try:
+        _slice_build(sl, 2)(e, 1)
+        if abandoned != "build":
+            e.slice_labels(scratch.ptr.value)
+        if abandoned == "set_bounds":
+            e.slice_bounds(scratch.ptr.value)
+            e.slice_set_bounds(scratch.ptr.value)
+        if whole == "step_launch":
+            t0, t1, bound, launched, prev = e.step_launch(inp.d_keys.ptr.value, inp.offsets, 0, 1, edges_buf.ptr.value, CAP)
+            assert launched and (t0, t1) == (0, e.num_tiles) and prev is None
+        else:
+            inp.build(e)
+        _no_slice_at_labels(e, scratch)
+        _no_finished_slice(e, scratch)
+        st = e.stats()
+        assert st["n_sources"] == inp.n_sources and st["n_entries"] == inp.n_entries and st["weighted"] == 0, st
+        if whole == "step_launch":      # the refused calls left the launched join alone
+            cnt = e.join_wait()
+            assert cnt == len(inp.ref) and _same(_got(edges_buf, cnt), inp.ref)
+        assert _same(_full_join(e, inp, edges_buf), inp.ref)
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("kind", REFUSED_BUILDS)
+@pytest.mark.parametrize("name", ["weighted_low20", "post700"])
+def test_refused_build_inside_a_slice_protocol_changes_nothing(pool, scratch, name, kind):
+    """A refused build behind every slice build (so between build_slice and slice_labels, and between build_slice and
+    slice_finish) and behind every slice_finish and export (between slice_finish and assemble): the protocol goes on."""
+    inp = pool[name]
+    dk = pool["n700"].d_keys.ptr.value
+    e = engine.Engine(0)
+    seen = []
+
+    def hook(where, p):
+        seen.append(where)
+        _refused_build(e, kind, dk)
+
+    pr = _protocol(e, inp, 3, hook=hook)
+    try:
+        assert not pr.first_pass() and not pr.second_pass()
+        pr.stack()
+        _refused_build(e, kind, dk)
+        pr.assemble()
+        assert _same(pr.join(), inp.ref)
+        assert seen == ["built"] * 3 + ["rebuilt", "finished", "exported"] * 3
+    finally:
+        pr.free()
+        e.close()
+
+
+@pytest.mark.parametrize("first", ["n700", "twin700"])
+@pytest.mark.parametrize("stage", ["finish", "assemble"])
+def test_whole_build_after_a_finished_slice_and_after_an_assemble(pool, edges_buf, scratch, stage, first):
+    """n700 and twin700 have the same offsets and other keys: after the slices of one, the whole build of the other gives
+    its own edges (the engine keeps the offsets, not the slices' lists), and nothing of the slice protocol is accepted."""
+    a = pool[first]
+    b = pool["twin700" if first == "n700" else "n700"]
+    e = engine.Engine(0)
+    try:
+        assert _sliced(e, a, 2, stop=stage) is None
+        b.build(e)
+        _no_slice_at_labels(e, scratch)
+        _no_finished_slice(e, scratch)
+        assert _same(_full_join(e, b, edges_buf), b.ref)
+        assert _same(_sliced(e, a, 3), a.ref)      # ... and the slices again behind the whole build
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("name", ["n129", "post700w"])
+def test_not_joinable_until_assembled(pool, edges_buf, scratch, name):
+    """A slice build on a joinable engine: nothing joins until the assemble, and the join launched on the whole build
+    before it (the same stream) is collected behind it with the whole build's count and edges."""
+    big, inp = pool["n3000"], pool[name]
+    e = engine.Engine(0)
+    pend = engine.DeviceBuffer(CAP * 16)
+    where = []
+
+    def hook(at, p):
+        if at in ("built", "finished"):
+            _not_joinable(e, edges_buf)
+        if not where:      # (after the first slice build)
+            cnt = e.join_wait()
+            assert cnt == len(big.ref) and _same(_got(pend, cnt), big.ref)
+            assert e.stats()["last_edges"] == len(big.ref)
+        where.append(at)
+
+    pr = _protocol(e, inp, 2, hook=hook)
+    try:
+        big.build(e)
+        e.join_launch(0, e.num_tiles, pend.ptr.value, CAP)
+        assert not pr.first_pass() and not pr.second_pass()
+        pr.stack()
+        _not_joinable(e, edges_buf)
+        pr.assemble()
+        assert _same(pr.join(), inp.ref)
+        assert e.balanced_cuts(2)[-1] == e.num_tiles
+    finally:
+        pr.free()
+        pend.free()
+        e.close()
+
+
+@pytest.mark.parametrize("name", ["n127", "weighted_low20", "post700"])
+def test_slice_calls_out_of_order(pool, edges_buf, scratch, name):
+    """slice_finish twice; slice_sizes / slice_export of a slice that is built and not finished; assemble twice."""
+    inp = pool[name]
+    e = engine.Engine(0)
+
+    def hook(at, p):
+        if at in ("built", "rebuilt"):      # the slice before this one was finished: its sizes went with the build
+            _refusal(e.slice_sizes, "build_slice has not been run")
+            q = scratch.ptr.value
+            _refusal(lambda: e.slice_export(q, q, q, q, q, q), "build_slice has not been run")
+        if at == "finished":
+            _refusal(lambda: e.slice_finish(pr.lab.ptr.value), "build_slice has not been run")
+
+    pr = _protocol(e, inp, 3, hook=hook)
+    try:
+        assert not pr.first_pass() and not pr.second_pass()
+        pr.stack()
+        pr.assemble()
+        first = e.stats()["n_block_keys"]
+        assert _same(_full_join(e, inp, edges_buf), inp.ref)
+        pr.assemble()
+        assert e.stats()["n_block_keys"] == first
+        assert _same(_full_join(e, inp, edges_buf), inp.ref)
+    finally:
+        pr.free()
+        e.close()
+
+
+# ---- F: slices inside the seeded sequences ---------------------------------------------------------------------------
+
+SLICE_POOL = ["n129", "n127", "one", "empty", "n700", "n3000", "weighted_low20", "post700", "post700w"]
+
+
+class SliceRunner(Runner):
+    """Runner's operations and two more: a pool input built in slices on this engine, and a slice protocol left at a
+    random point.  Slices run under the modes of test_random_sketches_in_slices_all_modes; weights and postings under
+    the weighted ones."""
+
+    def op(self, i):
+        r = self.rng.random()
+        if r < 0.16:
+            self.sliced(i, None)
+        elif r < 0.26:
+            self.sliced(i, STOPS[int(self.rng.integers(len(STOPS) - 1))])      # (any stop before the assemble)
+        else:
+            super().op(i)
+
+    def pick_sliced(self):
+        rng = self.rng
+        if self.mode not in SLICE_MODES:
+            self.mode = SLICE_MODES[int(rng.integers(len(SLICE_MODES)))]
+            self.log.append(f"mode {self.mode} (for slices)")
+            for k in ENV_KNOBS:
+                self.mp.delenv(k, raising=False)
+            for k, v in self.mode.items():
+                self.mp.setenv(k, v)
+        names = SLICE_POOL
+        if self.mode not in WEIGHTED_MODES:
+            names = [n for n in names if not self.pool[n].weighted and self.pool[n].kind == "sk"]
+        inp = self.pool[names[int(rng.integers(len(names)))]]
+        sum_bounds = inp.kind == "post" and bool(rng.integers(2))
+        return inp, int(rng.integers(1, 4)), sum_bounds
+
+    def sliced(self, i, stop):
+        inp, nparts, sum_bounds = self.pick_sliced()
+        behind = self.pending is not None and bool(self.rng.integers(2))
+        if self.pending is not None and not behind:
+            self.log.append("join_wait")
+            self.collect_pending()
+        self.log.append(f"slices of {inp.name}: {nparts}, summed bounds {sum_bounds}, " + (f"left at {stop}" if stop else "assembled"))
+        _sliced(self.e, inp, nparts, sum_bounds=sum_bounds, stop=stop or "assemble")
+        if behind:      # the join launched before the slices ran in front of them on the stream
+            self.log.append("join_wait")
+            self.collect_pending()
+        if stop:
+            self.cur = None
+            return
+        self.cur = inp
+        st = self.e.stats()
+        self.check(st["n_sources"] == inp.n_sources and st["weighted"] == int(inp.weighted), f"stats {st}")
+        if inp.kind == "sk":      # (a slice of postings reports its own entries)
+            self.check(st["n_entries"] == inp.n_entries, f"stats {st}")
+        self.expect_edges(_full_join(self.e, inp, self.buf), inp, "join of the assembled slices")
+
+
+@pytest.mark.parametrize("seed", range(10))
+def test_call_sequences_with_slices_on_one_engine(pool, edges_buf, monkeypatch, seed):
+    r = SliceRunner(seed, pool, edges_buf, monkeypatch)
+    for i in range(30):
+        r.op(i)
+    r.close()
+
+
+# ---- G: seeded walks over the state table (tests/engine_states.py, DESIGN.md 7g-2) -----------------------------------
+
+@functools.lru_cache(maxsize=None)
+def _walk_inputs():
+    import oracle
+    pool = _pool_cached()
+    out = {n: pool[n] for n in ES.SKETCH_INPUTS}
+    s = pool["n129"]
+    _, ko, hs = _postings(s.keys, s.offsets)
+    kw = np.random.default_rng(129).integers(1, 1001, size=ko.size - 1, dtype=np.uint32)
+    out["post129"] = Input("post129", oracle, postings=(ko, hs, None), n_sources=s.n_sources)
+    out["post129w"] = Input("post129w", oracle, postings=(ko, hs, kw), n_sources=s.n_sources)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _slices_of(name, nparts):
+    """The slices of a walk input as another rank would hand them over: made once on an engine of their own and kept on
+    the device (combined labels, the bounds to set, the stacked exports)."""
+    inp = _walk_inputs()[name]
+    e = engine.Engine(0)
+    pr = _protocol(e, inp, nparts)
+    assert not pr.first_pass() and not pr.second_pass()
+    pr.stack()
+    if pr.bnd is None:      # sketches: a slice reports every source's whole bound
+        pr.build(e, 0)
+        pr.bnd = engine.DeviceBuffer(max(4, inp.n_sources * 4))
+        e.slice_bounds(pr.bnd.ptr.value)
+    e.close()
+    pr.e = None
+    pr.inp = inp
+    return pr
+
+
+class Walker:
+    """One walk of engine_states.walk on one engine: a refused cell raises its code and message and leaves the stats
+    alone; an accepted one is made with valid arguments; joins are compared with the oracle."""
+
+    def __init__(self, seed, buf, scratch):
+        self.seed, self.buf, self.scratch = seed, buf, scratch
+        self.inputs = _walk_inputs()
+        self.e = engine.Engine(0)
+        self.buf2 = engine.DeviceBuffer(CAP * 16)
+        self.pend_buf = None
+        self.ctx = self.part = None
+        self.bounds_set = False
+        self.log = []
+
+    def check(self, cond, msg):
+        lines = "\n".join(f"  {i:3d}: {s}" for i, s in enumerate(self.log))
+        assert cond, f"seed {self.seed}, step {len(self.log) - 1}: {msg}\nsteps:\n{lines}"
+
+    def edges(self, got, name, what):
+        ref = self.inputs[name].ref
+        self.check(_same(got, ref), f"{what} of {name}: {len(got)} edges, oracle {len(ref)}")
+
+    def args(self, call):
+        """A refused call: arguments that pass the NULL checks, so the refusal is the state's."""
+        e, q, T = self.e, self.scratch.ptr.value, self.e.num_tiles
+        small = self.inputs["n127"]
+        host = np.zeros(4, dtype=engine.EDGE_DTYPE)
+        return {"slice_labels": lambda: e.slice_labels(q), "slice_bounds": lambda: e.slice_bounds(q),
+                "slice_set_bounds": lambda: e.slice_set_bounds(q), "slice_finish": lambda: e.slice_finish(q),
+                "slice_sizes": e.slice_sizes, "slice_export": lambda: e.slice_export(q, q, q, q, q, q),
+                "assemble": lambda: e.assemble(np.zeros(4, dtype=np.uint64), q, q, q, 1, q, q, q, 1),
+                "join": lambda: e.join(0, T, self.buf.ptr.value, CAP),
+                "join_launch": lambda: e.join_launch(0, T, self.buf.ptr.value, CAP),
+                "join_to_host": lambda: e.join_to_host(0, T, host.ctypes.data, host.size),
+                "balanced_cuts": lambda: e.balanced_cuts(2)}[call]
+
+    def step(self, s):
+        e, call, cell = self.e, s.call, s.cell
+        self.log.append(f"{s.state:9s} {'pending ' + s.pending if s.pending else '':16s} {call} "
+                        f"{(s.inp, s.nparts, s.part) if s.inp else ''} -> {cell.kind}")
+        if cell.kind == "refused":
+            in_flight = getattr(e, "_join_in_flight", False)
+            before = e.stats()
+            with pytest.raises(engine.KspError) as ei:
+                self.args(call)()
+            e._join_in_flight = in_flight      # (the wrapper's own note of a launched join: the engine kept it)
+            self.check(ei.value.code == getattr(engine, cell.code) and cell.stem in str(ei.value), f"refusal {ei.value}")
+            after = e.stats()
+            same = ("n_sources", "n_entries", "n_blocks", "weighted", "n_block_keys", "last_edges")
+            self.check(all(before[k] == after[k] for k in same), f"a refused call changed the stats: {before} -> {after}")
+            return
+        inp = self.inputs[s.inp] if s.inp else None
+        cur = self.inputs[s.cur] if s.cur else None
+        T = e.num_tiles
+        if call in ("build_blocks", "build_postings"):
+            inp.build(e)
+        elif call == "step_launch":
+            buf = self.buf if self.pend_buf is self.buf2 else self.buf2
+            t0, t1, bound, launched, prev = e.step_launch(inp.d_keys.ptr.value, inp.offsets, 0, 1, buf.ptr.value, CAP,
+                                                          d_weights_ptr=inp.d_weights)
+            self.check(launched and (t0, t1) == (0, e.num_tiles), f"step {t0, t1, bound, launched}")
+            if s.pending:
+                self.edges(_got(self.pend_buf, prev), s.pending, "step_launch's collected join")
+            self.pend_buf = buf
+        elif call in ES.SLICE_BUILDS:
+            self.ctx, self.part, self.bounds_set = _slices_of(s.inp, s.nparts), s.part, False
+            self.ctx.build(e, s.part)
+        elif call == "slice_labels":
+            e.slice_labels(self.scratch.ptr.value)
+        elif call == "slice_bounds":
+            e.slice_bounds(self.scratch.ptr.value)
+        elif call == "slice_set_bounds":
+            e.slice_set_bounds(self.ctx.bnd.ptr.value)
+            self.bounds_set = True
+        elif call == "slice_finish":
+            if self.ctx.sum_bounds and not self.bounds_set:      # (every slice of an index under the same, summed bounds)
+                e.slice_set_bounds(self.ctx.bnd.ptr.value)
+            e.slice_finish(self.ctx.lab.ptr.value)
+        elif call == "slice_sizes":
+            sz = e.slice_sizes()
+            want = self.ctx.sizes[4 * self.part:4 * self.part + 4]
+            self.check((sz == want).all(), f"slice_sizes {sz.tolist()}, the same slice on another engine {want.tolist()}")
+        elif call == "slice_export":
+            sz = e.slice_sizes()
+            L, nbig, nb = int(sz[0]), int(sz[2]), e.stats()["n_blocks"]
+            bufs = [engine.DeviceBuffer(max(4, L * 4)) for _ in range(3)] + [engine.DeviceBuffer((nb + 1) * 4) for _ in range(2)]
+            bufs.append(engine.DeviceBuffer(max(16, nbig * 16)))
+            e.slice_export(*[b.ptr.value for b in bufs])
+            raw = bufs[3].to_numpy(np.uint32, nb + 1)
+            want = self.ctx.parts[self.part]["raw"].view(np.uint32)
+            for b in bufs:
+                b.free()
+            if self.ctx.inp.n_entries:      # (nothing built: nothing is exported)
+                self.check((raw == want).all(), "slice_export: other keys per block than the same slice on another engine")
+        elif call == "assemble":
+            self.ctx.assemble(e)
+            st = e.stats()
+            self.check(st["n_sources"] == self.ctx.inp.n_sources and st["weighted"] == int(self.ctx.inp.weighted), f"stats {st}")
+        elif call == "join":
+            self.edges(_full_join(e, cur, self.buf), s.cur, "join")
+        elif call == "join_launch":
+            e.join_launch(0, T, self.buf2.ptr.value, CAP)
+            self.pend_buf = self.buf2
+        elif call == "join_to_host":
+            host = np.zeros(max(1, len(cur.ref)), dtype=engine.EDGE_DTYPE)
+            cnt = e.join_to_host(0, T, host.ctypes.data, len(cur.ref))
+            self.edges(_canon(host[:cnt]), s.cur, "join_to_host")
+        elif call == "join_wait":
+            cnt = e.join_wait()
+            if s.pending:
+                self.edges(_got(self.pend_buf, cnt), s.pending, "join_wait")
+            else:
+                self.check(cnt == 0, f"join_wait with nothing launched: {cnt}")
+            self.pend_buf = None
+        elif call == "balanced_cuts":
+            cuts = e.balanced_cuts(3)
+            self.check(cuts[0] == 0 and cuts[-1] == T and cuts == sorted(cuts), f"balanced_cuts {cuts}")
+        elif call == "edge_bound":
+            v = e.edge_bound(0, T)
+            self.check(v == 0 if cell.zero else v >= len(cur.ref), f"edge_bound {v}")
+        elif call == "lists_path":
+            v = e.lists_path()
+            self.check(v == 0 or not cell.zero, f"lists_path {v}")
+        elif call == "stats":
+            st = e.stats()
+            if s.state == "whole":
+                self.check(st["n_sources"] == cur.n_sources and st["n_entries"] == cur.n_entries, f"stats {st}")
+        if call in ES.WHOLE_BUILDS:
+            st = e.stats()
+            self.check(st["n_sources"] == inp.n_sources and st["n_entries"] == inp.n_entries and
+                       st["weighted"] == int(inp.weighted), f"stats {st}")
+
+    def close(self):
+        self.e.close()
+        self.buf2.free()
+
+
+def test_the_walk_inputs_are_what_the_model_says(pool):
+    for name, inp in _walk_inputs().items():
+        assert ES.SHARES[name] == (len(inp.ref) > 0), name
+        assert (inp.kind == "post") == (name in ES.POSTINGS_INPUTS), name
+
+
+@pytest.mark.parametrize("seed", ES.WALK_SEEDS)
+def test_walk_over_the_state_table(pool, edges_buf, scratch, seed):
+    w = Walker(seed, edges_buf, scratch)
+    try:
+        for s in ES.walk(seed):
+            w.step(s)
+    finally:
+        w.close()
